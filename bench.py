@@ -1,6 +1,6 @@
 """Benchmark of the north-star path on MI355X (contract: see the task brief / DESIGN.md §Measurement).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
 
 N > 1 needs no external launcher: this process then only starts N fresh rank processes (lightgrad_amd/launch.py,
 one per GPU; it never initialises a GPU itself), passes rank 0's JSON line through and exits non-zero if any rank
@@ -12,10 +12,15 @@ forward, backward, gradient all-reduce over RCCL (N > 1, overlapped with the tai
 Inputs are synthetic and resident in HBM before the timed region.  `value` is the whole-job aggregate steps/s
 (N ranks x K steps / max-over-ranks wall time): weak scaling.
 
-The same JSON line also carries BASELINE's second headline, the 4096^2 fp32 matmul forward+backward (`secondary`,
+A plain run sets up, warms up, times the K steps and prints the JSON line (`ms_per_step` = milliseconds of one timed step).
+With `--full` the same line also carries BASELINE's second headline, the 4096^2 fp32 matmul forward+backward (`secondary`,
 replicas on every rank), the roofline of the dominant kernel (the MFMA SGEMM; HIP events on the library's stream),
-the eager-tape rate next to the graph-replay rate, and the CPU baseline (this repo's CpuTensor backend running the
-same training loop on this host's cores; rank 0, N = 1 only).
+the eager-tape rate next to the graph-replay rate, the step with the batch as data, the cost of the exchange (N > 1),
+tiny-BERT and the CPU baseline (this repo's CpuTensor backend running the same training loop on this host's cores;
+rank 0, N = 1 only).
+
+`--dump-outputs DIR` writes what the last timed step computed on rank 0 - the loss and the updated parameters - as
+DIR/<name>.npy (float32).  The inputs are seeded, so two builds can be compared output for output.
 
 `--dry-run` replaces the GPU work by a few CPU steps (CpuTensor + gloo): it exists to test the launcher, the rank
 environment and the exchange protocol on machines without GPUs and prints a line marked "dry_run".
@@ -43,10 +48,15 @@ def parse():
     # measurement (16.4 k vs 16.7 k steps/s; 20 000 steps give what 2000 give)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: long window, eager tape, dispatch counts, batch as data, exchange "
+                         "cost (N > 1), matmul / roofline / HBM / BERT / CPU legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss and the parameters after the last timed step (rank 0) as DIR/<name>.npy")
     ap.add_argument("--matmul-iters", type=int, default=20)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-bert", action="store_true", help="skip the tiny-BERT forward+backward timing")
-    ap.add_argument("--no-extras", action="store_true", help="MLP step only: skip matmul / roofline / HBM / BERT / CPU legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the matmul / roofline / HBM / BERT / CPU legs")
     ap.add_argument("--no-fused-optimizer", action="store_true", help="run the optimizer as ~14 tape ops per parameter")
     ap.add_argument("--update-in-backward", action="store_true",
                     help="also on the legs of a multi-GPU run that train without the exchange (the default at N = 1, see --no-update-in-backward)")
@@ -465,6 +475,16 @@ def gpu_rank(args, rank, world):
             assert abs(dmax + dmin) <= 1e-6 * abs(dmax), "replicas diverged: %r" % ((dmax, -dmin),)
         if quick:
             return dict(steps_per_s=steps_per_s)
+        # what the last timed step computed (--dump-outputs), read before any later step moves the parameters
+        outputs = None
+        if args.dump_outputs and rank == 0:
+            outputs = {"loss": np.asarray(final_loss, np.float32)}
+            outputs.update((n, np.asarray(p.numpy(), np.float32)) for n, p in model.named_parameters())
+        R = dict(steps_per_s=steps_per_s, elapsed=elapsed, per_rank=per_rank, final_loss=final_loss, first_losses=first_losses,
+                 in_backward=in_backward, comm_in_graph=comm_in_graph, unroll=unroll, use_graph=use_graph, overlap=dp.overlap, w0=w0, x_np=x_np,
+                 onehot_np=onehot_np, outputs=outputs)
+        if not args.full:
+            return R
         # `value` covers exactly --steps steps; with few steps the two fences and the first launch weigh on it (20 steps = 1.2 ms:
         # -6 %), so the same loop is also timed over >= 0.1 s and reported NEXT to it (`value_long_window`), never as `value`
         long_window = None
@@ -530,9 +550,9 @@ def gpu_rank(args, rank, world):
             fence()
             data_input_steps_per_s = max(1, args.steps // per_graph) * per_graph / (time.perf_counter() - t0)
             opt.on_graph_replay((-(-args.warmup // per_graph) + max(1, args.steps // per_graph)) * per_graph)
-        return dict(steps_per_s=steps_per_s, elapsed=elapsed, per_rank=per_rank, final_loss=final_loss, first_losses=first_losses, in_backward=in_backward,
-                    eager_steps_per_s=eager_steps_per_s, dispatched_ops=dispatched_ops, launches_per_step=launches_per_step, long_window=long_window, data_input_steps_per_s=data_input_steps_per_s, comm_in_graph=comm_in_graph,
-                    unroll=unroll, use_graph=use_graph, overlap=dp.overlap, w0=w0, x_np=x_np, onehot_np=onehot_np)
+        R.update(eager_steps_per_s=eager_steps_per_s, dispatched_ops=dispatched_ops, launches_per_step=launches_per_step, long_window=long_window,
+                 data_input_steps_per_s=data_input_steps_per_s)
+        return R
 
     def communicator_fallback():
         """None when the bookkeeping runs on the first choice (RCCL between GPUs; peer windows for ranks sharing one GPU)"""
@@ -581,21 +601,24 @@ def gpu_rank(args, rank, world):
             "final_loss": round(R["final_loss"], 6),
             "first_losses": [round(v, 7) for v in R["first_losses"]],
             "ranks": ranks_info,
-            "value_long_window": R["long_window"],
             "mlp_gemm_tflops": round(R["steps_per_s"] * MLP_GEMM_FLOP / 1e12, 3),
-            "mlp_steps_per_sec_eager": round(R["eager_steps_per_s"], 2),
-            # the launch-bound step, per dispatched op - tape dispatches (outermost Function forward / backward calls +
-            # the optimizer) of one eager step, the kernel launches they turn into, and the host time per dispatch of the eager tape
-            "dispatch": {"tape_dispatches_per_step": R["dispatched_ops"], "launches_per_step": R["launches_per_step"],
-                         "us_per_dispatched_op_eager": round(1e6 / R["eager_steps_per_s"] * world / max(1, R["dispatched_ops"]), 2),
-                         "us_per_launch_replayed": round(1e6 / R["steps_per_s"] * world / max(1, R["launches_per_step"]), 2) if R["launches_per_step"] else None},
-            "mlp_steps_per_sec_batch_as_data": None if R["data_input_steps_per_s"] is None else round(R["data_input_steps_per_s"], 2),
         }
+        if args.full:
+            out.update({
+                "value_long_window": R["long_window"],
+                "mlp_steps_per_sec_eager": round(R["eager_steps_per_s"], 2),
+                # the launch-bound step, per dispatched op - tape dispatches (outermost Function forward / backward calls +
+                # the optimizer) of one eager step, the kernel launches they turn into, and the host time per dispatch of the eager tape
+                "dispatch": {"tape_dispatches_per_step": R["dispatched_ops"], "launches_per_step": R["launches_per_step"],
+                             "us_per_dispatched_op_eager": round(1e6 / R["eager_steps_per_s"] * world / max(1, R["dispatched_ops"]), 2),
+                             "us_per_launch_replayed": round(1e6 / R["steps_per_s"] * world / max(1, R["launches_per_step"]), 2) if R["launches_per_step"] else None},
+                "mlp_steps_per_sec_batch_as_data": None if R["data_input_steps_per_s"] is None else round(R["data_input_steps_per_s"], 2),
+            })
         out.update(extra)
         return out
 
     def side_measurements(R):
-        if args.no_extras:
+        if args.no_extras or not args.full:
             return {}
         return extras(R["first_losses"], args, rank, world, multi, comm, lib, L, light, HipTensor, CpuTensor, HipDevice, HipGraph, DataParallel,
                       SingleProcess, wall_max, fence, under_profiler, R["w0"], R["x_np"], R["onehot_np"])
@@ -695,7 +718,7 @@ def gpu_rank(args, rank, world):
                     sys.stderr.write("[bench] rank %d: the full run with exchange form %r failed (%s)\n" % (rank, mode, fallback_reason))
                     peer_lost = peer_lost or (uses_peer and peer is not None and peer.failed())
         cost = None
-        if not (peer_lost and (chosen == "p2p" or comm is peer)):
+        if args.full and not (peer_lost and (chosen == "p2p" or comm is peer)):
             state["line"] = json.dumps(assemble(best, chosen, calibration, fallback_reason, extra))
             cost = exchange_cost_of(chosen, guarded)
         out = assemble(best, chosen, calibration, fallback_reason, extra, cost)
@@ -713,8 +736,13 @@ def gpu_rank(args, rank, world):
                 fallback_reason = "%s: %s: %s" % (mode, type(e).__name__, e)
                 sys.stderr.write("[bench] rank %d: the leg with exchange form %r failed (%s); repeating with %r\n"
                                  % (rank, mode, fallback_reason, modes[k + 1]))
-        cost = exchange_cost_of(chosen) if world > 1 else None
+        cost = exchange_cost_of(chosen) if world > 1 and args.full else None
         out = assemble(R, chosen, calibration, fallback_reason, side_measurements(R), cost)
+        best = R
+    if rank == 0 and args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in best["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     if rank == 0:
         print(json.dumps(out))
         sys.stdout.flush()

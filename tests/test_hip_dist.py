@@ -211,8 +211,8 @@ BENCH = ["bench.py", "--gpus", "2", "--rehearse-on-one-gpu", "--steps", "40", "-
 
 
 def test_bench_two_ranks_end_to_end(spawn_ranks):
-    """`bench.py --gpus 2 --rehearse-on-one-gpu`: communicators, forms of the exchange, calibration, the JSON line"""
-    res = spawn_ranks(2, BENCH, timeout=420)
+    """`bench.py --gpus 2 --rehearse-on-one-gpu --full`: communicators, forms of the exchange, calibration, exchange cost, the JSON line"""
+    res = spawn_ranks(2, BENCH + ["--full"], timeout=420)
     assert res["rc"] == 0, "\n---- next rank ----\n".join(res["outputs"])
     out = _bench_line(res["outputs"][0])
     assert out["n_gpus"] == 2 and out["steps"] == 40 and out["metric"].startswith("REHEARSAL_")

@@ -10,8 +10,8 @@ step() {   # step <name> <seconds> <command...>   (stdout -> $out/<name>.out unl
   echo "[$name] rc=$rc"
   if [ $rc -eq 124 ] || [ $rc -eq 137 ] || [ $rc -eq 3 ]; then echo "step $name was killed at its limit or reported a hung exchange (rc $rc): stopping"; exit $rc; fi
 }
-step bench 400 "python bench.py > $out/bench.json 2> $out/bench.err"
-step stats 400 "rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --steps 200 --warmup 10 --no-cpu-baseline > $out/bench_under_rocprof.json 2> $out/bench_under_rocprof.err"
+step bench 400 "python bench.py --full > $out/bench.json 2> $out/bench.err"
+step stats 400 "rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --full --steps 200 --warmup 10 --no-cpu-baseline > $out/bench_under_rocprof.json 2> $out/bench_under_rocprof.err"
 step fetch 200 "rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/fetch -- python3 tools/profile_kernels.py > $out/fetch.log 2>&1"
 step write 200 "rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/write -- python3 tools/profile_kernels.py > $out/write.log 2>&1"
 step trace1 200 "rocprofv3 --kernel-trace --output-format csv -d $out/trace1 -- python3 bench.py --steps 200 --warmup 10 --no-extras --graph-steps 1 > $out/bench_one_step_per_graph.json 2> $out/trace1.err"
@@ -30,7 +30,7 @@ step bertbench 200 "python tools/bert_bench.py > $out/bert_bench.txt 2>&1; echo 
 step attntl 100 "python tools/attn_timeline.py > $out/attn_timeline.txt 2>&1"; cat $out/attn_timeline.txt
 step bertgemm 100 "python tools/bert_gemm_bench.py > $out/bert_gemm_bench.txt 2>&1"; cat $out/bert_gemm_bench.txt
 step cebench 100 "python tools/ce_bench.py > $out/ce_bench.txt 2>&1; LG_CE_HELD=0 python tools/ce_bench.py >> $out/ce_bench.txt 2>&1"; cat $out/ce_bench.txt
-step rehearse 400 "python bench.py --gpus 2 --rehearse-on-one-gpu --steps 80 --warmup 10 --no-cpu-baseline > $out/bench_rehearsal_two_ranks_one_gpu.json 2> $out/bench_rehearsal.err"; tail -c 300 $out/bench_rehearsal_two_ranks_one_gpu.json
+step rehearse 400 "python bench.py --gpus 2 --rehearse-on-one-gpu --full --steps 80 --warmup 10 --no-cpu-baseline > $out/bench_rehearsal_two_ranks_one_gpu.json 2> $out/bench_rehearsal.err"; tail -c 300 $out/bench_rehearsal_two_ranks_one_gpu.json
 step rehearsefb 400 "LG_BENCH_FAIL_RCCL=init:1 python bench.py --gpus 2 --rehearse-on-one-gpu --steps 80 --warmup 10 --no-extras --comm-open-timeout 5 > $out/bench_rehearsal_rccl_fallback.json 2> $out/bench_rehearsal_rccl_fallback.err"; tail -c 300 $out/bench_rehearsal_rccl_fallback.json
 step torchrun 400 "python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --rehearse-on-one-gpu --steps 80 --warmup 10 --no-extras > $out/bench_rehearsal_under_torchrun.json 2> $out/bench_rehearsal_under_torchrun.err"; tail -c 300 $out/bench_rehearsal_under_torchrun.json
 step ab 100 "python tools/mlp_step_ab.py 3 > $out/mlp_step_ab.txt 2>&1"; cat $out/mlp_step_ab.txt
