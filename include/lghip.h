@@ -339,8 +339,13 @@ int lg_adam_multi_dev_f32(float* p, const float* g, float* m, float* v, int nseg
  *                           optimizer, written as step_out[0] = step_in[0] + 1 (step_out NULL elsewhere; step_out !=
  *                           step_in: an optimizer keeps two plans per parameter, A -> B and B -> A, and alternates).
  *   lg_adam_epilogue_arm    before backward: the next kernel that OVERWRITES `grad` (n floats, dense; beta = 0) applies the
- *                           plan; the gradient itself is still written.  A kernel that ADDS into `grad` after that is
- *                           refused (LG_EINVAL): for gradients made by ONE kernel per step.
+ *                           plan; the gradient itself is still written.  After that, ANY entry point of this library that
+ *                           would write into those bytes in the same step - GEMMs, lg_ew, lg_reduce_acc, lg_copy_strided,
+ *                           lg_fill_strided, lg_put_axis, lg_scatter_add_axis_f32, lg_scatter_add_rows_f32,
+ *                           lg_layernorm_param_grads_f32, lg_gemm_group_colsum_f32, lg_head_bwd_f32; queued calls when they
+ *                           are queued - is refused (LG_EINVAL) and writes nothing: for gradients made by ONE kernel per
+ *                           step.  Writes before the overwrite, or into gradients no kernel took, are fine.  Host
+ *                           bookkeeping only (range compares against the applied plans; none at all while nothing is applied).
  *   lg_adam_epilogue_finish after backward: applies the armed plans no kernel took, in one launch (none when all were
  *                           taken), and disarms everything.  Host bookkeeping only: a step recorded in a hipGraph replays
  *                           as recorded; the directions alternate, so a graph holds an EVEN number of steps. */

@@ -24,11 +24,13 @@ class HipGraph(object):
 
     capturing = False         # True inside a `capture()` block (kernels are being recorded, not executed)
     # callables run when a capture ends successfully (before the graph is instantiated): state that alternates per step on the
-    # host - tensor.BackwardUpdate's two parameter buckets - checks that the recorded steps bring it back to where it started
+    # host - tensor.BackwardUpdate's two parameter buckets - checks that the recorded steps bring it back to where it started.
+    # A hook may return a callable that replay() runs first (it raises when the host state no longer matches the recording).
     capture_end_hooks = []
 
     def __init__(self):
         self._exec = None
+        self._replay_checks = ()
 
     @contextmanager
     def capture(self):
@@ -49,14 +51,16 @@ class HipGraph(object):
         _l.check(L.lg_graph_end(ctypes.byref(handle)))
         self._exec = handle
         try:
-            for hook in list(HipGraph.capture_end_hooks):
-                hook()
+            checks = [hook() for hook in list(HipGraph.capture_end_hooks)]
+            self._replay_checks = tuple(c for c in checks if c is not None)
         except BaseException:
             self.destroy()
             raise
 
     def replay(self):
         assert self._exec is not None, "nothing captured"
+        for check in self._replay_checks:
+            check()
         _l.check(_l._lib.lg_graph_launch(self._exec))
 
     def kernel_count(self) -> int:

@@ -216,10 +216,14 @@ class BackwardUpdate(object):
 
     The new parameter values cannot overwrite the old ones - `dx = g @ W` runs in the same launch as `dW = g^T @ x` - so the
     parameters live in TWO flat buckets and every step reads one and writes the other; the parameter tensors are re-pointed
-    after each step (views handed out earlier keep the old values: take them per step, as the tape does).  The step number
-    behind the bias corrections alternates between two device words the same way.  A hipGraph must therefore record an EVEN
-    number of steps.  Gradients any other kernel produces (or that are added to, not overwritten) are applied by
-    `finish()` in one extra launch - the result is the same either way, bit for bit: the same per-element arithmetic."""
+    after each step (views handed out earlier keep the old values: take them per step, as the tape does; lazy tensors that
+    still read the parameters are computed before the re-pointing).  The step number behind the bias corrections alternates
+    between two device words the same way.  A hipGraph must therefore record an EVEN number of steps, and it is replayed only
+    at the parity it was captured at (HipGraph.replay raises otherwise).  Gradients any other kernel produces (or that are
+    added to, not overwritten) are applied by `finish()` in one extra launch - the result is the same either way, bit for bit:
+    the same per-element arithmetic.  A gradient whose update a kernel applied is written by nothing else in that step: every
+    writer of the library refuses (HipError) to touch its bytes again - one weight used twice, a penalty on it, a tied table
+    (see optim.Adam.fuse_update_into_backward)."""
 
     def __init__(self, flat_p, parameters, grad, m, v, offsets, lr, b1, b2, eps, grad_scale, belief, steps_done):
         lib = _l.lib()
@@ -247,11 +251,22 @@ class BackwardUpdate(object):
         from .graph import HipGraph
         me = weakref.ref(self)
 
+        def parity_still(at_capture):
+            # the recorded kernels read the bucket of `at_capture` and write the other one: replayed at the other parity they
+            # would train on the bucket one step behind
+            def check():
+                this = me()
+                if this is not None and this.parity != at_capture:
+                    raise RuntimeError("a hipGraph captured at parameter-bucket parity %d is replayed at parity %d (an odd number of "
+                                       "eager steps since the capture, optimizer update inside the backward kernels): take one more "
+                                       "eager step first" % (at_capture, this.parity))
+            return check
+
         def capture_ended():
             this = me()
             if this is None:
                 HipGraph.capture_end_hooks.remove(capture_ended)
-                return
+                return None
             recorded, this._captured_steps = this._captured_steps, 0
             if recorded % 2:
                 for _ in range(1):                    # undo the host-side flip the recorded (not executed) odd step left behind
@@ -260,6 +275,7 @@ class BackwardUpdate(object):
                         p._data = this.buckets[this.parity]._data
                 raise RuntimeError("a hipGraph recorded %d steps of an optimizer whose update rides in the backward kernels: its two "
                                    "parameter buckets alternate, record an EVEN number of steps per graph" % recorded)
+            return parity_still(this.parity) if recorded else None      # (HipGraph.replay calls it first)
         HipGraph.capture_end_hooks.append(capture_ended)
 
     def _first_nonempty(self) -> int:
@@ -287,6 +303,9 @@ class BackwardUpdate(object):
         if HipGraph.capturing:
             self._captured_steps += 1
         self.armed = False
+        # lazy tensors defined from the parameters (a Linear's output nobody has read yet) still want the values of this step:
+        # computed now, while the parameters point at them - not after the re-pointing below
+        _make_lazy_readers_real(self.buckets[self.parity])
         self.parity ^= 1
         now = self.buckets[self.parity]._data
         for p in self.parameters:

@@ -86,9 +86,8 @@ __device__ __forceinline__ AdamScalars adam_plan_scalars(const AdamPlan* pl, int
 // host side (optim.hip): the plan armed for the gradient buffer `grad` of `n` floats, if the launch being prepared may apply
 // it - i.e. it OVERWRITES the gradient (accumulate == 0: the first and only write of this step).  The plan then counts as
 // applied.  NULL: nothing armed, or not applicable (the optimizer's lg_adam_epilogue_finish applies what is left).
-// A launch that ADDS into a gradient whose plan was already applied in this step is an error: *rc = LG_EINVAL.
+// A launch that writes into the bytes of a gradient whose plan was already applied in this step is an error: *rc = LG_EINVAL
+// (adam_epilogue_check_write, common.h: the same check for every other writer).
 const AdamPlan* adam_epilogue_take(const void* grad, int64_t n, int accumulate, int* rc);
-// a launch that only adds into / reads gradients: fails when `grad` belongs to a plan already applied in this step
-int adam_epilogue_check_write(const void* grad);
 
 }  // namespace lg

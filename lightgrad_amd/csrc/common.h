@@ -124,4 +124,31 @@ inline unsigned stream_grid(int64_t work_items, int block = 256) {
     return static_cast<unsigned>(need < cap ? need : cap);
 }
 
+// ---- writes into gradients whose optimizer update a kernel has already applied (lg_adam_epilogue_*, optim.hip) ------------
+// Every entry point that writes device memory it does not own (elementwise, reductions, layout, index, LayerNorm / embedding
+// gradients, GEMMs) asks here first.  The update rode with the kernel that wrote the gradient first; a later write into the same
+// bytes would change the gradient without changing the update, so it is refused (LG_EINVAL).  Host bookkeeping only; while no
+// plan has been applied in this step (every step without fuse_update_into_backward) the check is one load and one compare.
+extern int adam_applied_plans;
+int adam_epilogue_overlap(uintptr_t lo, uintptr_t hi);          // [lo, hi) bytes; LG_EINVAL + message when it meets an applied plan
+
+inline int adam_epilogue_check_write(const void* ptr, int64_t bytes) {
+    if (adam_applied_plans == 0 || ptr == nullptr || bytes <= 0) return LG_OK;
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(ptr);
+    return adam_epilogue_overlap(lo, lo + uintptr_t(bytes));
+}
+
+// the bytes a strided view of `ndim` extents / strides (elements, any sign) at `ptr` spans
+inline int adam_epilogue_check_strided(const void* ptr, int itemsize, int ndim, const int64_t* shape, const int64_t* strides) {
+    if (adam_applied_plans == 0 || ptr == nullptr) return LG_OK;
+    int64_t lo = 0, hi = 0;
+    for (int k = 0; k < ndim; ++k) {
+        if (shape[k] <= 0) return LG_OK;                             // nothing is written
+        const int64_t reach = (shape[k] - 1) * strides[k];
+        if (reach < 0) lo += reach; else hi += reach;
+    }
+    const uintptr_t base = reinterpret_cast<uintptr_t>(ptr);
+    return adam_epilogue_overlap(base + uintptr_t(lo * itemsize), base + uintptr_t((hi + 1) * itemsize));
+}
+
 }  // namespace lg

@@ -631,6 +631,11 @@ extern "C" int lg_ew(int op, int ndim, const int64_t* shape,
     for (int o = 0; o < nout; ++o)
         for (int k = 0; k < desc.ndim; ++k)
             LG_ARG(desc.shape[k] == 1 || desc.stride[o][k] != 0, "lg_ew: output %d has a zero stride over an extent > 1", o);
+    {
+        int arc = adam_epilogue_check_strided(out0, 4, ndim, shape, out0_strides);
+        if (arc == LG_OK && nout == 2) arc = adam_epilogue_check_strided(out1, 4, ndim, shape, out1_strides);
+        if (arc != LG_OK) return arc;
+    }
 
     EwArgs args;
     for (int i = 0; i < 4; ++i) args.in[i] = i < nin ? static_cast<const float*>(ins[i]) : nullptr;

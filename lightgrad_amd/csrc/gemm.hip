@@ -483,6 +483,7 @@ struct PairState {
     // as sgemm_triple_wgrad2_xgrad, anything else as single launches in call order.
     GemmArgs args[3];
     bool     is_s[3] = {false, false, false};
+    int64_t  batch[3] = {1, 1, 1};
     int64_t  tiles = 0;        // tickets handed out so far
     LossJob  job{};            // lg_gemm_pair_mse_loss: finished by a spare workgroup of the three-product launch, else by a launch of its own
 };
@@ -574,11 +575,35 @@ static int pair_flush(bool keep_collecting) {
     return rc;
 }
 
+// the bytes [lo, hi) a prepared product writes into C (every matrix of its batch) and into its row sums
+struct WriteSpan { uintptr_t lo, hi; };
+static WriteSpan product_c_span(const GemmArgs& g, int64_t batch) {
+    const int64_t outer = batch / g.batch_inner;
+    int64_t lo = 0, hi = (g.M - 1) * g.ldc + g.N;
+    const int64_t reach[2] = {(outer - 1) * g.sC, int64_t(g.batch_inner - 1) * g.sC2};
+    for (int64_t r : reach) { if (r < 0) lo += r; else hi += r; }
+    const uintptr_t base = reinterpret_cast<uintptr_t>(g.C);
+    return WriteSpan{base + uintptr_t(lo * 4), base + uintptr_t(hi * 4)};
+}
+static bool spans_meet(WriteSpan a, WriteSpan b) { return a.lo < b.hi && b.lo < a.hi; }
+static bool products_write_alike(const GemmArgs& a, int64_t batch_a, const GemmArgs& b, int64_t batch_b) {
+    const WriteSpan none{0, 0};
+    const WriteSpan ca = product_c_span(a, batch_a), cb = product_c_span(b, batch_b);
+    const WriteSpan ra = a.rowsum ? WriteSpan{reinterpret_cast<uintptr_t>(a.rowsum), reinterpret_cast<uintptr_t>(a.rowsum + a.M)} : none;
+    const WriteSpan rb = b.rowsum ? WriteSpan{reinterpret_cast<uintptr_t>(b.rowsum), reinterpret_cast<uintptr_t>(b.rowsum + b.M)} : none;
+    return spans_meet(ca, cb) || spans_meet(ca, rb) || spans_meet(ra, cb) || spans_meet(ra, rb);
+}
+
 // true: `g` (fully prepared, workspace allocated) has been taken over and will be launched by lg_gemm_pair_end
 static bool pair_try_defer(GemmArgs& g, bool akc, bool bkc, bool va, bool vb, int64_t batch) {
     PairState& P = pair_state();
     if (P.active != 1) return false;
     const int slot = P.count;
+    // a product that writes where a collected one writes (one weight used twice: dW2 = g2^T @ h overwrites, dW1 adds into the
+    // same buffer) must not share its launch - the workgroups of one launch run in no order.  Not taken: the caller launches
+    // what is pending, then this one, in call order.
+    for (int i = 0; i < slot; ++i)
+        if (products_write_alike(P.args[i], P.batch[i], g, batch)) return false;
     // Batched products (attention: one matrix per (batch, head)) share launches like single ones.
     const bool f_form = !akc && !bkc, s_form = akc;
     bool fits = slot < 3 && va && vb && batch >= 1;
@@ -594,6 +619,7 @@ static bool pair_try_defer(GemmArgs& g, bool akc, bool bkc, bool va, bool vb, in
     if (s_form) P.second_bkc = bkc;
     P.is_s[slot] = s_form;
     P.args[slot] = g;
+    P.batch[slot] = batch;
     P.count = slot + 1;
     return true;
 }
@@ -891,7 +917,11 @@ static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K,
     }
     // the optimizer's update in this launch's epilogue: a single product that OVERWRITES an armed gradient (optim.hip)
     {
+        const int64_t cshape[4] = {batch / batch_inner, batch_inner, M, N}, cst[4] = {strideC, strideC2, ldc, 1};
         int arc = LG_OK;
+        for (int i = 0; i < (g.multi ? 3 : 1) && arc == LG_OK; ++i)      // (any write into a gradient whose update was applied: refused)
+            arc = adam_epilogue_check_strided(C + g.coff[i], 4, 4, cshape, cst);
+        if (arc != LG_OK) return arc;
         const bool plain = batch == 1 && ldc == N && bias == nullptr && addend == nullptr && act == 0 && !g.multi && !g.seg_k;
         g.adam_c = adam_epilogue_take(C, M * N, plain ? accumulate : 1, &arc);
         if (arc != LG_OK) return arc;
@@ -1221,6 +1251,7 @@ extern "C" int lg_gemm_kseg3_f32(int transA, int transB, int64_t M, int64_t N, i
 extern "C" int lg_gemm_group_colsum_f32(const float* in, int64_t ld, int64_t rows, int64_t cols, float* out, int accumulate) {
     LG_REQUIRE_INIT();
     LG_ARG(in && out && rows >= 0 && cols >= 1 && ld >= cols, "lg_gemm_group_colsum_f32: bad arguments");
+    { const int arc = adam_epilogue_check_write(out, cols * int64_t(sizeof(float))); if (arc != LG_OK) return arc; }
     GroupState& G = lg::group_state();
     const int64_t wgs = (cols + 63) / 64;
     if (G.active == 1 && G.grp.cs_wgs == 0 && rows > 0 && wgs <= 65536 && !lg::pair_state().active) {

@@ -140,6 +140,7 @@ extern "C" int lg_put_axis(int itemsize, void* dst, int64_t outer, int64_t axis_
     LG_INDEX_ARGS("lg_put_axis");
     LG_ARG(itemsize == 1 || itemsize == 2 || itemsize == 4 || itemsize == 8, "lg_put_axis: itemsize %d not in {1,2,4,8}", itemsize);
     LG_ARG(dst != nullptr, "lg_put_axis: NULL pointer");
+    { const int arc = adam_epilogue_check_write(dst, outer * axis_len * inner * itemsize); if (arc != LG_OK) return arc; }
     if (idx_itemsize == 2)      launch_put(itemsize, dst, static_cast<const int16_t*>(idx), val, scalar_bits, d);
     else if (idx_itemsize == 4) launch_put(itemsize, dst, static_cast<const int32_t*>(idx), val, scalar_bits, d);
     else                        launch_put(itemsize, dst, static_cast<const int64_t*>(idx), val, scalar_bits, d);
@@ -151,6 +152,7 @@ extern "C" int lg_scatter_add_axis_f32(float* dst, int64_t outer, int64_t axis_l
                                        const void* idx, int idx_itemsize, int64_t n_idx, int64_t pair_period, const float* src) {
     LG_INDEX_ARGS("lg_scatter_add_axis_f32");
     LG_ARG(dst && src, "lg_scatter_add_axis_f32: NULL pointer");
+    { const int arc = adam_epilogue_check_write(dst, outer * axis_len * inner * int64_t(sizeof(float))); if (arc != LG_OK) return arc; }
     const dim3 grid(stream_grid(d.total)), block(256);
     hipStream_t s = rt().stream;
     if (idx_itemsize == 2)      hipLaunchKernelGGL(scatter_add_axis<int16_t>, grid, block, 0, s, dst, static_cast<const int16_t*>(idx), src, d);

@@ -111,6 +111,7 @@ extern "C" int lg_copy_strided(int itemsize, int ndim, const int64_t* shape, voi
     if (d.numel == 0) return LG_OK;
     for (int k = 0; k < d.ndim; ++k)
         LG_ARG(d.shape[k] == 1 || d.stride[0][k] != 0, "lg_copy_strided: destination has a zero stride over an extent > 1");
+    { const int arc = adam_epilogue_check_strided(dst, itemsize, ndim, shape, dst_strides); if (arc != LG_OK) return arc; }
     // both sides one contiguous run: plain device copy
     if (d.ndim == 1 && (d.numel == 1 || (d.stride[0][0] == 1 && d.stride[1][0] == 1)))
         return lg_memcpy_d2d(dst, src, size_t(d.numel) * itemsize);
@@ -139,6 +140,7 @@ extern "C" int lg_fill_strided(int itemsize, int ndim, const int64_t* shape, voi
     IterDesc d;
     LG_ARG(build_iter(ndim, shape, strides, 1, d), "lg_fill_strided: bad shape");
     if (d.numel == 0) return LG_OK;
+    { const int arc = adam_epilogue_check_strided(dst, itemsize, ndim, shape, dst_strides); if (arc != LG_OK) return arc; }
     int rc;
     switch (itemsize) {
         case 1: rc = fill_typed<uint8_t>(dst, d, value_bits); break;

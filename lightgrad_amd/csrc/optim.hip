@@ -278,30 +278,40 @@ struct EpilogueState {
 };
 static EpilogueState& epi() { static EpilogueState s; return s; }
 
+int adam_applied_plans = 0;
+
+static int refuse_second_write(const void* at) {
+    set_error("a kernel writes the gradient at %p again after its optimizer update was applied by the kernel that wrote it "
+              "first in this step (lg_adam_epilogue_arm is for gradients written by ONE kernel per step: no shared weights)", at);
+    return LG_EINVAL;
+}
+
+int adam_epilogue_overlap(uintptr_t lo, uintptr_t hi) {
+    for (const ArmedPlan& a : epi().armed) {
+        if (!a.applied) continue;
+        const uintptr_t g = reinterpret_cast<uintptr_t>(a.grad);
+        if (lo < g + uintptr_t(a.n) * sizeof(float) && g < hi) return refuse_second_write(a.grad);
+    }
+    return LG_OK;
+}
+
 const AdamPlan* adam_epilogue_take(const void* grad, int64_t n, int accumulate, int* rc) {
     if (rc) *rc = LG_OK;
     EpilogueState& E = epi();
     if (E.armed.empty() || grad == nullptr) return nullptr;
+    const int orc = adam_epilogue_check_write(grad, n * int64_t(sizeof(float)));
+    if (orc != LG_OK) {
+        if (rc) *rc = orc;
+        return nullptr;
+    }
     for (ArmedPlan& a : E.armed) {
         if (a.grad != grad) continue;
-        if (a.applied) {
-            set_error("a kernel writes the gradient at %p again after its optimizer update was applied by the kernel that wrote it "
-                      "first in this step (lg_adam_epilogue_arm is for gradients written by ONE kernel per step: no shared weights)", grad);
-            if (rc) *rc = LG_EINVAL;
-            return nullptr;
-        }
         if (accumulate || a.n != n) return nullptr;      // adds to an existing gradient / another extent: left to lg_adam_epilogue_finish
         a.applied = true;
+        ++adam_applied_plans;
         return a.plan_dev;
     }
     return nullptr;
-}
-
-int adam_epilogue_check_write(const void* grad) {
-    int rc = LG_OK;
-    for (const ArmedPlan& a : epi().armed)
-        if (a.grad == grad && a.applied) { (void)adam_epilogue_take(grad, a.n, 1, &rc); break; }
-    return rc;
 }
 
 constexpr int kPlanBatch = 32;
@@ -392,6 +402,7 @@ extern "C" int lg_adam_epilogue_arm(const float* grad, int64_t n, const void* pl
 
 extern "C" int lg_adam_epilogue_disarm(void) {
     epi().armed.clear();
+    adam_applied_plans = 0;
     return LG_OK;
 }
 
@@ -419,6 +430,7 @@ extern "C" int lg_adam_epilogue_finish(int* applied_by_kernels, int* applied_her
     }
     flush();
     E.armed.clear();
+    adam_applied_plans = 0;
     if (applied_by_kernels) *applied_by_kernels = taken;
     if (applied_here) *applied_here = left;
     LG_CHECK_LAUNCH();

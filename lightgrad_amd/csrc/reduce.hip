@@ -498,6 +498,7 @@ extern "C" int lg_reduce_acc(int op, int ndim, const int64_t* shape, const void*
         }
     }
     if (d.n_out == 0) return LG_OK;
+    { const int arc = adam_epilogue_check_write(out, d.n_out * int64_t(sizeof(float))); if (arc != LG_OK) return arc; }
     if (d.rlen == 0) {
         LG_ARG(op == LG_RED_SUM, "lg_reduce: zero-size reduction has no identity for max/min");
         if (accumulate) return LG_OK;

@@ -606,6 +606,7 @@ extern "C" int lg_scatter_add_rows_f32(const float* grad_out, const void* ids, i
     LG_ARG(n_ids >= 0 && row_len >= 0 && table_rows >= 0, "lg_scatter_add_rows_f32: bad shape");
     if (n_ids == 0 || row_len == 0) return LG_OK;
     LG_ARG(grad_out && ids && grad_table, "lg_scatter_add_rows_f32: NULL pointer");
+    { const int arc = adam_epilogue_check_write(grad_table, table_rows * row_len * int64_t(sizeof(float))); if (arc != LG_OK) return arc; }
     static const char* owner_env = getenv("LG_SCATTER_OWNER");        // experiments only: 0 = atomics for every size
     if (n_ids <= 4096 && !(owner_env && atoi(owner_env) == 0) && gemm_group_is_open()) {
         // inside a gradient group bracket (lg_gemm_group_begin): queued, and launched with the LayerNorm parameter gradients -
@@ -710,6 +711,11 @@ extern "C" int lg_layernorm_param_grads_f32(const float* g, const float* xhat, f
     LG_REQUIRE_INIT();
     LG_ARG(rows >= 0 && cols >= 1, "lg_layernorm_param_grads_f32: bad shape");
     LG_ARG(g && xhat && dw && db, "lg_layernorm_param_grads_f32: NULL pointer");
+    {
+        int arc = adam_epilogue_check_write(dw, cols * int64_t(sizeof(float)));
+        if (arc == LG_OK) arc = adam_epilogue_check_write(db, cols * int64_t(sizeof(float)));
+        if (arc != LG_OK) return arc;
+    }
     const int64_t blocks_x = (cols + 255) / 256;
     LG_ARG(blocks_x < (int64_t(1) << 31), "lg_layernorm_param_grads_f32: too many columns");
     int64_t splits = 1;

@@ -640,6 +640,9 @@ class DataParallel(object):
             optimizer.use_peer_exchange(self.comm)
             self._exchange_in_optimizer = True
             self.set_overlap(False)
+        # an exchange that runs outside the optimizer (sync_gradients) sums the bucket AFTER the backward kernels: an update
+        # applied by those kernels (Adam.fuse_update_into_backward) would use the local gradient
+        optimizer._exchange_outside = self._exchange_needed() and not self._exchange_in_optimizer
         return optimizer
 
     def broadcast_parameters(self, root: int = 0):

@@ -31,6 +31,7 @@ class Optimizer(object):
         strangers = [type(p).__name__ for p in self.parameters if not isinstance(p, AbstractTensor)]
         assert not strangers, "optimizers update tensors, got %s" % strangers
         self._flat_grad = None          # the gradient bucket, once a flat-bucket backend took over (use_flat_buckets)
+        self._exchange_outside = False  # dist.DataParallel.attach: the bucket is summed over the ranks after backward, before step
 
     def zero_grad(self) -> None:
         if self._flat_grad is None:
@@ -123,12 +124,17 @@ class Adam(Optimizer):
         """let the kernels that PRODUCE the parameter gradients apply this optimizer's update to them (HipTensor: the weight
         gradient GEMM's epilogue, its bias row sums, the skinny-head backward) - `step()` then launches nothing when every
         gradient was produced that way, and one kernel for the rest otherwise.  Same values as the update launch, bit for bit.
-        Needs flat buckets; not with a data-parallel exchange (the update needs the SUMMED gradient); every parameter's
-        gradient must be written by one kernel per step (no weight shared between layers: a second writer raises).  The
-        parameters alternate between two buckets: `zero_grad(); backward(); step()` in that order, one backward per step, and
-        an even number of steps inside a captured hipGraph (lightgrad_amd/autograd/hip/tensor.py: BackwardUpdate)."""
+        Needs flat buckets; not with a data-parallel exchange of any kind (the update needs the SUMMED gradient: asserted here,
+        also for an exchange that DataParallel.attach left to sync_gradients).  A kernel that OVERWRITES a parameter's whole
+        gradient applies its update; any later write into that gradient in the same step - a weight shared between layers, a
+        penalty on it, a tied table - raises HipError from that write (every writer of the library checks), after which
+        `disarm()` of the backend object makes the library usable again.  Gradients that are only ADDED to (or written by
+        kernels that carry no update) are updated by `step()` in one launch.  The parameters alternate between two buckets:
+        `zero_grad(); backward(); step()` in that order, one backward per step, and an even number of steps inside a captured
+        hipGraph, replayed from the bucket it was captured at (lightgrad_amd/autograd/hip/tensor.py: BackwardUpdate)."""
         assert self._flat is not None and hasattr(self._flat[0], "_new_backward_update"), "use_flat_buckets() first (dist.DataParallel(flatten=True).attach)"
-        assert self._peer_exchange is None, "the update cannot ride in the backward kernels when the gradients are exchanged first"
+        assert self._peer_exchange is None and not self._exchange_outside, \
+            "the update cannot ride in the backward kernels when the gradients are exchanged first"
         assert self.t % max(1, len(self.parameters)) == 0
         flat_p, flat_m, flat_v, offsets = self._flat
         self._backward_update = flat_p._new_backward_update(self.parameters, self._flat_grad, flat_m, flat_v, offsets, self.lr, self.b1, self.b2,

@@ -9,6 +9,8 @@ Weak 10).  A program here is a random walk over exactly those ingredients: Linea
 head kernels, some with no bias), relu / tanh / sigmoid, residual adds, scalar multiplies, reshapes and transposed views, reads of
 intermediates in the middle of a forward pass (which make lazy tensors real), in-place writes into inputs that lazy tensors still
 want to read, several losses, repeated backward passes with and without zero_grad, and one of the optimizers in one of its forms.
+Some programs also use a parameter twice (SHARED_KEYS: a square layer applied again, a penalty on a weight or a bias before or
+after the data loss) - the case where two kernels write one parameter gradient.
 
     run_program(T, seed, ...) -> {label: ndarray}          # everything a user could look at, in program order
     compare(cpu, other)                                     # raises AssertionError naming the first label that differs
@@ -27,8 +29,9 @@ class Net(light.nn.Module):
         self.norms = light.nn.ModuleList(*[light.nn.LayerNorm(b) if on else light.nn.Module() for b, on in zip(dims[1:], norms)])
 
 
-def draw_program(seed):
-    """the random choices of one program, independent of the backend"""
+def draw_program(seed, shared=False):
+    """the random choices of one program, independent of the backend; shared=True: with the shared-parameter ingredient
+    (draw_shared), otherwise its keys say "none" - the program each seed drew before that ingredient existed"""
     rng = np.random.RandomState(seed)
     deep = seed % 4 == 3                             # every fourth program is deep enough for the queued weight gradients (GradGroup)
     depth = int(rng.randint(5, 8)) if deep else int(rng.randint(1, 4))
@@ -59,7 +62,29 @@ def draw_program(seed):
         # the sum over a freshly normalised row is 0 in exact arithmetic: the loss and every gradient behind it would be rounding
         # noise (which AdaBelief then normalises into steps of size lr) - nothing two correct backends have to agree on
         prog["loss"] = "weighted"
+    prog.update(draw_shared(seed, prog) if shared else {"reuse": None, "penalty": None})
     return prog
+
+
+SHARED_KEYS = ("reuse", "penalty")
+
+
+def draw_shared(seed, prog):
+    """the shared-parameter ingredient, drawn from a stream of its own: the keys above are what every seed drew before it existed.
+      reuse    index k of a square layer applied a second time right behind itself (with its activation, tanh if it has
+               none: two products in a row stay bounded), or None
+      penalty  None or (target, layer, coefficient, place): coefficient * sum(p * p) of layer k's "weight" or "bias", added
+               "before" or "after" the data loss in the expression"""
+    rng = np.random.RandomState(7919 * seed + 104729)
+    dims, depth = prog["dims"], len(prog["dims"]) - 1
+    square = [k for k in range(depth) if dims[k] == dims[k + 1]]
+    reuse = int(rng.choice(square)) if square and rng.rand() < 0.6 else None
+    penalty = None
+    if rng.rand() < 0.5:
+        k = int(rng.randint(depth))
+        target = "bias" if prog["biases"][k] and rng.rand() < 0.4 else "weight"
+        penalty = (target, k, float(rng.choice([0.01, 0.05])), str(rng.choice(["before", "after"])))
+    return {"reuse": reuse, "penalty": penalty}
 
 
 def run_program(T, prog, dtype=np.float32, prepare=None):
@@ -108,6 +133,8 @@ def run_program(T, prog, dtype=np.float32, prepare=None):
             act = prog["acts"][k]
             if act != "none":
                 h = getattr(h, act)()
+            if prog["reuse"] == k:                       # the same weights once more: two writers of one gradient
+                h = getattr(layer(h), act if act != "none" else "tanh")()
             if prog["norm"][k]:
                 h = model.norms[k](h)
             if prog["residual"][k] and prev.shape == h.shape:
@@ -121,7 +148,7 @@ def run_program(T, prog, dtype=np.float32, prepare=None):
                     x[...] = T.from_numpy(poke_np, requires_grad=False)
         return x, h_in, h
 
-    def loss_of(h):
+    def data_loss(h):
         if prog["loss"] == "mse":
             return light.loss.mse(h, T.from_numpy(target_np, requires_grad=False))
         if prog["loss"] == "sum":
@@ -129,6 +156,17 @@ def run_program(T, prog, dtype=np.float32, prepare=None):
         if prog["loss"] == "ce":
             return light.loss.cross_entropy(h, T.from_numpy(labels_np, requires_grad=False))
         return (h * T.from_numpy(w_np, requires_grad=False)).sum()
+
+    def loss_of(h):
+        if prog["penalty"] is None:
+            return data_loss(h)
+        target, k, coef, place = prog["penalty"]
+        p = getattr(model.layers[k], target)
+        if place == "before":
+            pen = (p * p).sum() * coef
+            return pen + data_loss(h)
+        loss = data_loss(h)
+        return loss + (p * p).sum() * coef
 
     for step in range(prog["steps"]):
         tag = "s%d" % step
