@@ -33,6 +33,7 @@
 #include "mse_finalize.h"
 #include "head_fwd_body.h"
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 namespace lg {
@@ -45,6 +46,14 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define LG_SMALL_PD 2
 #endif
 constexpr int kSmallTilePrefetch = LG_SMALL_PD;
+// ... and of the wave-private K loop (gemm_tile_body.inc).  One, measured (MNIST MLP step, one box, alternating runs,
+// profiles/r5/README.md): 3 tiles in flight 46.6 us per step, 2: 45.9, 1: 45.4, the cooperative loop 47.1 - the loop has a second
+// workgroup on the CU to fill its waits, and a wave takes 64 bytes of a row per K-step: the fewer steps are in flight, the
+// more often the rest of the line is still in the L1 when a neighbouring wave asks for it
+#ifndef LG_WAVE_PRIVATE_PD
+#define LG_WAVE_PRIVATE_PD 1
+#endif
+constexpr int kWavePrivatePrefetch = LG_WAVE_PRIVATE_PD;
 
 // n / d for n < 2^31 with a host-made multiplier: (n * m) >> s, m = floor(2^(31+l) / d) + 1, l = ceil(log2 d).  A lone
 // small workgroup cannot issue its first load before it knows its tile: five emulated integer divisions (~25
@@ -160,6 +169,9 @@ template <int BM, int BN, bool XKC> constexpr bool kGatherStaging = !XKC && BM *
 #else
 template <int BM, int BN, bool XKC> constexpr bool kGatherStaging = false;
 #endif
+// the tiles that run the wave-private K loop when both operands are K-contiguous: one wave per K-group (32x32 with four K-groups).
+// The 64x32 / 32x64 tiles with two K-groups stay on the cooperative loop: the two waves of a K-group share an operand there.
+template <int BM, int BN, int WM, int WN, int KG> constexpr bool kWavePrivateTile = KG > 1 && WM * WN == 1 && BM == 32 && BN == 32;
 template <int BM, int BN, int BK, bool AKC, bool BKC, int KG>
 constexpr int gemm_lds_floats() {
     constexpr int BKS = BK * KG;
@@ -172,11 +184,14 @@ constexpr int gemm_lds_floats() {
 // XT: 1 = three products on one op(A) (lg_gemm_multi3_f32), 2 = K through three B operands (lg_gemm_kseg3_f32).  Separate
 // instantiations: as run-time branches of the common kernel their few instructions and argument loads cost every GEMM launch
 // 0.4 - 1 us (the MLP step 59.9 -> 62.3 us), on the path in front of a workgroup's first global load.
-template <int BM, int BN, int BK, int WM, int WN, bool AKC, bool BKC, bool VA, bool VB, int PD, int KG = 1, int XT = 0>
+// WP: the wave-private K loop of the K-group tiles whose waves share no operand (gemm_tile_body.inc).
+template <int BM, int BN, int BK, int WM, int WN, bool AKC, bool BKC, bool VA, bool VB, int PD, int KG = 1, int XT = 0, bool WP = false>
 __global__ void __launch_bounds__(WM * WN * KG * 64) sgemm_mfma(GemmArgs g) {
 #define LG_TILE_OWNS_LDS 1
 #define LG_TILE_BID blockIdx.x
+#define LG_TILE_WAVE_PRIVATE WP
 #include "gemm_tile_body.inc"
+#undef LG_TILE_WAVE_PRIVATE
 #undef LG_TILE_OWNS_LDS
 #undef LG_TILE_BID
 }
@@ -449,6 +464,17 @@ static void launch_layout(const GemmArgs& g, bool va, bool vb) {
     // are checked for zero scratch (tests/test_gemm_registers.py), and deeper rings on this tile do not build:
     constexpr int PD = (BM * BN <= 64 * 64) ? kSmallTilePrefetch : 2;
     static_assert(BM * BN < 256 * 256 || PD <= 2, "a third K-tile in flight does not fit the 256x256 tile's 128 registers: ring registers would spill while their loads are in flight");
+    if constexpr (kWavePrivateTile<BM, BN, WM, WN, KG> && AKC && BKC) {
+        // four K-groups that share no operand: every wave in a K loop of its own (same k-columns, same bits), no barrier in it.  LG_GEMM_KLOOP=coop
+        // (experiments) keeps the cooperative loop for A/B runs.
+        static const char* kloop_env = getenv("LG_GEMM_KLOOP");
+        if (va && vb && !(kloop_env && strcmp(kloop_env, "coop") == 0)) {
+            constexpr int WPD = kWavePrivatePrefetch;
+            if (g.multi) hipLaunchKernelGGL((sgemm_mfma<BM, BN, BK, WM, WN, true, true, true, true, WPD, KG, 1, true>), grid, block, 0, s, g);
+            else         hipLaunchKernelGGL((sgemm_mfma<BM, BN, BK, WM, WN, true, true, true, true, WPD, KG, 0, true>), grid, block, 0, s, g);
+            return;
+        }
+    }
     if constexpr (kHasExtras<BM, BN>) {
         // (the entry points have checked: multi comes K-contiguous on both sides, seg_k with an N-contiguous B, float4 staging)
         if constexpr (AKC && BKC)  { if (g.multi) { hipLaunchKernelGGL((sgemm_mfma<BM, BN, BK, WM, WN, AKC, BKC, true, true, PD, KG, 1>), grid, block, 0, s, g); return; } }
@@ -1006,7 +1032,8 @@ static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K,
                 if (tk <= cus && kgroups + 0.5 < best64) tile = t7 <= t8 ? 7 : 8;
                 // ... and when even 32x32 tiles give a CU no more than two workgroups: FOUR K-groups of 16 k on 32x32 tiles - twice the
                 // workgroups, each wave the same MFMA work; two workgroups per CU fill each other's waits (the forward product of the
-                // MNIST MLP: 13.16 -> 12.43 us, profiles/r4/fwd_tile_32x32_kgroups.txt; K-groups of 32 k: 13.0)
+                // MNIST MLP: 13.16 -> 12.43 us, profiles/r4/fwd_tile_32x32_kgroups.txt; K-groups of 32 k: 13.0; with every wave in a K
+                // loop of its own on its 16 columns and no barrier in the loop 13.15 -> 11.51 us under the profiler, profiles/r5/README.md)
                 if ((tile == 7 || tile == 8) && nblocks(32, 32) <= 2 * cus && !lg::pending_chain()) tile = 5;      // (the chained experiment is built on tile 7)
             }
         }

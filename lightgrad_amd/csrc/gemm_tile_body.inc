@@ -11,8 +11,19 @@
 #ifndef LG_TILE_SIGNAL
 #define LG_TILE_SIGNAL 0
 #endif
+// LG_TILE_WAVE_PRIVATE (sgemm_mfma's WP; one wave per K-group, both operands K-contiguous): the K-groups share no operand, so each
+// wave runs a K loop of its own on its own BK columns of every K-step - it fetches, stages (a region of LDS nobody else
+// touches) and multiplies them, and the loop has no barrier: a wave's LDS operations complete in order, so the
+// write of tile kt+2 behind the fragment reads of tile kt+1 needs neither a second buffer nor a wait.  Everything below that
+// says "staged together" (NTS threads, BKS k-values) then means one wave and its own BK columns.
+#ifndef LG_TILE_WAVE_PRIVATE
+#define LG_TILE_WAVE_PRIVATE false
+#endif
+    constexpr bool WPK = LG_TILE_WAVE_PRIVATE;
+    static_assert(!WPK || (KG > 1 && WM * WN == 1 && BM == 32 && BN == 32 && AKC && BKC && VA && VB && XT != 2 && !LG_TILE_SIGNAL), "wave-private K loop: one wave per K-group, NT form");
     constexpr int NT = WM * WN * KG * 64;
-    constexpr int BKS = BK * KG;                         // k-values staged per K-step
+    constexpr int NTS = WPK ? 64 : NT;                   // threads that stage one K-tile together
+    constexpr int BKS = WPK ? BK : BK * KG;              // k-values staged per K-step
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
     static_assert(TM >= 1 && TN >= 1 && BK % 16 == 0 && (KG == 1 || KG == 2 || KG == 4), "tile config");
     // "Gather" staging (round 4, the 256 x 256 tile): an M- / N-contiguous operand is fetched as FOUR single dwords along k per
@@ -27,22 +38,25 @@
     constexpr int B_PITCH = BLK ? BKS + 4 : BN;
     constexpr int A_TILE = ALK ? BM * A_PITCH : BKS * A_PITCH;
     constexpr int B_TILE = BLK ? BN * B_PITCH : BKS * B_PITCH;
-    constexpr int A_ELEMS = BM * BKS / NT, B_ELEMS = BN * BKS / NT;   // floats staged per thread
+    constexpr int A_ELEMS = BM * BKS / NTS, B_ELEMS = BN * BKS / NTS;   // floats staged per thread
     static_assert(A_ELEMS % 4 == 0 && B_ELEMS % 4 == 0, "staging must divide into float4");
 
-    static_assert(2 * (A_TILE + B_TILE) == gemm_lds_floats<BM, BN, BK, AKC, BKC, KG>(), "LDS size");
+    static_assert(WPK || 2 * (A_TILE + B_TILE) == gemm_lds_floats<BM, BN, BK, AKC, BKC, KG>(), "LDS size");
     static_assert(!(AG || BG) || TM * TN > 1, "gather staging: the multi-accumulator loop only");
 #if LG_TILE_OWNS_LDS
-    __shared__ __attribute__((aligned(16))) float lds[2 * (A_TILE + B_TILE)];
+    __shared__ __attribute__((aligned(16))) float lds[gemm_lds_floats<BM, BN, BK, AKC, BKC, KG>()];
 #endif
     // buffer b: A tile at lds + b*(A_TILE+B_TILE), B tile right behind it
     constexpr int BUF = A_TILE + B_TILE;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
-    const int kg = wave / (WM * WN), wl = wave % (WM * WN);          // K-group of this wave, wave inside the group
+    // (wave-private loop: the K-group picks the wave's K range, descriptors and trip count - scalar values)
+    const int kg = WPK ? __builtin_amdgcn_readfirstlane(wave) : wave / (WM * WN), wl = wave % (WM * WN);          // K-group of this wave, wave inside the group
     const int wm = wl / WN, wn = wl % WN;
-    const int kofs = kg * BK;                                        // its k offset inside a staged K-step
+    const int kofs = WPK ? 0 : kg * BK;                              // its k offset inside a staged K-step
+    const int stid = WPK ? lane : tid;                               // index among the threads that stage a tile together
+    float* const ldsw = WPK ? lds + kg * BUF : lds;                  // wave-private loop: ONE buffer per wave, its own
     const int r = lane & 31, h = lane >> 5;
     LG_TL(0);                                        // workgroup entered
 
@@ -113,10 +127,10 @@
     // addresses and four k coordinates apart and spilled 9-11 registers into its K loop (VERDICT r3).
     constexpr int A_W = VA ? 4 : 1, B_W = VB ? 4 : 1;
     constexpr int A_DIV = AG ? BM : (AKC ? BKS : BM) / A_W, B_DIV = BG ? BN : (BKC ? BKS : BN) / B_W;   // chunks per staged row (gather: per k-quad)
-    static_assert(NT % A_DIV == 0 && NT % B_DIV == 0, "a thread's chunks must differ by whole rows");
-    constexpr int A_STEP = NT / A_DIV, B_STEP = NT / B_DIV;                               // rows (k-rows, k-quads) between a thread's chunks
-    const int a_q = tid / A_DIV, a_r = AG ? tid % A_DIV : (tid % A_DIV) * A_W;            // AKC: (row, k)   gather: (k-quad, row)   else: (k, row)
-    const int b_q = tid / B_DIV, b_r = BG ? tid % B_DIV : (tid % B_DIV) * B_W;            // BKC: (col, k)   gather: (k-quad, col)   else: (k, col)
+    static_assert(NTS % A_DIV == 0 && NTS % B_DIV == 0, "a thread's chunks must differ by whole rows");
+    constexpr int A_STEP = NTS / A_DIV, B_STEP = NTS / B_DIV;                               // rows (k-rows, k-quads) between a thread's chunks
+    const int a_q = stid / A_DIV, a_r = AG ? stid % A_DIV : (stid % A_DIV) * A_W;            // AKC: (row, k)   gather: (k-quad, row)   else: (k, row)
+    const int b_q = stid / B_DIV, b_r = BG ? stid % B_DIV : (stid % B_DIV) * B_W;            // BKC: (col, k)   gather: (k-quad, col)   else: (k, col)
     auto kcA = [&](int i) { return AG ? 4 * (a_q + i * A_STEP) : (AKC ? a_r : a_q + i * A_STEP); };   // k coordinate of chunk i inside its K-tile
     auto kcB = [&](int i) { return BG ? 4 * (b_q + i * B_STEP) : (BKC ? b_r : b_q + i * B_STEP); };
     // LDS position of chunk 0 and the (compile-time) distance to the thread's next chunk
@@ -153,12 +167,24 @@
     };
     // tiles are requested strictly in order: running pointers instead of index arithmetic (every scalar instruction in
     // the K loop of a lone small-tile workgroup shows up in its time)
-    const float* nextA = AKC ? Atile0 + k_begin : Atile0 + k_begin * g.lda;
-    const float* nextB = BKC ? Btile0 + k_begin : Btile0 + k_begin * g.ldb;
-    const int64_t stepA = AKC ? int64_t(BKS) : int64_t(BKS) * g.lda, stepB = BKC ? int64_t(BKS) : int64_t(BKS) * g.ldb;
+    // wave-private loop: wave kg owns the k-columns kg * BK .. kg * BK + BK - 1 of every BK * KG - wide step of the slice, the columns it
+    // multiplies in the cooperative loop - so every accumulator, and with it the result, is bit for bit what that loop gives.  A wave
+    // whose columns lie beyond the slice's end in the last step skips it (the cooperative loop multiplies zeros there); one with
+    // no column at all contributes zeros to the exchange.
+    constexpr int KSTEP = BK * KG;                                   // k distance between a wave's (a workgroup's) consecutive tiles
+    int64_t wk_begin = k_begin, wk_len = k_end - k_begin;
+    if constexpr (WPK) {
+        wk_begin = k_begin + kg * BK;
+        wk_len = wk_len - kg * BK;
+        wk_len = wk_len < 0 ? 0 : wk_len;
+    }
+    const float* nextA = AKC ? Atile0 + wk_begin : Atile0 + wk_begin * g.lda;
+    const float* nextB = BKC ? Btile0 + wk_begin : Btile0 + wk_begin * g.ldb;
+    const int64_t stepA = AKC ? int64_t(KSTEP) : int64_t(KSTEP) * g.lda, stepB = BKC ? int64_t(KSTEP) : int64_t(KSTEP) * g.ldb;
     [[maybe_unused]] const unsigned gatherA = unsigned(g.lda) * 4u, gatherB = unsigned(g.ldb) * 4u;    // bytes between k-rows (gather staging)
-    const int nkt = int((k_end - k_begin + BKS - 1) / BKS);         // K-steps of this slice (32-bit: scalar compares in the loop)
-    const int last_krem = int(k_end - k_begin) - (nkt - 1) * BKS;    // k values of the last one
+    const int nkt = int((wk_len + KSTEP - 1) / KSTEP);              // K-steps of this slice (32-bit: scalar compares in the loop)
+    const int last_left = int(wk_len) - (nkt - 1) * KSTEP;
+    const int last_krem = last_left < BKS ? last_left : BKS;         // k values of the last one
     int requested = 0;
     int seg_left = 0, seg_idx = 0;                                   // K through several B operands (lg_gemm_kseg3_f32)
     if constexpr (XT == 2) seg_left = g.seg_steps;
@@ -238,8 +264,8 @@
     };
 
     auto store_tile = [&](int buf, int slot) {
-        float* a = lds + buf * BUF;
-        float* b = lds + buf * BUF + A_TILE;
+        float* a = ldsw + buf * BUF;
+        float* b = ldsw + buf * BUF + A_TILE;
         // K not a multiple of 4: the last float4 of a K-contiguous row runs into the next row - zero what lies beyond the
         // slice (only the slice's last tile can be short)
         if (g.k_tail && krem_ring[slot] < BKS) {
@@ -375,14 +401,62 @@
 #pragma unroll
     for (int u = 0; u < PD; ++u)
         if (u < nkt) load_tile(u);
-    {
+    if constexpr (!WPK) {
         const int younger = nkt - 1 < PD - 1 ? nkt - 1 : PD - 1;
         wait_tile(0, younger);
+        store_tile(0, 0);
+        __syncthreads();
     }
-    store_tile(0, 0);
-    __syncthreads();
     LG_TL(1);                                        // first K-tile in LDS
-    if constexpr (TM * TN == 1) {
+    if constexpr (WPK) {
+        // The wave's own pipeline: during iteration kt its LDS region holds tile kt, and tile kt+1 moves from the ring into the
+        // same region in the MIDDLE of the dependent MFMA chain - behind the reads of tile kt's second half in program order, which
+        // is all a single buffer needs; the first half of tile kt+1 follows it out of LDS under the second half's MFMAs.  A ring
+        // slot is refilled as soon as its tile is in LDS: before the wait for tile t the tiles up to t + PD - 1 have been requested.
+        static_assert(BK == 16, "one K-step is two k-blocks of 8");
+        float fa[2][4], fb[2][4];
+        auto read_half = [&](int half, int set) {
+            const float4 va = *reinterpret_cast<const float4*>(ldsw + r * A_PITCH + 4 * h + half * 8);
+            const float4 vb = *reinterpret_cast<const float4*>(ldsw + A_TILE + r * B_PITCH + 4 * h + half * 8);
+            fa[set][0] = va.x; fa[set][1] = va.y; fa[set][2] = va.z; fa[set][3] = va.w;
+            fb[set][0] = vb.x; fb[set][1] = vb.y; fb[set][2] = vb.z; fb[set][3] = vb.w;
+        };
+        auto mfma_part = [&](int set, int e0, int e1) {
+#pragma unroll
+            for (int e = e0; e < e1; ++e)
+                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[set][e], fb[set][e], acc[0][0], 0, 0, 0);
+        };
+        // tile t: ring -> LDS, and its ring slot is asked for tile t + PD
+        auto advance = [&](int t, int slot) {
+            const int younger = (nkt < t + PD ? nkt : t + PD) - (t + 1);
+            wait_tile(slot, younger);
+            store_tile(0, slot);
+            if (t + PD < nkt) load_tile(slot);
+        };
+        if (nkt > 0) {
+            advance(0, 0);
+            read_half(0, 0);
+        }
+        for (int kt0 = 0; kt0 < nkt; kt0 += PD) {
+#pragma unroll
+            for (int u = 0; u < PD; ++u) {
+                const int kt = kt0 + u;
+                if (kt < nkt) {
+                    read_half(1, 1);
+                    mfma_part(0, 0, 4);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (kt + 1 < nkt) advance(kt + 1, (u + 1) % PD);
+                    __builtin_amdgcn_sched_barrier(0);
+                    // the next tile's first half leaves LDS behind the first MFMA of this half: the wait in front of that MFMA
+                    // then covers the second-half fragments alone, and three MFMAs run over the read
+                    mfma_part(1, 0, 1);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (kt + 1 < nkt) read_half(0, 0);
+                    mfma_part(1, 1, 4);
+                }
+            }
+        }
+    } else if constexpr (TM * TN == 1) {
         // One accumulator per wave (small tiles: often ONE such wave per SIMD, nothing else to hide latency behind):
         // the fragments of the next half K-tile are fetched from LDS while the MFMAs of the current half run.  The
         // barrier sits between the halves: before it every wave has read ALL of tile kt and written its share of tile
@@ -480,8 +554,10 @@
         // barrier): slot (group - 1, wave-in-group, accumulator, register) holds one value per lane, so both sides move 256 B per
         // wave instruction without bank conflicts; group 0 adds them in group order.  The other groups are done after that.
         constexpr int GROUP_FLOATS = WM * WN * TM * TN * 16 * 64;
-        static_assert((KG - 1) * GROUP_FLOATS <= 2 * (A_TILE + B_TILE), "the K-group exchange must fit the staging buffers");
-        float* x = lds + (wl * TM * TN * 16) * 64 + lane;
+        static_assert(WPK || (KG - 1) * GROUP_FLOATS <= 2 * (A_TILE + B_TILE), "the K-group exchange must fit the staging buffers");
+        // (wave-private loop: no barrier says that the other waves have left their loops - the exchange lies behind their regions)
+        static_assert(!WPK || KG * BUF + (KG - 1) * GROUP_FLOATS <= gemm_lds_floats<BM, BN, BK, AKC, BKC, KG>(), "staging regions + exchange");
+        float* x = lds + (WPK ? KG * BUF : 0) + (wl * TM * TN * 16) * 64 + lane;
         if (kg >= 1) {
 #pragma unroll
             for (int i = 0; i < TM; ++i)
