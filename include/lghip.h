@@ -197,6 +197,15 @@ int lg_reduce_acc(int op, int ndim, const int64_t* shape,
                   const void* in, const int64_t* in_strides,
                   uint32_t axis_mask, void* out, int accumulate);
 
+/* Which kernel the most recent lg_reduce / lg_reduce_acc call of the calling thread launched (calls the library makes itself,
+ * such as the mean of lg_cross_entropy_mean_f32, count): host bookkeeping for tests, no device work.
+ *   out = {kernel, splits, groups, nk, nr, vector_path_possible}
+ * kernel: 0 = one wave per row, 1 = rows split over workgroups, 2 = 64-column tiles, 3 = general / column kernel, -1 = nothing
+ * launched (no output elements, the zero-length sum, a refused call: the other fields are then 0 except the last);
+ * splits: workgroups that share one output (1 = no fold); groups: first-level fold groups of kernel 1, else 0;
+ * nk, nr: kept and reduced dimensions left after merging contiguous neighbours; vector_path_possible: `in` is 16-byte aligned. */
+int lg_reduce_last_plan(int32_t out[6]);
+
 /* ---- SGEMM on MFMA ---------------------------------------------------------
  * C[b] (M x N, row-major, leading dimension ldc) (+)= op(A[b]) @ op(B[b]), fp32
  * in/out, fp32 accumulate on v_mfma_f32_32x32x2_f32.

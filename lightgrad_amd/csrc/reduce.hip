@@ -343,6 +343,16 @@ __global__ void __launch_bounds__(256) red_cols_tile(const float* __restrict__ i
 
 // ---- host ---------------------------------------------------------------------------------------
 
+// lg_reduce_last_plan: what the most recent lg_reduce / lg_reduce_acc call of this thread launched - host bookkeeping written
+// where the launch is issued, so that a test can see which kernel and fold its shape reached after the thresholds below move
+enum { PLAN_NONE = -1, PLAN_ROWS_WAVE = 0, PLAN_ROWS_SPLIT = 1, PLAN_COLS_TILE = 2, PLAN_COLS = 3 };
+static thread_local int32_t g_plan[6] = {PLAN_NONE, 0, 0, 0, 0, 0};
+
+static void note_plan(int kernel, int64_t splits, int64_t groups, int nk, int nr, const void* in) {
+    g_plan[0] = kernel; g_plan[1] = int32_t(splits); g_plan[2] = int32_t(groups);
+    g_plan[3] = nk;     g_plan[4] = nr;              g_plan[5] = aligned16(in) ? 1 : 0;
+}
+
 // collapse a list of (shape, stride) pairs in place; returns the new count (>= 1)
 static int collapse(int n, int64_t* shp, int64_t* st) {
     int m = 0;
@@ -368,6 +378,7 @@ static int run_reduce(const float* in, float* out, RedDesc& d) {
     if (rows) {
         // many rows, or short rows: a wave per row
         if (d.n_out >= 256 || d.rlen <= 8192) {
+            note_plan(PLAN_ROWS_WAVE, 1, 0, d.nk, d.nr, in);
             hipLaunchKernelGGL((red_rows_wave<OP>), dim3(unsigned((d.n_out + 3) / 4)), dim3(256), 0, s, in, out, d);
             return LG_OK;
         }
@@ -381,15 +392,18 @@ static int run_reduce(const float* in, float* out, RedDesc& d) {
         int64_t seg = ((d.rlen + splits - 1) / splits + 3) & ~int64_t(3);
         splits = (d.rlen + seg - 1) / seg;
         if (d.n_out > 65535) {   // grid.y limit: fall back to a wave per row
+            note_plan(PLAN_ROWS_WAVE, 1, 0, d.nk, d.nr, in);
             hipLaunchKernelGGL((red_rows_wave<OP>), dim3(unsigned((d.n_out + 3) / 4)), dim3(256), 0, s, in, out, d);
             return LG_OK;
         }
         if (splits == 1) {
+            note_plan(PLAN_ROWS_SPLIT, 1, 0, d.nk, d.nr, in);
             hipLaunchKernelGGL((red_rows_split<OP>), dim3(1, unsigned(d.n_out)), dim3(256), 0, s, in, out, nullptr, nullptr, d, seg, int64_t(1));
             return LG_OK;
         }
         const int64_t groups = (splits + kRowsFoldGroup - 1) / kRowsFoldGroup, n_tickets = d.n_out * (groups + 1);
         if (n_tickets > rt().n_gemm_tickets) {   // (n_out < 256 on this path and a few dozen groups: the pool is far larger)
+            note_plan(PLAN_ROWS_WAVE, 1, 0, d.nk, d.nr, in);
             hipLaunchKernelGGL((red_rows_wave<OP>), dim3(unsigned((d.n_out + 3) / 4)), dim3(256), 0, s, in, out, d);
             return LG_OK;
         }
@@ -398,6 +412,7 @@ static int run_reduce(const float* in, float* out, RedDesc& d) {
         float* partial = nullptr;
         int rc = lg_malloc(reinterpret_cast<void**>(&partial), size_t(d.n_out * (splits + groups)) * sizeof(float));
         if (rc != LG_OK) return rc;
+        note_plan(PLAN_ROWS_SPLIT, splits, groups, d.nk, d.nr, in);
         hipLaunchKernelGGL((red_rows_split<OP>), dim3(unsigned(splits), unsigned(d.n_out)), dim3(256), 0, s, in, out, partial,
                            rt().gemm_tickets, d, seg, tstride);
         return lg_free(partial);   // stream-ordered: the block is only reused by later launches
@@ -424,6 +439,7 @@ static int run_reduce(const float* in, float* out, RedDesc& d) {
                 int rc = lg_malloc(reinterpret_cast<void**>(&partial), size_t(d.n_out * splits) * sizeof(float));
                 if (rc != LG_OK) return rc;
             }
+            note_plan(PLAN_COLS_TILE, splits, 0, d.nk, d.nr, in);
             hipLaunchKernelGGL((red_cols_tile<OP>), dim3(unsigned(bx), unsigned(splits)), dim3(256), 0, s, in, out, partial,
                                rt().gemm_tickets, d.n_out, d.rlen, d.rstride[0], chunk, d.accumulate);
             return splits > 1 ? lg_free(partial) : LG_OK;
@@ -449,12 +465,14 @@ static int run_reduce(const float* in, float* out, RedDesc& d) {
     if (blocks_x >= (int64_t(1) << 31)) { set_error("lg_reduce: output too large"); return LG_EINVAL; }
     if (splits > 1 && blocks_x > rt().n_gemm_tickets) { splits = 1; chunk = d.rlen; }     // more output blocks than tickets
     if (splits == 1) {
+        note_plan(PLAN_COLS, 1, 0, d.nk, d.nr, in);
         hipLaunchKernelGGL((red_cols<OP>), dim3(unsigned(blocks_x), 1), dim3(256), 0, s, in, out, nullptr, nullptr, d, chunk);
         return LG_OK;
     }
     float* partial = nullptr;
     int rc = lg_malloc(reinterpret_cast<void**>(&partial), size_t(d.n_out * splits) * sizeof(float));
     if (rc != LG_OK) return rc;
+    note_plan(PLAN_COLS, splits, 0, d.nk, d.nr, in);
     hipLaunchKernelGGL((red_cols<OP>), dim3(unsigned(blocks_x), unsigned(splits)), dim3(256), 0, s, in, out, partial,
                        rt().gemm_tickets, d, chunk);
     return lg_free(partial);
@@ -475,6 +493,7 @@ extern "C" int lg_reduce(int op, int ndim, const int64_t* shape, const void* in,
 extern "C" int lg_reduce_acc(int op, int ndim, const int64_t* shape, const void* in, const int64_t* in_strides,
                              uint32_t axis_mask, void* out, int accumulate) {
     LG_REQUIRE_INIT();
+    note_plan(PLAN_NONE, 0, 0, 0, 0, in);                          // until a kernel is launched: refused calls, n_out == 0, the zero fill
     LG_ARG(!accumulate || op == LG_RED_SUM, "lg_reduce_acc: accumulate is defined for sums only");
     LG_ARG(ndim >= 0 && ndim <= LG_MAX_DIMS, "lg_reduce: ndim %d out of range [0, %d]", ndim, LG_MAX_DIMS);
     LG_ARG(in != nullptr && out != nullptr, "lg_reduce: NULL pointer");
@@ -519,5 +538,11 @@ extern "C" int lg_reduce_acc(int op, int ndim, const int64_t* shape, const void*
     }
     if (rc != LG_OK) return rc;
     LG_CHECK_LAUNCH();
+    return LG_OK;
+}
+
+extern "C" int lg_reduce_last_plan(int32_t out[6]) {
+    LG_ARG(out != nullptr, "lg_reduce_last_plan: NULL pointer");
+    for (int k = 0; k < 6; ++k) out[k] = g_plan[k];
     return LG_OK;
 }
