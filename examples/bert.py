@@ -84,15 +84,27 @@ class BertSelfAttention(nn.Module):
 
     def forward(self, hidden, attention_mask=None):
         b, s, _ = hidden.shape
-        if attention_mask is None and hasattr(hidden, "self_attention") and hidden.self_attention_supported(self.query.weight, self.h):
+        # a padded batch (a mask) or a length the plain kernels do not take (no multiple of 32) goes to the backend's masked forms,
+        # if it has them and the mask is what they read: a (b, s) or (1, s) float32 constant
+        masked = attention_mask is not None or s % 32 != 0
+        if masked:
+            fused = hasattr(hidden, "masked_attention") and (attention_mask is None or (
+                attention_mask.dtype == np.float32 and not attention_mask.requires_grad and tuple(attention_mask.shape) in ((b, s), (1, s))))
+            extra = {"masked": True}
+        else:
+            fused, extra = hasattr(hidden, "self_attention"), {}
+        scale = math.sqrt(self.d) ** -1
+        if fused and hidden.self_attention_supported(self.query.weight, self.h, **extra):
             # the backend's one-node form of this whole method: one launch for the three projections, one for the attention
+            extra = {"mask": attention_mask} if attention_mask is not None else {}
             context = hidden.self_attention(self.query.weight, self.query.bias, self.key.weight, self.key.bias,
-                                            self.value.weight, self.value.bias, heads=self.h, scale=math.sqrt(self.d) ** -1)
+                                            self.value.weight, self.value.bias, heads=self.h, scale=scale, **extra)
             return context, context.attention_probs
         q, k, v = self.query(hidden), self.key(hidden), self.value(hidden)
-        if attention_mask is None and hasattr(q, "attention") and q.attention_supported(self.h):
+        if fused and (q.masked_attention_supported(self.h) if masked else q.attention_supported(self.h)):
             # the backend's one-launch form of everything below (scores, scaling, softmax, context), forward and backward
-            context = q.attention(k, v, heads=self.h, scale=math.sqrt(self.d) ** -1)
+            context = q.masked_attention(k, v, heads=self.h, scale=scale, mask=attention_mask) if masked else \
+                q.attention(k, v, heads=self.h, scale=scale)
             return context, context.attention_probs
         # head split: (b, s, h*d) -> (b, h, s, d) as stride permutations, no copies
         q = q.reshape(b, s, self.h, self.d).transpose(0, 2, 1, 3)

@@ -425,6 +425,26 @@ int lg_attention_bwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* 
                          float* dv, int64_t lddv, int64_t sbdv, int64_t batch, int64_t heads, int64_t S, int64_t D,
                          float scale);
 
+/* The same two launches for what a tokenizer produces: any S in 1 .. 128 and a key-padding mask (reference
+ * examples/bert.py:80-83: `scores + (1.0 - attention_mask) * -10000.0` between the scaling and the softmax; bert.py:341-350
+ * feeds a sentence of arbitrary length).  mask: fp32, element (b, j) at mask + b * sbm + j, sbm = 0 for one row shared by
+ * the batch (the reference's (1, 1, 1, s) mask), NULL for none; the score of key j is fl(fl(acc * scale) + fl(fl(1 - mask) *
+ * -10000)) - the composite's own fp32 arithmetic, so a mask value between 0 and 1 means what it means there, and a mask
+ * of ones gives the bits of lg_attention_fwd_f32.  The tiles cover S rounded up to 32; rows >= S are neither read nor
+ * written, keys >= S take no part in any sum.  P is dense (batch, heads, S, S) with row pitch S.  The backward needs no
+ * mask (it reads P).  Supported: D = 32 or 64, 1 <= S <= 128 (lg_attention_masked_supported); operands as above; a
+ * non-NULL mask needs sbm == 0 or sbm >= S. */
+int lg_attention_masked_supported(int64_t S, int64_t D);
+int lg_attention_masked_fwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
+                                const float* v, int64_t ldv, int64_t sbv, float* o, int64_t ldo, int64_t sbo, float* p,
+                                int64_t batch, int64_t heads, int64_t S, int64_t D, float scale,
+                                const float* mask, int64_t sbm);
+int lg_attention_masked_bwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
+                                const float* v, int64_t ldv, int64_t sbv, const float* g, int64_t ldg, int64_t sbg,
+                                const float* p, float* dq, int64_t lddq, int64_t sbdq, float* dk, int64_t lddk, int64_t sbdk,
+                                float* dv, int64_t lddv, int64_t sbdv, int64_t batch, int64_t heads, int64_t S, int64_t D,
+                                float scale);
+
 /* ---- two independent products in one launch ----------------------------------------------------------
  * lg_gemm_pair_begin(); <product 1>; <product 2>; lg_gemm_pair_end();   with products issued through
  * lg_gemm_f32 / lg_gemm_rowsum_f32 / lg_gemm_fused_f32.  If the first resolves to the 64x64 tile with an

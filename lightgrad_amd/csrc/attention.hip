@@ -27,9 +27,17 @@
 // four MFMAs, the others four ds_read_b32 of 32 consecutive floats.  Row pitches: K-contiguous rows + 4 floats (16 lanes of a
 // b128 read hit 16 different 16-byte slots), M/N-contiguous rows = 8 mod 16 floats (the two lane halves, 4 rows apart, land
 // on different halves of the 64 banks).
+//
+// TAIL instantiations (lg_attention_masked_*): any S in 1 .. 128 and an additive per-key bias from a padding mask (reference
+// examples/bert.py:80-83: scores + (1 - mask) * -10000).  Everything above runs on Sp = S rounded up to 32 - grid, LDS, MFMA K
+// spans, hand-off counter - with the LDS operand rows [S, Sp) ZERO (not whatever the LDS held: NaN * 0 would reach the sums);
+// the softmax takes keys >= S out by selection, global rows >= S are neither read nor written, and the probabilities
+// (row pitch S, not 16-byte aligned unless S % 4 == 0) go out and come in as scalars.  The TAIL = false instantiations are
+// the kernels as they were.
 #include "common.h"
 #include "mfma_lds.h"
 #include <cmath>
+#include <type_traits>
 
 namespace lg {
 
@@ -53,20 +61,47 @@ struct AttnArgs {
     float scale;
 };
 
-template <int D>
-constexpr int attn_fwd_lds_floats(int S) { return 32 * (D + 4) + S * (D + 4) + S * (D + 8) + 32 * (S + 4) + 3 * 1024; }
+struct AttnTailArgs : AttnArgs {
+    const float* mask;               // key-padding mask, element (b, j) at mask + b * sbm + j (sbm = 0: one row for the batch); NULL = none
+    int64_t sbm;
+};
+
+__host__ __device__ constexpr int round32(int S) { return (S + 31) & ~31; }
 
 template <int D>
-__global__ void __launch_bounds__(256) attn_fwd(AttnArgs a) {
+constexpr int attn_fwd_lds_floats(int S) { return 32 * (D + 4) + S * (D + 4) + S * (D + 8) + 32 * (S + 4) + 3 * 1024; }
+// TAIL: the same layout over Sp rows and the per-key bias behind it
+template <int D>
+constexpr int attn_fwd_tail_lds_floats(int S) { return attn_fwd_lds_floats<D>(round32(S)) + 128; }
+
+// store_rows that also clears rows [rows, padded): an MFMA operand row past the sequence must be zero, not stale LDS
+template <int D, int N>
+__device__ __forceinline__ void store_rows_padded(const af32x4 (&v)[N], float* dst, int pitch, int rows, int padded) {
+    constexpr int Q = D / 4;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const int f = threadIdx.x + i * 256;
+        if (f < padded * Q) {
+            af32x4 t = v[i];
+            if (f >= rows * Q) t = af32x4{0.f, 0.f, 0.f, 0.f};
+            *reinterpret_cast<af32x4*>(dst + (f / Q) * pitch + (f % Q) * 4) = t;
+        }
+    }
+}
+
+template <int D, bool TAIL = false>
+__global__ void __launch_bounds__(256) attn_fwd(std::conditional_t<TAIL, AttnTailArgs, AttnArgs> a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int S = a.S;
+    const int S = a.S;                               // the sequence
+    const int Sp = TAIL ? round32(S) : S;            // what the tiles cover
     constexpr int PQ = D + 4, PV = D + 8;
-    const int PP = S + 4;
+    const int PP = Sp + 4;
     float* Qs = lds;
     float* Ks = Qs + 32 * PQ;
-    float* Vs = Ks + S * PQ;
-    float* Ps = Vs + S * PV;
+    float* Vs = Ks + Sp * PQ;
+    float* Ps = Vs + Sp * PV;
     float* Red = Ps + 32 * PP;
+    [[maybe_unused]] float* Bias = Red + 3 * 1024;   // TAIL: what key j adds to every score of its column
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     const int q0 = blockIdx.x * 32, head = blockIdx.y, b = blockIdx.z;
     LG_ATL(0);
@@ -74,29 +109,102 @@ __global__ void __launch_bounds__(256) attn_fwd(AttnArgs a) {
     {
         constexpr int NB = 32 * (D / 4) / 256 > 0 ? 32 * (D / 4) / 256 : 1, NA = 128 * (D / 4) / 256;   // float4 per thread: 32 rows / all rows
         af32x4 rq[NB], rk[NA], rv[NA];
-        load_rows<D, NB>(rq, a.q + int64_t(b) * a.sbq + int64_t(q0) * a.ldq + head * D, a.ldq, 32);
-        load_rows<D, NA>(rk, a.k + int64_t(b) * a.sbk + head * D, a.ldk, S);
-        load_rows<D, NA>(rv, a.v + int64_t(b) * a.sbv + head * D, a.ldv, S);
-        store_rows<D, NB>(rq, Qs, PQ, 32);
-        store_rows<D, NA>(rk, Ks, PQ, S);
-        store_rows<D, NA>(rv, Vs, PV, S);
+        if constexpr (!TAIL) {
+            load_rows<D, NB>(rq, a.q + int64_t(b) * a.sbq + int64_t(q0) * a.ldq + head * D, a.ldq, 32);
+            load_rows<D, NA>(rk, a.k + int64_t(b) * a.sbk + head * D, a.ldk, S);
+            load_rows<D, NA>(rv, a.v + int64_t(b) * a.sbv + head * D, a.ldv, S);
+            store_rows<D, NB>(rq, Qs, PQ, 32);
+            store_rows<D, NA>(rk, Ks, PQ, S);
+            store_rows<D, NA>(rv, Vs, PV, S);
+        } else {
+            const int qrows = S - q0 < 32 ? S - q0 : 32;                  // rows of this block that exist: a row past them is never read
+            load_rows<D, NB>(rq, a.q + int64_t(b) * a.sbq + int64_t(q0) * a.ldq + head * D, a.ldq, qrows);
+            load_rows<D, NA>(rk, a.k + int64_t(b) * a.sbk + head * D, a.ldk, S);
+            load_rows<D, NA>(rv, a.v + int64_t(b) * a.sbv + head * D, a.ldv, S);
+            store_rows_padded<D, NB>(rq, Qs, PQ, qrows, 32);
+            store_rows_padded<D, NA>(rk, Ks, PQ, S, Sp);
+            store_rows_padded<D, NA>(rv, Vs, PV, S, Sp);
+            // (1.0 - mask) * -10000.0 in fp32, the composite's own arithmetic (bert.py:82); -0.0f where the mask is 1 or absent:
+            // adding it changes no bit of a score
+            if (tid < Sp) Bias[tid] = (tid < S && a.mask) ? (1.0f - a.mask[int64_t(b) * a.sbm + tid]) * -10000.0f : -0.0f;
+        }
     }
     __syncthreads();
     LG_ATL(1);
 
     // scores of 32 queries against keys [32 wave, 32 wave + 32), scaled (the product rounded to fp32 first, like `scores * c`)
-    if (32 * wave < S) {
+    if (32 * wave < Sp) {
         af32x16 acc = zero16();
         wave_mma<true, true>(acc, Qs, PQ, Ks + 32 * wave * PQ, PQ, D, r, h);
+        if constexpr (TAIL) {
+            const float bias = Bias[32 * wave + r];
 #pragma unroll
-        for (int e = 0; e < 16; ++e) Ps[acc_row(e, h) * PP + 32 * wave + r] = acc[e] * a.scale;
+            for (int e = 0; e < 16; ++e) Ps[acc_row(e, h) * PP + 32 * wave + r] = acc[e] * a.scale + bias;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) Ps[acc_row(e, h) * PP + 32 * wave + r] = acc[e] * a.scale;
+        }
     }
     __syncthreads();
     LG_ATL(2);
 
     // softmax of each row: 8 threads per row, float4 columns sub, sub + 8, ... held in registers between the three passes;
     // exp(x - max) * (1 / sum) (autograd/ops.py:62-66)
-    {
+    if constexpr (TAIL) {
+        // the same three passes in the same order over the keys that exist: a key >= S is no part of the max or the sum, its
+        // column of the LDS tile becomes 0 (it is an MFMA operand of the context) and nothing of it is stored
+        const int row = tid >> 3, sub = tid & 7;
+        float* pr = Ps + row * PP;
+        af32x4 t[4];
+        float m = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int c = sub * 4 + 32 * i;
+            if (c < Sp) {
+                t[i] = *reinterpret_cast<const af32x4*>(pr + c);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (c + e < S) m = (t[i][e] > m || t[i][e] != t[i][e]) ? t[i][e] : m;
+            }
+        }
+#pragma unroll
+        for (int off = 1; off < 8; off <<= 1) { const float o = __shfl_xor(m, off, 64); m = (o > m || o != o) ? o : m; }
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int c = sub * 4 + 32 * i;
+            if (c < Sp) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (c + e < S) { t[i][e] = expf(t[i][e] + (-m)); s += t[i][e]; }
+                    else t[i][e] = 0.f;
+                }
+            }
+        }
+#pragma unroll
+        for (int off = 1; off < 8; off <<= 1) s += __shfl_xor(s, off, 64);
+        const float inv = 1.0f / s;
+        const bool row_exists = q0 + row < S;
+        float* pg = a.p + ((int64_t(b) * a.heads + head) * S + q0 + row) * S;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int c = sub * 4 + 32 * i;
+            if (c < Sp) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) t[i][e] *= inv;
+                *reinterpret_cast<af32x4*>(pr + c) = t[i];
+                if (row_exists) {
+                    if ((S & 3) == 0) {
+                        if (c < S) *reinterpret_cast<af32x4*>(pg + c) = t[i];
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (c + e < S) pg[c + e] = t[i][e];
+                    }
+                }
+            }
+        }
+    } else {
         const int row = tid >> 3, sub = tid & 7;
         float* pr = Ps + row * PP;
         af32x4 t[4];
@@ -141,7 +249,7 @@ __global__ void __launch_bounds__(256) attn_fwd(AttnArgs a) {
     // context = P @ V: D / 32 column tiles, the keys split over the remaining waves, partial sums folded in wave order
     constexpr int NT = D / 32, KP = 4 / NT;
     const int n = wave % NT, kp = wave / NT;
-    const int kspan = S / KP;
+    const int kspan = Sp / KP;
     af32x16 acc = zero16();
     wave_mma<true, false>(acc, Ps + kp * kspan, PP, Vs + kp * kspan * PV + 32 * n, PV, kspan, r, h);
     LG_ATL(4);
@@ -158,7 +266,8 @@ __global__ void __launch_bounds__(256) attn_fwd(AttnArgs a) {
         }
         float* og = a.o + int64_t(b) * a.sbo + int64_t(q0) * a.ldo + head * D + 32 * n + r;
 #pragma unroll
-        for (int e = 0; e < 16; ++e) og[int64_t(acc_row(e, h)) * a.ldo] = acc[e];
+        for (int e = 0; e < 16; ++e)
+            if (!TAIL || q0 + acc_row(e, h) < S) og[int64_t(acc_row(e, h)) * a.ldo] = acc[e];
     }
     LG_ATL(6);
 }
@@ -196,10 +305,33 @@ __device__ __forceinline__ void load_probs(ProbRows<PASSES>& pr, const float* y,
     }
 }
 
+// TAIL form: rows of pitch S are not 16-byte aligned, and a key >= S has no probability: scalars, 0 where there is none (so the
+// row pass below adds nothing for it and its dS is 0).  A row >= rows takes row 0's values like above: with its dP = 0 the
+// shift it forms is 0 / 1, not 0 / 0.
+template <int PASSES>
+__device__ __forceinline__ void load_probs_tail(ProbRows<PASSES>& pr, const float* y, int S, int rows) {
+    const int sub = threadIdx.x & 7;
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p) {
+        const int row0 = (threadIdx.x >> 3) + 32 * p, row = row0 < rows ? row0 : 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int c0 = sub * 4 + 32 * i + e, c = c0 < S ? c0 : 0;
+                const float t = y[int64_t(row) * S + c];
+                pr.y[p][i][e] = c0 < S ? t : 0.f;
+            }
+        }
+    }
+}
+
 // dS = float(double(y) * (double(g) - shift)) * scale, shift = sum(g * y) / sum(y) over the row in double, in place, for 32 rows of
 // dP held in LDS (pitch pp) against their probabilities y (load_probs); 8 threads per row.  The shift of every row is also
 // stored to `shift_out` (write-through: workgroups on other XCDs read it).
-__device__ __forceinline__ void softmax_bwd_rows(float* dp, int pp, const ProbRows<1>& pr, int S, float scale, double* shift_out) {
+// TAIL: only the first `rows` of the 32 rows exist; the others are computed on zeros and publish nothing.
+template <bool TAIL>
+__device__ __forceinline__ void softmax_bwd_rows(float* dp, int pp, const ProbRows<1>& pr, int S, float scale, double* shift_out, int rows) {
     const int sub = threadIdx.x & 7, row = threadIdx.x >> 3;
     float* gr = dp + row * pp;
     af32x4 g4[4];
@@ -216,7 +348,7 @@ __device__ __forceinline__ void softmax_bwd_rows(float* dp, int pp, const ProbRo
 #pragma unroll
     for (int off = 1; off < 8; off <<= 1) { dot += __shfl_xor(dot, off, 64); norm += __shfl_xor(norm, off, 64); }
     const double shift = dot / norm;
-    if (sub == 0) __hip_atomic_store(shift_out + row, shift, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (sub == 0 && (!TAIL || row < rows)) __hip_atomic_store(shift_out + row, shift, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int c = sub * 4 + 32 * i;
@@ -236,19 +368,22 @@ constexpr int attn_bwd_lds_floats(int S) {
     return query > key ? query : key;
 }
 
-template <int D>
+template <int D, bool TAIL = false>
 __global__ void __launch_bounds__(256) attn_bwd(AttnBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int S = a.S;
+    const int S = a.S;                               // the sequence
+    const int Sp = TAIL ? round32(S) : S;            // what the tiles, the shift slab and the hand-off counter cover
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     // the query-role workgroups of the whole grid are dispatched before any key-role one (role in the slowest grid index): a
     // key-role workgroup that waits, waits for workgroups that are already running and wait for nothing
     const int role = int(blockIdx.z) >= a.batch ? 1 : 0;
     const int blk = blockIdx.x, head = blockIdx.y, b = int(blockIdx.z) - role * a.batch;
-    const int j0 = blk * 32, nblk = S / 32;
+    const int j0 = blk * 32, nblk = Sp / 32;
+    constexpr int kBlock = 32;
+    const int brows = TAIL ? (S - j0 < kBlock ? S - j0 : kBlock) : kBlock;        // rows of this block that exist
     const int bh = b * a.heads + head;
     const float* pg = a.p + int64_t(bh) * S * S;
-    double* shifts = a.shift + int64_t(bh) * S;
+    double* shifts = a.shift + int64_t(bh) * Sp;
     int* flags = a.flags + 2 * bh;
     constexpr int NT = D / 32;
     constexpr int NB = 32 * (D / 4) / 256 > 0 ? 32 * (D / 4) / 256 : 1, NA = 128 * (D / 4) / 256;       // float4 per thread: 32 rows / all rows
@@ -257,26 +392,33 @@ __global__ void __launch_bounds__(256) attn_bwd(AttnBwdArgs a) {
     if (role == 0) {
         // ---- query role: dQ of queries [j0, j0 + 32), and the shift of their rows for the key role ------------------
         constexpr int PG = D + 4, PVK = D + 4, PK = D + 8;
-        const int PP = S + 4;
+        const int PP = Sp + 4;
         float* Gs = lds;                 // dO rows of the block          32 x PG
-        float* Vs = Gs + 32 * PG;        // V, K-contiguous B of dP       S x PVK
-        float* Ks = Vs + S * PVK;        // K, N-contiguous B of dQ       S x PK
-        float* Ss = Ks + S * PK;         // dP, then dS                   32 x PP
+        float* Vs = Gs + 32 * PG;        // V, K-contiguous B of dP       Sp x PVK
+        float* Ks = Vs + Sp * PVK;       // K, N-contiguous B of dQ       Sp x PK
+        float* Ss = Ks + Sp * PK;        // dP, then dS                   32 x PP
         float* Red = Ss + 32 * PP;
         {
             af32x4 rg[NB], rv[NA], rk[NA];
-            load_rows<D, NB>(rg, a.g + int64_t(b) * a.sbg + int64_t(j0) * a.ldg + head * D, a.ldg, 32);
+            load_rows<D, NB>(rg, a.g + int64_t(b) * a.sbg + int64_t(j0) * a.ldg + head * D, a.ldg, brows);
             load_rows<D, NA>(rv, a.v + int64_t(b) * a.sbv + head * D, a.ldv, S);
             load_rows<D, NA>(rk, a.k + int64_t(b) * a.sbk + head * D, a.ldk, S);
-            store_rows<D, NB>(rg, Gs, PG, 32);
-            store_rows<D, NA>(rv, Vs, PVK, S);
-            store_rows<D, NA>(rk, Ks, PK, S);
+            if constexpr (!TAIL) {
+                store_rows<D, NB>(rg, Gs, PG, 32);
+                store_rows<D, NA>(rv, Vs, PVK, S);
+                store_rows<D, NA>(rk, Ks, PK, S);
+            } else {
+                store_rows_padded<D, NB>(rg, Gs, PG, brows, 32);
+                store_rows_padded<D, NA>(rv, Vs, PVK, S, Sp);
+                store_rows_padded<D, NA>(rk, Ks, PK, S, Sp);
+            }
         }
         ProbRows<1> probs;
-        load_probs<1>(probs, pg + int64_t(j0) * S, S, 32);
+        if constexpr (TAIL) load_probs_tail<1>(probs, pg + int64_t(j0) * S, S, brows);
+        else                load_probs<1>(probs, pg + int64_t(j0) * S, S, 32);
         __syncthreads();
         LG_ATL(1);
-        if (32 * wave < S) {
+        if (32 * wave < Sp) {
             af32x16 acc = zero16();
             wave_mma<true, true>(acc, Gs, PG, Vs + 32 * wave * PVK, PVK, D, r, h);
 #pragma unroll
@@ -284,14 +426,15 @@ __global__ void __launch_bounds__(256) attn_bwd(AttnBwdArgs a) {
         }
         __syncthreads();
         LG_ATL(2);
-        softmax_bwd_rows(Ss, PP, probs, S, a.scale, shifts + j0);
+        // (TAIL: over the Sp columns of the tile - a key >= S has probability 0 and dP 0, so it adds nothing and its dS is 0)
+        softmax_bwd_rows<TAIL>(Ss, PP, probs, Sp, a.scale, shifts + j0, brows);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the shifts have left this CU
         __syncthreads();
         if (tid == 0) __hip_atomic_fetch_add(flags, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // 32 more rows are published
         LG_ATL(3);
         constexpr int KP = 4 / NT;
         const int n = wave % NT, kp = wave / NT;
-        const int kspan = S / KP;
+        const int kspan = Sp / KP;
         af32x16 acc = zero16();
         wave_mma<true, false>(acc, Ss + kp * kspan, PP, Ks + kp * kspan * PK + 32 * n, PK, kspan, r, h);
         LG_ATL(4);
@@ -308,7 +451,8 @@ __global__ void __launch_bounds__(256) attn_bwd(AttnBwdArgs a) {
             }
             float* dst = a.dq + int64_t(b) * a.sbdq + int64_t(j0) * a.lddq + head * D + 32 * n + r;
 #pragma unroll
-            for (int e = 0; e < 16; ++e) dst[int64_t(acc_row(e, h)) * a.lddq] = acc[e];
+            for (int e = 0; e < 16; ++e)
+                if (!TAIL || acc_row(e, h) < brows) dst[int64_t(acc_row(e, h)) * a.lddq] = acc[e];
         }
         LG_ATL(6);
         return;
@@ -321,27 +465,43 @@ __global__ void __launch_bounds__(256) attn_bwd(AttnBwdArgs a) {
     // between the roles (the same MFMA sequence over the same operands), so dS does too.
     constexpr int PG = D + 8;            // dO: K-contiguous A of dP (two-way conflicts there) and N-contiguous B of dV
     constexpr int PVK = D + 4, PQN = D + 8, PC = 40;
-    float* Gs = lds;                     // dO, all queries               S x PG
-    float* Qs = Gs + S * PG;             // Q, N-contiguous B of dK       S x PQN
-    float* Vj = Qs + S * PQN;            // V rows of the block           32 x PVK
-    float* Pc = Vj + 32 * PVK;           // P[:, block]                   S x PC
-    float* Dc = Pc + S * PC;             // dS[:, block]                  S x PC
-    float* Red = Dc + S * PC;
+    float* Gs = lds;                     // dO, all queries               Sp x PG
+    float* Qs = Gs + Sp * PG;            // Q, N-contiguous B of dK       Sp x PQN
+    float* Vj = Qs + Sp * PQN;           // V rows of the block           32 x PVK
+    float* Pc = Vj + 32 * PVK;           // P[:, block]                   Sp x PC
+    float* Dc = Pc + Sp * PC;            // dS[:, block]                  Sp x PC
+    float* Red = Dc + Sp * PC;
     {
         af32x4 rg[NA], rq[NA], rv[NB];
         load_rows<D, NA>(rg, a.g + int64_t(b) * a.sbg + head * D, a.ldg, S);
         load_rows<D, NA>(rq, a.q + int64_t(b) * a.sbq + head * D, a.ldq, S);
-        load_rows<D, NB>(rv, a.v + int64_t(b) * a.sbv + int64_t(j0) * a.ldv + head * D, a.ldv, 32);
-        store_rows<D, NA>(rg, Gs, PG, S);
-        store_rows<D, NA>(rq, Qs, PQN, S);
-        store_rows<D, NB>(rv, Vj, PVK, 32);
+        load_rows<D, NB>(rv, a.v + int64_t(b) * a.sbv + int64_t(j0) * a.ldv + head * D, a.ldv, brows);
+        if constexpr (!TAIL) {
+            store_rows<D, NA>(rg, Gs, PG, S);
+            store_rows<D, NA>(rq, Qs, PQN, S);
+            store_rows<D, NB>(rv, Vj, PVK, 32);
+        } else {
+            store_rows_padded<D, NA>(rg, Gs, PG, S, Sp);
+            store_rows_padded<D, NA>(rq, Qs, PQN, S, Sp);
+            store_rows_padded<D, NB>(rv, Vj, PVK, brows, 32);
+        }
     }
-    const bool active = 32 * wave < S;
+    const bool active = 32 * wave < Sp;
     // the probabilities that meet this wave's block of dP: element e of the accumulator is (row 32 w + acc_row(e, h), key j0 + r)
     float y[16];
     if (active) {
 #pragma unroll
-        for (int e = 0; e < 16; ++e) y[e] = pg[int64_t(32 * wave + acc_row(e, h)) * S + j0 + r];
+        for (int e = 0; e < 16; ++e) {
+            if constexpr (TAIL) {
+                // a (row, key) pair past the sequence has no probability: 0, so its dS and its share of dK / dV are 0
+                const int row = 32 * wave + acc_row(e, h);
+                const bool in = row < S && r < brows;
+                const float t = pg[in ? int64_t(row) * S + j0 + r : 0];
+                y[e] = in ? t : 0.f;
+            } else {
+                y[e] = pg[int64_t(32 * wave + acc_row(e, h)) * S + j0 + r];
+            }
+        }
     }
     __syncthreads();
     LG_ATL(1);
@@ -366,7 +526,10 @@ __global__ void __launch_bounds__(256) attn_bwd(AttnBwdArgs a) {
     if (active) {
         double sh[16];
 #pragma unroll
-        for (int e = 0; e < 16; ++e) sh[e] = __hip_atomic_load(shifts + 32 * wave + acc_row(e, h), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int e = 0; e < 16; ++e) {
+            sh[e] = __hip_atomic_load(shifts + 32 * wave + acc_row(e, h), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if constexpr (TAIL) sh[e] = 32 * wave + acc_row(e, h) < S ? sh[e] : 0.0;        // no row, nothing published: not read as a number
+        }
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int row = 32 * wave + acc_row(e, h);
@@ -389,7 +552,7 @@ __global__ void __launch_bounds__(256) attn_bwd(AttnBwdArgs a) {
     const int tile = wave % TILES, kp = wave / TILES;
     const bool is_dk = tile >= NT;
     const int n = tile % NT;
-    const int kspan = S / KP;
+    const int kspan = Sp / KP;
     af32x16 acc = zero16();
     if (is_dk) wave_mma<false, false>(acc, Dc + kp * kspan * PC, PC, Qs + kp * kspan * PQN + 32 * n, PQN, kspan, r, h);
     else       wave_mma<false, false>(acc, Pc + kp * kspan * PC, PC, Gs + kp * kspan * PG + 32 * n, PG, kspan, r, h);
@@ -410,7 +573,8 @@ __global__ void __launch_bounds__(256) attn_bwd(AttnBwdArgs a) {
                        : a.dv + int64_t(b) * a.sbdv + int64_t(j0) * a.lddv + head * D + 32 * n + r;
     const int64_t ldd = is_dk ? a.lddk : a.lddv;
 #pragma unroll
-    for (int e = 0; e < 16; ++e) dst[int64_t(acc_row(e, h)) * ldd] = acc[e];
+    for (int e = 0; e < 16; ++e)
+        if (!TAIL || acc_row(e, h) < brows) dst[int64_t(acc_row(e, h)) * ldd] = acc[e];
     LG_ATL(6);
 }
 
@@ -516,6 +680,92 @@ extern "C" int lg_attention_bwd_f32(const float* q, int64_t ldq, int64_t sbq, co
         int rc = allow_lds(&attn_bwd<32>, bytes);
         if (rc != LG_OK) return rc;
         hipLaunchKernelGGL(attn_bwd<32>, grid, dim3(256), bytes, rt().stream, a);
+    }
+    LG_CHECK_LAUNCH();
+    return lg_free(shift);          // stream-ordered: the block is only reused by later launches
+}
+
+extern "C" int lg_attention_masked_supported(int64_t S, int64_t D) {
+    return (D == 64 || D == 32) && S >= 1 && S <= 128;
+}
+
+extern "C" int lg_attention_masked_fwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
+                                           const float* v, int64_t ldv, int64_t sbv, float* o, int64_t ldo, int64_t sbo, float* p,
+                                           int64_t batch, int64_t heads, int64_t S, int64_t D, float scale,
+                                           const float* mask, int64_t sbm) {
+    LG_REQUIRE_INIT();
+    LG_ARG(lg_attention_masked_supported(S, D), "lg_attention_masked_fwd_f32: S = %lld (1..128), D = %lld (32 or 64) unsupported",
+           (long long)S, (long long)D);
+    LG_ARG(batch >= 0 && heads >= 1 && batch <= 65535 && heads <= 65535, "lg_attention_masked_fwd_f32: bad batch / heads");
+    if (batch == 0) return LG_OK;
+    LG_ARG(ok_operand(q, ldq, sbq) && ok_operand(k, ldk, sbk) && ok_operand(v, ldv, sbv) && ok_operand(o, ldo, sbo) && p && aligned16(p),
+           "lg_attention_masked_fwd_f32: operands must be 16-byte aligned with pitches that are multiples of 4");
+    LG_ARG(ldq >= heads * D && ldk >= heads * D && ldv >= heads * D && ldo >= heads * D, "lg_attention_masked_fwd_f32: row pitch below heads * D");
+    LG_ARG(!mask || sbm == 0 || sbm >= S, "lg_attention_masked_fwd_f32: mask batch pitch %lld is neither 0 (one row for the batch) nor >= S",
+           (long long)sbm);
+    const int Sp = round32(int(S));
+    AttnTailArgs a{{
+#ifdef LG_GEMM_TIMELINE
+        timeline_buffer(int(Sp / 32 * heads * batch)),
+#endif
+        q, k, v, ldq, sbq, ldk, sbk, ldv, sbv, o, ldo, sbo, p, int(S), int(heads), scale}, mask, sbm};
+    const dim3 grid(unsigned(Sp / 32), unsigned(heads), unsigned(batch));
+    if (D == 64) {
+        const size_t bytes = size_t(attn_fwd_tail_lds_floats<64>(int(S))) * 4;
+        int rc = allow_lds(&attn_fwd<64, true>, bytes);
+        if (rc != LG_OK) return rc;
+        hipLaunchKernelGGL((attn_fwd<64, true>), grid, dim3(256), bytes, rt().stream, a);
+    } else {
+        const size_t bytes = size_t(attn_fwd_tail_lds_floats<32>(int(S))) * 4;
+        int rc = allow_lds(&attn_fwd<32, true>, bytes);
+        if (rc != LG_OK) return rc;
+        hipLaunchKernelGGL((attn_fwd<32, true>), grid, dim3(256), bytes, rt().stream, a);
+    }
+    LG_CHECK_LAUNCH();
+    return LG_OK;
+}
+
+extern "C" int lg_attention_masked_bwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
+                                           const float* v, int64_t ldv, int64_t sbv, const float* g, int64_t ldg, int64_t sbg,
+                                           const float* p, float* dq, int64_t lddq, int64_t sbdq, float* dk, int64_t lddk, int64_t sbdk,
+                                           float* dv, int64_t lddv, int64_t sbdv, int64_t batch, int64_t heads, int64_t S, int64_t D,
+                                           float scale) {
+    LG_REQUIRE_INIT();
+    LG_ARG(lg_attention_masked_supported(S, D), "lg_attention_masked_bwd_f32: S = %lld (1..128), D = %lld (32 or 64) unsupported",
+           (long long)S, (long long)D);
+    LG_ARG(batch >= 0 && heads >= 1 && batch <= 65535 && heads <= 65535, "lg_attention_masked_bwd_f32: bad batch / heads");
+    if (batch == 0) return LG_OK;
+    LG_ARG(ok_operand(q, ldq, sbq) && ok_operand(k, ldk, sbk) && ok_operand(v, ldv, sbv) && ok_operand(g, ldg, sbg) &&
+               ok_operand(dq, lddq, sbdq) && ok_operand(dk, lddk, sbdk) && ok_operand(dv, lddv, sbdv) && p && aligned16(p),
+           "lg_attention_masked_bwd_f32: operands must be 16-byte aligned with pitches that are multiples of 4");
+    const int64_t w = heads * D;
+    LG_ARG(ldq >= w && ldk >= w && ldv >= w && ldg >= w && lddq >= w && lddk >= w && lddv >= w, "lg_attention_masked_bwd_f32: row pitch below heads * D");
+    LG_ARG(batch * heads <= rt().n_attn_pairs && 2 * batch <= 65535, "lg_attention_masked_bwd_f32: more than %d (batch, head) pairs in one launch",
+           rt().n_attn_pairs);
+    const int Sp = round32(int(S));
+    int* flags = rt().attn_flags;
+    double* shift = nullptr;
+    {
+        const int mrc = lg_malloc(reinterpret_cast<void**>(&shift), size_t(batch * heads * Sp) * sizeof(double));
+        if (mrc != LG_OK) return mrc;
+    }
+    AttnBwdArgs a{
+#ifdef LG_GEMM_TIMELINE
+        timeline_buffer(int(2 * (Sp / 32) * heads * batch)),
+#endif
+        q, k, v, g, ldq, sbq, ldk, sbk, ldv, sbv, ldg, sbg, p, dq, dk, dv, lddq, sbdq, lddk, sbdk, lddv, sbdv, int(S), int(heads), int(batch), scale,
+        shift, flags, rt().status_dev};
+    const dim3 grid(unsigned(Sp / 32), unsigned(heads), unsigned(2 * batch));
+    if (D == 64) {
+        const size_t bytes = size_t(attn_bwd_lds_floats<64>(Sp)) * 4;
+        int rc = allow_lds(&attn_bwd<64, true>, bytes);
+        if (rc != LG_OK) return rc;
+        hipLaunchKernelGGL((attn_bwd<64, true>), grid, dim3(256), bytes, rt().stream, a);
+    } else {
+        const size_t bytes = size_t(attn_bwd_lds_floats<32>(Sp)) * 4;
+        int rc = allow_lds(&attn_bwd<32, true>, bytes);
+        if (rc != LG_OK) return rc;
+        hipLaunchKernelGGL((attn_bwd<32, true>), grid, dim3(256), bytes, rt().stream, a);
     }
     LG_CHECK_LAUNCH();
     return lg_free(shift);          // stream-ordered: the block is only reused by later launches
