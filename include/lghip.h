@@ -571,6 +571,16 @@ int lg_gather_sum3_rows_f32(const float* t0, const void* ids0, int64_t n0, int64
                             int id_itemsize, float* out, int64_t n_out, int64_t row_len);
 int lg_scatter_add_rows_f32(const float* grad_out, const void* ids, int id_itemsize, float* grad_table,
                             int64_t n_ids, int64_t row_len, int64_t table_rows);
+/* What the most recent call of the calling thread to lg_softmax_scaled_f32 / lg_softmax_scaled_bwd_f32 (and the unscaled forms,
+ * which call them), lg_layernorm_f32, lg_layernorm_bwd_f32, lg_layernorm_param_grads_f32, lg_scatter_add_rows_f32 or
+ * lg_gather_rows_f32 decided: host bookkeeping for tests, no device work.
+ *   out = {kernel, a, b, queued}
+ * kernel: 0 = softmax forward, 1 = softmax backward, 2 = LayerNorm forward, 3 = LayerNorm backward, 4 = LayerNorm parameter
+ * gradients, 5 = scatter-add, 6 = gather, -1 = nothing launched or queued (an empty or refused call: the other fields are 0);
+ * a: softmax forward - floats per lane held in registers (2, 8, 32; 0 = the loop that re-reads the row); parameter gradients -
+ * the row splits, with b = the rows per split; scatter-add - 0 = queued, 1 = the chunked launch, 2 = the atomic kernel;
+ * queued: 1 when the call only queued its work inside an open lg_gemm_group_begin bracket. */
+int lg_rowwise_last_plan(int32_t out[4]);
 
 /* loss.cross_entropy (loss.py:14-24) for dense fp32 logits [rows, cols] and integer labels [rows] (int16/32/64):
  *   nll[r] = -log(softmax(logits[r])[label[r]]);  dlogits[r][c] = (softmax(logits[r])[c] - [c == label[r]]) / rows

@@ -145,6 +145,7 @@ PROTOTYPES = {
     "lg_gather_rows_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int64, c_int64]),
     "lg_gather_sum3_rows_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64] * 3 + [c_int, c_void_p, c_int64, c_int64]),
     "lg_scatter_add_rows_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int64, c_int64]),
+    "lg_rowwise_last_plan": (c_int, [POINTER(ctypes.c_int32)]),
 }
 
 # include/lghip_p2p.h: the peer-window gradient exchange, exported by liblghip.so itself (no RCCL)

@@ -440,6 +440,16 @@ __global__ void __launch_bounds__(256) param_grads_tail_group(TailGroup grp) {
 
 using namespace lg;
 
+// lg_rowwise_last_plan: what the most recent softmax / LayerNorm / gather / scatter-add entry point called by this thread decided -
+// host bookkeeping written where the launch or the queueing is decided, so that a test can see which path its shape reached
+// after the thresholds below move.  {kernel, a, b, queued}; a call that launches and queues nothing leaves kernel = -1.
+enum { RW_NONE = -1, RW_SOFTMAX_FWD = 0, RW_SOFTMAX_BWD = 1, RW_LAYERNORM_FWD = 2, RW_LAYERNORM_BWD = 3, RW_PARAM_GRADS = 4,
+       RW_SCATTER_ADD = 5, RW_GATHER = 6 };
+static thread_local int32_t g_rw_plan[4] = {RW_NONE, 0, 0, 0};
+static void note_rowwise(int kernel, int64_t a = 0, int64_t b = 0, int queued = 0) {
+    g_rw_plan[0] = kernel; g_rw_plan[1] = int32_t(a); g_rw_plan[2] = int32_t(b); g_rw_plan[3] = queued;
+}
+
 namespace lg {
 struct LnGroupState {
     int        count = 0;          // LayerNorm entries queued
@@ -508,16 +518,17 @@ int ln_group_flush_pending() {
 }  // namespace lg
 
 extern "C" int lg_softmax_scaled_f32(const float* x, float* y, int64_t rows, int64_t cols, float scale) {
+    note_rowwise(RW_NONE);
     LG_REQUIRE_INIT();
     LG_ARG(rows >= 0 && cols >= 1, "lg_softmax_f32: bad shape (%lld, %lld)", (long long)rows, (long long)cols);
     if (rows == 0) return LG_OK;
     LG_ARG(x && y, "lg_softmax_f32: NULL pointer");
     const unsigned blocks = unsigned((rows + 3) / 4);
     hipStream_t s = rt().stream;
-    if (cols <= 128)       hipLaunchKernelGGL(softmax_fwd<2>, dim3(blocks), dim3(256), 0, s, x, y, rows, cols, scale);
-    else if (cols <= 512)  hipLaunchKernelGGL(softmax_fwd<8>, dim3(blocks), dim3(256), 0, s, x, y, rows, cols, scale);
-    else if (cols <= 2048) hipLaunchKernelGGL(softmax_fwd<kRowRegs>, dim3(blocks), dim3(256), 0, s, x, y, rows, cols, scale);
-    else                   hipLaunchKernelGGL(softmax_fwd<0>, dim3(blocks), dim3(256), 0, s, x, y, rows, cols, scale);
+    if (cols <= 128)       { note_rowwise(RW_SOFTMAX_FWD, 2);        hipLaunchKernelGGL(softmax_fwd<2>, dim3(blocks), dim3(256), 0, s, x, y, rows, cols, scale); }
+    else if (cols <= 512)  { note_rowwise(RW_SOFTMAX_FWD, 8);        hipLaunchKernelGGL(softmax_fwd<8>, dim3(blocks), dim3(256), 0, s, x, y, rows, cols, scale); }
+    else if (cols <= 2048) { note_rowwise(RW_SOFTMAX_FWD, kRowRegs); hipLaunchKernelGGL(softmax_fwd<kRowRegs>, dim3(blocks), dim3(256), 0, s, x, y, rows, cols, scale); }
+    else                   { note_rowwise(RW_SOFTMAX_FWD, 0);        hipLaunchKernelGGL(softmax_fwd<0>, dim3(blocks), dim3(256), 0, s, x, y, rows, cols, scale); }
     LG_CHECK_LAUNCH();
     return LG_OK;
 }
@@ -527,10 +538,12 @@ extern "C" int lg_softmax_f32(const float* x, float* y, int64_t rows, int64_t co
 }
 
 extern "C" int lg_softmax_scaled_bwd_f32(const float* y, const float* g, float* dx, int64_t rows, int64_t cols, float scale) {
+    note_rowwise(RW_NONE);
     LG_REQUIRE_INIT();
     LG_ARG(rows >= 0 && cols >= 1, "lg_softmax_bwd_f32: bad shape");
     if (rows == 0) return LG_OK;
     LG_ARG(y && g && dx, "lg_softmax_bwd_f32: NULL pointer");
+    note_rowwise(RW_SOFTMAX_BWD);
     hipLaunchKernelGGL(softmax_bwd, dim3(unsigned((rows + 3) / 4)), dim3(256), 0, rt().stream, y, g, dx, rows, cols, scale);
     LG_CHECK_LAUNCH();
     return LG_OK;
@@ -542,10 +555,12 @@ extern "C" int lg_softmax_bwd_f32(const float* y, const float* g, float* dx, int
 
 extern "C" int lg_layernorm_f32(const float* x, const float* w, const float* b, float* y, float* xhat, float* rstd,
                                 int64_t rows, int64_t cols, double eps) {
+    note_rowwise(RW_NONE);
     LG_REQUIRE_INIT();
     LG_ARG(rows >= 0 && cols >= 1, "lg_layernorm_f32: bad shape");
     if (rows == 0) return LG_OK;
     LG_ARG(x && w && b && y && xhat && rstd, "lg_layernorm_f32: NULL pointer");
+    note_rowwise(RW_LAYERNORM_FWD);
     hipLaunchKernelGGL(layernorm_fwd, dim3(unsigned((rows + 3) / 4)), dim3(256), 0, rt().stream, x, w, b, y, xhat, rstd, rows, cols,
                        float(eps), float(1.0 / double(cols)));
     LG_CHECK_LAUNCH();
@@ -554,10 +569,12 @@ extern "C" int lg_layernorm_f32(const float* x, const float* w, const float* b, 
 
 extern "C" int lg_layernorm_bwd_f32(const float* g, const float* w, const float* xhat, const float* rstd, float* dx,
                                     int64_t rows, int64_t cols) {
+    note_rowwise(RW_NONE);
     LG_REQUIRE_INIT();
     LG_ARG(rows >= 0 && cols >= 1, "lg_layernorm_bwd_f32: bad shape");
     if (rows == 0) return LG_OK;
     LG_ARG(g && w && xhat && rstd && dx, "lg_layernorm_bwd_f32: NULL pointer");
+    note_rowwise(RW_LAYERNORM_BWD);
     hipLaunchKernelGGL(layernorm_bwd, dim3(unsigned((rows + 3) / 4)), dim3(256), 0, rt().stream, g, w, xhat, rstd, dx, rows, cols,
                        float(1.0 / double(cols)));
     LG_CHECK_LAUNCH();
@@ -566,12 +583,14 @@ extern "C" int lg_layernorm_bwd_f32(const float* g, const float* w, const float*
 
 extern "C" int lg_gather_rows_f32(const float* table, const void* ids, int id_itemsize, float* out, int64_t n_ids, int64_t row_len,
                                   int64_t table_rows) {
+    note_rowwise(RW_NONE);
     LG_REQUIRE_INIT();
     LG_ARG(id_itemsize == 4 || id_itemsize == 8, "lg_gather_rows_f32: ids must be int32 or int64");
     LG_ARG(n_ids >= 0 && row_len >= 0 && table_rows >= 0, "lg_gather_rows_f32: bad shape");
     if (n_ids == 0 || row_len == 0) return LG_OK;
     LG_ARG(table && ids && out, "lg_gather_rows_f32: NULL pointer");
     const unsigned grid = stream_grid(n_ids * row_len);
+    note_rowwise(RW_GATHER);
     if (id_itemsize == 4)
         hipLaunchKernelGGL(gather_rows<int32_t>, dim3(grid), dim3(256), 0, rt().stream, table, static_cast<const int32_t*>(ids), out, n_ids, row_len, table_rows, rt().status_dev);
     else
@@ -601,6 +620,7 @@ extern "C" int lg_gather_sum3_rows_f32(const float* t0, const void* ids0, int64_
 
 extern "C" int lg_scatter_add_rows_f32(const float* grad_out, const void* ids, int id_itemsize, float* grad_table, int64_t n_ids,
                                        int64_t row_len, int64_t table_rows) {
+    note_rowwise(RW_NONE);
     LG_REQUIRE_INIT();
     LG_ARG(id_itemsize == 4 || id_itemsize == 8, "lg_scatter_add_rows_f32: ids must be int32 or int64");
     LG_ARG(n_ids >= 0 && row_len >= 0 && table_rows >= 0, "lg_scatter_add_rows_f32: bad shape");
@@ -623,10 +643,12 @@ extern "C" int lg_scatter_add_rows_f32(const float* grad_out, const void* ids, i
         ScatterJob& j = S.grp.sc[S.n_scatter++];
         j.grad_out = grad_out; j.ids = ids; j.table = grad_table;
         j.n_ids = n_ids; j.row_len = row_len; j.table_rows = table_rows; j.id_itemsize = id_itemsize;
+        note_rowwise(RW_SCATTER_ADD, 0, 0, 1);
         return LG_OK;
     }
     if (n_ids <= 4096 && !(owner_env && atoi(owner_env) == 0)) {
         // the ids of one batch: chunks of 32 positions per id are summed in position order, few or no atomics (see the kernel)
+        note_rowwise(RW_SCATTER_ADD, 1);
         if (id_itemsize == 4)
             hipLaunchKernelGGL(scatter_add_rows_chunked<int32_t>, dim3(unsigned(n_ids)), dim3(256), 0, rt().stream, grad_out, static_cast<const int32_t*>(ids), grad_table, n_ids, row_len, table_rows, rt().status_dev);
         else
@@ -635,6 +657,7 @@ extern "C" int lg_scatter_add_rows_f32(const float* grad_out, const void* ids, i
         return LG_OK;
     }
     const unsigned grid = stream_grid(n_ids * row_len);
+    note_rowwise(RW_SCATTER_ADD, 2);
     if (id_itemsize == 4)
         hipLaunchKernelGGL(scatter_add_rows<int32_t>, dim3(grid), dim3(256), 0, rt().stream, grad_out, static_cast<const int32_t*>(ids), grad_table, n_ids, row_len, table_rows, rt().status_dev);
     else
@@ -708,6 +731,7 @@ extern "C" int lg_cross_entropy_mean_f32(const float* logits, const void* labels
 
 extern "C" int lg_layernorm_param_grads_f32(const float* g, const float* xhat, float* dw, float* db, int64_t rows, int64_t cols,
                                             int dw_accumulate, int db_accumulate) {
+    note_rowwise(RW_NONE);
     LG_REQUIRE_INIT();
     LG_ARG(rows >= 0 && cols >= 1, "lg_layernorm_param_grads_f32: bad shape");
     LG_ARG(g && xhat && dw && db, "lg_layernorm_param_grads_f32: NULL pointer");
@@ -752,10 +776,18 @@ extern "C" int lg_layernorm_param_grads_f32(const float* g, const float* xhat, f
         a.tickets = rt().gemm_tickets + rt().n_gemm_tickets / 2 + S.tickets;
         S.tickets += blocks_x;
         S.grp.ln.e[S.count++] = a;
+        note_rowwise(RW_PARAM_GRADS, splits, chunk, 1);
         return LG_OK;
     }
     a.tickets = rt().gemm_tickets + rt().n_gemm_tickets / 2;
+    note_rowwise(RW_PARAM_GRADS, splits, chunk);
     hipLaunchKernelGGL(layernorm_param_grads, dim3(unsigned(blocks_x), unsigned(splits)), dim3(256), 0, rt().stream, a);
     LG_CHECK_LAUNCH();
     return splits > 1 ? lg_free(a.partial) : LG_OK;
+}
+
+extern "C" int lg_rowwise_last_plan(int32_t out[4]) {
+    LG_ARG(out != nullptr, "lg_rowwise_last_plan: NULL pointer");
+    for (int k = 0; k < 4; ++k) out[k] = g_rw_plan[k];
+    return LG_OK;
 }
