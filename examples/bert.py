@@ -87,10 +87,12 @@ class BertSelfAttention(nn.Module):
         # a padded batch (a mask) or a length the plain kernels do not take (no multiple of 32) goes to the backend's masked forms,
         # if it has them and the mask is what they read: a (b, s) or (1, s) float32 constant
         masked = attention_mask is not None or s % 32 != 0
-        if masked:
-            fused = hasattr(hidden, "masked_attention") and (attention_mask is None or (
+        # beyond 128 positions (up to 512) the backend's long forms take over, with or without a mask, under the same conditions
+        long = s > 128
+        if masked or long:
+            fused = hasattr(hidden, "long_attention" if long else "masked_attention") and (attention_mask is None or (
                 attention_mask.dtype == np.float32 and not attention_mask.requires_grad and tuple(attention_mask.shape) in ((b, s), (1, s))))
-            extra = {"masked": True}
+            extra = {"long": True} if long else {"masked": True}
         else:
             fused, extra = hasattr(hidden, "self_attention"), {}
         scale = math.sqrt(self.d) ** -1
@@ -101,9 +103,11 @@ class BertSelfAttention(nn.Module):
                                             self.value.weight, self.value.bias, heads=self.h, scale=scale, **extra)
             return context, context.attention_probs
         q, k, v = self.query(hidden), self.key(hidden), self.value(hidden)
-        if fused and (q.masked_attention_supported(self.h) if masked else q.attention_supported(self.h)):
+        if fused and (q.long_attention_supported(self.h) if long else
+                      q.masked_attention_supported(self.h) if masked else q.attention_supported(self.h)):
             # the backend's one-launch form of everything below (scores, scaling, softmax, context), forward and backward
-            context = q.masked_attention(k, v, heads=self.h, scale=scale, mask=attention_mask) if masked else \
+            context = q.long_attention(k, v, heads=self.h, scale=scale, mask=attention_mask) if long else \
+                q.masked_attention(k, v, heads=self.h, scale=scale, mask=attention_mask) if masked else \
                 q.attention(k, v, heads=self.h, scale=scale)
             return context, context.attention_probs
         # head split: (b, s, h*d) -> (b, h, s, d) as stride permutations, no copies

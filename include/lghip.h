@@ -445,6 +445,23 @@ int lg_attention_masked_bwd_f32(const float* q, int64_t ldq, int64_t sbq, const 
                                 float* dv, int64_t lddv, int64_t sbdv, int64_t batch, int64_t heads, int64_t S, int64_t D,
                                 float scale);
 
+/* The same two launches for the lengths beyond what one CU's LDS holds of a (batch, head) pair: any S in 129 .. 512
+ * (csrc/attention_long.hip).  Only the 32 x S tile of one block of queries stays in LDS; K, V, Q and dO stream through it in
+ * chunks of 128 rows, accumulators stay in registers across the chunks and fold in a fixed order (no float atomics: the same
+ * bits every run).  Arguments, mask semantics, addressing, the dense P with row pitch S, what is read and written, and the
+ * rounding of scores and row shifts are those of the masked forms above.  Supported: D = 32 or 64, 129 <= S <= 512
+ * (lg_attention_long_supported, pure host code). */
+int lg_attention_long_supported(int64_t S, int64_t D);
+int lg_attention_long_fwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
+                              const float* v, int64_t ldv, int64_t sbv, float* o, int64_t ldo, int64_t sbo, float* p,
+                              int64_t batch, int64_t heads, int64_t S, int64_t D, float scale,
+                              const float* mask, int64_t sbm);
+int lg_attention_long_bwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
+                              const float* v, int64_t ldv, int64_t sbv, const float* g, int64_t ldg, int64_t sbg,
+                              const float* p, float* dq, int64_t lddq, int64_t sbdq, float* dk, int64_t lddk, int64_t sbdk,
+                              float* dv, int64_t lddv, int64_t sbdv, int64_t batch, int64_t heads, int64_t S, int64_t D,
+                              float scale);
+
 /* ---- two independent products in one launch ----------------------------------------------------------
  * lg_gemm_pair_begin(); <product 1>; <product 2>; lg_gemm_pair_end();   with products issued through
  * lg_gemm_f32 / lg_gemm_rowsum_f32 / lg_gemm_fused_f32.  If the first resolves to the 64x64 tile with an

@@ -2112,11 +2112,55 @@ class masked_attention(Function):
 HipTensor.masked_attention_supported = masked_attention_supported
 
 
-def self_attention_supported(x, wq, heads, masked=False):
+def long_attention_supported(q, heads):
+    """does `q.long_attention(k, v, heads, scale, mask)` exist for this shape? (b, s, heads * d) with d = 32 or 64 and any s in 129 .. 512"""
+    return len(q._shape) == 3 and q._dtype == _F32 and q._shape[2] % heads == 0 and q._shape[0] > 0 and \
+        bool(_l.lib().lg_attention_long_supported(q._shape[1], q._shape[2] // heads))
+
+
+@HipTensor.register_op()
+class long_attention(Function):
+    """ `masked_attention` for the lengths one CU's LDS does not hold a (batch, head) pair of: any s in 129 .. 512, with or without
+    a key-padding mask, forward and backward still in one launch each (csrc/attention_long.hip: K, V, Q and dO stream through LDS
+    in chunks).  mask: float32 (b, s) or (1, s), no gradient, None for none (the bits of a mask of ones).
+    `.attention_probs` (b, heads, s, s) as there, outside the tape. """
+    def forward(ctx, q, k, v, heads=1, scale=1.0, mask=None):
+        _require_f32(q, k, v)
+        assert q._shape == k._shape == v._shape and long_attention_supported(q, heads), \
+            "long_attention: unsupported shapes %s / %s / %s with %d heads" % (q._shape, k._shape, v._shape, heads)
+        b, s, width = q._shape
+        d = width // heads
+        mask, mptr, sbm = _key_mask(mask, b, s, "long_attention")
+        (q, ldq, sbq), (k, ldk, sbk), (v, ldv, sbv) = _token_rows(q), _token_rows(k), _token_rows(v)
+        out = HipTensor.empty((b, s, width))
+        probs = HipTensor.empty((b, heads, s, s), requires_grad=False)
+        _l.check(_l.lib().lg_attention_long_fwd_f32(q.ptr, ldq, sbq, k.ptr, ldk, sbk, v.ptr, ldv, sbv, out.ptr, width, s * width,
+                                                    probs.ptr, b, heads, s, d, float(scale), mptr, sbm))
+        ctx.save_for_backward(q, k, v, probs, heads, float(scale))
+        out.attention_probs = probs
+        return out
+
+    def backward(ctx, out_grad):
+        q, k, v, probs, heads, scale = ctx.get_saved_tensors()
+        b, s, width = q._shape
+        (q, ldq, sbq), (k, ldk, sbk), (v, ldv, sbv), (g, ldg, sbg) = _token_rows(q), _token_rows(k), _token_rows(v), _token_rows(out_grad)
+        dq, dk, dv = HipTensor.empty((b, s, width)), HipTensor.empty((b, s, width)), HipTensor.empty((b, s, width))
+        _l.check(_l.lib().lg_attention_long_bwd_f32(q.ptr, ldq, sbq, k.ptr, ldk, sbk, v.ptr, ldv, sbv, g.ptr, ldg, sbg, probs.ptr,
+                                                    dq.ptr, width, s * width, dk.ptr, width, s * width, dv.ptr, width, s * width,
+                                                    b, heads, s, width // heads, scale))
+        return dq, dk, dv
+
+
+HipTensor.long_attention_supported = long_attention_supported
+
+
+def self_attention_supported(x, wq, heads, masked=False, long=False):
     """does `x.self_attention(wq, bq, wk, bk, wv, bv, heads, scale)` exist for these shapes?  (b, s, hidden) input, three
     (width, hidden) weights with width = heads * d, d = 32 or 64, width a multiple of 64, s = 32 .. 128 in 32s; masked=True:
-    the same question for the form with `mask=` or a length that is no multiple of 32 - any s in 1 .. 128"""
-    fits = _l.lib().lg_attention_masked_supported if masked else _l.lib().lg_attention_supported
+    the same question for the form with `mask=` or a length that is no multiple of 32 - any s in 1 .. 128; long=True: the
+    same question for the lengths beyond - any s in 129 .. 512, with or without a mask"""
+    fits = _l.lib().lg_attention_long_supported if long else \
+        _l.lib().lg_attention_masked_supported if masked else _l.lib().lg_attention_supported
     return (len(x._shape) == 3 and x._dtype == _F32 and len(wq._shape) == 2 and wq._shape[1] == x._shape[2] and wq._shape[0] % heads == 0
             and wq._shape[0] % 64 == 0 and x._shape[2] % 4 == 0 and x.numel() > 0
             and bool(fits(x._shape[1], wq._shape[0] // heads)))
@@ -2134,12 +2178,14 @@ class self_attention(Function):
     place; backward: the attention kernel writes dq | dk | dv into one buffer of that shape, the input gradient is ONE product
     whose K runs through the three weights (lg_gemm_kseg3_f32, added to a gradient the input already holds in its epilogue),
     the weight / bias gradients take the routes of `linear`.  `.attention_probs` as for `attention`.  With a key-padding
-    `mask` (as for `masked_attention`) or a length that is no multiple of 32 the attention launches are the masked / tail ones;
-    everything else about the node is the same. """
+    `mask` (as for `masked_attention`) or a length that is no multiple of 32 the attention launches are the masked / tail ones,
+    beyond 128 positions (up to 512, mask or none) the long ones of csrc/attention_long.hip; everything else about the node is
+    the same. """
     def forward(ctx, x, wq, bq, wk, bk, wv, bv, heads=1, scale=1.0, mask=None):
         _require_f32(x, wq, bq, wk, bk, wv, bv)
+        long = len(x._shape) == 3 and x._shape[1] > 128
         tail = mask is not None or (len(x._shape) == 3 and x._shape[1] % 32 != 0)
-        assert self_attention_supported(x, wq, heads, masked=tail) and wq._shape == wk._shape == wv._shape and bq._shape == bk._shape == bv._shape == (wq._shape[0],), \
+        assert self_attention_supported(x, wq, heads, masked=tail, long=long) and wq._shape == wk._shape == wv._shape and bq._shape == bk._shape == bv._shape == (wq._shape[0],), \
             "self_attention: unsupported shapes %s with weights %s / %s / %s and %d heads" % (x._shape, wq._shape, wk._shape, wv._shape, heads)
         b, s, hidden = x._shape
         width = wq._shape[0]
@@ -2152,19 +2198,20 @@ class self_attention(Function):
         out = HipTensor.empty((b, s, width))
         probs = HipTensor.empty((b, heads, s, s), requires_grad=False)
         ld, sb = 3 * width, s * 3 * width
-        if tail:
+        if long or tail:
             mask, mptr, sbm = _key_mask(mask, b, s, "self_attention")
-            _l.check(_l.lib().lg_attention_masked_fwd_f32(base, ld, sb, base + 4 * width, ld, sb, base + 8 * width, ld, sb, out.ptr, width,
-                                                          s * width, probs.ptr, b, heads, s, width // heads, float(scale), mptr, sbm))
+            attention_fwd = _l.lib().lg_attention_long_fwd_f32 if long else _l.lib().lg_attention_masked_fwd_f32
+            _l.check(attention_fwd(base, ld, sb, base + 4 * width, ld, sb, base + 8 * width, ld, sb, out.ptr, width,
+                                   s * width, probs.ptr, b, heads, s, width // heads, float(scale), mptr, sbm))
         else:
             _l.check(_l.lib().lg_attention_fwd_f32(base, ld, sb, base + 4 * width, ld, sb, base + 8 * width, ld, sb, out.ptr, width, s * width,
                                                    probs.ptr, b, heads, s, width // heads, float(scale)))
-        ctx.save_for_backward(x, qkv, probs, heads, float(scale), tail)
+        ctx.save_for_backward(x, qkv, probs, heads, float(scale), tail, long)
         out.attention_probs = probs
         return out
 
     def backward(ctx, out_grad):
-        x, qkv, probs, heads, scale, tail = ctx.get_saved_tensors()
+        x, qkv, probs, heads, scale, tail, long = ctx.get_saved_tensors()
         x_in = ctx._parents[0]
         params = ctx._parents[1:7]
         b, s, hidden = x._shape
@@ -2173,7 +2220,8 @@ class self_attention(Function):
         dqkv = HipTensor.empty((b, s, 3 * width), requires_grad=False)
         base, dbase = qkv.ptr, dqkv.ptr
         ld, sb = 3 * width, s * 3 * width
-        attention_bwd = _l.lib().lg_attention_masked_bwd_f32 if tail else _l.lib().lg_attention_bwd_f32
+        attention_bwd = _l.lib().lg_attention_long_bwd_f32 if long else \
+            _l.lib().lg_attention_masked_bwd_f32 if tail else _l.lib().lg_attention_bwd_f32
         _l.check(attention_bwd(base, ld, sb, base + 4 * width, ld, sb, base + 8 * width, ld, sb, g.ptr, ldg, sbg, probs.ptr,
                                dbase, ld, sb, dbase + 4 * width, ld, sb, dbase + 8 * width, ld, sb,
                                b, heads, s, width // heads, scale))
