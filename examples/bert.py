@@ -8,7 +8,11 @@ Differences from the reference, on purpose:
     through the CPU and thereby drops the embedding gradient, bert.py:19-21);
   * `gelu` uses the backend's fused op when there is one (same expression, bert.py:12); so does the scaling of the
     attention scores in front of their softmax (bert.py:81-86) when there is no mask to add in between, and the two residual
-    additions of a layer (bert.py:101, :117), spelled `dense(h, residual=r)` (nn.Linear adds r where the product is made).
+    additions of a layer (bert.py:101, :117), spelled `dense(h, residual=r)` (nn.Linear adds r where the product is made);
+  * dropout is real: `hidden_dropout_prob` after the embedding LayerNorm, the attention output projection and the feed-forward
+    output projection, `attention_probs_dropout_prob` on the attention probabilities (the reference takes both arguments and
+    then sets `self.dropout = lambda x: x`, bert.py:37, :67, :102, :124).  Both default to 0, and with 0 or in `model.eval()`
+    every site takes exactly the path it took before.
 
     python examples/bert.py [--cpu] [--batch 8]        # forward + backward of a random tiny-BERT
 """
@@ -42,8 +46,9 @@ class Embedding(nn.Module):
 
 
 class BertEmbedding(nn.Module):
-    def __init__(self, hidden_size, vocab_size, max_position_embeddings, type_vocab_size):
+    def __init__(self, hidden_size, vocab_size, max_position_embeddings, type_vocab_size, hidden_dropout_prob=0.0):
         nn.Module.__init__(self)
+        self.dropout = nn.Dropout(hidden_dropout_prob)
         self.word_embeddings = Embedding(hidden_size, vocab_size)
         self.position_embeddings = Embedding(hidden_size, max_position_embeddings)
         self.token_type_embeddings = Embedding(hidden_size, type_vocab_size)
@@ -70,13 +75,14 @@ class BertEmbedding(nn.Module):
             e = word.embedding_sum(position, kind, ids0=input_ids, ids1=position_ids, ids2=token_type_ids)
         else:
             e = self.word_embeddings(input_ids) + self.position_embeddings(position_ids) + self.token_type_embeddings(token_type_ids)
-        return self.LayerNorm(e)
+        return self.dropout(self.LayerNorm(e))
 
 
 class BertSelfAttention(nn.Module):
-    def __init__(self, hidden_size, num_attention_heads):
+    def __init__(self, hidden_size, num_attention_heads, attention_probs_dropout_prob=0.0):
         nn.Module.__init__(self)
         assert hidden_size % num_attention_heads == 0
+        self.dropout = nn.Dropout(attention_probs_dropout_prob)
         self.h, self.d = num_attention_heads, hidden_size // num_attention_heads
         self.query = nn.Linear(hidden_size, hidden_size)
         self.key = nn.Linear(hidden_size, hidden_size)
@@ -96,6 +102,10 @@ class BertSelfAttention(nn.Module):
         else:
             fused, extra = hasattr(hidden, "self_attention"), {}
         scale = math.sqrt(self.d) ** -1
+        if self.training and self.dropout.p > 0:
+            # dropout of the probabilities sits between the softmax and the product with the values: the composite path below (the
+            # backends' one-launch attention forms hold the probabilities inside the kernel and do not draw masks)
+            fused = False
         if fused and hidden.self_attention_supported(self.query.weight, self.h, **extra):
             # the backend's one-node form of this whole method: one launch for the three projections, one for the attention
             extra = {"mask": attention_mask} if attention_mask is not None else {}
@@ -125,28 +135,34 @@ class BertSelfAttention(nn.Module):
                 mask = attention_mask.reshape(attention_mask.shape[0], 1, 1, attention_mask.shape[1])
                 scores = scores + ((1.0 - mask) * -10000.0).detach()
             probs = scores.softmax(axis=-1)
-        context = (probs @ v).transpose(0, 2, 1, 3).reshape(b, s, self.h * self.d)
+        context = (self.dropout(probs) @ v).transpose(0, 2, 1, 3).reshape(b, s, self.h * self.d)
         return context, probs
 
 
 class BertAttention(nn.Module):
-    def __init__(self, hidden_size, num_attention_heads):
+    def __init__(self, hidden_size, num_attention_heads, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0):
         nn.Module.__init__(self)
-        self.self = BertSelfAttention(hidden_size, num_attention_heads)
+        self.self = BertSelfAttention(hidden_size, num_attention_heads, attention_probs_dropout_prob)
+        self.dropout = nn.Dropout(hidden_dropout_prob)
         self.output = nn.Module()
         self.output.dense = nn.Linear(hidden_size, hidden_size)
         self.output.LayerNorm = nn.LayerNorm(hidden_size)
 
     def forward(self, hidden_in, attention_mask=None):
         hidden, probs = self.self(hidden_in, attention_mask=attention_mask)
-        hidden = self.output.LayerNorm(self.output.dense(hidden, residual=hidden_in))     # dense(hidden) + hidden_in
-        return hidden, probs
+        if self.training and self.dropout.p > 0:
+            # dropout sits between the product and the residual addition: one kernel for both instead of the GEMM's epilogue
+            hidden = self.dropout(self.output.dense(hidden), residual=hidden_in)
+        else:
+            hidden = self.output.dense(hidden, residual=hidden_in)                        # dense(hidden) + hidden_in
+        return self.output.LayerNorm(hidden), probs
 
 
 class BertLayer(nn.Module):
-    def __init__(self, hidden_size, intermediate_size, num_attention_heads):
+    def __init__(self, hidden_size, intermediate_size, num_attention_heads, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0):
         nn.Module.__init__(self)
-        self.attention = BertAttention(hidden_size, num_attention_heads)
+        self.attention = BertAttention(hidden_size, num_attention_heads, hidden_dropout_prob, attention_probs_dropout_prob)
+        self.dropout = nn.Dropout(hidden_dropout_prob)
         self.intermediate = nn.Module()
         self.intermediate.dense = nn.Linear(hidden_size, intermediate_size)
         self.output = nn.Module()
@@ -155,7 +171,9 @@ class BertLayer(nn.Module):
 
     def forward(self, hidden, attention_mask=None):
         hidden, probs = self.attention(hidden, attention_mask)
-        if hasattr(hidden, "feed_forward"):
+        if self.training and self.dropout.p > 0:
+            hidden = self.dropout(self.output.dense(gelu(self.intermediate.dense(hidden))), residual=hidden)
+        elif hasattr(hidden, "feed_forward"):
             # the backend's one-node form of the line below: gelu and residual in the products' epilogues, four launches for six
             up, down = self.intermediate.dense, self.output.dense
             hidden = hidden.feed_forward(up.weight, up.bias, down.weight, down.bias, hidden)
@@ -166,11 +184,12 @@ class BertLayer(nn.Module):
 
 class BertModel(nn.Module):
     def __init__(self, hidden_size, intermediate_size, num_hidden_layers, num_attention_heads, vocab_size,
-                 max_position_embeddings, type_vocab_size, **unused):
+                 max_position_embeddings, type_vocab_size, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0, **unused):
         nn.Module.__init__(self)
-        self.embeddings = BertEmbedding(hidden_size, vocab_size, max_position_embeddings, type_vocab_size)
+        self.embeddings = BertEmbedding(hidden_size, vocab_size, max_position_embeddings, type_vocab_size, hidden_dropout_prob)
         self.encoder = nn.Module()
-        self.encoder.layer = nn.ModuleList(*[BertLayer(hidden_size, intermediate_size, num_attention_heads)
+        self.encoder.layer = nn.ModuleList(*[BertLayer(hidden_size, intermediate_size, num_attention_heads, hidden_dropout_prob,
+                                                       attention_probs_dropout_prob)
                                              for _ in range(num_hidden_layers)])
 
     def forward(self, input_ids, attention_mask=None, token_type_ids=None):

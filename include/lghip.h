@@ -610,6 +610,25 @@ int lg_cross_entropy_f32(const float* logits, const void* labels, int label_item
 int lg_cross_entropy_mean_f32(const float* logits, const void* labels, int label_itemsize, float* dlogits, float* nll,
                               float* mean, int64_t rows, int64_t cols);
 
+/* ---- dropout from a counter-based random stream (csrc/dropout.hip) -----------------------------------
+ * The generator is Philox4x32-10 and its state - a 64-bit seed and the 64-bit number of dropout calls so far, `draws` - lives
+ * in device memory owned by the library (allocated by lg_init: seed 0, draws 0).  For the call with draws == b, element i of
+ * the dense tensor takes word i % 4 of
+ *   philox4x32_10(counter = (lo32(i / 4), hi32(i / 4), lo32(b), hi32(b)), key = (lo32(seed), hi32(seed)))
+ * and is KEPT iff that word >= T, T = min(floor(p * 2^32), 2^32 - 1):
+ *   y[i] = kept ? x[i] * s : +0.0 (then + residual[i] when residual is not NULL, two roundings),  s = float(1.0 / (1.0 - p))
+ *   dx[i] = kept ? g[i] * s : +0.0
+ * No mask is stored: the forward kernel reads `draws` from the state, writes the value it read to base_out[0] and advances
+ * `draws` by exactly one, whatever n is (n == 0 included); the backward kernel regenerates the mask from base[0] and the
+ * state's seed (do not reseed between the two).  Because seed and draws are read from memory, a captured graph draws a fresh
+ * mask on every replay and obeys an lg_rng_seed issued after the capture.  y may alias x, dx may alias g.
+ * 0 <= p < 1; n >= 0; base_out / base are device pointers to one uint64. */
+int lg_rng_seed(uint64_t seed);                          /* stream-ordered write of {seed, draws = 0}; refused while capturing */
+int lg_rng_state(uint64_t* seed, uint64_t* draws);       /* synchronises the stream; refused while capturing */
+int lg_dropout_fwd_f32(const float* x, const float* residual /* may be NULL */, float* y, int64_t n,
+                       double p, uint64_t* base_out);
+int lg_dropout_bwd_f32(const float* g, float* dx, int64_t n, double p, const uint64_t* base);
+
 /* library build info: "liblghip <version> gfx950 <build date>" */
 const char* lg_version(void);
 

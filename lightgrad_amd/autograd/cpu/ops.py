@@ -15,6 +15,8 @@ backend as SURVEY.md §8c prescribes:
 """
 import numpy as np
 from ..func import Function
+from ..dropout import DropoutFunction
+from ... import random as _random
 from .tensor import CpuTensor
 
 
@@ -269,6 +271,36 @@ class sum(Function):
             axes = tuple(sorted(a % len(shape) for a in axes))
             out_grad = np.expand_dims(out_grad, axis=axes) if len(shape) > 0 else out_grad
         return np.broadcast_to(out_grad, shape)
+
+
+""" Dropout (not an op of the reference, whose BERT example replaces it by the identity: examples/bert.py:37) """
+
+
+@_op()
+class dropout(DropoutFunction):
+    """ x.dropout(p, residual=None): the mask of `lightgrad_amd.random` for this call's number, kept elements times float32(1 / (1 - p)),
+    dropped ones +0.0 (a dropped NaN too), then `+ residual`.  Nothing is kept but (seed, call number, p): the backward makes the
+    mask again.  float32 only - and float64 while CpuTensor.default_dtype is float64 (the yardstick run of a float32 tape: the
+    same mask, the same float32 value of the scale) """
+    @staticmethod
+    def check_operands(x, residual):
+        DropoutFunction.check_residual(x, residual)
+        for t in (x, residual):
+            if t is not None and t.dtype != np.float32 and not (t.dtype == np.float64 and CpuTensor.default_dtype == np.float64):
+                raise TypeError("dropout is float32-only (got %s)" % t.dtype)
+
+    def forward(ctx, x, residual, p):
+        seed, draw = _random._CpuGenerator.seed, _random._CpuGenerator.next_draw()
+        ctx.save_for_backward(seed, draw, p, residual is not None)
+        keep = _random.keep_mask(seed, draw, x.size, p).reshape(x.shape)      # element index = index in the dense (row-major) result
+        y = np.where(keep, x * x.dtype.type(_random.scale(p)), x.dtype.type(0))
+        return y if residual is None else y + residual
+
+    def backward(ctx, out_grad):
+        seed, draw, p, has_residual = ctx.get_saved_tensors()
+        keep = _random.keep_mask(seed, draw, out_grad.size, p).reshape(out_grad.shape)
+        dx = np.where(keep, out_grad * out_grad.dtype.type(_random.scale(p)), out_grad.dtype.type(0))
+        return (dx, out_grad) if has_residual else dx
 
 
 """ Convolution (CNN example; reference cpu/ops.py:298-356) """

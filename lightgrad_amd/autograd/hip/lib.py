@@ -149,6 +149,10 @@ PROTOTYPES = {
     "lg_gather_sum3_rows_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64] * 3 + [c_int, c_void_p, c_int64, c_int64]),
     "lg_scatter_add_rows_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int64, c_int64]),
     "lg_rowwise_last_plan": (c_int, [POINTER(ctypes.c_int32)]),
+    "lg_rng_seed": (c_int, [c_uint64]),
+    "lg_rng_state": (c_int, [POINTER(c_uint64), POINTER(c_uint64)]),
+    "lg_dropout_fwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_double, c_void_p]),
+    "lg_dropout_bwd_f32": (c_int, [c_void_p, c_void_p, c_int64, c_double, c_void_p]),
 }
 
 # include/lghip_p2p.h: the peer-window gradient exchange, exported by liblghip.so itself (no RCCL)

@@ -11,6 +11,8 @@ import ctypes
 import os
 import numpy as np
 from ..func import Function
+from ..dropout import DropoutFunction
+from ... import random as _random
 import weakref
 from .tensor import HipTensor, HipBuffer, GradGroup, HeldPair, contiguous_strides, flush_lazy_readers
 from . import lib as _l
@@ -1951,6 +1953,37 @@ def _head_backward_riding(x, src, relu, weight, bias, g2, acc_w, acc_b, want_db)
 
 gelu = HipTensor.register_op("gelu", _unary_op("gelu", _l.EW_GELU, _l.EW_GELU_BWD, False,
                                                "tanh-approximated gelu of examples/bert.py:12 as one kernel (fwd) / one kernel (bwd)"))
+
+
+@HipTensor.register_op()
+class dropout(DropoutFunction):
+    """ x.dropout(p, residual=None): one launch of csrc/dropout.hip, which reads the generator's state from device memory and
+    advances it (so a captured step draws a new mask at every replay); `+ residual` in the same kernel.  The node keeps the one
+    word the kernel wrote - the call's number - and the backward launch makes the mask again from it; no mask is stored.  The
+    same stream, threshold and scale as the numpy backend (lightgrad_amd/random.py): equal bits. """
+    @staticmethod
+    def check_operands(x, residual):
+        DropoutFunction.check_residual(x, residual)
+        for t in (x, residual):
+            if t is not None and t._dtype != _F32:
+                raise TypeError("dropout is float32-only (got %s)" % t._dtype)
+
+    def forward(ctx, x, residual, p):
+        _random._apply_pending_hip_seed()
+        src = x.contiguous()                 # element index = index in the dense result
+        res = residual.contiguous() if residual is not None else None
+        out = HipTensor.empty(x._shape)
+        base = HipTensor.empty((1,), dtype=np.uint64, requires_grad=False)
+        _l.check(_l.lib().lg_dropout_fwd_f32(src.ptr, res.ptr if res is not None else _NULL, out.ptr, out.numel(), p, base.ptr))
+        ctx.save_for_backward(base, p, residual is not None)
+        return out
+
+    def backward(ctx, out_grad):
+        base, p, has_residual = ctx.get_saved_tensors()
+        g = out_grad.contiguous()
+        dx = HipTensor.empty(g._shape, requires_grad=False)
+        _l.check(_l.lib().lg_dropout_bwd_f32(g.ptr, dx.ptr, dx.numel(), p, base.ptr))
+        return (dx, out_grad) if has_residual else dx
 
 
 def _rows_view(t):

@@ -29,6 +29,8 @@ struct Runtime {
     // synchronisation and report LG_EINDEX once.
     int*        status_host = nullptr;
     int*        status_dev = nullptr;
+    // generator behind lg_dropout_* (dropout.hip): 64-bit words {seed, draws}, then the arrival tickets of the forward kernel
+    unsigned long long* rng_state = nullptr;
 };
 
 constexpr int LG_STATUS_BAD_INDEX = 1;
@@ -51,6 +53,9 @@ bool ln_group_writes(const void* ptr);
 struct TailGroup;
 bool tail_take(TailGroup* out);       // rowwise.hip: the queued LayerNorm / scatter jobs as one argument block ...
 int tail_taken();                     // ... and, once launched, out of the queue
+
+// dropout.hip: allocate the generator's state (seed 0, draws 0); called by lg_init
+int rng_init();
 
 // p2p.hip: what the first wait of the peer-window exchange that gave up was waiting for
 void p2p_describe_timeout(char* out, size_t len);

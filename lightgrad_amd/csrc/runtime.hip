@@ -195,6 +195,7 @@ int lg_init(int device) {
     LG_HIP(hipHostMalloc(reinterpret_cast<void**>(&R.status_host), 64, hipHostMallocMapped));
     R.status_host[0] = 0;
     LG_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&R.status_dev), R.status_host, 0));
+    { const int rc = rng_init(); if (rc != LG_OK) return rc; }
     R.device = device;
     R.ready = true;
     return LG_OK;

@@ -23,6 +23,10 @@ def _is_child(value) -> bool:
 
 class Module(object):
 
+    # training / evaluation switch (`train()`, `eval()`): layers that behave differently while training (Dropout) read it.
+    # A plain attribute, not a child: it never shows in `parameters()`, `named_parameters()` or `load_parameters`.
+    training = True
+
     def __init__(self):
         object.__setattr__(self, "_children", {})
 
@@ -33,6 +37,16 @@ class Module(object):
 
     def __call__(self, *inputs, **options):
         return self.forward(*inputs, **options)
+
+    def train(self, mode: bool = True):
+        """set `training` on this module and every sub-module; returns self"""
+        self.training = bool(mode)
+        for _, sub in self._own(Module):
+            sub.train(mode)
+        return self
+
+    def eval(self):
+        return self.train(False)
 
     # ---- bookkeeping ------------------------------------------------------------------------------------------------
 
@@ -134,6 +148,22 @@ class Linear(Module):
         y = x @ self.weight.T(1, 0)
         y = y if self.bias is None else y + self.bias
         return y if residual is None else y + residual
+
+
+class Dropout(Module):
+    """while training: x.dropout(p, residual=...) - each element zeroed with probability p, the others scaled by 1 / (1 - p),
+    `+ residual` in the same kernel; in `eval()` or with p == 0: the input itself (or the plain sum with the residual).  Not a
+    layer of the reference (its BERT example replaces dropout by the identity, examples/bert.py:37)."""
+
+    def __init__(self, p: float = 0.5):
+        Module.__init__(self)
+        from .random import check_probability
+        self.p = check_probability(p)
+
+    def forward(self, x, residual=None):
+        if self.training and self.p > 0:
+            return x.dropout(self.p, residual=residual)
+        return x if residual is None else x + residual
 
 
 class Conv2d(Module):

@@ -1,0 +1,112 @@
+"""The random stream behind `Tensor.dropout`: one definition, arithmetic only, shared by both backends.
+
+The generator is Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85, ten rounds).  Its
+state is a 64-bit `seed` and the 64-bit number of dropout calls so far, `draws`.  For the call with draws == b, element i of
+the flattened dense tensor takes word i % 4 of
+
+    philox4x32_10(counter = (lo32(i // 4), hi32(i // 4), lo32(b), hi32(b)), key = (lo32(seed), hi32(seed)))
+
+and is kept iff that word >= T, T = min(floor(p * 2**32), 2**32 - 1); kept elements are scaled by s = float32(1 / (1 - p)).
+A call advances `draws` by exactly one, whatever the tensor's size.  The numpy backend evaluates this here; the HIP backend
+evaluates the same arithmetic in csrc/dropout.hip from a state that lives in device memory, so the two produce the same mask
+bit for bit, and a captured hipGraph draws a fresh mask on every replay.
+
+    manual_seed(seed)        seed every backend's generator, draws back to 0
+    get_state(backend)       (seed, draws) of "cpu" or "hip"
+"""
+import ctypes
+import numpy as np
+
+_M0, _M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+_W0, _W1 = 0x9E3779B9, 0xBB67AE85
+_LOW, _SHIFT = np.uint64(0xFFFFFFFF), np.uint64(32)
+
+
+def philox4x32_10(counter, key):
+    """counter: four arrays (or ints) of 32-bit words, key: two 32-bit ints -> uint32 array [..., 4]"""
+    c0, c1, c2, c3 = np.broadcast_arrays(*[np.asarray(c, dtype=np.uint64) & _LOW for c in counter])
+    k0, k1 = int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF
+    for _ in range(10):
+        p0, p1 = _M0 * c0, _M1 * c2                      # 32 x 32 -> 64 bits: exact in uint64
+        c0, c1, c2, c3 = (p1 >> _SHIFT) ^ c1 ^ np.uint64(k0), p1 & _LOW, (p0 >> _SHIFT) ^ c3 ^ np.uint64(k1), p0 & _LOW
+        k0, k1 = (k0 + _W0) & 0xFFFFFFFF, (k1 + _W1) & 0xFFFFFFFF
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def words(seed: int, draw: int, n: int, first_group: int = 0) -> np.ndarray:
+    """the stream's words for elements 4 * first_group ... 4 * first_group + n - 1 of call number `draw`"""
+    groups = np.arange(first_group, first_group + (n + 3) // 4, dtype=np.uint64)
+    w = philox4x32_10((groups & _LOW, groups >> _SHIFT, draw & 0xFFFFFFFF, (draw >> 32) & 0xFFFFFFFF),
+                      (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF))
+    return w.reshape(-1)[:n]
+
+
+def threshold(p: float) -> int:
+    """T: an element is kept iff its word >= T"""
+    return min(int(np.floor(np.float64(p) * 4294967296.0)), 4294967295)
+
+
+def scale(p: float) -> np.float32:
+    """s: the division in double, rounded to float32 once"""
+    return np.float32(1.0 / (1.0 - np.float64(p)))
+
+
+def keep_mask(seed: int, draw: int, n: int, p: float) -> np.ndarray:
+    return words(seed, draw, n) >= np.uint32(threshold(p))
+
+
+def check_probability(p) -> float:
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("dropout probability must satisfy 0 <= p < 1 (got %r)" % p)
+    return p
+
+
+class _CpuGenerator(object):
+    seed, draws = 0, 0
+
+    @classmethod
+    def next_draw(cls) -> int:
+        cls.draws += 1
+        return cls.draws - 1
+
+
+# the HIP generator lives in device memory (lg_init: seed 0, draws 0).  A seed set before the library is loaded - or on a machine
+# without a GPU - waits here until the backend is first used.
+_pending_hip_seed = None
+
+
+def _apply_pending_hip_seed() -> None:
+    """called by the HIP backend before it draws or reports its state"""
+    global _pending_hip_seed
+    if _pending_hip_seed is not None:
+        from .autograd.hip import lib as _l
+        seed, _pending_hip_seed = _pending_hip_seed, None
+        _l.check(_l.lib().lg_rng_seed(seed))
+
+
+def manual_seed(seed: int) -> None:
+    """seed the generator of every backend and set its `draws` back to 0 (not inside a hipGraph capture: seed between replays)"""
+    global _pending_hip_seed
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("seed must fit 64 bits (got %r)" % seed)
+    _CpuGenerator.seed, _CpuGenerator.draws = seed, 0
+    from .autograd.hip import lib as _l
+    _pending_hip_seed = seed
+    if _l._lib is not None:                 # the library is initialised: a stream-ordered write, now
+        _apply_pending_hip_seed()
+
+
+def get_state(backend: str = "cpu") -> tuple:
+    """(seed, draws) of a backend's generator; "hip" synchronises with the device"""
+    if backend == "cpu":
+        return _CpuGenerator.seed, _CpuGenerator.draws
+    if backend == "hip":
+        from .autograd.hip import lib as _l
+        L = _l.lib()
+        _apply_pending_hip_seed()
+        seed, draws = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _l.check(L.lg_rng_state(ctypes.byref(seed), ctypes.byref(draws)))
+        return seed.value, draws.value
+    raise ValueError("unknown backend %r (cpu, hip)" % (backend,))
