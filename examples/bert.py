@@ -102,23 +102,22 @@ class BertSelfAttention(nn.Module):
         else:
             fused, extra = hasattr(hidden, "self_attention"), {}
         scale = math.sqrt(self.d) ** -1
-        if self.training and self.dropout.p > 0:
-            # dropout of the probabilities sits between the softmax and the product with the values: the composite path below (the
-            # backends' one-launch attention forms hold the probabilities inside the kernel and do not draw masks)
-            fused = False
+        # dropout of the probabilities sits between the softmax and the product with the values: the backends' one-launch forms
+        # draw the composite's mask inside the kernel (one call of the stream); without `dropout=` they are the forms as they were
+        drop = {"dropout": self.dropout.p} if self.training and self.dropout.p > 0 else {}
         if fused and hidden.self_attention_supported(self.query.weight, self.h, **extra):
             # the backend's one-node form of this whole method: one launch for the three projections, one for the attention
             extra = {"mask": attention_mask} if attention_mask is not None else {}
             context = hidden.self_attention(self.query.weight, self.query.bias, self.key.weight, self.key.bias,
-                                            self.value.weight, self.value.bias, heads=self.h, scale=scale, **extra)
+                                            self.value.weight, self.value.bias, heads=self.h, scale=scale, **extra, **drop)
             return context, context.attention_probs
         q, k, v = self.query(hidden), self.key(hidden), self.value(hidden)
         if fused and (q.long_attention_supported(self.h) if long else
                       q.masked_attention_supported(self.h) if masked else q.attention_supported(self.h)):
             # the backend's one-launch form of everything below (scores, scaling, softmax, context), forward and backward
-            context = q.long_attention(k, v, heads=self.h, scale=scale, mask=attention_mask) if long else \
-                q.masked_attention(k, v, heads=self.h, scale=scale, mask=attention_mask) if masked else \
-                q.attention(k, v, heads=self.h, scale=scale)
+            context = q.long_attention(k, v, heads=self.h, scale=scale, mask=attention_mask, **drop) if long else \
+                q.masked_attention(k, v, heads=self.h, scale=scale, mask=attention_mask, **drop) if masked else \
+                q.attention(k, v, heads=self.h, scale=scale, **drop)
             return context, context.attention_probs
         # head split: (b, s, h*d) -> (b, h, s, d) as stride permutations, no copies
         q = q.reshape(b, s, self.h, self.d).transpose(0, 2, 1, 3)

@@ -462,6 +462,29 @@ int lg_attention_long_bwd_f32(const float* q, int64_t ldq, int64_t sbq, const fl
                               float* dv, int64_t lddv, int64_t sbdv, int64_t batch, int64_t heads, int64_t S, int64_t D,
                               float scale);
 
+/* Attention with dropout of the probabilities inside the two launches, for every length the forms above take: 1 <= S <= 512,
+ * D = 32 or 64 (lg_attention_dropout_supported, pure host code).  With keep / s / T of the random stream below (lg_dropout_*):
+ *   P  = softmax(scores)                  written to `p` UNDROPPED, as above
+ *   Pd = keep ? fl(P * s) : +0.0          the operand of the context, never leaves the CU:   O = Pd V,   dV = Pd^T dO
+ *   dP = keep ? fl((dO V^T) * s) : +0.0   then dS = P o (dP - shift) * scale as above (shift in double from the masked dP)
+ * One forward is ONE call of the stream (`draws` advances by 1; the launch reads `draws` from device memory, so a captured graph
+ * draws a fresh mask at every replay) and element i of the call is the flat index into the dense (batch, heads, S, S)
+ * probabilities, i = ((b * heads + head) * S + row) * S + col: the mask `P.dropout(p)` of the composite form draws.  The forward
+ * writes the call's number to base_out (one word of device memory); the backward reads the seed from the generator's state and the
+ * number from `base`, and draws nothing.  The host picks the kernels: no mask, S % 32 == 0 and S <= 128 the plain ones, otherwise
+ * up to 128 the masked ones, beyond the long ones.  Arguments before `p` as for the masked forms and under their rules;
+ * 0 <= p < 1 (p == 0 keeps everything and still draws once); base_out / base non-NULL; batch >= 1 in the forward. */
+int lg_attention_dropout_supported(int64_t S, int64_t D);
+int lg_attention_dropout_fwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
+                                 const float* v, int64_t ldv, int64_t sbv, float* o, int64_t ldo, int64_t sbo, float* p,
+                                 int64_t batch, int64_t heads, int64_t S, int64_t D, float scale,
+                                 const float* mask, int64_t sbm, double prob, uint64_t* base_out);
+int lg_attention_dropout_bwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
+                                 const float* v, int64_t ldv, int64_t sbv, const float* g, int64_t ldg, int64_t sbg,
+                                 const float* p, float* dq, int64_t lddq, int64_t sbdq, float* dk, int64_t lddk, int64_t sbdk,
+                                 float* dv, int64_t lddv, int64_t sbdv, int64_t batch, int64_t heads, int64_t S, int64_t D,
+                                 float scale, double prob, const uint64_t* base);
+
 /* ---- two independent products in one launch ----------------------------------------------------------
  * lg_gemm_pair_begin(); <product 1>; <product 2>; lg_gemm_pair_end();   with products issued through
  * lg_gemm_f32 / lg_gemm_rowsum_f32 / lg_gemm_fused_f32.  If the first resolves to the 64x64 tile with an

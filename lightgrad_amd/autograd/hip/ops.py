@@ -2048,6 +2048,17 @@ def _token_rows(t):
     return t, st[1], st[0]
 
 
+def _attention_dropout(dropout):
+    """the validated probability of an attention form's `dropout=`; 0.0 means the launches without it"""
+    return _random.check_probability(dropout)
+
+
+def _dropout_base():
+    """the one word of device memory the forward launch writes the call's number to and the backward reads it from"""
+    _random._apply_pending_hip_seed()
+    return HipTensor.empty((1,), dtype=np.uint64, requires_grad=False)
+
+
 def attention_supported(q, heads):
     """does `q.attention(k, v, heads, scale)` exist for this shape? (b, s, heads * d) with d = 32 or 64 and s = 32 .. 128 in 32s"""
     return len(q._shape) == 3 and q._dtype == _F32 and q._shape[2] % heads == 0 and \
@@ -2059,8 +2070,11 @@ class attention(Function):
     """ softmax((q k^T) * scale) v per head, forward and backward in one launch each (csrc/attention.hip); q, k, v are the
     (batch, positions, heads * d) outputs of the three projections as they stand - the head split of examples/bert.py:78-80
     happens in the kernels' addressing.  The probabilities (batch, heads, s, s) the reference model returns next to the context
-    (bert.py:88) are on the result as `.attention_probs`, outside the tape (the composite form differentiates through them) """
-    def forward(ctx, q, k, v, heads=1, scale=1.0):
+    (bert.py:88) are on the result as `.attention_probs`, outside the tape (the composite form differentiates through them).
+    dropout=p > 0: `probs.dropout(p)` between the softmax and the context inside the same two launches - the mask the composite
+    draws (one call of the stream, lightgrad_amd/random.py); `.attention_probs` stays undropped """
+    def forward(ctx, q, k, v, heads=1, scale=1.0, dropout=0.0):
+        dropout = _attention_dropout(dropout)
         _require_f32(q, k, v)
         assert q._shape == k._shape == v._shape and attention_supported(q, heads), \
             "attention: unsupported shapes %s / %s / %s with %d heads" % (q._shape, k._shape, v._shape, heads)
@@ -2069,20 +2083,29 @@ class attention(Function):
         (q, ldq, sbq), (k, ldk, sbk), (v, ldv, sbv) = _token_rows(q), _token_rows(k), _token_rows(v)
         out = HipTensor.empty((b, s, width))
         probs = HipTensor.empty((b, heads, s, s), requires_grad=False)
-        _l.check(_l.lib().lg_attention_fwd_f32(q.ptr, ldq, sbq, k.ptr, ldk, sbk, v.ptr, ldv, sbv, out.ptr, width, s * width,
-                                               probs.ptr, b, heads, s, d, float(scale)))
-        ctx.save_for_backward(q, k, v, probs, heads, float(scale))
+        base = None
+        if dropout > 0.0:
+            base = _dropout_base()
+            _l.check(_l.lib().lg_attention_dropout_fwd_f32(q.ptr, ldq, sbq, k.ptr, ldk, sbk, v.ptr, ldv, sbv, out.ptr, width, s * width,
+                                                           probs.ptr, b, heads, s, d, float(scale), None, 0, dropout, base.ptr))
+        else:
+            _l.check(_l.lib().lg_attention_fwd_f32(q.ptr, ldq, sbq, k.ptr, ldk, sbk, v.ptr, ldv, sbv, out.ptr, width, s * width,
+                                                   probs.ptr, b, heads, s, d, float(scale)))
+        ctx.save_for_backward(q, k, v, probs, heads, float(scale), dropout, base)
         out.attention_probs = probs
         return out
 
     def backward(ctx, out_grad):
-        q, k, v, probs, heads, scale = ctx.get_saved_tensors()
+        q, k, v, probs, heads, scale, dropout, base = ctx.get_saved_tensors()
         b, s, width = q._shape
         (q, ldq, sbq), (k, ldk, sbk), (v, ldv, sbv), (g, ldg, sbg) = _token_rows(q), _token_rows(k), _token_rows(v), _token_rows(out_grad)
         dq, dk, dv = HipTensor.empty((b, s, width)), HipTensor.empty((b, s, width)), HipTensor.empty((b, s, width))
-        _l.check(_l.lib().lg_attention_bwd_f32(q.ptr, ldq, sbq, k.ptr, ldk, sbk, v.ptr, ldv, sbv, g.ptr, ldg, sbg, probs.ptr,
-                                               dq.ptr, width, s * width, dk.ptr, width, s * width, dv.ptr, width, s * width,
-                                               b, heads, s, width // heads, scale))
+        args = (q.ptr, ldq, sbq, k.ptr, ldk, sbk, v.ptr, ldv, sbv, g.ptr, ldg, sbg, probs.ptr,
+                dq.ptr, width, s * width, dk.ptr, width, s * width, dv.ptr, width, s * width, b, heads, s, width // heads, scale)
+        if base is not None:
+            _l.check(_l.lib().lg_attention_dropout_bwd_f32(*args, dropout, base.ptr))
+        else:
+            _l.check(_l.lib().lg_attention_bwd_f32(*args))
         return dq, dk, dv
 
 
@@ -2115,7 +2138,8 @@ class masked_attention(Function):
     `scores + (1.0 - mask) * -10000.0` before the softmax), forward and backward in one launch each (the TAIL kernels of
     csrc/attention.hip).  mask: float32 (b, s) or (1, s), no gradient, None for none.  A mask of ones gives the bits of `attention`.
     `.attention_probs` (b, heads, s, s) as there, outside the tape. """
-    def forward(ctx, q, k, v, heads=1, scale=1.0, mask=None):
+    def forward(ctx, q, k, v, heads=1, scale=1.0, mask=None, dropout=0.0):
+        dropout = _attention_dropout(dropout)           # > 0: `probs.dropout(p)` inside the two launches, as for `attention`
         _require_f32(q, k, v)
         assert q._shape == k._shape == v._shape and masked_attention_supported(q, heads), \
             "masked_attention: unsupported shapes %s / %s / %s with %d heads" % (q._shape, k._shape, v._shape, heads)
@@ -2125,20 +2149,25 @@ class masked_attention(Function):
         (q, ldq, sbq), (k, ldk, sbk), (v, ldv, sbv) = _token_rows(q), _token_rows(k), _token_rows(v)
         out = HipTensor.empty((b, s, width))
         probs = HipTensor.empty((b, heads, s, s), requires_grad=False)
-        _l.check(_l.lib().lg_attention_masked_fwd_f32(q.ptr, ldq, sbq, k.ptr, ldk, sbk, v.ptr, ldv, sbv, out.ptr, width, s * width,
-                                                      probs.ptr, b, heads, s, d, float(scale), mptr, sbm))
-        ctx.save_for_backward(q, k, v, probs, heads, float(scale))
+        base, fwd, extra = None, _l.lib().lg_attention_masked_fwd_f32, ()
+        if dropout > 0.0:
+            base = _dropout_base()
+            fwd, extra = _l.lib().lg_attention_dropout_fwd_f32, (dropout, base.ptr)
+        _l.check(fwd(q.ptr, ldq, sbq, k.ptr, ldk, sbk, v.ptr, ldv, sbv, out.ptr, width, s * width,
+                     probs.ptr, b, heads, s, d, float(scale), mptr, sbm, *extra))
+        ctx.save_for_backward(q, k, v, probs, heads, float(scale), dropout, base)
         out.attention_probs = probs
         return out
 
     def backward(ctx, out_grad):
-        q, k, v, probs, heads, scale = ctx.get_saved_tensors()
+        q, k, v, probs, heads, scale, dropout, base = ctx.get_saved_tensors()
         b, s, width = q._shape
         (q, ldq, sbq), (k, ldk, sbk), (v, ldv, sbv), (g, ldg, sbg) = _token_rows(q), _token_rows(k), _token_rows(v), _token_rows(out_grad)
         dq, dk, dv = HipTensor.empty((b, s, width)), HipTensor.empty((b, s, width)), HipTensor.empty((b, s, width))
-        _l.check(_l.lib().lg_attention_masked_bwd_f32(q.ptr, ldq, sbq, k.ptr, ldk, sbk, v.ptr, ldv, sbv, g.ptr, ldg, sbg, probs.ptr,
-                                                      dq.ptr, width, s * width, dk.ptr, width, s * width, dv.ptr, width, s * width,
-                                                      b, heads, s, width // heads, scale))
+        bwd, extra = (_l.lib().lg_attention_masked_bwd_f32, ()) if base is None else (_l.lib().lg_attention_dropout_bwd_f32, (dropout, base.ptr))
+        _l.check(bwd(q.ptr, ldq, sbq, k.ptr, ldk, sbk, v.ptr, ldv, sbv, g.ptr, ldg, sbg, probs.ptr,
+                     dq.ptr, width, s * width, dk.ptr, width, s * width, dv.ptr, width, s * width,
+                     b, heads, s, width // heads, scale, *extra))
         return dq, dk, dv
 
 
@@ -2157,7 +2186,8 @@ class long_attention(Function):
     a key-padding mask, forward and backward still in one launch each (csrc/attention_long.hip: K, V, Q and dO stream through LDS
     in chunks).  mask: float32 (b, s) or (1, s), no gradient, None for none (the bits of a mask of ones).
     `.attention_probs` (b, heads, s, s) as there, outside the tape. """
-    def forward(ctx, q, k, v, heads=1, scale=1.0, mask=None):
+    def forward(ctx, q, k, v, heads=1, scale=1.0, mask=None, dropout=0.0):
+        dropout = _attention_dropout(dropout)           # > 0: `probs.dropout(p)` inside the two launches, as for `attention`
         _require_f32(q, k, v)
         assert q._shape == k._shape == v._shape and long_attention_supported(q, heads), \
             "long_attention: unsupported shapes %s / %s / %s with %d heads" % (q._shape, k._shape, v._shape, heads)
@@ -2167,20 +2197,25 @@ class long_attention(Function):
         (q, ldq, sbq), (k, ldk, sbk), (v, ldv, sbv) = _token_rows(q), _token_rows(k), _token_rows(v)
         out = HipTensor.empty((b, s, width))
         probs = HipTensor.empty((b, heads, s, s), requires_grad=False)
-        _l.check(_l.lib().lg_attention_long_fwd_f32(q.ptr, ldq, sbq, k.ptr, ldk, sbk, v.ptr, ldv, sbv, out.ptr, width, s * width,
-                                                    probs.ptr, b, heads, s, d, float(scale), mptr, sbm))
-        ctx.save_for_backward(q, k, v, probs, heads, float(scale))
+        base, fwd, extra = None, _l.lib().lg_attention_long_fwd_f32, ()
+        if dropout > 0.0:
+            base = _dropout_base()
+            fwd, extra = _l.lib().lg_attention_dropout_fwd_f32, (dropout, base.ptr)
+        _l.check(fwd(q.ptr, ldq, sbq, k.ptr, ldk, sbk, v.ptr, ldv, sbv, out.ptr, width, s * width,
+                     probs.ptr, b, heads, s, d, float(scale), mptr, sbm, *extra))
+        ctx.save_for_backward(q, k, v, probs, heads, float(scale), dropout, base)
         out.attention_probs = probs
         return out
 
     def backward(ctx, out_grad):
-        q, k, v, probs, heads, scale = ctx.get_saved_tensors()
+        q, k, v, probs, heads, scale, dropout, base = ctx.get_saved_tensors()
         b, s, width = q._shape
         (q, ldq, sbq), (k, ldk, sbk), (v, ldv, sbv), (g, ldg, sbg) = _token_rows(q), _token_rows(k), _token_rows(v), _token_rows(out_grad)
         dq, dk, dv = HipTensor.empty((b, s, width)), HipTensor.empty((b, s, width)), HipTensor.empty((b, s, width))
-        _l.check(_l.lib().lg_attention_long_bwd_f32(q.ptr, ldq, sbq, k.ptr, ldk, sbk, v.ptr, ldv, sbv, g.ptr, ldg, sbg, probs.ptr,
-                                                    dq.ptr, width, s * width, dk.ptr, width, s * width, dv.ptr, width, s * width,
-                                                    b, heads, s, width // heads, scale))
+        bwd, extra = (_l.lib().lg_attention_long_bwd_f32, ()) if base is None else (_l.lib().lg_attention_dropout_bwd_f32, (dropout, base.ptr))
+        _l.check(bwd(q.ptr, ldq, sbq, k.ptr, ldk, sbk, v.ptr, ldv, sbv, g.ptr, ldg, sbg, probs.ptr,
+                     dq.ptr, width, s * width, dk.ptr, width, s * width, dv.ptr, width, s * width,
+                     b, heads, s, width // heads, scale, *extra))
         return dq, dk, dv
 
 
@@ -2214,7 +2249,8 @@ class self_attention(Function):
     `mask` (as for `masked_attention`) or a length that is no multiple of 32 the attention launches are the masked / tail ones,
     beyond 128 positions (up to 512, mask or none) the long ones of csrc/attention_long.hip; everything else about the node is
     the same. """
-    def forward(ctx, x, wq, bq, wk, bk, wv, bv, heads=1, scale=1.0, mask=None):
+    def forward(ctx, x, wq, bq, wk, bk, wv, bv, heads=1, scale=1.0, mask=None, dropout=0.0):
+        dropout = _attention_dropout(dropout)           # > 0: `probs.dropout(p)` inside the attention launches, as for `attention`
         _require_f32(x, wq, bq, wk, bk, wv, bv)
         long = len(x._shape) == 3 and x._shape[1] > 128
         tail = mask is not None or (len(x._shape) == 3 and x._shape[1] % 32 != 0)
@@ -2231,7 +2267,14 @@ class self_attention(Function):
         out = HipTensor.empty((b, s, width))
         probs = HipTensor.empty((b, heads, s, s), requires_grad=False)
         ld, sb = 3 * width, s * 3 * width
-        if long or tail:
+        drop_base = None
+        if dropout > 0.0:
+            mask, mptr, sbm = _key_mask(mask, b, s, "self_attention")
+            drop_base = _dropout_base()
+            _l.check(_l.lib().lg_attention_dropout_fwd_f32(base, ld, sb, base + 4 * width, ld, sb, base + 8 * width, ld, sb, out.ptr, width,
+                                                           s * width, probs.ptr, b, heads, s, width // heads, float(scale), mptr, sbm,
+                                                           dropout, drop_base.ptr))
+        elif long or tail:
             mask, mptr, sbm = _key_mask(mask, b, s, "self_attention")
             attention_fwd = _l.lib().lg_attention_long_fwd_f32 if long else _l.lib().lg_attention_masked_fwd_f32
             _l.check(attention_fwd(base, ld, sb, base + 4 * width, ld, sb, base + 8 * width, ld, sb, out.ptr, width,
@@ -2239,12 +2282,12 @@ class self_attention(Function):
         else:
             _l.check(_l.lib().lg_attention_fwd_f32(base, ld, sb, base + 4 * width, ld, sb, base + 8 * width, ld, sb, out.ptr, width, s * width,
                                                    probs.ptr, b, heads, s, width // heads, float(scale)))
-        ctx.save_for_backward(x, qkv, probs, heads, float(scale), tail, long)
+        ctx.save_for_backward(x, qkv, probs, heads, float(scale), tail, long, dropout, drop_base)
         out.attention_probs = probs
         return out
 
     def backward(ctx, out_grad):
-        x, qkv, probs, heads, scale, tail, long = ctx.get_saved_tensors()
+        x, qkv, probs, heads, scale, tail, long, dropout, drop_base = ctx.get_saved_tensors()
         x_in = ctx._parents[0]
         params = ctx._parents[1:7]
         b, s, hidden = x._shape
@@ -2255,9 +2298,12 @@ class self_attention(Function):
         ld, sb = 3 * width, s * 3 * width
         attention_bwd = _l.lib().lg_attention_long_bwd_f32 if long else \
             _l.lib().lg_attention_masked_bwd_f32 if tail else _l.lib().lg_attention_bwd_f32
+        extra = ()
+        if drop_base is not None:
+            attention_bwd, extra = _l.lib().lg_attention_dropout_bwd_f32, (dropout, drop_base.ptr)
         _l.check(attention_bwd(base, ld, sb, base + 4 * width, ld, sb, base + 8 * width, ld, sb, g.ptr, ldg, sbg, probs.ptr,
                                dbase, ld, sb, dbase + 4 * width, ld, sb, dbase + 8 * width, ld, sb,
-                               b, heads, s, width // heads, scale))
+                               b, heads, s, width // heads, scale, *extra))
         x2 = x.reshape(-1, hidden)
         grads = []
         for i in range(3):

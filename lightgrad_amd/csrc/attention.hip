@@ -36,6 +36,7 @@
 // the kernels as they were.
 #include "common.h"
 #include "mfma_lds.h"
+#include "rng_common.h"
 #include <cmath>
 #include <type_traits>
 
@@ -66,6 +67,36 @@ struct AttnTailArgs : AttnArgs {
     int64_t sbm;
 };
 
+// DROP instantiations: the tail arguments (mask NULL for none) and the call of the random stream
+struct AttnDropArgs : AttnTailArgs {
+    AttnDrop drop;
+};
+
+// the two 64-bit words of a call in LDS (DROP instantiations only: 16 bytes of static LDS next to the dynamic tiles)
+template <bool DROP>
+__device__ __forceinline__ unsigned long long* rng_call_slot() {
+    if constexpr (DROP) {
+        __shared__ unsigned long long call[2];
+        return call;
+    } else {
+        return nullptr;
+    }
+}
+
+// linear index of this workgroup over the 3-D grid / workgroups of the launch: what the tickets of the random stream count
+__device__ __forceinline__ int grid_linear_block() { return int((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x); }
+__device__ __forceinline__ int grid_blocks() { return int(gridDim.x * gridDim.y * gridDim.z); }
+
+// the float4 of probabilities at flat element index i of the dense (batch, heads, S, S) tensor as the context's MFMA operand:
+// P * s where the stream keeps the element, +0.0 where it drops it
+template <bool ALIGNED>
+__device__ __forceinline__ af32x4 drop4(af32x4 t, int64_t i, unsigned long long seed, unsigned long long base, uint32_t threshold, float s) {
+    uint32_t w[4];
+    rng_words4<ALIGNED>(i, seed, base, w);
+    return af32x4{rng_keep(t[0], w[0], threshold, s), rng_keep(t[1], w[1], threshold, s), rng_keep(t[2], w[2], threshold, s),
+                  rng_keep(t[3], w[3], threshold, s)};
+}
+
 __host__ __device__ constexpr int round32(int S) { return (S + 31) & ~31; }
 
 template <int D>
@@ -89,8 +120,10 @@ __device__ __forceinline__ void store_rows_padded(const af32x4 (&v)[N], float* d
     }
 }
 
-template <int D, bool TAIL = false>
-__global__ void __launch_bounds__(256) attn_fwd(std::conditional_t<TAIL, AttnTailArgs, AttnArgs> a) {
+// DROP: dropout of the probabilities between the softmax and the context, from the stream of dropout.hip (one call per launch:
+// read `draws`, take a ticket, the last arriver advances).  P goes to HBM undropped; what feeds the context MFMAs is Pd.
+template <int D, bool TAIL = false, bool DROP = false>
+__global__ void __launch_bounds__(256) attn_fwd(std::conditional_t<DROP, AttnDropArgs, std::conditional_t<TAIL, AttnTailArgs, AttnArgs>> a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int S = a.S;                               // the sequence
     const int Sp = TAIL ? round32(S) : S;            // what the tiles cover
@@ -105,6 +138,21 @@ __global__ void __launch_bounds__(256) attn_fwd(std::conditional_t<TAIL, AttnTai
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     const int q0 = blockIdx.x * 32, head = blockIdx.y, b = blockIdx.z;
     LG_ATL(0);
+    [[maybe_unused]] unsigned long long* const call = rng_call_slot<DROP>();
+    [[maybe_unused]] int order = 0, grp = 0, groups = 0;
+    [[maybe_unused]] int* tickets = nullptr;
+    [[maybe_unused]] int* mine = nullptr;
+    if constexpr (DROP) {
+        tickets = rng_tickets(a.drop.state);
+        grp = grid_linear_block() / a.drop.group;
+        groups = (grid_blocks() + a.drop.group - 1) / a.drop.group;
+        mine = tickets + (1 + grp) * kRngLine;
+        if (tid == 0) {
+            rng_read_call(a.drop.state, call);                        // `draws` is in a register before the ticket is taken
+            if (grid_linear_block() == 0) a.drop.base[0] = call[1];
+            order = rng_take_ticket(mine);
+        }
+    }
 
     {
         constexpr int NB = 32 * (D / 4) / 256 > 0 ? 32 * (D / 4) / 256 : 1, NA = 128 * (D / 4) / 256;   // float4 per thread: 32 rows / all rows
@@ -131,6 +179,8 @@ __global__ void __launch_bounds__(256) attn_fwd(std::conditional_t<TAIL, AttnTai
     }
     __syncthreads();
     LG_ATL(1);
+    [[maybe_unused]] unsigned long long seed = 0, base = 0;
+    if constexpr (DROP) { seed = rng_uniform64(call[0]); base = rng_uniform64(call[1]); }
 
     // scores of 32 queries against keys [32 wave, 32 wave + 32), scaled (the product rounded to fp32 first, like `scores * c`)
     if (32 * wave < Sp) {
@@ -192,7 +242,9 @@ __global__ void __launch_bounds__(256) attn_fwd(std::conditional_t<TAIL, AttnTai
             if (c < Sp) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) t[i][e] *= inv;
-                *reinterpret_cast<af32x4*>(pr + c) = t[i];
+                // (DROP: a key >= S holds 0 and stays 0 whatever word it meets; a row >= S is never stored)
+                if constexpr (DROP) *reinterpret_cast<af32x4*>(pr + c) = drop4<false>(t[i], (pg - a.p) + c, seed, base, a.drop.threshold, a.drop.s);
+                else                *reinterpret_cast<af32x4*>(pr + c) = t[i];
                 if (row_exists) {
                     if ((S & 3) == 0) {
                         if (c < S) *reinterpret_cast<af32x4*>(pg + c) = t[i];
@@ -238,7 +290,9 @@ __global__ void __launch_bounds__(256) attn_fwd(std::conditional_t<TAIL, AttnTai
             if (c < S) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) t[i][e] *= inv;
-                *reinterpret_cast<af32x4*>(pr + c) = t[i];
+                // (DROP: S % 32 == 0 here, so a float4 of a row is one group of the stream)
+                if constexpr (DROP) *reinterpret_cast<af32x4*>(pr + c) = drop4<true>(t[i], (pg - a.p) + c, seed, base, a.drop.threshold, a.drop.s);
+                else                *reinterpret_cast<af32x4*>(pr + c) = t[i];
                 *reinterpret_cast<af32x4*>(pg + c) = t[i];
             }
         }
@@ -268,6 +322,9 @@ __global__ void __launch_bounds__(256) attn_fwd(std::conditional_t<TAIL, AttnTai
 #pragma unroll
         for (int e = 0; e < 16; ++e)
             if (!TAIL || q0 + acc_row(e, h) < S) og[int64_t(acc_row(e, h)) * a.ldo] = acc[e];
+    }
+    if constexpr (DROP) {
+        if (tid == 0) rng_last_arriver_advances(a.drop.state, tickets, mine, order, grp, groups, a.drop.group, grid_blocks(), base);
     }
     LG_ATL(6);
 }
@@ -330,8 +387,19 @@ __device__ __forceinline__ void load_probs_tail(ProbRows<PASSES>& pr, const floa
 // dP held in LDS (pitch pp) against their probabilities y (load_probs); 8 threads per row.  The shift of every row is also
 // stored to `shift_out` (write-through: workgroups on other XCDs read it).
 // TAIL: only the first `rows` of the 32 rows exist; the others are computed on zeros and publish nothing.
-template <bool TAIL>
-__device__ __forceinline__ void softmax_bwd_rows(float* dp, int pp, const ProbRows<1>& pr, int S, float scale, double* shift_out, int rows) {
+// DROP: what the MFMAs left in LDS is dO V^T; dP is that under the mask of the forward, fl(x * s) or +0.0 (element (row, c) of the
+// block is element first + row * pitch + c of the call), and the shift is formed from the masked dP.
+struct DropRows {
+    unsigned long long seed, base;
+    uint32_t threshold;
+    float s;
+    int64_t first;                   // flat index of (first row of the block, key 0) in the dense (batch, heads, S, S) tensor
+    int pitch;                       // S
+};
+
+template <bool TAIL, bool DROP = false>
+__device__ __forceinline__ void softmax_bwd_rows(float* dp, int pp, const ProbRows<1>& pr, int S, float scale, double* shift_out, int rows,
+                                                 [[maybe_unused]] const DropRows& dr = DropRows{}) {
     const int sub = threadIdx.x & 7, row = threadIdx.x >> 3;
     float* gr = dp + row * pp;
     af32x4 g4[4];
@@ -341,6 +409,7 @@ __device__ __forceinline__ void softmax_bwd_rows(float* dp, int pp, const ProbRo
         const int c = sub * 4 + 32 * i;
         if (c < S) {
             g4[i] = *reinterpret_cast<const af32x4*>(gr + c);
+            if constexpr (DROP) g4[i] = drop4<!TAIL>(g4[i], dr.first + int64_t(row) * dr.pitch + c, dr.seed, dr.base, dr.threshold, dr.s);
 #pragma unroll
             for (int e = 0; e < 4; ++e) { const double yc = double(pr.y[0][i][e]); dot += double(g4[i][e]) * yc; norm += yc; }
         }
@@ -368,8 +437,14 @@ constexpr int attn_bwd_lds_floats(int S) {
     return query > key ? query : key;
 }
 
-template <int D, bool TAIL = false>
-__global__ void __launch_bounds__(256) attn_bwd(AttnBwdArgs a) {
+struct AttnBwdDropArgs : AttnBwdArgs {
+    AttnDrop drop;
+};
+
+// DROP: the mask of the forward again, from the seed in the generator's state and the call number the forward wrote; nothing
+// is drawn.  dP is masked in both roles after the same MFMA sequence (one multiply, the same bits), dV takes P under the mask.
+template <int D, bool TAIL = false, bool DROP = false>
+__global__ void __launch_bounds__(256) attn_bwd(std::conditional_t<DROP, AttnBwdDropArgs, AttnBwdArgs> a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int S = a.S;                               // the sequence
     const int Sp = TAIL ? round32(S) : S;            // what the tiles, the shift slab and the hand-off counter cover
@@ -387,6 +462,8 @@ __global__ void __launch_bounds__(256) attn_bwd(AttnBwdArgs a) {
     int* flags = a.flags + 2 * bh;
     constexpr int NT = D / 32;
     constexpr int NB = 32 * (D / 4) / 256 > 0 ? 32 * (D / 4) / 256 : 1, NA = 128 * (D / 4) / 256;       // float4 per thread: 32 rows / all rows
+    [[maybe_unused]] DropRows dr{};
+    if constexpr (DROP) dr = DropRows{a.drop.state[0], a.drop.base[0], a.drop.threshold, a.drop.s, (int64_t(bh) * S + j0) * S, S};
 
     LG_ATL(0);
     if (role == 0) {
@@ -427,7 +504,7 @@ __global__ void __launch_bounds__(256) attn_bwd(AttnBwdArgs a) {
         __syncthreads();
         LG_ATL(2);
         // (TAIL: over the Sp columns of the tile - a key >= S has probability 0 and dP 0, so it adds nothing and its dS is 0)
-        softmax_bwd_rows<TAIL>(Ss, PP, probs, Sp, a.scale, shifts + j0, brows);
+        softmax_bwd_rows<TAIL, DROP>(Ss, PP, probs, Sp, a.scale, shifts + j0, brows, dr);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the shifts have left this CU
         __syncthreads();
         if (tid == 0) __hip_atomic_fetch_add(flags, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // 32 more rows are published
@@ -533,8 +610,15 @@ __global__ void __launch_bounds__(256) attn_bwd(AttnBwdArgs a) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int row = 32 * wave + acc_row(e, h);
-            Dc[row * PC + r] = float(double(y[e]) * (double(dp[e]) - sh[e])) * a.scale;
-            Pc[row * PC + r] = y[e];
+            if constexpr (DROP) {
+                // element (row, j0 + r); a pair past the sequence has y = 0: 0 either way
+                const uint32_t word = rng_word((int64_t(bh) * S + row) * S + j0 + r, dr.seed, dr.base);
+                Dc[row * PC + r] = float(double(y[e]) * (double(rng_keep(dp[e], word, dr.threshold, dr.s)) - sh[e])) * a.scale;
+                Pc[row * PC + r] = rng_keep(y[e], word, dr.threshold, dr.s);
+            } else {
+                Dc[row * PC + r] = float(double(y[e]) * (double(dp[e]) - sh[e])) * a.scale;
+                Pc[row * PC + r] = y[e];
+            }
         }
     }
     __syncthreads();
@@ -767,6 +851,139 @@ extern "C" int lg_attention_masked_bwd_f32(const float* q, int64_t ldq, int64_t 
         if (rc != LG_OK) return rc;
         hipLaunchKernelGGL((attn_bwd<32, true>), grid, dim3(256), bytes, rt().stream, a);
     }
+    LG_CHECK_LAUNCH();
+    return lg_free(shift);          // stream-ordered: the block is only reused by later launches
+}
+
+// ---- attention with dropout of the probabilities: one pair for every length ------------------------------------------------
+namespace lg {
+// attention_long.hip: the launches of its DROP instantiations (129 <= S <= 512; arguments already checked)
+int attn_long_drop_fwd(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk, const float* v, int64_t ldv,
+                       int64_t sbv, float* o, int64_t ldo, int64_t sbo, float* p, int64_t batch, int64_t heads, int64_t S, int64_t D,
+                       float scale, const float* mask, int64_t sbm, const AttnDrop& drop);
+int attn_long_drop_bwd(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk, const float* v, int64_t ldv,
+                       int64_t sbv, const float* g, int64_t ldg, int64_t sbg, const float* p, float* dq, int64_t lddq, int64_t sbdq,
+                       float* dk, int64_t lddk, int64_t sbdk, float* dv, int64_t lddv, int64_t sbdv, int64_t batch, int64_t heads,
+                       int64_t S, int64_t D, float scale, const AttnDrop& drop);
+
+static int check_rows_write(const float* x, int64_t ld, int64_t sb, int64_t batch, int64_t S, int64_t width) {
+    const int64_t shape[3] = {batch, S, width}, strides[3] = {sb, ld, 1};
+    return adam_epilogue_check_strided(x, 4, 3, shape, strides);
+}
+
+template <int D, bool TAIL>
+static int launch_drop_fwd(const AttnDropArgs& a, dim3 grid, int Sp) {
+    const size_t bytes = size_t(TAIL ? attn_fwd_tail_lds_floats<D>(a.S) : attn_fwd_lds_floats<D>(a.S)) * 4;
+    (void)Sp;
+    int rc = allow_lds(&attn_fwd<D, TAIL, true>, bytes);
+    if (rc != LG_OK) return rc;
+    hipLaunchKernelGGL((attn_fwd<D, TAIL, true>), grid, dim3(256), bytes, rt().stream, a);
+    return LG_OK;
+}
+
+template <int D, bool TAIL>
+static int launch_drop_bwd(const AttnBwdDropArgs& a, dim3 grid, int Sp) {
+    const size_t bytes = size_t(attn_bwd_lds_floats<D>(Sp)) * 4;
+    int rc = allow_lds(&attn_bwd<D, TAIL, true>, bytes);
+    if (rc != LG_OK) return rc;
+    hipLaunchKernelGGL((attn_bwd<D, TAIL, true>), grid, dim3(256), bytes, rt().stream, a);
+    return LG_OK;
+}
+}  // namespace lg
+
+extern "C" int lg_attention_dropout_supported(int64_t S, int64_t D) {
+    return (D == 64 || D == 32) && S >= 1 && S <= 512;
+}
+
+extern "C" int lg_attention_dropout_fwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
+                                            const float* v, int64_t ldv, int64_t sbv, float* o, int64_t ldo, int64_t sbo, float* p,
+                                            int64_t batch, int64_t heads, int64_t S, int64_t D, float scale,
+                                            const float* mask, int64_t sbm, double prob, uint64_t* base_out) {
+    LG_REQUIRE_INIT();
+    LG_ARG(lg_attention_dropout_supported(S, D), "lg_attention_dropout_fwd_f32: S = %lld (1..512), D = %lld (32 or 64) unsupported",
+           (long long)S, (long long)D);
+    LG_ARG(prob >= 0.0 && prob < 1.0, "lg_attention_dropout_fwd_f32: p = %g outside [0, 1)", prob);
+    LG_ARG(base_out != nullptr, "lg_attention_dropout_fwd_f32: base_out is NULL");
+    LG_ARG(batch >= 0 && heads >= 1 && batch <= 65535 && heads <= 65535, "lg_attention_dropout_fwd_f32: bad batch / heads");
+    LG_ARG(batch > 0, "lg_attention_dropout_fwd_f32: an empty batch draws nothing (batch must be >= 1)");
+    LG_ARG(ok_operand(q, ldq, sbq) && ok_operand(k, ldk, sbk) && ok_operand(v, ldv, sbv) && ok_operand(o, ldo, sbo) && p && aligned16(p),
+           "lg_attention_dropout_fwd_f32: operands must be non-NULL and 16-byte aligned with pitches that are multiples of 4");
+    LG_ARG(ldq >= heads * D && ldk >= heads * D && ldv >= heads * D && ldo >= heads * D, "lg_attention_dropout_fwd_f32: row pitch below heads * D");
+    LG_ARG(!mask || sbm == 0 || sbm >= S, "lg_attention_dropout_fwd_f32: mask batch pitch %lld is neither 0 (one row for the batch) nor >= S",
+           (long long)sbm);
+    const int Sp = round32(int(S));
+    const int64_t wgs = int64_t(Sp / 32) * heads * batch;
+    LG_ARG(wgs <= int64_t(kRngMaxGroup) * kRngMaxGroup, "lg_attention_dropout_fwd_f32: %lld workgroups, more than the stream's tickets count", (long long)wgs);
+    { int rc = check_rows_write(o, ldo, sbo, batch, S, heads * D); if (rc != LG_OK) return rc; }
+    { int rc = adam_epilogue_check_write(p, batch * heads * S * S * 4); if (rc != LG_OK) return rc; }
+    { int rc = adam_epilogue_check_write(base_out, 8); if (rc != LG_OK) return rc; }
+    AttnDrop drop{rt().rng_state, reinterpret_cast<unsigned long long*>(base_out), 0u, 0.f, rng_group(unsigned(wgs))};
+    rng_threshold(prob, drop.threshold, drop.s);
+    if (S > 128) {
+        const int rc = attn_long_drop_fwd(q, ldq, sbq, k, ldk, sbk, v, ldv, sbv, o, ldo, sbo, p, batch, heads, S, D, scale, mask, sbm, drop);
+        if (rc != LG_OK) return rc;
+        LG_CHECK_LAUNCH();
+        return LG_OK;
+    }
+    AttnDropArgs a{{{
+#ifdef LG_GEMM_TIMELINE
+        timeline_buffer(int(wgs)),
+#endif
+        q, k, v, ldq, sbq, ldk, sbk, ldv, sbv, o, ldo, sbo, p, int(S), int(heads), scale}, mask, sbm}, drop};
+    const dim3 grid(unsigned(Sp / 32), unsigned(heads), unsigned(batch));
+    const bool plain = !mask && S % 32 == 0;
+    const int rc = D == 64 ? (plain ? launch_drop_fwd<64, false>(a, grid, Sp) : launch_drop_fwd<64, true>(a, grid, Sp))
+                           : (plain ? launch_drop_fwd<32, false>(a, grid, Sp) : launch_drop_fwd<32, true>(a, grid, Sp));
+    if (rc != LG_OK) return rc;
+    LG_CHECK_LAUNCH();
+    return LG_OK;
+}
+
+extern "C" int lg_attention_dropout_bwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
+                                            const float* v, int64_t ldv, int64_t sbv, const float* g, int64_t ldg, int64_t sbg,
+                                            const float* p, float* dq, int64_t lddq, int64_t sbdq, float* dk, int64_t lddk, int64_t sbdk,
+                                            float* dv, int64_t lddv, int64_t sbdv, int64_t batch, int64_t heads, int64_t S, int64_t D,
+                                            float scale, double prob, const uint64_t* base) {
+    LG_REQUIRE_INIT();
+    LG_ARG(lg_attention_dropout_supported(S, D), "lg_attention_dropout_bwd_f32: S = %lld (1..512), D = %lld (32 or 64) unsupported",
+           (long long)S, (long long)D);
+    LG_ARG(prob >= 0.0 && prob < 1.0, "lg_attention_dropout_bwd_f32: p = %g outside [0, 1)", prob);
+    LG_ARG(base != nullptr, "lg_attention_dropout_bwd_f32: base is NULL");
+    LG_ARG(batch >= 0 && heads >= 1 && batch <= 65535 && heads <= 65535, "lg_attention_dropout_bwd_f32: bad batch / heads");
+    if (batch == 0) return LG_OK;
+    LG_ARG(ok_operand(q, ldq, sbq) && ok_operand(k, ldk, sbk) && ok_operand(v, ldv, sbv) && ok_operand(g, ldg, sbg) &&
+               ok_operand(dq, lddq, sbdq) && ok_operand(dk, lddk, sbdk) && ok_operand(dv, lddv, sbdv) && p && aligned16(p),
+           "lg_attention_dropout_bwd_f32: operands must be non-NULL and 16-byte aligned with pitches that are multiples of 4");
+    const int64_t w = heads * D;
+    LG_ARG(ldq >= w && ldk >= w && ldv >= w && ldg >= w && lddq >= w && lddk >= w && lddv >= w, "lg_attention_dropout_bwd_f32: row pitch below heads * D");
+    LG_ARG(batch * heads <= rt().n_attn_pairs && 2 * batch <= 65535, "lg_attention_dropout_bwd_f32: more than %d (batch, head) pairs in one launch",
+           rt().n_attn_pairs);
+    { int rc = check_rows_write(dq, lddq, sbdq, batch, S, w); if (rc != LG_OK) return rc; }
+    { int rc = check_rows_write(dk, lddk, sbdk, batch, S, w); if (rc != LG_OK) return rc; }
+    { int rc = check_rows_write(dv, lddv, sbdv, batch, S, w); if (rc != LG_OK) return rc; }
+    AttnDrop drop{rt().rng_state, const_cast<unsigned long long*>(reinterpret_cast<const unsigned long long*>(base)), 0u, 0.f, 0};
+    rng_threshold(prob, drop.threshold, drop.s);
+    if (S > 128)
+        return attn_long_drop_bwd(q, ldq, sbq, k, ldk, sbk, v, ldv, sbv, g, ldg, sbg, p, dq, lddq, sbdq, dk, lddk, sbdk, dv, lddv, sbdv,
+                                  batch, heads, S, D, scale, drop);
+    const int Sp = round32(int(S));
+    double* shift = nullptr;
+    {
+        const int mrc = lg_malloc(reinterpret_cast<void**>(&shift), size_t(batch * heads * Sp) * sizeof(double));
+        if (mrc != LG_OK) return mrc;
+    }
+    AttnBwdDropArgs a{{
+#ifdef LG_GEMM_TIMELINE
+        timeline_buffer(int(2 * (Sp / 32) * heads * batch)),
+#endif
+        q, k, v, g, ldq, sbq, ldk, sbk, ldv, sbv, ldg, sbg, p, dq, dk, dv, lddq, sbdq, lddk, sbdk, lddv, sbdv, int(S), int(heads), int(batch), scale,
+        shift, rt().attn_flags, rt().status_dev}, drop};
+    const dim3 grid(unsigned(Sp / 32), unsigned(heads), unsigned(2 * batch));
+    // (which forward ran - plain or tail - makes no difference to the backward's bits; the plain kernels take what they can)
+    const bool plain = S % 32 == 0;
+    const int rc = D == 64 ? (plain ? launch_drop_bwd<64, false>(a, grid, Sp) : launch_drop_bwd<64, true>(a, grid, Sp))
+                           : (plain ? launch_drop_bwd<32, false>(a, grid, Sp) : launch_drop_bwd<32, true>(a, grid, Sp));
+    if (rc != LG_OK) { lg_free(shift); return rc; }
     LG_CHECK_LAUNCH();
     return lg_free(shift);          // stream-ordered: the block is only reused by later launches
 }

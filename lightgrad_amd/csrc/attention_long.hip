@@ -24,7 +24,9 @@
 // already running and wait for nothing - does not depend on occupancy.
 #include "common.h"
 #include "mfma_lds.h"
+#include "rng_common.h"
 #include <cmath>
+#include <type_traits>
 
 namespace lg {
 
@@ -58,6 +60,38 @@ struct AttnLongBwdArgs {
     int*    status;                  // device status flag (a wait that gives up raises it)
 };
 
+// DROP instantiations: the same arguments and the call of the random stream (rng_common.h)
+struct AttnLongDropArgs : AttnLongArgs {
+    AttnDrop drop;
+};
+struct AttnLongBwdDropArgs : AttnLongBwdArgs {
+    AttnDrop drop;
+};
+
+// the two 64-bit words of a call in LDS (DROP instantiations only: 16 bytes of static LDS next to the dynamic tiles)
+template <bool DROP>
+__device__ __forceinline__ unsigned long long* long_rng_call_slot() {
+    if constexpr (DROP) {
+        __shared__ unsigned long long call[2];
+        return call;
+    } else {
+        return nullptr;
+    }
+}
+
+// linear index of this workgroup over the 3-D grid / workgroups of the launch: what the tickets of the random stream count
+__device__ __forceinline__ int long_grid_linear_block() { return int((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x); }
+__device__ __forceinline__ int long_grid_blocks() { return int(gridDim.x * gridDim.y * gridDim.z); }
+
+// a float4 at flat element index i of the dense (batch, heads, S, S) tensor under the mask of the call: x * s where the stream
+// keeps the element, +0.0 where it drops it (S % 4 != 0: the four words can come from two groups)
+__device__ __forceinline__ af32x4 long_drop4(af32x4 t, int64_t i, unsigned long long seed, unsigned long long base, uint32_t threshold, float s) {
+    uint32_t w[4];
+    rng_words4<false>(i, seed, base, w);
+    return af32x4{rng_keep(t[0], w[0], threshold, s), rng_keep(t[1], w[1], threshold, s), rng_keep(t[2], w[2], threshold, s),
+                  rng_keep(t[3], w[3], threshold, s)};
+}
+
 // store_rows that also clears rows [rows, padded): an MFMA operand row past the sequence must be zero, not stale LDS
 template <int D, int N>
 __device__ __forceinline__ void long_store_rows(const af32x4 (&v)[N], float* dst, int pitch, int rows, int padded) {
@@ -90,8 +124,10 @@ __device__ __forceinline__ void chunk_store(const af32x4 (&v)[N], float* dst, in
 template <int D>
 constexpr int attn_long_fwd_lds_floats(int Sp) { return 32 * (D + 4) + 32 * (Sp + 4) + kLongChunk * (D + 8) + 3 * 1024 + Sp; }
 
-template <int D>
-__global__ void __launch_bounds__(256) attn_long_fwd(AttnLongArgs a) {
+// DROP: dropout of the probabilities between the softmax and the context, from the stream of dropout.hip (one call per launch:
+// read `draws`, take a ticket, the last arriver advances).  P goes to HBM undropped; what feeds the context MFMAs is Pd.
+template <int D, bool DROP = false>
+__global__ void __launch_bounds__(256) attn_long_fwd(std::conditional_t<DROP, AttnLongDropArgs, AttnLongArgs> a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int S = a.S, Sp = long_pad32(S), PP = Sp + 4;
     constexpr int PQ = D + 4, PV = D + 8;
@@ -106,6 +142,21 @@ __global__ void __launch_bounds__(256) attn_long_fwd(AttnLongArgs a) {
     const int qrows = S - q0 < 32 ? S - q0 : 32;                      // rows of this block that exist: a row past them is never read
     const float* kg = a.k + int64_t(b) * a.sbk + head * D;
     const float* vg = a.v + int64_t(b) * a.sbv + head * D;
+    [[maybe_unused]] unsigned long long* const call = long_rng_call_slot<DROP>();
+    [[maybe_unused]] int order = 0, grp = 0, groups = 0;
+    [[maybe_unused]] int* tickets = nullptr;
+    [[maybe_unused]] int* mine = nullptr;
+    if constexpr (DROP) {
+        tickets = rng_tickets(a.drop.state);
+        grp = long_grid_linear_block() / a.drop.group;
+        groups = (long_grid_blocks() + a.drop.group - 1) / a.drop.group;
+        mine = tickets + (1 + grp) * kRngLine;
+        if (tid == 0) {
+            rng_read_call(a.drop.state, call);                        // `draws` is in a register before the ticket is taken
+            if (long_grid_linear_block() == 0) a.drop.base[0] = call[1];
+            order = rng_take_ticket(mine);
+        }
+    }
 
     af32x4 rc[NA];
     {
@@ -141,6 +192,9 @@ __global__ void __launch_bounds__(256) attn_long_fwd(AttnLongArgs a) {
     // exp(x - max) * (1 / sum) (autograd/ops.py:62-66) over the keys that exist: a key >= S is no part of the max or the sum,
     // its column of the LDS tile becomes 0 (it is an MFMA operand of the context) and nothing of it is stored
     {
+        // (the barriers of the score chunks lie between thread 0's write of the call and these reads)
+        [[maybe_unused]] unsigned long long seed = 0, base = 0;
+        if constexpr (DROP) { seed = rng_uniform64(call[0]); base = rng_uniform64(call[1]); }
         const int row = tid >> 3, sub = tid & 7;
         float* pr = Ps + row * PP;
         af32x4 t[kLongMaxBlocks];
@@ -180,7 +234,9 @@ __global__ void __launch_bounds__(256) attn_long_fwd(AttnLongArgs a) {
             if (c < Sp) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) t[i][e] *= inv;
-                *reinterpret_cast<af32x4*>(pr + c) = t[i];
+                // (DROP: a key >= S holds 0 and stays 0 whatever word it meets; a row >= S is never stored)
+                if constexpr (DROP) *reinterpret_cast<af32x4*>(pr + c) = long_drop4(t[i], (pg - a.p) + c, seed, base, a.drop.threshold, a.drop.s);
+                else                *reinterpret_cast<af32x4*>(pr + c) = t[i];
                 if (row_exists) {
                     if ((S & 3) == 0) {
                         if (c < S) *reinterpret_cast<af32x4*>(pg + c) = t[i];
@@ -222,6 +278,10 @@ __global__ void __launch_bounds__(256) attn_long_fwd(AttnLongArgs a) {
         for (int e = 0; e < 16; ++e)
             if (acc_row(e, h) < qrows) og[int64_t(acc_row(e, h)) * a.ldo] = acc[e];
     }
+    if constexpr (DROP) {
+        if (tid == 0)
+            rng_last_arriver_advances(a.drop.state, tickets, mine, order, grp, groups, a.drop.group, long_grid_blocks(), rng_uniform64(call[1]));
+    }
 }
 
 // floats of LDS: the larger of the two roles
@@ -232,8 +292,11 @@ constexpr int attn_long_bwd_lds_floats(int Sp) {
     return query > key ? query : key;
 }
 
-template <int D>
-__global__ void __launch_bounds__(256) attn_long_bwd(AttnLongBwdArgs a) {
+// DROP: the mask of the forward again, from the seed in the generator's state and the call number the forward wrote; nothing
+// is drawn.  dP is masked in both roles after the same MFMA sequence (one multiply, the same bits); the key role forms dS from
+// the undropped P[chunk, block] in registers and stores that tile under the mask for dV: no second tile.
+template <int D, bool DROP = false>
+__global__ void __launch_bounds__(256) attn_long_bwd(std::conditional_t<DROP, AttnLongBwdDropArgs, AttnLongBwdArgs> a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int S = a.S, Sp = long_pad32(S);           // the sequence / what the tiles, the shift slab and the hand-off counter cover
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
@@ -253,6 +316,8 @@ __global__ void __launch_bounds__(256) attn_long_bwd(AttnLongBwdArgs a) {
     const float* kg = a.k + int64_t(b) * a.sbk + head * D;
     const float* vg = a.v + int64_t(b) * a.sbv + head * D;
     const float* gg = a.g + int64_t(b) * a.sbg + head * D;
+    [[maybe_unused]] unsigned long long seed = 0, base = 0;
+    if constexpr (DROP) { seed = a.drop.state[0]; base = a.drop.base[0]; }
 
     if (role == 0) {
         // ---- query role: dQ of queries [j0, j0 + 32), and the shift of their rows for the key role ------------------
@@ -315,7 +380,13 @@ __global__ void __launch_bounds__(256) attn_long_bwd(AttnLongBwdArgs a) {
             for (int i = 0; i < kLongMaxBlocks; ++i) {
                 const int c = sub * 4 + 32 * i;
                 if (c < Sp) {
-                    const af32x4 g4 = *reinterpret_cast<const af32x4*>(gr + c);
+                    af32x4 g4 = *reinterpret_cast<const af32x4*>(gr + c);
+                    if constexpr (DROP) {
+                        // what the MFMAs left is dO V^T: dP is that under the forward's mask, kept for the pass below (this
+                        // thread's own float4: no barrier); the shift is formed from the masked dP
+                        g4 = long_drop4(g4, (int64_t(bh) * S + j0 + row) * S + c, seed, base, a.drop.threshold, a.drop.s);
+                        *reinterpret_cast<af32x4*>(gr + c) = g4;
+                    }
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { const double yc = double(y[i][e]); dot += double(g4[e]) * yc; norm += yc; }
                 }
@@ -445,8 +516,15 @@ __global__ void __launch_bounds__(256) attn_long_bwd(AttnLongBwdArgs a) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int row = 32 * wave + acc_row(e, h);
-                Dc[row * PC + r] = float(double(y[e]) * (double(dp[e]) - sh[e])) * a.scale;
-                Pc[row * PC + r] = y[e];
+                if constexpr (DROP) {
+                    // element (c0 + row, j0 + r); a pair past the sequence has y = 0: 0 either way
+                    const uint32_t word = rng_word((int64_t(bh) * S + c0 + row) * S + j0 + r, seed, base);
+                    Dc[row * PC + r] = float(double(y[e]) * (double(rng_keep(dp[e], word, a.drop.threshold, a.drop.s)) - sh[e])) * a.scale;
+                    Pc[row * PC + r] = rng_keep(y[e], word, a.drop.threshold, a.drop.s);
+                } else {
+                    Dc[row * PC + r] = float(double(y[e]) * (double(dp[e]) - sh[e])) * a.scale;
+                    Pc[row * PC + r] = y[e];
+                }
             }
         }
         __syncthreads();
@@ -491,6 +569,58 @@ static int long_allow_lds(K kernel, size_t bytes) {
 }
 
 static bool long_ok_operand(const void* p, int64_t ld, int64_t sb) { return p && aligned16(p) && ld % 4 == 0 && sb % 4 == 0; }
+
+// the launches behind lg_attention_dropout_*_f32 (attention.hip, which has checked the arguments) for 129 <= S <= 512
+int attn_long_drop_fwd(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk, const float* v, int64_t ldv,
+                       int64_t sbv, float* o, int64_t ldo, int64_t sbo, float* p, int64_t batch, int64_t heads, int64_t S, int64_t D,
+                       float scale, const float* mask, int64_t sbm, const AttnDrop& drop) {
+    const int Sp = long_pad32(int(S));
+    AttnLongDropArgs a{{q, k, v, ldq, sbq, ldk, sbk, ldv, sbv, o, ldo, sbo, p, int(S), int(heads), scale, mask, sbm}, drop};
+    const dim3 grid(unsigned(Sp / 32), unsigned(heads), unsigned(batch));
+    if (D == 64) {
+        const size_t bytes = size_t(attn_long_fwd_lds_floats<64>(Sp)) * 4;
+        int rc = long_allow_lds(&attn_long_fwd<64, true>, bytes);
+        if (rc != LG_OK) return rc;
+        hipLaunchKernelGGL((attn_long_fwd<64, true>), grid, dim3(256), bytes, rt().stream, a);
+    } else {
+        const size_t bytes = size_t(attn_long_fwd_lds_floats<32>(Sp)) * 4;
+        int rc = long_allow_lds(&attn_long_fwd<32, true>, bytes);
+        if (rc != LG_OK) return rc;
+        hipLaunchKernelGGL((attn_long_fwd<32, true>), grid, dim3(256), bytes, rt().stream, a);
+    }
+    return LG_OK;
+}
+
+int attn_long_drop_bwd(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk, const float* v, int64_t ldv,
+                       int64_t sbv, const float* g, int64_t ldg, int64_t sbg, const float* p, float* dq, int64_t lddq, int64_t sbdq,
+                       float* dk, int64_t lddk, int64_t sbdk, float* dv, int64_t lddv, int64_t sbdv, int64_t batch, int64_t heads,
+                       int64_t S, int64_t D, float scale, const AttnDrop& drop) {
+    const int Sp = long_pad32(int(S));
+    double* shift = nullptr;
+    {
+        const int mrc = lg_malloc(reinterpret_cast<void**>(&shift), size_t(batch * heads * Sp) * sizeof(double));
+        if (mrc != LG_OK) return mrc;
+    }
+    AttnLongBwdDropArgs a{{q, k, v, g, ldq, sbq, ldk, sbk, ldv, sbv, ldg, sbg, p, dq, dk, dv, lddq, sbdq, lddk, sbdk, lddv, sbdv,
+                           int(S), int(heads), int(batch), scale, shift, rt().attn_flags, rt().status_dev}, drop};
+    const dim3 grid(unsigned(Sp / 32), unsigned(heads), unsigned(2 * batch));
+    int rc = LG_OK;
+    if (D == 64) {
+        const size_t bytes = size_t(attn_long_bwd_lds_floats<64>(Sp)) * 4;
+        rc = long_allow_lds(&attn_long_bwd<64, true>, bytes);
+        if (rc == LG_OK) hipLaunchKernelGGL((attn_long_bwd<64, true>), grid, dim3(256), bytes, rt().stream, a);
+    } else {
+        const size_t bytes = size_t(attn_long_bwd_lds_floats<32>(Sp)) * 4;
+        rc = long_allow_lds(&attn_long_bwd<32, true>, bytes);
+        if (rc == LG_OK) hipLaunchKernelGGL((attn_long_bwd<32, true>), grid, dim3(256), bytes, rt().stream, a);
+    }
+    if (rc == LG_OK && hipGetLastError() != hipSuccess) {
+        set_error("lg_attention_dropout_bwd_f32: kernel launch failed");
+        rc = LG_EHIP;
+    }
+    const int frc = lg_free(shift);          // stream-ordered: the block is only reused by later launches
+    return rc != LG_OK ? rc : frc;
+}
 
 }  // namespace lg
 

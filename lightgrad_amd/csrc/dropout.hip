@@ -14,28 +14,9 @@
 // workgroups of 2^28 elements.  A group holds g workgroups, g the power of two with g * g >= workgroups: the longest chain is
 // g + g adds (2^28 elements: 13 us, under the time the data takes), and no size takes another path.
 #include "common.h"
+#include "rng_common.h"
 
 namespace lg {
-
-constexpr int kRngMaxGroup = 4096;                 // workgroups per first-level ticket, at most: 2^24 workgroups, 2^34 elements a call
-constexpr int64_t kRngMaxElements = int64_t(kRngMaxGroup) * kRngMaxGroup * 1024;
-constexpr int kRngGroups = kRngMaxGroup;           // first-level tickets
-constexpr int kRngLine = 16;                       // ints per ticket line (64 bytes: what one memory-side atomic request covers)
-// layout of Runtime::rng_state (64-bit words): [0] seed, [1] draws; from byte 128 on the ticket lines: the top one, then the groups'
-constexpr size_t kRngTicketByte = 128;
-constexpr size_t kRngStateBytes = kRngTicketByte + size_t(kRngGroups + 1) * kRngLine * sizeof(int);
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                               uint32_t (&out)[4]) {
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const uint64_t p0 = uint64_t(0xD2511F53u) * c0, p1 = uint64_t(0xCD9E8D57u) * c2;     // (one 32 x 32 -> 64 multiply each)
-        const uint32_t n0 = uint32_t(p1 >> 32) ^ c1 ^ k0, n2 = uint32_t(p0 >> 32) ^ c3 ^ k1;
-        c0 = n0; c1 = uint32_t(p1); c2 = n2; c3 = uint32_t(p0);
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 
 // x * s for a kept element, +0.0 for a dropped one (a select: a dropped NaN or infinity becomes +0.0 too); with a residual the
 // sum is a second rounding, and a dropped element is +0.0 + r like the numpy expression
@@ -79,37 +60,21 @@ template <bool RES, bool VEC>
 __global__ void __launch_bounds__(256) dropout_fwd(const float* x, const float* res, float* y, int64_t n, uint32_t threshold, float s,
                                                    unsigned long long* state, unsigned long long* base_out, int group) {
     __shared__ unsigned long long call[2];
-    int* const tickets = reinterpret_cast<int*>(reinterpret_cast<char*>(state) + kRngTicketByte);
+    int* const tickets = rng_tickets(state);
     if (threadIdx.x == 0) {
-        call[0] = state[0];
-        call[1] = __hip_atomic_load(state + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // `draws` is in a register before the ticket below is taken
+        rng_read_call(state, call);                                // `draws` is in a register before the ticket below is taken
         if (blockIdx.x == 0) base_out[0] = call[1];
     }
     __syncthreads();
     int order = 0;
     const int grp = blockIdx.x / group, groups = (gridDim.x + group - 1) / group;
     int* const mine = tickets + (1 + grp) * kRngLine;
-    if (threadIdx.x == 0) order = __hip_atomic_fetch_add(mine, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // (uniform values out of LDS: in scalar registers the ten key additions of a Philox call cost no vector instruction)
-    const uint32_t seed_lo = __builtin_amdgcn_readfirstlane(uint32_t(call[0])), seed_hi = __builtin_amdgcn_readfirstlane(uint32_t(call[0] >> 32));
-    const uint32_t base_lo = __builtin_amdgcn_readfirstlane(uint32_t(call[1])), base_hi = __builtin_amdgcn_readfirstlane(uint32_t(call[1] >> 32));
-    const unsigned long long seed = (static_cast<unsigned long long>(seed_hi) << 32) | seed_lo;
-    const unsigned long long base = (static_cast<unsigned long long>(base_hi) << 32) | base_lo;
+    if (threadIdx.x == 0) order = rng_take_ticket(mine);
+    const unsigned long long seed = rng_uniform64(call[0]), base = rng_uniform64(call[1]);
 
     drop_items<RES, VEC>(x, res, y, n, threshold, s, seed, base);
 
-    if (threadIdx.x == 0) {
-        const int in_group = grp == groups - 1 ? int(gridDim.x) - grp * group : group;
-        if (order == in_group - 1) {                               // last of its group: every workgroup of the group has read `draws`
-            __hip_atomic_store(mine, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            int* const top = tickets;
-            if (__hip_atomic_fetch_add(top, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == groups - 1) {     // last group: so has every workgroup
-                __hip_atomic_store(top, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(state + 1, base + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    }
+    if (threadIdx.x == 0) rng_last_arriver_advances(state, tickets, mine, order, grp, groups, group, int(gridDim.x), base);
 }
 
 template <bool VEC>
@@ -134,20 +99,6 @@ int rng_init() {
 static unsigned rng_grid(int64_t n) {
     const int64_t need = ((n + 3) / 4 + 255) / 256;
     return unsigned(need < 1 ? 1 : need);
-}
-
-// workgroups per first-level ticket: the power of two g with g * g >= workgroups (and (g / 2)^2 < workgroups)
-static int rng_group(unsigned blocks) {
-    int g = 1;
-    while (int64_t(g) * g < int64_t(blocks)) g *= 2;
-    return g;
-}
-
-// T and s as the stream's definition gives them: both computed in double on the host, s rounded to float32 once
-static void rng_threshold(double p, uint32_t& threshold, float& s) {
-    const double t = p * 4294967296.0;
-    threshold = t >= 4294967295.0 ? 4294967295u : uint32_t(t);
-    s = float(1.0 / (1.0 - p));
 }
 
 }  // namespace lg

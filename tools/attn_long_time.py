@@ -3,6 +3,11 @@
 (8, 512, 2, 64), with and without a key-padding mask:
 
     python tools/attn_long_time.py [--rounds 3] [--iters 300] [--out profiles/attention_long.txt]
+    python tools/attn_long_time.py --dropout 0.1 --out profiles/attention_dropout.txt
+
+With --dropout p both routes drop the probabilities with probability p - the fused node inside its two attention launches
+(dropout=p), the composite with `probs.dropout(p)` between the softmax and the context product, the path such a model took before the
+kernels drew masks - at tiny-BERT's shape (8, 128, 2 heads, d = 64: 16 (batch, head) pairs) and at (8, 512, 2, 64), without a mask.
 
 Both routes start from the same (b, s, hidden) input and the same three projection weights, like BertSelfAttention.forward: the
 fused route is the one node, the composite route three nn.Linear products, the head split by strides, the scores GEMM, divide,
@@ -19,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def measure(route, b, s, heads, d, masked, iters):
+def measure(route, b, s, heads, d, masked, iters, dropout=0.0):
     """{"eager_us", "graph_us"} of one forward + backward of `route` ("fused" or "composite")"""
     import numpy as np
     from lightgrad_amd import HipTensor
@@ -46,7 +51,8 @@ def measure(route, b, s, heads, d, masked, iters):
         for t in [x] + params:
             t.zero_grad()
         if route == "fused":
-            out = x.self_attention(*params, heads=heads, scale=scale, **({"mask": mask} if masked else {}))
+            out = x.self_attention(*params, heads=heads, scale=scale, **({"mask": mask} if masked else {}),
+                                   **({"dropout": dropout} if dropout > 0 else {}))
         else:                                                          # examples/bert.py, the composite lines
             q, k, v = (x.linear(params[2 * i], params[2 * i + 1]) if hasattr(x, "linear") else x @ params[2 * i].transpose(1, 0) + params[2 * i + 1]
                        for i in range(3))
@@ -59,6 +65,8 @@ def measure(route, b, s, heads, d, masked, iters):
             else:
                 scores = scores / math.sqrt(d) + ((1.0 - mask.reshape(b, 1, 1, s)) * -10000.0).detach()
                 probs = scores.softmax(axis=-1)
+            if dropout > 0:
+                probs = probs.dropout(dropout)
             out = (probs @ v4).transpose(0, 2, 1, 3).reshape(b, s, width)
         (out * w).backward(allow_fill=True)
 
@@ -92,6 +100,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--iters", type=int, default=300)
+    ap.add_argument("--dropout", type=float, default=0.0)
     ap.add_argument("--out")
     args = ap.parse_args()
     lines = []
@@ -102,9 +111,11 @@ def main():
 
     say("self-attention forward + backward beyond 128 positions (projections included), fused node (long launches) against the composite tape "
         "of this build, us per step, %d rounds of %d steps:" % (args.rounds, args.iters))
-    for shape in ((8, 256, 2, 64), (8, 512, 2, 64)):
-        for masked in (True, False):
-            res = {route: [measure(route, *shape, masked, args.iters) for _ in range(args.rounds)] for route in ("fused", "composite")}
+    if args.dropout > 0:
+        say("dropout of the probabilities with p = %g on both routes" % args.dropout)
+    for shape in ((8, 128, 2, 64), (8, 512, 2, 64)) if args.dropout > 0 else ((8, 256, 2, 64), (8, 512, 2, 64)):
+        for masked in (False,) if args.dropout > 0 else (True, False):
+            res = {route: [measure(route, *shape, masked, args.iters, args.dropout) for _ in range(args.rounds)] for route in ("fused", "composite")}
             for key in ("graph_us", "eager_us"):
                 f, c = [r[key] for r in res["fused"]], [r[key] for r in res["composite"]]
                 say("  %-22s %-12s %-9s fused %s   composite %s   composite / fused %.2f"

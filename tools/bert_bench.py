@@ -49,7 +49,10 @@ def main():
     bert = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bert)
     np.random.seed(0)
-    model = bert.BertForMaskedLM(**bert.TINY).map_parameters(lambda t: t.hip())
+    # --attention-dropout p / --hidden-dropout p: the model in training mode with these probabilities (0: the benchmarked step)
+    drop = {key: float(sys.argv[sys.argv.index(flag) + 1]) for flag, key in (("--attention-dropout", "attention_probs_dropout_prob"),
+                                                                              ("--hidden-dropout", "hidden_dropout_prob")) if flag in sys.argv}
+    model = bert.BertForMaskedLM(**bert.TINY, **drop).map_parameters(lambda t: t.hip())
     ids = HipTensor.from_numpy(np.random.randint(0, bert.TINY["vocab_size"], (8, 128)).astype(np.int32), requires_grad=False)
     labels = HipTensor.from_numpy(np.random.randint(0, bert.TINY["vocab_size"], (8 * 128,)).astype(np.int64), requires_grad=False)
     dp = DataParallel(model.parameters(), SingleProcess(), flatten=True)
@@ -78,7 +81,9 @@ def main():
     for _ in range(replays):
         graph.replay()
     HipDevice.synchronize()
-    print("hipGraph:   %.3f ms per forward+backward over %d replays, loss %.6f" % (1e3 * (time.perf_counter() - t0) / replays, replays, state["loss"].item()))
+    print("hipGraph:   %.3f ms per forward+backward over %d replays, loss %.6f, %d kernels in the graph%s"
+          % (1e3 * (time.perf_counter() - t0) / replays, replays, state["loss"].item(), graph.kernel_count(),
+             "  (%s)" % ", ".join("%s = %g" % kv for kv in sorted(drop.items())) if drop else ""))
 
 
 if __name__ == "__main__":
