@@ -12,7 +12,8 @@ Differences from the reference, on purpose:
   * dropout is real: `hidden_dropout_prob` after the embedding LayerNorm, the attention output projection and the feed-forward
     output projection, `attention_probs_dropout_prob` on the attention probabilities (the reference takes both arguments and
     then sets `self.dropout = lambda x: x`, bert.py:37, :67, :102, :124).  Both default to 0, and with 0 or in `model.eval()`
-    every site takes exactly the path it took before.
+    every site takes exactly the path it took before.  Each hidden dropout sits next to a LayerNorm: where the backend has the
+    one-launch forms (`layer_norm_dropout`, `dropout_add_layer_norm`) the pair is one node, with the same masks.
 
     python examples/bert.py [--cpu] [--batch 8]        # forward + backward of a random tiny-BERT
 """
@@ -75,6 +76,9 @@ class BertEmbedding(nn.Module):
             e = word.embedding_sum(position, kind, ids0=input_ids, ids1=position_ids, ids2=token_type_ids)
         else:
             e = self.word_embeddings(input_ids) + self.position_embeddings(position_ids) + self.token_type_embeddings(token_type_ids)
+        if self.training and self.dropout.p > 0 and hasattr(e, "layer_norm_dropout"):
+            # the backend's one-launch form of the line below: the mask is drawn where the LayerNorm kernel stores its row
+            return e.layer_norm_dropout(self.LayerNorm.weight, self.LayerNorm.bias, self.dropout.p, self.LayerNorm.eps)
         return self.dropout(self.LayerNorm(e))
 
 
@@ -150,7 +154,11 @@ class BertAttention(nn.Module):
     def forward(self, hidden_in, attention_mask=None):
         hidden, probs = self.self(hidden_in, attention_mask=attention_mask)
         if self.training and self.dropout.p > 0:
-            # dropout sits between the product and the residual addition: one kernel for both instead of the GEMM's epilogue
+            # dropout sits between the product and the residual addition, so the addition leaves the GEMM's epilogue
+            norm = self.output.LayerNorm
+            if hasattr(hidden, "dropout_add_layer_norm"):
+                # the backend's one-launch form of dropout, addition and LayerNorm: the mask is drawn where the kernel loads its row
+                return self.output.dense(hidden).dropout_add_layer_norm(hidden_in, norm.weight, norm.bias, self.dropout.p, norm.eps), probs
             hidden = self.dropout(self.output.dense(hidden), residual=hidden_in)
         else:
             hidden = self.output.dense(hidden, residual=hidden_in)                        # dense(hidden) + hidden_in
@@ -171,6 +179,11 @@ class BertLayer(nn.Module):
     def forward(self, hidden, attention_mask=None):
         hidden, probs = self.attention(hidden, attention_mask)
         if self.training and self.dropout.p > 0:
+            if hasattr(hidden, "feed_forward") and hasattr(hidden, "dropout_add_layer_norm"):
+                # the one-node feed-forward without its residual, then dropout, addition and LayerNorm in one launch
+                up, down, norm = self.intermediate.dense, self.output.dense, self.output.LayerNorm
+                out = hidden.feed_forward(up.weight, up.bias, down.weight, down.bias)
+                return out.dropout_add_layer_norm(hidden, norm.weight, norm.bias, self.dropout.p, norm.eps), probs
             hidden = self.dropout(self.output.dense(gelu(self.intermediate.dense(hidden))), residual=hidden)
         elif hasattr(hidden, "feed_forward"):
             # the backend's one-node form of the line below: gelu and residual in the products' epilogues, four launches for six

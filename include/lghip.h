@@ -616,7 +616,7 @@ int lg_scatter_add_rows_f32(const float* grad_out, const void* ids, int id_items
  * lg_gather_rows_f32 decided: host bookkeeping for tests, no device work.
  *   out = {kernel, a, b, queued}
  * kernel: 0 = softmax forward, 1 = softmax backward, 2 = LayerNorm forward, 3 = LayerNorm backward, 4 = LayerNorm parameter
- * gradients, 5 = scatter-add, 6 = gather, -1 = nothing launched or queued (an empty or refused call: the other fields are 0);
+ * gradients, 5 = scatter-add, 6 = gather, 7 / 8 = lg_dropout_layernorm_fwd_f32 / _bwd_f32 (a = mode), -1 = nothing launched or queued (an empty or refused call: the other fields are 0);
  * a: softmax forward - floats per lane held in registers (2, 8, 32; 0 = the loop that re-reads the row); parameter gradients -
  * the row splits, with b = the rows per split; scatter-add - 0 = queued, 1 = the chunked launch, 2 = the atomic kernel;
  * queued: 1 when the call only queued its work inside an open lg_gemm_group_begin bracket. */
@@ -651,6 +651,28 @@ int lg_rng_state(uint64_t* seed, uint64_t* draws);       /* synchronises the str
 int lg_dropout_fwd_f32(const float* x, const float* residual /* may be NULL */, float* y, int64_t n,
                        double p, uint64_t* base_out);
 int lg_dropout_bwd_f32(const float* g, float* dx, int64_t n, double p, const uint64_t* base);
+
+/* ---- hidden dropout inside the LayerNorm launches (csrc/rowwise.hip) ----------------------------------
+ * A dropout that sits directly in front of or behind a LayerNorm over dense fp32 [rows, cols], drawn where the LayerNorm
+ * kernel loads or stores its row.  ONE call of the stream above per forward; element i = row * cols + col of the dense operand
+ * takes the word lg_dropout_fwd_f32 would give element i, so the results are the bits of the two-launch forms:
+ *   mode 0  y = layernorm(dropout(x, p) + residual)   = lg_dropout_fwd_f32(x, residual, t) then lg_layernorm_f32(t, ...)
+ *           (residual may be NULL: no addition); t is never written to memory.  Backward, with d = lg_layernorm_bwd_f32's dx:
+ *           dres[i] = d[i] (dres may be NULL), dx[i] = kept ? d[i] * s : +0.0
+ *   mode 1  y = dropout(layernorm(x), p)               = lg_layernorm_f32 then lg_dropout_fwd_f32 (the embedding site; residual
+ *           must be NULL).  Backward: gdrop[i] = kept ? g[i] * s : +0.0, dx = lg_layernorm_bwd_f32 of gdrop; gdrop is written
+ *           to memory because the LayerNorm's parameter gradients are lg_layernorm_param_grads_f32(gdrop, xhat, ...).
+ * xhat and rstd are those of the LayerNorm in both modes.  The forward reads `draws`, writes it to base_out[0] and advances it
+ * by one, whatever the shape (rows == 0 included), like lg_dropout_fwd_f32, and a captured graph draws a fresh mask per replay;
+ * the backward draws nothing (rows == 0: no launch).  No output may alias an input or another output.
+ * 0 <= p < 1; rows >= 0 (at most 2^26), cols >= 1, rows * cols <= 2^34; lg_rowwise_last_plan: kernel 7 (forward) / 8
+ * (backward), a = mode. */
+int lg_dropout_layernorm_fwd_f32(const float* x, const float* residual /* NULL unless mode 0 */, const float* w, const float* b,
+                                 float* y, float* xhat, float* rstd, int64_t rows, int64_t cols, float eps, double p, int mode,
+                                 uint64_t* base_out);
+int lg_dropout_layernorm_bwd_f32(const float* g, const float* w, const float* xhat, const float* rstd, float* dx,
+                                 float* dres /* mode 0, may be NULL */, float* gdrop /* mode 1 */, int64_t rows, int64_t cols,
+                                 double p, int mode, const uint64_t* base);
 
 /* library build info: "liblghip <version> gfx950 <build date>" */
 const char* lg_version(void);

@@ -156,6 +156,8 @@ PROTOTYPES = {
     "lg_rng_state": (c_int, [POINTER(c_uint64), POINTER(c_uint64)]),
     "lg_dropout_fwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_double, c_void_p]),
     "lg_dropout_bwd_f32": (c_int, [c_void_p, c_void_p, c_int64, c_double, c_void_p]),
+    "lg_dropout_layernorm_fwd_f32": (c_int, [c_void_p] * 7 + [c_int64, c_int64, c_float, c_double, c_int, c_void_p]),
+    "lg_dropout_layernorm_bwd_f32": (c_int, [c_void_p] * 7 + [c_int64, c_int64, c_double, c_int, c_void_p]),
 }
 
 # include/lghip_p2p.h: the peer-window gradient exchange, exported by liblghip.so itself (no RCCL)

@@ -10,7 +10,7 @@ import builtins as _py      # this module defines ops named max / min / sum / po
 import ctypes
 import os
 import numpy as np
-from ..func import Function
+from ..func import Function, _FunctionType
 from ..dropout import DropoutFunction
 from ... import random as _random
 import weakref
@@ -2363,34 +2363,124 @@ class layer_norm(Function):
         g = out_grad.contiguous()
         dx = HipTensor.empty(xhat._shape)
         _l.check(_l.lib().lg_layernorm_bwd_f32(g.ptr, w.ptr, xhat.ptr, rstd.ptr, dx.ptr, rows, cols))
-        # dw = sum_rows(g * xhat), db = sum_rows(g) from one launch, added straight into the parameters' gradient buffers
-        # when they have one (leaf parameters after zero_grad), like linear.backward does
-        weight, bias = ctx._parents[1], ctx._parents[2]
-        acc_w = weight._grad_accumulator() if weight.requires_grad else None
-        acc_b = bias._grad_accumulator() if bias.requires_grad else None
-        acc_w = acc_w if (acc_w is not None and acc_w.is_contiguous()) else None
-        acc_b = acc_b if (acc_b is not None and acc_b.is_contiguous()) else None
-        dw = acc_w if acc_w is not None else HipTensor.empty((cols,))
-        db = acc_b if acc_b is not None else HipTensor.empty((cols,))
+        return (dx,) + _layer_norm_param_grads(ctx._parents[1], ctx._parents[2], g, xhat, rows, cols)
 
-        def param_grads():
-            for t in (acc_w, acc_b):
-                if t is not None:
-                    flush_lazy_readers(t)
-            _l.check(_l.lib().lg_layernorm_param_grads_f32(
-                g.ptr, xhat.ptr, dw.ptr, db.ptr, rows, cols,
-                1 if (acc_w is not None and not weight._consume_zero_pending()) else 0,
-                1 if (acc_b is not None and not bias._consume_zero_pending()) else 0))
-        if acc_w is not None and acc_b is not None and GradGroup.usable_for(weight, bias):
-            with GradGroup.issue(reads=(g, xhat), writes=(acc_w, acc_b)):          # queued, like a Linear's dW
-                param_grads()
-        else:
+
+def _layer_norm_param_grads(weight, bias, g, xhat, rows, cols):
+    """(dw, db) of a LayerNorm node for Function.backward: dw = sum_rows(g * xhat), db = sum_rows(g) from one launch, added
+    straight into the parameters' gradient buffers when they have one (leaf parameters after zero_grad), like linear.backward
+    does - then None is reported for that parameter"""
+    acc_w = weight._grad_accumulator() if weight.requires_grad else None
+    acc_b = bias._grad_accumulator() if bias.requires_grad else None
+    acc_w = acc_w if (acc_w is not None and acc_w.is_contiguous()) else None
+    acc_b = acc_b if (acc_b is not None and acc_b.is_contiguous()) else None
+    dw = acc_w if acc_w is not None else HipTensor.empty((cols,))
+    db = acc_b if acc_b is not None else HipTensor.empty((cols,))
+
+    def param_grads():
+        for t in (acc_w, acc_b):
+            if t is not None:
+                flush_lazy_readers(t)
+        _l.check(_l.lib().lg_layernorm_param_grads_f32(
+            g.ptr, xhat.ptr, dw.ptr, db.ptr, rows, cols,
+            1 if (acc_w is not None and not weight._consume_zero_pending()) else 0,
+            1 if (acc_b is not None and not bias._consume_zero_pending()) else 0))
+    if acc_w is not None and acc_b is not None and GradGroup.usable_for(weight, bias):
+        with GradGroup.issue(reads=(g, xhat), writes=(acc_w, acc_b)):          # queued, like a Linear's dW
             param_grads()
-        if acc_w is not None:
-            weight._notify_grad_written()
-        if acc_b is not None:
-            bias._notify_grad_written()
-        return dx, (None if acc_w is not None else dw), (None if acc_b is not None else db)
+    else:
+        param_grads()
+    if acc_w is not None:
+        weight._notify_grad_written()
+    if acc_b is not None:
+        bias._notify_grad_written()
+    return (None if acc_w is not None else dw), (None if acc_b is not None else db)
+
+
+def _check_dropout_layer_norm(name, x, residual, weight, bias):
+    """what `x.dropout(p, residual=residual).layer_norm(weight, bias)` would refuse, before anything is drawn"""
+    DropoutFunction.check_residual(x, residual)
+    for t in (x, residual, weight, bias):
+        if t is not None and t._dtype != _F32:
+            raise TypeError("%s is float32-only (got %s)" % (name, t._dtype))
+    assert len(weight._shape) == 1 and weight._shape == bias._shape == x._shape[-1:], \
+        "%s fuses a 1-D normalised shape; got %s for input %s" % (name, weight._shape, x._shape)
+
+
+class _DropoutAddLayerNormType(_FunctionType):
+    """call protocol of the node below (autograd/dropout.py has dropout's): the residual is a positional parent, and p == 0 is
+    no new node - the plain sum and the plain LayerNorm, nothing drawn"""
+
+    def __call__(cls, x, residual, weight, bias, p, eps=1e-5):
+        p = _random.check_probability(p)
+        _check_dropout_layer_norm(cls.__name__, x, residual, weight, bias)
+        if p == 0.0:
+            return (x if residual is None else x + residual).layer_norm(weight, bias, eps=eps)
+        return _FunctionType.__call__(cls, x, residual, weight, bias, p, float(eps))
+
+
+class _LayerNormDropoutType(_FunctionType):
+
+    def __call__(cls, x, weight, bias, p, eps=1e-5):
+        p = _random.check_probability(p)
+        _check_dropout_layer_norm(cls.__name__, x, None, weight, bias)
+        if p == 0.0:
+            return x.layer_norm(weight, bias, eps=eps)
+        return _FunctionType.__call__(cls, x, weight, bias, p, float(eps))
+
+
+def _dropout_layer_norm_forward(x, residual, weight, bias, p, eps, mode):
+    """one launch: the LayerNorm kernel with the mask of ONE call of the stream drawn where it loads (mode 0) or stores (mode 1)"""
+    xc, rows, cols = _rows_view(x)               # element index of the stream = index in the dense operand
+    res = residual.contiguous() if residual is not None else None
+    w, b = weight.contiguous(), bias.contiguous()
+    y, xhat, rstd = HipTensor.empty(xc._shape), HipTensor.empty(xc._shape), HipTensor.empty((rows,))
+    base = _dropout_base()
+    _l.check(_l.lib().lg_dropout_layernorm_fwd_f32(xc.ptr, res.ptr if res is not None else _NULL, w.ptr, b.ptr, y.ptr, xhat.ptr, rstd.ptr,
+                                                   rows, cols, eps, p, mode, base.ptr))
+    return y, (w, xhat, rstd, rows, cols, p, base)
+
+
+@HipTensor.register_op()
+class dropout_add_layer_norm(Function, metaclass=_DropoutAddLayerNormType):
+    """ x.dropout_add_layer_norm(residual, weight, bias, p, eps=1e-5): the bits of `x.dropout(p, residual=residual).layer_norm(weight,
+    bias, eps=eps)` from one launch each way (residual may be None).  The mask is drawn where the LayerNorm kernel loads its row
+    and dropout(x) + residual exists in registers only; saved are xhat, rstd and the call's number.  The backward launch forms the
+    LayerNorm's row gradient d, which is the residual's gradient as it is and x's through the mask. """
+    def forward(ctx, x, residual, weight, bias, p, eps):
+        y, saved = _dropout_layer_norm_forward(x, residual, weight, bias, p, eps, 0)
+        ctx.save_for_backward(*saved)
+        return y
+
+    def backward(ctx, out_grad):
+        w, xhat, rstd, rows, cols, p, base = ctx.get_saved_tensors()
+        residual = ctx._parents[1]
+        g = out_grad.contiguous()
+        dx = HipTensor.empty(xhat._shape, requires_grad=False)
+        dres = HipTensor.empty(xhat._shape, requires_grad=False) if (residual is not None and residual.requires_grad) else None
+        _l.check(_l.lib().lg_dropout_layernorm_bwd_f32(g.ptr, w.ptr, xhat.ptr, rstd.ptr, dx.ptr, dres.ptr if dres is not None else _NULL,
+                                                       _NULL, rows, cols, p, 0, base.ptr))
+        return (dx, dres) + _layer_norm_param_grads(ctx._parents[2], ctx._parents[3], g, xhat, rows, cols)
+
+
+@HipTensor.register_op()
+class layer_norm_dropout(Function, metaclass=_LayerNormDropoutType):
+    """ x.layer_norm_dropout(weight, bias, p, eps=1e-5): the bits of `x.layer_norm(weight, bias, eps=eps).dropout(p)` from one launch
+    each way: the mask is drawn where the LayerNorm kernel stores its row.  The backward launch writes the masked gradient g' to
+    memory as well, because the LayerNorm's parameter gradients (one more launch, usually queued) are sums over g'. """
+    def forward(ctx, x, weight, bias, p, eps):
+        y, saved = _dropout_layer_norm_forward(x, None, weight, bias, p, eps, 1)
+        ctx.save_for_backward(*saved)
+        return y
+
+    def backward(ctx, out_grad):
+        w, xhat, rstd, rows, cols, p, base = ctx.get_saved_tensors()
+        g = out_grad.contiguous()
+        dx = HipTensor.empty(xhat._shape, requires_grad=False)
+        gdrop = HipTensor.empty(xhat._shape, requires_grad=False)
+        _l.check(_l.lib().lg_dropout_layernorm_bwd_f32(g.ptr, w.ptr, xhat.ptr, rstd.ptr, dx.ptr, _NULL, gdrop.ptr, rows, cols, p, 1,
+                                                       base.ptr))
+        return (dx,) + _layer_norm_param_grads(ctx._parents[1], ctx._parents[2], gdrop, xhat, rows, cols)
 
 
 def _gather_rows(table, ids):

@@ -8,6 +8,7 @@
 //   LayerNorm nn.py:109-124           D = x - mean; V = mean(D*D); D / (V + eps)**0.5 * weight + bias
 //   Embedding examples/bert.py:14-21  weight[ids]  (the reference round-trips through the CPU and drops the gradient)
 #include "common.h"
+#include "rng_common.h"
 #include "tail_jobs.h"
 
 namespace lg {
@@ -106,48 +107,196 @@ __global__ void __launch_bounds__(256) softmax_bwd(const float* __restrict__ y, 
 }
 
 // ---- LayerNorm over the last axis ---------------------------------------------------------------------
+// Each row body is written once.  Where it loads an element of its input or stores an element of its result it asks a policy:
+// the plain kernels pass the value through, the kernels with dropout (below) draw the stream's mask at that point - same
+// lane-to-column mapping, same sums, same expressions, so they give the bits of the two-launch forms.  `i` is the flat index
+// of the element, `k` counts the lane's elements (c = lane + 64 k); first() is the first load of an element, again() a later one.
+struct LnLoad {
+    const float* x;
+    __device__ __forceinline__ float first(int64_t i, int) { return x[i]; }
+    __device__ __forceinline__ float again(int64_t i, int) { return x[i]; }
+};
+struct LnStore {
+    float* y;
+    __device__ __forceinline__ void operator()(int64_t i, float v) const { y[i] = v; }
+};
+
 // y = ((x - mean) * rstd) * w + b ; saves xhat = (x - mean) * rstd and rstd for the backward
-__global__ void __launch_bounds__(256) layernorm_fwd(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
-                                                     float* __restrict__ y, float* __restrict__ xhat, float* __restrict__ rstd,
-                                                     int64_t rows, int64_t cols, float eps, float inv_n) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const float* xr = x + row * cols;
+template <typename Load, typename Store>
+__device__ __forceinline__ void layernorm_fwd_row(Load& in, const Store& out, const float* __restrict__ w, const float* __restrict__ b,
+                                                  float* __restrict__ xhat, float* __restrict__ rstd, int64_t row, int64_t cols,
+                                                  float eps, float inv_n, int lane) {
+    const int64_t at = row * cols;
     float s = 0.f;
-    for (int64_t c = lane; c < cols; c += 64) s += xr[c];
+    int k = 0;
+    for (int64_t c = lane; c < cols; c += 64, ++k) s += in.first(at + c, k);
     const float mean = wave_sum(s) * inv_n;
     float q = 0.f;
-    for (int64_t c = lane; c < cols; c += 64) { const float d = xr[c] - mean; q += d * d; }
+    k = 0;
+    for (int64_t c = lane; c < cols; c += 64, ++k) { const float d = in.again(at + c, k) - mean; q += d * d; }
     const float var = wave_sum(q) * inv_n;
     const float r = 1.0f / sqrtf(var + eps);
     if (lane == 0) rstd[row] = r;
-    for (int64_t c = lane; c < cols; c += 64) {
-        const float h = (xr[c] - mean) * r;
-        xhat[row * cols + c] = h;
-        y[row * cols + c] = h * w[c] + b[c];
+    k = 0;
+    for (int64_t c = lane; c < cols; c += 64, ++k) {
+        const float h = (in.again(at + c, k) - mean) * r;
+        xhat[at + c] = h;
+        out(at + c, h * w[c] + b[c]);
     }
 }
 
 // dx = rstd * (gh - mean(gh) - xhat * mean(gh * xhat)),  gh = g * w
-__global__ void __launch_bounds__(256) layernorm_bwd(const float* __restrict__ g, const float* __restrict__ w, const float* __restrict__ xhat,
-                                                     const float* __restrict__ rstd, float* __restrict__ dx, int64_t rows, int64_t cols,
-                                                     float inv_n) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const float* gr = g + row * cols;
-    const float* hr = xhat + row * cols;
+template <typename Load, typename Store>
+__device__ __forceinline__ void layernorm_bwd_row(Load& in, const Store& out, const float* __restrict__ w, const float* __restrict__ xhat,
+                                                  const float* __restrict__ rstd, int64_t row, int64_t cols, float inv_n, int lane) {
+    const int64_t at = row * cols;
+    const float* hr = xhat + at;
     float s1 = 0.f, s2 = 0.f;
-    for (int64_t c = lane; c < cols; c += 64) {
-        const float gh = gr[c] * w[c];
+    int k = 0;
+    for (int64_t c = lane; c < cols; c += 64, ++k) {
+        const float gh = in.first(at + c, k) * w[c];
         s1 += gh;
         s2 += gh * hr[c];
     }
     s1 = wave_sum(s1) * inv_n;
     s2 = wave_sum(s2) * inv_n;
     const float r = rstd[row];
-    for (int64_t c = lane; c < cols; c += 64) dx[row * cols + c] = r * (gr[c] * w[c] - s1 - hr[c] * s2);
+    k = 0;
+    for (int64_t c = lane; c < cols; c += 64, ++k) out(at + c, r * (in.again(at + c, k) * w[c] - s1 - hr[c] * s2));
+}
+
+__global__ void __launch_bounds__(256) layernorm_fwd(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
+                                                     float* __restrict__ y, float* __restrict__ xhat, float* __restrict__ rstd,
+                                                     int64_t rows, int64_t cols, float eps, float inv_n) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    LnLoad in{x};
+    layernorm_fwd_row(in, LnStore{y}, w, b, xhat, rstd, row, cols, eps, inv_n, lane);
+}
+
+__global__ void __launch_bounds__(256) layernorm_bwd(const float* __restrict__ g, const float* __restrict__ w, const float* __restrict__ xhat,
+                                                     const float* __restrict__ rstd, float* __restrict__ dx, int64_t rows, int64_t cols,
+                                                     float inv_n) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    LnLoad in{g};
+    layernorm_bwd_row(in, LnStore{dx}, w, xhat, rstd, row, cols, inv_n, lane);
+}
+
+// ---- LayerNorm with the hidden dropout next to it inside the same launch (C ABI: include/lghip.h, lg_dropout_layernorm_*) ------
+// mode 0: y = LayerNorm(dropout(x) + residual); mode 1: y = dropout(LayerNorm(x)).  The mask is the stream's (rng_common.h): the
+// word of element i of the dense (rows, cols) operand, one Philox call per element (groups of four straddle rows and lanes).
+struct LnDraw {
+    uint32_t threshold;
+    float s;
+    unsigned long long seed, base;
+    __device__ __forceinline__ bool keep(int64_t i) const { return rng_word(i, seed, base) >= threshold; }
+    __device__ __forceinline__ float operator()(float v, int64_t i) const { return rng_keep(v, rng_word(i, seed, base), threshold, s); }
+};
+
+// forward, mode 0: dropout(x) [+ residual], the expressions of drop_value (dropout.hip); the sum exists in registers only.  The
+// row is loaded three times: the keep bits of a lane's first 32 elements are remembered (rows up to 2048 draw once)
+template <bool RES>
+struct LnLoadDropAdd {
+    const float* x;
+    const float* res;
+    LnDraw draw;
+    uint32_t kept;
+    __device__ __forceinline__ float value(int64_t i, bool keep) const {
+        const float v = keep ? __fmul_rn(x[i], draw.s) : 0.0f;          // rng_keep
+        return RES ? __fadd_rn(v, res[i]) : v;
+    }
+    __device__ __forceinline__ float first(int64_t i, int k) {
+        const bool keep = draw.keep(i);
+        if (k < 32) kept |= uint32_t(keep) << k;
+        return value(i, keep);
+    }
+    __device__ __forceinline__ float again(int64_t i, int k) { return value(i, k < 32 ? ((kept >> k) & 1u) != 0 : draw.keep(i)); }
+};
+// forward, mode 1: the finished element goes through the mask
+struct LnStoreDrop {
+    float* y;
+    LnDraw draw;
+    __device__ __forceinline__ void operator()(int64_t i, float v) const { y[i] = draw(v, i); }
+};
+// backward, mode 0: the row gradient d is the residual's gradient as it is and the input's through the mask
+struct LnStoreDropGrad {
+    float* dx;
+    float* dres;
+    LnDraw draw;
+    __device__ __forceinline__ void operator()(int64_t i, float d) const {
+        if (dres != nullptr) dres[i] = d;
+        dx[i] = draw(d, i);
+    }
+};
+// backward, mode 1: g' = dropout's gradient of g, written to gdrop (the parameter-gradient launch reads it) and read back
+// from there by the lane that wrote it
+struct LnLoadDropGrad {
+    const float* g;
+    float* gdrop;
+    LnDraw draw;
+    __device__ __forceinline__ float first(int64_t i, int) {
+        const float v = draw(g[i], i);
+        gdrop[i] = v;
+        return v;
+    }
+    __device__ __forceinline__ float again(int64_t i, int) { return gdrop[i]; }
+};
+
+// read, ticket, advance as dropout_fwd (dropout.hip) does: no wave leaves before the barrier behind which call[] is shared;
+// a launch without rows (rows == 0: one workgroup) only advances `draws`
+template <int MODE, bool RES>
+__global__ void __launch_bounds__(256) dropout_layernorm_fwd(const float* x, const float* res, const float* w, const float* b, float* y,
+                                                             float* xhat, float* rstd, int64_t rows, int64_t cols, float eps, float inv_n,
+                                                             uint32_t threshold, float s, unsigned long long* state,
+                                                             unsigned long long* base_out, int group) {
+    __shared__ unsigned long long call[2];
+    int* const tickets = rng_tickets(state);
+    if (threadIdx.x == 0) {
+        rng_read_call(state, call);                                // `draws` is in a register before the ticket below is taken
+        if (blockIdx.x == 0) base_out[0] = call[1];
+    }
+    __syncthreads();
+    int order = 0;
+    const int grp = blockIdx.x / group, groups = (gridDim.x + group - 1) / group;
+    int* const mine = tickets + (1 + grp) * kRngLine;
+    if (threadIdx.x == 0) order = rng_take_ticket(mine);
+    const LnDraw draw{threshold, s, rng_uniform64(call[0]), rng_uniform64(call[1])};
+
+    const int lane = threadIdx.x & 63;
+    const int64_t row = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
+    if (row < rows) {
+        if constexpr (MODE == 0) {
+            LnLoadDropAdd<RES> in{x, res, draw, 0u};
+            layernorm_fwd_row(in, LnStore{y}, w, b, xhat, rstd, row, cols, eps, inv_n, lane);
+        } else {
+            LnLoad in{x};
+            layernorm_fwd_row(in, LnStoreDrop{y, draw}, w, b, xhat, rstd, row, cols, eps, inv_n, lane);
+        }
+    }
+
+    if (threadIdx.x == 0) rng_last_arriver_advances(state, tickets, mine, order, grp, groups, group, int(gridDim.x), draw.base);
+}
+
+// draws nothing: the seed from the state, the call's number from what the forward wrote
+template <int MODE>
+__global__ void __launch_bounds__(256) dropout_layernorm_bwd(const float* g, const float* w, const float* xhat, const float* rstd, float* dx,
+                                                             float* dres, float* gdrop, int64_t rows, int64_t cols, float inv_n,
+                                                             uint32_t threshold, float s, const unsigned long long* state,
+                                                             const unsigned long long* base) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const LnDraw draw{threshold, s, state[0], base[0]};
+    if constexpr (MODE == 0) {
+        LnLoad in{g};
+        layernorm_bwd_row(in, LnStoreDropGrad{dx, dres, draw}, w, xhat, rstd, row, cols, inv_n, lane);
+    } else {
+        LnLoadDropGrad in{g, gdrop, draw};
+        layernorm_bwd_row(in, LnStore{dx}, w, xhat, rstd, row, cols, inv_n, lane);
+    }
 }
 
 __global__ void __launch_bounds__(256) layernorm_param_grads(LnParamGrads a) {
@@ -444,7 +593,7 @@ using namespace lg;
 // host bookkeeping written where the launch or the queueing is decided, so that a test can see which path its shape reached
 // after the thresholds below move.  {kernel, a, b, queued}; a call that launches and queues nothing leaves kernel = -1.
 enum { RW_NONE = -1, RW_SOFTMAX_FWD = 0, RW_SOFTMAX_BWD = 1, RW_LAYERNORM_FWD = 2, RW_LAYERNORM_BWD = 3, RW_PARAM_GRADS = 4,
-       RW_SCATTER_ADD = 5, RW_GATHER = 6 };
+       RW_SCATTER_ADD = 5, RW_GATHER = 6, RW_DROPOUT_LAYERNORM_FWD = 7, RW_DROPOUT_LAYERNORM_BWD = 8 };
 static thread_local int32_t g_rw_plan[4] = {RW_NONE, 0, 0, 0};
 static void note_rowwise(int kernel, int64_t a = 0, int64_t b = 0, int queued = 0) {
     g_rw_plan[0] = kernel; g_rw_plan[1] = int32_t(a); g_rw_plan[2] = int32_t(b); g_rw_plan[3] = queued;
@@ -577,6 +726,80 @@ extern "C" int lg_layernorm_bwd_f32(const float* g, const float* w, const float*
     note_rowwise(RW_LAYERNORM_BWD);
     hipLaunchKernelGGL(layernorm_bwd, dim3(unsigned((rows + 3) / 4)), dim3(256), 0, rt().stream, g, w, xhat, rstd, dx, rows, cols,
                        float(1.0 / double(cols)));
+    LG_CHECK_LAUNCH();
+    return LG_OK;
+}
+
+// shape, probability and mode checks shared by the two entry points below; false: the error is set
+static bool dropout_layernorm_args(const char* who, int64_t rows, int64_t cols, double p, int mode) {
+    if (!(rows >= 0 && cols >= 1)) { set_error("%s: bad shape (%lld, %lld)", who, (long long)rows, (long long)cols); return false; }
+    // one workgroup per four rows: the tickets of the forward launch take kRngMaxGroup^2 workgroups
+    if (!(rows <= int64_t(4) * kRngMaxGroup * kRngMaxGroup && rows <= kRngMaxElements / cols)) {
+        set_error("%s: rows = %lld, cols = %lld: more than 2^26 rows or 2^34 elements", who, (long long)rows, (long long)cols);
+        return false;
+    }
+    if (!(p >= 0.0 && p < 1.0)) { set_error("%s: p = %g outside [0, 1)", who, p); return false; }
+    if (!(mode == 0 || mode == 1)) { set_error("%s: mode = %d (0: dropout, add, normalise; 1: normalise, dropout)", who, mode); return false; }
+    return true;
+}
+
+extern "C" int lg_dropout_layernorm_fwd_f32(const float* x, const float* residual, const float* w, const float* b, float* y, float* xhat,
+                                            float* rstd, int64_t rows, int64_t cols, float eps, double p, int mode, uint64_t* base_out) {
+    note_rowwise(RW_NONE);
+    LG_REQUIRE_INIT();
+    if (!dropout_layernorm_args("lg_dropout_layernorm_fwd_f32", rows, cols, p, mode)) return LG_EINVAL;
+    LG_ARG(x && w && b && y && xhat && rstd && base_out, "lg_dropout_layernorm_fwd_f32: NULL pointer");
+    LG_ARG(residual == nullptr || mode == 0, "lg_dropout_layernorm_fwd_f32: a residual in mode 1 (it belongs to mode 0)");
+    { const int rc = adam_epilogue_check_write(y, rows * cols * 4); if (rc != LG_OK) return rc; }
+    uint32_t threshold;
+    float s;
+    rng_threshold(p, threshold, s);
+    const dim3 grid(unsigned(rows == 0 ? 1 : (rows + 3) / 4)), block(256);      // without rows: one workgroup, which advances `draws`
+    const int group = rng_group(grid.x);
+    const float inv_n = float(1.0 / double(cols));
+    unsigned long long* const state = rt().rng_state;
+    unsigned long long* const out = reinterpret_cast<unsigned long long*>(base_out);
+    hipStream_t st = rt().stream;
+    note_rowwise(RW_DROPOUT_LAYERNORM_FWD, mode);
+    if (mode == 1)
+        hipLaunchKernelGGL((dropout_layernorm_fwd<1, false>), grid, block, 0, st, x, residual, w, b, y, xhat, rstd, rows, cols, eps, inv_n,
+                           threshold, s, state, out, group);
+    else if (residual != nullptr)
+        hipLaunchKernelGGL((dropout_layernorm_fwd<0, true>), grid, block, 0, st, x, residual, w, b, y, xhat, rstd, rows, cols, eps, inv_n,
+                           threshold, s, state, out, group);
+    else
+        hipLaunchKernelGGL((dropout_layernorm_fwd<0, false>), grid, block, 0, st, x, residual, w, b, y, xhat, rstd, rows, cols, eps, inv_n,
+                           threshold, s, state, out, group);
+    LG_CHECK_LAUNCH();
+    return LG_OK;
+}
+
+extern "C" int lg_dropout_layernorm_bwd_f32(const float* g, const float* w, const float* xhat, const float* rstd, float* dx, float* dres,
+                                            float* gdrop, int64_t rows, int64_t cols, double p, int mode, const uint64_t* base) {
+    note_rowwise(RW_NONE);
+    LG_REQUIRE_INIT();
+    if (!dropout_layernorm_args("lg_dropout_layernorm_bwd_f32", rows, cols, p, mode)) return LG_EINVAL;
+    LG_ARG(g && w && xhat && rstd && dx && base, "lg_dropout_layernorm_bwd_f32: NULL pointer");
+    LG_ARG(dres == nullptr || mode == 0, "lg_dropout_layernorm_bwd_f32: dres in mode 1 (the residual belongs to mode 0)");
+    LG_ARG(mode == 0 || gdrop != nullptr, "lg_dropout_layernorm_bwd_f32: NULL pointer (gdrop, which mode 1 writes)");
+    if (rows == 0) return LG_OK;
+    for (float* out : {dx, dres, mode == 1 ? gdrop : nullptr}) {
+        const int rc = adam_epilogue_check_write(out, rows * cols * 4);
+        if (rc != LG_OK) return rc;
+    }
+    uint32_t threshold;
+    float s;
+    rng_threshold(p, threshold, s);
+    const dim3 grid(unsigned((rows + 3) / 4)), block(256);
+    const float inv_n = float(1.0 / double(cols));
+    const unsigned long long* const bp = reinterpret_cast<const unsigned long long*>(base);
+    note_rowwise(RW_DROPOUT_LAYERNORM_BWD, mode);
+    if (mode == 0)
+        hipLaunchKernelGGL(dropout_layernorm_bwd<0>, grid, block, 0, rt().stream, g, w, xhat, rstd, dx, dres, gdrop, rows, cols, inv_n,
+                           threshold, s, rt().rng_state, bp);
+    else
+        hipLaunchKernelGGL(dropout_layernorm_bwd<1>, grid, block, 0, rt().stream, g, w, xhat, rstd, dx, dres, gdrop, rows, cols, inv_n,
+                           threshold, s, rt().rng_state, bp);
     LG_CHECK_LAUNCH();
     return LG_OK;
 }
