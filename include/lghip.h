@@ -337,6 +337,36 @@ int lg_adam_multi_dev_f32(float* p, const float* g, float* m, float* v, int nseg
                           double lr, double b1, double b2, double eps,
                           int64_t* step, int64_t step_slots, double gscale, int belief);
 
+/* The rest of a BERT training recipe around that launch: clipping by the global L2 norm, a warmup / linear-decay schedule of
+ * the learning rate and decoupled weight decay (AdamW).  optim.py's expression form defines the arithmetic:
+ *   lg_grad_norm_clip_f32   ONE launch over the flat gradient bucket:
+ *                             out[0] = norm = sqrt(sum_i (g[i] * gscale)^2)      (the product rounded to fp32 first when gscale != 1,
+ *                                                                                 squares in fp32, sums of workgroups folded in double)
+ *                             out[1] = coef = min(1, max_norm / (norm + 1e-6))   (in double from the fp32 norm, rounded once)
+ *                           `partial` is scratch of LG_GRAD_NORM_PARTIALS floats, `ticket` one int that is zero before the first
+ *                           call and zero again after every call; both and `out` are device memory the caller keeps.  The
+ *                           workgroup that finishes last folds the partial sums in an order that does not depend on timing:
+ *                           the same input gives the same bits on every run.  No workgroup waits for another.
+ *   lg_adamw_multi_dev_f32  lg_adam_multi_dev_f32 (same buckets, offsets, step slots) with, per element,
+ *                             g' = g * gscale (skipped when gscale == 1);  g'' = g' * clip[1] (skipped when clip == NULL)
+ *                             m, v and delta as above from g'' with lr_s = lr * factor(steps done) in place of lr
+ *                             p += delta + (-(lr_s * weight_decay)) * p    where decay_flags[j] != 0 and weight_decay != 0
+ *                             p += delta                                    elsewhere
+ *                           lr_s and -(lr_s * weight_decay) are formed in double ON THE DEVICE from the step number the bias
+ *                           corrections use, and rounded once: a replayed hipGraph follows the schedule.  schedule_kind 0:
+ *                           factor = 1; 1 (warmup-linear): factor(s) = (s + 1) / warmup_steps for s < warmup_steps, else
+ *                           max(0, (total_steps - s) / max(1, total_steps - warmup_steps)).  decay_flags: nseg bytes of HOST
+ *                           memory (may be NULL when weight_decay == 0), copied into the launch arguments like `offsets`;
+ *                           clip: the `out` of lg_grad_norm_clip_f32 (device) or NULL.  With weight_decay == 0, clip == NULL
+ *                           and schedule_kind == 0 the result equals lg_adam_multi_dev_f32's bit for bit. */
+#define LG_GRAD_NORM_PARTIALS 512
+int lg_grad_norm_clip_f32(const float* g, int64_t n, double gscale, double max_norm, float* partial, int* ticket, float* out);
+int lg_adamw_multi_dev_f32(float* p, const float* g, float* m, float* v, int nseg, const int64_t* offsets,
+                           double lr, double b1, double b2, double eps,
+                           int64_t* step, int64_t step_slots, double gscale, int belief,
+                           double weight_decay, const uint8_t* decay_flags, const float* clip,
+                           int schedule_kind, int64_t warmup_steps, int64_t total_steps);
+
 /* The update applied by the kernel that MAKES the gradient (round 4): `p += compute_delta(p.grad, i)` of optim.py:10-13 / :47-52
  * without a launch of its own.  The reference's optimizer is ~14 tensor expressions per parameter after backward; the fused
  * kernels above made that one launch; these entry points let the backward kernels themselves apply it to the values they are

@@ -90,6 +90,9 @@ PROTOTYPES = {
     "lg_counter_add_i64": (c_int, [c_void_p, c_int64]),
     "lg_adam_multi_dev_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, _I64P, c_double, c_double, c_double,
                                       c_double, c_void_p, c_int64, c_double, c_int]),
+    "lg_grad_norm_clip_f32": (c_int, [c_void_p, c_int64, c_double, c_double, c_void_p, c_void_p, c_void_p]),
+    "lg_adamw_multi_dev_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, _I64P, c_double, c_double, c_double,
+                                       c_double, c_void_p, c_int64, c_double, c_int, c_double, c_char_p, c_void_p, c_int, c_int64, c_int64]),
     "lg_adam_plan_create": (c_int, [POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64,
                                     c_double, c_double, c_double, c_double, c_double, c_int]),
     "lg_adam_plan_destroy": (c_int, [c_void_p]),
@@ -162,6 +165,7 @@ PROTOTYPES = {
 
 # include/lghip_p2p.h: the peer-window gradient exchange, exported by liblghip.so itself (no RCCL)
 P2P_HANDLE_BYTES, P2P_MAX_RANKS = 64, 8
+GRAD_NORM_PARTIALS = 512          # include/lghip.h: LG_GRAD_NORM_PARTIALS
 P2P_SUM, P2P_MAX = 0, 1
 P2P_PROTOTYPES = {
     "lg_p2p_export": (c_int, [c_int, c_int, c_int64, c_void_p]),          # char handle[64]

@@ -691,6 +691,39 @@ class HipTensor(AbstractTensor):
                                                 lr, b1, b2, eps, step_counter.ptr, step_counter.numel() - 2, grad_scale,
                                                 1 if belief else 0))
 
+    def _fused_adamw_multi_dev(self, grad, m, v, offsets, lr, b1, b2, eps, step_counter, grad_scale, belief,
+                               weight_decay, decay_flags, clip, schedule_kind, warmup_steps, total_steps):
+        """`_fused_adam_multi_dev` with decoupled weight decay (`decay_flags`: one bool per parameter), the gradient multiplied
+        by `clip[1]` (`clip`: what `_grad_norm_clip` wrote, or None) and the learning rate scheduled on the device
+        (schedule_kind 1: warmup / linear decay of the step counter) - include/lghip.h: lg_adamw_multi_dev_f32"""
+        for t in (self, grad, m, v):
+            assert t.is_contiguous() and t._shape == self._shape and t._dtype == np.float32
+        assert offsets[-1] == self.numel()
+        assert len(decay_flags) == len(offsets) - 1
+        assert clip is None or (clip.is_contiguous() and clip._dtype == np.float32 and clip.numel() == 2)
+        flush_lazy_readers(self)
+        _l.check(_l.lib().lg_adamw_multi_dev_f32(self.ptr, grad.ptr, m.ptr, v.ptr, len(offsets) - 1, _l.i64(tuple(offsets)),
+                                                 lr, b1, b2, eps, step_counter.ptr, step_counter.numel() - 2, grad_scale,
+                                                 1 if belief else 0, weight_decay, bytes(bytearray(1 if f else 0 for f in decay_flags)),
+                                                 None if clip is None else clip.ptr, schedule_kind, warmup_steps, total_steps))
+
+    def _grad_norm_clip(self, grad_scale, max_norm, scratch):
+        """self is the flat gradient bucket: ONE launch leaves (norm of self * grad_scale, min(1, max_norm / (norm + 1e-6))) in
+        scratch[2] - `scratch = _new_grad_norm_scratch()`, allocated once - include/lghip.h: lg_grad_norm_clip_f32"""
+        partial, ticket, out = scratch
+        assert self.is_contiguous() and self._dtype == np.float32 and self.numel() >= 1
+        assert partial.is_contiguous() and partial._dtype == np.float32 and partial.numel() >= _l.GRAD_NORM_PARTIALS
+        assert ticket.is_contiguous() and ticket._dtype == np.int32 and out.is_contiguous() and out._dtype == np.float32 and out.numel() == 2
+        flush_lazy_readers(out)
+        _l.check(_l.lib().lg_grad_norm_clip_f32(self.ptr, self.numel(), grad_scale, max_norm, partial.ptr, ticket.ptr, out.ptr))
+
+    @staticmethod
+    def _new_grad_norm_scratch():
+        """(partial sums, ticket, (norm, coef)) of `_grad_norm_clip`: allocated when an optimizer is configured, never in a step"""
+        return (HipTensor.zeros((_l.GRAD_NORM_PARTIALS,), requires_grad=False),
+                HipTensor.from_numpy(np.zeros(1, dtype=np.int32), requires_grad=False),
+                HipTensor.from_numpy(np.asarray([0.0, 1.0], dtype=np.float32), requires_grad=False))
+
     def _fused_adam_multi_p2p(self, grad, m, v, offsets, lr, b1, b2, eps, step_counter, grad_scale, belief):
         """`_fused_adam_multi_dev` of a data-parallel rank: the SAME launch first sums `grad` over the ranks through the peer
         windows (include/lghip_p2p.h) and also advances the step counter (`_new_step_counter(step, slots=...)`: every

@@ -19,6 +19,27 @@ __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v,
     p = p + (c.neg_lr * mh) * (1.0f / (sqrtf(vh) + c.eps));
 }
 
+// adam_elem with the rest of a BERT recipe around it (lg_adamw_multi_dev_f32, optim.hip): the gradient is first multiplied by
+// the clipping coefficient of the norm launch (clip != 0), and a decaying parameter (decay != 0) also moves by
+// neg_decay * p = (-(lr_s * weight_decay)) * p - decoupled weight decay, added to the Adam update BEFORE that meets p, as
+// the expression `p += delta + (-(lr_s * weight_decay)) * p` does.  c.neg_lr holds -lr_s, the scheduled learning rate.
+// With clip == 0 and decay == 0 these are adam_elem's operations, so the same bits.
+struct AdamwScalars {
+    float coef, neg_decay;
+    int   clip, decay;
+};
+
+__device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v, const AdamScalars& c, const AdamwScalars& w) {
+    if (c.scale_grad) g = g * c.gscale;
+    if (w.clip) g = g * w.coef;
+    m = c.b1 * m + c.one_minus_b1 * g;
+    const float s = c.belief ? g - m : g;
+    v = c.b2 * v + c.one_minus_b2 * (s * s);
+    const float mh = m * c.inv_bias1, vh = v * c.inv_bias2;
+    const float delta = (c.neg_lr * mh) * (1.0f / (sqrtf(vh) + c.eps));
+    p = w.decay ? p + (delta + w.neg_decay * p) : p + delta;
+}
+
 // the host scalars of one update, rounded once to fp32 like numpy rounds a python float that meets an fp32 array
 inline AdamScalars adam_scalars(double lr, double b1, double b2, double eps, double inv_bias1, double inv_bias2, double gscale, int belief) {
     AdamScalars c;
@@ -26,6 +47,82 @@ inline AdamScalars adam_scalars(double lr, double b1, double b2, double eps, dou
     c.eps = float(eps); c.inv_bias1 = float(inv_bias1); c.inv_bias2 = float(inv_bias2); c.gscale = float(gscale); c.belief = belief;
     c.scale_grad = gscale != 1.0;
     return c;
+}
+
+// ---- the argument block of the multi-tensor launches (lg_adam_multi_dev_f32 / lg_adamw_multi_dev_f32, optim.hip) ------------
+constexpr int kMaxSegments = 64;
+struct AdamSegments {
+    int     nseg;          // parameters in THIS launch (<= kMaxSegments)
+    int     nseg_total;    // parameters of the optimizer: the reference's `t` advances once per PARAMETER (optim.py:36/:48)
+    int     first;         // index of this launch's first parameter
+    int     slot_base;     // step slot of workgroup 0 of this launch
+    int     mirror_slot;   // the workgroup with this slot also writes step[0] (-1: none in this launch)
+    // COMPACT grid (round 4): parameter j owns workgroups wg_base[j] .. wg_base[j+1] - one per 1024 elements - instead of a row of
+    // a 2-D grid as wide as the LONGEST parameter needs: for the MNIST MLP that grid had 1568 workgroups of which 399 had work,
+    // and dispatching the 1169 that return at once is not free (the same lesson as the tail jobs of round 3)
+    int     wg_base[kMaxSegments + 1];
+    int64_t offsets[kMaxSegments + 1];
+};
+
+// what lg_adamw_multi_dev_f32 adds to the launch: by value like the segments, `decay` copied from the caller's HOST flags
+struct AdamwRecipe {
+    double       lr, weight_decay;
+    const float* clip;             // device: {norm, coef} of lg_grad_norm_clip_f32, or NULL (no clipping)
+    int          schedule_kind;    // 0: lr as given; 1: warmup / linear decay of the DEVICE step number
+    int64_t      warmup_steps, total_steps;
+    uint8_t      decay[kMaxSegments];      // per parameter of THIS launch: 1 = weight decay applies
+};
+
+// Host side of one group of <= kMaxSegments parameters: the compact grid, the group's step slots and which workgroup mirrors
+// the step number.  *slots_used = workgroups of the group's grid (0: nothing to launch).  No device call in here.
+inline int adam_segments_fill(AdamSegments& seg, int nseg, const int64_t* offsets, int first, int nseg_total, int64_t step_slots,
+                              int slot_base, bool* mirrored, int* slots_used) {
+    seg.nseg = nseg;
+    seg.nseg_total = nseg_total;
+    seg.first = first;
+    seg.slot_base = slot_base;
+    seg.mirror_slot = -1;
+    int64_t total = 0;
+    seg.wg_base[0] = 0;
+    for (int j = 0; j <= nseg; ++j) {
+        seg.offsets[j] = offsets[j];
+        if (j > 0) {
+            LG_ARG(offsets[j] >= offsets[j - 1], "lg_adam_multi_dev_f32: offsets must be non-decreasing");
+            total += (offsets[j] - offsets[j - 1] + 1023) / 1024;          // one workgroup per 1024 elements (four per thread)
+            LG_ARG(total < (int64_t(1) << 22), "lg_adam_multi_dev_f32: bucket too large for one launch");
+            seg.wg_base[j] = int(total);
+        }
+    }
+    *slots_used = int(total);
+    if (total == 0) return LG_OK;
+    if (step_slots > 0) {
+        LG_ARG(slot_base + *slots_used <= step_slots, "lg_adam_multi_dev_f32: the grid spans %d step slots, the caller gave %lld (lghip.h)",
+               slot_base + *slots_used, (long long)step_slots);
+        if (!*mirrored)                                   // the first workgroup of the first non-empty parameter keeps step[0] current
+            for (int j = 0; j < nseg; ++j)
+                if (offsets[j + 1] > offsets[j]) { seg.mirror_slot = slot_base + seg.wg_base[j]; *mirrored = true; break; }
+    }
+    return LG_OK;
+}
+
+// Host side of the recipe for the group starting at parameter `first`: the scalars and this group's slice of the decay flags
+// (decay_flags may be NULL when weight_decay == 0; flags other than 0 count as 1)
+inline int adamw_recipe_fill(AdamwRecipe& r, int nseg, int first, double lr, double weight_decay, const uint8_t* decay_flags,
+                             const float* clip, int schedule_kind, int64_t warmup_steps, int64_t total_steps) {
+    LG_ARG(nseg >= 1 && nseg <= kMaxSegments && first >= 0, "lg_adamw_multi_dev_f32: a group of %d parameters", nseg);
+    LG_ARG(schedule_kind == 0 || schedule_kind == 1, "lg_adamw_multi_dev_f32: schedule_kind %d (0 none, 1 warmup-linear)", schedule_kind);
+    LG_ARG(schedule_kind == 0 || (0 <= warmup_steps && warmup_steps <= total_steps),
+           "lg_adamw_multi_dev_f32: warmup-linear needs 0 <= warmup_steps <= total_steps, got %lld and %lld", (long long)warmup_steps,
+           (long long)total_steps);
+    LG_ARG(weight_decay == 0.0 || decay_flags != nullptr, "lg_adamw_multi_dev_f32: weight_decay without decay_flags");
+    r.lr = lr;
+    r.weight_decay = weight_decay;
+    r.clip = clip;
+    r.schedule_kind = schedule_kind;
+    r.warmup_steps = warmup_steps;
+    r.total_steps = total_steps;
+    for (int j = 0; j < kMaxSegments; ++j) r.decay[j] = (j < nseg && weight_decay != 0.0 && decay_flags[first + j]) ? 1 : 0;
+    return LG_OK;
 }
 
 // ---- the update applied where the gradient is made (lg_adam_plan_* / lg_adam_epilogue_*, optim.hip) --------------------

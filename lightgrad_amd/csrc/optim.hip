@@ -127,19 +127,7 @@ extern "C" int lg_counter_add_i64(int64_t* counter, int64_t delta) {
 // the NEXT step, with bookkeeping across hipGraph captures that went wrong for separately captured graphs).
 namespace lg {
 
-constexpr int kMaxSegments = 64;
-struct AdamSegments {
-    int     nseg;          // parameters in THIS launch (<= kMaxSegments)
-    int     nseg_total;    // parameters of the optimizer: the reference's `t` advances once per PARAMETER (optim.py:36/:48)
-    int     first;         // index of this launch's first parameter
-    int     slot_base;     // step slot of workgroup 0 of this launch
-    int     mirror_slot;   // the workgroup with this slot also writes step[0] (-1: none in this launch)
-    // COMPACT grid (round 4): parameter j owns workgroups wg_base[j] .. wg_base[j+1] - one per 1024 elements - instead of a row of
-    // a 2-D grid as wide as the LONGEST parameter needs: for the MNIST MLP that grid had 1568 workgroups of which 399 had work,
-    // and dispatching the 1169 that return at once is not free (the same lesson as the tail jobs of round 3)
-    int     wg_base[kMaxSegments + 1];
-    int64_t offsets[kMaxSegments + 1];
-};
+// (AdamSegments, kMaxSegments: adam_common.h, with the host code that fills them)
 
 __global__ void __launch_bounds__(256) adam_multi_dev(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                       float* __restrict__ v, AdamSegments seg, AdamScalars c,
@@ -193,43 +181,177 @@ __global__ void __launch_bounds__(256) adam_multi_dev(float* __restrict__ p, con
     }
 }
 
+// adam_multi_dev with the rest of the recipe (lg_adamw_multi_dev_f32): the same grid, segments and step slots.  Thread 0 forms,
+// from the SAME steps_done as the bias corrections and in double like the python expressions, the scheduled learning rate
+// lr_s = lr * factor(steps_done) and the decay scalar -(lr_s * weight_decay), each rounded once to fp32, and reads the
+// clipping coefficient the norm launch left in clip[1]; the lanes get them through LDS behind the one barrier.
+__global__ void __launch_bounds__(256) adamw_multi_dev(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                       float* __restrict__ v, AdamSegments seg, AdamScalars c, AdamwRecipe r,
+                                                       int64_t* __restrict__ step, double b1, double b2, int own_slots, int base_aligned) {
+    __shared__ float scal[5];
+    const int b = blockIdx.x;
+    int j = 0;
+    while (j + 1 < seg.nseg && b >= seg.wg_base[j + 1]) ++j;          // uniform: scalar loads
+    const int local = b - seg.wg_base[j], wgs = seg.wg_base[j + 1] - seg.wg_base[j];
+    const int64_t begin = seg.offsets[j], n = seg.offsets[j + 1] - begin;
+    const int vec = (base_aligned && (begin & 3) == 0) ? 1 : 0;
+    const int slot = seg.slot_base + b;
+    int64_t steps_done = 0;
+    if (threadIdx.x == 0) {
+        steps_done = __hip_atomic_load(own_slots ? step + 2 + slot : step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const double t = double(steps_done * seg.nseg_total + seg.first + j + 1);
+        scal[0] = float(1.0 / (1.0 - pow(b1, t)));
+        scal[1] = float(1.0 / (1.0 - pow(b2, t)));
+        double factor = 1.0;
+        if (r.schedule_kind == 1) {          // optim.WarmupLinear.factor, operation for operation
+            if (steps_done < r.warmup_steps) {
+                factor = double(steps_done + 1) / double(r.warmup_steps);
+            } else {
+                const int64_t span = r.total_steps - r.warmup_steps;
+                factor = double(r.total_steps - steps_done) / double(span > 1 ? span : 1);
+                if (!(factor > 0.0)) factor = 0.0;
+            }
+        }
+        const double lr_s = r.schedule_kind == 0 ? r.lr : r.lr * factor;
+        scal[2] = float(-lr_s);
+        scal[3] = float(-(lr_s * r.weight_decay));
+        scal[4] = r.clip ? r.clip[1] : 1.0f;
+    }
+    __syncthreads();
+    c.inv_bias1 = scal[0];
+    c.inv_bias2 = scal[1];
+    c.neg_lr = scal[2];
+    AdamwScalars w;
+    w.neg_decay = scal[3];
+    w.coef = scal[4];
+    w.clip = r.clip != nullptr;
+    w.decay = r.decay[j];
+    float* P = p + begin;
+    const float* G = g + begin;
+    float* M = m + begin;
+    float* V = v + begin;
+    const int64_t stride = int64_t(wgs) * blockDim.x;
+    if (vec) {
+        const int64_t nvec = n / 4;
+        for (int64_t i = int64_t(local) * blockDim.x + threadIdx.x; i < nvec; i += stride) {
+            float4 pp = reinterpret_cast<float4*>(P)[i], gg = reinterpret_cast<const float4*>(G)[i];
+            float4 mm = reinterpret_cast<float4*>(M)[i], vv = reinterpret_cast<float4*>(V)[i];
+            adamw_elem(pp.x, gg.x, mm.x, vv.x, c, w);
+            adamw_elem(pp.y, gg.y, mm.y, vv.y, c, w);
+            adamw_elem(pp.z, gg.z, mm.z, vv.z, c, w);
+            adamw_elem(pp.w, gg.w, mm.w, vv.w, c, w);
+            reinterpret_cast<float4*>(P)[i] = pp;
+            reinterpret_cast<float4*>(M)[i] = mm;
+            reinterpret_cast<float4*>(V)[i] = vv;
+        }
+        if (local == 0)
+            for (int64_t i = nvec * 4 + threadIdx.x; i < n; i += blockDim.x) adamw_elem(P[i], G[i], M[i], V[i], c, w);
+    } else {
+        for (int64_t i = int64_t(local) * blockDim.x + threadIdx.x; i < n; i += stride) adamw_elem(P[i], G[i], M[i], V[i], c, w);
+    }
+    if (own_slots && threadIdx.x == 0) {
+        __hip_atomic_store(step + 2 + slot, steps_done + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (slot == seg.mirror_slot) __hip_atomic_store(step, steps_done + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// ---- the global L2 norm of the gradient bucket and the clipping coefficient, ONE launch --------------------------------------
+// out[0] = norm = sqrt(sum_i (g[i] * gscale)^2), out[1] = coef = min(1, max_norm / (norm + 1e-6)): what lg_adamw_multi_dev_f32
+// multiplies every gradient by.  Every workgroup strides over the bucket (float4 loads from the first 16-byte boundary on, the
+// up to three floats in front of it and behind the last float4 one by one), squares in fp32 like the expression `g * g`,
+// publishes ONE partial sum and takes a ticket; the workgroup that draws the last ticket folds the partials - in double, thread k
+// the k-th run of consecutive partials, then a fixed tree over the threads - writes norm and coef and resets the ticket (the
+// pattern of red_rows_split, reduce.hip).  Which workgroup folds depends on timing, WHAT it adds in which order does not: the
+// result is bit-reproducible from run to run.  No workgroup waits for another, no spin loop, no float atomics.
+// At most kNormMaxWgs workgroups: tickets on one address are served one after the other, 13 ns each (reduce.hip).
+constexpr int kNormMaxWgs = LG_GRAD_NORM_PARTIALS;
+
+__device__ __forceinline__ float sumsq4(float4 x, float gscale, int scale_grad) {
+    if (scale_grad) { x.x = x.x * gscale; x.y = x.y * gscale; x.z = x.z * gscale; x.w = x.w * gscale; }
+    return (x.x * x.x + x.y * x.y) + (x.z * x.z + x.w * x.w);
+}
+
+__global__ void __launch_bounds__(256) grad_norm_clip(const float* __restrict__ g, int64_t n, int head, float gscale, int scale_grad,
+                                                      double max_norm, float* partial, int* ticket, float* out) {
+    __shared__ double fold[256];
+    __shared__ int arrived_last;
+    const int tid = threadIdx.x;
+    const int64_t nvec = (n - head) / 4;
+    const float4* g4 = reinterpret_cast<const float4*>(g + head);
+    const int64_t stride = int64_t(gridDim.x) * 256;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    int64_t i = int64_t(blockIdx.x) * 256 + tid;
+    for (; i + 3 * stride < nvec; i += 4 * stride) {
+        const float4 x0 = g4[i], x1 = g4[i + stride], x2 = g4[i + 2 * stride], x3 = g4[i + 3 * stride];
+        a0 += sumsq4(x0, gscale, scale_grad);
+        a1 += sumsq4(x1, gscale, scale_grad);
+        a2 += sumsq4(x2, gscale, scale_grad);
+        a3 += sumsq4(x3, gscale, scale_grad);
+    }
+    for (; i < nvec; i += stride) a0 += sumsq4(g4[i], gscale, scale_grad);
+    double acc = (double(a0) + double(a1)) + (double(a2) + double(a3));
+    if (blockIdx.x == 0) {          // the floats no float4 covers: `head` in front, n - head - 4 * nvec (< 4) behind
+        const int64_t rest = n - 4 * nvec;
+        if (tid < rest) {
+            float x = g[tid < head ? int64_t(tid) : 4 * nvec + tid];
+            if (scale_grad) x = x * gscale;
+            acc += double(x * x);
+        }
+    }
+    fold[tid] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) fold[tid] += fold[tid + s];
+        __syncthreads();
+    }
+    const int wgs = gridDim.x;
+    if (tid == 0) {
+        __hip_atomic_store(partial + blockIdx.x, float(fold[0]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const int last = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == wgs - 1;
+        if (last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        arrived_last = last;
+    }
+    __syncthreads();
+    if (!arrived_last) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int per = (wgs + 255) / 256;          // <= kNormMaxWgs / 256 consecutive partials per thread, in index order
+    double f = 0.0;
+    for (int k = 0; k < per; ++k) {
+        const int idx = tid * per + k;
+        if (idx < wgs) f += double(__hip_atomic_load(partial + idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    }
+    fold[tid] = f;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) fold[tid] += fold[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const float norm = float(sqrt(fold[0]));
+        const double c = max_norm / (double(norm) + 1e-6);
+        out[0] = norm;
+        out[1] = float(c < 1.0 ? c : 1.0);
+    }
+}
+
 }  // namespace lg
 
 // launches one group of <= kMaxSegments parameters; returns the number of step slots the group's grid spans in *slots_used
 static int lg_adam_multi_group(float* p, const float* g, float* m, float* v, int nseg, const int64_t* offsets, int first, int nseg_total,
                                double lr, double b1, double b2, double eps, int64_t* step, int64_t step_slots, int slot_base, bool* mirrored,
-                               double gscale, int belief, int* slots_used) {
+                               double gscale, int belief, int* slots_used, const AdamwRecipe* recipe = nullptr) {
     AdamSegments seg;
-    seg.nseg = nseg;
-    seg.nseg_total = nseg_total;
-    seg.first = first;
-    seg.slot_base = slot_base;
-    seg.mirror_slot = -1;
-    int64_t total = 0;
-    seg.wg_base[0] = 0;
-    for (int j = 0; j <= nseg; ++j) {
-        seg.offsets[j] = offsets[j];
-        if (j > 0) {
-            LG_ARG(offsets[j] >= offsets[j - 1], "lg_adam_multi_dev_f32: offsets must be non-decreasing");
-            total += (offsets[j] - offsets[j - 1] + 1023) / 1024;          // one workgroup per 1024 elements (four per thread)
-            LG_ARG(total < (int64_t(1) << 22), "lg_adam_multi_dev_f32: bucket too large for one launch");
-            seg.wg_base[j] = int(total);
-        }
-    }
-    *slots_used = 0;
-    if (total == 0) return LG_OK;
+    const int rc = adam_segments_fill(seg, nseg, offsets, first, nseg_total, step_slots, slot_base, mirrored, slots_used);
+    if (rc != LG_OK || *slots_used == 0) return rc;
     const AdamScalars c = adam_scalars(lr, b1, b2, eps, 0.0, 0.0, gscale, belief);
     const int base_aligned = (aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v)) ? 1 : 0;
-    *slots_used = int(total);
-    if (step_slots > 0) {
-        LG_ARG(slot_base + *slots_used <= step_slots, "lg_adam_multi_dev_f32: the grid spans %d step slots, the caller gave %lld (lghip.h)",
-               slot_base + *slots_used, (long long)step_slots);
-        if (!*mirrored)                                   // the first workgroup of the first non-empty parameter keeps step[0] current
-            for (int j = 0; j < nseg; ++j)
-                if (offsets[j + 1] > offsets[j]) { seg.mirror_slot = slot_base + seg.wg_base[j]; *mirrored = true; break; }
-    }
-    hipLaunchKernelGGL(adam_multi_dev, dim3(unsigned(total)), dim3(256), 0, rt().stream, p, g, m, v, seg, c, step, b1, b2,
-                       step_slots > 0 ? 1 : 0, base_aligned);
+    if (recipe)
+        hipLaunchKernelGGL(adamw_multi_dev, dim3(unsigned(*slots_used)), dim3(256), 0, rt().stream, p, g, m, v, seg, c, *recipe, step, b1, b2,
+                           step_slots > 0 ? 1 : 0, base_aligned);
+    else
+        hipLaunchKernelGGL(adam_multi_dev, dim3(unsigned(*slots_used)), dim3(256), 0, rt().stream, p, g, m, v, seg, c, step, b1, b2,
+                           step_slots > 0 ? 1 : 0, base_aligned);
     LG_CHECK_LAUNCH();
     return LG_OK;
 }
@@ -253,6 +375,46 @@ extern "C" int lg_adam_multi_dev_f32(float* p, const float* g, float* m, float* 
         if (rc != LG_OK) return rc;
         slot_base += used;
     }
+    return LG_OK;
+}
+
+extern "C" int lg_adamw_multi_dev_f32(float* p, const float* g, float* m, float* v, int nseg, const int64_t* offsets,
+                                      double lr, double b1, double b2, double eps, int64_t* step, int64_t step_slots, double gscale,
+                                      int belief, double weight_decay, const uint8_t* decay_flags, const float* clip, int schedule_kind,
+                                      int64_t warmup_steps, int64_t total_steps) {
+    LG_REQUIRE_INIT();
+    LG_ARG(nseg >= 1, "lg_adamw_multi_dev_f32: %d segments", nseg);
+    LG_ARG(p && g && m && v && step && offsets, "lg_adamw_multi_dev_f32: NULL pointer");
+    LG_ARG(step_slots >= 0, "lg_adamw_multi_dev_f32: negative step_slots");
+    int slot_base = 0;
+    bool mirrored = false;
+    for (int first = 0; first < nseg; first += kMaxSegments) {          // groups as in lg_adam_multi_dev_f32, each with its slice of the flags
+        const int count = nseg - first < kMaxSegments ? nseg - first : kMaxSegments;
+        AdamwRecipe recipe;
+        int rc = adamw_recipe_fill(recipe, count, first, lr, weight_decay, decay_flags, clip, schedule_kind, warmup_steps, total_steps);
+        if (rc != LG_OK) return rc;
+        int used = 0;
+        rc = lg_adam_multi_group(p, g, m, v, count, offsets + first, first, nseg, lr, b1, b2, eps, step, step_slots, slot_base, &mirrored,
+                                 gscale, belief, &used, &recipe);
+        if (rc != LG_OK) return rc;
+        slot_base += used;
+    }
+    return LG_OK;
+}
+
+extern "C" int lg_grad_norm_clip_f32(const float* g, int64_t n, double gscale, double max_norm, float* partial, int* ticket, float* out) {
+    LG_REQUIRE_INIT();
+    LG_ARG(n >= 1, "lg_grad_norm_clip_f32: %lld elements", (long long)n);
+    LG_ARG(g && partial && ticket && out, "lg_grad_norm_clip_f32: NULL pointer");
+    LG_ARG((reinterpret_cast<uintptr_t>(g) & 3u) == 0, "lg_grad_norm_clip_f32: the gradient is not 4-byte aligned");
+    int head = int(((16u - (reinterpret_cast<uintptr_t>(g) & 15u)) & 15u) / 4u);          // floats in front of the first 16-byte boundary
+    if (head > n) head = int(n);
+    // one float4 per thread as stream_grid sizes it, up to kNormMaxWgs workgroups (LG_GRAD_NORM_PARTIALS: what `partial` holds)
+    const unsigned need = stream_grid((n + 3) / 4);
+    const unsigned wgs = need < unsigned(kNormMaxWgs) ? need : unsigned(kNormMaxWgs);
+    hipLaunchKernelGGL(grad_norm_clip, dim3(wgs), dim3(256), 0, rt().stream, g, n, head, float(gscale), gscale != 1.0 ? 1 : 0, max_norm,
+                       partial, ticket, out);
+    LG_CHECK_LAUNCH();
     return LG_OK;
 }
 

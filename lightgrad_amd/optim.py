@@ -16,6 +16,11 @@ kernels that evaluate the SAME expression sequence per element:
   use_flat_buckets  parameters / gradients / moments live in flat buckets
                     (dist.DataParallel(flatten=True)): zero_grad is one fill and
                     the update of ALL parameters is one launch
+
+Adam / AdaBelief also carry the rest of a BERT recipe, every part off by default:
+decoupled weight decay (AdamW), clipping of the gradient by its global L2 norm and
+a learning-rate schedule (`WarmupLinear`).  With flat buckets these ride in the
+update launch, plus one reduction launch in front of it when clipping is on.
 """
 from .autograd import Gradients, AbstractTensor
 
@@ -66,14 +71,56 @@ class SGD(Optimizer):
         return update
 
 
+class WarmupLinear(object):
+    """learning-rate schedule of the BERT recipes: the factor rises linearly over `warmup_steps` steps to 1 and then falls
+    linearly to 0 at `total_steps` (and stays there).  `factor(steps_done)` is evaluated in python floats (double); the
+    flat-bucket update launch evaluates the same expressions on the device from its step counter (csrc/optim.hip)."""
+
+    def __init__(self, warmup_steps: int, total_steps: int):
+        warmup_steps, total_steps = int(warmup_steps), int(total_steps)
+        assert 0 <= warmup_steps <= total_steps, "WarmupLinear needs 0 <= warmup_steps <= total_steps, got %d and %d" % (warmup_steps, total_steps)
+        self.warmup_steps, self.total_steps = warmup_steps, total_steps
+
+    def factor(self, steps_done: int) -> float:
+        if steps_done < self.warmup_steps:
+            return (steps_done + 1) / self.warmup_steps
+        return max(0.0, (self.total_steps - steps_done) / max(1, self.total_steps - self.warmup_steps))
+
+
 class Adam(Optimizer):
     """Adam (Kingma & Ba): running means of the gradient (`m`) and of its square (`v`), both bias-corrected by the number of
-    updates `t` - which, as in the reference (optim.py:36), counts every PARAMETER's update, not every step."""
+    updates `t` - which, as in the reference (optim.py:36), counts every PARAMETER's update, not every step.
+
+    The rest of a training recipe, every part off by default (a step then runs exactly as it did without them).  With `s` the
+    optimizer steps done before this one (`t // len(parameters)`):
+      max_grad_norm  the gradients (after grad_scale) are multiplied by min(1, max_grad_norm / (norm + 1e-6)), norm their
+                     global L2 norm - which `grad_norm()` returns afterwards, as it was before clipping
+      schedule       an object with `factor(steps_done) -> float` (`WarmupLinear`): the step uses lr * schedule.factor(s)
+      weight_decay   decoupled (AdamW): a decaying parameter also moves by -(lr_s * weight_decay) * p.  `decay_mask` holds
+                     one bool per parameter; None: a parameter decays iff it has 2 or more dimensions (no decay on biases
+                     and LayerNorm parameters)
+    The expression form defines them on every backend (it reads the norm back to the host to form the coefficient).  With
+    flat buckets they ride in the update launch - the schedule as a function of the DEVICE step counter, so a replayed
+    hipGraph follows it - plus one reduction launch in front of it when clipping is on; the only schedule that launch knows
+    is `WarmupLinear`.  `fused=True` WITHOUT flat buckets falls back to the expression form when any of them is set."""
     belief = False
 
     def __init__(self, parameters, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
-                 fused: bool = False, grad_scale: float = 1.0, device_step: bool = False):
+                 fused: bool = False, grad_scale: float = 1.0, device_step: bool = False,
+                 weight_decay: float = 0.0, decay_mask=None, max_grad_norm: float = None, schedule=None):
         Optimizer.__init__(self, parameters)
+        self.weight_decay, self.max_grad_norm, self.schedule = weight_decay, max_grad_norm, schedule
+        if weight_decay == 0:
+            self.decay_mask = (False,) * len(self.parameters)            # (the mask is ignored without a decay)
+        elif decay_mask is None:
+            self.decay_mask = tuple(len(p.shape) >= 2 for p in self.parameters)
+        else:
+            self.decay_mask = tuple(bool(d) for d in decay_mask)
+            assert len(self.decay_mask) == len(self.parameters), \
+                "decay_mask holds %d entries for %d parameters" % (len(self.decay_mask), len(self.parameters))
+        self._recipe = weight_decay != 0 or max_grad_norm is not None or schedule is not None
+        self._grad_norm = None          # 0-d tensor: the global gradient norm of the last step, before clipping
+        self._clip_scratch = None       # flat buckets with clipping: (partial sums, ticket, (norm, coef)) of the norm launch
         self.lr, self.eps = lr, eps
         self.b1, self.b2 = beta1, beta2
         count = len(self.parameters)
@@ -89,12 +136,38 @@ class Adam(Optimizer):
     def second_moment_input(self, grad, m):
         return grad
 
-    def compute_delta(self, grad, i):
+    def compute_delta(self, grad, i, lr=None):
         self.t += 1
         self.m[i] = self.b1 * self.m[i] + (1 - self.b1) * grad
         self.v[i] = self.b2 * self.v[i] + (1 - self.b2) * self.second_moment_input(grad, self.m[i])**2
         m, v = self.m[i] / (1 - self.b1**self.t), self.v[i] / (1 - self.b2**self.t)
-        return -self.lr * m / (v**0.5 + self.eps)
+        return -(self.lr if lr is None else lr) * m / (v**0.5 + self.eps)
+
+    def grad_norm(self):
+        """the global L2 norm of the gradients of the last step (after grad_scale, BEFORE clipping): a 0-d tensor of the
+        parameters' backend.  Needs max_grad_norm."""
+        assert self.max_grad_norm is not None, "grad_norm() is computed for clipping: pass max_grad_norm"
+        if self._clip_scratch is not None:
+            return self._clip_scratch[2][0]
+        assert self._grad_norm is not None, "no step taken yet"
+        return self._grad_norm
+
+    def _step_recipe_expression(self) -> None:
+        """one step with weight decay / clipping / schedule as tensor expressions: the definition, on every backend"""
+        steps_done = self.t // len(self.parameters)
+        grads = [p.grad if self.grad_scale == 1.0 else p.grad * self.grad_scale for p in self.parameters]
+        if self.max_grad_norm is not None:
+            total = None
+            for g in grads:
+                sq = (g * g).sum()
+                total = sq if total is None else total + sq
+            self._grad_norm = total ** 0.5
+            coef = min(1.0, self.max_grad_norm / (float(self._grad_norm.item()) + 1e-6))      # (no tensor-level minimum: host)
+            grads = [g * coef for g in grads]
+        lr = self.lr if self.schedule is None else self.lr * self.schedule.factor(steps_done)
+        for i, (p, g) in enumerate(zip(self.parameters, grads)):
+            delta = self.compute_delta(g, i, lr)
+            p += (delta + (-(lr * self.weight_decay)) * p) if self.decay_mask[i] else delta
 
     def use_flat_buckets(self, flat_params, flat_grads, offsets) -> None:
         """called by dist.DataParallel(flatten=True).attach(optimizer): parameter i is
@@ -109,11 +182,21 @@ class Adam(Optimizer):
         # the update launch advances the device step number itself: one private copy per workgroup of its grid
         longest = max(b - a for a, b in zip(self._flat[3][:-1], self._flat[3][1:]))
         self._step_counter = flat_params._new_step_counter(0, slots=max(1, len(self.parameters) * -(-longest // 1024)))
+        if self._recipe:
+            assert hasattr(flat_params, "_fused_adamw_multi_dev"), "the backend's flat-bucket update knows no weight decay / clipping / schedule"
+            assert self.schedule is None or type(self.schedule) is WarmupLinear, \
+                "the flat-bucket update evaluates the schedule on the device and knows WarmupLinear only"
+            if self.max_grad_norm is not None:
+                self._clip_scratch = flat_params._new_grad_norm_scratch()        # allocated here, never inside a (capturable) step
 
     def use_peer_exchange(self, comm) -> None:
         """data parallel with a communicator whose exchange rides in the optimizer launch (dist.PeerWindowCommunicator):
         step() first sums the flat gradient bucket over the ranks, in the same kernel"""
         assert self._flat is not None and hasattr(self._flat[0], "_fused_adam_multi_p2p"), "use_flat_buckets() first"
+        assert not self._recipe, \
+            "weight_decay / max_grad_norm / schedule are not part of the launch that exchanges the gradients between the ranks " \
+            "(clipping needs the whole summed gradient before any update; decay and schedule inside that launch are not built): " \
+            "attach(optimizer, exchange_in_optimizer=False) keeps the exchange in sync_gradients()"
         assert self.t == 0, "switch to the exchange inside the optimizer launch before the first step"
         self._peer_exchange = comm
         offsets = self._flat[3]
@@ -135,6 +218,9 @@ class Adam(Optimizer):
         assert self._flat is not None and hasattr(self._flat[0], "_new_backward_update"), "use_flat_buckets() first (dist.DataParallel(flatten=True).attach)"
         assert self._peer_exchange is None and not self._exchange_outside, \
             "the update cannot ride in the backward kernels when the gradients are exchanged first"
+        assert not self._recipe, \
+            "weight_decay / max_grad_norm / schedule cannot ride in the backward kernels: clipping needs the WHOLE gradient " \
+            "before any parameter moves, and decay and schedule inside the update plans are not built"
         assert self.t % max(1, len(self.parameters)) == 0
         flat_p, flat_m, flat_v, offsets = self._flat
         self._backward_update = flat_p._new_backward_update(self.parameters, self._flat_grad, flat_m, flat_v, offsets, self.lr, self.b1, self.b2,
@@ -159,10 +245,23 @@ class Adam(Optimizer):
             for p in self.parameters:
                 p._materialize_zero_grad()        # parameters no gradient reached since zero_grad
             flat_p, flat_m, flat_v, offsets = self._flat
+            if self._recipe:
+                # (an exchange outside this launch has already summed the bucket: the norm is the same on every rank)
+                if self._clip_scratch is not None:
+                    self._flat_grad._grad_norm_clip(self.grad_scale, self.max_grad_norm, self._clip_scratch)
+                kind, warmup, total = (0, 0, 0) if self.schedule is None else (1, self.schedule.warmup_steps, self.schedule.total_steps)
+                flat_p._fused_adamw_multi_dev(self._flat_grad, flat_m, flat_v, offsets, self.lr, self.b1, self.b2, self.eps,
+                                              self._step_counter, self.grad_scale, self.belief, self.weight_decay, self.decay_mask,
+                                              None if self._clip_scratch is None else self._clip_scratch[2], kind, warmup, total)
+                self.t += n_params
+                return
             update = flat_p._fused_adam_multi_dev if self._peer_exchange is None else flat_p._fused_adam_multi_p2p
             update(self._flat_grad, flat_m, flat_v, offsets, self.lr, self.b1, self.b2, self.eps,
                                          self._step_counter, self.grad_scale, self.belief)   # advances the device counter too
             self.t += n_params
+            return
+        if self._recipe:                          # (fused=True has no per-parameter kernel for these: the expression form)
+            self._step_recipe_expression()
             return
         for i, p in enumerate(self.parameters):
             kernel = getattr(p, "_fused_adam_step", None) if self.fused else None
@@ -186,7 +285,8 @@ class Adam(Optimizer):
             self.parameters[0]._advance_step_counter(self._step_counter)      # these kernels only read the counter: one tiny launch
 
     def on_graph_replay(self, n: int = 1) -> None:
-        """keep the host-side step count in line after `n` replays of a captured step"""
+        """keep the host-side step count in line after `n` replays of a captured step (the schedule needs nothing here: the
+        flat-bucket launch evaluates it from the device step counter, which the replays advance)"""
         self.t += n * len(self.parameters)
 
 
