@@ -105,7 +105,9 @@ int lg_graph_kernel_count(void* graph, int* kernels);          /* kernel launche
 
 /* dst[idx] = src[idx] over `shape`; either side may be strided/broadcast.
  * replaces the `atom` kernel with op 'o = a' used by contiguous()/copy()/getitem/setitem
- * (opencl/tensor.py:103-116, opencl/ops.py:322-340). itemsize in {1,2,4,8}. */
+ * (opencl/tensor.py:103-116, opencl/ops.py:322-340). itemsize in {1,2,4,8}.
+ * Elements are read and written in no particular order: `src` must not overlap `dst` unless it is the identical view (same
+ * pointer, same strides).  A caller that moves data within one buffer (`t[:, 1:] = t[:, :-1]`) copies the source first. */
 int lg_copy_strided(int itemsize, int ndim, const int64_t* shape,
                     void* dst, const int64_t* dst_strides,
                     const void* src, const int64_t* src_strides);
@@ -122,7 +124,11 @@ int lg_fill_strided(int itemsize, int ndim, const int64_t* shape,
  * a NULL operand pointer means "this operand is the scalar `scalar`"
  * (reference: scalar kernel arguments, kernels.py:139-150).
  * out0/out1 are written; an output may alias an input with identical strides
- * (in-place forms `a += b`, kernels.py `additional_read`).
+ * (in-place forms `a += b`, kernels.py `additional_read`).  That is the ONLY overlap allowed: an input that shares
+ * memory with an output must be the identical view (same pointer, same strides), so that every element is read and
+ * written by the one thread that owns it.  Any other overlap - `t += t^T`, a shifted slice of the output - is read in
+ * no defined order relative to the writes and gives wrong values; the caller copies such an input first (numpy's
+ * "right-hand side first", what autograd/hip/ops.py does).  The two outputs must not overlap each other.
  * The library picks a vectorised contiguous path, an inner-dimension
  * vectorised path or a generic strided path; results do not depend on it. */
 typedef enum {
@@ -160,6 +166,19 @@ int lg_ew(int op, int ndim, const int64_t* shape,
           const void* d, const int64_t* d_strides,
           float scalar);
 
+/* Which kernel family the most recent lg_ew call of the calling thread launched (lg_copy_strided calls it for 4-byte items that
+ * are not one dense run): host bookkeeping for tests, no device work.
+ *   out = {path, form, ndim, mask}
+ * path: 0 = flat, 1 = rows (float4 along the inner dimension), 2 = transposed tile (staged through LDS), 3 = flat-2D (dense 2-D
+ * outputs, any 2-D inputs), 4 = gather (one element per thread), -1 = nothing launched (no elements, a refused call: the other
+ * fields are then 0);
+ * form: flat - bit 0 = the float4 kernel ran, bit 1 = the scalar tail kernel ran; transposed tile - 0 = the scalar tile, 1 = float4
+ * with one staged input, 2 = float4 with two staged inputs, 3 = the 128 x 128 tile; otherwise 0;
+ * ndim: dimensions left after dropping extents of 1 and merging jointly contiguous neighbours;
+ * mask: bit i = input i, as the kernel got it - flat: the input steps through memory (clear: it is one value in memory);
+ * transposed tile: the input is staged; flat-2D: the input is dense and moves as float4; otherwise 0. */
+int lg_ew_last_plan(int32_t out[4]);
+
 /* ---- reductions fp32 -------------------------------------------------------
  * replaces the multi-pass `reduce` kernel (opencl/kernels.py:344-501) as used by
  * sum/max/min (opencl/ops.py:344-400).  Dimensions whose bit is set in
@@ -179,7 +198,8 @@ int lg_reduce(int op, int ndim, const int64_t* shape,
  * (cpu/ops.py:52-84, :260-293): integers wrap around, integer sums are int64, max / min keep the dtype and propagate NaN.
  *   lg_ew_typed      out = a (op) b, all three of `dtype`, numpy broadcasting through strides; op = LG_EW_COPY / NEG (unary),
  *                    ADD / SUB / MUL, and for float64 DIV / POW; a NULL operand is the scalar (scalar_i for integers, scalar_f
- *                    for float64); out may alias an operand element for element (in-place forms)
+ *                    for float64); out may alias an operand element for element (in-place forms) and in no other way: an operand that
+ *                    overlaps `out` must be the identical view, as for lg_ew
  *   lg_reduce_typed  as lg_reduce; `out` holds int64 for integer sums, `dtype` otherwise
  *   lg_cast          out[i] = (dst type) in[i], any pair of the five dtypes (numpy's astype: float -> int truncates) */
 typedef enum { LG_DT_I16 = 1, LG_DT_I32 = 2, LG_DT_I64 = 3, LG_DT_F64 = 4, LG_DT_F32 = 5 } lg_dtype_t;

@@ -66,6 +66,7 @@ PROTOTYPES = {
     "lg_fill_strided": (c_int, [c_int, c_int, _I64P, c_void_p, _I64P, c_uint64]),
     "lg_ew": (c_int, [c_int, c_int, _I64P, c_void_p, _I64P, c_void_p, _I64P,
                       c_void_p, _I64P, c_void_p, _I64P, c_void_p, _I64P, c_void_p, _I64P, c_float]),
+    "lg_ew_last_plan": (c_int, [POINTER(ctypes.c_int32)]),
     "lg_reduce": (c_int, [c_int, c_int, _I64P, c_void_p, _I64P, c_uint32, c_void_p]),
     "lg_ew_typed": (c_int, [c_int, c_int, c_int, _I64P, c_void_p, _I64P, c_void_p, _I64P, c_void_p, _I64P, c_double, c_int64]),
     "lg_reduce_typed": (c_int, [c_int, c_int, c_int, _I64P, c_void_p, _I64P, c_uint32, c_void_p]),

@@ -53,11 +53,25 @@ def _bstrides(t, shape):
     return (0,) * lead + tuple(0 if s == 1 and o != 1 else st for s, st, o in zip(t._shape, t._strides, shape[lead:]))
 
 
+def _apart_from(out, t):
+    """`t` as an operand of a kernel that writes `out`.  The kernels read and write in no particular order, so an input that
+    overlaps the output must be the IDENTICAL view (every element is then read and written by the one thread that owns it:
+    `a += b`, `t *= t`).  Any other view of `out`'s storage - `t += t.transpose(1, 0)`, a shifted slice - is copied first, which
+    is numpy's answer ("the right-hand side is evaluated before the assignment").  One identity comparison per operand, false for
+    every operand that lives elsewhere; two interleaved views are not proven disjoint, they are copied."""
+    if t._data is not out._data or t._data is None:
+        return t
+    if t._offset == out._offset and t._strides == out._strides and t._shape == out._shape:
+        return t
+    return t.copy(requires_grad=False)
+
+
 def _ew(op, shape, ins, scalar=0.0, n_out=1, out=None):
     """enqueue one lg_ew call; `ins` holds HipTensors or None (= the scalar operand)"""
     L = _l.lib()
     if out is not None:
         flush_lazy_readers(out)          # writing into existing storage: lazy tensors defined from it are computed first
+        ins = [t if t is None else _apart_from(out, t) for t in ins]
     outs = [out] if out is not None else [HipTensor.empty(shape) for _ in range(n_out)]
     args = []
     for k in range(4):
@@ -107,6 +121,8 @@ def _ew_typed(op, dt, shape, a, b, out=None):
     if out is not None:
         assert out._dtype == dt
         flush_lazy_readers(out)
+        a = _apart_from(out, a) if isinstance(a, HipTensor) else a
+        b = _apart_from(out, b) if isinstance(b, HipTensor) else b
     else:
         out = HipTensor.empty(shape, dtype=dt)
     scalar = next((x for x in (a, b) if x is not None and not isinstance(x, HipTensor)), 0)
@@ -1083,6 +1099,8 @@ def _put(a, plan, val):
     if isinstance(val, HipTensor):
         assert val._dtype == a._dtype, "setitem: dtype mismatch (%s <- %s)" % (a._dtype, val._dtype)
         assert _broadcast_shapes(shape, val._shape) == shape, "setitem: value of shape %s does not broadcast to %s" % (val._shape, shape)
+        if val._data is a._data and val._data is not None:
+            val = val.copy(requires_grad=False)       # a view of the tensor being written: read it first (see _apart_from)
         if val._shape != shape or not val.is_contiguous():
             full = HipTensor.empty(shape, dtype=a._dtype, requires_grad=False)
             _l.check(_l.lib().lg_copy_strided(a._dtype.itemsize, len(shape), i64(shape), full.ptr, i64(full._strides), val.ptr,
@@ -1291,6 +1309,9 @@ class setitem(Function):
             assert val._dtype == a._dtype, "setitem: dtype mismatch (%s <- %s)" % (a._dtype, val._dtype)
             assert _broadcast_shapes(view._shape, val._shape) == view._shape, \
                 "setitem: value of shape %s does not broadcast to %s" % (val._shape, view._shape)
+            val = _apart_from(view, val)      # `t[:, 1:] = <a view of t>`: the copy kernels do not order reads before writes
+            if val._data is view._data:
+                return a                      # the identical view: nothing to move
             _l.check(_l.lib().lg_copy_strided(a._dtype.itemsize, len(view._shape), i64(view._shape), view.ptr,
                                               i64(view._strides), val.ptr, i64(_bstrides(val, view._shape))))
         else:

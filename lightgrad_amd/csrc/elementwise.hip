@@ -455,6 +455,16 @@ __global__ void __launch_bounds__(256) ew_flat2d_vec4(EwArgs a, IterDesc d, int 
 }
 
 // ---- host dispatch ----------------------------------------------------------------------------
+// lg_ew_last_plan: which kernel family the most recent lg_ew call of this thread launched - host bookkeeping written where the
+// launch is issued, so that a test can see which path its shape reached after the conditions below move.
+// {path, form, collapsed ndim, the mask the kernel got}; a call that launches nothing leaves path = -1.
+enum { EW_NONE = -1, EW_FLAT = 0, EW_ROWS = 1, EW_TRANSPOSED = 2, EW_FLAT2D = 3, EW_GATHER = 4 };
+enum { EW_TILE_SCALAR = 0, EW_TILE_V4_ONE = 1, EW_TILE_V4_TWO = 2, EW_TILE_BIG = 3 };
+static thread_local int32_t g_ew_plan[4] = {EW_NONE, 0, 0, 0};
+static void note_ew(int path, int form = 0, int ndim = 0, int mask = 0) {
+    g_ew_plan[0] = path; g_ew_plan[1] = form; g_ew_plan[2] = ndim; g_ew_plan[3] = mask;
+}
+
 template <class Op>
 static int launch_ew(const EwArgs& args, const IterDesc& d) {
     hipStream_t s = rt().stream;
@@ -490,6 +500,7 @@ static int launch_ew(const EwArgs& args, const IterDesc& d) {
             hipLaunchKernelGGL((ew_flat_scalar<Op>), dim3(stream_grid(d.numel - tail_begin)), dim3(256), 0, s, args,
                                tail_begin, d.numel, mask);
         }
+        note_ew(EW_FLAT, (nvec > 0 ? 1 : 0) | (tail_begin < d.numel ? 2 : 0), nd, step_mask);
         return LG_OK;
     }
 
@@ -517,6 +528,7 @@ static int launch_ew(const EwArgs& args, const IterDesc& d) {
             hipLaunchKernelGGL((ew_rows_vec4<Op, uint32_t>), dim3(stream_grid(nvec)), dim3(256), 0, s, args, d, nvec);
         else
             hipLaunchKernelGGL((ew_rows_vec4<Op, uint64_t>), dim3(stream_grid(nvec)), dim3(256), 0, s, args, d, nvec);
+        note_ew(EW_ROWS, 0, nd);
         return LG_OK;
     }
 
@@ -544,7 +556,9 @@ static int launch_ew(const EwArgs& args, const IterDesc& d) {
                     else if (s1 == 1) v4 = aligned16(args.in[i]) && s0 % 4 == 0;
                 }
                 const bool one = __builtin_popcount(tr_mask) == 1;
-                if (v4 && one && d.numel >= (int64_t(1) << 25))                   // 128 MiB and more per operand
+                const bool big = v4 && one && d.numel >= (int64_t(1) << 25);     // 128 MiB and more per operand
+                note_ew(EW_TRANSPOSED, big ? EW_TILE_BIG : v4 ? (one ? EW_TILE_V4_ONE : EW_TILE_V4_TWO) : EW_TILE_SCALAR, nd, tr_mask);
+                if (big)
                     launch_transposed_big<Op, 128, 128, 1024>(s, args, d, __builtin_ctz(tr_mask));
                 else if (v4 && one)
                     hipLaunchKernelGGL((ew_transposed_tile_v4<Op, 1>), dim3(unsigned(tiles_r * tiles_c)), dim3(256), 0, s, args, d,
@@ -573,6 +587,7 @@ static int launch_ew(const EwArgs& args, const IterDesc& d) {
         if (ok) {
             const int64_t nvec = d.numel / 4;
             hipLaunchKernelGGL((ew_flat2d_vec4<Op>), dim3(unsigned((nvec + 255) / 256)), dim3(256), 0, s, args, d, dense_mask, nvec);
+            note_ew(EW_FLAT2D, 0, nd, dense_mask);
             return LG_OK;
         }
     }
@@ -581,6 +596,7 @@ static int launch_ew(const EwArgs& args, const IterDesc& d) {
         hipLaunchKernelGGL((ew_gather<Op, uint32_t>), dim3(stream_grid(d.numel)), dim3(256), 0, s, args, d);
     else
         hipLaunchKernelGGL((ew_gather<Op, uint64_t>), dim3(stream_grid(d.numel)), dim3(256), 0, s, args, d);
+    note_ew(EW_GATHER, 0, nd);
     return LG_OK;
 }
 
@@ -596,6 +612,7 @@ extern "C" int lg_ew(int op, int ndim, const int64_t* shape,
                      const void* c, const int64_t* c_strides,
                      const void* d, const int64_t* d_strides,
                      float scalar) {
+    note_ew(EW_NONE);                    // an empty or refused call reports that it launched nothing
     LG_REQUIRE_INIT();
     LG_ARG(ndim >= 0 && ndim <= LG_MAX_DIMS, "lg_ew: ndim %d out of range [0, %d]", ndim, LG_MAX_DIMS);
     LG_ARG(ndim == 0 || shape != nullptr, "lg_ew: shape is NULL");
@@ -661,5 +678,11 @@ extern "C" int lg_ew(int op, int ndim, const int64_t* shape,
     }
     if (rc != LG_OK) return rc;
     LG_CHECK_LAUNCH();
+    return LG_OK;
+}
+
+extern "C" int lg_ew_last_plan(int32_t out[4]) {
+    LG_ARG(out != nullptr, "lg_ew_last_plan: NULL pointer");
+    for (int k = 0; k < 4; ++k) out[k] = g_ew_plan[k];
     return LG_OK;
 }
