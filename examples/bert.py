@@ -16,6 +16,8 @@ Differences from the reference, on purpose:
     one-launch forms (`layer_norm_dropout`, `dropout_add_layer_norm`) the pair is one node, with the same masks.
 
     python examples/bert.py [--cpu] [--batch 8]        # forward + backward of a random tiny-BERT
+    python examples/bert.py --mlm [--graph]            # the masked-LM objective: token masking from the random stream (inside the
+                                                       # capture with --graph), cross-entropy over the masked positions only
 """
 import math
 import os
@@ -223,8 +225,13 @@ class BertForMaskedLM(nn.Module):
         self.cls.predictions.decoder = nn.Linear(hidden_size, vocab_size, bias=False)
         self.cls.predictions.bias = light.zeros(vocab_size)
 
-    def forward(self, input_ids, attention_mask=None, token_type_ids=None):
+    def forward(self, input_ids, attention_mask=None, token_type_ids=None, masked_positions=None):
         h = self.bert(input_ids=input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids)
+        if masked_positions is not None:
+            # only the positions to predict go through the head: a constant int tensor of flat indices into the (b * s) token rows,
+            # of static length (b * max_predictions; a padded slot may name any row - its label carries the loss's ignore_index).
+            # The logits then have len(masked_positions) rows; the gather's backward scatter-adds into the hidden rows
+            h = h.reshape(-1, h.shape[-1])[masked_positions]
         t = self.cls.predictions.transform
         h = t.LayerNorm(gelu(t.dense(h)))
         return self.cls.predictions.decoder(h) + self.cls.predictions.bias
@@ -239,8 +246,27 @@ def forward_backward(model, ids):
     return loss
 
 
+MASK_TOKEN, SPECIAL_TOKENS = 103, (0, 100, 101, 102)          # [MASK]; [PAD], [UNK], [CLS], [SEP] of the public BERT vocabulary
+
+
+def mlm_forward_backward(model, ids, p=0.15):
+    """one masked-LM step: mask the batch from the backend's random stream (on the device for HipTensors - inside a captured
+    graph every replay masks a fresh batch), predict, and average the loss over the selected positions only"""
+    vocab = model.cls.predictions.decoder.weight.shape[0]
+    masked, labels = light.data.mask_tokens(ids, p, MASK_TOKEN, vocab, special_ids=SPECIAL_TOKENS, ignore_index=-100)
+    logits = model(masked)
+    loss = light.loss.cross_entropy(logits.reshape(-1, vocab), labels.reshape(-1), ignore_index=-100)
+    for q in model.parameters():
+        q.zero_grad()
+    loss.backward()
+    return loss
+
+
 if __name__ == "__main__":
     cpu = "--cpu" in sys.argv
+    if "--mlm" in sys.argv:
+        light.manual_seed(0)
+        forward_backward = mlm_forward_backward            # the masked-LM objective in place of the stand-in loss below
     batch = int(sys.argv[sys.argv.index("--batch") + 1]) if "--batch" in sys.argv else 8
     to_device = (lambda t: t) if cpu else (lambda t: t.hip())
     np.random.seed(0)

@@ -683,6 +683,18 @@ int lg_cross_entropy_f32(const float* logits, const void* labels, int label_item
 int lg_cross_entropy_mean_f32(const float* logits, const void* labels, int label_itemsize, float* dlogits, float* nll,
                               float* mean, int64_t rows, int64_t cols);
 
+/* The masked-LM form: rows whose label - as stored, before any negative-index wrap - equals ignore_index do not count.
+ *   valid[r] = label[r] != ignore_index;  n = number of valid rows (written to n_valid[0], device memory, by a count launch in front)
+ *   nll[r] = valid ? -log(softmax(logits[r])[label[r]]) : 0;   mean[0] = (sum of nll) * float(1.0 / double(n))
+ *   dlogits[r][c] = valid ? (softmax(logits[r])[c] - [c == label[r]]) * float(1.0 / double(n)) : +0.0
+ * An ignored row's logits are not read (they may hold NaN or infinities).  A valid label outside [-cols, cols) behaves as above
+ * (NaN + LG_STATUS_BAD_INDEX).  n == 0: mean = NaN, dlogits all +0.0, no status flag.  The factor is formed on the device from
+ * n_valid, so the call is legal under graph capture with labels that change between replays.  Launches: the count + what
+ * lg_cross_entropy_mean_f32 takes for the shape (vocabulary-sized rows: 2 in all; otherwise count, rows, sum, scale).
+ * Same argument checks as lg_cross_entropy_mean_f32; n_valid must not be NULL. */
+int lg_cross_entropy_ignore_f32(const float* logits, const void* labels, int label_itemsize, float* dlogits, float* nll,
+                                float* mean, int64_t* n_valid, int64_t rows, int64_t cols, int64_t ignore_index);
+
 /* ---- dropout from a counter-based random stream (csrc/dropout.hip) -----------------------------------
  * The generator is Philox4x32-10 and its state - a 64-bit seed and the 64-bit number of dropout calls so far, `draws` - lives
  * in device memory owned by the library (allocated by lg_init: seed 0, draws 0).  For the call with draws == b, element i of
@@ -701,6 +713,22 @@ int lg_rng_state(uint64_t* seed, uint64_t* draws);       /* synchronises the str
 int lg_dropout_fwd_f32(const float* x, const float* residual /* may be NULL */, float* y, int64_t n,
                        double p, uint64_t* base_out);
 int lg_dropout_bwd_f32(const float* g, float* dx, int64_t n, double p, const uint64_t* base);
+
+/* ---- BERT's token masking from the same stream (csrc/mlm.hip) ------------------------------------------
+ * ONE call of the stream: `draws` advances by exactly one, whatever n is (n == 0 included: one workgroup is launched), and the
+ * value read is written to base_out[0].  For the call with draws == b, element i (flat index) takes the WHOLE block
+ *   w = philox4x32_10(counter = (lo32(i), hi32(i), lo32(b), hi32(b)), key = (lo32(seed), hi32(seed)))
+ * and is SELECTED iff ids[i] is none of special_ids[0 .. n_special) and w[0] < T(p) (T as above):
+ *   not selected:  masked[i] = ids[i], labels[i] = ignore_index
+ *   selected:      labels[i] = ids[i];  masked[i] = mask_token_id                       if w[1] < 3435973836  (floor(0.8 * 2^32))
+ *                                                   (uint64(w[2]) * vocab_size) >> 32   else if w[1] < 3865470566  (floor(0.9 * 2^32))
+ *                                                   ids[i]                              otherwise
+ * ids / masked / labels: dense int32 (itemsize 4) or int64 (8) device arrays of n elements, no two the same; special_ids is
+ * HOST memory, read during the call (at most 8, passed to the kernel by value).  Seed and draws are read by the kernel: a
+ * captured graph masks a fresh batch on every replay.  0 <= p < 1; 0 <= n <= 2^32; 1 <= vocab_size <= 2^31; mask_token_id and
+ * ignore_index must fit the ids' type. */
+int lg_mlm_mask(const void* ids, int itemsize, void* masked, void* labels, int64_t n, double p, int64_t mask_token_id,
+                int64_t vocab_size, const int64_t* special_ids, int n_special, int64_t ignore_index, uint64_t* base_out);
 
 /* ---- hidden dropout inside the LayerNorm launches (csrc/rowwise.hip) ----------------------------------
  * A dropout that sits directly in front of or behind a LayerNorm over dense fp32 [rows, cols], drawn where the LayerNorm

@@ -303,6 +303,19 @@ class dropout(DropoutFunction):
         return (dx, out_grad) if has_residual else dx
 
 
+def _mlm_mask(ids, p, mask_token_id, vocab_size, special_ids=(), ignore_index=-100):
+    """ ids.mlm_mask(p, mask_token_id, vocab_size, special_ids=(), ignore_index=-100) -> (masked_ids, labels): BERT's token
+    masking as `lightgrad_amd.random.mlm_mask_words` defines it for this call's number - one call of the stream.  int32 / int64
+    ids of any shape; both results have the ids' dtype and shape and are constants of the tape. """
+    args = _random.check_mlm_arguments(ids.dtype, p, mask_token_id, vocab_size, special_ids, ignore_index)
+    seed, draw = _random._CpuGenerator.seed, _random._CpuGenerator.next_draw()
+    masked, labels = _random.mlm_mask_words(seed, draw, ids.data, *args)
+    return CpuTensor.from_numpy(masked, requires_grad=False), CpuTensor.from_numpy(labels, requires_grad=False)
+
+
+CpuTensor.mlm_mask = _mlm_mask
+
+
 """ Convolution (CNN example; reference cpu/ops.py:298-356) """
 
 

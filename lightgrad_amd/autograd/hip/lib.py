@@ -146,6 +146,7 @@ PROTOTYPES = {
     "lg_layernorm_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64]),
     "lg_cross_entropy_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int64]),
     "lg_cross_entropy_mean_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64]),
+    "lg_cross_entropy_ignore_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64]),
     "lg_layernorm_param_grads_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int]),
     "lg_take_axis": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int64, c_int64, c_void_p]),
     "lg_put_axis": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int64, c_int64, c_void_p, c_uint64]),
@@ -160,6 +161,7 @@ PROTOTYPES = {
     "lg_rng_state": (c_int, [POINTER(c_uint64), POINTER(c_uint64)]),
     "lg_dropout_fwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_double, c_void_p]),
     "lg_dropout_bwd_f32": (c_int, [c_void_p, c_void_p, c_int64, c_double, c_void_p]),
+    "lg_mlm_mask": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_double, c_int64, c_int64, POINTER(c_int64), c_int, c_int64, c_void_p]),
     "lg_dropout_layernorm_fwd_f32": (c_int, [c_void_p] * 7 + [c_int64, c_int64, c_float, c_double, c_int, c_void_p]),
     "lg_dropout_layernorm_bwd_f32": (c_int, [c_void_p] * 7 + [c_int64, c_int64, c_double, c_int, c_void_p]),
 }

@@ -2007,6 +2007,25 @@ class dropout(DropoutFunction):
         return (dx, out_grad) if has_residual else dx
 
 
+def _mlm_mask(ids, p, mask_token_id, vocab_size, special_ids=(), ignore_index=-100):
+    """ ids.mlm_mask(p, mask_token_id, vocab_size, special_ids=(), ignore_index=-100) -> (masked_ids, labels): BERT's token
+    masking in one launch of csrc/mlm.hip, which reads the generator's state from device memory and advances it by one call (a
+    captured step masks a fresh batch at every replay).  The bits of the numpy backend (lightgrad_amd/random.py). """
+    p, mask_token_id, vocab_size, special_ids, ignore_index = _random.check_mlm_arguments(ids._dtype, p, mask_token_id, vocab_size,
+                                                                                          special_ids, ignore_index)
+    src = ids.contiguous()                   # element index = index in the dense result
+    masked = HipTensor.empty(ids._shape, dtype=ids._dtype, requires_grad=False)
+    labels = HipTensor.empty(ids._shape, dtype=ids._dtype, requires_grad=False)
+    base = _dropout_base()
+    special = (ctypes.c_int64 * _py.max(len(special_ids), 1))(*special_ids)
+    _l.check(_l.lib().lg_mlm_mask(src.ptr, ids._dtype.itemsize, masked.ptr, labels.ptr, src.numel(), p, mask_token_id, vocab_size,
+                                  special, len(special_ids), ignore_index, base.ptr))
+    return masked, labels
+
+
+HipTensor.mlm_mask = _mlm_mask
+
+
 def _rows_view(t):
     """dense (rows, cols) pointer view of a tensor whose last axis is the row"""
     t = t.contiguous()
@@ -2539,9 +2558,11 @@ def mse_forward(y, y_hat):
     return loss, err
 
 
-def cross_entropy_forward(y, labels):
+def cross_entropy_forward(y, labels, ignore_index=None):
     """fused loss.cross_entropy forward for logits (N, C) and integer labels (N,): returns (mean nll of shape (),
-    dlogits = (softmax(y) - onehot) / N) from one row-wise pass (lg_cross_entropy_f32) + the mean over rows"""
+    dlogits = (softmax(y) - onehot) / N) from one row-wise pass (lg_cross_entropy_f32) + the mean over rows.  With `ignore_index`
+    the rows carrying that label do not count: N is the number of the others, counted on the device, and the ignored rows of
+    dlogits are +0.0 (lg_cross_entropy_ignore_f32)"""
     _require_f32(y)
     assert len(y._shape) == 2 and labels._shape == (y._shape[0],), \
         "cross_entropy: logits %s and labels %s do not match" % (y._shape, labels._shape)
@@ -2554,6 +2575,11 @@ def cross_entropy_forward(y, labels):
         total = _reduce(_l.RED_SUM, nll, (0,), False)
         return _ew(_l.EW_MUL, (), [total, None], scalar=float("nan")), dlogits          # mean of nothing
     loss = HipTensor.empty(())
+    if ignore_index is not None:
+        n_valid = HipTensor.empty((1,), dtype=np.int64, requires_grad=False)
+        _l.check(_l.lib().lg_cross_entropy_ignore_f32(y.ptr, labels.ptr, labels._dtype.itemsize, dlogits.ptr, nll.ptr, loss.ptr, n_valid.ptr,
+                                                      n, c, int(ignore_index)))
+        return loss, dlogits
     _l.check(_l.lib().lg_cross_entropy_mean_f32(y.ptr, labels.ptr, labels._dtype.itemsize, dlogits.ptr, nll.ptr, loss.ptr, n, c))
     return loss, dlogits
 

@@ -675,10 +675,11 @@ class HipTensor(AbstractTensor):
                 return fused
         return mse_forward(self, y_hat)
 
-    def _fused_cross_entropy(self, labels):
-        """optional loss hook (loss.cross_entropy): (loss, (softmax - onehot) / N) from one row-wise kernel"""
+    def _fused_cross_entropy(self, labels, ignore_index=None):
+        """optional loss hook (loss.cross_entropy): (loss, (softmax - onehot) / N) from one row-wise kernel; with `ignore_index`
+        N counts the rows whose label differs from it, and the others get a zero gradient"""
         from .ops import cross_entropy_forward
-        return cross_entropy_forward(self, labels)
+        return cross_entropy_forward(self, labels, ignore_index=ignore_index)
 
     def _fused_adam_multi_dev(self, grad, m, v, offsets, lr, b1, b2, eps, step_counter, grad_scale, belief):
         """self/grad/m/v are flat buckets holding len(offsets)-1 parameters: ONE launch updates them all and advances the step

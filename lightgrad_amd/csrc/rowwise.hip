@@ -311,13 +311,57 @@ __global__ void __launch_bounds__(256) layernorm_param_grads_group(LnParamGradsG
 
 // ---- cross entropy of softmax(logits) against integer labels (reference loss.py:14-24) ------------------------
 // one wave per row: p = softmax(row); nll[row] = -log(p[label]); d[row][c] = (p[c] - [c == label]) / rows
+//
+// The ignoring forms (IGN, lg_cross_entropy_ignore_f32): a row whose label, as stored, equals `ignore` is not read - its wave or
+// workgroup writes +0.0 over the gradient row and nll[row] = 0 - and the other rows are scaled by 1 / n_valid in place of
+// 1 / rows.  n_valid[0] is device memory, written by count_valid_labels in front (a captured graph's labels change between
+// replays, so the host cannot pass the factor).  Every kernel below is one body with that flag; the launches without it pass
+// IGN = false and compile to what they were.  The held kernel has no register to spare for a division in double next to the
+// row it holds: the count launch leaves the factor in mean[0], where the held kernel reads it - the one workgroup that
+// arrives last replaces it by the mean, after every workgroup has used it (a workgroup takes its ticket behind its last use).
+__device__ __forceinline__ float ce_inv_valid(const int64_t* n_valid) {
+    return float(1.0 / double(n_valid[0]));
+}
+
+// the number of labels that differ from `ignore`: ONE workgroup, each thread counts rows t, t + 1024, ...; integers, so the order
+// of the additions does not matter and the result is the same on every run
 template <typename LabelT>
-__global__ void __launch_bounds__(256) cross_entropy_rows(const float* __restrict__ x, const LabelT* __restrict__ labels,
-                                                          float* __restrict__ dlogits, float* __restrict__ nll, int64_t rows,
-                                                          int64_t cols, float inv_rows, int* status) {
+__global__ void __launch_bounds__(1024) count_valid_labels(const LabelT* __restrict__ labels, int64_t rows, int64_t ignore,
+                                                           int64_t* __restrict__ n_valid, float* __restrict__ inv_valid) {
+    __shared__ int red_n[16];
+    int mine = 0;                                    // rows / 1024 <= 2^21 per thread
+    for (int64_t r = threadIdx.x; r < rows; r += 1024) mine += int64_t(labels[r]) != ignore ? 1 : 0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
+    if ((threadIdx.x & 63) == 0) red_n[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int64_t total = 0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) total += red_n[w];
+        n_valid[0] = total;
+        inv_valid[0] = float(1.0 / double(total));       // no valid row: +inf, and the mean 0 * inf = NaN like the mean of nothing
+    }
+}
+
+// mean[0] *= 1 / n_valid, the factor read from device memory (lg_ew's scalar is a host value)
+__global__ void scale_by_inv_valid(float* mean, const int64_t* n_valid) { mean[0] = mean[0] * ce_inv_valid(n_valid); }
+
+template <bool IGN, typename LabelT>
+__device__ __forceinline__ void cross_entropy_rows_body(const float* __restrict__ x, const LabelT* __restrict__ labels,
+                                                        float* __restrict__ dlogits, float* __restrict__ nll, int64_t rows,
+                                                        int64_t cols, float inv_rows, int* status, int64_t ignore, const int64_t* n_valid) {
     const int lane = threadIdx.x & 63;
     const int64_t row = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
+    if constexpr (IGN) {
+        if (int64_t(labels[row]) == ignore) {            // (the whole wave: nothing of the logits row is read)
+            for (int64_t c = lane; c < cols; c += 64) dlogits[row * cols + c] = 0.0f;
+            if (lane == 0) nll[row] = 0.0f;
+            return;
+        }
+        inv_rows = ce_inv_valid(n_valid);
+    }
     const float* xr = x + row * cols;
     float m = -INFINITY;
     for (int64_t c = lane; c < cols; c += 64) { const float t = xr[c]; m = (t > m || t != t) ? t : m; }
@@ -338,15 +382,37 @@ __global__ void __launch_bounds__(256) cross_entropy_rows(const float* __restric
     }
 }
 
+template <typename LabelT>
+__global__ void __launch_bounds__(256) cross_entropy_rows(const float* __restrict__ x, const LabelT* __restrict__ labels,
+                                                          float* __restrict__ dlogits, float* __restrict__ nll, int64_t rows,
+                                                          int64_t cols, float inv_rows, int* status) {
+    cross_entropy_rows_body<false>(x, labels, dlogits, nll, rows, cols, inv_rows, status, 0, nullptr);
+}
+
+template <typename LabelT>
+__global__ void __launch_bounds__(256) cross_entropy_rows_ignore(const float* __restrict__ x, const LabelT* __restrict__ labels,
+                                                                 float* __restrict__ dlogits, float* __restrict__ nll, int64_t rows,
+                                                                 int64_t cols, int* status, int64_t ignore, const int64_t* n_valid) {
+    cross_entropy_rows_body<true>(x, labels, dlogits, nll, rows, cols, 0.0f, status, ignore, n_valid);
+}
+
 // wide rows (a vocabulary): one WORKGROUP per row.  Pass 1 keeps a running (max, sum of exp) per thread over coalesced
 // loads, combined across the workgroup; pass 2 re-reads the row (L2 / Infinity Cache) and writes the gradient.
-template <typename LabelT>
-__global__ void __launch_bounds__(256) cross_entropy_wide(const float* __restrict__ x, const LabelT* __restrict__ labels,
-                                                          float* __restrict__ dlogits, float* __restrict__ nll, int64_t cols,
-                                                          float inv_rows, int* status) {
+template <bool IGN, typename LabelT>
+__device__ __forceinline__ void cross_entropy_wide_body(const float* __restrict__ x, const LabelT* __restrict__ labels,
+                                                        float* __restrict__ dlogits, float* __restrict__ nll, int64_t cols,
+                                                        float inv_rows, int* status, int64_t ignore, const int64_t* n_valid) {
     __shared__ float red_m[4], red_s[4];
     const int64_t row = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if constexpr (IGN) {
+        if (int64_t(labels[row]) == ignore) {            // (the whole workgroup, before any barrier)
+            for (int64_t c = threadIdx.x; c < cols; c += 256) dlogits[row * cols + c] = 0.0f;
+            if (threadIdx.x == 0) nll[row] = 0.0f;
+            return;
+        }
+        inv_rows = ce_inv_valid(n_valid);
+    }
     const float* xr = x + row * cols;
     float m = -INFINITY, sum = 0.f;
     auto absorb = [&](float t) {
@@ -388,6 +454,20 @@ __global__ void __launch_bounds__(256) cross_entropy_wide(const float* __restric
     }
 }
 
+template <typename LabelT>
+__global__ void __launch_bounds__(256) cross_entropy_wide(const float* __restrict__ x, const LabelT* __restrict__ labels,
+                                                          float* __restrict__ dlogits, float* __restrict__ nll, int64_t cols,
+                                                          float inv_rows, int* status) {
+    cross_entropy_wide_body<false>(x, labels, dlogits, nll, cols, inv_rows, status, 0, nullptr);
+}
+
+template <typename LabelT>
+__global__ void __launch_bounds__(256) cross_entropy_wide_ignore(const float* __restrict__ x, const LabelT* __restrict__ labels,
+                                                                 float* __restrict__ dlogits, float* __restrict__ nll, int64_t cols,
+                                                                 int* status, int64_t ignore, const int64_t* n_valid) {
+    cross_entropy_wide_body<true>(x, labels, dlogits, nll, cols, 0.0f, status, ignore, n_valid);
+}
+
 // wide rows that one workgroup can HOLD in registers (cols <= THREADS * PER): the row is read from memory once - maximum, exp
 // and sum work on the held values (numpy's own order of operations: max, exp(x - max), sum, divide) and the gradient is
 // written straight from them.  Two shapes: 1024 threads x 8 / 16 values, and for a vocabulary 512 threads x 60 values - at 128
@@ -395,14 +475,61 @@ __global__ void __launch_bounds__(256) cross_entropy_wide(const float* __restric
 // back-to-back launches (tools/ce_bench.py): two-pass kernel 72.7 us, this one 58.6 us = 4.3 TB/s of logits read + gradient
 // written (61.4 without the line-aligned walk below).  Measured and not kept: a 2^x-based exp for non-positive arguments, 8
 // instructions instead of ~25 - 70.8 us, SLOWER: the kernel is bound by its memory phases, not by the exps.
-template <typename LabelT, int PER, int THREADS>
-__global__ void __launch_bounds__(THREADS, 4) cross_entropy_held(const float* __restrict__ x, const LabelT* __restrict__ labels,
-                                                                 float* __restrict__ dlogits, float* nll, int64_t cols, float inv_rows,
-                                                                 int* status, float* mean_out, int* ticket) {
+// mean over rows inside the held launch (saves the reduction + scaling launches behind it): drain, take a ticket, the last
+// workgroup sums the row losses in a fixed order - thread t takes rows t, t + THREADS, ...; waves, then the workgroup, in
+// index order - and multiplies by 1/rows like the two-kernel form.  Every thread of the workgroup calls it; red_s is free.
+// IGN: the factor is what the count launch left in mean_out[0].
+template <bool IGN, int THREADS>
+__device__ __forceinline__ void cross_entropy_held_mean(const float* nll, float inv_rows, float* mean_out, int* ticket, float* red_s) {
+    constexpr int WAVES = THREADS / 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    __shared__ int arrived_last;
+    if (tid == 0) {
+        const int order = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int last = order == int(gridDim.x) - 1;
+        if (last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        arrived_last = last;
+    }
+    __syncthreads();
+    if (!arrived_last) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    float total = 0.f;
+    for (int64_t i = tid; i < int64_t(gridDim.x); i += THREADS)
+        total += __hip_atomic_load(nll + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    total = wave_sum(total);
+    __syncthreads();                             // red_s is free again
+    if (lane == 0) red_s[wave] = total;
+    __syncthreads();
+    if (tid == 0) {
+        float t = 0.f;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) t += red_s[w];
+        mean_out[0] = t * (IGN ? mean_out[0] : inv_rows);
+    }
+}
+
+template <bool IGN, typename LabelT, int PER, int THREADS>
+__device__ __forceinline__ void cross_entropy_held_body(const float* __restrict__ x, const LabelT* __restrict__ labels,
+                                                        float* __restrict__ dlogits, float* nll, int64_t cols, float inv_rows,
+                                                        int* status, float* mean_out, int* ticket, int64_t ignore) {
     constexpr int WAVES = THREADS / 64;
     __shared__ float red_m[WAVES], red_s[WAVES];
     const int64_t row = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if constexpr (IGN) {
+        if (int64_t(labels[row]) == ignore) {            // (the whole workgroup) nothing of the logits row is read
+            const int zoff = int((row * cols) & 31), zcols = int(cols) + zoff;       // the line-aligned walk of the stores below
+            float* zr = dlogits + row * cols - zoff;
+#pragma unroll 1                                 // (a rolled loop: unrolled, its 60 column indices are hoisted over the branch into the path below)
+            for (int c = tid; c < zcols; c += THREADS)
+                if (c >= zoff) zr[c] = 0.0f;
+            if (tid == 0) __hip_atomic_store(nll + row, 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            cross_entropy_held_mean<IGN, THREADS>(nll, 0.0f, mean_out, ticket, red_s);
+            return;
+        }
+    }
     // A row starts wherever the previous one ended (30522 floats: 8-byte aligned at best).  The threads walk the row from
     // the 128-byte line its first element lies in: every wave access then covers whole lines - unaligned, each 256-byte
     // access touches three lines instead of two, for the reads and for the gradient writes alike.
@@ -451,6 +578,12 @@ __global__ void __launch_bounds__(THREADS, 4) cross_entropy_held(const float* __
 #pragma unroll
     for (int w = 0; w < WAVES; ++w) S += red_s[w];
     const float inv = 1.0f / S;
+    if constexpr (IGN) {
+        // 1 / n_valid, once per workgroup, and the label a second time: scalar loads here, so that nothing more than in the
+        // launch without the flag stays in a register across the phases above (the 60 x 512 shape has none to spare)
+        inv_rows = mean_out[0];
+        asm volatile("" : "+s"(labels));
+    }
     int64_t label = int64_t(labels[row]);
     if (label < 0) label += cols;
     if (label < 0 || label >= cols) {
@@ -473,42 +606,36 @@ __global__ void __launch_bounds__(THREADS, 4) cross_entropy_held(const float* __
     // per-row losses are published write-through: the workgroup that arrives LAST reads all of them for the mean (below)
     if (p_label >= 0.0f || p_label != p_label) __hip_atomic_store(nll + row, -logf(p_label), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (mean_out == nullptr) return;
-    // mean over rows inside this launch (saves the reduction + scaling launches behind it): drain, take a ticket, the last
-    // workgroup sums the row losses in a fixed order - thread t takes rows t, t + THREADS, ...; waves, then the workgroup, in
-    // index order - and multiplies by 1/rows like the two-kernel form
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    __shared__ int arrived_last;
-    if (tid == 0) {
-        const int order = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = order == int(gridDim.x) - 1;
-        if (last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        arrived_last = last;
-    }
-    __syncthreads();
-    if (!arrived_last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    float total = 0.f;
-    for (int64_t i = tid; i < int64_t(gridDim.x); i += THREADS)
-        total += __hip_atomic_load(nll + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    total = wave_sum(total);
-    __syncthreads();                             // red_s is free again
-    if (lane == 0) red_s[wave] = total;
-    __syncthreads();
-    if (tid == 0) {
-        float t = 0.f;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) t += red_s[w];
-        mean_out[0] = t * inv_rows;
-    }
+    cross_entropy_held_mean<IGN, THREADS>(nll, inv_rows, mean_out, ticket, red_s);
 }
 
+template <typename LabelT, int PER, int THREADS>
+__global__ void __launch_bounds__(THREADS, 4) cross_entropy_held(const float* __restrict__ x, const LabelT* __restrict__ labels,
+                                                                 float* __restrict__ dlogits, float* nll, int64_t cols, float inv_rows,
+                                                                 int* status, float* mean_out, int* ticket) {
+    cross_entropy_held_body<false, LabelT, PER, THREADS>(x, labels, dlogits, nll, cols, inv_rows, status, mean_out, ticket, 0);
+}
+
+template <typename LabelT, int PER, int THREADS>
+__global__ void __launch_bounds__(THREADS, 4) cross_entropy_held_ignore(const float* __restrict__ x, const LabelT* __restrict__ labels,
+                                                                        float* __restrict__ dlogits, float* nll, int64_t cols, int* status,
+                                                                        float* mean_out, int* ticket, int64_t ignore) {
+    cross_entropy_held_body<true, LabelT, PER, THREADS>(x, labels, dlogits, nll, cols, 0.0f, status, mean_out, ticket, ignore);
+}
+
+// n_valid != nullptr: the ignoring form (n_valid[0], and the factor in mean_out[0], are written by a launch in front)
 template <typename LabelT>
 static void launch_cross_entropy_held(const float* logits, const LabelT* labels, float* dlogits, float* nll, int64_t rows, int64_t cols,
-                                      float inv_rows, float* mean_out) {
+                                      float inv_rows, float* mean_out, int64_t ignore = 0, const int64_t* n_valid = nullptr) {
     const dim3 grid{unsigned(rows)};
     hipStream_t s = rt().stream;
     int* ticket = rt().gemm_tickets + rt().n_gemm_tickets - 1;          // the last slot: nobody else counts that far
+    if (n_valid != nullptr) {
+        if (cols + 31 <= 1024 * 8)       hipLaunchKernelGGL((cross_entropy_held_ignore<LabelT, 8, 1024>), grid, dim3(1024), 0, s, logits, labels, dlogits, nll, cols, rt().status_dev, mean_out, ticket, ignore);
+        else if (cols + 31 <= 1024 * 16) hipLaunchKernelGGL((cross_entropy_held_ignore<LabelT, 16, 1024>), grid, dim3(1024), 0, s, logits, labels, dlogits, nll, cols, rt().status_dev, mean_out, ticket, ignore);
+        else                             hipLaunchKernelGGL((cross_entropy_held_ignore<LabelT, 60, 512>), grid, dim3(512), 0, s, logits, labels, dlogits, nll, cols, rt().status_dev, mean_out, ticket, ignore);
+        return;
+    }
     if (cols + 31 <= 1024 * 8)       hipLaunchKernelGGL((cross_entropy_held<LabelT, 8, 1024>), grid, dim3(1024), 0, s, logits, labels, dlogits, nll, cols, inv_rows, rt().status_dev, mean_out, ticket);
     else if (cols + 31 <= 1024 * 16) hipLaunchKernelGGL((cross_entropy_held<LabelT, 16, 1024>), grid, dim3(1024), 0, s, logits, labels, dlogits, nll, cols, inv_rows, rt().status_dev, mean_out, ticket);
     else                             hipLaunchKernelGGL((cross_entropy_held<LabelT, 60, 512>), grid, dim3(512), 0, s, logits, labels, dlogits, nll, cols, inv_rows, rt().status_dev, mean_out, ticket);
@@ -889,8 +1016,9 @@ extern "C" int lg_scatter_add_rows_f32(const float* grad_out, const void* ids, i
     return LG_OK;
 }
 
+// n_valid != nullptr: the ignoring form - one count launch in front, then the ignoring instantiation of the same dispatch
 static int cross_entropy_impl(const float* logits, const void* labels, int label_itemsize, float* dlogits, float* nll,
-                              int64_t rows, int64_t cols, float* mean_out, bool* mean_done) {
+                              int64_t rows, int64_t cols, float* mean_out, bool* mean_done, int64_t ignore = 0, int64_t* n_valid = nullptr) {
     *mean_done = false;
     LG_REQUIRE_INIT();
     LG_ARG(label_itemsize == 2 || label_itemsize == 4 || label_itemsize == 8, "lg_cross_entropy_f32: labels must be int16/int32/int64");
@@ -901,12 +1029,33 @@ static int cross_entropy_impl(const float* logits, const void* labels, int label
     const float inv_rows = float(1.0 / double(rows));
     hipStream_t s = rt().stream;
     static const char* ce_env = getenv("LG_CE_HELD");        // experiments only: 0 = the two-pass kernel for every width
+    if (n_valid != nullptr) {
+        if (label_itemsize == 2)      hipLaunchKernelGGL(count_valid_labels<int16_t>, dim3(1), dim3(1024), 0, s, static_cast<const int16_t*>(labels), rows, ignore, n_valid, mean_out);
+        else if (label_itemsize == 4) hipLaunchKernelGGL(count_valid_labels<int32_t>, dim3(1), dim3(1024), 0, s, static_cast<const int32_t*>(labels), rows, ignore, n_valid, mean_out);
+        else                          hipLaunchKernelGGL(count_valid_labels<int64_t>, dim3(1), dim3(1024), 0, s, static_cast<const int64_t*>(labels), rows, ignore, n_valid, mean_out);
+        LG_CHECK_LAUNCH();
+    }
     if (cols >= 4096 && cols + 31 <= 512 * 60 && rows < (int64_t(1) << 31) && !(ce_env && atoi(ce_env) == 0)) {
         // a vocabulary per row that fits one workgroup's registers: a single pass over memory
-        if (label_itemsize == 2)      launch_cross_entropy_held(logits, static_cast<const int16_t*>(labels), dlogits, nll, rows, cols, inv_rows, mean_out);
-        else if (label_itemsize == 4) launch_cross_entropy_held(logits, static_cast<const int32_t*>(labels), dlogits, nll, rows, cols, inv_rows, mean_out);
-        else                          launch_cross_entropy_held(logits, static_cast<const int64_t*>(labels), dlogits, nll, rows, cols, inv_rows, mean_out);
+        if (label_itemsize == 2)      launch_cross_entropy_held(logits, static_cast<const int16_t*>(labels), dlogits, nll, rows, cols, inv_rows, mean_out, ignore, n_valid);
+        else if (label_itemsize == 4) launch_cross_entropy_held(logits, static_cast<const int32_t*>(labels), dlogits, nll, rows, cols, inv_rows, mean_out, ignore, n_valid);
+        else                          launch_cross_entropy_held(logits, static_cast<const int64_t*>(labels), dlogits, nll, rows, cols, inv_rows, mean_out, ignore, n_valid);
         *mean_done = mean_out != nullptr;
+        LG_CHECK_LAUNCH();
+        return LG_OK;
+    }
+    if (n_valid != nullptr) {                               // the two launches below in their ignoring form
+        const dim3 wgrid{unsigned(rows)};
+        const bool wide = cols >= 4096 && rows < (int64_t(1) << 31);
+#define LG_CE_IGNORE(T)                                                                                                                  \
+        do {                                                                                                                             \
+            if (wide) hipLaunchKernelGGL(cross_entropy_wide_ignore<T>, wgrid, block, 0, s, logits, static_cast<const T*>(labels), dlogits, nll, cols, rt().status_dev, ignore, n_valid); \
+            else hipLaunchKernelGGL(cross_entropy_rows_ignore<T>, grid, block, 0, s, logits, static_cast<const T*>(labels), dlogits, nll, rows, cols, rt().status_dev, ignore, n_valid); \
+        } while (0)
+        if (label_itemsize == 2)      LG_CE_IGNORE(int16_t);
+        else if (label_itemsize == 4) LG_CE_IGNORE(int32_t);
+        else                          LG_CE_IGNORE(int64_t);
+#undef LG_CE_IGNORE
         LG_CHECK_LAUNCH();
         return LG_OK;
     }
@@ -950,6 +1099,22 @@ extern "C" int lg_cross_entropy_mean_f32(const float* logits, const void* labels
     const int64_t none[1] = {1};
     return lg_ew(LG_EW_MUL, 0, none, mean, none, nullptr, nullptr, mean, none, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                  float(1.0 / double(rows)));                       // mean = mean * (1 / rows): the scalar is operand b
+}
+
+extern "C" int lg_cross_entropy_ignore_f32(const float* logits, const void* labels, int label_itemsize, float* dlogits, float* nll,
+                                           float* mean, int64_t* n_valid, int64_t rows, int64_t cols, int64_t ignore_index) {
+    LG_ARG(mean != nullptr && rows >= 1, "lg_cross_entropy_ignore_f32: needs rows >= 1 and a place for the mean");
+    LG_ARG(n_valid != nullptr, "lg_cross_entropy_ignore_f32: needs a place for the number of valid rows");
+    bool done = false;
+    int rc = cross_entropy_impl(logits, labels, label_itemsize, dlogits, nll, rows, cols, mean, &done, ignore_index, n_valid);
+    if (rc != LG_OK || done) return rc;
+    // narrow / very wide rows: the generic sum, then * (1 / n_valid) with the factor read on the device
+    const int64_t shape[1] = {rows}, strides[1] = {1};
+    rc = lg_reduce(LG_RED_SUM, 1, shape, nll, strides, 1u, mean);
+    if (rc != LG_OK) return rc;
+    hipLaunchKernelGGL(scale_by_inv_valid, dim3(1), dim3(1), 0, rt().stream, mean, n_valid);
+    LG_CHECK_LAUNCH();
+    return LG_OK;
 }
 
 extern "C" int lg_layernorm_param_grads_f32(const float* g, const float* xhat, float* dw, float* db, int64_t rows, int64_t cols,

@@ -45,3 +45,15 @@ class Dataset(object):
             self.shuffle()
         for first in range(0, self.n, self._batch):
             yield self[first:first + self._batch]
+
+
+def mask_tokens(ids, p: float = 0.15, mask_token_id: int = 103, vocab_size: int = 30522, special_ids=(), ignore_index: int = -100) -> tuple:
+    """BERT's token masking for the masked-LM objective: `ids.mlm_mask(...)` -> (masked_ids, labels).  Each id that is none of
+    `special_ids` is selected with probability p; a selected one becomes the label of its position and is replaced by
+    `mask_token_id` (80 %), a uniform token of the vocabulary (10 %) or left as it is (10 %); every other position gets the label
+    `ignore_index` - what `loss.cross_entropy(..., ignore_index=)` leaves out.  Drawn from the backend's counter-based stream
+    (lightgrad_amd/random.py; one call), on the device for HipTensors: inside a captured graph every replay masks a fresh batch.
+    The defaults are those of the public BERT vocabulary ([MASK] = 103)."""
+    if not isinstance(ids, AbstractTensor):
+        raise TypeError("mask_tokens needs a tensor of int32 / int64 ids")
+    return ids.mlm_mask(p, mask_token_id, vocab_size, special_ids=special_ids, ignore_index=ignore_index)

@@ -1,4 +1,4 @@
-"""The random stream behind `Tensor.dropout`: one definition, arithmetic only, shared by both backends.
+"""The random stream behind `Tensor.dropout` and `Tensor.mlm_mask`: one definition, arithmetic only, shared by both backends.
 
 The generator is Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85, ten rounds).  Its
 state is a 64-bit `seed` and the 64-bit number of dropout calls so far, `draws`.  For the call with draws == b, element i of
@@ -10,6 +10,16 @@ and is kept iff that word >= T, T = min(floor(p * 2**32), 2**32 - 1); kept eleme
 A call advances `draws` by exactly one, whatever the tensor's size.  The numpy backend evaluates this here; the HIP backend
 evaluates the same arithmetic in csrc/dropout.hip from a state that lives in device memory, so the two produce the same mask
 bit for bit, and a captured hipGraph draws a fresh mask on every replay.
+
+`Tensor.mlm_mask` (BERT's token masking) is one call of the same stream, `draws` advancing by one: for the call with
+draws == b, element i of the flattened ids takes the WHOLE block
+
+    w = philox4x32_10(counter = (lo32(i), hi32(i), lo32(b), hi32(b)), key)        = words(seed, b, 4 * n).reshape(n, 4)[i]
+
+and is selected iff ids[i] is none of the special ids and w[0] < T (the T above).  An element that is not selected keeps its id
+and gets the label `ignore_index`; a selected one gets its id as label and becomes the mask token if w[1] < floor(0.8 * 2**32),
+the uniform token (uint64(w[2]) * vocab_size) >> 32 if w[1] < floor(0.9 * 2**32), and stays as it is otherwise.
+`mlm_mask_words` below is the definition; csrc/mlm.hip evaluates it on the device.
 
     manual_seed(seed)        seed every backend's generator, draws back to 0
     get_state(backend)       (seed, draws) of "cpu" or "hip"
@@ -53,6 +63,43 @@ def scale(p: float) -> np.float32:
 
 def keep_mask(seed: int, draw: int, n: int, p: float) -> np.ndarray:
     return words(seed, draw, n) >= np.uint32(threshold(p))
+
+
+MLM_MASK_BELOW, MLM_RANDOM_BELOW = 3435973836, 3865470566        # floor(0.8 * 2**32), floor(0.9 * 2**32)
+MLM_MAX_SPECIAL = 8
+
+
+def check_mlm_arguments(dtype, p, mask_token_id, vocab_size, special_ids, ignore_index):
+    """the validated (p, mask_token_id, vocab_size, special_ids, ignore_index) of an `mlm_mask` call on ids of `dtype`"""
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+        raise TypeError("mlm_mask: ids must be int32 or int64 (got %s)" % dtype)
+    p = check_probability(p)
+    mask_token_id, vocab_size, ignore_index = int(mask_token_id), int(vocab_size), int(ignore_index)
+    special_ids = tuple(int(t) for t in special_ids)
+    if len(special_ids) > MLM_MAX_SPECIAL:
+        raise ValueError("mlm_mask: at most %d special ids (got %d)" % (MLM_MAX_SPECIAL, len(special_ids)))
+    if not 1 <= vocab_size <= 1 << 31:
+        raise ValueError("mlm_mask: vocab_size must lie in [1, 2**31] (got %r)" % vocab_size)
+    info = np.iinfo(dtype)
+    for name, v in (("mask_token_id", mask_token_id), ("ignore_index", ignore_index)):
+        if not info.min <= v <= info.max:
+            raise ValueError("mlm_mask: %s = %d does not fit %s" % (name, v, dtype))
+    return p, mask_token_id, vocab_size, special_ids, ignore_index
+
+
+def mlm_mask_words(seed: int, draw: int, ids, p: float, mask_token_id: int, vocab_size: int, special_ids=(), ignore_index: int = -100):
+    """(masked ids, labels) of call number `draw` for the integer array `ids`: same dtype and shape"""
+    ids = np.asarray(ids)
+    flat = ids.reshape(-1)
+    w = words(seed, draw, 4 * flat.size).reshape(flat.size, 4)          # element i: the block of counter i
+    selected = (w[:, 0] < np.uint32(threshold(p))) & ~np.isin(flat, np.asarray(special_ids, dtype=np.int64))
+    uniform = ((w[:, 2].astype(np.uint64) * np.uint64(vocab_size)) >> _SHIFT).astype(ids.dtype)
+    replaced = np.where(w[:, 1] < np.uint32(MLM_MASK_BELOW), ids.dtype.type(mask_token_id),
+                        np.where(w[:, 1] < np.uint32(MLM_RANDOM_BELOW), uniform, flat))
+    masked = np.where(selected, replaced, flat).astype(ids.dtype)
+    labels = np.where(selected, flat, ids.dtype.type(ignore_index)).astype(ids.dtype)
+    return masked.reshape(ids.shape), labels.reshape(ids.shape)
 
 
 def check_probability(p) -> float:
