@@ -18,6 +18,8 @@ Differences from the reference, on purpose:
     python examples/bert.py [--cpu] [--batch 8]        # forward + backward of a random tiny-BERT
     python examples/bert.py --mlm [--graph]            # the masked-LM objective: token masking from the random stream (inside the
                                                        # capture with --graph), cross-entropy over the masked positions only
+    python examples/bert.py --mlm --accuracy [--graph] # also counts the masked tokens predicted right (light.metrics.accuracy), on
+                                                       # the device, over every step and replay: one host read at the end
 """
 import math
 import os
@@ -249,13 +251,16 @@ def forward_backward(model, ids):
 MASK_TOKEN, SPECIAL_TOKENS = 103, (0, 100, 101, 102)          # [MASK]; [PAD], [UNK], [CLS], [SEP] of the public BERT vocabulary
 
 
-def mlm_forward_backward(model, ids, p=0.15):
+def mlm_forward_backward(model, ids, p=0.15, accuracy_total=None):
     """one masked-LM step: mask the batch from the backend's random stream (on the device for HipTensors - inside a captured
-    graph every replay masks a fresh batch), predict, and average the loss over the selected positions only"""
+    graph every replay masks a fresh batch), predict, and average the loss over the selected positions only.  With
+    `accuracy_total` - an int64 tensor {correct, counted} - the step's masked tokens predicted right are added to it."""
     vocab = model.cls.predictions.decoder.weight.shape[0]
     masked, labels = light.data.mask_tokens(ids, p, MASK_TOKEN, vocab, special_ids=SPECIAL_TOKENS, ignore_index=-100)
     logits = model(masked)
     loss = light.loss.cross_entropy(logits.reshape(-1, vocab), labels.reshape(-1), ignore_index=-100)
+    if accuracy_total is not None:
+        light.metrics.accuracy(logits.reshape(-1, vocab), labels.reshape(-1), ignore_index=-100, into=accuracy_total)
     for q in model.parameters():
         q.zero_grad()
     loss.backward()
@@ -272,6 +277,11 @@ if __name__ == "__main__":
     np.random.seed(0)
     model = BertForMaskedLM(**TINY).map_parameters(to_device)
     ids = to_device(light.from_numpy(np.random.randint(0, TINY["vocab_size"], (batch, 128)).astype(np.int32), requires_grad=False))
+    total = None
+    if "--accuracy" in sys.argv:
+        assert "--mlm" in sys.argv, "--accuracy counts the masked tokens of the --mlm objective"
+        total = to_device(light.from_numpy(np.zeros(2, np.int64), requires_grad=False))
+        forward_backward = lambda m, i: mlm_forward_backward(m, i, accuracy_total=total)      # noqa: E731
     for it in range(3):
         t0 = time.perf_counter()
         value = forward_backward(model, ids).item()            # .item() synchronises
@@ -290,3 +300,6 @@ if __name__ == "__main__":
             value = loss.item()
             if it < 3 or it == replays - 1:
                 print("replay %d: loss %.6f  fwd+bwd %.2f ms (hipGraph)" % (it, value, 1e3 * (time.perf_counter() - t0)))
+    if total is not None:
+        correct, counted = total.numpy()                       # the only host read of the counts
+        print("masked-token accuracy %.4f (%d of %d masked tokens over every step and replay)" % (correct / max(counted, 1), correct, counted))

@@ -2,10 +2,12 @@
 the BASELINE shapes 784 -> 512 -> 10, batch 1024; the real dataset needs network access).  A NEW batch is
 generated on the host and uploaded EVERY step, so the printed rate is the PCIe-inclusive one.
 
-    python examples/mnist.py [--cpu] [--steps 200] [--graph] [--cnn]
+    python examples/mnist.py [--cpu] [--steps 200] [--graph] [--cnn] [--eval]
 
 --graph: the step is captured once into a hipGraph; every iteration uploads the batch into the graph's static
 input tensors (pinned staging, asynchronous) and replays the graph.
+--eval: after training, the reference's evaluation loop (examples/mnist.py:72-79) over held-out synthetic batches, counted on
+the model's device with `light.metrics.accuracy`: one host read, at the end.
 """
 import argparse
 import os
@@ -51,6 +53,20 @@ def synthetic_batch(rng, batch):
     return x, one_hot
 
 
+def evaluate(model, to_device, batch, n_batches=4):
+    """top-1 accuracy over held-out batches (the labels of the synthetic data are random: expect one in ten)"""
+    rng = np.random.RandomState(2)
+    total = None
+    with light.no_grad():
+        for _ in range(n_batches):
+            x, one_hot = synthetic_batch(rng, batch)
+            labels = light.from_numpy(one_hot.argmax(-1).astype(np.int64), requires_grad=False)
+            y = model(to_device(light.from_numpy(x, requires_grad=False)))
+            total = light.metrics.accuracy(y, to_device(labels), into=total)
+    correct, counted = total.numpy()                                     # the only host read of the evaluation
+    print("Accuracy:\t %.4f (%d of %d held-out samples)" % (correct / counted, correct, counted))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cpu", action="store_true")
@@ -59,6 +75,7 @@ def main():
     ap.add_argument("--loss", choices=["mse", "ce"], default="mse", help="ce: the alternative the reference keeps commented out (mnist.py:57)")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--batch", type=int, default=1024)
+    ap.add_argument("--eval", action="store_true", help="evaluate on held-out batches after training (light.metrics.accuracy)")
     args = ap.parse_args()
     to_device = (lambda t: t) if args.cpu else (lambda t: t.hip())
     np.random.seed(0)
@@ -97,7 +114,8 @@ def main():
         final = loss.item()                                              # the only synchronisation
         dt = time.perf_counter() - t0
         print("graph replay + per-step upload: final loss %.5f   %.1f steps/s (PCIe-inclusive, upload and compute in one stream)" % (final, args.steps / dt))
-
+        if args.eval:
+            evaluate(model, to_device, args.batch)
         return
 
     optim = light.optim.AdaBelief(model.parameters(), lr=0.001, fused=not args.cpu)
@@ -118,6 +136,8 @@ def main():
         dt = time.perf_counter() - t0
     print("loss %.5f -> %.5f   %.1f steps/s (eager tape, per-step upload and loss.item())" % (losses[0], losses[-1], args.steps / dt))
     prof.print(topn=12)
+    if args.eval:
+        evaluate(model, to_device, args.batch)
 
 
 if __name__ == "__main__":

@@ -226,6 +226,37 @@ int lg_reduce_acc(int op, int ndim, const int64_t* shape,
  * nk, nr: kept and reduced dimensions left after merging contiguous neighbours; vector_path_possible: `in` is 16-byte aligned. */
 int lg_reduce_last_plan(int32_t out[6]);
 
+/* ---- argmax / argmin and top-1 counting (csrc/argreduce.hip) ------------------------------------------------
+ * out[...] = the index along `axis` (axis = -1: into the row-major flattening of the whole view) of the maximum (LG_RED_MAX) or
+ * minimum (LG_RED_MIN) of a strided fp32 view; `out` is int64, CONTIGUOUS over the kept dimensions in their original order.
+ * numpy's answer bit for bit: a candidate (v, i) beats (w, j) when v is NaN and w is not; or neither is NaN and v > w (v < w
+ * for the minimum); or neither of the two holds in either direction and i < j.  So the lowest index wins among equal extrema
+ * (-0.0 == +0.0), a run of nothing but -inf answers 0, and a run that holds a NaN answers the index of its first NaN.  The
+ * order is total: every fold order gives the same result.
+ * The dimensions in front of the axis, the axis (every dimension for -1) and the dimensions behind it must each merge into at
+ * most ONE (extent, stride): any other view is refused with LG_EINVAL (copy it dense first), as is a reduced extent of 0.
+ * No output elements: LG_OK, nothing is launched. */
+int lg_argreduce_f32(int op, int ndim, const int64_t* shape, const float* in, const int64_t* in_strides, int axis, int64_t* out);
+
+/* What the most recent lg_argreduce_f32 call of the calling thread launched: host bookkeeping for tests, no device work.
+ *   out = {kernel, splits, merged, vector}
+ * kernel: 0 = one wave per row, 1 = rows split over workgroups (one workgroup per row segment), 2 = one thread per output with
+ * the axis strided, -1 = nothing launched (no output elements, a refused call: the other fields are then 0);
+ * splits: workgroups that share one output (1 = no fold); merged: the dimensions in front of and behind the axis form one
+ * output dimension (always for kernels 0 and 1); vector: the first run read holds a 16-byte aligned float4 (kernels 0, 1). */
+int lg_argreduce_last_plan(int32_t out[4]);
+
+/* Top-1 counting of dense fp32 logits [rows, cols] against integer labels [rows] (int16/32/64) in ONE launch:
+ *   counts[0] (+)= rows whose label equals the row's argmax (the rules above: a label on the second of two tied maxima is wrong,
+ *                  a row with a NaN is right only for the label of its first NaN)
+ *   counts[1] (+)= rows counted: all but those whose label, as stored, equals ignore_index (has_ignore != 0); those rows are not read
+ * accumulate != 0 adds to `counts` (a running total over batches), else `counts` is overwritten.  A negative label that is not
+ * ignored wraps by +cols; one out of range is not counted and raises the device status flag (LG_EINDEX at the next
+ * synchronising call), as lg_cross_entropy_f32 does.  Nothing is a host scalar: a captured launch counts the batch that is in
+ * the tensors at every replay. */
+int lg_top1_count_f32(const float* logits, int64_t rows, int64_t cols, const void* labels, int label_itemsize, int has_ignore,
+                      int64_t ignore_index, int accumulate, int64_t* counts);
+
 /* ---- SGEMM on MFMA ---------------------------------------------------------
  * C[b] (M x N, row-major, leading dimension ldc) (+)= op(A[b]) @ op(B[b]), fp32
  * in/out, fp32 accumulate on v_mfma_f32_32x32x2_f32.

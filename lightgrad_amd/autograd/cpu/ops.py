@@ -316,6 +316,20 @@ def _mlm_mask(ids, p, mask_token_id, vocab_size, special_ids=(), ignore_index=-1
 CpuTensor.mlm_mask = _mlm_mask
 
 
+def _arg_extremum(name):
+    np_fn = getattr(np, name)
+
+    def method(t, axis=None, keepdims=False):
+        return CpuTensor.from_numpy(np.asarray(np_fn(t.data, axis=axis, keepdims=keepdims), dtype=np.int64), requires_grad=False)
+    method.__name__ = method.__qualname__ = name
+    method.__doc__ = (""" t.%s(axis=None, keepdims=False) -> int64 indices, numpy's: the lowest index among equal extrema, the first NaN
+    when the reduced run holds one, the row-major flattening of the view for axis=None.  A constant of the tape. """ % name)
+    return method
+
+
+CpuTensor.argmax, CpuTensor.argmin = _arg_extremum("argmax"), _arg_extremum("argmin")
+
+
 """ Convolution (CNN example; reference cpu/ops.py:298-356) """
 
 

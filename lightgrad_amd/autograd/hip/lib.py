@@ -73,6 +73,9 @@ PROTOTYPES = {
     "lg_cast": (c_int, [c_int, c_int, c_int, _I64P, c_void_p, _I64P, c_void_p, _I64P]),
     "lg_reduce_acc": (c_int, [c_int, c_int, _I64P, c_void_p, _I64P, c_uint32, c_void_p, c_int]),
     "lg_reduce_last_plan": (c_int, [POINTER(ctypes.c_int32)]),
+    "lg_argreduce_f32": (c_int, [c_int, c_int, _I64P, c_void_p, _I64P, c_int, c_void_p]),
+    "lg_argreduce_last_plan": (c_int, [POINTER(ctypes.c_int32)]),
+    "lg_top1_count_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int, c_int, c_int64, c_int, c_void_p]),
     "lg_gemm_f32": (c_int, [c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64,
                             c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int]),
     "lg_gemm_pair_begin": (c_int, []),

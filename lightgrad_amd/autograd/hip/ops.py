@@ -1415,6 +1415,77 @@ max = HipTensor.register_op("max", _extremum("max", _l.RED_MAX, "every tied maxi
 min = HipTensor.register_op("min", _extremum("min", _l.RED_MIN, "cpu/ops.py:274-286"))
 
 
+def _one_stride(shape, strides):
+    """do these dimensions merge into at most one (extent, stride)?  (what lg_argreduce_f32 asks of the dimensions in front of
+    the axis, of the axis, and of those behind it)"""
+    last, left = None, 0
+    for s, st in zip(shape, strides):
+        if s == 1:
+            continue
+        if last is not None and last == st * s:
+            last = st
+        else:
+            last, left = st, left + 1
+    return left <= 1
+
+
+def _arg_extremum(name, red_op):
+    def method(x, axis=None, keepdims=False):
+        if x._dtype != _F32:
+            raise TypeError("%s is float32-only on HipTensor (got %s)" % (name, x._dtype))
+        shape, nd = x._shape, len(x._shape)
+        if axis is None:
+            reduced, kept, full = x.numel(), (), (1,) * nd
+        else:
+            axis = int(axis)
+            if not -_py.max(nd, 1) <= axis < _py.max(nd, 1):
+                raise np.exceptions.AxisError(axis, nd)
+            if nd == 0:
+                axis = None                  # numpy: a 0-d array has the one axis 0 / -1 of its flattening
+                reduced, kept, full = 1, (), ()
+            else:
+                axis %= nd
+                reduced, kept, full = shape[axis], shape[:axis] + shape[axis + 1:], shape[:axis] + (1,) + shape[axis + 1:]
+        if reduced == 0:
+            raise ValueError("attempt to get %s of an empty sequence" % name)
+        out = HipTensor.empty(kept, dtype=np.int64, requires_grad=False)
+        if out.numel() > 0:
+            if axis is None:
+                dense = _one_stride(shape, x._strides)
+            else:
+                dense = _one_stride(shape[:axis], x._strides[:axis]) and _one_stride(shape[axis + 1:], x._strides[axis + 1:])
+            src = x if dense else x.contiguous()
+            _l.check(_l.lib().lg_argreduce_f32(red_op, nd, i64(shape), src.ptr, i64(src._strides), -1 if axis is None else axis, out.ptr))
+        return HipTensor(out.data, full, None, out._offset, out._dtype, requires_grad=False) if keepdims else out
+    method.__name__ = method.__qualname__ = name
+    method.__doc__ = (""" x.%s(axis=None, keepdims=False) -> int64 indices with numpy's rules (the lowest index among equal extrema, the
+    first NaN when the reduced run holds one, the row-major flattening of the view for axis=None): one launch of
+    csrc/argreduce.hip.  A constant of the tape; float32 only. """ % name)
+    return method
+
+
+HipTensor.argmax, HipTensor.argmin = _arg_extremum("argmax", _l.RED_MAX), _arg_extremum("argmin", _l.RED_MIN)
+
+
+def top1_count(logits, labels, ignore_index=None, into=None):
+    """metrics.accuracy for HipTensors: {correct, counted} of 2-D float32 logits against integer labels in ONE launch
+    (lg_top1_count_f32), written into a new int64 tensor of shape (2,) or added to `into`"""
+    if not isinstance(labels, HipTensor):
+        raise TypeError("accuracy: the labels of HipTensor logits must be a HipTensor (got %s)" % type(labels).__name__)
+    if logits._dtype != _F32:
+        raise TypeError("accuracy is float32-only on HipTensor (got %s)" % logits._dtype)
+    y, lab = logits.contiguous(), labels.contiguous()
+    rows, cols = y._shape
+    if into is None:
+        counts = HipTensor.empty((2,), dtype=np.int64, requires_grad=False)
+    else:
+        counts = into
+        flush_lazy_readers(counts)
+    _l.check(_l.lib().lg_top1_count_f32(y.ptr, rows, cols, lab.ptr, lab._dtype.itemsize, 0 if ignore_index is None else 1,
+                                        0 if ignore_index is None else int(ignore_index), 0 if into is None else 1, counts.ptr))
+    return counts
+
+
 """ Convolution (CNN example, SURVEY.md §8f row 4 tail): window VIEW -> one gather copy -> MFMA GEMM """
 
 
