@@ -783,6 +783,45 @@ int lg_dropout_layernorm_bwd_f32(const float* g, const float* w, const float* xh
                                  float* dres /* mode 0, may be NULL */, float* gdrop /* mode 1 */, int64_t rows, int64_t cols,
                                  double p, int mode, const uint64_t* base);
 
+/* ---- 2-D convolution and pooling (csrc/conv.hip) -------------------------------------------------------
+ * Dense fp32 tensors: x [N, C, H, W], w [O, C, KH, KW], y and g [N, O, OH, OW] with OH = (H + 2 pad - KH) / sh + 1 and
+ * OW = (W + 2 pad - KW) / sw + 1: the cross-correlation of the reference's `conv` (cpu/ops.py:298-356) over an input that is
+ * zero-padded by `pad` on both sides of both spatial axes.  Each entry point is ONE launch of an implicit GEMM on fp32 MFMA: the
+ * window matrix is gathered while tiles are staged and never exists in memory; nothing outside a tensor is read.
+ *   fwd  y[n,o,oh,ow] = fl(sum over (c, kh, kw) ascending of x[n,c,oh*sh+kh-pad,ow*sw+kw-pad] * w[o,c,kh,kw]), then + bias[o]
+ *        as a second rounding when bias (O floats) is not NULL.
+ *   dx   dx[n,c,h,w] = sum over (o, kh, kw) of g[n,o,(h+pad-kh)/sh,(w+pad-kw)/sw] * w[o,c,kh,kw] over the taps whose divisions
+ *        are exact and in range.  Every element of dx is written exactly once.
+ *   dw   dw[o,c,kh,kw] = sum over (n, oh, ow) of g[n,o,oh,ow] * x[n,c,oh*sh+kh-pad,ow*sw+kw-pad] and, when db is not NULL,
+ *        db[o] = sum g[n,o,:,:] from the same launch.  The positions are split over workgroups whose partial tiles the last
+ *        arriver folds in slice order: the slice count depends on the shape only, so the result is the same bits on every run.
+ *        Both are OVERWRITTEN.
+ * relu_x != 0: x is a pre-activation and max(x, 0) (NaN kept) is applied while it is staged (fwd, dw).
+ * Refused with LG_EINVAL: an extent below 1, a stride below 1, a negative pad, a window larger than the padded input; H, W, pad
+ * or a stride above 16384; C*KH*KW or O*KH*KW above 2048 (the offset table in LDS); N*OH*OW, N*H*W, C*H*W or O*OH*OW of 2^31 or
+ * more.  The three entry points refuse the same shapes.  No output may alias an input. */
+int lg_conv2d_fwd_f32(const float* x, const float* w, const float* bias /* may be NULL */, float* y, int64_t N, int64_t C, int64_t H,
+                      int64_t W, int64_t O, int64_t KH, int64_t KW, int64_t sh, int64_t sw, int64_t pad, int relu_x);
+int lg_conv2d_dx_f32(const float* g, const float* w, float* dx, int64_t N, int64_t C, int64_t H, int64_t W, int64_t O,
+                     int64_t KH, int64_t KW, int64_t sh, int64_t sw, int64_t pad);
+int lg_conv2d_dw_f32(const float* g, const float* x, float* dw, float* db /* may be NULL */, int64_t N, int64_t C, int64_t H, int64_t W,
+                     int64_t O, int64_t KH, int64_t KW, int64_t sh, int64_t sw, int64_t pad, int relu_x);
+/* What the most recent lg_conv2d_* call of the calling thread launched: host bookkeeping for tests, no device work.
+ *   out = {kernel, tile_rows, tile_cols, k_chunk, dw_slices, relu_x}
+ * kernel: 0 fwd, 1 dx, 2 dw, -1 nothing yet; the tile is that of a workgroup; dw_slices is the number of position slices of the
+ * most recent dw call (1 = one workgroup per output tile, no fold; at most 256) and is left alone by fwd and dx. */
+int lg_conv2d_last_plan(int32_t out[6]);
+
+/* Max (op 0) / min (op 1) pooling over non-overlapping kh x kw windows of the last two axes of a dense fp32 [L, H, W] (all
+ * leading axes flattened into L); the input is cropped to a multiple of the window: y is [L, H / kh, W / kw].  NaN as in np.max /
+ * np.min: a window with a NaN gives NaN.
+ *   bwd  dx[l,h,w] = g[l,h/kh,w/kw] * (x[l,h,w] == y[l,h/kh,w/kw] ? 1 : 0): every tied extremum receives the gradient (LG_EW_MAX_BWD),
+ *        a window whose result is NaN none; the cropped margin gets +0.0.  Every element of dx is written once; y is fwd's output.
+ * Refused with LG_EINVAL: an extent below 1, a window larger than the input, L*H*W of 2^31 or more. */
+int lg_pool2d_fwd_f32(int op, const float* x, float* y, int64_t L, int64_t H, int64_t W, int64_t kh, int64_t kw);
+int lg_pool2d_bwd_f32(const float* x, const float* y, const float* g, float* dx, int64_t L, int64_t H, int64_t W, int64_t kh,
+                      int64_t kw);
+
 /* library build info: "liblghip <version> gfx950 <build date>" */
 const char* lg_version(void);
 

@@ -167,6 +167,12 @@ PROTOTYPES = {
     "lg_mlm_mask": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_double, c_int64, c_int64, POINTER(c_int64), c_int, c_int64, c_void_p]),
     "lg_dropout_layernorm_fwd_f32": (c_int, [c_void_p] * 7 + [c_int64, c_int64, c_float, c_double, c_int, c_void_p]),
     "lg_dropout_layernorm_bwd_f32": (c_int, [c_void_p] * 7 + [c_int64, c_int64, c_double, c_int, c_void_p]),
+    "lg_conv2d_fwd_f32": (c_int, [c_void_p] * 4 + [c_int64] * 10 + [c_int]),
+    "lg_conv2d_dx_f32": (c_int, [c_void_p] * 3 + [c_int64] * 10),
+    "lg_conv2d_dw_f32": (c_int, [c_void_p] * 4 + [c_int64] * 10 + [c_int]),
+    "lg_conv2d_last_plan": (c_int, [POINTER(ctypes.c_int32)]),
+    "lg_pool2d_fwd_f32": (c_int, [c_int, c_void_p, c_void_p] + [c_int64] * 5),
+    "lg_pool2d_bwd_f32": (c_int, [c_void_p] * 4 + [c_int64] * 5),
 }
 
 # include/lghip_p2p.h: the peer-window gradient exchange, exported by liblghip.so itself (no RCCL)

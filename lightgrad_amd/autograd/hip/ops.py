@@ -10,7 +10,7 @@ import builtins as _py      # this module defines ops named max / min / sum / po
 import ctypes
 import os
 import numpy as np
-from ..func import Function, _FunctionType
+from ..func import Function, WrapperFunction, _FunctionType
 from ..dropout import DropoutFunction
 from ... import random as _random
 import weakref
@@ -1547,6 +1547,176 @@ class conv(Function):
             _binary(_l.EW_ADD, dst, src, out=dst)
         assert nsp == len(k_shape) - 2
         return dx, dw
+
+
+""" conv2d and 2-D max / min pooling as kernels of their own (csrc/conv.hip): what nn.Conv2d and the CNN example run on """
+
+
+class _Refused(Exception):
+    """the C ABI answered LG_EINVAL: a shape the kernels do not take (lghip.h lists them) - the caller uses the composite"""
+
+
+def _call_or_refuse(rc):
+    if rc == -1:                                                    # LG_EINVAL
+        raise _Refused(_l.lib().lg_last_error().decode())
+    _l.check(rc)
+
+
+def _lazy_relu_input_4d(x):
+    """the dense pre-activation t if x is a still-lazy relu(t) of an image batch: conv2d applies the relu while it stages t"""
+    if x._data is None and x._lazy_source is not None and x._lazy_source[0] == "relu" and len(x._shape) == 4:
+        return x._lazy_source[1]
+    return None
+
+
+def _conv2d_geometry(x, w, bias, stride, pad):
+    """(N, C, H, W, O, KH, KW, sh, sw, pad) when the operands are what lg_conv2d_* take, else None"""
+    if not (isinstance(x, HipTensor) and isinstance(w, HipTensor)) or x._dtype != _F32 or w._dtype != _F32:
+        return None
+    if len(x._shape) != 4 or len(w._shape) != 4 or x._shape[1] != w._shape[1]:
+        return None
+    out_c = w._shape[0]
+    if bias is not None and not (isinstance(bias, HipTensor) and bias._dtype == _F32 and bias._shape in ((1, out_c, 1, 1), (out_c,))):
+        return None
+    if isinstance(stride, (int, np.integer)):
+        sh = sw = int(stride)
+    else:
+        stride = tuple(stride)
+        if len(stride) != 2:
+            return None
+        sh, sw = int(stride[0]), int(stride[1])
+    if not isinstance(pad, (int, np.integer)) or pad < 0:
+        return None
+    return x._shape + (out_c,) + w._shape[2:] + (sh, sw, int(pad))
+
+
+_conv2d_composite = HipTensor.conv2d              # autograd/ops.py: pad, conv, add
+
+
+class _conv2d_by_taps(WrapperFunction):
+    """ the composite for 4-D operands of a dtype the GEMM behind `conv` does not take (float64): per tap one strided slice of the
+    padded input, its product with that tap's (O, C) weights and the sum over the channels - ops that take any float dtype """
+    def forward(ctx, x, w, bias=None, stride=1, pad=0):
+        sh, sw = (stride, stride) if isinstance(stride, (int, np.integer)) else stride
+        xp = x.pad(pad) if pad else x
+        (n, c, h, wd), (out_c, _, kh, kw) = xp.shape, w.shape
+        oh, ow = (h - kh) // sh + 1, (wd - kw) // sw + 1
+        y = None
+        for i in range(kh):
+            for j in range(kw):
+                win = xp[:, :, i:i + sh * (oh - 1) + 1:sh, j:j + sw * (ow - 1) + 1:sw].reshape(n, 1, c, oh, ow)
+                tap = (win * w[:, :, i, j].reshape(1, out_c, c, 1, 1)).sum(axis=2)
+                y = tap if y is None else y + tap
+        if bias is None:
+            return y
+        return y + (bias if len(bias.shape) == 4 else bias.reshape(1, -1, 1, 1))
+
+
+class _Conv2dType(_FunctionType):
+    """call protocol of the node below: operands the kernels do not take (another dtype or rank, a shape the C ABI refuses) go
+    through the composite, so conv2d itself never refuses a legal call"""
+
+    def __call__(cls, x, w, bias=None, stride=1, pad=0):
+        geom = _conv2d_geometry(x, w, bias, stride, pad)
+        if geom is not None:
+            try:
+                return _FunctionType.__call__(cls, x, w, bias, geom)
+            except _Refused:
+                pass
+        elif (isinstance(x, HipTensor) and isinstance(w, HipTensor) and x._dtype == w._dtype != _F32 and x._dtype.kind == "f"
+              and len(x._shape) == len(w._shape) == 4 and x._shape[1] == w._shape[1] and isinstance(pad, (int, np.integer))
+              and x._shape[2] + 2 * pad >= w._shape[2] and x._shape[3] + 2 * pad >= w._shape[3]):
+            return _conv2d_by_taps(x, w, bias, stride=stride, pad=pad)
+        return _conv2d_composite(x, w, bias, stride=stride, pad=pad)
+
+
+@HipTensor.register_op(overwrite=True)
+class conv2d(Function, metaclass=_Conv2dType):
+    """ x.conv2d(w, bias=None, stride=1, pad=0): the values of `x.pad(pad).conv(w, strides=stride) + bias` from ONE launch of an
+    implicit GEMM (lg_conv2d_fwd_f32): no window matrix, no transpose copy, nothing but x and w saved.  backward: dW and db from
+    one launch (lg_conv2d_dw_f32), dx from one more (lg_conv2d_dx_f32) that is skipped when x wants no gradient.  A lazy
+    relu(t) as input is read as t with the relu applied while staging, forward and dW alike, like `linear` does. """
+    def forward(ctx, x, w, bias, geom):
+        pre = _lazy_relu_input_4d(x)
+        src = pre if pre is not None else x.contiguous()
+        n, _, h, wd, out_c, kh, kw, sh, sw, p = geom
+        oh, ow = (h + 2 * p - kh) // sh + 1, (wd + 2 * p - kw) // sw + 1
+        if n < 1 or oh < 1 or ow < 1:
+            raise _Refused("conv2d: no output elements")
+        y = HipTensor.empty((n, out_c, oh, ow))
+        b = bias.contiguous() if bias is not None else None
+        _call_or_refuse(_l.lib().lg_conv2d_fwd_f32(src.ptr, w.contiguous().ptr, b.ptr if b is not None else _NULL, y.ptr, *geom,
+                                                  1 if pre is not None else 0))
+        ctx.save_for_backward(x, w, geom)
+        return y
+
+    def backward(ctx, out_grad):
+        x, w, geom = ctx.get_saved_tensors()
+        bias = ctx._parents[2]
+        _require_f32(out_grad)
+        g = out_grad.contiguous()
+        wanting = ctx.parent_tensors
+        dx = dw = db = None
+        if _py.any(t is w or t is bias for t in wanting):
+            pre = _lazy_relu_input_4d(x)
+            src = pre if pre is not None else x.contiguous()
+            dw = HipTensor.empty(w._shape, requires_grad=False)
+            if bias is not None and bias.requires_grad:
+                db = HipTensor.empty(bias._shape, requires_grad=False)
+            _l.check(_l.lib().lg_conv2d_dw_f32(g.ptr, src.ptr, dw.ptr, db.ptr if db is not None else _NULL, *geom,
+                                               1 if pre is not None else 0))
+        if _py.any(t is x for t in wanting):
+            dx = HipTensor.empty(x._shape, requires_grad=False)
+            _l.check(_l.lib().lg_conv2d_dx_f32(g.ptr, w.contiguous().ptr, dx.ptr, *geom))
+        return dx, dw, db
+
+
+def conv2d_last_plan():
+    """{kernel, tile, k_chunk, dw_slices, relu_x} of the most recent lg_conv2d_* call (lghip.h: lg_conv2d_last_plan)"""
+    out = (ctypes.c_int32 * 6)()
+    _l.check(_l.lib().lg_conv2d_last_plan(out))
+    return {"kernel": ("fwd", "dx", "dw")[out[0]] if out[0] >= 0 else None, "tile": (out[1], out[2]), "k_chunk": out[3],
+            "dw_slices": out[4], "relu_x": bool(out[5])}
+
+
+def _pool2d(name, op, composite):
+    def fused(t, kernel):
+        if not isinstance(kernel, (tuple, list)) or len(kernel) != 2 or t._dtype != _F32 or len(t._shape) < 2:
+            return False
+        kh, kw = kernel
+        return 1 <= kh <= t._shape[-2] and 1 <= kw <= t._shape[-1] and 0 < t.numel() < 2 ** 31
+
+    class _Type(_FunctionType):
+        def __call__(cls, t, kernel=(2, 2)):
+            if fused(t, kernel):
+                return _FunctionType.__call__(cls, t, (int(kernel[0]), int(kernel[1])))
+            return composite(t, kernel=kernel)
+
+    class Op(Function, metaclass=_Type):
+        def forward(ctx, t, kernel):
+            x = t.contiguous()
+            (h, w), (kh, kw) = x._shape[-2:], kernel
+            y = HipTensor.empty(x._shape[:-2] + (h // kh, w // kw))
+            _l.check(_l.lib().lg_pool2d_fwd_f32(op, x.ptr, y.ptr, x.numel() // (h * w), h, w, kh, kw))
+            ctx.save_for_backward(x, _saved_output(y), kernel)
+            return y
+
+        def backward(ctx, out_grad):
+            x, y, (kh, kw) = ctx.get_saved_tensors()
+            _require_f32(out_grad)
+            h, w = x._shape[-2:]
+            dx = HipTensor.empty(x._shape, requires_grad=False)
+            _l.check(_l.lib().lg_pool2d_bwd_f32(x.ptr, y.ptr, out_grad.contiguous().ptr, dx.ptr, x.numel() // (h * w), h, w, kh, kw))
+            return dx
+    Op.__name__ = Op.__qualname__ = name
+    Op.__doc__ = (" t.%s(kernel=(kh, kw)) over the last two axes of a float32 tensor: the values and gradients of `t.pool(kernel).%s(axis=0)` "
+                  "from one launch each way (lg_pool2d_*); every tied extremum receives the gradient, the cropped margin zeros.  Other "
+                  "kernel lengths and dtypes take the composite. " % (name, name[:3]))
+    return Op
+
+
+max_pool = HipTensor.register_op("max_pool", _pool2d("max_pool", 0, HipTensor.max_pool), overwrite=True)
+min_pool = HipTensor.register_op("min_pool", _pool2d("min_pool", 1, HipTensor.min_pool), overwrite=True)
 
 
 """ Fused forms used by nn / optim / loss (SURVEY.md §8f row 1) """

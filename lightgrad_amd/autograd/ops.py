@@ -148,6 +148,17 @@ class pool(Function):
         return g
 
 
+@_register("conv2d")
+def conv2d(x, w, bias=None, stride=1, pad: int = 0):
+    """ nn.Conv2d as one op: x (N, C, H, W) zero-padded by `pad` on both spatial axes, cross-correlated with w (O, C, KH, KW) at
+    `stride` (an int or (sh, sw)), plus a bias of shape (1, O, 1, 1) or (O,).  The composite of pad, conv and add; a backend may
+    overwrite it with a kernel (hip/ops.py) """
+    y = (x.pad(pad) if pad else x).conv(w, strides=stride)
+    if bias is None:
+        return y
+    return y + (bias if len(bias.shape) == 4 else bias.reshape(1, -1, 1, 1))
+
+
 @_register("max_pool")
 def max_pool(t, kernel: tuple = (2, 2)):
     return t.pool(kernel=kernel).max(axis=0, keepdims=False)

@@ -177,9 +177,7 @@ class Conv2d(Module):
         self.p = kernelsize // 2 if pad is None else pad
 
     def forward(self, x):
-        padded = x.pad(self.p) if self.p > 0 else x
-        y = padded.conv(self.w, strides=self.s)
-        return y if self.b is None else y + self.b
+        return x.conv2d(self.w, self.b, stride=self.s, pad=self.p)
 
 
 class LayerNorm(Module):
