@@ -20,6 +20,8 @@ Differences from the reference, on purpose:
                                                        # capture with --graph), cross-entropy over the masked positions only
     python examples/bert.py --mlm --accuracy [--graph] # also counts the masked tokens predicted right (light.metrics.accuracy), on
                                                        # the device, over every step and replay: one host read at the end
+    python examples/bert.py --mlm --bf16-decoder       # the decoder onto the vocabulary (forward, dx, dW) on the bf16 matrix cores:
+                                                       # config key `decoder_precision="bf16"`; tensors stay float32
 """
 import math
 import os
@@ -216,7 +218,9 @@ class BertModel(nn.Module):
 
 
 class BertForMaskedLM(nn.Module):
-    def __init__(self, hidden_size, vocab_size, **config):
+    def __init__(self, hidden_size, vocab_size, decoder_precision=None, **config):
+        """`decoder_precision="bf16"`: the product onto the vocabulary and its two gradient products round their operands to
+        bfloat16 on the way into the matrix cores (nn.Linear's `precision`); nothing else in the model changes"""
         nn.Module.__init__(self)
         self.bert = BertModel(hidden_size=hidden_size, vocab_size=vocab_size, **config)
         self.cls = nn.Module()
@@ -224,7 +228,7 @@ class BertForMaskedLM(nn.Module):
         self.cls.predictions.transform = nn.Module()
         self.cls.predictions.transform.dense = nn.Linear(hidden_size, hidden_size)
         self.cls.predictions.transform.LayerNorm = nn.LayerNorm(hidden_size)
-        self.cls.predictions.decoder = nn.Linear(hidden_size, vocab_size, bias=False)
+        self.cls.predictions.decoder = nn.Linear(hidden_size, vocab_size, bias=False, precision=decoder_precision)
         self.cls.predictions.bias = light.zeros(vocab_size)
 
     def forward(self, input_ids, attention_mask=None, token_type_ids=None, masked_positions=None):
@@ -275,7 +279,8 @@ if __name__ == "__main__":
     batch = int(sys.argv[sys.argv.index("--batch") + 1]) if "--batch" in sys.argv else 8
     to_device = (lambda t: t) if cpu else (lambda t: t.hip())
     np.random.seed(0)
-    model = BertForMaskedLM(**TINY).map_parameters(to_device)
+    config = dict(TINY, decoder_precision="bf16" if "--bf16-decoder" in sys.argv else None)
+    model = BertForMaskedLM(**config).map_parameters(to_device)
     ids = to_device(light.from_numpy(np.random.randint(0, TINY["vocab_size"], (batch, 128)).astype(np.int32), requires_grad=False))
     total = None
     if "--accuracy" in sys.argv:

@@ -278,6 +278,22 @@ int lg_gemm_f32(int transA, int transB, int64_t M, int64_t N, int64_t K,
                 float* C, int64_t ldc, int64_t strideC,
                 int64_t batch, int accumulate);
 
+/* The same product with both operands rounded to bfloat16 (nearest, ties to even; NaN, +-Inf and the sign of zero kept, a
+ * finite value beyond the largest bfloat16 becomes +-Inf) on their way into the matrix cores: C (+)= r(op(A)) @ r(op(B)) [+ bias].
+ * Products of two bfloat16 values are exact in fp32; the sums are formed in fp32 on v_mfma_f32_32x32x16_bf16.  Operands,
+ * result and bias (N values, may be NULL) stay fp32 in memory; layouts and leading dimensions as for lg_gemm_f32, one matrix
+ * product, all four transA x transB layouts consumed in place (the same 16-byte fetches, so the same 12 readable bytes behind
+ * an operand).  bias is added after the fp32 sum; bias together with accumulate is LG_EINVAL.  M or N of 0: nothing happens;
+ * K of 0: C = 0 (+ bias) unless accumulate.  Few output tiles over a long K are cut along K and folded in ascending order by a
+ * second kernel: the same bits from run to run, no atomics.  Subnormal fp32 inputs are unspecified. */
+int lg_gemm_bf16_f32(int transA, int transB, int64_t M, int64_t N, int64_t K,
+                     const float* A, int64_t lda, const float* B, int64_t ldb,
+                     float* C, int64_t ldc, const float* bias, int accumulate);
+
+/* dst[i] = r(src[i]) for n dense fp32 values: rounded to bfloat16 exactly as lg_gemm_bf16_f32 rounds its operands, kept as fp32
+ * (the low 16 bits zero).  dst may be src. */
+int lg_bf16_round_f32(const float* src, float* dst, int64_t n);
+
 /* Same product with a bias row added in the epilogue: C[b][m][n] = (op(A[b]) @ op(B[b]))[m][n] + bias[n]
  * (bias may be NULL).  The sum is rounded to fp32 before the bias is added, exactly like the separate
  * `x @ W.T + b` of nn.Linear (nn.py:96).  Fuses one elementwise pass per Linear layer. */

@@ -7,3 +7,9 @@ empty, zeros, ones = Tensor.empty, Tensor.zeros, Tensor.ones
 uniform, xavier = Tensor.uniform, Tensor.xavier
 from_numpy = Tensor.from_numpy
 manual_seed = random.manual_seed
+
+
+def bf16_round(t):
+    """every value of `t` rounded to bfloat16 (nearest, ties to even) and kept as float32: the rounding `dot_bf16` /
+    `linear_bf16` apply to their operands (autograd/cpu/ops.py: bf16_round_array).  A tensor of t's backend, no gradient."""
+    return t.bf16_round()

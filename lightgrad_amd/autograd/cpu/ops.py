@@ -161,6 +161,79 @@ for _name, _value, _gradients, _keep, _extra in _FORMULAS:
     globals()[_name] = _formula_op(_name, _value, _gradients, _keep, cite="reference cpu/ops.py, op `%s`" % _name, **_extra)
 
 
+""" Products with bfloat16 operands (not ops of the reference): fp32 tensors, both operands of a product rounded to bfloat16
+on their way into it, the sum formed in fp32 - what `lg_gemm_bf16_f32` computes on the bf16 matrix cores (DESIGN.md) """
+
+
+def bf16_round_array(x):
+    """r(x): every value rounded to bfloat16 (8-bit significand; nearest, ties to even) and kept in x's own float dtype.  NaN
+    stays NaN, +-Inf and the sign of zero are kept, a finite value beyond the largest bfloat16 becomes +-Inf.  THE definition
+    of the rounding for both backends; subnormal fp32 inputs are unspecified (the matrix cores may flush them).  A float64
+    array (the float64 run of a float32 tape) is rounded to float32 first and comes back as float64."""
+    x = np.asarray(x)
+    f = np.ascontiguousarray(x, dtype=np.float32)
+    u = f.view(np.uint32)
+    r = ((u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) & np.uint32(0xFFFF0000)).view(np.float32)
+    return np.where(np.isnan(f), f, r).astype(x.dtype if x.dtype.kind == "f" else np.float32)
+
+
+def _require_bf16_operands(name, *operands):
+    for t in operands:
+        if t is not None and t.dtype != np.float32 and not (t.dtype == np.float64 and CpuTensor.default_dtype == np.float64):
+            raise TypeError("%s is float32-only (got %s)" % (name, t.dtype))
+
+
+def _require_matrix_ranks(name, a, b):
+    if a.ndim < 2 or b.ndim != 2:
+        raise ValueError("%s: (M, K) @ (K, N) or (..., M, K) @ (K, N) only (got %s and %s)" % (name, a.shape, b.shape))
+
+
+@_op()
+class dot_bf16(Function):
+    """ a.dot_bf16(b) = r(a) @ r(b), r = `bf16_round_array`: (M, K) @ (K, N), or (..., M, K) @ (K, N) as one tall product.
+    backward: dA = r(g) @ r(b)^T, dB = r(a)^T @ r(g) - every operand, the gradient included, is rounded again. """
+    def forward(ctx, a, b):
+        _require_bf16_operands("dot_bf16", a, b)
+        _require_matrix_ranks("dot_bf16", a, b)
+        ra, rb = bf16_round_array(a), bf16_round_array(b)
+        ctx.save_for_backward(ra, rb)
+        return ra @ rb
+
+    def backward(ctx, out_grad):
+        ra, rb = ctx.get_saved_tensors()
+        rg = bf16_round_array(out_grad)
+        return rg @ rb.T, ra.reshape(-1, ra.shape[-1]).T @ rg.reshape(-1, rg.shape[-1])
+
+
+@_op()
+class linear_bf16(Function):
+    """ x.linear_bf16(weight, bias=None) = r(x) @ r(weight)^T + bias, weight as nn.Linear holds it ((out, in)); the sum is
+    rounded to fp32 before the bias is added.  backward: dx = r(g) @ r(W), dW = r(g)^T @ r(x), db = column sums of the
+    (unrounded) g. """
+    def forward(ctx, x, weight, bias=None):
+        _require_bf16_operands("linear_bf16", x, weight, bias)
+        _require_matrix_ranks("linear_bf16", x, weight)
+        rx, rw = bf16_round_array(x), bf16_round_array(weight)
+        ctx.save_for_backward(rx, rw, bias is not None)
+        y = rx @ rw.T
+        return y if bias is None else y + bias
+
+    def backward(ctx, out_grad):
+        rx, rw, has_bias = ctx.get_saved_tensors()
+        g2 = out_grad.reshape(-1, rw.shape[0])
+        rg = bf16_round_array(g2)
+        dx, dw = (rg @ rw).reshape(rx.shape), rg.T @ rx.reshape(-1, rx.shape[-1])
+        return (dx, dw, g2.sum(axis=0)) if has_bias else (dx, dw)
+
+
+def _bf16_round(t):
+    """ t.bf16_round() (also `lightgrad_amd.bf16_round(t)`): r(t) as a new tensor, a constant of the tape (no gradient) """
+    return CpuTensor.from_numpy(bf16_round_array(t.data), requires_grad=False)
+
+
+CpuTensor.bf16_round = _bf16_round
+
+
 """ In-place operators and fill: no backward, the result IS the input's storage (cpu/ops.py:120-153) """
 
 

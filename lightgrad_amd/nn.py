@@ -132,14 +132,23 @@ class ModuleList(Module, list):
 class Linear(Module):
     """y = x @ W^T + b with W of shape (out, in), both drawn by `xavier` (nn.py:90-96)"""
 
-    def __init__(self, in_feats: int, out_feats: int, bias: bool = True):
+    def __init__(self, in_feats: int, out_feats: int, bias: bool = True, precision: str = None):
+        """`precision` (extension of the reference): None = fp32 products; "bf16" = both operands of every product of this
+        layer, forward and backward, rounded to bfloat16 on their way into the matrix cores, sums in fp32 (`linear_bf16`).
+        Parameters, activations and gradients stay float32 either way."""
         Module.__init__(self)
+        if precision not in (None, "bf16"):
+            raise ValueError("Linear: precision must be None or 'bf16' (got %r)" % (precision,))
+        self.precision = precision
         self.weight = Tensor.xavier((out_feats, in_feats))
         self.bias = Tensor.xavier((out_feats,)) if bias else None
 
     def forward(self, x, residual=None):
         """`residual` (extension of the reference's forward(x)): a tensor of the output's shape added to the result, as in
         `dense(h) + h_in` of a transformer block - a backend with a fused op adds it where the product is made"""
+        if self.precision == "bf16":
+            y = x.linear_bf16(self.weight) if self.bias is None else x.linear_bf16(self.weight, self.bias)
+            return y if residual is None else y + residual
         fused = getattr(x, "linear", None)
         if fused is not None:        # one tape node, bias (and residual) added in the GEMM epilogue (HipTensor)
             if residual is not None:
