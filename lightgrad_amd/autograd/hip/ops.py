@@ -2319,309 +2319,10 @@ def _scaled_softmax(t, scale, axis=-1):
 HipTensor.scaled_softmax = _scaled_softmax
 
 
-def _token_rows(t):
-    """(tensor, row pitch, batch pitch) of a (batch, positions, width) tensor whose rows the attention kernels can address as
-    they lie: width contiguous, pitches multiples of 4, 16-byte aligned; anything else is copied once"""
-    st, sh = t._strides, t._shape
-    if st[2] != 1 or st[1] % 4 or st[0] % 4 or st[1] < sh[2] or t._byte_offset % 16:
-        t = t.contiguous()
-        st = t._strides
-    return t, st[1], st[0]
-
-
-def _attention_dropout(dropout):
-    """the validated probability of an attention form's `dropout=`; 0.0 means the launches without it"""
-    return _random.check_probability(dropout)
-
-
 def _dropout_base():
     """the one word of device memory the forward launch writes the call's number to and the backward reads it from"""
     _random._apply_pending_hip_seed()
     return HipTensor.empty((1,), dtype=np.uint64, requires_grad=False)
-
-
-def attention_supported(q, heads):
-    """does `q.attention(k, v, heads, scale)` exist for this shape? (b, s, heads * d) with d = 32 or 64 and s = 32 .. 128 in 32s"""
-    return len(q._shape) == 3 and q._dtype == _F32 and q._shape[2] % heads == 0 and \
-        bool(_l.lib().lg_attention_supported(q._shape[1], q._shape[2] // heads))
-
-
-@HipTensor.register_op()
-class attention(Function):
-    """ softmax((q k^T) * scale) v per head, forward and backward in one launch each (csrc/attention.hip); q, k, v are the
-    (batch, positions, heads * d) outputs of the three projections as they stand - the head split of examples/bert.py:78-80
-    happens in the kernels' addressing.  The probabilities (batch, heads, s, s) the reference model returns next to the context
-    (bert.py:88) are on the result as `.attention_probs`, outside the tape (the composite form differentiates through them).
-    dropout=p > 0: `probs.dropout(p)` between the softmax and the context inside the same two launches - the mask the composite
-    draws (one call of the stream, lightgrad_amd/random.py); `.attention_probs` stays undropped """
-    def forward(ctx, q, k, v, heads=1, scale=1.0, dropout=0.0):
-        dropout = _attention_dropout(dropout)
-        _require_f32(q, k, v)
-        assert q._shape == k._shape == v._shape and attention_supported(q, heads), \
-            "attention: unsupported shapes %s / %s / %s with %d heads" % (q._shape, k._shape, v._shape, heads)
-        b, s, width = q._shape
-        d = width // heads
-        (q, ldq, sbq), (k, ldk, sbk), (v, ldv, sbv) = _token_rows(q), _token_rows(k), _token_rows(v)
-        out = HipTensor.empty((b, s, width))
-        probs = HipTensor.empty((b, heads, s, s), requires_grad=False)
-        base = None
-        if dropout > 0.0:
-            base = _dropout_base()
-            _l.check(_l.lib().lg_attention_dropout_fwd_f32(q.ptr, ldq, sbq, k.ptr, ldk, sbk, v.ptr, ldv, sbv, out.ptr, width, s * width,
-                                                           probs.ptr, b, heads, s, d, float(scale), None, 0, dropout, base.ptr))
-        else:
-            _l.check(_l.lib().lg_attention_fwd_f32(q.ptr, ldq, sbq, k.ptr, ldk, sbk, v.ptr, ldv, sbv, out.ptr, width, s * width,
-                                                   probs.ptr, b, heads, s, d, float(scale)))
-        ctx.save_for_backward(q, k, v, probs, heads, float(scale), dropout, base)
-        out.attention_probs = probs
-        return out
-
-    def backward(ctx, out_grad):
-        q, k, v, probs, heads, scale, dropout, base = ctx.get_saved_tensors()
-        b, s, width = q._shape
-        (q, ldq, sbq), (k, ldk, sbk), (v, ldv, sbv), (g, ldg, sbg) = _token_rows(q), _token_rows(k), _token_rows(v), _token_rows(out_grad)
-        dq, dk, dv = HipTensor.empty((b, s, width)), HipTensor.empty((b, s, width)), HipTensor.empty((b, s, width))
-        args = (q.ptr, ldq, sbq, k.ptr, ldk, sbk, v.ptr, ldv, sbv, g.ptr, ldg, sbg, probs.ptr,
-                dq.ptr, width, s * width, dk.ptr, width, s * width, dv.ptr, width, s * width, b, heads, s, width // heads, scale)
-        if base is not None:
-            _l.check(_l.lib().lg_attention_dropout_bwd_f32(*args, dropout, base.ptr))
-        else:
-            _l.check(_l.lib().lg_attention_bwd_f32(*args))
-        return dq, dk, dv
-
-
-HipTensor.attention_supported = attention_supported
-
-
-def masked_attention_supported(q, heads):
-    """does `q.masked_attention(k, v, heads, scale, mask)` exist for this shape? (b, s, heads * d) with d = 32 or 64 and ANY s in 1 .. 128"""
-    return len(q._shape) == 3 and q._dtype == _F32 and q._shape[2] % heads == 0 and q._shape[0] > 0 and \
-        bool(_l.lib().lg_attention_masked_supported(q._shape[1], q._shape[2] // heads))
-
-
-def _key_mask(mask, b, s, what):
-    """(tensor kept alive, address, batch pitch) of a key-padding mask as lg_attention_masked_fwd_f32 reads it: float32, (b, s) or
-    (1, s) - one row for the whole batch, pitch 0 -, rows contiguous (anything else is copied once), no gradient"""
-    if mask is None:
-        return None, None, 0
-    assert isinstance(mask, HipTensor) and mask._dtype == _F32, "%s: the mask must be a float32 HipTensor, got %s" % (
-        what, mask._dtype if isinstance(mask, HipTensor) else type(mask).__name__)
-    assert not mask.requires_grad, "%s: the mask takes no gradient (requires_grad must be False)" % what
-    assert mask._shape in ((b, s), (1, s)), "%s: mask of shape %s, expected (%d, %d) or (1, %d)" % (what, mask._shape, b, s, s)
-    if (s > 1 and mask._strides[1] != 1) or (mask._shape[0] > 1 and mask._strides[0] < s):
-        mask = mask.contiguous()
-    return mask, mask.ptr, (0 if mask._shape[0] == 1 else mask._strides[0])
-
-
-@HipTensor.register_op()
-class masked_attention(Function):
-    """ `attention` for what a tokenizer produces: any s in 1 .. 128 and a key-padding mask (reference examples/bert.py:80-83:
-    `scores + (1.0 - mask) * -10000.0` before the softmax), forward and backward in one launch each (the TAIL kernels of
-    csrc/attention.hip).  mask: float32 (b, s) or (1, s), no gradient, None for none.  A mask of ones gives the bits of `attention`.
-    `.attention_probs` (b, heads, s, s) as there, outside the tape. """
-    def forward(ctx, q, k, v, heads=1, scale=1.0, mask=None, dropout=0.0):
-        dropout = _attention_dropout(dropout)           # > 0: `probs.dropout(p)` inside the two launches, as for `attention`
-        _require_f32(q, k, v)
-        assert q._shape == k._shape == v._shape and masked_attention_supported(q, heads), \
-            "masked_attention: unsupported shapes %s / %s / %s with %d heads" % (q._shape, k._shape, v._shape, heads)
-        b, s, width = q._shape
-        d = width // heads
-        mask, mptr, sbm = _key_mask(mask, b, s, "masked_attention")
-        (q, ldq, sbq), (k, ldk, sbk), (v, ldv, sbv) = _token_rows(q), _token_rows(k), _token_rows(v)
-        out = HipTensor.empty((b, s, width))
-        probs = HipTensor.empty((b, heads, s, s), requires_grad=False)
-        base, fwd, extra = None, _l.lib().lg_attention_masked_fwd_f32, ()
-        if dropout > 0.0:
-            base = _dropout_base()
-            fwd, extra = _l.lib().lg_attention_dropout_fwd_f32, (dropout, base.ptr)
-        _l.check(fwd(q.ptr, ldq, sbq, k.ptr, ldk, sbk, v.ptr, ldv, sbv, out.ptr, width, s * width,
-                     probs.ptr, b, heads, s, d, float(scale), mptr, sbm, *extra))
-        ctx.save_for_backward(q, k, v, probs, heads, float(scale), dropout, base)
-        out.attention_probs = probs
-        return out
-
-    def backward(ctx, out_grad):
-        q, k, v, probs, heads, scale, dropout, base = ctx.get_saved_tensors()
-        b, s, width = q._shape
-        (q, ldq, sbq), (k, ldk, sbk), (v, ldv, sbv), (g, ldg, sbg) = _token_rows(q), _token_rows(k), _token_rows(v), _token_rows(out_grad)
-        dq, dk, dv = HipTensor.empty((b, s, width)), HipTensor.empty((b, s, width)), HipTensor.empty((b, s, width))
-        bwd, extra = (_l.lib().lg_attention_masked_bwd_f32, ()) if base is None else (_l.lib().lg_attention_dropout_bwd_f32, (dropout, base.ptr))
-        _l.check(bwd(q.ptr, ldq, sbq, k.ptr, ldk, sbk, v.ptr, ldv, sbv, g.ptr, ldg, sbg, probs.ptr,
-                     dq.ptr, width, s * width, dk.ptr, width, s * width, dv.ptr, width, s * width,
-                     b, heads, s, width // heads, scale, *extra))
-        return dq, dk, dv
-
-
-HipTensor.masked_attention_supported = masked_attention_supported
-
-
-def long_attention_supported(q, heads):
-    """does `q.long_attention(k, v, heads, scale, mask)` exist for this shape? (b, s, heads * d) with d = 32 or 64 and any s in 129 .. 512"""
-    return len(q._shape) == 3 and q._dtype == _F32 and q._shape[2] % heads == 0 and q._shape[0] > 0 and \
-        bool(_l.lib().lg_attention_long_supported(q._shape[1], q._shape[2] // heads))
-
-
-@HipTensor.register_op()
-class long_attention(Function):
-    """ `masked_attention` for the lengths one CU's LDS does not hold a (batch, head) pair of: any s in 129 .. 512, with or without
-    a key-padding mask, forward and backward still in one launch each (csrc/attention_long.hip: K, V, Q and dO stream through LDS
-    in chunks).  mask: float32 (b, s) or (1, s), no gradient, None for none (the bits of a mask of ones).
-    `.attention_probs` (b, heads, s, s) as there, outside the tape. """
-    def forward(ctx, q, k, v, heads=1, scale=1.0, mask=None, dropout=0.0):
-        dropout = _attention_dropout(dropout)           # > 0: `probs.dropout(p)` inside the two launches, as for `attention`
-        _require_f32(q, k, v)
-        assert q._shape == k._shape == v._shape and long_attention_supported(q, heads), \
-            "long_attention: unsupported shapes %s / %s / %s with %d heads" % (q._shape, k._shape, v._shape, heads)
-        b, s, width = q._shape
-        d = width // heads
-        mask, mptr, sbm = _key_mask(mask, b, s, "long_attention")
-        (q, ldq, sbq), (k, ldk, sbk), (v, ldv, sbv) = _token_rows(q), _token_rows(k), _token_rows(v)
-        out = HipTensor.empty((b, s, width))
-        probs = HipTensor.empty((b, heads, s, s), requires_grad=False)
-        base, fwd, extra = None, _l.lib().lg_attention_long_fwd_f32, ()
-        if dropout > 0.0:
-            base = _dropout_base()
-            fwd, extra = _l.lib().lg_attention_dropout_fwd_f32, (dropout, base.ptr)
-        _l.check(fwd(q.ptr, ldq, sbq, k.ptr, ldk, sbk, v.ptr, ldv, sbv, out.ptr, width, s * width,
-                     probs.ptr, b, heads, s, d, float(scale), mptr, sbm, *extra))
-        ctx.save_for_backward(q, k, v, probs, heads, float(scale), dropout, base)
-        out.attention_probs = probs
-        return out
-
-    def backward(ctx, out_grad):
-        q, k, v, probs, heads, scale, dropout, base = ctx.get_saved_tensors()
-        b, s, width = q._shape
-        (q, ldq, sbq), (k, ldk, sbk), (v, ldv, sbv), (g, ldg, sbg) = _token_rows(q), _token_rows(k), _token_rows(v), _token_rows(out_grad)
-        dq, dk, dv = HipTensor.empty((b, s, width)), HipTensor.empty((b, s, width)), HipTensor.empty((b, s, width))
-        bwd, extra = (_l.lib().lg_attention_long_bwd_f32, ()) if base is None else (_l.lib().lg_attention_dropout_bwd_f32, (dropout, base.ptr))
-        _l.check(bwd(q.ptr, ldq, sbq, k.ptr, ldk, sbk, v.ptr, ldv, sbv, g.ptr, ldg, sbg, probs.ptr,
-                     dq.ptr, width, s * width, dk.ptr, width, s * width, dv.ptr, width, s * width,
-                     b, heads, s, width // heads, scale, *extra))
-        return dq, dk, dv
-
-
-HipTensor.long_attention_supported = long_attention_supported
-
-
-def self_attention_supported(x, wq, heads, masked=False, long=False):
-    """does `x.self_attention(wq, bq, wk, bk, wv, bv, heads, scale)` exist for these shapes?  (b, s, hidden) input, three
-    (width, hidden) weights with width = heads * d, d = 32 or 64, width a multiple of 64, s = 32 .. 128 in 32s; masked=True:
-    the same question for the form with `mask=` or a length that is no multiple of 32 - any s in 1 .. 128; long=True: the
-    same question for the lengths beyond - any s in 129 .. 512, with or without a mask"""
-    fits = _l.lib().lg_attention_long_supported if long else \
-        _l.lib().lg_attention_masked_supported if masked else _l.lib().lg_attention_supported
-    return (len(x._shape) == 3 and x._dtype == _F32 and len(wq._shape) == 2 and wq._shape[1] == x._shape[2] and wq._shape[0] % heads == 0
-            and wq._shape[0] % 64 == 0 and x._shape[2] % 4 == 0 and x.numel() > 0
-            and bool(fits(x._shape[1], wq._shape[0] // heads)))
-
-
-def _ptr3(a, b, c):
-    return (ctypes.c_void_p * 3)(a, b, c)
-
-
-@HipTensor.register_op()
-class self_attention(Function):
-    """ the query / key / value projections and the attention over them as ONE tape node (reference examples/bert.py:78-88:
-    three nn.Linear, scores, scaling, softmax, context): the three projections are one launch (lg_gemm_multi3_f32 - the weights
-    stay the separately allocated parameters they are) into one (b, s, 3 * width) buffer that the attention kernel reads in
-    place; backward: the attention kernel writes dq | dk | dv into one buffer of that shape, the input gradient is ONE product
-    whose K runs through the three weights (lg_gemm_kseg3_f32, added to a gradient the input already holds in its epilogue),
-    the weight / bias gradients take the routes of `linear`.  `.attention_probs` as for `attention`.  With a key-padding
-    `mask` (as for `masked_attention`) or a length that is no multiple of 32 the attention launches are the masked / tail ones,
-    beyond 128 positions (up to 512, mask or none) the long ones of csrc/attention_long.hip; everything else about the node is
-    the same. """
-    def forward(ctx, x, wq, bq, wk, bk, wv, bv, heads=1, scale=1.0, mask=None, dropout=0.0):
-        dropout = _attention_dropout(dropout)           # > 0: `probs.dropout(p)` inside the attention launches, as for `attention`
-        _require_f32(x, wq, bq, wk, bk, wv, bv)
-        long = len(x._shape) == 3 and x._shape[1] > 128
-        tail = mask is not None or (len(x._shape) == 3 and x._shape[1] % 32 != 0)
-        assert self_attention_supported(x, wq, heads, masked=tail, long=long) and wq._shape == wk._shape == wv._shape and bq._shape == bk._shape == bv._shape == (wq._shape[0],), \
-            "self_attention: unsupported shapes %s with weights %s / %s / %s and %d heads" % (x._shape, wq._shape, wk._shape, wv._shape, heads)
-        b, s, hidden = x._shape
-        width = wq._shape[0]
-        x = x.contiguous()
-        ws, bs = [w.contiguous() for w in (wq, wk, wv)], [t.contiguous() for t in (bq, bk, bv)]
-        qkv = HipTensor.empty((b, s, 3 * width), requires_grad=False)
-        base = qkv.ptr
-        _l.check(_l.lib().lg_gemm_multi3_f32(0, 1, b * s, width, hidden, x.ptr, hidden, _ptr3(*(w.ptr for w in ws)), hidden,
-                                             _ptr3(base, base + 4 * width, base + 8 * width), 3 * width, _ptr3(*(t.ptr for t in bs))))
-        out = HipTensor.empty((b, s, width))
-        probs = HipTensor.empty((b, heads, s, s), requires_grad=False)
-        ld, sb = 3 * width, s * 3 * width
-        drop_base = None
-        if dropout > 0.0:
-            mask, mptr, sbm = _key_mask(mask, b, s, "self_attention")
-            drop_base = _dropout_base()
-            _l.check(_l.lib().lg_attention_dropout_fwd_f32(base, ld, sb, base + 4 * width, ld, sb, base + 8 * width, ld, sb, out.ptr, width,
-                                                           s * width, probs.ptr, b, heads, s, width // heads, float(scale), mptr, sbm,
-                                                           dropout, drop_base.ptr))
-        elif long or tail:
-            mask, mptr, sbm = _key_mask(mask, b, s, "self_attention")
-            attention_fwd = _l.lib().lg_attention_long_fwd_f32 if long else _l.lib().lg_attention_masked_fwd_f32
-            _l.check(attention_fwd(base, ld, sb, base + 4 * width, ld, sb, base + 8 * width, ld, sb, out.ptr, width,
-                                   s * width, probs.ptr, b, heads, s, width // heads, float(scale), mptr, sbm))
-        else:
-            _l.check(_l.lib().lg_attention_fwd_f32(base, ld, sb, base + 4 * width, ld, sb, base + 8 * width, ld, sb, out.ptr, width, s * width,
-                                                   probs.ptr, b, heads, s, width // heads, float(scale)))
-        ctx.save_for_backward(x, qkv, probs, heads, float(scale), tail, long, dropout, drop_base)
-        out.attention_probs = probs
-        return out
-
-    def backward(ctx, out_grad):
-        x, qkv, probs, heads, scale, tail, long, dropout, drop_base = ctx.get_saved_tensors()
-        x_in = ctx._parents[0]
-        params = ctx._parents[1:7]
-        b, s, hidden = x._shape
-        width = qkv._shape[2] // 3
-        g, ldg, sbg = _token_rows(out_grad)
-        dqkv = HipTensor.empty((b, s, 3 * width), requires_grad=False)
-        base, dbase = qkv.ptr, dqkv.ptr
-        ld, sb = 3 * width, s * 3 * width
-        attention_bwd = _l.lib().lg_attention_long_bwd_f32 if long else \
-            _l.lib().lg_attention_masked_bwd_f32 if tail else _l.lib().lg_attention_bwd_f32
-        extra = ()
-        if drop_base is not None:
-            attention_bwd, extra = _l.lib().lg_attention_dropout_bwd_f32, (dropout, drop_base.ptr)
-        _l.check(attention_bwd(base, ld, sb, base + 4 * width, ld, sb, base + 8 * width, ld, sb, g.ptr, ldg, sbg, probs.ptr,
-                               dbase, ld, sb, dbase + 4 * width, ld, sb, dbase + 8 * width, ld, sb,
-                               b, heads, s, width // heads, scale, *extra))
-        x2 = x.reshape(-1, hidden)
-        grads = []
-        for i in range(3):
-            weight, bias = params[2 * i], params[2 * i + 1]
-            gi = HipTensor(dqkv.data, (b * s, width), (3 * width, 1), dqkv._offset + i * width, _F32, requires_grad=False)
-            want_db = bias.requires_grad
-            acc_w = weight._grad_accumulator() if weight.requires_grad else None
-            acc_w = acc_w if (acc_w is not None and acc_w.is_contiguous()) else None
-            acc_b = bias._grad_accumulator() if want_db else None
-            acc_b = acc_b if (acc_b is not None and acc_b.is_contiguous()) else None
-            if acc_w is not None and (not want_db or acc_b is not None) and GradGroup.usable_for(weight, bias):
-                with GradGroup.issue(reads=(gi, x2), writes=(acc_w, acc_b)):
-                    grads += list(linear._weight_products(x2, weight, bias, want_db, gi, acc_w, acc_b))
-            else:
-                grads += list(linear._weight_products(x2, weight, bias, want_db, gi, acc_w, acc_b))
-        dx = None
-        if x_in.requires_grad:
-            ws = [params[0].contiguous(), params[2].contiguous(), params[4].contiguous()]
-            wptrs = _ptr3(*(w.ptr for w in ws))
-            have = x_in._grad if (x_in._ctx is not None and x_in._view_of_leaf is None) else None
-            if (have is not None and have.__class__ is HipTensor and have._shape == x_in._shape and have._dtype == _F32 and have.is_contiguous()):
-                # the input already holds a contribution (the residual branch): added in this product's epilogue
-                if x_in._grad_shared:
-                    new = HipTensor.empty(x_in._shape, requires_grad=False)
-                    _l.check(_l.lib().lg_gemm_kseg3_f32(0, 0, b * s, hidden, width, dbase, 3 * width, wptrs, hidden, new.ptr, hidden, 0,
-                                                        have.ptr, hidden))
-                    x_in._grad, x_in._grad_shared = new, False
-                else:
-                    flush_lazy_readers(have)
-                    _l.check(_l.lib().lg_gemm_kseg3_f32(0, 0, b * s, hidden, width, dbase, 3 * width, wptrs, hidden, have.ptr, hidden, 1, None, 0))
-            else:
-                dx = HipTensor.empty(x_in._shape, requires_grad=False)
-                _l.check(_l.lib().lg_gemm_kseg3_f32(0, 0, b * s, hidden, width, dbase, 3 * width, wptrs, hidden, dx.ptr, hidden, 0, None, 0))
-        return (dx,) + tuple(grads)
-
-
-HipTensor.self_attention_supported = self_attention_supported
 
 
 @HipTensor.register_op()

@@ -34,91 +34,21 @@
 // the softmax takes keys >= S out by selection, global rows >= S are neither read nor written, and the probabilities
 // (row pitch S, not 16-byte aligned unless S % 4 == 0) go out and come in as scalars.  The TAIL = false instantiations are
 // the kernels as they were.
-#include "common.h"
-#include "mfma_lds.h"
-#include "rng_common.h"
-#include <cmath>
-#include <type_traits>
+//
+// Layout.  attention_common.h has what this file and attention_long.hip share: the argument structs, the small device helpers, and
+// the host interface.  This file has the short kernels (attn_fwd, attn_bwd: <D, TAIL, DROP>), their launchers, and the ONE host
+// path of all eight lg_attention_*_f32 launch entries - attn_forward / attn_backward: the checks in one order, the selection
+// of the kernels (pick_form), the `shift` slab allocated and freed in one place - plus the plain, masked and dropout entries,
+// which only fill a call struct and name their family.  attention_long.hip adds the long kernels, their launchers and entries.
+#include "attention_common.h"
 
 namespace lg {
-
-#ifdef LG_GEMM_TIMELINE
-// experiments build only (make timeline; tools/attn_timeline.py): 16 timestamps of the 100 MHz wall clock per workgroup
-#define LG_ATL(slot) do { if (a.tl && threadIdx.x == 0) a.tl[size_t((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 16 + (slot)] = wall_clock64(); } while (0)
-#define LG_ATL_FIELD unsigned long long* tl;
-#else
-#define LG_ATL(slot) do { } while (0)
-#define LG_ATL_FIELD
-#endif
-
-struct AttnArgs {
-    LG_ATL_FIELD
-    const float *q, *k, *v;          // element (b, s, head, d) of X at X + b * sbX + s * ldX + head * D + d
-    int64_t ldq, sbq, ldk, sbk, ldv, sbv;
-    float* o;                        // context, same addressing
-    int64_t ldo, sbo;
-    float* p;                        // probabilities (batch, heads, S, S), dense
-    int S, heads;
-    float scale;
-};
-
-struct AttnTailArgs : AttnArgs {
-    const float* mask;               // key-padding mask, element (b, j) at mask + b * sbm + j (sbm = 0: one row for the batch); NULL = none
-    int64_t sbm;
-};
-
-// DROP instantiations: the tail arguments (mask NULL for none) and the call of the random stream
-struct AttnDropArgs : AttnTailArgs {
-    AttnDrop drop;
-};
-
-// the two 64-bit words of a call in LDS (DROP instantiations only: 16 bytes of static LDS next to the dynamic tiles)
-template <bool DROP>
-__device__ __forceinline__ unsigned long long* rng_call_slot() {
-    if constexpr (DROP) {
-        __shared__ unsigned long long call[2];
-        return call;
-    } else {
-        return nullptr;
-    }
-}
-
-// linear index of this workgroup over the 3-D grid / workgroups of the launch: what the tickets of the random stream count
-__device__ __forceinline__ int grid_linear_block() { return int((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x); }
-__device__ __forceinline__ int grid_blocks() { return int(gridDim.x * gridDim.y * gridDim.z); }
-
-// the float4 of probabilities at flat element index i of the dense (batch, heads, S, S) tensor as the context's MFMA operand:
-// P * s where the stream keeps the element, +0.0 where it drops it
-template <bool ALIGNED>
-__device__ __forceinline__ af32x4 drop4(af32x4 t, int64_t i, unsigned long long seed, unsigned long long base, uint32_t threshold, float s) {
-    uint32_t w[4];
-    rng_words4<ALIGNED>(i, seed, base, w);
-    return af32x4{rng_keep(t[0], w[0], threshold, s), rng_keep(t[1], w[1], threshold, s), rng_keep(t[2], w[2], threshold, s),
-                  rng_keep(t[3], w[3], threshold, s)};
-}
-
-__host__ __device__ constexpr int round32(int S) { return (S + 31) & ~31; }
 
 template <int D>
 constexpr int attn_fwd_lds_floats(int S) { return 32 * (D + 4) + S * (D + 4) + S * (D + 8) + 32 * (S + 4) + 3 * 1024; }
 // TAIL: the same layout over Sp rows and the per-key bias behind it
 template <int D>
 constexpr int attn_fwd_tail_lds_floats(int S) { return attn_fwd_lds_floats<D>(round32(S)) + 128; }
-
-// store_rows that also clears rows [rows, padded): an MFMA operand row past the sequence must be zero, not stale LDS
-template <int D, int N>
-__device__ __forceinline__ void store_rows_padded(const af32x4 (&v)[N], float* dst, int pitch, int rows, int padded) {
-    constexpr int Q = D / 4;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const int f = threadIdx.x + i * 256;
-        if (f < padded * Q) {
-            af32x4 t = v[i];
-            if (f >= rows * Q) t = af32x4{0.f, 0.f, 0.f, 0.f};
-            *reinterpret_cast<af32x4*>(dst + (f / Q) * pitch + (f % Q) * 4) = t;
-        }
-    }
-}
 
 // DROP: dropout of the probabilities between the softmax and the context, from the stream of dropout.hip (one call per launch:
 // read `draws`, take a ticket, the last arriver advances).  P goes to HBM undropped; what feeds the context MFMAs is Pd.
@@ -329,20 +259,6 @@ __global__ void __launch_bounds__(256) attn_fwd(std::conditional_t<DROP, AttnDro
     LG_ATL(6);
 }
 
-struct AttnBwdArgs {
-    LG_ATL_FIELD
-    const float *q, *k, *v, *g;      // g = gradient of the context; addressing as in AttnArgs
-    int64_t ldq, sbq, ldk, sbk, ldv, sbv, ldg, sbg;
-    const float* p;                  // probabilities saved by the forward
-    float *dq, *dk, *dv;
-    int64_t lddq, sbdq, lddk, sbdk, lddv, sbdv;
-    int S, heads, batch;
-    float scale;
-    double* shift;                   // [batch, heads, S]: the softmax shift of every query row, query role -> key role
-    int*    flags;                   // [batch * heads][2]: rows published / key-role workgroups served; zero between launches
-    int*    status;                  // device status flag (a wait that gives up raises it)
-};
-
 // The probabilities a thread needs for its rows: row = (tid >> 3) + 32 * pass, float4 columns (tid & 7) + 8 * i.  Fetched into
 // registers ahead of the MFMAs whose result they meet, so the row pass below never waits for HBM.
 template <int PASSES>
@@ -436,10 +352,6 @@ constexpr int attn_bwd_lds_floats(int S) {
     const int key = 2 * S * (D + 8) + 32 * (D + 4) + 2 * S * 40 + 2048;
     return query > key ? query : key;
 }
-
-struct AttnBwdDropArgs : AttnBwdArgs {
-    AttnDrop drop;
-};
 
 // DROP: the mask of the forward again, from the seed in the generator's state and the call number the forward wrote; nothing
 // is drawn.  dP is masked in both roles after the same MFMA sequence (one multiply, the same bits), dV takes P under the mask.
@@ -662,13 +574,6 @@ __global__ void __launch_bounds__(256) attn_bwd(std::conditional_t<DROP, AttnBwd
     LG_ATL(6);
 }
 
-template <class K>
-static int allow_lds(K kernel, size_t bytes) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes));
-    if (e != hipSuccess) { set_error("attention: %zu bytes of LDS refused: %s", bytes, hipGetErrorString(e)); return LG_EHIP; }
-    return LG_OK;
-}
-
 #ifdef LG_GEMM_TIMELINE
 static unsigned long long* g_atl = nullptr;
 static int g_atl_wgs = 0;
@@ -682,46 +587,176 @@ static unsigned long long* timeline_buffer(int wgs) {
 }
 #endif
 
+// ---- the launchers: LDS size, allow_lds, launch.  `a` is sliced to the struct the instantiation takes ---------------------------
+template <int D, bool TAIL, bool DROP>
+static int launch_fwd_as(const AttnDropArgs& a, dim3 grid) {
+    const size_t bytes = size_t(TAIL ? attn_fwd_tail_lds_floats<D>(a.S) : attn_fwd_lds_floats<D>(a.S)) * 4;
+    int rc = allow_lds(&attn_fwd<D, TAIL, DROP>, bytes);
+    if (rc != LG_OK) return rc;
+    hipLaunchKernelGGL((attn_fwd<D, TAIL, DROP>), grid, dim3(256), bytes, rt().stream, a);
+    return LG_OK;
+}
+
+template <int D, bool TAIL, bool DROP>
+static int launch_bwd_as(const AttnBwdDropArgs& a, dim3 grid) {
+    const size_t bytes = size_t(attn_bwd_lds_floats<D>(round32(a.S))) * 4;
+    int rc = allow_lds(&attn_bwd<D, TAIL, DROP>, bytes);
+    if (rc != LG_OK) return rc;
+    hipLaunchKernelGGL((attn_bwd<D, TAIL, DROP>), grid, dim3(256), bytes, rt().stream, a);
+    return LG_OK;
+}
+
+static int launch_fwd(const AttnDropArgs& a, dim3 grid, int64_t D, bool tail, bool drop) {
+    static int (*const table[2][2][2])(const AttnDropArgs&, dim3) = {          // [D == 64][tail][drop]
+        {{launch_fwd_as<32, false, false>, launch_fwd_as<32, false, true>}, {launch_fwd_as<32, true, false>, launch_fwd_as<32, true, true>}},
+        {{launch_fwd_as<64, false, false>, launch_fwd_as<64, false, true>}, {launch_fwd_as<64, true, false>, launch_fwd_as<64, true, true>}}};
+    return table[D == 64][tail][drop](a, grid);
+}
+
+static int launch_bwd(const AttnBwdDropArgs& a, dim3 grid, int64_t D, bool tail, bool drop) {
+    static int (*const table[2][2][2])(const AttnBwdDropArgs&, dim3) = {       // [D == 64][tail][drop]
+        {{launch_bwd_as<32, false, false>, launch_bwd_as<32, false, true>}, {launch_bwd_as<32, true, false>, launch_bwd_as<32, true, true>}},
+        {{launch_bwd_as<64, false, false>, launch_bwd_as<64, false, true>}, {launch_bwd_as<64, true, false>, launch_bwd_as<64, true, true>}}};
+    return table[D == 64][tail][drop](a, grid);
+}
+
+// ---- the one host path ---------------------------------------------------------------------------------------------------------
 static bool ok_operand(const void* p, int64_t ld, int64_t sb) { return p && aligned16(p) && ld % 4 == 0 && sb % 4 == 0; }
+
+static int check_rows_write(const AttnOut& x, int64_t batch, int64_t S, int64_t width) {
+    const int64_t shape[3] = {batch, S, width}, strides[3] = {x.sb, x.ld, 1};
+    return adam_epilogue_check_strided(x.x, 4, 3, shape, strides);
+}
+
+static int check_launch(const char* name) {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return LG_OK;
+    set_error("%s: kernel launch failed: %s", name, hipGetErrorString(e));
+    return LG_EHIP;
+}
+
+// The selection rule.  A family with a form of its own runs that form for every call it accepts - the masked entries the TAIL
+// kernels also at S % 32 == 0 and with mask == NULL.  The dropout family goes by length: the long kernels beyond 128, else
+// the plain kernels where `plain_fits` (forward: no mask and S % 32 == 0; backward: S % 32 == 0 - which forward ran makes no
+// difference to the backward's bits), else the TAIL ones.
+static AttnForm pick_form(const AttnFamily& f, int64_t S, bool plain_fits) {
+    if (f.form != AttnForm::ByLength) return f.form;
+    return S > 128 ? AttnForm::Long : plain_fits ? AttnForm::Plain : AttnForm::Tail;
+}
+
+int attn_forward(const AttnFamily& f, const AttnFwdCall& c) {
+    const char* name = f.fwd;
+    const bool drops = f.dropout();
+    const int64_t batch = c.batch, heads = c.heads, S = c.S, D = c.D, w = heads * D;
+    LG_ARG(f.supported(S, D), "%s: S = %lld (%s), D = %lld (32 or 64) unsupported", name, (long long)S, f.range, (long long)D);
+    if (drops) {
+        LG_ARG(c.prob >= 0.0 && c.prob < 1.0, "%s: p = %g outside [0, 1)", name, c.prob);
+        LG_ARG(c.base != nullptr, "%s: base_out is NULL", name);
+    }
+    LG_ARG(batch >= 0 && heads >= 1 && batch <= 65535 && heads <= 65535, "%s: bad batch / heads", name);
+    if (drops) LG_ARG(batch > 0, "%s: an empty batch draws nothing (batch must be >= 1)", name);
+    if (batch == 0) return LG_OK;
+    LG_ARG(ok_operand(c.q.x, c.q.ld, c.q.sb) && ok_operand(c.k.x, c.k.ld, c.k.sb) && ok_operand(c.v.x, c.v.ld, c.v.sb) &&
+               ok_operand(c.o.x, c.o.ld, c.o.sb) && c.p && aligned16(c.p),
+           "%s: operands must be %s16-byte aligned with pitches that are multiples of 4", name, drops ? "non-NULL and " : "");
+    LG_ARG(c.q.ld >= w && c.k.ld >= w && c.v.ld >= w && c.o.ld >= w, "%s: row pitch below heads * D", name);
+    LG_ARG(!c.mask || c.sbm == 0 || c.sbm >= S, "%s: mask batch pitch %lld is neither 0 (one row for the batch) nor >= S", name, (long long)c.sbm);
+    const int Sp = round32(int(S));                  // what the grid and the tiles cover; S itself where the plain form runs
+    const int64_t wgs = int64_t(Sp / 32) * heads * batch;
+    AttnDrop drop{};
+    if (drops) {
+        LG_ARG(wgs <= int64_t(kRngMaxGroup) * kRngMaxGroup, "%s: %lld workgroups, more than the stream's tickets count", name, (long long)wgs);
+        { int rc = check_rows_write(c.o, batch, S, w); if (rc != LG_OK) return rc; }
+        { int rc = adam_epilogue_check_write(c.p, batch * heads * S * S * 4); if (rc != LG_OK) return rc; }
+        { int rc = adam_epilogue_check_write(c.base, 8); if (rc != LG_OK) return rc; }
+        drop = AttnDrop{rt().rng_state, reinterpret_cast<unsigned long long*>(c.base), 0u, 0.f, rng_group(unsigned(wgs))};
+        rng_threshold(c.prob, drop.threshold, drop.s);
+    }
+    const AttnForm form = pick_form(f, S, !c.mask && S % 32 == 0);
+    AttnDropArgs a{{{
+#ifdef LG_GEMM_TIMELINE
+        form == AttnForm::Long ? nullptr : timeline_buffer(int(wgs)),        // the long kernels take no timestamps
+#endif
+        c.q.x, c.k.x, c.v.x, c.q.ld, c.q.sb, c.k.ld, c.k.sb, c.v.ld, c.v.sb, c.o.x, c.o.ld, c.o.sb, c.p, int(S), int(heads), c.scale},
+        c.mask, c.sbm}, drop};
+    const dim3 grid(unsigned(Sp / 32), unsigned(heads), unsigned(batch));
+    const int rc = form == AttnForm::Long ? attn_long_launch_fwd(a, grid, D, drops) : launch_fwd(a, grid, D, form == AttnForm::Tail, drops);
+    return rc != LG_OK ? rc : check_launch(name);
+}
+
+int attn_backward(const AttnFamily& f, const AttnBwdCall& c) {
+    const char* name = f.bwd;
+    const bool drops = f.dropout();
+    const int64_t batch = c.batch, heads = c.heads, S = c.S, D = c.D, w = heads * D;
+    LG_ARG(f.supported(S, D), "%s: S = %lld (%s), D = %lld (32 or 64) unsupported", name, (long long)S, f.range, (long long)D);
+    if (drops) {
+        LG_ARG(c.prob >= 0.0 && c.prob < 1.0, "%s: p = %g outside [0, 1)", name, c.prob);
+        LG_ARG(c.base != nullptr, "%s: base is NULL", name);
+    }
+    LG_ARG(batch >= 0 && heads >= 1 && batch <= 65535 && heads <= 65535, "%s: bad batch / heads", name);
+    if (batch == 0) return LG_OK;
+    LG_ARG(ok_operand(c.q.x, c.q.ld, c.q.sb) && ok_operand(c.k.x, c.k.ld, c.k.sb) && ok_operand(c.v.x, c.v.ld, c.v.sb) &&
+               ok_operand(c.g.x, c.g.ld, c.g.sb) && ok_operand(c.dq.x, c.dq.ld, c.dq.sb) && ok_operand(c.dk.x, c.dk.ld, c.dk.sb) &&
+               ok_operand(c.dv.x, c.dv.ld, c.dv.sb) && c.p && aligned16(c.p),
+           "%s: operands must be %s16-byte aligned with pitches that are multiples of 4", name, drops ? "non-NULL and " : "");
+    LG_ARG(c.q.ld >= w && c.k.ld >= w && c.v.ld >= w && c.g.ld >= w && c.dq.ld >= w && c.dk.ld >= w && c.dv.ld >= w,
+           "%s: row pitch below heads * D", name);
+    LG_ARG(batch * heads <= rt().n_attn_pairs && 2 * batch <= 65535, "%s: more than %d (batch, head) pairs in one launch", name, rt().n_attn_pairs);
+    AttnDrop drop{};
+    if (drops) {
+        { int rc = check_rows_write(c.dq, batch, S, w); if (rc != LG_OK) return rc; }
+        { int rc = check_rows_write(c.dk, batch, S, w); if (rc != LG_OK) return rc; }
+        { int rc = check_rows_write(c.dv, batch, S, w); if (rc != LG_OK) return rc; }
+        drop = AttnDrop{rt().rng_state, const_cast<unsigned long long*>(reinterpret_cast<const unsigned long long*>(c.base)), 0u, 0.f, 0};
+        rng_threshold(c.prob, drop.threshold, drop.s);
+    }
+    const int Sp = round32(int(S));                  // what the grid, the tiles and the shift slab cover; S itself where the plain form runs
+    const AttnForm form = pick_form(f, S, S % 32 == 0);
+    double* shift = nullptr;
+    {
+        const int mrc = lg_malloc(reinterpret_cast<void**>(&shift), size_t(batch * heads * Sp) * sizeof(double));
+        if (mrc != LG_OK) return mrc;
+    }
+    AttnBwdDropArgs a{{
+#ifdef LG_GEMM_TIMELINE
+        form == AttnForm::Long ? nullptr : timeline_buffer(int(2 * (Sp / 32) * heads * batch)),
+#endif
+        c.q.x, c.k.x, c.v.x, c.g.x, c.q.ld, c.q.sb, c.k.ld, c.k.sb, c.v.ld, c.v.sb, c.g.ld, c.g.sb, c.p, c.dq.x, c.dk.x, c.dv.x,
+        c.dq.ld, c.dq.sb, c.dk.ld, c.dk.sb, c.dv.ld, c.dv.sb, int(S), int(heads), int(batch), c.scale, shift, rt().attn_flags, rt().status_dev},
+        drop};
+    const dim3 grid(unsigned(Sp / 32), unsigned(heads), unsigned(2 * batch));
+    int rc = form == AttnForm::Long ? attn_long_launch_bwd(a, grid, D, drops) : launch_bwd(a, grid, D, form == AttnForm::Tail, drops);
+    if (rc == LG_OK) rc = check_launch(name);
+    const int frc = lg_free(shift);                  // on every path out; stream-ordered: the block is only reused by later launches
+    return rc != LG_OK ? rc : frc;
+}
 
 }  // namespace lg
 
 using namespace lg;
 
+// ---- the entries: each fills the call, names its family and takes the path above ---------------------------------------------
 extern "C" int lg_attention_supported(int64_t S, int64_t D) {
     return (D == 64 || D == 32) && S >= 32 && S <= 128 && S % 32 == 0;
 }
+extern "C" int lg_attention_masked_supported(int64_t S, int64_t D) {
+    return (D == 64 || D == 32) && S >= 1 && S <= 128;
+}
+extern "C" int lg_attention_dropout_supported(int64_t S, int64_t D) {
+    return (D == 64 || D == 32) && S >= 1 && S <= 512;
+}
+
+static const AttnFamily kPlain{"lg_attention_fwd_f32", "lg_attention_bwd_f32", lg_attention_supported, "32..128, multiple of 32", AttnForm::Plain};
+static const AttnFamily kMasked{"lg_attention_masked_fwd_f32", "lg_attention_masked_bwd_f32", lg_attention_masked_supported, "1..128", AttnForm::Tail};
+// one pair for every length, with dropout of the probabilities inside the launches
+static const AttnFamily kDropout{"lg_attention_dropout_fwd_f32", "lg_attention_dropout_bwd_f32", lg_attention_dropout_supported, "1..512",
+                                 AttnForm::ByLength};
 
 extern "C" int lg_attention_fwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
                                     const float* v, int64_t ldv, int64_t sbv, float* o, int64_t ldo, int64_t sbo, float* p,
                                     int64_t batch, int64_t heads, int64_t S, int64_t D, float scale) {
     LG_REQUIRE_INIT();
-    LG_ARG(lg_attention_supported(S, D), "lg_attention_fwd_f32: S = %lld (32..128, multiple of 32), D = %lld (32 or 64) unsupported",
-           (long long)S, (long long)D);
-    LG_ARG(batch >= 0 && heads >= 1 && batch <= 65535 && heads <= 65535, "lg_attention_fwd_f32: bad batch / heads");
-    if (batch == 0) return LG_OK;
-    LG_ARG(ok_operand(q, ldq, sbq) && ok_operand(k, ldk, sbk) && ok_operand(v, ldv, sbv) && ok_operand(o, ldo, sbo) && p && aligned16(p),
-           "lg_attention_fwd_f32: operands must be 16-byte aligned with pitches that are multiples of 4");
-    LG_ARG(ldq >= heads * D && ldk >= heads * D && ldv >= heads * D && ldo >= heads * D, "lg_attention_fwd_f32: row pitch below heads * D");
-    AttnArgs a{
-#ifdef LG_GEMM_TIMELINE
-        timeline_buffer(int(S / 32 * heads * batch)),
-#endif
-        q, k, v, ldq, sbq, ldk, sbk, ldv, sbv, o, ldo, sbo, p, int(S), int(heads), scale};
-    const dim3 grid(unsigned(S / 32), unsigned(heads), unsigned(batch));
-    if (D == 64) {
-        const size_t bytes = size_t(attn_fwd_lds_floats<64>(int(S))) * 4;
-        int rc = allow_lds(&attn_fwd<64>, bytes);
-        if (rc != LG_OK) return rc;
-        hipLaunchKernelGGL(attn_fwd<64>, grid, dim3(256), bytes, rt().stream, a);
-    } else {
-        const size_t bytes = size_t(attn_fwd_lds_floats<32>(int(S))) * 4;
-        int rc = allow_lds(&attn_fwd<32>, bytes);
-        if (rc != LG_OK) return rc;
-        hipLaunchKernelGGL(attn_fwd<32>, grid, dim3(256), bytes, rt().stream, a);
-    }
-    LG_CHECK_LAUNCH();
-    return LG_OK;
+    return attn_forward(kPlain, {{q, ldq, sbq}, {k, ldk, sbk}, {v, ldv, sbv}, {o, ldo, sbo}, p, batch, heads, S, D, scale, nullptr, 0, 0.0, nullptr});
 }
 
 extern "C" int lg_attention_bwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
@@ -730,47 +765,8 @@ extern "C" int lg_attention_bwd_f32(const float* q, int64_t ldq, int64_t sbq, co
                                     float* dv, int64_t lddv, int64_t sbdv, int64_t batch, int64_t heads, int64_t S, int64_t D,
                                     float scale) {
     LG_REQUIRE_INIT();
-    LG_ARG(lg_attention_supported(S, D), "lg_attention_bwd_f32: S = %lld (32..128, multiple of 32), D = %lld (32 or 64) unsupported",
-           (long long)S, (long long)D);
-    LG_ARG(batch >= 0 && heads >= 1 && batch <= 65535 && heads <= 65535, "lg_attention_bwd_f32: bad batch / heads");
-    if (batch == 0) return LG_OK;
-    LG_ARG(ok_operand(q, ldq, sbq) && ok_operand(k, ldk, sbk) && ok_operand(v, ldv, sbv) && ok_operand(g, ldg, sbg) &&
-               ok_operand(dq, lddq, sbdq) && ok_operand(dk, lddk, sbdk) && ok_operand(dv, lddv, sbdv) && p && aligned16(p),
-           "lg_attention_bwd_f32: operands must be 16-byte aligned with pitches that are multiples of 4");
-    const int64_t w = heads * D;
-    LG_ARG(ldq >= w && ldk >= w && ldv >= w && ldg >= w && lddq >= w && lddk >= w && lddv >= w, "lg_attention_bwd_f32: row pitch below heads * D");
-    LG_ARG(batch * heads <= rt().n_attn_pairs && 2 * batch <= 65535, "lg_attention_bwd_f32: more than %d (batch, head) pairs in one launch",
-           rt().n_attn_pairs);
-    int* flags = rt().attn_flags;
-    double* shift = nullptr;
-    {
-        const int mrc = lg_malloc(reinterpret_cast<void**>(&shift), size_t(batch * heads * S) * sizeof(double));
-        if (mrc != LG_OK) return mrc;
-    }
-    AttnBwdArgs a{
-#ifdef LG_GEMM_TIMELINE
-        timeline_buffer(int(2 * (S / 32) * heads * batch)),
-#endif
-        q, k, v, g, ldq, sbq, ldk, sbk, ldv, sbv, ldg, sbg, p, dq, dk, dv, lddq, sbdq, lddk, sbdk, lddv, sbdv, int(S), int(heads), int(batch), scale,
-        shift, flags, rt().status_dev};
-    const dim3 grid(unsigned(S / 32), unsigned(heads), unsigned(2 * batch));
-    if (D == 64) {
-        const size_t bytes = size_t(attn_bwd_lds_floats<64>(int(S))) * 4;
-        int rc = allow_lds(&attn_bwd<64>, bytes);
-        if (rc != LG_OK) return rc;
-        hipLaunchKernelGGL(attn_bwd<64>, grid, dim3(256), bytes, rt().stream, a);
-    } else {
-        const size_t bytes = size_t(attn_bwd_lds_floats<32>(int(S))) * 4;
-        int rc = allow_lds(&attn_bwd<32>, bytes);
-        if (rc != LG_OK) return rc;
-        hipLaunchKernelGGL(attn_bwd<32>, grid, dim3(256), bytes, rt().stream, a);
-    }
-    LG_CHECK_LAUNCH();
-    return lg_free(shift);          // stream-ordered: the block is only reused by later launches
-}
-
-extern "C" int lg_attention_masked_supported(int64_t S, int64_t D) {
-    return (D == 64 || D == 32) && S >= 1 && S <= 128;
+    return attn_backward(kPlain, {{q, ldq, sbq}, {k, ldk, sbk}, {v, ldv, sbv}, {g, ldg, sbg}, p, {dq, lddq, sbdq}, {dk, lddk, sbdk},
+                                  {dv, lddv, sbdv}, batch, heads, S, D, scale, 0.0, nullptr});
 }
 
 extern "C" int lg_attention_masked_fwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
@@ -778,35 +774,7 @@ extern "C" int lg_attention_masked_fwd_f32(const float* q, int64_t ldq, int64_t 
                                            int64_t batch, int64_t heads, int64_t S, int64_t D, float scale,
                                            const float* mask, int64_t sbm) {
     LG_REQUIRE_INIT();
-    LG_ARG(lg_attention_masked_supported(S, D), "lg_attention_masked_fwd_f32: S = %lld (1..128), D = %lld (32 or 64) unsupported",
-           (long long)S, (long long)D);
-    LG_ARG(batch >= 0 && heads >= 1 && batch <= 65535 && heads <= 65535, "lg_attention_masked_fwd_f32: bad batch / heads");
-    if (batch == 0) return LG_OK;
-    LG_ARG(ok_operand(q, ldq, sbq) && ok_operand(k, ldk, sbk) && ok_operand(v, ldv, sbv) && ok_operand(o, ldo, sbo) && p && aligned16(p),
-           "lg_attention_masked_fwd_f32: operands must be 16-byte aligned with pitches that are multiples of 4");
-    LG_ARG(ldq >= heads * D && ldk >= heads * D && ldv >= heads * D && ldo >= heads * D, "lg_attention_masked_fwd_f32: row pitch below heads * D");
-    LG_ARG(!mask || sbm == 0 || sbm >= S, "lg_attention_masked_fwd_f32: mask batch pitch %lld is neither 0 (one row for the batch) nor >= S",
-           (long long)sbm);
-    const int Sp = round32(int(S));
-    AttnTailArgs a{{
-#ifdef LG_GEMM_TIMELINE
-        timeline_buffer(int(Sp / 32 * heads * batch)),
-#endif
-        q, k, v, ldq, sbq, ldk, sbk, ldv, sbv, o, ldo, sbo, p, int(S), int(heads), scale}, mask, sbm};
-    const dim3 grid(unsigned(Sp / 32), unsigned(heads), unsigned(batch));
-    if (D == 64) {
-        const size_t bytes = size_t(attn_fwd_tail_lds_floats<64>(int(S))) * 4;
-        int rc = allow_lds(&attn_fwd<64, true>, bytes);
-        if (rc != LG_OK) return rc;
-        hipLaunchKernelGGL((attn_fwd<64, true>), grid, dim3(256), bytes, rt().stream, a);
-    } else {
-        const size_t bytes = size_t(attn_fwd_tail_lds_floats<32>(int(S))) * 4;
-        int rc = allow_lds(&attn_fwd<32, true>, bytes);
-        if (rc != LG_OK) return rc;
-        hipLaunchKernelGGL((attn_fwd<32, true>), grid, dim3(256), bytes, rt().stream, a);
-    }
-    LG_CHECK_LAUNCH();
-    return LG_OK;
+    return attn_forward(kMasked, {{q, ldq, sbq}, {k, ldk, sbk}, {v, ldv, sbv}, {o, ldo, sbo}, p, batch, heads, S, D, scale, mask, sbm, 0.0, nullptr});
 }
 
 extern "C" int lg_attention_masked_bwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
@@ -815,84 +783,8 @@ extern "C" int lg_attention_masked_bwd_f32(const float* q, int64_t ldq, int64_t 
                                            float* dv, int64_t lddv, int64_t sbdv, int64_t batch, int64_t heads, int64_t S, int64_t D,
                                            float scale) {
     LG_REQUIRE_INIT();
-    LG_ARG(lg_attention_masked_supported(S, D), "lg_attention_masked_bwd_f32: S = %lld (1..128), D = %lld (32 or 64) unsupported",
-           (long long)S, (long long)D);
-    LG_ARG(batch >= 0 && heads >= 1 && batch <= 65535 && heads <= 65535, "lg_attention_masked_bwd_f32: bad batch / heads");
-    if (batch == 0) return LG_OK;
-    LG_ARG(ok_operand(q, ldq, sbq) && ok_operand(k, ldk, sbk) && ok_operand(v, ldv, sbv) && ok_operand(g, ldg, sbg) &&
-               ok_operand(dq, lddq, sbdq) && ok_operand(dk, lddk, sbdk) && ok_operand(dv, lddv, sbdv) && p && aligned16(p),
-           "lg_attention_masked_bwd_f32: operands must be 16-byte aligned with pitches that are multiples of 4");
-    const int64_t w = heads * D;
-    LG_ARG(ldq >= w && ldk >= w && ldv >= w && ldg >= w && lddq >= w && lddk >= w && lddv >= w, "lg_attention_masked_bwd_f32: row pitch below heads * D");
-    LG_ARG(batch * heads <= rt().n_attn_pairs && 2 * batch <= 65535, "lg_attention_masked_bwd_f32: more than %d (batch, head) pairs in one launch",
-           rt().n_attn_pairs);
-    const int Sp = round32(int(S));
-    int* flags = rt().attn_flags;
-    double* shift = nullptr;
-    {
-        const int mrc = lg_malloc(reinterpret_cast<void**>(&shift), size_t(batch * heads * Sp) * sizeof(double));
-        if (mrc != LG_OK) return mrc;
-    }
-    AttnBwdArgs a{
-#ifdef LG_GEMM_TIMELINE
-        timeline_buffer(int(2 * (Sp / 32) * heads * batch)),
-#endif
-        q, k, v, g, ldq, sbq, ldk, sbk, ldv, sbv, ldg, sbg, p, dq, dk, dv, lddq, sbdq, lddk, sbdk, lddv, sbdv, int(S), int(heads), int(batch), scale,
-        shift, flags, rt().status_dev};
-    const dim3 grid(unsigned(Sp / 32), unsigned(heads), unsigned(2 * batch));
-    if (D == 64) {
-        const size_t bytes = size_t(attn_bwd_lds_floats<64>(Sp)) * 4;
-        int rc = allow_lds(&attn_bwd<64, true>, bytes);
-        if (rc != LG_OK) return rc;
-        hipLaunchKernelGGL((attn_bwd<64, true>), grid, dim3(256), bytes, rt().stream, a);
-    } else {
-        const size_t bytes = size_t(attn_bwd_lds_floats<32>(Sp)) * 4;
-        int rc = allow_lds(&attn_bwd<32, true>, bytes);
-        if (rc != LG_OK) return rc;
-        hipLaunchKernelGGL((attn_bwd<32, true>), grid, dim3(256), bytes, rt().stream, a);
-    }
-    LG_CHECK_LAUNCH();
-    return lg_free(shift);          // stream-ordered: the block is only reused by later launches
-}
-
-// ---- attention with dropout of the probabilities: one pair for every length ------------------------------------------------
-namespace lg {
-// attention_long.hip: the launches of its DROP instantiations (129 <= S <= 512; arguments already checked)
-int attn_long_drop_fwd(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk, const float* v, int64_t ldv,
-                       int64_t sbv, float* o, int64_t ldo, int64_t sbo, float* p, int64_t batch, int64_t heads, int64_t S, int64_t D,
-                       float scale, const float* mask, int64_t sbm, const AttnDrop& drop);
-int attn_long_drop_bwd(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk, const float* v, int64_t ldv,
-                       int64_t sbv, const float* g, int64_t ldg, int64_t sbg, const float* p, float* dq, int64_t lddq, int64_t sbdq,
-                       float* dk, int64_t lddk, int64_t sbdk, float* dv, int64_t lddv, int64_t sbdv, int64_t batch, int64_t heads,
-                       int64_t S, int64_t D, float scale, const AttnDrop& drop);
-
-static int check_rows_write(const float* x, int64_t ld, int64_t sb, int64_t batch, int64_t S, int64_t width) {
-    const int64_t shape[3] = {batch, S, width}, strides[3] = {sb, ld, 1};
-    return adam_epilogue_check_strided(x, 4, 3, shape, strides);
-}
-
-template <int D, bool TAIL>
-static int launch_drop_fwd(const AttnDropArgs& a, dim3 grid, int Sp) {
-    const size_t bytes = size_t(TAIL ? attn_fwd_tail_lds_floats<D>(a.S) : attn_fwd_lds_floats<D>(a.S)) * 4;
-    (void)Sp;
-    int rc = allow_lds(&attn_fwd<D, TAIL, true>, bytes);
-    if (rc != LG_OK) return rc;
-    hipLaunchKernelGGL((attn_fwd<D, TAIL, true>), grid, dim3(256), bytes, rt().stream, a);
-    return LG_OK;
-}
-
-template <int D, bool TAIL>
-static int launch_drop_bwd(const AttnBwdDropArgs& a, dim3 grid, int Sp) {
-    const size_t bytes = size_t(attn_bwd_lds_floats<D>(Sp)) * 4;
-    int rc = allow_lds(&attn_bwd<D, TAIL, true>, bytes);
-    if (rc != LG_OK) return rc;
-    hipLaunchKernelGGL((attn_bwd<D, TAIL, true>), grid, dim3(256), bytes, rt().stream, a);
-    return LG_OK;
-}
-}  // namespace lg
-
-extern "C" int lg_attention_dropout_supported(int64_t S, int64_t D) {
-    return (D == 64 || D == 32) && S >= 1 && S <= 512;
+    return attn_backward(kMasked, {{q, ldq, sbq}, {k, ldk, sbk}, {v, ldv, sbv}, {g, ldg, sbg}, p, {dq, lddq, sbdq}, {dk, lddk, sbdk},
+                                   {dv, lddv, sbdv}, batch, heads, S, D, scale, 0.0, nullptr});
 }
 
 extern "C" int lg_attention_dropout_fwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
@@ -900,43 +792,7 @@ extern "C" int lg_attention_dropout_fwd_f32(const float* q, int64_t ldq, int64_t
                                             int64_t batch, int64_t heads, int64_t S, int64_t D, float scale,
                                             const float* mask, int64_t sbm, double prob, uint64_t* base_out) {
     LG_REQUIRE_INIT();
-    LG_ARG(lg_attention_dropout_supported(S, D), "lg_attention_dropout_fwd_f32: S = %lld (1..512), D = %lld (32 or 64) unsupported",
-           (long long)S, (long long)D);
-    LG_ARG(prob >= 0.0 && prob < 1.0, "lg_attention_dropout_fwd_f32: p = %g outside [0, 1)", prob);
-    LG_ARG(base_out != nullptr, "lg_attention_dropout_fwd_f32: base_out is NULL");
-    LG_ARG(batch >= 0 && heads >= 1 && batch <= 65535 && heads <= 65535, "lg_attention_dropout_fwd_f32: bad batch / heads");
-    LG_ARG(batch > 0, "lg_attention_dropout_fwd_f32: an empty batch draws nothing (batch must be >= 1)");
-    LG_ARG(ok_operand(q, ldq, sbq) && ok_operand(k, ldk, sbk) && ok_operand(v, ldv, sbv) && ok_operand(o, ldo, sbo) && p && aligned16(p),
-           "lg_attention_dropout_fwd_f32: operands must be non-NULL and 16-byte aligned with pitches that are multiples of 4");
-    LG_ARG(ldq >= heads * D && ldk >= heads * D && ldv >= heads * D && ldo >= heads * D, "lg_attention_dropout_fwd_f32: row pitch below heads * D");
-    LG_ARG(!mask || sbm == 0 || sbm >= S, "lg_attention_dropout_fwd_f32: mask batch pitch %lld is neither 0 (one row for the batch) nor >= S",
-           (long long)sbm);
-    const int Sp = round32(int(S));
-    const int64_t wgs = int64_t(Sp / 32) * heads * batch;
-    LG_ARG(wgs <= int64_t(kRngMaxGroup) * kRngMaxGroup, "lg_attention_dropout_fwd_f32: %lld workgroups, more than the stream's tickets count", (long long)wgs);
-    { int rc = check_rows_write(o, ldo, sbo, batch, S, heads * D); if (rc != LG_OK) return rc; }
-    { int rc = adam_epilogue_check_write(p, batch * heads * S * S * 4); if (rc != LG_OK) return rc; }
-    { int rc = adam_epilogue_check_write(base_out, 8); if (rc != LG_OK) return rc; }
-    AttnDrop drop{rt().rng_state, reinterpret_cast<unsigned long long*>(base_out), 0u, 0.f, rng_group(unsigned(wgs))};
-    rng_threshold(prob, drop.threshold, drop.s);
-    if (S > 128) {
-        const int rc = attn_long_drop_fwd(q, ldq, sbq, k, ldk, sbk, v, ldv, sbv, o, ldo, sbo, p, batch, heads, S, D, scale, mask, sbm, drop);
-        if (rc != LG_OK) return rc;
-        LG_CHECK_LAUNCH();
-        return LG_OK;
-    }
-    AttnDropArgs a{{{
-#ifdef LG_GEMM_TIMELINE
-        timeline_buffer(int(wgs)),
-#endif
-        q, k, v, ldq, sbq, ldk, sbk, ldv, sbv, o, ldo, sbo, p, int(S), int(heads), scale}, mask, sbm}, drop};
-    const dim3 grid(unsigned(Sp / 32), unsigned(heads), unsigned(batch));
-    const bool plain = !mask && S % 32 == 0;
-    const int rc = D == 64 ? (plain ? launch_drop_fwd<64, false>(a, grid, Sp) : launch_drop_fwd<64, true>(a, grid, Sp))
-                           : (plain ? launch_drop_fwd<32, false>(a, grid, Sp) : launch_drop_fwd<32, true>(a, grid, Sp));
-    if (rc != LG_OK) return rc;
-    LG_CHECK_LAUNCH();
-    return LG_OK;
+    return attn_forward(kDropout, {{q, ldq, sbq}, {k, ldk, sbk}, {v, ldv, sbv}, {o, ldo, sbo}, p, batch, heads, S, D, scale, mask, sbm, prob, base_out});
 }
 
 extern "C" int lg_attention_dropout_bwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
@@ -945,47 +801,8 @@ extern "C" int lg_attention_dropout_bwd_f32(const float* q, int64_t ldq, int64_t
                                             float* dv, int64_t lddv, int64_t sbdv, int64_t batch, int64_t heads, int64_t S, int64_t D,
                                             float scale, double prob, const uint64_t* base) {
     LG_REQUIRE_INIT();
-    LG_ARG(lg_attention_dropout_supported(S, D), "lg_attention_dropout_bwd_f32: S = %lld (1..512), D = %lld (32 or 64) unsupported",
-           (long long)S, (long long)D);
-    LG_ARG(prob >= 0.0 && prob < 1.0, "lg_attention_dropout_bwd_f32: p = %g outside [0, 1)", prob);
-    LG_ARG(base != nullptr, "lg_attention_dropout_bwd_f32: base is NULL");
-    LG_ARG(batch >= 0 && heads >= 1 && batch <= 65535 && heads <= 65535, "lg_attention_dropout_bwd_f32: bad batch / heads");
-    if (batch == 0) return LG_OK;
-    LG_ARG(ok_operand(q, ldq, sbq) && ok_operand(k, ldk, sbk) && ok_operand(v, ldv, sbv) && ok_operand(g, ldg, sbg) &&
-               ok_operand(dq, lddq, sbdq) && ok_operand(dk, lddk, sbdk) && ok_operand(dv, lddv, sbdv) && p && aligned16(p),
-           "lg_attention_dropout_bwd_f32: operands must be non-NULL and 16-byte aligned with pitches that are multiples of 4");
-    const int64_t w = heads * D;
-    LG_ARG(ldq >= w && ldk >= w && ldv >= w && ldg >= w && lddq >= w && lddk >= w && lddv >= w, "lg_attention_dropout_bwd_f32: row pitch below heads * D");
-    LG_ARG(batch * heads <= rt().n_attn_pairs && 2 * batch <= 65535, "lg_attention_dropout_bwd_f32: more than %d (batch, head) pairs in one launch",
-           rt().n_attn_pairs);
-    { int rc = check_rows_write(dq, lddq, sbdq, batch, S, w); if (rc != LG_OK) return rc; }
-    { int rc = check_rows_write(dk, lddk, sbdk, batch, S, w); if (rc != LG_OK) return rc; }
-    { int rc = check_rows_write(dv, lddv, sbdv, batch, S, w); if (rc != LG_OK) return rc; }
-    AttnDrop drop{rt().rng_state, const_cast<unsigned long long*>(reinterpret_cast<const unsigned long long*>(base)), 0u, 0.f, 0};
-    rng_threshold(prob, drop.threshold, drop.s);
-    if (S > 128)
-        return attn_long_drop_bwd(q, ldq, sbq, k, ldk, sbk, v, ldv, sbv, g, ldg, sbg, p, dq, lddq, sbdq, dk, lddk, sbdk, dv, lddv, sbdv,
-                                  batch, heads, S, D, scale, drop);
-    const int Sp = round32(int(S));
-    double* shift = nullptr;
-    {
-        const int mrc = lg_malloc(reinterpret_cast<void**>(&shift), size_t(batch * heads * Sp) * sizeof(double));
-        if (mrc != LG_OK) return mrc;
-    }
-    AttnBwdDropArgs a{{
-#ifdef LG_GEMM_TIMELINE
-        timeline_buffer(int(2 * (Sp / 32) * heads * batch)),
-#endif
-        q, k, v, g, ldq, sbq, ldk, sbk, ldv, sbv, ldg, sbg, p, dq, dk, dv, lddq, sbdq, lddk, sbdk, lddv, sbdv, int(S), int(heads), int(batch), scale,
-        shift, rt().attn_flags, rt().status_dev}, drop};
-    const dim3 grid(unsigned(Sp / 32), unsigned(heads), unsigned(2 * batch));
-    // (which forward ran - plain or tail - makes no difference to the backward's bits; the plain kernels take what they can)
-    const bool plain = S % 32 == 0;
-    const int rc = D == 64 ? (plain ? launch_drop_bwd<64, false>(a, grid, Sp) : launch_drop_bwd<64, true>(a, grid, Sp))
-                           : (plain ? launch_drop_bwd<32, false>(a, grid, Sp) : launch_drop_bwd<32, true>(a, grid, Sp));
-    if (rc != LG_OK) { lg_free(shift); return rc; }
-    LG_CHECK_LAUNCH();
-    return lg_free(shift);          // stream-ordered: the block is only reused by later launches
+    return attn_backward(kDropout, {{q, ldq, sbq}, {k, ldk, sbk}, {v, ldv, sbv}, {g, ldg, sbg}, p, {dq, lddq, sbdq}, {dk, lddk, sbdk},
+                                    {dv, lddv, sbdv}, batch, heads, S, D, scale, prob, base});
 }
 
 #ifdef LG_GEMM_TIMELINE

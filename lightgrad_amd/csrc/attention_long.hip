@@ -22,90 +22,16 @@
 // LDS at D = 64, S = 512: forward 126 KB, query role 124 KB, key role 132 KB: one workgroup per CU.  The argument for the
 // hand-off - query-role workgroups fill the front of the grid, so a key-role workgroup only ever waits for workgroups that are
 // already running and wait for nothing - does not depend on occupancy.
-#include "common.h"
-#include "mfma_lds.h"
-#include "rng_common.h"
-#include <cmath>
-#include <type_traits>
+//
+// Layout.  The argument structs and device helpers are attention.hip's own (attention_common.h).  This file holds the long kernels,
+// one launcher per direction (attn_long_launch_fwd / _bwd, called by the shared host path of attention.hip - for the long
+// entries below and, beyond 128 positions, for the dropout entries) and the two lg_attention_long_* entries.
+#include "attention_common.h"
 
 namespace lg {
 
 constexpr int kLongChunk = 128;        // rows of a streamed operand in LDS at a time
 constexpr int kLongMaxBlocks = 16;     // 32-column blocks of the longest row (512 / 32)
-
-__host__ __device__ constexpr int long_pad32(int S) { return (S + 31) & ~31; }
-
-struct AttnLongArgs {
-    const float *q, *k, *v;          // element (b, s, head, d) of X at X + b * sbX + s * ldX + head * D + d
-    int64_t ldq, sbq, ldk, sbk, ldv, sbv;
-    float* o;                        // context, same addressing
-    int64_t ldo, sbo;
-    float* p;                        // probabilities (batch, heads, S, S), dense
-    int S, heads;
-    float scale;
-    const float* mask;               // key-padding mask, element (b, j) at mask + b * sbm + j (sbm = 0: one row for the batch); NULL = none
-    int64_t sbm;
-};
-
-struct AttnLongBwdArgs {
-    const float *q, *k, *v, *g;      // g = gradient of the context
-    int64_t ldq, sbq, ldk, sbk, ldv, sbv, ldg, sbg;
-    const float* p;                  // probabilities saved by the forward
-    float *dq, *dk, *dv;
-    int64_t lddq, sbdq, lddk, sbdk, lddv, sbdv;
-    int S, heads, batch;
-    float scale;
-    double* shift;                   // [batch, heads, Sp]: the softmax shift of every query row, query role -> key role
-    int*    flags;                   // [batch * heads][2]: rows published / key-role workgroups served; zero between launches
-    int*    status;                  // device status flag (a wait that gives up raises it)
-};
-
-// DROP instantiations: the same arguments and the call of the random stream (rng_common.h)
-struct AttnLongDropArgs : AttnLongArgs {
-    AttnDrop drop;
-};
-struct AttnLongBwdDropArgs : AttnLongBwdArgs {
-    AttnDrop drop;
-};
-
-// the two 64-bit words of a call in LDS (DROP instantiations only: 16 bytes of static LDS next to the dynamic tiles)
-template <bool DROP>
-__device__ __forceinline__ unsigned long long* long_rng_call_slot() {
-    if constexpr (DROP) {
-        __shared__ unsigned long long call[2];
-        return call;
-    } else {
-        return nullptr;
-    }
-}
-
-// linear index of this workgroup over the 3-D grid / workgroups of the launch: what the tickets of the random stream count
-__device__ __forceinline__ int long_grid_linear_block() { return int((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x); }
-__device__ __forceinline__ int long_grid_blocks() { return int(gridDim.x * gridDim.y * gridDim.z); }
-
-// a float4 at flat element index i of the dense (batch, heads, S, S) tensor under the mask of the call: x * s where the stream
-// keeps the element, +0.0 where it drops it (S % 4 != 0: the four words can come from two groups)
-__device__ __forceinline__ af32x4 long_drop4(af32x4 t, int64_t i, unsigned long long seed, unsigned long long base, uint32_t threshold, float s) {
-    uint32_t w[4];
-    rng_words4<false>(i, seed, base, w);
-    return af32x4{rng_keep(t[0], w[0], threshold, s), rng_keep(t[1], w[1], threshold, s), rng_keep(t[2], w[2], threshold, s),
-                  rng_keep(t[3], w[3], threshold, s)};
-}
-
-// store_rows that also clears rows [rows, padded): an MFMA operand row past the sequence must be zero, not stale LDS
-template <int D, int N>
-__device__ __forceinline__ void long_store_rows(const af32x4 (&v)[N], float* dst, int pitch, int rows, int padded) {
-    constexpr int Q = D / 4;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const int f = threadIdx.x + i * 256;
-        if (f < padded * Q) {
-            af32x4 t = v[i];
-            if (f >= rows * Q) t = af32x4{0.f, 0.f, 0.f, 0.f};
-            *reinterpret_cast<af32x4*>(dst + (f / Q) * pitch + (f % Q) * 4) = t;
-        }
-    }
-}
 
 // rows [c0, c0 + 128) of an operand of S rows: global -> registers (only rows < S are addressed; c0 < S) ...
 template <int D, int N>
@@ -118,7 +44,7 @@ template <int D, int N>
 __device__ __forceinline__ void chunk_store(const af32x4 (&v)[N], float* dst, int pitch, int c0, int S, int Sp) {
     const int rows = S - c0 < kLongChunk ? S - c0 : kLongChunk;
     const int padded = Sp - c0 < kLongChunk ? Sp - c0 : kLongChunk;
-    long_store_rows<D, N>(v, dst, pitch, rows, padded);
+    store_rows_padded<D, N>(v, dst, pitch, rows, padded);
 }
 
 template <int D>
@@ -127,9 +53,9 @@ constexpr int attn_long_fwd_lds_floats(int Sp) { return 32 * (D + 4) + 32 * (Sp 
 // DROP: dropout of the probabilities between the softmax and the context, from the stream of dropout.hip (one call per launch:
 // read `draws`, take a ticket, the last arriver advances).  P goes to HBM undropped; what feeds the context MFMAs is Pd.
 template <int D, bool DROP = false>
-__global__ void __launch_bounds__(256) attn_long_fwd(std::conditional_t<DROP, AttnLongDropArgs, AttnLongArgs> a) {
+__global__ void __launch_bounds__(256) attn_long_fwd(std::conditional_t<DROP, AttnDropArgs, AttnTailArgs> a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int S = a.S, Sp = long_pad32(S), PP = Sp + 4;
+    const int S = a.S, Sp = round32(S), PP = Sp + 4;
     constexpr int PQ = D + 4, PV = D + 8;
     constexpr int NB = 32 * (D / 4) / 256 > 0 ? 32 * (D / 4) / 256 : 1, NA = kLongChunk * (D / 4) / 256;
     float* Qs = lds;                      // Q rows of the block                    32 x PQ
@@ -142,18 +68,18 @@ __global__ void __launch_bounds__(256) attn_long_fwd(std::conditional_t<DROP, At
     const int qrows = S - q0 < 32 ? S - q0 : 32;                      // rows of this block that exist: a row past them is never read
     const float* kg = a.k + int64_t(b) * a.sbk + head * D;
     const float* vg = a.v + int64_t(b) * a.sbv + head * D;
-    [[maybe_unused]] unsigned long long* const call = long_rng_call_slot<DROP>();
+    [[maybe_unused]] unsigned long long* const call = rng_call_slot<DROP>();
     [[maybe_unused]] int order = 0, grp = 0, groups = 0;
     [[maybe_unused]] int* tickets = nullptr;
     [[maybe_unused]] int* mine = nullptr;
     if constexpr (DROP) {
         tickets = rng_tickets(a.drop.state);
-        grp = long_grid_linear_block() / a.drop.group;
-        groups = (long_grid_blocks() + a.drop.group - 1) / a.drop.group;
+        grp = grid_linear_block() / a.drop.group;
+        groups = (grid_blocks() + a.drop.group - 1) / a.drop.group;
         mine = tickets + (1 + grp) * kRngLine;
         if (tid == 0) {
             rng_read_call(a.drop.state, call);                        // `draws` is in a register before the ticket is taken
-            if (long_grid_linear_block() == 0) a.drop.base[0] = call[1];
+            if (grid_linear_block() == 0) a.drop.base[0] = call[1];
             order = rng_take_ticket(mine);
         }
     }
@@ -163,7 +89,7 @@ __global__ void __launch_bounds__(256) attn_long_fwd(std::conditional_t<DROP, At
         af32x4 rq[NB];
         load_rows<D, NB>(rq, a.q + int64_t(b) * a.sbq + int64_t(q0) * a.ldq + head * D, a.ldq, qrows);
         chunk_load<D, NA>(rc, kg, a.ldk, 0, S);
-        long_store_rows<D, NB>(rq, Qs, PQ, qrows, 32);
+        store_rows_padded<D, NB>(rq, Qs, PQ, qrows, 32);
         // (1.0 - mask) * -10000.0 in fp32, the composite's own arithmetic (bert.py:82); -0.0f where the mask is 1 or absent:
         // adding it changes no bit of a score
         for (int j = tid; j < Sp; j += 256) Bias[j] = (j < S && a.mask) ? (1.0f - a.mask[int64_t(b) * a.sbm + j]) * -10000.0f : -0.0f;
@@ -235,7 +161,7 @@ __global__ void __launch_bounds__(256) attn_long_fwd(std::conditional_t<DROP, At
 #pragma unroll
                 for (int e = 0; e < 4; ++e) t[i][e] *= inv;
                 // (DROP: a key >= S holds 0 and stays 0 whatever word it meets; a row >= S is never stored)
-                if constexpr (DROP) *reinterpret_cast<af32x4*>(pr + c) = long_drop4(t[i], (pg - a.p) + c, seed, base, a.drop.threshold, a.drop.s);
+                if constexpr (DROP) *reinterpret_cast<af32x4*>(pr + c) = drop4<false>(t[i], (pg - a.p) + c, seed, base, a.drop.threshold, a.drop.s);
                 else                *reinterpret_cast<af32x4*>(pr + c) = t[i];
                 if (row_exists) {
                     if ((S & 3) == 0) {
@@ -280,7 +206,7 @@ __global__ void __launch_bounds__(256) attn_long_fwd(std::conditional_t<DROP, At
     }
     if constexpr (DROP) {
         if (tid == 0)
-            rng_last_arriver_advances(a.drop.state, tickets, mine, order, grp, groups, a.drop.group, long_grid_blocks(), rng_uniform64(call[1]));
+            rng_last_arriver_advances(a.drop.state, tickets, mine, order, grp, groups, a.drop.group, grid_blocks(), rng_uniform64(call[1]));
     }
 }
 
@@ -296,9 +222,9 @@ constexpr int attn_long_bwd_lds_floats(int Sp) {
 // is drawn.  dP is masked in both roles after the same MFMA sequence (one multiply, the same bits); the key role forms dS from
 // the undropped P[chunk, block] in registers and stores that tile under the mask for dV: no second tile.
 template <int D, bool DROP = false>
-__global__ void __launch_bounds__(256) attn_long_bwd(std::conditional_t<DROP, AttnLongBwdDropArgs, AttnLongBwdArgs> a) {
+__global__ void __launch_bounds__(256) attn_long_bwd(std::conditional_t<DROP, AttnBwdDropArgs, AttnBwdArgs> a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int S = a.S, Sp = long_pad32(S);           // the sequence / what the tiles, the shift slab and the hand-off counter cover
+    const int S = a.S, Sp = round32(S);           // the sequence / what the tiles, the shift slab and the hand-off counter cover
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     // the query-role workgroups of the whole grid are dispatched before any key-role one (role in the slowest grid index): a
     // key-role workgroup that waits, waits for workgroups that are already running and wait for nothing
@@ -332,7 +258,7 @@ __global__ void __launch_bounds__(256) attn_long_bwd(std::conditional_t<DROP, At
             af32x4 rg[NB];
             load_rows<D, NB>(rg, gg + int64_t(j0) * a.ldg, a.ldg, brows);
             chunk_load<D, NA>(rc, vg, a.ldv, 0, S);
-            long_store_rows<D, NB>(rg, Gs, PG, brows, 32);
+            store_rows_padded<D, NB>(rg, Gs, PG, brows, 32);
         }
         // the probabilities of this thread's row (tid >> 3), float4 columns (tid & 7) + 8 i, fetched ahead of the MFMAs whose
         // result they meet.  A key >= S has no probability: 0, so the row pass adds nothing for it and its dS is 0.  A row
@@ -384,7 +310,7 @@ __global__ void __launch_bounds__(256) attn_long_bwd(std::conditional_t<DROP, At
                     if constexpr (DROP) {
                         // what the MFMAs left is dO V^T: dP is that under the forward's mask, kept for the pass below (this
                         // thread's own float4: no barrier); the shift is formed from the masked dP
-                        g4 = long_drop4(g4, (int64_t(bh) * S + j0 + row) * S + c, seed, base, a.drop.threshold, a.drop.s);
+                        g4 = drop4<false>(g4, (int64_t(bh) * S + j0 + row) * S + c, seed, base, a.drop.threshold, a.drop.s);
                         *reinterpret_cast<af32x4*>(gr + c) = g4;
                     }
 #pragma unroll
@@ -457,7 +383,7 @@ __global__ void __launch_bounds__(256) attn_long_bwd(std::conditional_t<DROP, At
         load_rows<D, NB>(rv, vg + int64_t(j0) * a.ldv, a.ldv, brows);
         chunk_load<D, NA>(rg, gg, a.ldg, 0, S);
         chunk_load<D, NA>(rq, qg, a.ldq, 0, S);
-        long_store_rows<D, NB>(rv, Vj, PVK, brows, 32);
+        store_rows_padded<D, NB>(rv, Vj, PVK, brows, 32);
     }
     // dV = P[:, block]^T @ dO and dK = dS[:, block]^T @ Q: 2 * NT output tiles of 32 x 32 over four waves
     constexpr int TILES = 2 * NT, KP = 4 / TILES > 0 ? 4 / TILES : 1;
@@ -561,65 +487,35 @@ __global__ void __launch_bounds__(256) attn_long_bwd(std::conditional_t<DROP, At
         if (acc_row(e, h) < brows) dst[int64_t(acc_row(e, h)) * ldd] = acc[e];
 }
 
-template <class K>
-static int long_allow_lds(K kernel, size_t bytes) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes));
-    if (e != hipSuccess) { set_error("attention: %zu bytes of LDS refused: %s", bytes, hipGetErrorString(e)); return LG_EHIP; }
+// ---- the launchers behind attn_forward / attn_backward (attention.hip): LDS size, allow_lds, launch -----------------------------
+template <int D, bool DROP>
+static int launch_long_fwd_as(const AttnDropArgs& a, dim3 grid) {
+    const size_t bytes = size_t(attn_long_fwd_lds_floats<D>(round32(a.S))) * 4;
+    int rc = allow_lds(&attn_long_fwd<D, DROP>, bytes);
+    if (rc != LG_OK) return rc;
+    hipLaunchKernelGGL((attn_long_fwd<D, DROP>), grid, dim3(256), bytes, rt().stream, a);
     return LG_OK;
 }
 
-static bool long_ok_operand(const void* p, int64_t ld, int64_t sb) { return p && aligned16(p) && ld % 4 == 0 && sb % 4 == 0; }
-
-// the launches behind lg_attention_dropout_*_f32 (attention.hip, which has checked the arguments) for 129 <= S <= 512
-int attn_long_drop_fwd(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk, const float* v, int64_t ldv,
-                       int64_t sbv, float* o, int64_t ldo, int64_t sbo, float* p, int64_t batch, int64_t heads, int64_t S, int64_t D,
-                       float scale, const float* mask, int64_t sbm, const AttnDrop& drop) {
-    const int Sp = long_pad32(int(S));
-    AttnLongDropArgs a{{q, k, v, ldq, sbq, ldk, sbk, ldv, sbv, o, ldo, sbo, p, int(S), int(heads), scale, mask, sbm}, drop};
-    const dim3 grid(unsigned(Sp / 32), unsigned(heads), unsigned(batch));
-    if (D == 64) {
-        const size_t bytes = size_t(attn_long_fwd_lds_floats<64>(Sp)) * 4;
-        int rc = long_allow_lds(&attn_long_fwd<64, true>, bytes);
-        if (rc != LG_OK) return rc;
-        hipLaunchKernelGGL((attn_long_fwd<64, true>), grid, dim3(256), bytes, rt().stream, a);
-    } else {
-        const size_t bytes = size_t(attn_long_fwd_lds_floats<32>(Sp)) * 4;
-        int rc = long_allow_lds(&attn_long_fwd<32, true>, bytes);
-        if (rc != LG_OK) return rc;
-        hipLaunchKernelGGL((attn_long_fwd<32, true>), grid, dim3(256), bytes, rt().stream, a);
-    }
+template <int D, bool DROP>
+static int launch_long_bwd_as(const AttnBwdDropArgs& a, dim3 grid) {
+    const size_t bytes = size_t(attn_long_bwd_lds_floats<D>(round32(a.S))) * 4;
+    int rc = allow_lds(&attn_long_bwd<D, DROP>, bytes);
+    if (rc != LG_OK) return rc;
+    hipLaunchKernelGGL((attn_long_bwd<D, DROP>), grid, dim3(256), bytes, rt().stream, a);
     return LG_OK;
 }
 
-int attn_long_drop_bwd(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk, const float* v, int64_t ldv,
-                       int64_t sbv, const float* g, int64_t ldg, int64_t sbg, const float* p, float* dq, int64_t lddq, int64_t sbdq,
-                       float* dk, int64_t lddk, int64_t sbdk, float* dv, int64_t lddv, int64_t sbdv, int64_t batch, int64_t heads,
-                       int64_t S, int64_t D, float scale, const AttnDrop& drop) {
-    const int Sp = long_pad32(int(S));
-    double* shift = nullptr;
-    {
-        const int mrc = lg_malloc(reinterpret_cast<void**>(&shift), size_t(batch * heads * Sp) * sizeof(double));
-        if (mrc != LG_OK) return mrc;
-    }
-    AttnLongBwdDropArgs a{{q, k, v, g, ldq, sbq, ldk, sbk, ldv, sbv, ldg, sbg, p, dq, dk, dv, lddq, sbdq, lddk, sbdk, lddv, sbdv,
-                           int(S), int(heads), int(batch), scale, shift, rt().attn_flags, rt().status_dev}, drop};
-    const dim3 grid(unsigned(Sp / 32), unsigned(heads), unsigned(2 * batch));
-    int rc = LG_OK;
-    if (D == 64) {
-        const size_t bytes = size_t(attn_long_bwd_lds_floats<64>(Sp)) * 4;
-        rc = long_allow_lds(&attn_long_bwd<64, true>, bytes);
-        if (rc == LG_OK) hipLaunchKernelGGL((attn_long_bwd<64, true>), grid, dim3(256), bytes, rt().stream, a);
-    } else {
-        const size_t bytes = size_t(attn_long_bwd_lds_floats<32>(Sp)) * 4;
-        rc = long_allow_lds(&attn_long_bwd<32, true>, bytes);
-        if (rc == LG_OK) hipLaunchKernelGGL((attn_long_bwd<32, true>), grid, dim3(256), bytes, rt().stream, a);
-    }
-    if (rc == LG_OK && hipGetLastError() != hipSuccess) {
-        set_error("lg_attention_dropout_bwd_f32: kernel launch failed");
-        rc = LG_EHIP;
-    }
-    const int frc = lg_free(shift);          // stream-ordered: the block is only reused by later launches
-    return rc != LG_OK ? rc : frc;
+int attn_long_launch_fwd(const AttnDropArgs& a, dim3 grid, int64_t D, bool drop) {
+    static int (*const table[2][2])(const AttnDropArgs&, dim3) = {             // [D == 64][drop]
+        {launch_long_fwd_as<32, false>, launch_long_fwd_as<32, true>}, {launch_long_fwd_as<64, false>, launch_long_fwd_as<64, true>}};
+    return table[D == 64][drop](a, grid);
+}
+
+int attn_long_launch_bwd(const AttnBwdDropArgs& a, dim3 grid, int64_t D, bool drop) {
+    static int (*const table[2][2])(const AttnBwdDropArgs&, dim3) = {          // [D == 64][drop]
+        {launch_long_bwd_as<32, false>, launch_long_bwd_as<32, true>}, {launch_long_bwd_as<64, false>, launch_long_bwd_as<64, true>}};
+    return table[D == 64][drop](a, grid);
 }
 
 }  // namespace lg
@@ -630,37 +526,14 @@ extern "C" int lg_attention_long_supported(int64_t S, int64_t D) {
     return (D == 64 || D == 32) && S >= 129 && S <= 512;
 }
 
+static const AttnFamily kLong{"lg_attention_long_fwd_f32", "lg_attention_long_bwd_f32", lg_attention_long_supported, "129..512", AttnForm::Long};
+
 extern "C" int lg_attention_long_fwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
                                          const float* v, int64_t ldv, int64_t sbv, float* o, int64_t ldo, int64_t sbo, float* p,
                                          int64_t batch, int64_t heads, int64_t S, int64_t D, float scale,
                                          const float* mask, int64_t sbm) {
     LG_REQUIRE_INIT();
-    LG_ARG(lg_attention_long_supported(S, D), "lg_attention_long_fwd_f32: S = %lld (129..512), D = %lld (32 or 64) unsupported",
-           (long long)S, (long long)D);
-    LG_ARG(batch >= 0 && heads >= 1 && batch <= 65535 && heads <= 65535, "lg_attention_long_fwd_f32: bad batch / heads");
-    if (batch == 0) return LG_OK;
-    LG_ARG(long_ok_operand(q, ldq, sbq) && long_ok_operand(k, ldk, sbk) && long_ok_operand(v, ldv, sbv) && long_ok_operand(o, ldo, sbo) &&
-               p && aligned16(p),
-           "lg_attention_long_fwd_f32: operands must be 16-byte aligned with pitches that are multiples of 4");
-    LG_ARG(ldq >= heads * D && ldk >= heads * D && ldv >= heads * D && ldo >= heads * D, "lg_attention_long_fwd_f32: row pitch below heads * D");
-    LG_ARG(!mask || sbm == 0 || sbm >= S, "lg_attention_long_fwd_f32: mask batch pitch %lld is neither 0 (one row for the batch) nor >= S",
-           (long long)sbm);
-    const int Sp = long_pad32(int(S));
-    AttnLongArgs a{q, k, v, ldq, sbq, ldk, sbk, ldv, sbv, o, ldo, sbo, p, int(S), int(heads), scale, mask, sbm};
-    const dim3 grid(unsigned(Sp / 32), unsigned(heads), unsigned(batch));
-    if (D == 64) {
-        const size_t bytes = size_t(attn_long_fwd_lds_floats<64>(Sp)) * 4;
-        int rc = long_allow_lds(&attn_long_fwd<64>, bytes);
-        if (rc != LG_OK) return rc;
-        hipLaunchKernelGGL(attn_long_fwd<64>, grid, dim3(256), bytes, rt().stream, a);
-    } else {
-        const size_t bytes = size_t(attn_long_fwd_lds_floats<32>(Sp)) * 4;
-        int rc = long_allow_lds(&attn_long_fwd<32>, bytes);
-        if (rc != LG_OK) return rc;
-        hipLaunchKernelGGL(attn_long_fwd<32>, grid, dim3(256), bytes, rt().stream, a);
-    }
-    LG_CHECK_LAUNCH();
-    return LG_OK;
+    return attn_forward(kLong, {{q, ldq, sbq}, {k, ldk, sbk}, {v, ldv, sbv}, {o, ldo, sbo}, p, batch, heads, S, D, scale, mask, sbm, 0.0, nullptr});
 }
 
 extern "C" int lg_attention_long_bwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
@@ -669,37 +542,6 @@ extern "C" int lg_attention_long_bwd_f32(const float* q, int64_t ldq, int64_t sb
                                          float* dv, int64_t lddv, int64_t sbdv, int64_t batch, int64_t heads, int64_t S, int64_t D,
                                          float scale) {
     LG_REQUIRE_INIT();
-    LG_ARG(lg_attention_long_supported(S, D), "lg_attention_long_bwd_f32: S = %lld (129..512), D = %lld (32 or 64) unsupported",
-           (long long)S, (long long)D);
-    LG_ARG(batch >= 0 && heads >= 1 && batch <= 65535 && heads <= 65535, "lg_attention_long_bwd_f32: bad batch / heads");
-    if (batch == 0) return LG_OK;
-    LG_ARG(long_ok_operand(q, ldq, sbq) && long_ok_operand(k, ldk, sbk) && long_ok_operand(v, ldv, sbv) && long_ok_operand(g, ldg, sbg) &&
-               long_ok_operand(dq, lddq, sbdq) && long_ok_operand(dk, lddk, sbdk) && long_ok_operand(dv, lddv, sbdv) && p && aligned16(p),
-           "lg_attention_long_bwd_f32: operands must be 16-byte aligned with pitches that are multiples of 4");
-    const int64_t w = heads * D;
-    LG_ARG(ldq >= w && ldk >= w && ldv >= w && ldg >= w && lddq >= w && lddk >= w && lddv >= w, "lg_attention_long_bwd_f32: row pitch below heads * D");
-    LG_ARG(batch * heads <= rt().n_attn_pairs && 2 * batch <= 65535, "lg_attention_long_bwd_f32: more than %d (batch, head) pairs in one launch",
-           rt().n_attn_pairs);
-    const int Sp = long_pad32(int(S));
-    double* shift = nullptr;
-    {
-        const int mrc = lg_malloc(reinterpret_cast<void**>(&shift), size_t(batch * heads * Sp) * sizeof(double));
-        if (mrc != LG_OK) return mrc;
-    }
-    AttnLongBwdArgs a{q, k, v, g, ldq, sbq, ldk, sbk, ldv, sbv, ldg, sbg, p, dq, dk, dv, lddq, sbdq, lddk, sbdk, lddv, sbdv,
-                      int(S), int(heads), int(batch), scale, shift, rt().attn_flags, rt().status_dev};
-    const dim3 grid(unsigned(Sp / 32), unsigned(heads), unsigned(2 * batch));
-    if (D == 64) {
-        const size_t bytes = size_t(attn_long_bwd_lds_floats<64>(Sp)) * 4;
-        int rc = long_allow_lds(&attn_long_bwd<64>, bytes);
-        if (rc != LG_OK) return rc;
-        hipLaunchKernelGGL(attn_long_bwd<64>, grid, dim3(256), bytes, rt().stream, a);
-    } else {
-        const size_t bytes = size_t(attn_long_bwd_lds_floats<32>(Sp)) * 4;
-        int rc = long_allow_lds(&attn_long_bwd<32>, bytes);
-        if (rc != LG_OK) return rc;
-        hipLaunchKernelGGL(attn_long_bwd<32>, grid, dim3(256), bytes, rt().stream, a);
-    }
-    LG_CHECK_LAUNCH();
-    return lg_free(shift);          // stream-ordered: the block is only reused by later launches
+    return attn_backward(kLong, {{q, ldq, sbq}, {k, ldk, sbk}, {v, ldv, sbv}, {g, ldg, sbg}, p, {dq, lddq, sbdq}, {dk, lddk, sbdk},
+                                 {dv, lddv, sbdv}, batch, heads, S, D, scale, 0.0, nullptr});
 }
