@@ -2,12 +2,13 @@
 the BASELINE shapes 784 -> 512 -> 10, batch 1024; the real dataset needs network access).  A NEW batch is
 generated on the host and uploaded EVERY step, so the printed rate is the PCIe-inclusive one.
 
-    python examples/mnist.py [--cpu] [--steps 200] [--graph] [--cnn] [--eval]
+    python examples/mnist.py [--cpu] [--steps 200] [--graph] [--cnn [--batchnorm]] [--eval]
 
 --graph: the step is captured once into a hipGraph; every iteration uploads the batch into the graph's static
 input tensors (pinned staging, asynchronous) and replays the graph.
---eval: after training, the reference's evaluation loop (examples/mnist.py:72-79) over held-out synthetic batches, counted on
-the model's device with `light.metrics.accuracy`: one host read, at the end.
+--batchnorm: the CNN with a BatchNorm2d after each convolution (conv -> BN -> max_pool -> relu, twice).
+--eval: after training, the reference's evaluation loop (examples/mnist.py:72-79) over held-out synthetic batches in `eval()` mode
+(BatchNorm then uses its running statistics), counted on the model's device with `light.metrics.accuracy`: one host read, at the end.
 """
 import argparse
 import os
@@ -33,15 +34,19 @@ class NN(nn.Module):
 
 class CNN(nn.Module):
     """ the reference's examples/mnist.py:14-22 """
-    def __init__(self):
+    def __init__(self, batchnorm=False):
         nn.Module.__init__(self)
         self.c1 = nn.Conv2d(1, 8, kernelsize=3, bias=False, pad=0)
         self.c2 = nn.Conv2d(8, 16, kernelsize=3, bias=False, pad=0)
         self.l1 = nn.Linear(5 * 5 * 16, 10)
+        self.n1 = nn.BatchNorm2d(8) if batchnorm else None               # (after the others: the parameter order without them stays)
+        self.n2 = nn.BatchNorm2d(16) if batchnorm else None
 
     def forward(self, x):
-        y = self.c1(x).max_pool().relu()
-        y = self.c2(y).max_pool().relu()
+        y = self.c1(x)
+        y = (y if self.n1 is None else self.n1(y)).max_pool().relu()
+        y = self.c2(y)
+        y = (y if self.n2 is None else self.n2(y)).max_pool().relu()
         return self.l1(y.reshape(-1, 5 * 5 * 16))
 
 
@@ -57,12 +62,14 @@ def evaluate(model, to_device, batch, n_batches=4):
     """top-1 accuracy over held-out batches (the labels of the synthetic data are random: expect one in ten)"""
     rng = np.random.RandomState(2)
     total = None
+    model.eval()
     with light.no_grad():
         for _ in range(n_batches):
             x, one_hot = synthetic_batch(rng, batch)
             labels = light.from_numpy(one_hot.argmax(-1).astype(np.int64), requires_grad=False)
             y = model(to_device(light.from_numpy(x, requires_grad=False)))
             total = light.metrics.accuracy(y, to_device(labels), into=total)
+    model.train()
     correct, counted = total.numpy()                                     # the only host read of the evaluation
     print("Accuracy:\t %.4f (%d of %d held-out samples)" % (correct / counted, correct, counted))
 
@@ -72,6 +79,7 @@ def main():
     ap.add_argument("--cpu", action="store_true")
     ap.add_argument("--graph", action="store_true")
     ap.add_argument("--cnn", action="store_true", help="the convolutional model instead of the MLP")
+    ap.add_argument("--batchnorm", action="store_true", help="with --cnn: a BatchNorm2d after each convolution")
     ap.add_argument("--loss", choices=["mse", "ce"], default="mse", help="ce: the alternative the reference keeps commented out (mnist.py:57)")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--batch", type=int, default=1024)
@@ -79,7 +87,9 @@ def main():
     args = ap.parse_args()
     to_device = (lambda t: t) if args.cpu else (lambda t: t.hip())
     np.random.seed(0)
-    model = (CNN() if args.cnn else NN()).map_parameters(to_device)
+    if args.batchnorm and not args.cnn:
+        ap.error("--batchnorm needs --cnn")
+    model = (CNN(batchnorm=args.batchnorm) if args.cnn else NN()).map_parameters(to_device)
     rng = np.random.RandomState(1)
     batches = [synthetic_batch(rng, args.batch) for _ in range(8)]       # host-side data, re-uploaded every step
     losses = []

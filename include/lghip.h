@@ -838,6 +838,39 @@ int lg_pool2d_fwd_f32(int op, const float* x, float* y, int64_t L, int64_t H, in
 int lg_pool2d_bwd_f32(const float* x, const float* y, const float* g, float* dx, int64_t L, int64_t H, int64_t W, int64_t kh,
                       int64_t kw);
 
+/* ---- batch normalisation (csrc/batchnorm.hip) ------------------------------------------------------------
+ * Dense fp32 x, y, g, dx of geometry (N, C, L): element (n, c, l) at (n*C + c)*L + l - (N, C, H, W) with L = H*W, (N, C) with
+ * L = 1.  Per channel c over the count = N*L elements with that c: mean_c, the biased variance var_c = mean((x - mean_c)^2) and
+ * rstd_c = 1 / sqrt(var_c + eps).  w, b, running_*, save_*, dw and db hold C floats.
+ *   fwd    y = (x - mean_c) * (rstd_c * w_c) + b_c (w NULL: 1, b NULL: 0); save_mean = mean, save_rstd = rstd; when the running
+ *          pointers are not NULL, on the device and in the same launch as the statistics:
+ *            running_mean = (1 - momentum) * running_mean + momentum * mean
+ *            running_var  = (1 - momentum) * running_var  + momentum * var * count / (count - 1)
+ *          Two launches: statistics, then apply.  A workgroup reduces a slice of a channel to (count, mean, M2) around a shift
+ *          (never E[x^2] - E[x]^2); the slices of a channel are merged with Chan's formula in slice order by the workgroup that
+ *          arrives last at the channel's ticket.  The slice count depends on the shape and on 16-byte alignment only: the same
+ *          bits on every run.
+ *   bwd    db_c = sum g, dw_c = sum g * xhat with xhat = (x - save_mean_c) * save_rstd_c recomputed from x (folded the same
+ *          way, OVERWRITTEN), then dx = w_c * rstd_c * (g - db_c / count - xhat * dw_c / count).  dx, dw and db may each be
+ *          NULL; without dx the second launch is skipped.
+ *   infer  y = (x - running_mean_c) * (w_c / sqrt(running_var_c + eps)) + b_c: one elementwise launch.
+ * relu_x != 0: x is a pre-activation and max(x, 0) (NaN kept) is applied as it is loaded (all three).
+ * Refused with LG_EINVAL: an extent below 1; N*L below 2 (fwd); N*C*L of 2^31 or more; more channels (L > 1) or blocks of 64
+ * channels (L == 1) than the ticket pool holds (65536); a negative eps; a momentum outside (0, 1].  No output may alias an input. */
+int lg_batchnorm_fwd_f32(const float* x, const float* w /* may be NULL */, const float* b /* may be NULL */, float* y, float* save_mean,
+                         float* save_rstd, float* running_mean /* may be NULL */, float* running_var /* may be NULL */, int64_t N,
+                         int64_t C, int64_t L, float eps, float momentum, int relu_x);
+int lg_batchnorm_bwd_f32(const float* g, const float* x, const float* w /* may be NULL */, const float* save_mean, const float* save_rstd,
+                         float* dx /* may be NULL */, float* dw /* may be NULL */, float* db /* may be NULL */, int64_t N, int64_t C,
+                         int64_t L, int relu_x);
+int lg_batchnorm_infer_f32(const float* x, const float* w /* may be NULL */, const float* b /* may be NULL */, const float* running_mean,
+                           const float* running_var, float* y, int64_t N, int64_t C, int64_t L, float eps, int relu_x);
+/* What the most recent lg_batchnorm_* call of the calling thread launched: host bookkeeping for tests, no device work.
+ *   out = {kernel, form, slices, relu_x}
+ * kernel: 0 fwd, 1 bwd, 2 infer, -1 nothing yet; form: 0 lanes along L, 1 lanes across channels (L == 1); slices: workgroups per
+ * channel (form 0) or per block of 64 channels (form 1) of the statistics / sums launch, 1 for infer. */
+int lg_batchnorm_last_plan(int32_t out[4]);
+
 /* library build info: "liblghip <version> gfx950 <build date>" */
 const char* lg_version(void);
 

@@ -176,6 +176,10 @@ PROTOTYPES = {
     "lg_conv2d_last_plan": (c_int, [POINTER(ctypes.c_int32)]),
     "lg_pool2d_fwd_f32": (c_int, [c_int, c_void_p, c_void_p] + [c_int64] * 5),
     "lg_pool2d_bwd_f32": (c_int, [c_void_p] * 4 + [c_int64] * 5),
+    "lg_batchnorm_fwd_f32": (c_int, [c_void_p] * 8 + [c_int64] * 3 + [c_float, c_float, c_int]),
+    "lg_batchnorm_bwd_f32": (c_int, [c_void_p] * 8 + [c_int64] * 3 + [c_int]),
+    "lg_batchnorm_infer_f32": (c_int, [c_void_p] * 6 + [c_int64] * 3 + [c_float, c_int]),
+    "lg_batchnorm_last_plan": (c_int, [POINTER(ctypes.c_int32)]),
 }
 
 # include/lghip_p2p.h: the peer-window gradient exchange, exported by liblghip.so itself (no RCCL)

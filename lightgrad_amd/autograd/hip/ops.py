@@ -1719,6 +1719,148 @@ max_pool = HipTensor.register_op("max_pool", _pool2d("max_pool", 0, HipTensor.ma
 min_pool = HipTensor.register_op("min_pool", _pool2d("min_pool", 1, HipTensor.min_pool), overwrite=True)
 
 
+""" batch normalisation as kernels of its own (csrc/batchnorm.hip): what nn.BatchNorm1d / BatchNorm2d run on """
+
+
+def _batchnorm_geometry(x, *per_channel):
+    """(N, C, L) when the operands are what lg_batchnorm_* take, else None: a float32 input of 2 to 4 axes with fewer than 2^31
+    elements, every per-channel operand None or a dense float32 (C,)"""
+    if not isinstance(x, HipTensor) or x._dtype != _F32 or not 2 <= len(x._shape) <= 4:
+        return None
+    n, c = x._shape[:2]
+    for t in per_channel:
+        if t is not None and not (isinstance(t, HipTensor) and t._dtype == _F32 and t._shape == (c,) and t.is_contiguous()):
+            return None
+    length = 1
+    for s in x._shape[2:]:
+        length *= s
+    if not 0 < n * c * length < 2 ** 31:
+        return None
+    return n, c, length
+
+
+def _batchnorm_source(x):
+    """(the dense tensor the kernels read, relu_x): a still-lazy relu(t) of an image batch is read as t"""
+    pre = _lazy_relu_input_4d(x)
+    return (pre, 1) if pre is not None else (x.contiguous(), 0)
+
+
+def _ptr_or_null(t):
+    return t.ptr if t is not None else _NULL
+
+
+_batch_norm_composite = HipTensor.batch_norm                  # autograd/ops.py
+_batch_norm_infer_composite = HipTensor.batch_norm_infer
+
+
+class _BatchNormType(_FunctionType):
+    """call protocol of the node below: operands the kernels do not take (another dtype or rank, a shape the C ABI refuses) and
+    arguments that are errors (one value per channel, a momentum outside (0, 1]) go to the composite, which computes or raises"""
+
+    def __call__(cls, x, weight=None, bias=None, running_mean=None, running_var=None, momentum=0.1, eps=1e-5):
+        geom = _batchnorm_geometry(x, weight, bias, running_mean, running_var)
+        if geom is not None and geom[0] * geom[2] >= 2 and 0.0 < momentum <= 1.0 and eps >= 0.0:
+            try:
+                return _FunctionType.__call__(cls, x, weight, bias, (running_mean, running_var, float(momentum), float(eps), geom))
+            except _Refused:
+                pass
+        return _batch_norm_composite(x, weight, bias, running_mean, running_var, momentum=momentum, eps=eps)
+
+
+@HipTensor.register_op(overwrite=True)
+class batch_norm(Function, metaclass=_BatchNormType):
+    """ x.batch_norm(weight, bias, running_mean, running_var, momentum, eps): the values of the composite from TWO launches
+    (lg_batchnorm_fwd_f32: statistics with the running update, then apply); x, the (C,) mean and the (C,) 1 / sqrt(var + eps) are
+    all that is saved.  backward: dw, db from one launch and dx from one more that is skipped when x wants no gradient
+    (lg_batchnorm_bwd_f32), the normalised input recomputed from x.  A lazy relu(t) of an image batch is read as t with the relu
+    applied on load, both ways, as conv2d does. """
+    def forward(ctx, x, weight, bias, aux):
+        running_mean, running_var, momentum, eps, (n, c, length) = aux
+        src, relu_x = _batchnorm_source(x)
+        w = weight.contiguous() if weight is not None else None
+        y = HipTensor.empty(x._shape)
+        mean, rstd = HipTensor.empty((c,), requires_grad=False), HipTensor.empty((c,), requires_grad=False)
+        for t in (running_mean, running_var):
+            if t is not None:
+                flush_lazy_readers(t)
+        _call_or_refuse(_l.lib().lg_batchnorm_fwd_f32(src.ptr, _ptr_or_null(w), _ptr_or_null(bias), y.ptr, mean.ptr, rstd.ptr,
+                                                     _ptr_or_null(running_mean), _ptr_or_null(running_var), n, c, length, eps, momentum,
+                                                     relu_x))
+        ctx.save_for_backward(x, w, mean, rstd, (n, c, length))
+        return y
+
+    def backward(ctx, out_grad):
+        x, w, mean, rstd, (n, c, length) = ctx.get_saved_tensors()
+        weight, bias = ctx._parents[1], ctx._parents[2]
+        _require_f32(out_grad)
+        g = out_grad.contiguous()
+        wanting = ctx.parent_tensors
+        src, relu_x = _batchnorm_source(x)
+        dx = HipTensor.empty(x._shape, requires_grad=False) if _py.any(t is x for t in wanting) else None
+        dw = HipTensor.empty((c,), requires_grad=False) if weight is not None and _py.any(t is weight for t in wanting) else None
+        db = HipTensor.empty((c,), requires_grad=False) if bias is not None and _py.any(t is bias for t in wanting) else None
+        _l.check(_l.lib().lg_batchnorm_bwd_f32(g.ptr, src.ptr, _ptr_or_null(w), mean.ptr, rstd.ptr, _ptr_or_null(dx), _ptr_or_null(dw),
+                                               _ptr_or_null(db), n, c, length, relu_x))
+        return dx, dw, db
+
+
+class _BatchNormInferType(_FunctionType):
+    def __call__(cls, x, weight, bias, running_mean, running_var, eps=1e-5):
+        geom = _batchnorm_geometry(x, weight, bias, running_mean, running_var)
+        if geom is not None and running_mean is not None and running_var is not None and eps >= 0.0:
+            try:
+                return _FunctionType.__call__(cls, x, weight, bias, (running_mean, running_var, float(eps), geom))
+            except _Refused:
+                pass
+        return _batch_norm_infer_composite(x, weight, bias, running_mean, running_var, eps=eps)
+
+
+@HipTensor.register_op(overwrite=True)
+class batch_norm_infer(Function, metaclass=_BatchNormInferType):
+    """ x.batch_norm_infer(weight, bias, running_mean, running_var, eps): the evaluation form from ONE elementwise launch
+    (lg_batchnorm_infer_f32).  backward: dw and db from lg_batchnorm_bwd_f32's sums launch with the running statistics in the place
+    of the batch's, dx = g * weight / sqrt(running_var + eps) from elementwise ops. """
+    def forward(ctx, x, weight, bias, aux):
+        running_mean, running_var, eps, (n, c, length) = aux
+        src, relu_x = _batchnorm_source(x)
+        w = weight.contiguous() if weight is not None else None
+        y = HipTensor.empty(x._shape)
+        _call_or_refuse(_l.lib().lg_batchnorm_infer_f32(src.ptr, _ptr_or_null(w), _ptr_or_null(bias), running_mean.ptr, running_var.ptr,
+                                                       y.ptr, n, c, length, eps, relu_x))
+        ctx.save_for_backward(x, w, aux)
+        return y
+
+    def backward(ctx, out_grad):
+        x, w, (running_mean, running_var, eps, (n, c, length)) = ctx.get_saved_tensors()
+        weight, bias = ctx._parents[1], ctx._parents[2]
+        _require_f32(out_grad)
+        g = out_grad.contiguous()
+        wanting = ctx.parent_tensors
+        rstd = _binary(_l.EW_POW, _binary(_l.EW_ADD, running_var, eps), -0.5)
+        dx = dw = db = None
+        if weight is not None and _py.any(t is weight for t in wanting):
+            dw = HipTensor.empty((c,), requires_grad=False)
+        if bias is not None and _py.any(t is bias for t in wanting):
+            db = HipTensor.empty((c,), requires_grad=False)
+        if dw is not None or db is not None:
+            src, relu_x = _batchnorm_source(x)
+            _l.check(_l.lib().lg_batchnorm_bwd_f32(g.ptr, src.ptr, _NULL, running_mean.ptr, rstd.ptr, _NULL, _ptr_or_null(dw),
+                                                   _ptr_or_null(db), n, c, length, relu_x))
+        if _py.any(t is x for t in wanting):
+            scale = _binary(_l.EW_MUL, rstd, w) if w is not None else rstd
+            dx = _binary(_l.EW_MUL, g, HipTensor(scale.data, (1, c) + (1,) * (len(x._shape) - 2), None, scale._offset, scale._dtype,
+                                                 requires_grad=False))
+        return dx, dw, db
+
+
+def batchnorm_last_plan():
+    """{kernel, form, slices, relu_x} of the most recent lg_batchnorm_* call (lghip.h: lg_batchnorm_last_plan)"""
+    out = (ctypes.c_int32 * 4)()
+    _l.check(_l.lib().lg_batchnorm_last_plan(out))
+    return {"kernel": ("fwd", "bwd", "infer")[out[0]] if out[0] >= 0 else None, "form": ("along_l", "across_c")[out[1]],
+            "slices": out[2], "relu_x": bool(out[3])}
+
+
 """ Fused forms used by nn / optim / loss (SURVEY.md §8f row 1) """
 
 

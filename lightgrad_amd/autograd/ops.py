@@ -172,3 +172,74 @@ def min_pool(t, kernel: tuple = (2, 2)):
 @_register("mean_pool")
 def mean_pool(t, kernel: tuple = (2, 2)):
     return t.pool(kernel=kernel).mean(axis=0, keepdims=False)
+
+
+""" Batch normalisation (nn.BatchNorm1d / BatchNorm2d): statistics over every axis but axis 1 """
+
+from .grads import Gradients  # noqa: E402
+
+
+def _per_channel(x, t):
+    """a (C,) tensor as a view that broadcasts against x along axis 1"""
+    return t.reshape(1, -1, *((1,) * (len(x.shape) - 2)))
+
+
+def _check_batch_norm_input(name, x):
+    if not 2 <= len(x.shape) <= 4:
+        raise ValueError("%s: the input must be (N, C), (N, C, L) or (N, C, H, W), got shape %s" % (name, tuple(x.shape)))
+
+
+@_register("batch_norm")
+def batch_norm(x, weight=None, bias=None, running_mean=None, running_var=None, momentum: float = 0.1, eps: float = 1e-5):
+    """ the training form: y = (x - mean_c) / sqrt(var_c + eps) * weight_c + bias_c with the mean and the biased variance of this batch
+    over every axis but the channel axis 1 (two passes: the variance is the mean of the squared centred values).  `weight` / `bias`
+    (C,) or None.  When given, the (C,) running tensors are updated in place, outside the tape:
+    running_mean = (1 - momentum) * running_mean + momentum * mean_c and the same with the unbiased variance var_c * count /
+    (count - 1) for running_var.  A backend may overwrite it with a kernel (hip/ops.py) """
+    _check_batch_norm_input("batch_norm", x)
+    if not 0.0 < momentum <= 1.0:
+        raise ValueError("batch_norm: momentum must lie in (0, 1], got %r" % (momentum,))
+    count = x.numel() // max(x.shape[1], 1)
+    if count < 2:
+        raise ValueError("batch_norm: batch statistics need more than one value per channel (input of shape %s)" % (tuple(x.shape),))
+    axes = (0,) + tuple(range(2, len(x.shape)))
+    mean = x.mean(axis=axes, keepdims=True)
+    centred = x - mean
+    var = (centred * centred).mean(axis=axes, keepdims=True)
+    y = centred * (var + eps).pow(-0.5)
+    if running_mean is not None or running_var is not None:
+        Gradients.disable()
+        try:
+            if running_mean is not None:
+                running_mean *= 1.0 - momentum
+                running_mean += mean.reshape(-1) * momentum
+            if running_var is not None:
+                running_var *= 1.0 - momentum
+                running_var += var.reshape(-1) * (momentum * (count / (count - 1)))
+        finally:
+            Gradients.enable()
+    if weight is not None:
+        y = y * _per_channel(x, weight)
+    if bias is not None:
+        y = y + _per_channel(x, bias)
+    return y
+
+
+@_register("batch_norm_infer")
+def batch_norm_infer(x, weight, bias, running_mean, running_var, eps: float = 1e-5):
+    """ the evaluation form: y = (x - running_mean_c) / sqrt(running_var_c + eps) * weight_c + bias_c.  Differentiable in x, weight
+    and bias (fine-tuning with frozen statistics); the running tensors are constants of the tape """
+    _check_batch_norm_input("batch_norm_infer", x)
+    Gradients.disable()
+    try:
+        shift = _per_channel(x, running_mean)
+        scale = (_per_channel(x, running_var) + eps).pow(-0.5)
+    finally:
+        Gradients.enable()
+    shift._requires_grad = scale._requires_grad = False
+    y = (x - shift) * scale
+    if weight is not None:
+        y = y * _per_channel(x, weight)
+    if bias is not None:
+        y = y + _per_channel(x, bias)
+    return y

@@ -10,6 +10,8 @@ training script written against lightgrad runs unchanged); the implementation is
   * `parameters`, `named_parameters`, `map_parameters` (nn.py:47-55: `model.map_parameters(lambda p: p.hip())` is how
     a model moves to a backend) and `load_parameters` (nn.py:57-76: tensors of any backend or ndarrays) are thin
     loops over `_leaves()` - no per-method recursion;
+  * a tensor filed with `register_buffer` is a BUFFER (the running statistics of BatchNorm): the same table, the same traversal
+    order, but `buffers` / `named_buffers` / `load_buffers` see it and the parameter methods do not; `map_parameters` maps both;
   * `Linear` / `LayerNorm` use a backend's fused tape op when the tensor class offers one (`linear`, `layer_norm` on
     HipTensor) and the reference's composite expression (nn.py:96, :117-124) otherwise - identical values.
 """
@@ -29,6 +31,7 @@ class Module(object):
 
     def __init__(self):
         object.__setattr__(self, "_children", {})
+        object.__setattr__(self, "_buffer_names", set())
 
     # ---- the call protocol ------------------------------------------------------------------------------------------
 
@@ -53,7 +56,19 @@ class Module(object):
     def __setattr__(self, name, value):
         if _is_child(value):
             self.register_param_or_module(name, value)
+            if name in self._buffer_names and isinstance(value, AbstractTensor):
+                value._requires_grad = False                         # a buffer stays one when it is replaced (map_parameters)
         object.__setattr__(self, name, value)
+
+    def register_buffer(self, name, tensor):
+        """file `tensor` under `name` as a BUFFER: state of the module that is no parameter (the running statistics of BatchNorm).
+        It is an attribute, never requires a gradient, is absent from `parameters()` / `named_parameters()` / `load_parameters`
+        and present in `buffers()` / `named_buffers()` / `load_buffers`; `map_parameters` maps it with the parameters"""
+        if not isinstance(tensor, AbstractTensor):
+            raise TypeError("register_buffer: %r must be a tensor, got %s" % (name, type(tensor).__name__))
+        self._buffer_names.add(name)
+        setattr(self, name, tensor)
+        return tensor
 
     def register_param_or_module(self, name, value):
         """file a tensor / sub-module under `name` (re-assigning a name keeps its position in the table)"""
@@ -62,17 +77,20 @@ class Module(object):
         return value
 
     def unregister_param_or_module(self, name):
+        self._buffer_names.discard(name)
         return self._children.pop(name, None)
 
     def _own(self, kind):
         return [(n, c) for n, c in self._children.items() if isinstance(c, kind)]
 
-    def _leaves(self, scope: str = "", sep: str = "."):
-        """every parameter below this module: (owner, attribute name, qualified name, tensor); own tensors first"""
+    def _leaves(self, scope: str = "", sep: str = ".", buffers: bool = False):
+        """every parameter (`buffers`: every buffer instead) below this module: (owner, attribute name, qualified name, tensor);
+        own tensors first"""
         for name, tensor in self._own(AbstractTensor):
-            yield self, name, scope + name, tensor
+            if (name in self._buffer_names) == buffers:
+                yield self, name, scope + name, tensor
         for name, sub in self._own(Module):
-            yield from sub._leaves(scope + name + sep, sep)
+            yield from sub._leaves(scope + name + sep, sep, buffers)
 
     # ---- the reference's traversal API ------------------------------------------------------------------------------
 
@@ -83,8 +101,16 @@ class Module(object):
         scope = prefix + separator if prefix else ""
         return ((qualified, tensor) for _, _, qualified, tensor in self._leaves(scope, separator))
 
+    def buffers(self):
+        return (leaf[3] for leaf in self._leaves(buffers=True))
+
+    def named_buffers(self, prefix: str = "", separator: str = "."):
+        scope = prefix + separator if prefix else ""
+        return ((qualified, tensor) for _, _, qualified, tensor in self._leaves(scope, separator, buffers=True))
+
     def map_parameters(self, fn):
-        for owner, name, _, tensor in list(self._leaves()):
+        """replace every parameter AND every buffer p by fn(p): how a model moves to a backend"""
+        for owner, name, _, tensor in list(self._leaves()) + list(self._leaves(buffers=True)):
             setattr(owner, name, fn(tensor))
         return self
 
@@ -94,6 +120,15 @@ class Module(object):
         for owner, name, qualified, current in list(self._leaves(scope, separator)):
             if qualified not in source:
                 raise AssertionError("no entry %r among the parameters to load (have: %s)" % (qualified, sorted(source)))
+            setattr(owner, name, _as_tensor_like(current, source[qualified], qualified))
+
+    def load_buffers(self, buffer_dict, prefix: str = "", separator: str = ".") -> None:
+        """`load_parameters` for the buffers: every buffer of the module must have an entry"""
+        source = dict(buffer_dict)
+        scope = prefix + separator if prefix else ""
+        for owner, name, qualified, current in list(self._leaves(scope, separator, buffers=True)):
+            if qualified not in source:
+                raise AssertionError("no entry %r among the buffers to load (have: %s)" % (qualified, sorted(source)))
             setattr(owner, name, _as_tensor_like(current, source[qualified], qualified))
 
 
@@ -210,3 +245,39 @@ class LayerNorm(Module):
         centred = x - x.mean(axis=axes, keepdims=True)
         variance = (centred * centred).mean(axis=axes, keepdims=True)
         return centred / (variance + self.eps).pow(1 / 2) * self.weight + self.bias
+
+
+class _BatchNorm(Module):
+    """y = (x - mean_c) / sqrt(var_c + eps) * weight_c + bias_c over every axis but the channel axis 1.  While training: the
+    statistics of the batch (`batch_norm`), and the running statistics - buffers, not parameters - follow them with `momentum`
+    (running_var takes the unbiased variance, PyTorch's convention).  In `eval()`: the running statistics (`batch_norm_infer`),
+    which stay as they are.  Each data-parallel rank normalises its own batch.  Not a layer of the reference."""
+
+    _ranks = ()
+
+    def __init__(self, channels: int, eps: float = 1e-5, momentum: float = 0.1, affine: bool = True):
+        Module.__init__(self)
+        if not 0.0 < momentum <= 1.0:
+            raise ValueError("%s: momentum must lie in (0, 1], got %r" % (type(self).__name__, momentum))
+        self.channels, self.eps, self.momentum = int(channels), eps, momentum
+        self.weight = Tensor.ones((self.channels,)) if affine else None
+        self.bias = Tensor.zeros((self.channels,)) if affine else None
+        self.register_buffer("running_mean", Tensor.zeros((self.channels,), requires_grad=False))
+        self.register_buffer("running_var", Tensor.ones((self.channels,), requires_grad=False))
+
+    def forward(self, x):
+        if len(x.shape) not in self._ranks or x.shape[1] != self.channels:
+            raise AssertionError("%s over %d channels applied to an input of shape %s" % (type(self).__name__, self.channels, tuple(x.shape)))
+        if self.training:
+            return x.batch_norm(self.weight, self.bias, self.running_mean, self.running_var, momentum=self.momentum, eps=self.eps)
+        return x.batch_norm_infer(self.weight, self.bias, self.running_mean, self.running_var, eps=self.eps)
+
+
+class BatchNorm1d(_BatchNorm):
+    """batch normalisation of (N, C) or (N, C, L) inputs"""
+    _ranks = (2, 3)
+
+
+class BatchNorm2d(_BatchNorm):
+    """batch normalisation of (N, C, H, W) inputs"""
+    _ranks = (4,)
