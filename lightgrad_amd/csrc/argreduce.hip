@@ -24,12 +24,13 @@
 //                   storing it (lg_top1_count_f32): ignored rows are not read, workgroups publish their integer counts and the last
 //                   arriver folds them.
 //   arg_rows_split  few long rows (axis = all of a big tensor): a row is split over many workgroups, each publishes one candidate,
-//                   and the hand-off of reduce.hip's red_rows_split (groups of 32 segments with a ticket each, then one ticket per
-//                   row) folds them inside the launch.
+//                   and the two-level fold of handoff.h (groups of 32 segments with a ticket each, then one ticket per row) folds
+//                   them inside the launch.
 //   arg_cols        the axis is strided: one thread per output element, lanes along the output (coalesced when the kept axis is
 //                   contiguous); a long axis is split over blockIdx.y with the same publish-and-fold, one ticket per 256 outputs.
 // Views that do not collapse to one stride each are refused (LG_EINVAL); the tensor layer makes them dense first.
 #include "common.h"
+#include "handoff.h"
 #include <cmath>
 #include <climits>
 
@@ -75,61 +76,7 @@ __device__ __forceinline__ Pair wave_fold(Pair x) {     // butterfly: every lane
     return x;
 }
 
-__device__ __forceinline__ void publish(Pair* slot, Pair x) {        // write-through stores, drained by the caller
-    __hip_atomic_store(&slot->a, x.a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&slot->b, x.b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ Pair fetch(const Pair* slot) {
-    Pair x;
-    x.a = __hip_atomic_load(&slot->a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    x.b = __hip_atomic_load(&slot->b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return x;
-}
-
-// one arrival at a ticket that `expected` workgroups take: true for the last, which leaves the ticket at zero
-__device__ __forceinline__ bool arrive(int* ticket, int expected) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the published words have left before the ticket is taken
-    const bool last = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == expected - 1;
-    if (last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return last;
-}
-
-constexpr int kFoldGroup = 32;                           // slots per first-level ticket (<= 64: folded by one wave)
-
-// The two-level fold of red_rows_split for `n` workgroups that each hold one Pair (`mine`, valid in thread 0; this one is number
-// `idx`): groups of kFoldGroup consecutive slots with a ticket each (`tickets`[0 .. groups), `tstride` ints apart), then one ticket
-// for the groups.  One ticket for hundreds of workgroups that finish together serialises their atomics on one address.
-// Returns true in wave 0 of the ONE workgroup that arrived last of all, with the total in `mine` (every lane).
-// slots: n + groups Pairs.  Called by whole workgroups of 256 threads.
-template <class F>
-__device__ __forceinline__ bool fold_across_workgroups(Pair& mine, Pair* slots, int* tickets, int64_t tstride, int64_t idx, int64_t n) {
-    __shared__ int last1, last2;                         // one word per level: slower waves still read the first
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t groups = (n + kFoldGroup - 1) / kFoldGroup, grp = idx / kFoldGroup;
-    const int64_t in_group = (grp == groups - 1) ? n - grp * kFoldGroup : kFoldGroup;
-    Pair* const slots2 = slots + n;
-    if (threadIdx.x == 0) {
-        publish(slots + idx, mine);
-        last1 = arrive(tickets + grp * tstride, int(in_group));
-    }
-    __syncthreads();
-    if (!last1) return false;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (wave == 0) {
-        const Pair g = wave_fold<F>(lane < in_group ? fetch(slots + grp * kFoldGroup + lane) : F::identity());
-        if (lane == 0) {
-            publish(slots2 + grp, g);
-            last2 = arrive(tickets + groups * tstride, int(groups));
-        }
-    }
-    __syncthreads();
-    if (!last2 || wave != 0) return false;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    Pair f = F::identity();
-    for (int64_t r = lane; r < groups; r += 64) f = F::comb(f, fetch(slots2 + r));
-    mine = wave_fold<F>(f);
-    return true;
-}
+using handoff::kFoldGroup;                              // workgroups that hold one Pair each fold them in two levels (handoff.h)
 
 // ---- walking a contiguous run ------------------------------------------------------------------------------------------------
 
@@ -232,10 +179,13 @@ __global__ void __launch_bounds__(256) arg_rows_wave(const float* __restrict__ i
     }
     if constexpr (COUNT) {
         __shared__ u64 wc[4][2];
+        __shared__ int last[2];
         if (lane == 0) { wc[wave][0] = correct; wc[wave][1] = counted; }
         __syncthreads();
         Pair total{wc[0][0] + wc[1][0] + wc[2][0] + wc[3][0], wc[0][1] + wc[1][1] + wc[2][1] + wc[3][1]};
-        if (gridDim.x > 1 && !fold_across_workgroups<CountFold>(total, c.slots, c.tickets, c.tstride, blockIdx.x, gridDim.x)) return;
+        if (gridDim.x > 1 && !handoff::fold_two_level<CountFold, u64>(total, c.slots, c.slots + gridDim.x, c.tickets, c.tstride, blockIdx.x,
+                                                                      gridDim.x, last, wave_fold<CountFold>))
+            return;
         if (threadIdx.x == 0) {
             c.counts[0] = int64_t(total.a) + (c.accumulate ? c.counts[0] : 0);
             c.counts[1] = int64_t(total.b) + (c.accumulate ? c.counts[1] : 0);
@@ -248,6 +198,7 @@ template <int OP>
 __global__ void __launch_bounds__(256) arg_rows_split(const float* __restrict__ in, int64_t* __restrict__ out, Pair* slots, int* tickets,
                                                       int64_t rlen, int64_t row_stride, int64_t seg, int64_t tstride) {
     __shared__ Pair wbest[4];
+    __shared__ int last[2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t row = blockIdx.y, split = blockIdx.x, splits = gridDim.x;
     const int64_t begin = split * seg;
@@ -262,7 +213,9 @@ __global__ void __launch_bounds__(256) arg_rows_split(const float* __restrict__ 
     Pair best = settle(ArgFold<OP>::comb(ArgFold<OP>::comb(wbest[0], wbest[1]), ArgFold<OP>::comb(wbest[2], wbest[3])), begin);
     if (splits > 1) {
         const int64_t groups = (splits + kFoldGroup - 1) / kFoldGroup;
-        if (!fold_across_workgroups<ArgFold<OP>>(best, slots + row * (splits + groups), tickets + row * (groups + 1) * tstride, tstride, split, splits))
+        Pair* const mine = slots + row * (splits + groups);                      // [row]: splits, then groups
+        if (!handoff::fold_two_level<ArgFold<OP>, u64>(best, mine, mine + splits, tickets + row * (groups + 1) * tstride, tstride, split, splits,
+                                                       last, wave_fold<ArgFold<OP>>))
             return;
     }
     if (threadIdx.x == 0) out[row] = int64_t(best.b);
@@ -291,24 +244,19 @@ __global__ void __launch_bounds__(256) arg_cols(const float* __restrict__ in, in
     Pair best = settle(as_pair(bv, bi), begin);
     const int splits = gridDim.y;
     if (splits > 1) {
-        publish(slots + split * n_out + o, best);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its own stores
-        __syncthreads();
         __shared__ int arrived_last;
-        if (threadIdx.x == 0) arrived_last = arrive(tickets + blockIdx.x, splits);
-        __syncthreads();
-        if (!arrived_last) return;
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        handoff::publish<u64>(slots + split * n_out + o, best);
+        if (!handoff::arrive_workgroup(tickets + blockIdx.x, splits, &arrived_last)) return;
         best = ArgFold<OP>::identity();
         int s = 0;
         for (; s + 3 < splits; s += 4) {                 // four candidates in flight: their loads cross XCDs
             Pair x[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) x[e] = fetch(slots + int64_t(s + e) * n_out + o);
+            for (int e = 0; e < 4; ++e) x[e] = handoff::fetch<Pair, u64>(slots + int64_t(s + e) * n_out + o);
 #pragma unroll
             for (int e = 0; e < 4; ++e) best = ArgFold<OP>::comb(best, x[e]);
         }
-        for (; s < splits; ++s) best = ArgFold<OP>::comb(best, fetch(slots + int64_t(s) * n_out + o));
+        for (; s < splits; ++s) best = ArgFold<OP>::comb(best, handoff::fetch<Pair, u64>(slots + int64_t(s) * n_out + o));
     }
     if (live) out[o] = int64_t(best.b);
 }
@@ -344,11 +292,6 @@ static bool run_has_vector(const float* p, int64_t n) {
     return n - head >= 4;
 }
 
-static int ticket_stride(int64_t n_tickets) {            // tickets on cache lines of their own while the pool allows
-    int64_t t = rt().n_gemm_tickets / n_tickets;
-    return int(t > 32 ? 32 : t);
-}
-
 template <int OP>
 static int run_argreduce(const float* in, int64_t* out, int64_t n_outer, int64_t so, int64_t rlen, int64_t sa, int64_t n_inner, int64_t si) {
     hipStream_t s = rt().stream;
@@ -378,12 +321,12 @@ static int run_argreduce(const float* in, int64_t* out, int64_t n_outer, int64_t
             hipLaunchKernelGGL((arg_rows_split<OP>), dim3(1, unsigned(n_out)), dim3(256), 0, s, in, out, nullptr, nullptr, rlen, so, seg, int64_t(1));
             return LG_OK;
         }
-        if (n_tickets > rt().n_gemm_tickets) return wave_per_row();     // (fewer than 256 rows, a few dozen groups: the pool is far larger)
+        if (n_tickets > rt().n_tickets) return wave_per_row();     // (fewer than 256 rows, a few dozen groups: the pool is far larger)
         Pair* slots = nullptr;
         const int rc = lg_malloc(reinterpret_cast<void**>(&slots), size_t(n_out * (splits + groups)) * sizeof(Pair));
         if (rc != LG_OK) return rc;
         note_arg_plan(ARG_ROWS_SPLIT, splits, 1, run_has_vector(in, seg));
-        hipLaunchKernelGGL((arg_rows_split<OP>), dim3(unsigned(splits), unsigned(n_out)), dim3(256), 0, s, in, out, slots, rt().gemm_tickets,
+        hipLaunchKernelGGL((arg_rows_split<OP>), dim3(unsigned(splits), unsigned(n_out)), dim3(256), 0, s, in, out, slots, rt().tickets,
                            rlen, so, seg, int64_t(ticket_stride(n_tickets)));
         return lg_free(slots);                           // stream-ordered: the block is only reused by later launches
     }
@@ -408,14 +351,14 @@ static int run_argreduce(const float* in, int64_t* out, int64_t n_outer, int64_t
     }
     int64_t chunk = (rlen + splits - 1) / splits;
     splits = (rlen + chunk - 1) / chunk;
-    if (splits > 1 && blocks_x > rt().n_gemm_tickets) { splits = 1; chunk = rlen; }
+    if (splits > 1 && blocks_x > rt().n_tickets) { splits = 1; chunk = rlen; }
     Pair* slots = nullptr;
     if (splits > 1) {
         const int rc = lg_malloc(reinterpret_cast<void**>(&slots), size_t(n_out * splits) * sizeof(Pair));
         if (rc != LG_OK) return rc;
     }
     note_arg_plan(ARG_COLS, splits, merged, 0);
-    hipLaunchKernelGGL((arg_cols<OP>), dim3(unsigned(blocks_x), unsigned(splits)), dim3(256), 0, s, in, out, slots, rt().gemm_tickets, n_out,
+    hipLaunchKernelGGL((arg_cols<OP>), dim3(unsigned(blocks_x), unsigned(splits)), dim3(256), 0, s, in, out, slots, rt().tickets, n_out,
                        n_inner, so, si, sa, rlen, chunk);
     return splits > 1 ? lg_free(slots) : LG_OK;
 }
@@ -485,8 +428,8 @@ extern "C" int lg_top1_count_f32(const float* logits, int64_t rows, int64_t cols
     const int64_t groups = (blocks + kFoldGroup - 1) / kFoldGroup;
     CountArgs c{};
     c.labels = labels; c.ignore = ignore_index; c.has_ignore = has_ignore ? 1 : 0; c.accumulate = accumulate ? 1 : 0;
-    c.counts = counts; c.tickets = rt().gemm_tickets; c.tstride = ticket_stride(groups + 1); c.status = rt().status_dev;
-    LG_ARG(groups + 1 <= rt().n_gemm_tickets, "lg_top1_count_f32: the ticket pool holds %d counters, %lld are needed", rt().n_gemm_tickets,
+    c.counts = counts; c.tickets = rt().tickets; c.tstride = ticket_stride(groups + 1); c.status = rt().status_dev;
+    LG_ARG(groups + 1 <= rt().n_tickets, "lg_top1_count_f32: the ticket pool holds %d counters, %lld are needed", rt().n_tickets,
            (long long)(groups + 1));
     if (blocks > 1) {
         const int rc = lg_malloc(reinterpret_cast<void**>(&c.slots), size_t(blocks + groups) * sizeof(Pair));

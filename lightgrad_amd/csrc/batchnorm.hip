@@ -14,11 +14,12 @@
 // Statistics are (count, mean, M2) triples: a thread sums (x - K) and (x - K)^2 around K = its own first element, turns the two
 // sums into a triple, and triples are merged with Chan's formula - within the wave, across the waves, and across the slices - so
 // nothing ever forms E[x^2] - E[x]^2 of the raw values.
-// Across workgroups: every slice publishes its partial (write-through agent-scope stores, drained), takes the channel's ticket from
-// rt().gemm_tickets (zero between launches), and the last arriver reads the partials past its caches and merges them IN SLICE ORDER by a fixed tree,
-// whoever it is - the same bits on every run.  The slice count depends on the shape alone.  Nobody waits for another workgroup.
+// Across workgroups (handoff.h): every slice publishes its partial into a 16-byte slot and takes the channel's ticket; the last
+// arriver merges the partials IN SLICE ORDER by a fixed tree, whoever it is - the same bits on every run.  The slice count depends
+// on the shape alone.
 // The last arriver also writes save_mean / save_rstd and updates the running statistics, all in the stats launch.
 #include "common.h"
+#include "handoff.h"
 
 namespace lg {
 
@@ -65,40 +66,6 @@ __device__ __forceinline__ Stat shifted_to_stat(float cnt, float k, float s1, fl
 }
 
 __device__ __forceinline__ float relu_keep_nan(float v) { return v < 0.0f ? 0.0f : v; }
-
-__device__ __forceinline__ void publish(float4* slot, float a, float b, float c) {
-    float* p = reinterpret_cast<float*>(slot);
-    __hip_atomic_store(p, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(p + 1, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(p + 2, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ Stat fetch_stat(const float4* slot) {
-    const float* p = reinterpret_cast<const float*>(slot);
-    return Stat{__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __hip_atomic_load(p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
-                __hip_atomic_load(p + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)};
-}
-__device__ __forceinline__ Pair fetch_pair(const float4* slot) {
-    const float* p = reinterpret_cast<const float*>(slot);
-    return Pair{__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __hip_atomic_load(p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)};
-}
-
-// after this workgroup's partials are stored (write-through, agent scope): every storing wave drains its stores, then ONE lane takes
-// the ticket.  The last of `expected` arrivers leaves the ticket at zero for the next launch and reads the partials with agent-scope
-// loads only (fetch_*), which pass the caches of this CU.  (The sequence of reduce.hip's red_cols.)
-__device__ __forceinline__ bool arrive_last(int* ticket, int expected, int* lds_flag) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int order = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = order == expected - 1;
-        if (last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *lds_flag = last;
-    }
-    __syncthreads();
-    const bool last = *lds_flag != 0;
-    if (last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");      // no instruction: keeps the loads of the fold below the ticket
-    return last;
-}
 
 struct BnP {
     unsigned N, C, Lu;          // Lu: units per row (L / VEC)
@@ -176,10 +143,10 @@ __global__ void __launch_bounds__(256) bn_stats_l(const float* __restrict__ x, f
     });
     Stat t = block_merge(shifted_to_stat(cnt, k, s1, s2), lds4);
     if (p.slices > 1) {
-        if (threadIdx.x == 0) publish(partial + size_t(c) * p.slices + s, t.n, t.mean, t.m2);
-        if (!arrive_last(tickets + size_t(c) * p.tstride, int(p.slices), &last_flag)) return;
+        if (threadIdx.x == 0) handoff::publish<float>(partial + size_t(c) * p.slices + s, t);
+        if (!handoff::arrive_workgroup(tickets + size_t(c) * p.tstride, int(p.slices), &last_flag)) return;
         Stat mine{0.0f, 0.0f, 0.0f};
-        if (threadIdx.x < p.slices) mine = fetch_stat(partial + size_t(c) * p.slices + threadIdx.x);
+        if (threadIdx.x < p.slices) mine = handoff::fetch<Stat, float>(partial + size_t(c) * p.slices + threadIdx.x);
         t = block_merge(mine, lds4);
     }
     if (threadIdx.x == 0) finish_channel(t, c, p, save_mean, save_rstd, running_mean, running_var);
@@ -208,10 +175,10 @@ __global__ void __launch_bounds__(256) bn_sums_l(const float* __restrict__ g, co
     });
     Pair t = block_merge(Pair{sg, sgx}, lds4);
     if (p.slices > 1) {
-        if (threadIdx.x == 0) publish(partial + size_t(c) * p.slices + s, t.a, t.b, 0.0f);
-        if (!arrive_last(tickets + size_t(c) * p.tstride, int(p.slices), &last_flag)) return;
+        if (threadIdx.x == 0) handoff::publish<float>(partial + size_t(c) * p.slices + s, t);
+        if (!handoff::arrive_workgroup(tickets + size_t(c) * p.tstride, int(p.slices), &last_flag)) return;
         Pair mine{0.0f, 0.0f};
-        if (threadIdx.x < p.slices) mine = fetch_pair(partial + size_t(c) * p.slices + threadIdx.x);
+        if (threadIdx.x < p.slices) mine = handoff::fetch<Pair, float>(partial + size_t(c) * p.slices + threadIdx.x);
         t = block_merge(mine, lds4);
     }
     if (threadIdx.x == 0) {
@@ -270,9 +237,9 @@ __global__ void __launch_bounds__(256) bn_stats_c(const float* __restrict__ x, f
     Stat t = merge(merge(lds[0][lane], lds[1][lane]), merge(lds[2][lane], lds[3][lane]));
     if (p.slices > 1) {
         float4* mine = partial + size_t(blockIdx.x) * p.slices * 64;
-        if (wave == 0) publish(mine + s * 64 + lane, t.n, t.mean, t.m2);
-        if (!arrive_last(tickets + size_t(blockIdx.x) * p.tstride, int(p.slices), &last_flag)) return;
-        t = fold_slices_cl(Stat{0.0f, 0.0f, 0.0f}, p.slices, lds, [&](unsigned sl, unsigned ln) { return fetch_stat(mine + sl * 64 + ln); });
+        if (wave == 0) handoff::publish<float>(mine + s * 64 + lane, t);
+        if (!handoff::arrive_workgroup(tickets + size_t(blockIdx.x) * p.tstride, int(p.slices), &last_flag)) return;
+        t = fold_slices_cl(Stat{0.0f, 0.0f, 0.0f}, p.slices, lds, [&](unsigned sl, unsigned ln) { return handoff::fetch<Stat, float>(mine + sl * 64 + ln); });
     }
     if (wave == 0 && live) finish_channel(t, c, p, save_mean, save_rstd, running_mean, running_var);
 }
@@ -307,9 +274,9 @@ __global__ void __launch_bounds__(256) bn_sums_c(const float* __restrict__ g, co
     Pair t = merge(merge(lds[0][lane], lds[1][lane]), merge(lds[2][lane], lds[3][lane]));
     if (p.slices > 1) {
         float4* mine = partial + size_t(blockIdx.x) * p.slices * 64;
-        if (wave == 0) publish(mine + s * 64 + lane, t.a, t.b, 0.0f);
-        if (!arrive_last(tickets + size_t(blockIdx.x) * p.tstride, int(p.slices), &last_flag)) return;
-        t = fold_slices_cl(Pair{0.0f, 0.0f}, p.slices, lds, [&](unsigned sl, unsigned ln) { return fetch_pair(mine + sl * 64 + ln); });
+        if (wave == 0) handoff::publish<float>(mine + s * 64 + lane, t);
+        if (!handoff::arrive_workgroup(tickets + size_t(blockIdx.x) * p.tstride, int(p.slices), &last_flag)) return;
+        t = fold_slices_cl(Pair{0.0f, 0.0f}, p.slices, lds, [&](unsigned sl, unsigned ln) { return handoff::fetch<Pair, float>(mine + sl * 64 + ln); });
     }
     if (wave == 0 && live) {
         sums[2 * c] = t.a; sums[2 * c + 1] = t.b;
@@ -390,7 +357,7 @@ static int bn_geometry(const char* who, int64_t N, int64_t C, int64_t L, bool tr
     o.N = N; o.C = C; o.L = L; o.numel = N * C * L;
     o.form = L == 1 ? 1 : 0;
     o.groups_x = o.form == 1 ? (C + 63) / 64 : C;
-    LG_ARG(o.groups_x <= rt().n_gemm_tickets, "%s: %lld channels are more than the ticket pool holds", who, (long long)C);
+    LG_ARG(o.groups_x <= rt().n_tickets, "%s: %lld channels are more than the ticket pool holds", who, (long long)C);
     int64_t slices = (kBnTargetGroups + o.groups_x - 1) / o.groups_x;
     if (o.form == 0) {
         const int64_t units = N * (L / vec);
@@ -413,9 +380,7 @@ static BnP bn_params(const BnGeom& g, int vec, float eps, float momentum, int re
     BnP p;
     p.N = unsigned(g.N); p.C = unsigned(g.C); p.Lu = unsigned(g.L / vec);
     p.chunk = unsigned(g.chunk); p.slices = unsigned(g.slices);
-    // atomics on one cache line are served one after the other (13 ns each, reduce.hip): a line per ticket
-    const int64_t apart = rt().n_gemm_tickets / g.groups_x;
-    p.tstride = unsigned(apart > 32 ? 32 : apart);
+    p.tstride = unsigned(ticket_stride(g.groups_x));
     const double count = double(g.N) * double(g.L);
     p.count = float(count); p.eps = eps; p.momentum = momentum;
     p.unbias = count > 1.0 ? float(count / (count - 1.0)) : 1.0f;
@@ -480,9 +445,9 @@ extern "C" int lg_batchnorm_fwd_f32(const float* x, const float* w, const float*
     if (rc != LG_OK) return rc;
     const BnP p = bn_params(geo, vec_stats, eps, momentum, relu_x);
     const dim3 grid(unsigned(geo.groups_x), unsigned(geo.slices));
-    if (geo.form == 1) hipLaunchKernelGGL(bn_stats_c, grid, dim3(256), 0, rt().stream, x, partial, rt().gemm_tickets, save_mean, save_rstd, running_mean, running_var, p);
-    else if (vec_stats == 4) hipLaunchKernelGGL((bn_stats_l<4>), grid, dim3(256), 0, rt().stream, x, partial, rt().gemm_tickets, save_mean, save_rstd, running_mean, running_var, p);
-    else hipLaunchKernelGGL((bn_stats_l<1>), grid, dim3(256), 0, rt().stream, x, partial, rt().gemm_tickets, save_mean, save_rstd, running_mean, running_var, p);
+    if (geo.form == 1) hipLaunchKernelGGL(bn_stats_c, grid, dim3(256), 0, rt().stream, x, partial, rt().tickets, save_mean, save_rstd, running_mean, running_var, p);
+    else if (vec_stats == 4) hipLaunchKernelGGL((bn_stats_l<4>), grid, dim3(256), 0, rt().stream, x, partial, rt().tickets, save_mean, save_rstd, running_mean, running_var, p);
+    else hipLaunchKernelGGL((bn_stats_l<1>), grid, dim3(256), 0, rt().stream, x, partial, rt().tickets, save_mean, save_rstd, running_mean, running_var, p);
     hipError_t launched = hipGetLastError();
     if (partial != nullptr) {
         rc = lg_free(partial);                                          // stream-ordered: only later launches reuse the block
@@ -521,9 +486,9 @@ extern "C" int lg_batchnorm_bwd_f32(const float* g, const float* x, const float*
     if (rc != LG_OK) { (void)lg_free(sums); return rc; }
     const BnP p = bn_params(geo, vec_sums, 0.0f, 1.0f, relu_x);
     const dim3 grid(unsigned(geo.groups_x), unsigned(geo.slices));
-    if (geo.form == 1) hipLaunchKernelGGL(bn_sums_c, grid, dim3(256), 0, rt().stream, g, x, save_mean, save_rstd, partial, rt().gemm_tickets, sums, dw, db, p);
-    else if (vec_sums == 4) hipLaunchKernelGGL((bn_sums_l<4>), grid, dim3(256), 0, rt().stream, g, x, save_mean, save_rstd, partial, rt().gemm_tickets, sums, dw, db, p);
-    else hipLaunchKernelGGL((bn_sums_l<1>), grid, dim3(256), 0, rt().stream, g, x, save_mean, save_rstd, partial, rt().gemm_tickets, sums, dw, db, p);
+    if (geo.form == 1) hipLaunchKernelGGL(bn_sums_c, grid, dim3(256), 0, rt().stream, g, x, save_mean, save_rstd, partial, rt().tickets, sums, dw, db, p);
+    else if (vec_sums == 4) hipLaunchKernelGGL((bn_sums_l<4>), grid, dim3(256), 0, rt().stream, g, x, save_mean, save_rstd, partial, rt().tickets, sums, dw, db, p);
+    else hipLaunchKernelGGL((bn_sums_l<1>), grid, dim3(256), 0, rt().stream, g, x, save_mean, save_rstd, partial, rt().tickets, sums, dw, db, p);
     hipError_t launched = hipGetLastError();
     if (launched == hipSuccess && dx != nullptr) {
         const int vec = bn_vec(C, L, x, g, dx);

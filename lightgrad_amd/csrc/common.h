@@ -17,10 +17,10 @@ struct Runtime {
     int         device = -1;
     hipStream_t stream = nullptr;
     int         compute_units = 0;
-    // arrival counters of the split-K GEMM (one per output tile): zero between launches - the workgroup that
-    // arrives last at a tile folds the partial products and resets the counter
-    int*        gemm_tickets = nullptr;
-    int         n_gemm_tickets = 0;
+    // arrival counters of every kernel that folds across workgroups inside its launch (split-K tiles, reductions, ...): zero
+    // between launches - the workgroup that arrives last folds and resets its counter.  Who counts where: handoff.h
+    int*        tickets = nullptr;
+    int         n_tickets = 0;
     // hand-off counters of the fused attention backward (attention.hip): two per (batch, head) pair, zero between launches
     int*        attn_flags = nullptr;
     int         n_attn_pairs = 1 << 14;

@@ -23,13 +23,14 @@
 //
 // dw: the output is tiny and the reduction long, so the reduction is split.  A workgroup owns a 32 x 32 output tile and one
 // slice of the positions, walked in chunks of 128 of which every wave takes 32; the four accumulators are summed through LDS
-// in wave order.  With more than one slice the workgroup publishes its partial tile (write-through stores, released), takes a
-// ticket for the tile (rt().gemm_tickets, zero between launches) and the last arriver folds the partials in slice order - the
-// hand-off of reduce.hip.  The slice count depends on the shape only, so a result is the same bits on every run.  db is the
-// column K of the tile: the gathered operand has a column of ones there, as in lg_gemm_rowsum_f32.
+// in wave order.  With more than one slice the workgroup publishes its partial tile, takes a ticket for the tile and the last
+// arriver folds the partials in slice order (handoff.h).  The slice count depends on the shape only, so a result is the same
+// bits on every run.  db is the column K of the tile: the gathered operand has a column of ones there, as in
+// lg_gemm_rowsum_f32.
 //
 // POOLING: one thread per output element (forward) / per input element (backward); see lghip.h for the semantics.
 #include "common.h"
+#include "handoff.h"
 #include "mfma_lds.h"
 
 namespace lg {
@@ -272,8 +273,7 @@ __global__ void __launch_bounds__(256) conv2d_igemm(const float* __restrict__ A,
                     if (slices == 1) store(rl, r, v);
                     else {
                         const int64_t tile = int64_t(blockIdx.y) * gridDim.x + blockIdx.x, tiles = int64_t(gridDim.x) * gridDim.y;
-                        __hip_atomic_store(partial + ((int64_t(slice) * tiles + tile) << 10) + rl * 32 + r, v, __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_AGENT);
+                        handoff::publish<float>(partial + ((int64_t(slice) * tiles + tile) << 10) + rl * 32 + r, v);
                     }
                 }
             }
@@ -284,20 +284,6 @@ __global__ void __launch_bounds__(256) conv2d_igemm(const float* __restrict__ A,
         const int64_t tile = int64_t(blockIdx.y) * gridDim.x + blockIdx.x, tiles = int64_t(gridDim.x) * gridDim.y;
         const int live = live_rows * live_cols;
         const int64_t pstride = tiles << 10;
-        auto arrive_last = [&](int* ticket, int expected) {           // after this thread's stores: release, then the ticket
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            __syncthreads();
-            if (tid == 0) {
-                const int order = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-                const int last = order == expected - 1;
-                if (last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                arrived_last = last;
-            }
-            __syncthreads();
-            const bool last = arrived_last != 0;
-            if (last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            return last;
-        };
         // fold `count` partial tiles from `src` on (pstride apart): thread (j, e) sums tiles j, j + J, ... of live element e in
         // ascending order, then the J sums are added in order of j.  J depends on the tile's live size and `count` only.
         auto fold_tiles = [&](const float* src, int count, auto&& sink) {
@@ -335,7 +321,7 @@ __global__ void __launch_bounds__(256) conv2d_igemm(const float* __restrict__ A,
                 }
             }
         };
-        if (!arrive_last(tickets + tile, slices)) return;
+        if (!handoff::arrive_workgroup(tickets + tile, slices, &arrived_last)) return;
         fold_tiles(partial + (tile << 10), slices, store);
     }
 }
@@ -456,7 +442,7 @@ extern "C" int lg_conv2d_dw_f32(const float* g, const float* x, float* dw, float
     int64_t cps = (chunks + kConvMaxSlices - 1) / kConvMaxSlices;
     if (cps < 2) cps = 2;
     int64_t slices = (chunks + cps - 1) / cps;
-    if (int64_t(tiles.x) * tiles.y > rt().n_gemm_tickets) { slices = 1; cps = chunks; }         // more tiles than tickets: no split
+    if (int64_t(tiles.x) * tiles.y > rt().n_tickets) { slices = 1; cps = chunks; }         // more tiles than tickets: no split
     LG_ARG(cps < (int64_t(1) << 31), "lg_conv2d_dw_f32: too many positions");
     p.chunks_per_slice = int(cps);
     float* partial = nullptr;
@@ -465,8 +451,8 @@ extern "C" int lg_conv2d_dw_f32(const float* g, const float* x, float* dw, float
         if (rc != LG_OK) return rc;
     }
     const dim3 grid(tiles.x, tiles.y, unsigned(slices));
-    if (relu_x) hipLaunchKernelGGL((conv2d_igemm<CONV_DW, true>), grid, dim3(256), 0, rt().stream, g, x, nullptr, dw, db, partial, rt().gemm_tickets, p);
-    else hipLaunchKernelGGL((conv2d_igemm<CONV_DW, false>), grid, dim3(256), 0, rt().stream, g, x, nullptr, dw, db, partial, rt().gemm_tickets, p);
+    if (relu_x) hipLaunchKernelGGL((conv2d_igemm<CONV_DW, true>), grid, dim3(256), 0, rt().stream, g, x, nullptr, dw, db, partial, rt().tickets, p);
+    else hipLaunchKernelGGL((conv2d_igemm<CONV_DW, false>), grid, dim3(256), 0, rt().stream, g, x, nullptr, dw, db, partial, rt().tickets, p);
     const hipError_t launched = hipGetLastError();
     if (partial != nullptr) {
         rc = lg_free(partial);                                          // stream-ordered: only later launches reuse the block

@@ -217,7 +217,7 @@ struct HeadChain {
     int*    status;
 };
 static const HeadChain*& pending_chain() { static const HeadChain* p = nullptr; return p; }     // set by lg_gemm_bias_head_fwd_f32 around its product
-constexpr int kChainTicketBase = 16384, kChainTicketStride = 32, kChainRowBlocks = 64;      // (pairs / groups count from 0, LayerNorm's queue from the middle)
+constexpr int kChainTicketBase = 16384, kChainTicketStride = 32, kChainRowBlocks = 64;      // (pairs / groups count from 0, the tail jobs from tickets_tail(): handoff.h)
 template <int OMAX, int PD>
 __global__ void __launch_bounds__(256) sgemm_bias_head_fwd(GemmArgs g, HeadChain c) {
     constexpr int BM = 64, BN = 32, BK = 32, WM = 2, WN = 1, KG = 2, XT = 0;
@@ -639,8 +639,8 @@ static bool pair_try_defer(GemmArgs& g, bool akc, bool bkc, bool va, bool vb, in
     // (three share a launch only as single matrices, the third with an N-contiguous B: what the MLP's backward produces)
     if (slot == 1 && f_form) fits = fits && batch == 1 && P.args[0].nwg == int64_t(P.args[0].tiles_m) * P.args[0].tiles_n * P.args[0].k_slices;
     const int64_t tiles = int64_t(g.tiles_m) * g.tiles_n * batch;
-    if (!fits || P.tiles + tiles > rt().n_gemm_tickets) return false;
-    g.tickets = rt().gemm_tickets + P.tiles;               // the products fold their K-slices with disjoint tickets
+    if (!fits || P.tiles + tiles > rt().n_tickets) return false;
+    g.tickets = rt().tickets + P.tiles;               // the products fold their K-slices with disjoint tickets
     P.tiles += tiles;
     if (s_form) P.second_bkc = bkc;
     P.is_s[slot] = s_form;
@@ -726,11 +726,11 @@ static bool group_try_defer(GemmArgs& g, bool akc, bool bkc, bool va, bool vb, i
         // an embedding scatter / LayerNorm gradient queued EARLIER writes the same buffer: everything queued leaves now, in call order
         rc = gemm_group_flush_pending();
         if (rc != LG_OK) return false;
-    } else if (clash || G.count == kGroupMax || G.tiles + tiles > rt().n_gemm_tickets / 2) {     // (the upper half: LayerNorm's queue)
+    } else if (clash || G.count == kGroupMax || G.tiles + tiles > tickets_group_end()) {
         rc = group_flush();
         if (rc != LG_OK) return false;
     }
-    g.tickets = rt().gemm_tickets + G.tiles;            // disjoint tickets: the products fold their K-slices side by side
+    g.tickets = rt().tickets + G.tiles;            // disjoint tickets: the products fold their K-slices side by side
     G.tiles += tiles;
     G.queued[G.count] = g;
     G.count += 1;
@@ -811,7 +811,7 @@ static int launch_config(const GemmArgs& base, bool akc, bool bkc, bool va, bool
     g.div_last_group = make_fastdiv(g.tiles_m % g.group_m ? g.tiles_m % g.group_m : g.group_m);
     g.div_batch_inner = make_fastdiv(g.batch_inner);
     g.W = nullptr;
-    g.tickets = rt().gemm_tickets;
+    g.tickets = rt().tickets;
 #ifdef LG_GEMM_TIMELINE
     {
         static unsigned long long* tl_buf = nullptr;
@@ -821,7 +821,7 @@ static int launch_config(const GemmArgs& base, bool akc, bool bkc, bool va, bool
         lg_debug_timeline_state(tl_buf, g.nwg, g.k_slices, int(tiles));
     }
 #endif
-    if (slices > 1 && tiles > rt().n_gemm_tickets) {       // more tiles than tickets: plenty of workgroups anyway
+    if (slices > 1 && tiles > rt().n_tickets) {       // more tiles than tickets: plenty of workgroups anyway
         slices = 1;
         g.k_per_slice = (g.K + BK - 1) / BK * BK;
         g.k_slices = 1;
@@ -1097,14 +1097,14 @@ extern "C" int lg_gemm_bias_head_fwd_f32(const float* x, int64_t ldx, const floa
     HeadChain c{};
     c.h.x = pre; c.h.w = w2; c.h.bias = b2; c.h.target = target; c.h.y = y; c.h.err = err; c.h.row_loss = row_loss; c.h.gpre = gpre; c.h.dx = dx;
     c.h.rows = rows; c.h.ldx = hidden; c.h.hidden = int(hidden); c.h.outs = int(outs); c.h.relu = relu;
-    c.tickets = rt().gemm_tickets + kChainTicketBase;
+    c.tickets = rt().tickets + kChainTicketBase;
     c.stride = kChainTicketStride;
     c.status = rt().status_dev;
     // one launch when the rows fit the row workgroups' registers and tickets, W2 fits the LDS the product's tile owns, and the product
     // resolves to the tile this launch is built on (gemm_impl's cost model: 64x32 with two K-groups); else two launches
     constexpr int kLdsFloats = gemm_lds_floats<64, 32, 32, true, true, 2>();
     const bool can_chain = chain != 0 && hidden <= 1024 && outs * hidden <= kLdsFloats && rows <= int64_t(kChainRowBlocks) * 64
-                           && kChainTicketBase + kChainRowBlocks * kChainTicketStride <= rt().n_gemm_tickets / 2 && aligned16(dx) && aligned16(gpre);
+                           && kChainTicketBase + kChainRowBlocks * kChainTicketStride <= tickets_group_end() && aligned16(dx) && aligned16(gpre);
     if (can_chain) pending_chain() = &c;
     const int rc = gemm_impl(0, 1, rows, hidden, d_in, x, ldx, 0, w1, ldw1, 0, pre, hidden, 0, 1, 0, b1);
     const bool chained = can_chain && pending_chain() == nullptr;

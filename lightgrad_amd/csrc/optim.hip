@@ -9,6 +9,7 @@
 // (the tape's `/` is `a * b**-1`, autograd/ops.py:30-36, hence the reciprocal-then-multiply form)
 #include "common.h"
 #include "adam_common.h"
+#include "handoff.h"
 #include <vector>
 #include <cmath>
 
@@ -259,11 +260,10 @@ __global__ void __launch_bounds__(256) adamw_multi_dev(float* __restrict__ p, co
 // out[0] = norm = sqrt(sum_i (g[i] * gscale)^2), out[1] = coef = min(1, max_norm / (norm + 1e-6)): what lg_adamw_multi_dev_f32
 // multiplies every gradient by.  Every workgroup strides over the bucket (float4 loads from the first 16-byte boundary on, the
 // up to three floats in front of it and behind the last float4 one by one), squares in fp32 like the expression `g * g`,
-// publishes ONE partial sum and takes a ticket; the workgroup that draws the last ticket folds the partials - in double, thread k
-// the k-th run of consecutive partials, then a fixed tree over the threads - writes norm and coef and resets the ticket (the
-// pattern of red_rows_split, reduce.hip).  Which workgroup folds depends on timing, WHAT it adds in which order does not: the
-// result is bit-reproducible from run to run.  No workgroup waits for another, no spin loop, no float atomics.
-// At most kNormMaxWgs workgroups: tickets on one address are served one after the other, 13 ns each (reduce.hip).
+// publishes ONE partial sum and takes a ticket (handoff.h); the workgroup that draws the last ticket folds the partials - in double,
+// thread k the k-th run of consecutive partials, then a fixed tree over the threads - and writes norm and coef.  Which workgroup
+// folds depends on timing, WHAT it adds in which order does not: the result is bit-reproducible from run to run.  No float atomics.
+// At most kNormMaxWgs workgroups: tickets on one address are served one after the other, 13 ns each (handoff.h).
 constexpr int kNormMaxWgs = LG_GRAD_NORM_PARTIALS;
 
 __device__ __forceinline__ float sumsq4(float4 x, float gscale, int scale_grad) {
@@ -305,16 +305,8 @@ __global__ void __launch_bounds__(256) grad_norm_clip(const float* __restrict__ 
         __syncthreads();
     }
     const int wgs = gridDim.x;
-    if (tid == 0) {
-        __hip_atomic_store(partial + blockIdx.x, float(fold[0]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int last = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == wgs - 1;
-        if (last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        arrived_last = last;
-    }
-    __syncthreads();
-    if (!arrived_last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (tid == 0) handoff::publish<float>(partial + blockIdx.x, float(fold[0]));
+    if (!handoff::arrive_thread0(ticket, wgs, &arrived_last)) return;
     const int per = (wgs + 255) / 256;          // <= kNormMaxWgs / 256 consecutive partials per thread, in index order
     double f = 0.0;
     for (int k = 0; k < per; ++k) {

@@ -16,6 +16,7 @@
 // (max/min exact incl. NaN propagation like np.max; sum is a tree sum in fp32).
 // The multi-pass LDS tree of opencl/kernels.py:344-501 is not reproduced.
 #include "common.h"
+#include "handoff.h"
 #include <cmath>
 #include <cstdlib>
 
@@ -86,12 +87,11 @@ __global__ void __launch_bounds__(256) red_rows_wave(const float* __restrict__ i
     if (lane == 0) out[row] = d.accumulate ? out[row] + acc : acc;
 }
 
-constexpr int kRowsFoldGroup = 32;     // segments per first-level ticket (<= 64: folded by one wave)
 template <int OP>
 __global__ void __launch_bounds__(256) red_rows_split(const float* __restrict__ in, float* out, float* partial, int* tickets,
                                                       RedDesc d, int64_t seg, int64_t tstride) {
     __shared__ float wsum[4];
-    __shared__ int arrived_last, arrived_last2;      // (one word per level: the first is still being read by slower wavefronts when the first wavefront moves on)
+    __shared__ int arrived_last[2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t row = blockIdx.y, split = blockIdx.x, splits = gridDim.x;
     const int64_t begin = split * seg;
@@ -120,61 +120,24 @@ __global__ void __launch_bounds__(256) red_rows_split(const float* __restrict__ 
     float acc = wave_reduce<OP>(Red<OP>::comb(acc0, acc1));
     if (lane == 0) wsum[wave] = acc;
     __syncthreads();
-    if (splits == 1) {
-        if (threadIdx.x == 0) {
-            const float v = Red<OP>::comb(Red<OP>::comb(wsum[0], wsum[1]), Red<OP>::comb(wsum[2], wsum[3]));
-            out[row] = d.accumulate ? out[row] + v : v;
-        }
-        return;
+    float v = Red<OP>::identity();
+    if (threadIdx.x == 0) v = Red<OP>::comb(Red<OP>::comb(wsum[0], wsum[1]), Red<OP>::comb(wsum[2], wsum[3]));
+    if (splits > 1) {
+        // several workgroups per row: the second pass of a two-launch reduction, inside this launch (handoff.h).  Two levels,
+        // because ONE ticket for all 768 workgroups of a full sum costs more than the launch it saves (64 MiB: 14.2 -> 23.9 us,
+        // profiles/r4/hbm_sum_single_ticket.txt).  partial: [row][split], then [row][group]; tickets: groups + 1 per row.
+        const int64_t groups = (splits + handoff::kFoldGroup - 1) / handoff::kFoldGroup;
+        if (!handoff::fold_two_level<Red<OP>, float>(v, partial + row * splits, partial + int64_t(gridDim.y) * splits + row * groups,
+                                                     tickets + row * (groups + 1) * tstride, tstride, split, splits, arrived_last,
+                                                     wave_reduce<OP>))
+            return;
     }
-    // several workgroups per row: the second pass of a two-launch reduction, inside this launch.  A workgroup publishes its
-    // partial (write-through, drained) and takes a ticket.  ONE ticket for all 768 workgroups of a full sum costs more than the
-    // launch it saves - atomics on one address are served one after the other, 13 ns each (64 MiB: 14.2 -> 23.9 us,
-    // profiles/r4/hbm_sum_single_ticket.txt) - so the fold has two levels: groups of kRowsFoldGroup consecutive segments with a
-    // ticket each (on cache lines of their own); a group's last arriver folds the group and takes the row's ticket; the last
-    // of those folds the groups.  Fixed trees at both levels: bit-reproducible.
-    const int64_t groups = (splits + kRowsFoldGroup - 1) / kRowsFoldGroup, grp = split / kRowsFoldGroup;
-    const int64_t in_group = (grp == groups - 1) ? splits - grp * kRowsFoldGroup : kRowsFoldGroup;
-    float* const partial2 = partial + int64_t(gridDim.y) * splits;              // [row][group]
-    int* const t1 = tickets + (row * (groups + 1) + grp) * tstride;
-    int* const t2 = tickets + (row * (groups + 1) + groups) * tstride;
-    if (threadIdx.x == 0) {
-        const float v = Red<OP>::comb(Red<OP>::comb(wsum[0], wsum[1]), Red<OP>::comb(wsum[2], wsum[3]));
-        __hip_atomic_store(partial + row * splits + split, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int last = __hip_atomic_fetch_add(t1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == int(in_group) - 1;
-        if (last) __hip_atomic_store(t1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        arrived_last = last;
-    }
-    __syncthreads();
-    if (!arrived_last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (wave == 0) {                                          // in_group <= 64 partials: one per lane of the first wave
-        const float x = lane < in_group ? __hip_atomic_load(partial + row * splits + grp * kRowsFoldGroup + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                        : Red<OP>::identity();
-        const float v = wave_reduce<OP>(x);
-        if (lane == 0) {
-            __hip_atomic_store(partial2 + row * groups + grp, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            const int last = __hip_atomic_fetch_add(t2, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == int(groups) - 1;
-            if (last) __hip_atomic_store(t2, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            arrived_last2 = last;
-        }
-    }
-    __syncthreads();
-    if (!arrived_last2 || wave != 0) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    float f = Red<OP>::identity();
-    for (int64_t r = lane; r < groups; r += 64)
-        f = Red<OP>::comb(f, __hip_atomic_load(partial2 + row * groups + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    f = wave_reduce<OP>(f);
-    if (lane == 0) out[row] = d.accumulate ? out[row] + f : f;
+    if (threadIdx.x == 0) out[row] = d.accumulate ? out[row] + v : v;
 }
 
 // ---- cols / general: one thread per output element --------------------------------------------
-// gridDim.y > 1: the reduced range is split over blockIdx.y.  Each split publishes its partial (write-through store,
-// drained), takes a ticket for its block of 256 outputs, and the workgroup that arrives last folds the partials in
-// split order - the in-launch form of a second pass (cdna_hip_programming.md, in-launch split-K recipe).
+// gridDim.y > 1: the reduced range is split over blockIdx.y, one ticket per block of 256 outputs, and the workgroup that
+// arrives last folds the partials in split order (handoff.h).
 template <int OP>
 __global__ void __launch_bounds__(256) red_cols(const float* __restrict__ in, float* out, float* partial, int* tickets,
                                                 RedDesc d, int64_t chunk) {
@@ -221,20 +184,9 @@ __global__ void __launch_bounds__(256) red_cols(const float* __restrict__ in, fl
     float v = Red<OP>::comb(Red<OP>::comb(a0, a1), Red<OP>::comb(a2, a3));
     const int splits = gridDim.y;
     if (splits > 1) {
-        __hip_atomic_store(partial + split * d.n_out + o, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
         __shared__ int arrived_last;
-        if (threadIdx.x == 0) {
-            int* ticket = tickets + blockIdx.x;
-            const int order = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int last = order == splits - 1;
-            if (last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            arrived_last = last;
-        }
-        __syncthreads();
-        if (!arrived_last) return;
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        handoff::publish<float>(partial + split * d.n_out + o, v);
+        if (!handoff::arrive_workgroup(tickets + blockIdx.x, splits, &arrived_last)) return;
         // 8 partials in flight per thread (their loads cross XCDs: ~1 us each), combined in a fixed order
         float f[8];
 #pragma unroll
@@ -315,19 +267,8 @@ __global__ void __launch_bounds__(256) red_cols_tile(const float* __restrict__ i
     }
     const int splits = gridDim.y;
     if (splits > 1) {
-        if (tid < 64 && o < n_out) __hip_atomic_store(partial + int64_t(blockIdx.y) * n_out + o, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) {
-            int* ticket = tickets + blockIdx.x;
-            const int order = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int last = order == splits - 1;
-            if (last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            arrived_last = last;
-        }
-        __syncthreads();
-        if (!arrived_last) return;
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (tid < 64 && o < n_out) handoff::publish<float>(partial + int64_t(blockIdx.y) * n_out + o, v);
+        if (!handoff::arrive_workgroup(tickets + blockIdx.x, splits, &arrived_last)) return;
         if (tid < 64 && o < n_out) {
             float x[16];                                             // splits <= 16: every partial of this column in flight at once
 #pragma unroll
@@ -401,20 +342,18 @@ static int run_reduce(const float* in, float* out, RedDesc& d) {
             hipLaunchKernelGGL((red_rows_split<OP>), dim3(1, unsigned(d.n_out)), dim3(256), 0, s, in, out, nullptr, nullptr, d, seg, int64_t(1));
             return LG_OK;
         }
-        const int64_t groups = (splits + kRowsFoldGroup - 1) / kRowsFoldGroup, n_tickets = d.n_out * (groups + 1);
-        if (n_tickets > rt().n_gemm_tickets) {   // (n_out < 256 on this path and a few dozen groups: the pool is far larger)
+        const int64_t groups = (splits + handoff::kFoldGroup - 1) / handoff::kFoldGroup, n_tickets = d.n_out * (groups + 1);
+        if (n_tickets > rt().n_tickets) {   // (n_out < 256 on this path and a few dozen groups: the pool is far larger)
             note_plan(PLAN_ROWS_WAVE, 1, 0, d.nk, d.nr, in);
             hipLaunchKernelGGL((red_rows_wave<OP>), dim3(unsigned((d.n_out + 3) / 4)), dim3(256), 0, s, in, out, d);
             return LG_OK;
         }
-        int64_t tstride = rt().n_gemm_tickets / n_tickets;          // tickets on cache lines of their own while the pool allows
-        if (tstride > 32) tstride = 32;
         float* partial = nullptr;
         int rc = lg_malloc(reinterpret_cast<void**>(&partial), size_t(d.n_out * (splits + groups)) * sizeof(float));
         if (rc != LG_OK) return rc;
         note_plan(PLAN_ROWS_SPLIT, splits, groups, d.nk, d.nr, in);
         hipLaunchKernelGGL((red_rows_split<OP>), dim3(unsigned(splits), unsigned(d.n_out)), dim3(256), 0, s, in, out, partial,
-                           rt().gemm_tickets, d, seg, tstride);
+                           rt().tickets, d, seg, int64_t(ticket_stride(n_tickets)));
         return lg_free(partial);   // stream-ordered: the block is only reused by later launches
     }
 
@@ -433,7 +372,7 @@ static int run_reduce(const float* in, float* out, RedDesc& d) {
         if (splits < 1) splits = 1;
         int64_t chunk = ((d.rlen + splits - 1) / splits + 15) & ~int64_t(15);
         splits = (d.rlen + chunk - 1) / chunk;
-        if (bx <= rt().n_gemm_tickets && bx < (int64_t(1) << 31)) {
+        if (bx <= rt().n_tickets && bx < (int64_t(1) << 31)) {
             float* partial = nullptr;
             if (splits > 1) {
                 int rc = lg_malloc(reinterpret_cast<void**>(&partial), size_t(d.n_out * splits) * sizeof(float));
@@ -441,7 +380,7 @@ static int run_reduce(const float* in, float* out, RedDesc& d) {
             }
             note_plan(PLAN_COLS_TILE, splits, 0, d.nk, d.nr, in);
             hipLaunchKernelGGL((red_cols_tile<OP>), dim3(unsigned(bx), unsigned(splits)), dim3(256), 0, s, in, out, partial,
-                               rt().gemm_tickets, d.n_out, d.rlen, d.rstride[0], chunk, d.accumulate);
+                               rt().tickets, d.n_out, d.rlen, d.rstride[0], chunk, d.accumulate);
             return splits > 1 ? lg_free(partial) : LG_OK;
         }
     }
@@ -463,7 +402,7 @@ static int run_reduce(const float* in, float* out, RedDesc& d) {
     int64_t chunk = (d.rlen + splits - 1) / splits;
     splits = (d.rlen + chunk - 1) / chunk;
     if (blocks_x >= (int64_t(1) << 31)) { set_error("lg_reduce: output too large"); return LG_EINVAL; }
-    if (splits > 1 && blocks_x > rt().n_gemm_tickets) { splits = 1; chunk = d.rlen; }     // more output blocks than tickets
+    if (splits > 1 && blocks_x > rt().n_tickets) { splits = 1; chunk = d.rlen; }     // more output blocks than tickets
     if (splits == 1) {
         note_plan(PLAN_COLS, 1, 0, d.nk, d.nr, in);
         hipLaunchKernelGGL((red_cols<OP>), dim3(unsigned(blocks_x), 1), dim3(256), 0, s, in, out, nullptr, nullptr, d, chunk);
@@ -474,7 +413,7 @@ static int run_reduce(const float* in, float* out, RedDesc& d) {
     if (rc != LG_OK) return rc;
     note_plan(PLAN_COLS, splits, 0, d.nk, d.nr, in);
     hipLaunchKernelGGL((red_cols<OP>), dim3(unsigned(blocks_x), unsigned(splits)), dim3(256), 0, s, in, out, partial,
-                       rt().gemm_tickets, d, chunk);
+                       rt().tickets, d, chunk);
     return lg_free(partial);
 }
 

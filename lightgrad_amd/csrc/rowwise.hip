@@ -475,26 +475,16 @@ __global__ void __launch_bounds__(256) cross_entropy_wide_ignore(const float* __
 // back-to-back launches (tools/ce_bench.py): two-pass kernel 72.7 us, this one 58.6 us = 4.3 TB/s of logits read + gradient
 // written (61.4 without the line-aligned walk below).  Measured and not kept: a 2^x-based exp for non-positive arguments, 8
 // instructions instead of ~25 - 70.8 us, SLOWER: the kernel is bound by its memory phases, not by the exps.
-// mean over rows inside the held launch (saves the reduction + scaling launches behind it): drain, take a ticket, the last
-// workgroup sums the row losses in a fixed order - thread t takes rows t, t + THREADS, ...; waves, then the workgroup, in
+// mean over rows inside the held launch (saves the reduction + scaling launches behind it): the last workgroup to arrive
+// (handoff.h) sums the row losses in a fixed order - thread t takes rows t, t + THREADS, ...; waves, then the workgroup, in
 // index order - and multiplies by 1/rows like the two-kernel form.  Every thread of the workgroup calls it; red_s is free.
 // IGN: the factor is what the count launch left in mean_out[0].
 template <bool IGN, int THREADS>
 __device__ __forceinline__ void cross_entropy_held_mean(const float* nll, float inv_rows, float* mean_out, int* ticket, float* red_s) {
     constexpr int WAVES = THREADS / 64;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
     __shared__ int arrived_last;
-    if (tid == 0) {
-        const int order = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = order == int(gridDim.x) - 1;
-        if (last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        arrived_last = last;
-    }
-    __syncthreads();
-    if (!arrived_last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (!handoff::arrive_workgroup(ticket, int(gridDim.x), &arrived_last)) return;
     float total = 0.f;
     for (int64_t i = tid; i < int64_t(gridDim.x); i += THREADS)
         total += __hip_atomic_load(nll + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -604,7 +594,7 @@ __device__ __forceinline__ void cross_entropy_held_body(const float* __restrict_
         __builtin_amdgcn_sched_barrier(0);
     }
     // per-row losses are published write-through: the workgroup that arrives LAST reads all of them for the mean (below)
-    if (p_label >= 0.0f || p_label != p_label) __hip_atomic_store(nll + row, -logf(p_label), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (p_label >= 0.0f || p_label != p_label) handoff::publish<float>(nll + row, -logf(p_label));
     if (mean_out == nullptr) return;
     cross_entropy_held_mean<IGN, THREADS>(nll, inv_rows, mean_out, ticket, red_s);
 }
@@ -629,7 +619,7 @@ static void launch_cross_entropy_held(const float* logits, const LabelT* labels,
                                       float inv_rows, float* mean_out, int64_t ignore = 0, const int64_t* n_valid = nullptr) {
     const dim3 grid{unsigned(rows)};
     hipStream_t s = rt().stream;
-    int* ticket = rt().gemm_tickets + rt().n_gemm_tickets - 1;          // the last slot: nobody else counts that far
+    int* ticket = ticket_of_loss();
     if (n_valid != nullptr) {
         if (cols + 31 <= 1024 * 8)       hipLaunchKernelGGL((cross_entropy_held_ignore<LabelT, 8, 1024>), grid, dim3(1024), 0, s, logits, labels, dlogits, nll, cols, rt().status_dev, mean_out, ticket, ignore);
         else if (cols + 31 <= 1024 * 16) hipLaunchKernelGGL((cross_entropy_held_ignore<LabelT, 16, 1024>), grid, dim3(1024), 0, s, logits, labels, dlogits, nll, cols, rt().status_dev, mean_out, ticket, ignore);
@@ -1136,7 +1126,7 @@ extern "C" int lg_layernorm_param_grads_f32(const float* g, const float* xhat, f
         if (splits * 16 > rows) splits = rows / 16;            // ... with at least 16 rows each
         if (splits > 32) splits = 32;                          // ... and a short fold
         if (splits < 1) splits = 1;
-        if (blocks_x > rt().n_gemm_tickets / 2) splits = 1;
+        if (blocks_x > tickets_tail_count()) splits = 1;
     }
     const int64_t chunk = rows > 0 ? (rows + splits - 1) / splits : 1;
     splits = rows > 0 ? (rows + chunk - 1) / chunk : 1;
@@ -1151,23 +1141,23 @@ extern "C" int lg_layernorm_param_grads_f32(const float* g, const float* xhat, f
     }
     // While a gradient group is open (lg_gemm_group_begin) the launch is queued with the group's other work: the parameter
     // gradients of all LayerNorms of a backward pass go out as ONE launch (7.5 us each alone, most of it launch + hand-off).
-    // Tickets: the upper half of the array, the GEMM group counts from the bottom.
+    // Tickets: the tail region of the pool (handoff.h); the GEMM group counts from the bottom.
     LnGroupState& S = ln_group();
     const bool queue = gemm_group_is_open() && blocks_x <= 64 && rows > 0;
     if (queue) {
         bool clash = false;
         for (int i = 0; i < S.count; ++i) clash = clash || S.grp.ln.e[i].dw == dw || S.grp.ln.e[i].db == db;
-        if (clash || S.count == kLnGroupMax || S.tickets + blocks_x > rt().n_gemm_tickets / 2 - 1) {      // (the very last slot: the loss kernel's)
+        if (clash || S.count == kLnGroupMax || S.tickets + blocks_x > tickets_tail_count()) {
             const int rc = gemm_group_flush_pending();      // queued GEMM products first, then this group: call order (see lg_scatter_add_rows_f32)
             if (rc != LG_OK) return rc;
         }
-        a.tickets = rt().gemm_tickets + rt().n_gemm_tickets / 2 + S.tickets;
+        a.tickets = tickets_tail() + S.tickets;
         S.tickets += blocks_x;
         S.grp.ln.e[S.count++] = a;
         note_rowwise(RW_PARAM_GRADS, splits, chunk, 1);
         return LG_OK;
     }
-    a.tickets = rt().gemm_tickets + rt().n_gemm_tickets / 2;
+    a.tickets = tickets_tail();
     note_rowwise(RW_PARAM_GRADS, splits, chunk);
     hipLaunchKernelGGL(layernorm_param_grads, dim3(unsigned(blocks_x), unsigned(splits)), dim3(256), 0, rt().stream, a);
     LG_CHECK_LAUNCH();

@@ -78,7 +78,7 @@ int check_device_status(const char* who) {
     if (status & LG_STATUS_HANDOFF_TIMEOUT) {
         // (attention.hip's backward, gemm.hip's product + head rows.  The tickets such a launch leaves behind are not at zero: reset
         //  the pool so that later launches start clean - the stream is idle here, status is only looked at after a synchronisation)
-        if (R.gemm_tickets) (void)hipMemset(R.gemm_tickets, 0, size_t(R.n_gemm_tickets) * sizeof(int));
+        if (R.tickets) (void)hipMemset(R.tickets, 0, size_t(R.n_tickets) * sizeof(int));
         set_error("%s: a launch whose workgroups wait for other workgroups of the same launch (the attention backward, the hidden layer's "
                   "product followed by the output layer's rows) gave up waiting (2 s; device status %d): its results are not to be trusted",
                   who, status);
@@ -187,9 +187,9 @@ int lg_init(int device) {
     hipDeviceProp_t prop;
     LG_HIP(hipGetDeviceProperties(&prop, device));
     R.compute_units = prop.multiProcessorCount;
-    R.n_gemm_tickets = 1 << 16;
-    LG_HIP(hipMalloc(reinterpret_cast<void**>(&R.gemm_tickets), size_t(R.n_gemm_tickets) * sizeof(int)));
-    LG_HIP(hipMemset(R.gemm_tickets, 0, size_t(R.n_gemm_tickets) * sizeof(int)));    // synchronous: ordered before any launch
+    R.n_tickets = 1 << 16;
+    LG_HIP(hipMalloc(reinterpret_cast<void**>(&R.tickets), size_t(R.n_tickets) * sizeof(int)));
+    LG_HIP(hipMemset(R.tickets, 0, size_t(R.n_tickets) * sizeof(int)));    // synchronous: ordered before any launch
     LG_HIP(hipMalloc(reinterpret_cast<void**>(&R.attn_flags), size_t(R.n_attn_pairs) * 2 * sizeof(int)));
     LG_HIP(hipMemset(R.attn_flags, 0, size_t(R.n_attn_pairs) * 2 * sizeof(int)));
     LG_HIP(hipHostMalloc(reinterpret_cast<void**>(&R.status_host), 64, hipHostMallocMapped));

@@ -4,13 +4,14 @@
 // beside MFMA-bound work, 34 us of tiny-BERT's backward that no longer wait for the 102 us in front of them).
 #pragma once
 #include "common.h"
+#include "handoff.h"
 
 namespace lg {
 
 // ---- LayerNorm parameter gradients: dw[c] = sum_r g[r][c] * xhat[r][c], db[c] = sum_r g[r][c] -------------------
-// one thread per column (coalesced along the row), the rows split over blockIdx.y; with more than one split the
-// partial sums are published write-through, a per-column-block ticket elects the last workgroup, which folds them in
-// split order (cdna_hip_programming.md, in-launch split-K recipe).  Replaces mul + two column sums + two adds.
+// one thread per column (coalesced along the row), the rows split over blockIdx.y; with more than one split a
+// per-column-block ticket elects the last workgroup, which folds the partial sums in split order (handoff.h).
+// Replaces mul + two column sums + two adds.
 struct LnParamGrads {
     const float* g;
     const float* xhat;
@@ -53,21 +54,10 @@ __device__ __forceinline__ void layernorm_param_grads_body(const LnParamGrads& a
     }
     float vw = (sw[0] + sw[1]) + (sw[2] + sw[3]), vb = (sb[0] + sb[1]) + (sb[2] + sb[3]);
     if (splits > 1) {
-        __hip_atomic_store(partial + (split * 2 + 0) * cols + c, vw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(partial + (split * 2 + 1) * cols + c, vb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
         __shared__ int arrived_last;
-        if (threadIdx.x == 0) {
-            int* ticket = a.tickets + block_x;
-            const int order = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int last = order == int(splits) - 1;
-            if (last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            arrived_last = last;
-        }
-        __syncthreads();
-        if (!arrived_last) return;
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        handoff::publish<float>(partial + (split * 2 + 0) * cols + c, vw);
+        handoff::publish<float>(partial + (split * 2 + 1) * cols + c, vb);
+        if (!handoff::arrive_workgroup(a.tickets + block_x, int(splits), &arrived_last)) return;
         vw = vb = 0.f;
         int64_t s0 = 0;
         for (; s0 + 3 < splits; s0 += 4) {

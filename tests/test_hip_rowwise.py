@@ -10,7 +10,7 @@ for bit; real-valued outputs are judged PER ROW against float64 by the rule of t
 most max(1e-5, twice the float32 numpy composite's distance on that row) - so that one bad row cannot hide in the array.
 
 Two branches of the dispatch are not reached by any case, and no case is contorted to reach them: `blocks_x >
-n_gemm_tickets / 2` in the parameter gradients (more than 8 million columns) and row counts at or above 2**31.
+tickets_tail_count()` in the parameter gradients (more than 8 million columns) and row counts at or above 2**31.
 
 The queued forms: a bracket that holds ONE weight-gradient product launches it alone and the jobs behind it; with two products
 the jobs ride as extra workgroups of the products' launch.  Both are run."""
