@@ -278,6 +278,18 @@ int lg_gemm_f32(int transA, int transB, int64_t M, int64_t N, int64_t K,
                 float* C, int64_t ldc, int64_t strideC,
                 int64_t batch, int accumulate);
 
+/* What the most recent fp32 product (any lg_gemm_*_f32 entry above or below, lg_gemm_bf16_f32 excepted) of the calling thread
+ * resolved to: host bookkeeping for tests, recorded once the slice count is final; no device work, no effect on any launch.
+ *   out = {BM, BN, BK, KG, k_slices, k_per_slice, flags, route}
+ * BM x BN: the workgroup's tile of C; BK: k-values per K-group and K-step; KG: K-groups inside the workgroup (a K-step stages
+ * BK * KG k-values).  BM = -1 before any product; BM = 0 (and everything else 0) when the call launched no GEMM kernel (M, N or
+ * batch of 0; K = 0, which fills C).  k_slices: workgroups along K per tile as launched (1 = no cross-workgroup split), each over
+ * k_per_slice k-values.  flags: bit 0 A K-contiguous (transA = 0), bit 1 B K-contiguous (transB = 1), bit 2 / 3 A / B staged as
+ * float4, bit 4 the wave-private K loop ran.  route: 0 launched on its own, 1 deferred into a lg_gemm_pair_* bracket, 2 queued
+ * in a lg_gemm_group_* bracket (either may still re-tune its slice count when it leaves), 3 the chained head launch of
+ * lg_gemm_bias_head_fwd_f32. */
+int lg_gemm_last_plan(int32_t out[8]);
+
 /* The same product with both operands rounded to bfloat16 (nearest, ties to even; NaN, +-Inf and the sign of zero kept, a
  * finite value beyond the largest bfloat16 becomes +-Inf) on their way into the matrix cores: C (+)= r(op(A)) @ r(op(B)) [+ bias].
  * Products of two bfloat16 values are exact in fp32; the sums are formed in fp32 on v_mfma_f32_32x32x16_bf16.  Operands,

@@ -78,6 +78,7 @@ PROTOTYPES = {
     "lg_top1_count_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int, c_int, c_int64, c_int, c_void_p]),
     "lg_gemm_f32": (c_int, [c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64,
                             c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int]),
+    "lg_gemm_last_plan": (c_int, [POINTER(ctypes.c_int32)]),
     "lg_gemm_bf16_f32": (c_int, [c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                                  c_void_p, c_int]),
     "lg_bf16_round_f32": (c_int, [c_void_p, c_void_p, c_int64]),

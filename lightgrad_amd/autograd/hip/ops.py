@@ -1679,6 +1679,16 @@ def conv2d_last_plan():
             "dw_slices": out[4], "relu_x": bool(out[5])}
 
 
+def gemm_last_plan():
+    """{tile, bk, kg, k_slices, k_per_slice, a_kc, b_kc, va, vb, wave_private, route} of the most recent fp32 product of this
+    thread (lghip.h: lg_gemm_last_plan); tile is None before any product and (0, 0) when the call launched no GEMM kernel"""
+    out = (ctypes.c_int32 * 8)()
+    _l.check(_l.lib().lg_gemm_last_plan(out))
+    return {"tile": (out[0], out[1]) if out[0] >= 0 else None, "bk": out[2], "kg": out[3], "k_slices": out[4],
+            "k_per_slice": out[5], "a_kc": bool(out[6] & 1), "b_kc": bool(out[6] & 2), "va": bool(out[6] & 4),
+            "vb": bool(out[6] & 8), "wave_private": bool(out[6] & 16), "route": ("own", "pair", "group", "chain")[out[7]]}
+
+
 def _pool2d(name, op, composite):
     def fused(t, kernel):
         if not isinstance(kernel, (tuple, list)) or len(kernel) != 2 or t._dtype != _F32 or len(t._shape) < 2:

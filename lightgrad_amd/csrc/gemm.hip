@@ -444,8 +444,13 @@ __global__ void __launch_bounds__(256) sgemm_group_wgrad(GemmGroup grp) {
 #undef LG_TILE_OWNS_LDS
 }
 
+// lg_gemm_last_plan: what the most recent product of the calling thread resolved to - host bookkeeping written by launch_config
+// once the slice count is final (gemm_impl for the calls that launch no GEMM kernel); the tests pin every case to its tile with it
+static thread_local int32_t g_gemm_plan[8] = {-1, 0, 0, 0, 0, 0, 0, 0};
+
+// true: the wave-private K loop was launched
 template <int BM, int BN, int BK, int WM, int WN, bool AKC, bool BKC, int KG>
-static void launch_layout(const GemmArgs& g, bool va, bool vb) {
+static bool launch_layout(const GemmArgs& g, bool va, bool vb) {
     dim3 grid(g.nwg), block(WM * WN * KG * 64);
     hipStream_t s = rt().stream;
     // K-tiles in flight between global memory and LDS.  The large tiles ran with ONE until the end of round 3 ("enough MFMAs per
@@ -472,24 +477,25 @@ static void launch_layout(const GemmArgs& g, bool va, bool vb) {
             constexpr int WPD = kWavePrivatePrefetch;
             if (g.multi) hipLaunchKernelGGL((sgemm_mfma<BM, BN, BK, WM, WN, true, true, true, true, WPD, KG, 1, true>), grid, block, 0, s, g);
             else         hipLaunchKernelGGL((sgemm_mfma<BM, BN, BK, WM, WN, true, true, true, true, WPD, KG, 0, true>), grid, block, 0, s, g);
-            return;
+            return true;
         }
     }
     if constexpr (kHasExtras<BM, BN>) {
         // (the entry points have checked: multi comes K-contiguous on both sides, seg_k with an N-contiguous B, float4 staging)
-        if constexpr (AKC && BKC)  { if (g.multi) { hipLaunchKernelGGL((sgemm_mfma<BM, BN, BK, WM, WN, AKC, BKC, true, true, PD, KG, 1>), grid, block, 0, s, g); return; } }
-        if constexpr (AKC && !BKC) { if (g.seg_k) { hipLaunchKernelGGL((sgemm_mfma<BM, BN, BK, WM, WN, AKC, BKC, true, true, PD, KG, 2>), grid, block, 0, s, g); return; } }
+        if constexpr (AKC && BKC)  { if (g.multi) { hipLaunchKernelGGL((sgemm_mfma<BM, BN, BK, WM, WN, AKC, BKC, true, true, PD, KG, 1>), grid, block, 0, s, g); return false; } }
+        if constexpr (AKC && !BKC) { if (g.seg_k) { hipLaunchKernelGGL((sgemm_mfma<BM, BN, BK, WM, WN, AKC, BKC, true, true, PD, KG, 2>), grid, block, 0, s, g); return false; } }
     }
     if constexpr (!kHasExtras<BM, BN>) {
         // the 256x256 tile exists in its float4 / gather form only (gemm_impl: va is always set, vb unless row sums ride along -
         // and those never take this tile)
         hipLaunchKernelGGL((sgemm_mfma<BM, BN, BK, WM, WN, AKC, BKC, true, true, PD, KG>), grid, block, 0, s, g);
-        return;
+        return false;
     }
     if (va && vb)  hipLaunchKernelGGL((sgemm_mfma<BM, BN, BK, WM, WN, AKC, BKC, true, true, PD, KG>), grid, block, 0, s, g);
     else if (va)   hipLaunchKernelGGL((sgemm_mfma<BM, BN, BK, WM, WN, AKC, BKC, true, false, 1, KG>), grid, block, 0, s, g);
     else if (vb)   hipLaunchKernelGGL((sgemm_mfma<BM, BN, BK, WM, WN, AKC, BKC, false, true, 1, KG>), grid, block, 0, s, g);
     else           hipLaunchKernelGGL((sgemm_mfma<BM, BN, BK, WM, WN, AKC, BKC, false, false, 1, KG>), grid, block, 0, s, g);
+    return false;
 }
 
 // ---- two products in one launch (lg_gemm_pair_begin / _end) --------------------------------------------------------------
@@ -828,6 +834,11 @@ static int launch_config(const GemmArgs& base, bool akc, bool bkc, bool va, bool
         g.nwg = int(tiles);
         g.div_slices = make_fastdiv(1);
     }
+    {
+        const int32_t plan[8] = {BM, BN, BK, KG, int32_t(g.k_slices), int32_t(g.k_per_slice),
+                                 (akc ? 1 : 0) | (bkc ? 2 : 0) | (va ? 4 : 0) | (vb ? 8 : 0), 0};
+        for (int i = 0; i < 8; ++i) g_gemm_plan[i] = plan[i];
+    }
     if (slices > 1) {
         int rc = lg_malloc(reinterpret_cast<void**>(&g.W), size_t(tiles * slices) * BM * BN * sizeof(float));
         if (rc != LG_OK) return rc;
@@ -835,9 +846,9 @@ static int launch_config(const GemmArgs& base, bool akc, bool bkc, bool va, bool
     // (measured and not kept: two wave groups per single-accumulator tile, each on half of every K-tile - the loop is bound
     // by the workgroup barrier, which more waves of the SAME workgroup do not hide: 25.9 -> 25.4 us at 1024x512x1024)
     if constexpr (BM == 64 && BN == 64 && WM == 2 && WN == 2 && KG == 1) {
-        if (pair_try_defer(g, akc, bkc, va, vb, batch)) return LG_OK;
+        if (pair_try_defer(g, akc, bkc, va, vb, batch)) { g_gemm_plan[7] = 1; return LG_OK; }
         int grc = LG_OK;
-        if (group_try_defer(g, akc, bkc, va, vb, batch, grc)) return LG_OK;
+        if (group_try_defer(g, akc, bkc, va, vb, batch, grc)) { g_gemm_plan[7] = 2; return LG_OK; }
         if (grc != LG_OK) return grc;
     }
     if (pair_state().count && pair_state().active != 3) {      // something else inside a pair bracket: what is pending goes first
@@ -859,13 +870,16 @@ static int launch_config(const GemmArgs& base, bool akc, bool bkc, bool va, bool
             else if (omax == 8)  hipLaunchKernelGGL((sgemm_bias_head_fwd<8, PD>), grid, block, 0, rt().stream, g, c);
             else if (omax == 10) hipLaunchKernelGGL((sgemm_bias_head_fwd<10, PD>), grid, block, 0, rt().stream, g, c);
             else                 hipLaunchKernelGGL((sgemm_bias_head_fwd<16, PD>), grid, block, 0, rt().stream, g, c);
+            g_gemm_plan[7] = 3;
             return LG_OK;
         }
     }
-    if (akc && bkc) launch_layout<BM, BN, BK, WM, WN, true, true, KG>(g, va, vb);
-    else if (akc)   launch_layout<BM, BN, BK, WM, WN, true, false, KG>(g, va, vb);
-    else if (bkc)   launch_layout<BM, BN, BK, WM, WN, false, true, KG>(g, va, vb);
-    else            launch_layout<BM, BN, BK, WM, WN, false, false, KG>(g, va, vb);
+    bool wave_private;
+    if (akc && bkc) wave_private = launch_layout<BM, BN, BK, WM, WN, true, true, KG>(g, va, vb);
+    else if (akc)   wave_private = launch_layout<BM, BN, BK, WM, WN, true, false, KG>(g, va, vb);
+    else if (bkc)   wave_private = launch_layout<BM, BN, BK, WM, WN, false, true, KG>(g, va, vb);
+    else            wave_private = launch_layout<BM, BN, BK, WM, WN, false, false, KG>(g, va, vb);
+    if (wave_private) g_gemm_plan[6] |= 16;
     if (slices > 1) return lg_free(g.W);     // stream-ordered: reused only by later launches
     return LG_OK;
 }
@@ -873,6 +887,8 @@ static int launch_config(const GemmArgs& base, bool akc, bool bkc, bool va, bool
 }  // namespace lg
 
 using namespace lg;
+
+static void note_no_gemm_kernel() { for (int i = 0; i < 8; ++i) lg::g_gemm_plan[i] = 0; }
 
 static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K,
                      const float* A, int64_t lda, int64_t strideA,
@@ -885,7 +901,7 @@ static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K,
     LG_REQUIRE_INIT();
     LG_ARG(M >= 0 && N >= 0 && K >= 0 && batch >= 0, "lg_gemm_f32: negative extent (M=%lld N=%lld K=%lld batch=%lld)",
            (long long)M, (long long)N, (long long)K, (long long)batch);
-    if (M == 0 || N == 0 || batch == 0) return LG_OK;
+    if (M == 0 || N == 0 || batch == 0) { note_no_gemm_kernel(); return LG_OK; }
     LG_ARG(A && B && C, "lg_gemm_f32: NULL operand");
     LG_ARG(lda >= (transA ? M : K) && ldb >= (transB ? K : N) && ldc >= N,
            "lg_gemm_f32: leading dimension too small (lda=%lld ldb=%lld ldc=%lld for M=%lld N=%lld K=%lld tA=%d tB=%d)",
@@ -895,6 +911,7 @@ static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K,
            "lg_gemm_addend_f32: one matrix product with K > 0, no accumulate / row sums, ldadd >= N");
     if (K == 0) {
         LG_ARG(bias == nullptr, "lg_gemm_bias_f32: K == 0 with a bias is not supported");
+        note_no_gemm_kernel();
         if (rowsum && !rowsum_accumulate) {
             int64_t shape1[1] = {M}, st1[1] = {1};
             int rc1 = lg_fill_strided(4, 1, shape1, rowsum, st1, 0);
@@ -1064,6 +1081,12 @@ extern "C" int lg_gemm_f32(int transA, int transB, int64_t M, int64_t N, int64_t
                            float* C, int64_t ldc, int64_t strideC,
                            int64_t batch, int accumulate) {
     return gemm_impl(transA, transB, M, N, K, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, batch, accumulate, nullptr);
+}
+
+extern "C" int lg_gemm_last_plan(int32_t out[8]) {
+    LG_ARG(out != nullptr, "lg_gemm_last_plan: NULL pointer");
+    for (int i = 0; i < 8; ++i) out[i] = lg::g_gemm_plan[i];
+    return LG_OK;
 }
 
 extern "C" int lg_gemm_bias_f32(int transA, int transB, int64_t M, int64_t N, int64_t K,

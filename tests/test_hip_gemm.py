@@ -35,6 +35,88 @@ def test_all_layouts(hip, mkn):
         np.testing.assert_allclose(out, ref, rtol=1e-4, atol=1e-5 * K ** 0.5, err_msg=tag)
 
 
+# (M, K, N) whose tile the dispatch chooses on its own; (10, 24, 70): the 32x64 skinny tile without a split
+NATURAL = SHAPES + [(33, 784, 33), (10, 24, 70), (4000, 37, 4000)]
+# what the shapes above must reach between them, as (BM, BN, KG, K split across workgroups or not)
+MUST_REACH = {(64, 32, 1, False), (64, 32, 1, True), (32, 64, 1, False), (32, 64, 1, True), (64, 64, 1, False), (64, 64, 1, True),
+              (32, 32, 4, False), (256, 256, 1, False)}
+
+
+def test_natural_dispatch_plans(hip):
+    """lg_gemm_last_plan after every product of NATURAL in every layout: what no retune of the cost model may break, and that the
+    list still reaches every tile the default dispatch uses.  The second is a condition on the SHAPES: if a retune moves one of
+    them to another tile, put a shape into NATURAL that reaches the missing tile again - do not bend the model to the list."""
+    from lightgrad_amd.autograd.hip import ops as H
+    reached = {}
+    for (M, K, N) in NATURAL:
+        rng = np.random.RandomState(M + 3 * K + 7 * N)
+        a, b = rng.uniform(-1, 1, (M, K)).astype(np.float32), rng.uniform(-1, 1, (K, N)).astype(np.float32)
+        ta, tb = hip.from_numpy(a, requires_grad=False), hip.from_numpy(b, requires_grad=False)
+        ta_t = hip.from_numpy(np.ascontiguousarray(a.T), requires_grad=False).transpose(1, 0)
+        tb_t = hip.from_numpy(np.ascontiguousarray(b.T), requires_grad=False).transpose(1, 0)
+        for x, y, tag in [(ta, tb, "NN"), (ta, tb_t, "NT"), (ta_t, tb, "TN"), (ta_t, tb_t, "TT")]:
+            (x @ y).numpy()
+            p = H.gemm_last_plan()
+            what = "%s %s: %s" % ((M, K, N), tag, p)
+            print(what)
+            (bm, bn), kg, slices = p["tile"], p["kg"], p["k_slices"]
+            assert p["va"] and p["vb"] and p["route"] == "own", what
+            if min(M, K, N) > 1:                                            # (an extent of 1 fits either layout)
+                assert (p["a_kc"], p["b_kc"]) == (tag[0] == "N", tag[1] == "T"), what
+            if N <= 32:
+                assert (bm, bn, kg) == (64, 32, 1), what
+            elif M <= 32:
+                assert (bm, bn, kg) == (32, 64, 1), what
+            assert kg == 1 or slices == 1, what
+            assert slices == 1 or -(-M // bm) * -(-N // bn) < 256, what
+            assert p["k_per_slice"] % p["bk"] == 0 and (slices - 1) * p["k_per_slice"] < K <= slices * p["k_per_slice"], what
+            assert p["wave_private"] == ((bm, bn, kg) == (32, 32, 4) and p["a_kc"] and p["b_kc"]), what
+            reached.setdefault((bm, bn, kg, slices > 1), (M, K, N))
+    # extras are not compiled into the 256x256 tile: the same product with row sums must not stay on it
+    M, K, N = NATURAL[-1]
+    H._gemm_rowsum(ta, tb)[0].numpy()
+    p = H.gemm_last_plan()
+    assert p["tile"] != (256, 256) and p["k_slices"] * p["k_per_slice"] >= K, p
+    print("reached:", reached)
+    missing = MUST_REACH - set(reached)
+    assert not missing, ("no shape of NATURAL takes %s any more: add a shape that does (the cost model is not the thing to change)"
+                         % sorted(missing))
+
+
+def test_4000_37_4000_on_the_256_tile_whole_against_float64(hip):
+    """the 256x256 tile where 4096^3 never takes it: M and N no multiples of 256, K = 37 (a second K-tile of 5, a tail float4 of
+    1), padded leading dimensions, every float around the operands NaN - all four layouts through the raw C ABI, the WHOLE result
+    against float64: relative Frobenius error within max(1e-5, 2 x numpy float32's own), every element within the bound that holds
+    for any order of summation ((K + 8) * 2^-24 * |A| @ |B|), nothing written outside the result, no NaN in it"""
+    import gemm_cases as G
+    from lightgrad_amd.autograd.hip import lib as L
+    from lightgrad_amd.autograd.hip import ops as H
+    lib = L.lib()
+    M, K, N = 4000, 37, 4000
+    rng = np.random.RandomState(4037)
+    a, b = rng.uniform(-1, 1, (1, M, K)).astype(np.float32), rng.uniform(-1, 1, (1, K, N)).astype(np.float32)
+    ref = a[0].astype(np.float64) @ b[0].astype(np.float64)
+    bound = (K + 8) * G.U * (np.abs(a[0]).astype(np.float64) @ np.abs(b[0]).astype(np.float64))
+    cpu_err = rel_err(a[0] @ b[0], ref)
+    for (tA, tB), pads in zip(G.LAYOUTS, ((3, 1, 5), (1, 5, 0), (5, 3, 1), (0, 1, 3))):
+        A = G.Matrix(a.transpose(0, 2, 1) if tA else a, pads[0])
+        B = G.Matrix(b.transpose(0, 2, 1) if tB else b, pads[1])
+        C = G.Matrix(np.zeros((1, M, N), np.float32), pads[2], fill=G.PATTERN).blank()
+        dA, dB, dC = (hip.from_numpy(x.buf, requires_grad=False) for x in (A, B, C))
+        L.check(lib.lg_gemm_f32(tA, tB, M, N, K, dA.ptr + 4 * A.start, A.ld, 0, dB.ptr + 4 * B.start, B.ld, 0, dC.ptr + 4 * C.start, C.ld, 0, 1, 0))
+        p = H.gemm_last_plan()
+        assert p["tile"] == (256, 256) and p["k_slices"] == 1, ("(4000, 37, 4000) no longer takes the 256x256 tile: pick a shape that does", p)
+        out = dC.numpy()
+        got = C.get(out)[0]
+        assert C.outside_untouched(out), (tA, tB)
+        assert not np.isnan(got).any(), (tA, tB, int(np.isnan(got).sum()))
+        e = rel_err(got, ref)
+        worst = float((np.abs(got - ref) / bound).max())
+        print("tA=%d tB=%d: relative Frobenius error %.3g (numpy float32 %.3g), worst share of the element bound %.3g" % (tA, tB, e, cpu_err, worst))
+        assert e <= max(1e-5, 2 * cpu_err), (tA, tB, e, cpu_err)
+        assert worst <= 1.0, (tA, tB, worst)
+
+
 def test_identity_is_exact(hip):
     """A @ I == A bit for bit, in every layout: catches a swapped C/D row<->col map (asymmetric A)"""
     rng = np.random.RandomState(5)
