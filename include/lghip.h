@@ -117,6 +117,17 @@ int lg_copy_strided(int itemsize, int ndim, const int64_t* shape,
 int lg_fill_strided(int itemsize, int ndim, const int64_t* shape,
                     void* dst, const int64_t* dst_strides, uint64_t value_bits);
 
+/* What the most recent lg_copy_strided / lg_fill_strided call of the calling thread did (calls the library makes itself, such
+ * as the zero fill of an empty sum, count): host bookkeeping for tests, no device work.
+ *   out = {path, index_bits, head_items, body_vectors}
+ * path: 0 = device memcpy (both sides one contiguous run), 1 = handed to lg_ew (4-byte items; lg_ew_last_plan says the rest),
+ * 2 = the copy gather kernel (1-, 2-, 8-byte items), 3 = the flat fill (a dense run), 4 = the fill gather kernel, -1 = nothing
+ * launched (no elements, a refused call);
+ * index_bits: 32 or 64, the width of the element counter of paths 2 and 4, else 0;
+ * head_items, body_vectors: path 3 only - the items in front of the first 16-byte boundary (capped by the length) and the
+ * 16-byte stores behind them (capped at INT32_MAX); the rest of the run is the tail.  Else 0. */
+int lg_layout_last_plan(int32_t out[4]);
+
 /* ---- elementwise fp32 ------------------------------------------------------
  * One generic entry point replacing the run-time generated `atom` kernels
  * (opencl/kernels.py:24-195) for every op string used in opencl/ops.py:40-400.

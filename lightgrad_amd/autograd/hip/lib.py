@@ -64,6 +64,7 @@ PROTOTYPES = {
     "lg_graph_kernel_count": (c_int, [c_void_p, POINTER(c_int)]),
     "lg_copy_strided": (c_int, [c_int, c_int, _I64P, c_void_p, _I64P, c_void_p, _I64P]),
     "lg_fill_strided": (c_int, [c_int, c_int, _I64P, c_void_p, _I64P, c_uint64]),
+    "lg_layout_last_plan": (c_int, [POINTER(ctypes.c_int32)]),
     "lg_ew": (c_int, [c_int, c_int, _I64P, c_void_p, _I64P, c_void_p, _I64P,
                       c_void_p, _I64P, c_void_p, _I64P, c_void_p, _I64P, c_void_p, _I64P, c_float]),
     "lg_ew_last_plan": (c_int, [POINTER(ctypes.c_int32)]),

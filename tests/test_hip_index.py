@@ -173,3 +173,96 @@ def test_index_out_of_range_is_reported(hip):
     with pytest.raises(IndexError):
         loss.item()
     assert np.isnan(loss.item())
+
+
+# ---- the sweep: every case of tests/index_cases.py on the device -----------------------------------------------------------------
+import index_cases as IC      # noqa: E402
+from test_hip_layout import run_on_device      # noqa: E402
+
+
+@pytest.mark.parametrize("name", [c.name for c in IC.CASES])
+def test_sweep_case_equals_numpy(hip, name):
+    """bit for bit against numpy on the same arrays (tests/index_cases.py says which two cases are held to another rule, and why):
+    the values every case returns and every tensor it assigned into, whole"""
+    run_on_device(hip, IC, name)
+
+
+def test_sweep_masks_cross_the_scan_chunk_and_read_back_only_their_count(hip, monkeypatch):
+    """the mask lengths of the sweep span 1, 2, 256, 257 and 259 blocks of the count / positions kernels, so the block scan runs
+    one chunk, exactly one chunk, and a second chunk with a carry; the largest mask, all on the device, costs ONE read-back of
+    8 bytes"""
+    blocks = sorted({IC.mask_blocks(n) for n in IC.MASK_LENGTHS})
+    assert blocks == sorted(IC.MASK_BLOCK_COUNTS)
+    print("mask block counts swept: %s" % blocks)
+    n = IC.MASK_LENGTHS[-1]
+    m = IC.rng_of("mask_count_only").uniform(0, 1, n) < 0.5
+    t, dm = hip.from_numpy(np.arange(n, dtype=np.int64), requires_grad=False), hip.from_numpy(m, requires_grad=False)
+    reads = []
+    real = hip.numpy
+    monkeypatch.setattr(hip, "numpy", lambda self: (reads.append(self.shape), real(self))[1])
+    z = t[dm]
+    monkeypatch.setattr(hip, "numpy", real)
+    assert reads == [(1,)], reads
+    np.testing.assert_array_equal(z.numpy(), np.flatnonzero(m))
+
+
+@pytest.mark.parametrize("side", ["above", "below"])
+def test_sweep_one_index_one_step_out_of_range(hip, side):
+    """exactly one entry of a device index array is axis_len (or -axis_len - 1): the next synchronising call raises IndexError,
+    once; the gather's bad element reads all-ones bytes and the others are right; assignment and scatter-add leave the tensor as a
+    run without the bad entry does"""
+    from lightgrad_amd.autograd.hip import HipDevice
+    length, at = 11, 4
+    bad_value = length if side == "above" else -length - 1
+    D = lambda a: hip.from_numpy(a, requires_grad=False)      # noqa: E731
+
+    def once(read):
+        with pytest.raises(IndexError):
+            read()
+        HipDevice.synchronize()                                # reported once
+        return read()
+
+    keep = np.arange(9) != at
+    for dt in IC.DEVICE_INDEX:
+        for dtype in IC.SOURCE_DTYPES:
+            name = "oor_%s_%s_%s" % (side, np.dtype(dt), dtype)
+            a = IC.values(name, (3, length, 7), dtype)
+            i = IC.rng_of(name).randint(-length, length, 9)
+            bad = i.copy()
+            bad[at] = bad_value
+            got = once(D(a)[:, D(bad.astype(dt))].numpy)
+            assert got[:, keep].tobytes() == a[:, i][:, keep].tobytes()
+            assert (np.ascontiguousarray(got[:, at]).view(np.uint8) == 0xFF).all()
+            # assignment: distinct positions, the bad entry writes nothing
+            i = IC._distinct(name, length, 9)
+            bad = i.copy()
+            bad[at] = bad_value
+            v = IC.values(name + "v", (3, 9, 7), dtype)
+            for value, kept in ((D(v), v[:, keep]), (IC._scalar(dtype), IC._scalar(dtype))):
+                t = D(a.copy())
+                t[:, D(bad.astype(dt))] = value
+                want = a.copy()
+                want[:, i[keep]] = kept
+                assert once(t.numpy).tobytes() == want.tobytes()
+        # scatter-add (the backward of the gather): integer contributions, so any order of adding gives the same sums
+        name = "oor_scatter_%s_%s" % (side, np.dtype(dt))
+        i = IC.rng_of(name).randint(-3, 3, 64)
+        bad = i.copy()
+        bad[at] = 3 if side == "above" else -4
+        w = IC.rng_of(name + "w").randint(-8, 9, (2, 64, 5)).astype(np.float32)
+        t = hip.from_numpy(np.zeros((2, 3, 5), np.float32))
+        y = t[:, D(bad.astype(dt))]
+        with pytest.raises(IndexError):
+            y.numpy()                                          # the gather's own report
+        (y * D(w)).backward(allow_fill=True)
+        want = np.zeros((2, 3, 5), np.float32)
+        np.add.at(want, (slice(None), np.delete(i, at)), np.delete(w, at, axis=1))
+        assert once(t.grad.numpy).tobytes() == want.tobytes()
+        # several index arrays folded into one
+        a = IC.values(name + "fold", (6, 5, 7), np.float32)
+        i0, i1 = IC.rng_of(name + "0").randint(-6, 6, 9), IC.rng_of(name + "1").randint(-5, 5, 9)
+        for which in (0, 1):
+            b0, b1 = i0.copy(), i1.copy()
+            (b0, b1)[which][at] = ((6, 5)[which] if side == "above" else -(6, 5)[which] - 1)
+            got = once(D(a)[D(b0.astype(dt)), D(b1.astype(np.int64))].numpy)
+            assert got[keep].tobytes() == a[i0, i1][keep].tobytes()

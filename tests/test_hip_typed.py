@@ -120,3 +120,19 @@ def test_large_typed_reductions_and_empty_operands(hip):
     e = hip.from_numpy(np.zeros((0, 4), np.int32), requires_grad=False)
     assert (e + e).numpy().shape == (0, 4)
     np.testing.assert_array_equal(e.sum(axis=0).numpy(), np.zeros(4, np.int64))
+
+
+# ---- the sweep: every case of tests/typed_cases.py on the device ---------------------------------------------------------------------
+import typed_cases as TC      # noqa: E402
+from test_hip_layout import run_on_device      # noqa: E402
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", [c.name for c in TC.CASES])
+def test_sweep_case_equals_numpy(hip, name):
+    """elementwise results, casts, integer sums and sums of integer-valued doubles bit for bit (any NaN equals any NaN); max / min
+    as values, with the answers the planted extrema and NaNs force; float64 sums of general values inside gamma(n - 1) * sum |x|
+    of math.fsum - tests/typed_cases.py has the rules and the reasons"""
+    B = run_on_device(hip, TC, name)
+    if name.startswith("extrema_"):
+        assert B.forced >= 2 * len(TC.RED_LENGTHS) * 9
