@@ -20,6 +20,9 @@ Differences from the reference, on purpose:
                                                        # capture with --graph), cross-entropy over the masked positions only
     python examples/bert.py --mlm --accuracy [--graph] # also counts the masked tokens predicted right (light.metrics.accuracy), on
                                                        # the device, over every step and replay: one host read at the end
+    python examples/bert.py --clm [--graph] [--cpu]    # a causal language model of the same parameters: config key `causal=True`
+                                                       # (query i sees keys j <= i, inside the fused attention launches) and the
+                                                       # next-token objective (light.data.next_token_labels)
     python examples/bert.py --mlm --bf16-decoder       # the decoder onto the vocabulary (forward, dx, dW) on the bf16 matrix cores:
                                                        # config key `decoder_precision="bf16"`; tensors stay float32
 """
@@ -89,14 +92,27 @@ class BertEmbedding(nn.Module):
 
 
 class BertSelfAttention(nn.Module):
-    def __init__(self, hidden_size, num_attention_heads, attention_probs_dropout_prob=0.0):
+    def __init__(self, hidden_size, num_attention_heads, attention_probs_dropout_prob=0.0, causal=False):
+        """`causal=True`: query i sees keys j <= i only - the decoder-style mask of a causal language model.  The values are those
+        of the composite branch below: one more additive constant, `(1 - tril) * -10000`, behind the key-padding bias"""
         nn.Module.__init__(self)
         assert hidden_size % num_attention_heads == 0
+        self.causal = bool(causal)
+        self._tril = {}             # (backend class, s, dtype) -> the (1, 1, s, s) lower-triangular constant of ones
         self.dropout = nn.Dropout(attention_probs_dropout_prob)
         self.h, self.d = num_attention_heads, hidden_size // num_attention_heads
         self.query = nn.Linear(hidden_size, hidden_size)
         self.key = nn.Linear(hidden_size, hidden_size)
         self.value = nn.Linear(hidden_size, hidden_size)
+
+    def _lower_triangle(self, like, s):
+        key = (like.__class__, s, np.dtype(like.dtype))
+        if key not in self._tril:
+            t = like.__class__.from_numpy(np.tril(np.ones((1, 1, s, s), dtype=like.dtype)), requires_grad=False)
+            if hasattr(t, "freeze"):
+                t.freeze()                  # a constant of the model, like the position ids
+            self._tril[key] = t
+        return self._tril[key]
 
     def forward(self, hidden, attention_mask=None):
         b, s, _ = hidden.shape
@@ -115,6 +131,10 @@ class BertSelfAttention(nn.Module):
         # dropout of the probabilities sits between the softmax and the product with the values: the backends' one-launch forms
         # draw the composite's mask inside the kernel (one call of the stream); without `dropout=` they are the forms as they were
         drop = {"dropout": self.dropout.p} if self.training and self.dropout.p > 0 else {}
+        # the causal mask is a flag of the same forms (their forward launch leaves the keys j > i out); without it, the calls of before
+        if self.causal:
+            extra["causal"] = True
+            drop = dict(drop, causal=True)
         if fused and hidden.self_attention_supported(self.query.weight, self.h, **extra):
             # the backend's one-node form of this whole method: one launch for the three projections, one for the attention
             extra = {"mask": attention_mask} if attention_mask is not None else {}
@@ -122,8 +142,9 @@ class BertSelfAttention(nn.Module):
                                             self.value.weight, self.value.bias, heads=self.h, scale=scale, **extra, **drop)
             return context, context.attention_probs
         q, k, v = self.query(hidden), self.key(hidden), self.value(hidden)
-        if fused and (q.long_attention_supported(self.h) if long else
-                      q.masked_attention_supported(self.h) if masked else q.attention_supported(self.h)):
+        flag = {"causal": True} if self.causal else {}
+        if fused and (q.long_attention_supported(self.h, **flag) if long else
+                      q.masked_attention_supported(self.h, **flag) if masked else q.attention_supported(self.h, **flag)):
             # the backend's one-launch form of everything below (scores, scaling, softmax, context), forward and backward
             context = q.long_attention(k, v, heads=self.h, scale=scale, mask=attention_mask, **drop) if long else \
                 q.masked_attention(k, v, heads=self.h, scale=scale, mask=attention_mask, **drop) if masked else \
@@ -134,7 +155,7 @@ class BertSelfAttention(nn.Module):
         k = k.reshape(b, s, self.h, self.d).transpose(0, 2, 3, 1)
         v = v.reshape(b, s, self.h, self.d).transpose(0, 2, 1, 3)
         scores = q @ k
-        if attention_mask is None and hasattr(scores, "scaled_softmax"):
+        if attention_mask is None and not self.causal and hasattr(scores, "scaled_softmax"):
             # the backend's one-kernel form of the two lines below: the same x * sqrt(d)**-1, rounded to fp32, then softmax
             probs = scores.scaled_softmax(math.sqrt(self.d) ** -1)
         else:
@@ -143,15 +164,18 @@ class BertSelfAttention(nn.Module):
                 # (b, s) -> (b, 1, 1, s); for batch 1 this is the reference's (1, 1, 1, s) (bert.py:82, which breaks for b > 1)
                 mask = attention_mask.reshape(attention_mask.shape[0], 1, 1, attention_mask.shape[1])
                 scores = scores + ((1.0 - mask) * -10000.0).detach()
+            if self.causal:
+                # the same line for the keys j > i of query i: exp underflows to exactly 0 there; -0.0 for a visible key changes no bit
+                scores = scores + ((1.0 - self._lower_triangle(scores, s)) * -10000.0).detach()
             probs = scores.softmax(axis=-1)
         context = (self.dropout(probs) @ v).transpose(0, 2, 1, 3).reshape(b, s, self.h * self.d)
         return context, probs
 
 
 class BertAttention(nn.Module):
-    def __init__(self, hidden_size, num_attention_heads, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0):
+    def __init__(self, hidden_size, num_attention_heads, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0, causal=False):
         nn.Module.__init__(self)
-        self.self = BertSelfAttention(hidden_size, num_attention_heads, attention_probs_dropout_prob)
+        self.self = BertSelfAttention(hidden_size, num_attention_heads, attention_probs_dropout_prob, causal=causal)
         self.dropout = nn.Dropout(hidden_dropout_prob)
         self.output = nn.Module()
         self.output.dense = nn.Linear(hidden_size, hidden_size)
@@ -172,9 +196,10 @@ class BertAttention(nn.Module):
 
 
 class BertLayer(nn.Module):
-    def __init__(self, hidden_size, intermediate_size, num_attention_heads, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0):
+    def __init__(self, hidden_size, intermediate_size, num_attention_heads, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0,
+                 causal=False):
         nn.Module.__init__(self)
-        self.attention = BertAttention(hidden_size, num_attention_heads, hidden_dropout_prob, attention_probs_dropout_prob)
+        self.attention = BertAttention(hidden_size, num_attention_heads, hidden_dropout_prob, attention_probs_dropout_prob, causal=causal)
         self.dropout = nn.Dropout(hidden_dropout_prob)
         self.intermediate = nn.Module()
         self.intermediate.dense = nn.Linear(hidden_size, intermediate_size)
@@ -202,12 +227,15 @@ class BertLayer(nn.Module):
 
 class BertModel(nn.Module):
     def __init__(self, hidden_size, intermediate_size, num_hidden_layers, num_attention_heads, vocab_size,
-                 max_position_embeddings, type_vocab_size, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0, **unused):
+                 max_position_embeddings, type_vocab_size, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0, causal=False,
+                 **unused):
+        """`causal=True`: every layer's attention is causal - with the next-token objective (`clm_forward_backward`) a decoder-style
+        language model of the same parameters"""
         nn.Module.__init__(self)
         self.embeddings = BertEmbedding(hidden_size, vocab_size, max_position_embeddings, type_vocab_size, hidden_dropout_prob)
         self.encoder = nn.Module()
         self.encoder.layer = nn.ModuleList(*[BertLayer(hidden_size, intermediate_size, num_attention_heads, hidden_dropout_prob,
-                                                       attention_probs_dropout_prob)
+                                                       attention_probs_dropout_prob, causal=causal)
                                              for _ in range(num_hidden_layers)])
 
     def forward(self, input_ids, attention_mask=None, token_type_ids=None):
@@ -271,15 +299,32 @@ def mlm_forward_backward(model, ids, p=0.15, accuracy_total=None):
     return loss
 
 
+def clm_forward_backward(model, ids):
+    """one causal-LM step of a model built with `causal=True`: position i predicts token i + 1 from the tokens up to i; the last
+    position has no label.  The labels are made on the ids' own backend (no host read: a captured step shifts what the ids hold
+    at each replay)."""
+    vocab = model.cls.predictions.decoder.weight.shape[0]
+    labels = light.data.next_token_labels(ids, ignore_index=-100)
+    logits = model(ids)
+    loss = light.loss.cross_entropy(logits.reshape(-1, vocab), labels.reshape(-1), ignore_index=-100)
+    for q in model.parameters():
+        q.zero_grad()
+    loss.backward()
+    return loss
+
+
 if __name__ == "__main__":
     cpu = "--cpu" in sys.argv
     if "--mlm" in sys.argv:
         light.manual_seed(0)
         forward_backward = mlm_forward_backward            # the masked-LM objective in place of the stand-in loss below
+    if "--clm" in sys.argv:
+        assert "--mlm" not in sys.argv, "--clm and --mlm are two objectives"
+        forward_backward = clm_forward_backward            # the next-token objective over causal attention
     batch = int(sys.argv[sys.argv.index("--batch") + 1]) if "--batch" in sys.argv else 8
     to_device = (lambda t: t) if cpu else (lambda t: t.hip())
     np.random.seed(0)
-    config = dict(TINY, decoder_precision="bf16" if "--bf16-decoder" in sys.argv else None)
+    config = dict(TINY, decoder_precision="bf16" if "--bf16-decoder" in sys.argv else None, causal="--clm" in sys.argv)
     model = BertForMaskedLM(**config).map_parameters(to_device)
     ids = to_device(light.from_numpy(np.random.randint(0, TINY["vocab_size"], (batch, 128)).astype(np.int32), requires_grad=False))
     total = None

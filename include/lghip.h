@@ -605,6 +605,26 @@ int lg_attention_dropout_bwd_f32(const float* q, int64_t ldq, int64_t sbq, const
                                  float* dv, int64_t lddv, int64_t sbdv, int64_t batch, int64_t heads, int64_t S, int64_t D,
                                  float scale, double prob, const uint64_t* base);
 
+/* The forward with a causal mask, for every length: 1 <= S <= 512, D = 32 or 64 (lg_attention_causal_supported, pure host code).
+ * Query i sees keys j <= i only: a key j > i takes no part in the max or the sum of row i, and P[i][j] = +0.0 is STORED for it
+ * (the dense (batch, heads, S, S) tensor is what the model returns and what the backward reads).  The values are those of the
+ * composite `scores + (1 - tril) * -10000` added after the key-padding bias whenever |scaled score| << 10000.  `mask` composes:
+ * a padded key j <= i keeps its bias; key 0 is visible to every row, so no row is empty.  Up to 128 positions the masked forms'
+ * kernels run (also at multiples of 32 and with mask == NULL), beyond them the long forms'; key blocks wholly above the diagonal
+ * of a block of queries cost no MFMAs, and a row depends on S, its block and positions <= i only.
+ *   base_out == NULL, prob == 0   no dropout, nothing drawn; an empty batch returns LG_OK
+ *   base_out != NULL              dropout of P as in lg_attention_dropout_fwd_f32, under that entry's rules (one call of the
+ *                                 stream over the whole dense tensor, element i at flat index i; a zero stays zero; batch >= 1)
+ *   base_out == NULL, prob != 0   LG_EINVAL
+ * Arguments as for lg_attention_dropout_fwd_f32, checked in its order.  There is no causal backward: P is zero above the
+ * diagonal, so dS = P o (dP - shift) * scale is zero there, and the backward of a causal forward is the backward entry of the
+ * same length and dropout: lg_attention_bwd_f32 / _masked_ / _long_ / _dropout_bwd_f32. */
+int lg_attention_causal_supported(int64_t S, int64_t D);
+int lg_attention_causal_fwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
+                                const float* v, int64_t ldv, int64_t sbv, float* o, int64_t ldo, int64_t sbo, float* p,
+                                int64_t batch, int64_t heads, int64_t S, int64_t D, float scale,
+                                const float* mask, int64_t sbm, double prob, uint64_t* base_out);
+
 /* ---- two independent products in one launch ----------------------------------------------------------
  * lg_gemm_pair_begin(); <product 1>; <product 2>; lg_gemm_pair_end();   with products issued through
  * lg_gemm_f32 / lg_gemm_rowsum_f32 / lg_gemm_fused_f32.  If the first resolves to the 64x64 tile with an

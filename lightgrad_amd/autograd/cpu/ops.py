@@ -389,6 +389,21 @@ def _mlm_mask(ids, p, mask_token_id, vocab_size, special_ids=(), ignore_index=-1
 CpuTensor.mlm_mask = _mlm_mask
 
 
+def _next_token_labels(ids, ignore_index=-100):
+    """ ids.next_token_labels(ignore_index=-100): the labels of the next-token objective - `ids` shifted left by one along the last
+    axis, `ignore_index` in the last column; same dtype and shape, a constant of the tape. """
+    assert ids.dtype in (np.dtype(np.int32), np.dtype(np.int64)) and len(ids.shape) >= 1, \
+        "next_token_labels: ids must be int32 or int64 with at least one axis (got %s %s)" % (ids.dtype, ids.shape)
+    ignore_index = int(ignore_index)
+    assert np.iinfo(ids.dtype).min <= ignore_index <= np.iinfo(ids.dtype).max, "next_token_labels: ignore_index does not fit %s" % ids.dtype
+    labels = np.full(ids.shape, ignore_index, dtype=ids.dtype)
+    labels[..., :-1] = ids.data[..., 1:]
+    return CpuTensor.from_numpy(labels, requires_grad=False)
+
+
+CpuTensor.next_token_labels = _next_token_labels
+
+
 def _arg_extremum(name):
     np_fn = getattr(np, name)
 

@@ -2419,6 +2419,30 @@ def _mlm_mask(ids, p, mask_token_id, vocab_size, special_ids=(), ignore_index=-1
 HipTensor.mlm_mask = _mlm_mask
 
 
+def _next_token_labels(ids, ignore_index=-100):
+    """ ids.next_token_labels(ignore_index=-100): the labels of the next-token objective - `ids` shifted left by one along the last
+    axis, `ignore_index` in the last column; same dtype and shape, a constant of the tape.  One strided copy and one strided fill
+    (csrc/layout.hip), no host read: it can sit in a captured step. """
+    assert ids._dtype in (np.dtype(np.int32), np.dtype(np.int64)) and len(ids._shape) >= 1, \
+        "next_token_labels: ids must be int32 or int64 with at least one axis (got %s %s)" % (ids._dtype, ids._shape)
+    ignore_index = int(ignore_index)
+    assert np.iinfo(ids._dtype).min <= ignore_index <= np.iinfo(ids._dtype).max, "next_token_labels: ignore_index does not fit %s" % ids._dtype
+    n = ids._shape[-1]
+    out = HipTensor.empty(ids._shape, dtype=ids._dtype, requires_grad=False)
+    if out.numel() == 0:
+        return out
+    last = HipTensor(out.data, ids._shape[:-1] + (1,), out._strides, out._offset + (n - 1), out._dtype, requires_grad=False)
+    last.fill(ignore_index)
+    if n > 1:
+        itemsize = ids._dtype.itemsize
+        _l.check(_l.lib().lg_copy_strided(itemsize, len(ids._shape), i64(ids._shape[:-1] + (n - 1,)), out.ptr, i64(out._strides),
+                                          ids.ptr + ids._strides[-1] * itemsize, i64(ids._strides)))
+    return out
+
+
+HipTensor.next_token_labels = _next_token_labels
+
+
 def _rows_view(t):
     """dense (rows, cols) pointer view of a tensor whose last axis is the row"""
     t = t.contiguous()

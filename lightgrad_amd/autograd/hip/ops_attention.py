@@ -3,7 +3,8 @@
 
 The library has four entry families - plain, masked, long, and the dropout pair that covers every length - and every op here
 goes through the same two helpers, `_launch_attention_fwd` / `_launch_attention_bwd`: the op names its form, `dropout > 0`
-takes the dropout entries instead.  That rule, and each symbol's name, stand here once.
+takes the dropout entries instead.  That rule, and each symbol's name, stand here once.  `causal=True` on any op swaps the
+forward launch for the causal entry (one for every form, with or without dropout); the backward launch stays the form's own.
 """
 import ctypes
 from ..func import Function
@@ -18,6 +19,8 @@ _ENTRIES = {
     "masked": ("lg_attention_masked_supported", "lg_attention_masked_fwd_f32", "lg_attention_masked_bwd_f32"),
     "long": ("lg_attention_long_supported", "lg_attention_long_fwd_f32", "lg_attention_long_bwd_f32"),
     "dropout": ("lg_attention_dropout_supported", "lg_attention_dropout_fwd_f32", "lg_attention_dropout_bwd_f32"),
+    # `causal=True`: one forward entry for every form, with or without dropout; the backward is the form's own (it reads P)
+    "causal": ("lg_attention_causal_supported", "lg_attention_causal_fwd_f32", None),
 }
 
 
@@ -54,12 +57,17 @@ def _key_mask(mask, b, s, what):
     return mask, mask.ptr, (0 if mask._shape[0] == 1 else mask._strides[0])
 
 
-def _launch_attention_fwd(form, q3, k3, v3, out, probs, dims, scale, mask3, dropout):
-    """the forward launch of `form` ("plain", "masked" or "long"), or the dropout entry where dropout > 0.  q3, k3, v3: (address,
-    row pitch, batch pitch); out (b, s, heads * d) and probs dense; dims = (b, heads, s, d); mask3 as `_key_mask` returns it.
+def _launch_attention_fwd(form, q3, k3, v3, out, probs, dims, scale, mask3, dropout, causal=False):
+    """the forward launch of `form` ("plain", "masked" or "long"), or the dropout entry where dropout > 0; causal=True: the causal
+    entry, which takes both.  q3, k3, v3: (address, row pitch, batch pitch); out (b, s, heads * d) and probs dense; dims =
+    (b, heads, s, d); mask3 as `_key_mask` returns it.
     Returns the word the dropout launch wrote the call's number to, None without dropout."""
     b, heads, s, d = dims
     args = (*q3, *k3, *v3, out.ptr, heads * d, s * heads * d, probs.ptr, b, heads, s, d, scale)
+    if causal:
+        base = _dropout_base() if dropout > 0.0 else None
+        _l.check(getattr(_l.lib(), _ENTRIES["causal"][1])(*args, mask3[1], mask3[2], dropout, None if base is None else base.ptr))
+        return base
     if dropout > 0.0:
         base = _dropout_base()
         _l.check(getattr(_l.lib(), _ENTRIES["dropout"][1])(*args, mask3[1], mask3[2], dropout, base.ptr))
@@ -71,8 +79,8 @@ def _launch_attention_fwd(form, q3, k3, v3, out, probs, dims, scale, mask3, drop
 
 
 def _launch_attention_bwd(form, q3, k3, v3, g3, probs, dq3, dk3, dv3, dims, scale, dropout, base):
-    """the backward launch that belongs to `_launch_attention_fwd(form, ...)`, whose result `base` is; every operand as
-    (address, row pitch, batch pitch)"""
+    """the backward launch that belongs to `_launch_attention_fwd(form, ...)`, whose result `base` is - causal or not: the
+    probabilities carry the zeros; every operand as (address, row pitch, batch pitch)"""
     b, heads, s, d = dims
     args = (*q3, *k3, *v3, *g3, probs.ptr, *dq3, *dk3, *dv3, b, heads, s, d, scale)
     if base is not None:
@@ -82,18 +90,18 @@ def _launch_attention_bwd(form, q3, k3, v3, g3, probs, dq3, dk3, dv3, dims, scal
 
 
 def _attention_supported(form, positive_batch, doc):
-    def supported(q, heads):
+    def supported(q, heads, causal=False):
         return len(q._shape) == 3 and q._dtype == _F32 and q._shape[2] % heads == 0 and (not positive_batch or q._shape[0] > 0) and \
-            _fits(form, q._shape[1], q._shape[2] // heads)
+            _fits(form, q._shape[1], q._shape[2] // heads) and (not causal or _fits("causal", q._shape[1], q._shape[2] // heads))
     supported.__doc__ = doc
     return supported
 
 
 def _attention_op(name, supported, form, takes_mask, doc):
-    def forward(ctx, q, k, v, heads=1, scale=1.0, mask=None, dropout=0.0):
+    def forward(ctx, q, k, v, heads=1, scale=1.0, mask=None, dropout=0.0, causal=False):
         dropout = _attention_dropout(dropout)           # > 0: `probs.dropout(p)` inside the two launches
         _require_f32(q, k, v)
-        assert q._shape == k._shape == v._shape and supported(q, heads), \
+        assert q._shape == k._shape == v._shape and supported(q, heads, causal), \
             "%s: unsupported shapes %s / %s / %s with %d heads" % (name, q._shape, k._shape, v._shape, heads)
         b, s, width = q._shape
         dims = (b, heads, s, width // heads)
@@ -101,7 +109,8 @@ def _attention_op(name, supported, form, takes_mask, doc):
         (q, ldq, sbq), (k, ldk, sbk), (v, ldv, sbv) = _token_rows(q), _token_rows(k), _token_rows(v)
         out = HipTensor.empty((b, s, width))
         probs = HipTensor.empty((b, heads, s, s), requires_grad=False)
-        base = _launch_attention_fwd(form, (q.ptr, ldq, sbq), (k.ptr, ldk, sbk), (v.ptr, ldv, sbv), out, probs, dims, float(scale), mask3, dropout)
+        base = _launch_attention_fwd(form, (q.ptr, ldq, sbq), (k.ptr, ldk, sbk), (v.ptr, ldv, sbv), out, probs, dims, float(scale), mask3, dropout,
+                                     bool(causal))
         ctx.save_for_backward(q, k, v, probs, dims, float(scale), dropout, base)
         out.attention_probs = probs
         return out
@@ -109,8 +118,8 @@ def _attention_op(name, supported, form, takes_mask, doc):
     if not takes_mask:
         with_mask = forward
 
-        def forward(ctx, q, k, v, heads=1, scale=1.0, dropout=0.0):
-            return with_mask(ctx, q, k, v, heads, scale, None, dropout)
+        def forward(ctx, q, k, v, heads=1, scale=1.0, dropout=0.0, causal=False):
+            return with_mask(ctx, q, k, v, heads, scale, None, dropout, causal)
 
     def backward(ctx, out_grad):
         q, k, v, probs, dims, scale, dropout, base = ctx.get_saved_tensors()
@@ -140,7 +149,10 @@ attention = _attention_op(
     happens in the kernels' addressing.  The probabilities (batch, heads, s, s) the reference model returns next to the context
     (bert.py:88) are on the result as `.attention_probs`, outside the tape (the composite form differentiates through them).
     dropout=p > 0: `probs.dropout(p)` between the softmax and the context inside the same two launches - the mask the composite
-    draws (one call of the stream, lightgrad_amd/random.py); `.attention_probs` stays undropped """)
+    draws (one call of the stream, lightgrad_amd/random.py); `.attention_probs` stays undropped.
+    causal=True: query i sees keys j <= i only (the composite's `scores + (1 - tril) * -10000`); the forward is the causal launch
+    (lg_attention_causal_fwd_f32), `.attention_probs` holds exact zeros above the diagonal and the backward is the same launch
+    as without - here and in `masked_attention`, `long_attention` and `self_attention` """)
 masked_attention = _attention_op(
     "masked_attention", masked_attention_supported, "masked", True,
     """ `attention` for what a tokenizer produces: any s in 1 .. 128 and a key-padding mask (reference examples/bert.py:80-83:
@@ -155,15 +167,15 @@ long_attention = _attention_op(
     `.attention_probs` (b, heads, s, s) as there, outside the tape. """)
 
 
-def self_attention_supported(x, wq, heads, masked=False, long=False):
+def self_attention_supported(x, wq, heads, masked=False, long=False, causal=False):
     """does `x.self_attention(wq, bq, wk, bk, wv, bv, heads, scale)` exist for these shapes?  (b, s, hidden) input, three
     (width, hidden) weights with width = heads * d, d = 32 or 64, width a multiple of 64, s = 32 .. 128 in 32s; masked=True:
     the same question for the form with `mask=` or a length that is no multiple of 32 - any s in 1 .. 128; long=True: the
-    same question for the lengths beyond - any s in 129 .. 512, with or without a mask"""
+    same question for the lengths beyond - any s in 129 .. 512, with or without a mask; causal=True: and with `causal=True`"""
     form = "long" if long else "masked" if masked else "plain"
     return (len(x._shape) == 3 and x._dtype == _F32 and len(wq._shape) == 2 and wq._shape[1] == x._shape[2] and wq._shape[0] % heads == 0
             and wq._shape[0] % 64 == 0 and x._shape[2] % 4 == 0 and x.numel() > 0
-            and _fits(form, x._shape[1], wq._shape[0] // heads))
+            and _fits(form, x._shape[1], wq._shape[0] // heads) and (not causal or _fits("causal", x._shape[1], wq._shape[0] // heads)))
 
 
 def _ptr3(a, b, c):
@@ -180,13 +192,13 @@ class self_attention(Function):
     the weight / bias gradients take the routes of `linear`.  `.attention_probs` as for `attention`.  With a key-padding
     `mask` (as for `masked_attention`) or a length that is no multiple of 32 the attention launches are the masked / tail ones,
     beyond 128 positions (up to 512, mask or none) the long ones of csrc/attention_long.hip; everything else about the node is
-    the same. """
-    def forward(ctx, x, wq, bq, wk, bk, wv, bv, heads=1, scale=1.0, mask=None, dropout=0.0):
+    the same - also with causal=True, which only picks the causal forward launch of the attention. """
+    def forward(ctx, x, wq, bq, wk, bk, wv, bv, heads=1, scale=1.0, mask=None, dropout=0.0, causal=False):
         dropout = _attention_dropout(dropout)           # > 0: `probs.dropout(p)` inside the attention launches, as for `attention`
         _require_f32(x, wq, bq, wk, bk, wv, bv)
         long = len(x._shape) == 3 and x._shape[1] > 128
         tail = mask is not None or (len(x._shape) == 3 and x._shape[1] % 32 != 0)
-        assert self_attention_supported(x, wq, heads, masked=tail, long=long) and wq._shape == wk._shape == wv._shape and bq._shape == bk._shape == bv._shape == (wq._shape[0],), \
+        assert self_attention_supported(x, wq, heads, masked=tail, long=long, causal=causal) and wq._shape == wk._shape == wv._shape and bq._shape == bk._shape == bv._shape == (wq._shape[0],), \
             "self_attention: unsupported shapes %s with weights %s / %s / %s and %d heads" % (x._shape, wq._shape, wk._shape, wv._shape, heads)
         form = "long" if long else "masked" if tail else "plain"
         b, s, hidden = x._shape
@@ -202,7 +214,7 @@ class self_attention(Function):
         ld, sb = 3 * width, s * 3 * width
         mask3 = _key_mask(mask, b, s, "self_attention")
         drop_base = _launch_attention_fwd(form, (base, ld, sb), (base + 4 * width, ld, sb), (base + 8 * width, ld, sb), out, probs,
-                                          (b, heads, s, width // heads), float(scale), mask3, dropout)
+                                          (b, heads, s, width // heads), float(scale), mask3, dropout, bool(causal))
         ctx.save_for_backward(x, qkv, probs, heads, float(scale), form, dropout, drop_base)
         out.attention_probs = probs
         return out

@@ -36,10 +36,11 @@
 // the kernels as they were.
 //
 // Layout.  attention_common.h has what this file and attention_long.hip share: the argument structs, the small device helpers, and
-// the host interface.  This file has the short kernels (attn_fwd, attn_bwd: <D, TAIL, DROP>), their launchers, and the ONE host
-// path of all eight lg_attention_*_f32 launch entries - attn_forward / attn_backward: the checks in one order, the selection
-// of the kernels (pick_form), the `shift` slab allocated and freed in one place - plus the plain, masked and dropout entries,
-// which only fill a call struct and name their family.  attention_long.hip adds the long kernels, their launchers and entries.
+// the host interface.  This file has the short kernels (attn_fwd: <D, TAIL, DROP, CAUSAL>, attn_bwd: <D, TAIL, DROP>), their
+// launchers, and the ONE host path of all nine lg_attention_*_f32 launch entries - attn_forward / attn_backward: the checks in one
+// order, the selection of the kernels (pick_form), the `shift` slab allocated and freed in one place - plus the plain, masked,
+// dropout and causal entries, which only fill a call struct and name their family.  attention_long.hip adds the long kernels,
+// their launchers and entries.
 #include "attention_common.h"
 
 namespace lg {
@@ -52,8 +53,12 @@ constexpr int attn_fwd_tail_lds_floats(int S) { return attn_fwd_lds_floats<D>(ro
 
 // DROP: dropout of the probabilities between the softmax and the context, from the stream of dropout.hip (one call per launch:
 // read `draws`, take a ticket, the last arriver advances).  P goes to HBM undropped; what feeds the context MFMAs is Pd.
-template <int D, bool TAIL = false, bool DROP = false>
+// CAUSAL (TAIL only): query i sees keys j <= i.  The selection that takes keys >= S out of the softmax also takes out keys
+// j > q0 + row: no part of the max or the sum, 0 in the LDS tile, +0.0 stored to P (the backward reads the whole dense tensor).
+// A wave whose 32 keys all lie above the block's diagonal leaves its score MFMAs out: what it would have written is deselected.
+template <int D, bool TAIL = false, bool DROP = false, bool CAUSAL = false>
 __global__ void __launch_bounds__(256) attn_fwd(std::conditional_t<DROP, AttnDropArgs, std::conditional_t<TAIL, AttnTailArgs, AttnArgs>> a) {
+    static_assert(TAIL || !CAUSAL, "the causal selection lives in the TAIL softmax");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int S = a.S;                               // the sequence
     const int Sp = TAIL ? round32(S) : S;            // what the tiles cover
@@ -113,7 +118,11 @@ __global__ void __launch_bounds__(256) attn_fwd(std::conditional_t<DROP, AttnDro
     if constexpr (DROP) { seed = rng_uniform64(call[0]); base = rng_uniform64(call[1]); }
 
     // scores of 32 queries against keys [32 wave, 32 wave + 32), scaled (the product rounded to fp32 first, like `scores * c`)
-    if (32 * wave < Sp) {
+    bool has_scores = 32 * wave < Sp;
+    // (CAUSAL: keys wholly above the diagonal of the block are no one's: their columns of the tile stay stale, loaded by the
+    // softmax and never used - the bound is the same for the whole wave)
+    if constexpr (CAUSAL) has_scores = has_scores && 32 * wave <= q0 + 31;
+    if (has_scores) {
         af32x16 acc = zero16();
         wave_mma<true, true>(acc, Qs, PQ, Ks + 32 * wave * PQ, PQ, D, r, h);
         if constexpr (TAIL) {
@@ -134,6 +143,8 @@ __global__ void __launch_bounds__(256) attn_fwd(std::conditional_t<DROP, AttnDro
         // the same three passes in the same order over the keys that exist: a key >= S is no part of the max or the sum, its
         // column of the LDS tile becomes 0 (it is an MFMA operand of the context) and nothing of it is stored
         const int row = tid >> 3, sub = tid & 7;
+        // the keys of this row: [0, S), CAUSAL [0, min(S, q0 + row + 1)) - key 0 is always one of them
+        const int vis = CAUSAL ? (q0 + row + 1 < S ? q0 + row + 1 : S) : S;
         float* pr = Ps + row * PP;
         af32x4 t[4];
         float m = -INFINITY;
@@ -144,7 +155,7 @@ __global__ void __launch_bounds__(256) attn_fwd(std::conditional_t<DROP, AttnDro
                 t[i] = *reinterpret_cast<const af32x4*>(pr + c);
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    if (c + e < S) m = (t[i][e] > m || t[i][e] != t[i][e]) ? t[i][e] : m;
+                    if (c + e < vis) m = (t[i][e] > m || t[i][e] != t[i][e]) ? t[i][e] : m;
             }
         }
 #pragma unroll
@@ -156,7 +167,7 @@ __global__ void __launch_bounds__(256) attn_fwd(std::conditional_t<DROP, AttnDro
             if (c < Sp) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    if (c + e < S) { t[i][e] = expf(t[i][e] + (-m)); s += t[i][e]; }
+                    if (c + e < vis) { t[i][e] = expf(t[i][e] + (-m)); s += t[i][e]; }
                     else t[i][e] = 0.f;
                 }
             }
@@ -588,12 +599,12 @@ static unsigned long long* timeline_buffer(int wgs) {
 #endif
 
 // ---- the launchers: LDS size, allow_lds, launch.  `a` is sliced to the struct the instantiation takes ---------------------------
-template <int D, bool TAIL, bool DROP>
+template <int D, bool TAIL, bool DROP, bool CAUSAL = false>
 static int launch_fwd_as(const AttnDropArgs& a, dim3 grid) {
     const size_t bytes = size_t(TAIL ? attn_fwd_tail_lds_floats<D>(a.S) : attn_fwd_lds_floats<D>(a.S)) * 4;
-    int rc = allow_lds(&attn_fwd<D, TAIL, DROP>, bytes);
+    int rc = allow_lds(&attn_fwd<D, TAIL, DROP, CAUSAL>, bytes);
     if (rc != LG_OK) return rc;
-    hipLaunchKernelGGL((attn_fwd<D, TAIL, DROP>), grid, dim3(256), bytes, rt().stream, a);
+    hipLaunchKernelGGL((attn_fwd<D, TAIL, DROP, CAUSAL>), grid, dim3(256), bytes, rt().stream, a);
     return LG_OK;
 }
 
@@ -611,6 +622,14 @@ static int launch_fwd(const AttnDropArgs& a, dim3 grid, int64_t D, bool tail, bo
         {{launch_fwd_as<32, false, false>, launch_fwd_as<32, false, true>}, {launch_fwd_as<32, true, false>, launch_fwd_as<32, true, true>}},
         {{launch_fwd_as<64, false, false>, launch_fwd_as<64, false, true>}, {launch_fwd_as<64, true, false>, launch_fwd_as<64, true, true>}}};
     return table[D == 64][tail][drop](a, grid);
+}
+
+// the causal family's short form: the TAIL kernels at every length 1 .. 128
+static int launch_causal_fwd(const AttnDropArgs& a, dim3 grid, int64_t D, bool drop) {
+    static int (*const table[2][2])(const AttnDropArgs&, dim3) = {             // [D == 64][drop]
+        {launch_fwd_as<32, true, false, true>, launch_fwd_as<32, true, true, true>},
+        {launch_fwd_as<64, true, false, true>, launch_fwd_as<64, true, true, true>}};
+    return table[D == 64][drop](a, grid);
 }
 
 static int launch_bwd(const AttnBwdDropArgs& a, dim3 grid, int64_t D, bool tail, bool drop) {
@@ -638,7 +657,7 @@ static int check_launch(const char* name) {
 // The selection rule.  A family with a form of its own runs that form for every call it accepts - the masked entries the TAIL
 // kernels also at S % 32 == 0 and with mask == NULL.  The dropout family goes by length: the long kernels beyond 128, else
 // the plain kernels where `plain_fits` (forward: no mask and S % 32 == 0; backward: S % 32 == 0 - which forward ran makes no
-// difference to the backward's bits), else the TAIL ones.
+// difference to the backward's bits), else the TAIL ones.  The causal family goes by length too and has no plain form.
 static AttnForm pick_form(const AttnFamily& f, int64_t S, bool plain_fits) {
     if (f.form != AttnForm::ByLength) return f.form;
     return S > 128 ? AttnForm::Long : plain_fits ? AttnForm::Plain : AttnForm::Tail;
@@ -646,12 +665,14 @@ static AttnForm pick_form(const AttnFamily& f, int64_t S, bool plain_fits) {
 
 int attn_forward(const AttnFamily& f, const AttnFwdCall& c) {
     const char* name = f.fwd;
-    const bool drops = f.dropout();
+    const bool drops = f.causal ? c.base != nullptr : f.dropout();       // the causal entry draws where it is given a base_out
     const int64_t batch = c.batch, heads = c.heads, S = c.S, D = c.D, w = heads * D;
     LG_ARG(f.supported(S, D), "%s: S = %lld (%s), D = %lld (32 or 64) unsupported", name, (long long)S, f.range, (long long)D);
     if (drops) {
         LG_ARG(c.prob >= 0.0 && c.prob < 1.0, "%s: p = %g outside [0, 1)", name, c.prob);
         LG_ARG(c.base != nullptr, "%s: base_out is NULL", name);
+    } else if (f.causal) {
+        LG_ARG(c.prob == 0.0, "%s: p = %g with a NULL base_out (dropout writes the call's number there)", name, c.prob);
     }
     LG_ARG(batch >= 0 && heads >= 1 && batch <= 65535 && heads <= 65535, "%s: bad batch / heads", name);
     if (drops) LG_ARG(batch > 0, "%s: an empty batch draws nothing (batch must be >= 1)", name);
@@ -672,7 +693,7 @@ int attn_forward(const AttnFamily& f, const AttnFwdCall& c) {
         drop = AttnDrop{rt().rng_state, reinterpret_cast<unsigned long long*>(c.base), 0u, 0.f, rng_group(unsigned(wgs))};
         rng_threshold(c.prob, drop.threshold, drop.s);
     }
-    const AttnForm form = pick_form(f, S, !c.mask && S % 32 == 0);
+    const AttnForm form = pick_form(f, S, !f.causal && !c.mask && S % 32 == 0);
     AttnDropArgs a{{{
 #ifdef LG_GEMM_TIMELINE
         form == AttnForm::Long ? nullptr : timeline_buffer(int(wgs)),        // the long kernels take no timestamps
@@ -680,7 +701,9 @@ int attn_forward(const AttnFamily& f, const AttnFwdCall& c) {
         c.q.x, c.k.x, c.v.x, c.q.ld, c.q.sb, c.k.ld, c.k.sb, c.v.ld, c.v.sb, c.o.x, c.o.ld, c.o.sb, c.p, int(S), int(heads), c.scale},
         c.mask, c.sbm}, drop};
     const dim3 grid(unsigned(Sp / 32), unsigned(heads), unsigned(batch));
-    const int rc = form == AttnForm::Long ? attn_long_launch_fwd(a, grid, D, drops) : launch_fwd(a, grid, D, form == AttnForm::Tail, drops);
+    const int rc = form == AttnForm::Long ? attn_long_launch_fwd(a, grid, D, drops, f.causal)
+                   : f.causal             ? launch_causal_fwd(a, grid, D, drops)
+                                          : launch_fwd(a, grid, D, form == AttnForm::Tail, drops);
     return rc != LG_OK ? rc : check_launch(name);
 }
 
@@ -745,12 +768,18 @@ extern "C" int lg_attention_masked_supported(int64_t S, int64_t D) {
 extern "C" int lg_attention_dropout_supported(int64_t S, int64_t D) {
     return (D == 64 || D == 32) && S >= 1 && S <= 512;
 }
+extern "C" int lg_attention_causal_supported(int64_t S, int64_t D) {
+    return (D == 64 || D == 32) && S >= 1 && S <= 512;
+}
 
 static const AttnFamily kPlain{"lg_attention_fwd_f32", "lg_attention_bwd_f32", lg_attention_supported, "32..128, multiple of 32", AttnForm::Plain};
 static const AttnFamily kMasked{"lg_attention_masked_fwd_f32", "lg_attention_masked_bwd_f32", lg_attention_masked_supported, "1..128", AttnForm::Tail};
 // one pair for every length, with dropout of the probabilities inside the launches
 static const AttnFamily kDropout{"lg_attention_dropout_fwd_f32", "lg_attention_dropout_bwd_f32", lg_attention_dropout_supported, "1..512",
                                  AttnForm::ByLength};
+// the forward with a causal mask at every length; dropout where the call brings a base_out.  No backward of its own: P is zero
+// above the diagonal, and the backward entry of the form reads P.
+static const AttnFamily kCausal{"lg_attention_causal_fwd_f32", nullptr, lg_attention_causal_supported, "1..512", AttnForm::ByLength, true};
 
 extern "C" int lg_attention_fwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
                                     const float* v, int64_t ldv, int64_t sbv, float* o, int64_t ldo, int64_t sbo, float* p,
@@ -803,6 +832,14 @@ extern "C" int lg_attention_dropout_bwd_f32(const float* q, int64_t ldq, int64_t
     LG_REQUIRE_INIT();
     return attn_backward(kDropout, {{q, ldq, sbq}, {k, ldk, sbk}, {v, ldv, sbv}, {g, ldg, sbg}, p, {dq, lddq, sbdq}, {dk, lddk, sbdk},
                                     {dv, lddv, sbdv}, batch, heads, S, D, scale, prob, base});
+}
+
+extern "C" int lg_attention_causal_fwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
+                                           const float* v, int64_t ldv, int64_t sbv, float* o, int64_t ldo, int64_t sbo, float* p,
+                                           int64_t batch, int64_t heads, int64_t S, int64_t D, float scale,
+                                           const float* mask, int64_t sbm, double prob, uint64_t* base_out) {
+    LG_REQUIRE_INIT();
+    return attn_forward(kCausal, {{q, ldq, sbq}, {k, ldk, sbk}, {v, ldv, sbv}, {o, ldo, sbo}, p, batch, heads, S, D, scale, mask, sbm, prob, base_out});
 }
 
 #ifdef LG_GEMM_TIMELINE

@@ -1,6 +1,7 @@
 // What attention.hip (S <= 128: a (batch, head) pair lives in LDS) and attention_long.hip (129 .. 512: chunks stream through
 // LDS) share: the kernels' argument structs and small device helpers, and the ONE host path behind the eight lg_attention_*
-// launch entries - a call struct per direction, a descriptor per entry family, attn_forward / attn_backward (attention.hip).
+// launch entries and the causal forward entry - a call struct per direction, a descriptor per entry family, attn_forward /
+// attn_backward (attention.hip).
 #pragma once
 #include "common.h"
 #include "mfma_lds.h"
@@ -147,14 +148,15 @@ enum class AttnForm {
     ByLength                         // the dropout family: Long beyond 128, else Plain where the plain kernels can, else Tail
 };
 
-// what differs between the four entry families (plain, masked, long, dropout)
+// what differs between the entry families (plain, masked, long, dropout; causal: a forward only)
 struct AttnFamily {
     const char* fwd;                 // the entry points' names, for messages
     const char* bwd;
     int (*supported)(int64_t S, int64_t D);
     const char* range;               // the lengths `supported` takes, for the message of a refusal
     AttnForm form;                   // Plain takes no mask
-    bool dropout() const { return form == AttnForm::ByLength; }      // the DROP instantiations, and the checks only they need
+    bool causal = false;             // the causal forward entry: the CAUSAL instantiations by length, DROP where the call has a base_out
+    bool dropout() const { return form == AttnForm::ByLength && !causal; }      // the DROP instantiations, and the checks only they need
 };
 
 // the one path behind the launch entries (attention.hip): checks in their fixed order, arguments, launch
@@ -162,7 +164,7 @@ int attn_forward(const AttnFamily& f, const AttnFwdCall& c);
 int attn_backward(const AttnFamily& f, const AttnBwdCall& c);
 
 // attention_long.hip: the launches of its kernels (arguments checked, `shift` allocated; the caller checks the launch)
-int attn_long_launch_fwd(const AttnDropArgs& a, dim3 grid, int64_t D, bool drop);
+int attn_long_launch_fwd(const AttnDropArgs& a, dim3 grid, int64_t D, bool drop, bool causal = false);
 int attn_long_launch_bwd(const AttnBwdDropArgs& a, dim3 grid, int64_t D, bool drop);
 
 }  // namespace lg

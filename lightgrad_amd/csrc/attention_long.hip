@@ -25,7 +25,8 @@
 //
 // Layout.  The argument structs and device helpers are attention.hip's own (attention_common.h).  This file holds the long kernels,
 // one launcher per direction (attn_long_launch_fwd / _bwd, called by the shared host path of attention.hip - for the long
-// entries below and, beyond 128 positions, for the dropout entries) and the two lg_attention_long_* entries.
+// entries below and, beyond 128 positions, for the dropout entries and the causal forward entry) and the two
+// lg_attention_long_* entries.
 #include "attention_common.h"
 
 namespace lg {
@@ -52,7 +53,10 @@ constexpr int attn_long_fwd_lds_floats(int Sp) { return 32 * (D + 4) + 32 * (Sp 
 
 // DROP: dropout of the probabilities between the softmax and the context, from the stream of dropout.hip (one call per launch:
 // read `draws`, take a ticket, the last arriver advances).  P goes to HBM undropped; what feeds the context MFMAs is Pd.
-template <int D, bool DROP = false>
+// CAUSAL: query i sees keys j <= i (attention.hip: the selection of the softmax, +0.0 stored to P above the diagonal).  No key
+// beyond column q0 + 31 is anyone's in this block, so the K chunks and the V chunks end at the chunk that holds that column -
+// Sc = q0 + 32 stands where Sp stood: the same bound for the whole workgroup, about half the MFMAs over the grid.
+template <int D, bool DROP = false, bool CAUSAL = false>
 __global__ void __launch_bounds__(256) attn_long_fwd(std::conditional_t<DROP, AttnDropArgs, AttnTailArgs> a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int S = a.S, Sp = round32(S), PP = Sp + 4;
@@ -66,6 +70,7 @@ __global__ void __launch_bounds__(256) attn_long_fwd(std::conditional_t<DROP, At
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     const int q0 = blockIdx.x * 32, head = blockIdx.y, b = blockIdx.z;
     const int qrows = S - q0 < 32 ? S - q0 : 32;                      // rows of this block that exist: a row past them is never read
+    const int Sc = CAUSAL ? q0 + 32 : Sp;                             // the key columns the chunk loops cover (q0 + 32 <= Sp)
     const float* kg = a.k + int64_t(b) * a.sbk + head * D;
     const float* vg = a.v + int64_t(b) * a.sbv + head * D;
     [[maybe_unused]] unsigned long long* const call = rng_call_slot<DROP>();
@@ -97,12 +102,13 @@ __global__ void __launch_bounds__(256) attn_long_fwd(std::conditional_t<DROP, At
 
     // scores: the keys arrive in chunks of 128; wave w takes keys [c0 + 32 w, c0 + 32 w + 32) of the chunk, scaled (the product
     // rounded to fp32 first, like `scores * c`)
-    for (int c0 = 0; c0 < Sp; c0 += kLongChunk) {
-        chunk_store<D, NA>(rc, Buf, PQ, c0, S, Sp);
+    // (CAUSAL: columns [Sc, Sp) of the tile are never written: the softmax below deselects them before it looks at them)
+    for (int c0 = 0; c0 < Sc; c0 += kLongChunk) {
+        chunk_store<D, NA>(rc, Buf, PQ, c0, S, Sc);
         __syncthreads();
-        if (c0 + kLongChunk < Sp) chunk_load<D, NA>(rc, kg, a.ldk, c0 + kLongChunk, S);
+        if (c0 + kLongChunk < Sc) chunk_load<D, NA>(rc, kg, a.ldk, c0 + kLongChunk, S);
         else                      chunk_load<D, NA>(rc, vg, a.ldv, 0, S);                 // the first chunk of V flies behind the softmax
-        const int rows = Sp - c0 < kLongChunk ? Sp - c0 : kLongChunk;
+        const int rows = Sc - c0 < kLongChunk ? Sc - c0 : kLongChunk;
         if (32 * wave < rows) {
             af32x16 acc = zero16();
             wave_mma<true, true>(acc, Qs, PQ, Buf + 32 * wave * PQ, PQ, D, r, h);
@@ -122,6 +128,8 @@ __global__ void __launch_bounds__(256) attn_long_fwd(std::conditional_t<DROP, At
         [[maybe_unused]] unsigned long long seed = 0, base = 0;
         if constexpr (DROP) { seed = rng_uniform64(call[0]); base = rng_uniform64(call[1]); }
         const int row = tid >> 3, sub = tid & 7;
+        // the keys of this row: [0, S), CAUSAL [0, min(S, q0 + row + 1)) - key 0 is always one of them
+        const int vis = CAUSAL ? (q0 + row + 1 < S ? q0 + row + 1 : S) : S;
         float* pr = Ps + row * PP;
         af32x4 t[kLongMaxBlocks];
         float m = -INFINITY;
@@ -132,7 +140,7 @@ __global__ void __launch_bounds__(256) attn_long_fwd(std::conditional_t<DROP, At
                 t[i] = *reinterpret_cast<const af32x4*>(pr + c);
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    if (c + e < S) m = (t[i][e] > m || t[i][e] != t[i][e]) ? t[i][e] : m;
+                    if (c + e < vis) m = (t[i][e] > m || t[i][e] != t[i][e]) ? t[i][e] : m;
             }
         }
 #pragma unroll
@@ -144,7 +152,7 @@ __global__ void __launch_bounds__(256) attn_long_fwd(std::conditional_t<DROP, At
             if (c < Sp) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    if (c + e < S) { t[i][e] = expf(t[i][e] + (-m)); s += t[i][e]; }
+                    if (c + e < vis) { t[i][e] = expf(t[i][e] + (-m)); s += t[i][e]; }
                     else t[i][e] = 0.f;
                 }
             }
@@ -181,11 +189,11 @@ __global__ void __launch_bounds__(256) attn_long_fwd(std::conditional_t<DROP, At
     constexpr int NT = D / 32, KP = 4 / NT;
     const int n = wave % NT, kp = wave / NT;
     af32x16 acc = zero16();
-    for (int c0 = 0; c0 < Sp; c0 += kLongChunk) {
-        chunk_store<D, NA>(rc, Buf, PV, c0, S, Sp);
+    for (int c0 = 0; c0 < Sc; c0 += kLongChunk) {
+        chunk_store<D, NA>(rc, Buf, PV, c0, S, Sc);
         __syncthreads();                                              // (the first one also publishes the probabilities in LDS)
-        if (c0 + kLongChunk < Sp) chunk_load<D, NA>(rc, vg, a.ldv, c0 + kLongChunk, S);
-        const int rows = Sp - c0 < kLongChunk ? Sp - c0 : kLongChunk, kspan = rows / KP;
+        if (c0 + kLongChunk < Sc) chunk_load<D, NA>(rc, vg, a.ldv, c0 + kLongChunk, S);
+        const int rows = Sc - c0 < kLongChunk ? Sc - c0 : kLongChunk, kspan = rows / KP;
         wave_mma<true, false>(acc, Ps + c0 + kp * kspan, PP, Buf + kp * kspan * PV + 32 * n, PV, kspan, r, h);
         __syncthreads();
     }
@@ -488,12 +496,12 @@ __global__ void __launch_bounds__(256) attn_long_bwd(std::conditional_t<DROP, At
 }
 
 // ---- the launchers behind attn_forward / attn_backward (attention.hip): LDS size, allow_lds, launch -----------------------------
-template <int D, bool DROP>
+template <int D, bool DROP, bool CAUSAL = false>
 static int launch_long_fwd_as(const AttnDropArgs& a, dim3 grid) {
     const size_t bytes = size_t(attn_long_fwd_lds_floats<D>(round32(a.S))) * 4;
-    int rc = allow_lds(&attn_long_fwd<D, DROP>, bytes);
+    int rc = allow_lds(&attn_long_fwd<D, DROP, CAUSAL>, bytes);
     if (rc != LG_OK) return rc;
-    hipLaunchKernelGGL((attn_long_fwd<D, DROP>), grid, dim3(256), bytes, rt().stream, a);
+    hipLaunchKernelGGL((attn_long_fwd<D, DROP, CAUSAL>), grid, dim3(256), bytes, rt().stream, a);
     return LG_OK;
 }
 
@@ -506,10 +514,12 @@ static int launch_long_bwd_as(const AttnBwdDropArgs& a, dim3 grid) {
     return LG_OK;
 }
 
-int attn_long_launch_fwd(const AttnDropArgs& a, dim3 grid, int64_t D, bool drop) {
-    static int (*const table[2][2])(const AttnDropArgs&, dim3) = {             // [D == 64][drop]
-        {launch_long_fwd_as<32, false>, launch_long_fwd_as<32, true>}, {launch_long_fwd_as<64, false>, launch_long_fwd_as<64, true>}};
-    return table[D == 64][drop](a, grid);
+int attn_long_launch_fwd(const AttnDropArgs& a, dim3 grid, int64_t D, bool drop, bool causal) {
+    static int (*const table[2][2][2])(const AttnDropArgs&, dim3) = {          // [causal][D == 64][drop]
+        {{launch_long_fwd_as<32, false>, launch_long_fwd_as<32, true>}, {launch_long_fwd_as<64, false>, launch_long_fwd_as<64, true>}},
+        {{launch_long_fwd_as<32, false, true>, launch_long_fwd_as<32, true, true>},
+         {launch_long_fwd_as<64, false, true>, launch_long_fwd_as<64, true, true>}}};
+    return table[causal][D == 64][drop](a, grid);
 }
 
 int attn_long_launch_bwd(const AttnBwdDropArgs& a, dim3 grid, int64_t D, bool drop) {

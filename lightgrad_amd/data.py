@@ -57,3 +57,13 @@ def mask_tokens(ids, p: float = 0.15, mask_token_id: int = 103, vocab_size: int 
     if not isinstance(ids, AbstractTensor):
         raise TypeError("mask_tokens needs a tensor of int32 / int64 ids")
     return ids.mlm_mask(p, mask_token_id, vocab_size, special_ids=special_ids, ignore_index=ignore_index)
+
+
+def next_token_labels(ids, ignore_index: int = -100):
+    """the labels of the causal-LM objective: `ids.next_token_labels(...)` - `ids` shifted left by one along the last axis (position
+    i is to predict token i + 1) with `ignore_index` in the last column, which has nothing to predict and which
+    `loss.cross_entropy(..., ignore_index=)` leaves out.  Same dtype and shape; on the device for HipTensors, with no host read:
+    inside a captured graph every replay shifts what the ids hold then."""
+    if not isinstance(ids, AbstractTensor):
+        raise TypeError("next_token_labels needs a tensor of int32 / int64 ids")
+    return ids.next_token_labels(ignore_index)
