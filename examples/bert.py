@@ -23,6 +23,10 @@ Differences from the reference, on purpose:
     python examples/bert.py --clm [--graph] [--cpu]    # a causal language model of the same parameters: config key `causal=True`
                                                        # (query i sees keys j <= i, inside the fused attention launches) and the
                                                        # next-token objective (light.data.next_token_labels)
+    python examples/bert.py --generate 16 [--graph] [--cpu]   # greedy decoding with a key / value cache (nn.KVCache): the prompt once through
+                                                       # the causal forward, then one token per step against the cache - on HipTensor
+                                                       # two launches of attention per layer (csrc/decode.hip), nothing read back until
+                                                       # the ids are printed; --graph: the step is captured once and replayed
     python examples/bert.py --mlm --bf16-decoder       # the decoder onto the vocabulary (forward, dx, dW) on the bf16 matrix cores:
                                                        # config key `decoder_precision="bf16"`; tensors stay float32
 """
@@ -75,8 +79,13 @@ class BertEmbedding(nn.Module):
                     t.freeze()              # constants of the model: a backend may keep what it derives from them (and record it in graphs)
         return self._const_ids[key]
 
-    def forward(self, input_ids, token_type_ids=None):
+    def forward(self, input_ids, token_type_ids=None, token_position=None):
+        """`token_position`: an int32 tensor of one element on the ids' backend - the position of the ONE token per sequence that
+        `input_ids` (b, 1) holds (a decode step: looked up where the tensor lives, no host read); None: positions 0 .. s - 1"""
         zeros, position_ids = self._constant_ids(input_ids.__class__, input_ids.shape)
+        if token_position is not None:
+            assert input_ids.shape[-1] == 1, "a position goes with one token per sequence, got ids of shape %s" % (tuple(input_ids.shape),)
+            position_ids = token_position
         if token_type_ids is None:
             token_type_ids = zeros
         word, position, kind = self.word_embeddings.weight, self.position_embeddings.weight, self.token_type_embeddings.weight
@@ -114,7 +123,43 @@ class BertSelfAttention(nn.Module):
             self._tril[key] = t
         return self._tril[key]
 
-    def forward(self, hidden, attention_mask=None):
+    def _decode(self, hidden, attention_mask, cache, index):
+        """one new token per sequence against the cached keys and values: position t = the cache's position attends to keys 0 .. t
+        - the row the causal forward computes for query t.  attention_mask: None or (b, capacity) over the cache's rows"""
+        b = hidden.shape[0]
+        scale = math.sqrt(self.d) ** -1
+        k_cache, v_cache = cache.k[index], cache.v[index]
+        mask_ok = attention_mask is None or (attention_mask.dtype == np.float32 and not attention_mask.requires_grad and
+                                             tuple(attention_mask.shape) in ((b, cache.capacity), (1, cache.capacity)))
+        if hasattr(hidden, "self_attention_decode") and mask_ok and hidden.self_attention_decode_supported(self.query.weight, self.h, cache.capacity):
+            # the backend's one-node form: one launch for the three projections, one for the attention, which reads the position on
+            # the device and writes the new key / value rows into the cache itself
+            extra = {"mask": attention_mask} if attention_mask is not None else {}
+            context = hidden.self_attention_decode(self.query.weight, self.query.bias, self.key.weight, self.key.bias, self.value.weight,
+                                                   self.value.bias, k_cache, v_cache, cache.pos, heads=self.h, scale=scale, **extra)
+            return context, None
+        # the same over the tensor API: the host mirror of the position slices the cache
+        t = cache.length
+        assert t < cache.capacity, "the cache holds %d positions: no room for position %d" % (cache.capacity, t)
+        q, k, v = self.query(hidden), self.key(hidden), self.value(hidden)
+        k_cache[:, t:t + 1] = k
+        v_cache[:, t:t + 1] = v
+        q = q.reshape(b, 1, self.h, self.d).transpose(0, 2, 1, 3)
+        k = k_cache[:, :t + 1].reshape(b, t + 1, self.h, self.d).transpose(0, 2, 3, 1)
+        v = v_cache[:, :t + 1].reshape(b, t + 1, self.h, self.d).transpose(0, 2, 1, 3)
+        scores = (q @ k) / math.sqrt(self.d)
+        if attention_mask is not None:
+            mask = attention_mask[:, :t + 1]
+            scores = scores + ((1.0 - mask.reshape(mask.shape[0], 1, 1, t + 1)) * -10000.0).detach()
+        probs = scores.softmax(axis=-1)
+        return (probs @ v).transpose(0, 2, 1, 3).reshape(b, 1, self.h * self.d), probs
+
+    def forward(self, hidden, attention_mask=None, cache=None, index=None):
+        """cache (nn.KVCache) and index (this layer's): with tokens in the cache, `hidden` is one new token per sequence (`_decode`);
+        with an empty one, the prompt takes the path below and its keys and values become the cache's first rows"""
+        if cache is not None and cache.length > 0:
+            assert self.causal and hidden.shape[1] == 1, "a decode step is one token per sequence of a causal model"
+            return self._decode(hidden, attention_mask, cache, index)
         b, s, _ = hidden.shape
         # a padded batch (a mask) or a length the plain kernels do not take (no multiple of 32) goes to the backend's masked forms,
         # if it has them and the mask is what they read: a (b, s) or (1, s) float32 constant
@@ -140,8 +185,14 @@ class BertSelfAttention(nn.Module):
             extra = {"mask": attention_mask} if attention_mask is not None else {}
             context = hidden.self_attention(self.query.weight, self.query.bias, self.key.weight, self.key.bias,
                                             self.value.weight, self.value.bias, heads=self.h, scale=scale, **extra, **drop)
+            if cache is not None:
+                # the projection launch's q | k | v buffer: its key and value columns go to the cache on the device
+                width, qkv = self.h * self.d, context.attention_qkv
+                cache.fill(index, qkv[:, :, width:2 * width], qkv[:, :, 2 * width:])
             return context, context.attention_probs
         q, k, v = self.query(hidden), self.key(hidden), self.value(hidden)
+        if cache is not None:
+            cache.fill(index, k, v)
         flag = {"causal": True} if self.causal else {}
         if fused and (q.long_attention_supported(self.h, **flag) if long else
                       q.masked_attention_supported(self.h, **flag) if masked else q.attention_supported(self.h, **flag)):
@@ -181,8 +232,11 @@ class BertAttention(nn.Module):
         self.output.dense = nn.Linear(hidden_size, hidden_size)
         self.output.LayerNorm = nn.LayerNorm(hidden_size)
 
-    def forward(self, hidden_in, attention_mask=None):
-        hidden, probs = self.self(hidden_in, attention_mask=attention_mask)
+    def forward(self, hidden_in, attention_mask=None, cache=None, index=None):
+        if cache is None:
+            hidden, probs = self.self(hidden_in, attention_mask=attention_mask)
+        else:
+            hidden, probs = self.self(hidden_in, attention_mask=attention_mask, cache=cache, index=index)
         if self.training and self.dropout.p > 0:
             # dropout sits between the product and the residual addition, so the addition leaves the GEMM's epilogue
             norm = self.output.LayerNorm
@@ -207,8 +261,11 @@ class BertLayer(nn.Module):
         self.output.dense = nn.Linear(intermediate_size, hidden_size)
         self.output.LayerNorm = nn.LayerNorm(hidden_size)
 
-    def forward(self, hidden, attention_mask=None):
-        hidden, probs = self.attention(hidden, attention_mask)
+    def forward(self, hidden, attention_mask=None, cache=None, index=None):
+        if cache is None:
+            hidden, probs = self.attention(hidden, attention_mask)
+        else:
+            hidden, probs = self.attention(hidden, attention_mask, cache=cache, index=index)
         if self.training and self.dropout.p > 0:
             if hasattr(hidden, "feed_forward") and hasattr(hidden, "dropout_add_layer_norm"):
                 # the one-node feed-forward without its residual, then dropout, addition and LayerNorm in one launch
@@ -238,10 +295,33 @@ class BertModel(nn.Module):
                                                        attention_probs_dropout_prob, causal=causal)
                                              for _ in range(num_hidden_layers)])
 
-    def forward(self, input_ids, attention_mask=None, token_type_ids=None):
+    def forward(self, input_ids, attention_mask=None, token_type_ids=None, cache=None):
+        if cache is not None:
+            return self._forward_cached(input_ids, attention_mask, token_type_ids, cache)
         hidden = self.embeddings(input_ids, token_type_ids=token_type_ids)
         for layer in self.encoder.layer:
             hidden, _ = layer(hidden, attention_mask=attention_mask)
+        return hidden
+
+    def _forward_cached(self, input_ids, attention_mask, token_type_ids, cache):
+        """inference with an nn.KVCache, outside the tape.  An empty cache: `input_ids` (b, s0) is the prompt - the causal forward
+        as without a cache (attention_mask: None or (b, s0)), whose keys and values fill rows 0 .. s0 - 1 of every layer's cache
+        on the device; the position becomes s0.  Otherwise `input_ids` (b, 1) is the token at the cache's position (attention_mask:
+        None or (b, capacity) over the cache's rows); the caller moves the position on with `cache.advance()`"""
+        b, s = input_ids.shape
+        assert cache.layers == len(self.encoder.layer) and cache.batch == b, "the cache was made for %d layers and a batch of %d" % (cache.layers, cache.batch)
+        prefill = cache.length == 0
+        assert prefill or s == 1, "the cache holds %d positions: a decode step takes one token per sequence, got %d" % (cache.length, s)
+        assert s <= cache.capacity, "a prompt of %d tokens does not fit a cache of %d positions" % (s, cache.capacity)
+        with light.no_grad():
+            if prefill:
+                hidden = self.embeddings(input_ids, token_type_ids=token_type_ids)
+            else:
+                hidden = self.embeddings(input_ids, token_type_ids=token_type_ids, token_position=cache.pos)
+            for index, layer in enumerate(self.encoder.layer):
+                hidden, _ = layer(hidden, attention_mask=attention_mask, cache=cache, index=index)
+            if prefill:
+                cache.set_length(s)
         return hidden
 
 
@@ -259,13 +339,21 @@ class BertForMaskedLM(nn.Module):
         self.cls.predictions.decoder = nn.Linear(hidden_size, vocab_size, bias=False, precision=decoder_precision)
         self.cls.predictions.bias = light.zeros(vocab_size)
 
-    def forward(self, input_ids, attention_mask=None, token_type_ids=None, masked_positions=None):
+    def forward(self, input_ids, attention_mask=None, token_type_ids=None, masked_positions=None, cache=None):
+        if cache is not None:
+            # inference through an nn.KVCache (BertModel._forward_cached): the logits of every row given, outside the tape
+            h = self.bert(input_ids=input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids, cache=cache)
+            with light.no_grad():
+                return self.head(h)
         h = self.bert(input_ids=input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids)
         if masked_positions is not None:
             # only the positions to predict go through the head: a constant int tensor of flat indices into the (b * s) token rows,
             # of static length (b * max_predictions; a padded slot may name any row - its label carries the loss's ignore_index).
             # The logits then have len(masked_positions) rows; the gather's backward scatter-adds into the hidden rows
             h = h.reshape(-1, h.shape[-1])[masked_positions]
+        return self.head(h)
+
+    def head(self, h):
         t = self.cls.predictions.transform
         h = t.LayerNorm(gelu(t.dense(h)))
         return self.cls.predictions.decoder(h) + self.cls.predictions.bias
@@ -313,8 +401,98 @@ def clm_forward_backward(model, ids):
     return loss
 
 
+def decode_mask(attention_mask, capacity):
+    """a key-padding mask (b, s0) over a prompt as a decode step reads it: (b, capacity) over the cache's rows, ones behind the
+    prompt (a generated token is never padding); made on the mask's own backend"""
+    if attention_mask is None:
+        return None
+    b, s0 = attention_mask.shape
+    full = attention_mask.__class__.from_numpy(np.ones((b, capacity), dtype=attention_mask.dtype), requires_grad=False)
+    full[:, :s0] = attention_mask
+    return full
+
+
+def decode_step(model, cache, token, out_ids, mask=None):
+    """one greedy step, all on the ids' backend: the token (b, 1) at the cache's position goes through the model's decode forward
+    and the head, the argmax of its logits is written back into `token` and into column position + 1 of `out_ids`, and the
+    position moves on.  No host read, no value from the host: a captured step replays as it stands."""
+    logits = model(token, attention_mask=mask, cache=cache)                 # (b, 1, vocab)
+    cache.advance()
+    nxt = logits.argmax(-1).astype(np.int32)                                # (b, 1)
+    token[:, :] = nxt
+    out_ids[:, cache.pos] = nxt                                             # the column is the device position: s0 + steps done
+
+
+def generate(model, ids, max_new_tokens, attention_mask=None, cache=None, graph=None):
+    """greedy decoding of a model built with `causal=True`: (b, s0) prompt ids -> (b, s0 + max_new_tokens) int32 ids on the
+    prompt's backend.  The prompt is prefilled once through the causal forward, which fills an nn.KVCache (made here unless
+    given: one of exactly s0 + max_new_tokens positions); every further token is one `decode_step` on the last position only.
+    Nothing is read back to the host - the caller's `.numpy()` is the first read.  attention_mask: a key-padding mask (b, s0)
+    over the prompt.  graph: an empty HipGraph (HipTensor only) - the decode step is captured into it once after the prefill
+    and replayed for each of the max_new_tokens - 1 tokens behind the prompt's own."""
+    b, s0 = ids.shape
+    positions = model.bert.embeddings.position_embeddings.weight.shape[0]
+    layer0 = model.bert.encoder.layer[0].attention.self
+    assert layer0.causal, "generate needs a model built with causal=True"
+    assert max_new_tokens >= 1 and s0 >= 1
+    if cache is None:
+        cache = nn.KVCache(len(model.bert.encoder.layer), b, s0 + max_new_tokens, layer0.h * layer0.d, like=model.bert.embeddings.word_embeddings.weight)
+    assert s0 + max_new_tokens <= cache.capacity <= positions, \
+        "a prompt of %d tokens and %d new ones need a cache of at least %d positions, and the model has %d position embeddings (cache: %d)" % (
+            s0, max_new_tokens, s0 + max_new_tokens, positions, cache.capacity)
+    cache.reset()
+    ids32 = ids if ids.dtype == np.int32 else ids.astype(np.int32)
+    out_ids = ids.__class__.from_numpy(np.zeros((b, s0 + max_new_tokens), np.int32), requires_grad=False)
+    out_ids[:, :s0] = ids32
+    mask = decode_mask(attention_mask, cache.capacity)
+    # the prompt: every position at once; only its last row goes through the head
+    token = ids.__class__.from_numpy(np.zeros((b, 1), np.int32), requires_grad=False)      # the id buffer every step reads and writes
+    with light.no_grad():
+        hidden = model.bert(ids32, attention_mask=attention_mask, cache=cache)
+        token[:, :] = model.head(hidden[:, s0 - 1:s0]).argmax(-1).astype(np.int32)          # the first new token, position s0
+    out_ids[:, s0:s0 + 1] = token
+    steps = max_new_tokens - 1                        # the last new token is fed to nobody
+    if graph is None or steps == 0:
+        for _ in range(steps):
+            decode_step(model, cache, token, out_ids, mask)
+        return out_ids
+    # the first step once eagerly - it loads the kernels, fills the memory pool and uploads the constants of a (b, 1) forward -,
+    # then back to where the prefill left off: the recorded step writes the same row, token and column again
+    decode_step(model, cache, token, out_ids, mask)
+    cache.set_length(s0)
+    token[:, :] = out_ids[:, s0:s0 + 1]
+    with graph.capture():
+        decode_step(model, cache, token, out_ids, mask)           # recorded, not run: the host mirror moved on, the device position not
+    for i in range(steps):
+        graph.replay()
+        if i:
+            cache.replayed()
+    return out_ids
+
+
 if __name__ == "__main__":
     cpu = "--cpu" in sys.argv
+    if "--generate" in sys.argv:
+        n_new = int(sys.argv[sys.argv.index("--generate") + 1])
+        batch = int(sys.argv[sys.argv.index("--batch") + 1]) if "--batch" in sys.argv else 2
+        np.random.seed(0)
+        lm = BertForMaskedLM(**dict(TINY, causal=True)).eval()
+        prompt = light.from_numpy(np.random.randint(0, TINY["vocab_size"], (batch, 8)).astype(np.int32), requires_grad=False)
+        if not cpu:
+            lm.map_parameters(lambda t: t.hip())
+            prompt = prompt.hip(requires_grad=False)
+        recorded = None
+        if "--graph" in sys.argv and not cpu and n_new > 1:
+            from lightgrad_amd.autograd.hip import HipGraph
+            recorded = HipGraph()
+        t0 = time.perf_counter()
+        new_ids = generate(lm, prompt, n_new, graph=recorded).numpy()          # the only host read
+        print("generated %d tokens per sequence in %.1f ms (%s)" % (
+            n_new, 1e3 * (time.perf_counter() - t0),
+            "decode step captured once, %d kernels, replayed %d times" % (recorded.kernel_count(), n_new - 1) if recorded else "eager decode steps"))
+        for row in new_ids:
+            print(" ".join(str(i) for i in row[8:]))
+        sys.exit(0)
     if "--mlm" in sys.argv:
         light.manual_seed(0)
         forward_backward = mlm_forward_backward            # the masked-LM objective in place of the stand-in loss below

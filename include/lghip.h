@@ -625,6 +625,29 @@ int lg_attention_causal_fwd_f32(const float* q, int64_t ldq, int64_t sbq, const 
                                 int64_t batch, int64_t heads, int64_t S, int64_t D, float scale,
                                 const float* mask, int64_t sbm, double prob, uint64_t* base_out);
 
+/* ---- attention of ONE new token against a key / value cache (csrc/decode.hip) -----------------------------
+ * Incremental decoding of the causal model: with t = *pos, the position of the new token, read BY THE KERNEL from one word in
+ * device memory (a captured step replays with what the word holds then),
+ *   - k_new is written to row t of k_cache and v_new to row t of v_cache, bit for bit;
+ *   - o = softmax(scale * q K[0..t]^T + (1 - mask[0..t]) * -10000) V[0..t] per (batch, head); keys j > t take no part in the max
+ *     or the sum, exactly as in lg_attention_causal_fwd_f32;
+ *   - p, if given, holds the t + 1 probabilities followed by exact +0.0 up to `capacity`.
+ * Rows j > t of the caches are neither read nor written; row t is taken from k_new / v_new, not read back.  One workgroup per
+ * (batch, head) pair, K / V rows straight into registers, no matrix cores; every fold in a fixed order (same bits every run).
+ * t < 0 or t >= capacity: the launch writes nothing and raises the device status flag - LG_EINDEX at the next lg_sync /
+ * lg_memcpy_d2h, as for the index kernels.  Supported: D = 32 or 64, 1 <= capacity <= 512 (lg_attention_decode_supported, pure
+ * host code).  Checked in this order, each LG_EINVAL, before anything is launched: D / capacity; a pitch that is no multiple of
+ * 4 or a base that is not 16-byte aligned; ldc < heads * D; a mask with 0 < sbm < capacity. */
+int lg_attention_decode_supported(int64_t capacity, int64_t D);
+int lg_attention_decode_f32(const float* q, int64_t sbq,             /* the new token's rows: element (b, head, d) at x + b*sb + head*D + d */
+                            const float* k_new, int64_t sbk, const float* v_new, int64_t sbv,
+                            float* k_cache, float* v_cache, int64_t ldc, int64_t sbc,   /* (batch, capacity, heads*D), addressing as above */
+                            const int32_t* pos,                      /* ONE word in device memory: the position of the new token */
+                            float* o, int64_t sbo,                   /* context (batch, heads*D) */
+                            float* p,                                /* NULL, or probabilities (batch, heads, capacity), dense */
+                            int64_t batch, int64_t heads, int64_t capacity, int64_t D, float scale,
+                            const float* mask, int64_t sbm);         /* key-padding mask over the capacity; NULL = none */
+
 /* ---- two independent products in one launch ----------------------------------------------------------
  * lg_gemm_pair_begin(); <product 1>; <product 2>; lg_gemm_pair_end();   with products issued through
  * lg_gemm_f32 / lg_gemm_rowsum_f32 / lg_gemm_fused_f32.  If the first resolves to the 64x64 tile with an

@@ -5,9 +5,14 @@ The library has four entry families - plain, masked, long, and the dropout pair 
 goes through the same two helpers, `_launch_attention_fwd` / `_launch_attention_bwd`: the op names its form, `dropout > 0`
 takes the dropout entries instead.  That rule, and each symbol's name, stand here once.  `causal=True` on any op swaps the
 forward launch for the causal entry (one for every form, with or without dropout); the backward launch stays the form's own.
+
+`decode_attention` / `self_attention_decode` are the inference ops of incremental decoding: one new token against a key / value
+cache, over lg_attention_decode_f32 (csrc/decode.hip).  They share nothing with the forms above and stay outside the tape.
 """
 import ctypes
+import numpy as np
 from ..func import Function
+from ..grads import Gradients
 from ... import random as _random
 from .tensor import HipTensor, GradGroup, flush_lazy_readers
 from . import lib as _l
@@ -217,6 +222,7 @@ class self_attention(Function):
                                           (b, heads, s, width // heads), float(scale), mask3, dropout, bool(causal))
         ctx.save_for_backward(x, qkv, probs, heads, float(scale), form, dropout, drop_base)
         out.attention_probs = probs
+        out.attention_qkv = qkv             # q | k | v as the projection launch wrote them (a key / value cache copies its rows from here)
         return out
 
     def backward(ctx, out_grad):
@@ -269,3 +275,123 @@ class self_attention(Function):
 
 
 HipTensor.self_attention_supported = self_attention_supported
+
+
+""" Incremental decoding: one new token against a key / value cache (csrc/decode.hip) """
+
+_I32 = np.dtype(np.int32)
+
+
+def _inference_only(name, *operands):
+    """the decode ops have no backward: outside `no_grad` they refuse operands that ask for a gradient"""
+    if Gradients._is_enabled():
+        for t in operands:
+            assert t is None or not t.requires_grad, \
+                "%s is an inference op (no backward): run it under Gradients.no_grad(), or pass operands with requires_grad=False" % name
+
+
+def _token_row(t, name):
+    """(tensor, batch pitch) of the new token's (b, 1, width) or (b, width) rows as the decode kernel addresses them: width
+    contiguous, a batch pitch that is a multiple of 4, 16-byte aligned - a slice of a projection buffer is taken in place,
+    anything else is copied once"""
+    assert len(t._shape) in (2, 3) and (len(t._shape) == 2 or t._shape[1] == 1), "%s: expected (b, 1, width) or (b, width), got %s" % (name, t._shape)
+    st = t._strides
+    if (t._shape[-1] > 1 and st[-1] != 1) or (t._shape[0] > 1 and st[0] % 4) or t._byte_offset % 16:
+        t = t.contiguous()
+        st = t._strides
+    return t, (st[0] if t._shape[0] > 1 else 0)
+
+
+def _check_cache(name, k_cache, v_cache, pos, b, width):
+    for c in (k_cache, v_cache):
+        assert isinstance(c, HipTensor) and c._dtype == _F32 and len(c._shape) == 3 and c._shape[0] == b and c._shape[2] == width, \
+            "%s: the caches are float32 (batch, capacity, width) = (%d, *, %d) tensors, got %s" % (name, b, width, getattr(c, "_shape", c))
+        assert not c.requires_grad, "%s: a cache is state, not a parameter (requires_grad must be False)" % name
+    assert k_cache._shape == v_cache._shape and k_cache._strides == v_cache._strides, "%s: the two caches must have one shape and one layout" % name
+    # the kernel writes row t in place: a cache it cannot address as it lies is an error, never a copy
+    st = k_cache._strides
+    assert st[2] == 1 and st[1] % 4 == 0 and st[0] % 4 == 0 and st[1] >= width and k_cache._byte_offset % 16 == 0 and v_cache._byte_offset % 16 == 0, \
+        "%s: cache rows must be contiguous and 16-byte aligned with pitches that are multiples of 4 (strides %s)" % (name, st)
+    assert isinstance(pos, HipTensor) and pos._dtype == _I32 and pos.numel() == 1, "%s: pos is an int32 HipTensor of one element" % name
+
+
+def _launch_decode(name, q2, k2, v2, k_cache, v_cache, pos, out, heads, scale, mask, probs):
+    """q2, k2, v2: (address, batch pitch); out: (b, ..., width) dense.  Returns the probabilities (b, heads, 1, capacity) or None"""
+    b, capacity, width = k_cache._shape
+    mask3 = _key_mask(mask, b, capacity, name)
+    p = HipTensor.empty((b, heads, 1, capacity), requires_grad=False) if probs else None
+    flush_lazy_readers(k_cache)
+    flush_lazy_readers(v_cache)
+    _l.check(_l.lib().lg_attention_decode_f32(*q2, *k2, *v2, k_cache.ptr, v_cache.ptr, k_cache._strides[1], k_cache._strides[0], pos.ptr,
+                                              out.ptr, width, p.ptr if probs else None, b, heads, capacity, width // heads, float(scale),
+                                              mask3[1], mask3[2]))
+    return p
+
+
+def decode_attention_supported(q, heads, capacity):
+    """does `q.decode_attention(k_new, v_new, k_cache, v_cache, pos, heads, scale)` exist for this shape?  (b, 1, heads * d) or
+    (b, heads * d) float32 with d = 32 or 64, b >= 1 and a cache of 1 .. 512 rows"""
+    sh = q._shape
+    return (len(sh) in (2, 3) and (len(sh) == 2 or sh[1] == 1) and q._dtype == _F32 and sh[0] > 0 and sh[-1] % heads == 0
+            and bool(_l.lib().lg_attention_decode_supported(capacity, sh[-1] // heads)))
+
+
+def decode_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False):
+    """ attention of ONE new token per sequence against a key / value cache, one launch (lg_attention_decode_f32): with t = the
+    int32 word `pos` holds ON THE DEVICE, k_new / v_new become row t of the caches (b, capacity, heads * d) and the result is
+    softmax(scale * q K[0..t]^T + (1 - mask[0..t]) * -10000) V[0..t] per head - the row the causal forward computes for query t.
+    q, k_new, v_new: (b, 1, width) or (b, width); slices of one (b, 1, 3 * width) projection buffer are read in place.  mask:
+    float32 (b, capacity) or (1, capacity) over the cache's rows, None for none.  probs=True: `.attention_probs` (b, heads, 1,
+    capacity), exact zeros beyond t.  A position outside the cache writes nothing and raises IndexError at the next
+    synchronisation.  An inference op: the result is outside the tape. """
+    name = "decode_attention"
+    _inference_only(name, q, k_new, v_new)
+    _require_f32(q, k_new, v_new)
+    assert q._shape == k_new._shape == v_new._shape and decode_attention_supported(q, heads, k_cache._shape[1] if len(k_cache._shape) == 3 else 0), \
+        "%s: unsupported shapes %s / %s / %s with %d heads and caches %s" % (name, q._shape, k_new._shape, v_new._shape, heads, k_cache._shape)
+    _check_cache(name, k_cache, v_cache, pos, q._shape[0], q._shape[-1])
+    (q, sbq), (k_new, sbk), (v_new, sbv) = _token_row(q, name), _token_row(k_new, name), _token_row(v_new, name)
+    out = HipTensor.empty(q._shape, requires_grad=False)
+    p = _launch_decode(name, (q.ptr, sbq), (k_new.ptr, sbk), (v_new.ptr, sbv), k_cache, v_cache, pos, out, heads, scale, mask, probs)
+    if probs:
+        out.attention_probs = p
+    return out
+
+
+def self_attention_decode(x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False):
+    """ the one-node form of a decode step's attention: the three projections of the new token in ONE launch (lg_gemm_multi3_f32,
+    as in `self_attention`) into a (b, 1, 3 * width) buffer that the decode launch reads in place - two launches per layer.
+    x: (b, 1, hidden); everything else as for `decode_attention`. """
+    name = "self_attention_decode"
+    _inference_only(name, x, wq, bq, wk, bk, wv, bv)
+    _require_f32(x, wq, bq, wk, bk, wv, bv)
+    assert self_attention_decode_supported(x, wq, heads, k_cache._shape[1] if len(k_cache._shape) == 3 else 0) and \
+        wq._shape == wk._shape == wv._shape and bq._shape == bk._shape == bv._shape == (wq._shape[0],), \
+        "%s: unsupported shapes %s with weights %s / %s / %s, %d heads and caches %s" % (name, x._shape, wq._shape, wk._shape, wv._shape, heads, k_cache._shape)
+    b, _, hidden = x._shape
+    width = wq._shape[0]
+    _check_cache(name, k_cache, v_cache, pos, b, width)
+    x = x.contiguous()
+    ws, bs = [w.contiguous() for w in (wq, wk, wv)], [t.contiguous() for t in (bq, bk, bv)]
+    qkv = HipTensor.empty((b, 1, 3 * width), requires_grad=False)
+    base = qkv.ptr
+    _l.check(_l.lib().lg_gemm_multi3_f32(0, 1, b, width, hidden, x.ptr, hidden, _ptr3(*(w.ptr for w in ws)), hidden,
+                                         _ptr3(base, base + 4 * width, base + 8 * width), 3 * width, _ptr3(*(t.ptr for t in bs))))
+    out = HipTensor.empty((b, 1, width), requires_grad=False)
+    sb = 3 * width
+    p = _launch_decode(name, (base, sb), (base + 4 * width, sb), (base + 8 * width, sb), k_cache, v_cache, pos, out, heads, scale, mask, probs)
+    if probs:
+        out.attention_probs = p
+    return out
+
+
+def self_attention_decode_supported(x, wq, heads, capacity):
+    """does `x.self_attention_decode(...)` exist for these shapes?  (b, 1, hidden) input, (width, hidden) weights with width =
+    heads * d, d = 32 or 64, width a multiple of 64, a cache of 1 .. 512 rows"""
+    return (len(x._shape) == 3 and x._shape[1] == 1 and x._dtype == _F32 and len(wq._shape) == 2 and wq._shape[1] == x._shape[2]
+            and wq._shape[0] % heads == 0 and wq._shape[0] % 64 == 0 and x._shape[2] % 4 == 0 and x._shape[0] > 0
+            and bool(_l.lib().lg_attention_decode_supported(capacity, wq._shape[0] // heads)))
+
+
+HipTensor.decode_attention, HipTensor.decode_attention_supported = decode_attention, decode_attention_supported
+HipTensor.self_attention_decode, HipTensor.self_attention_decode_supported = self_attention_decode, self_attention_decode_supported

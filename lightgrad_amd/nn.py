@@ -281,3 +281,51 @@ class BatchNorm1d(_BatchNorm):
 class BatchNorm2d(_BatchNorm):
     """batch normalisation of (N, C, H, W) inputs"""
     _ranks = (4,)
+
+
+class KVCache(object):
+    """the keys and values of the tokens a causal model has seen, per layer: `k[i]`, `v[i]` of shape (batch, capacity, width) on
+    the backend (and in the dtype) of `like`, and the position of the NEXT token - `pos`, an int32 tensor of one element on that
+    backend, which the backend's decode attention and the position lookup read on the device, and `length`, its mirror on the
+    host for the backends that have no decode op (they slice the cache with it).  `advance()` adds 1 on the device with the
+    in-place int32 add - inside a hipGraph capture it is recorded like any kernel, and every replay moves the position on.
+    State, not parameters: not a Module, so it is in no `parameters()` / `buffers()` and never reaches an optimizer.  Not a
+    class of the reference (its model has no decoder)."""
+
+    def __init__(self, layers: int, batch: int, capacity: int, width: int, like=None):
+        cls = Tensor if like is None else type(like)
+        dtype = np.dtype(np.float32 if like is None else like.dtype)
+        assert layers >= 1 and batch >= 1 and capacity >= 1 and width >= 1
+        self.layers, self.batch, self.capacity, self.width = int(layers), int(batch), int(capacity), int(width)
+        shape = (self.batch, self.capacity, self.width)          # (an array of its own each: CpuTensor.from_numpy adopts what it is given)
+        self.k = [cls.from_numpy(np.zeros(shape, dtype), requires_grad=False) for _ in range(self.layers)]
+        self.v = [cls.from_numpy(np.zeros(shape, dtype), requires_grad=False) for _ in range(self.layers)]
+        self.pos = cls.from_numpy(np.zeros(1, np.int32), requires_grad=False)
+        self.length = 0
+
+    def advance(self, n: int = 1) -> None:
+        """the next token's position, + n: on the device, and in the host mirror"""
+        self.pos += int(n)
+        self.length += int(n)
+
+    def replayed(self, n: int = 1) -> None:
+        """a captured step that holds `advance()` was replayed n more times: the device position moved, the host mirror follows"""
+        self.length += int(n)
+
+    def set_length(self, n: int) -> None:
+        """rows 0 .. n - 1 have been filled (a prompt): the next token's position is n"""
+        assert 0 <= n <= self.capacity, "KVCache: %d positions do not fit a capacity of %d" % (n, self.capacity)
+        self.pos.fill(int(n))
+        self.length = int(n)
+
+    def reset(self) -> None:
+        """forget every token: the position goes back to 0 (the rows stay as they are - nothing reads beyond the position)"""
+        self.set_length(0)
+
+    def fill(self, layer: int, k, v) -> None:
+        """the keys / values (batch, s, width) of a prompt become rows 0 .. s - 1 of a layer, on the tensors' own backend"""
+        s = k.shape[1]
+        assert tuple(k.shape) == tuple(v.shape) == (self.batch, s, self.width) and s <= self.capacity, \
+            "KVCache: keys / values of shape %s / %s do not fit (%d, <= %d, %d)" % (tuple(k.shape), tuple(v.shape), self.batch, self.capacity, self.width)
+        self.k[layer][:, :s] = k
+        self.v[layer][:, :s] = v
