@@ -27,6 +27,10 @@ Differences from the reference, on purpose:
                                                        # the causal forward, then one token per step against the cache - on HipTensor
                                                        # two launches of attention per layer (csrc/decode.hip), nothing read back until
                                                        # the ids are printed; --graph: the step is captured once and replayed
+    python examples/bert.py --generate 16 --sample [--temperature T] [--top-k K] [--top-p P] [--seed S] [--graph] [--cpu]
+                                                       # sampled decoding: every token is `logits.sample(T, K, P)` - one launch
+                                                       # (csrc/sample.hip) in place of argmax + astype, drawn from the random stream
+                                                       # after light.manual_seed(S); under --graph every replay draws fresh numbers
     python examples/bert.py --mlm --bf16-decoder       # the decoder onto the vocabulary (forward, dx, dW) on the bf16 matrix cores:
                                                        # config key `decoder_precision="bf16"`; tensors stay float32
 """
@@ -412,21 +416,34 @@ def decode_mask(attention_mask, capacity):
     return full
 
 
-def decode_step(model, cache, token, out_ids, mask=None):
-    """one greedy step, all on the ids' backend: the token (b, 1) at the cache's position goes through the model's decode forward
-    and the head, the argmax of its logits is written back into `token` and into column position + 1 of `out_ids`, and the
-    position moves on.  No host read, no value from the host: a captured step replays as it stands."""
+def next_token(logits, sampler=None):
+    """(b, 1) int32 ids from (b, 1, vocab) logits: the argmax, or - sampler = (temperature, top_k, top_p) - one call of
+    `logits.sample`, which draws from the backend's random stream (one launch in place of argmax + astype)"""
+    if sampler is None:
+        return logits.argmax(-1).astype(np.int32)
+    temperature, top_k, top_p = sampler
+    return logits.sample(temperature=temperature, top_k=top_k, top_p=top_p, dtype=np.int32)
+
+
+def decode_step(model, cache, token, out_ids, mask=None, sampler=None):
+    """one step, all on the ids' backend: the token (b, 1) at the cache's position goes through the model's decode forward
+    and the head, the argmax of its logits (sampler=None: greedy) or a token sampled from them (sampler = (temperature, top_k,
+    top_p)) is written back into `token` and into column position + 1 of `out_ids`, and the position moves on.  No host read,
+    no value from the host: a captured step replays as it stands, and a sampling one draws fresh numbers at every replay."""
     logits = model(token, attention_mask=mask, cache=cache)                 # (b, 1, vocab)
     cache.advance()
-    nxt = logits.argmax(-1).astype(np.int32)                                # (b, 1)
+    nxt = next_token(logits, sampler)                                       # (b, 1)
     token[:, :] = nxt
     out_ids[:, cache.pos] = nxt                                             # the column is the device position: s0 + steps done
 
 
-def generate(model, ids, max_new_tokens, attention_mask=None, cache=None, graph=None):
-    """greedy decoding of a model built with `causal=True`: (b, s0) prompt ids -> (b, s0 + max_new_tokens) int32 ids on the
-    prompt's backend.  The prompt is prefilled once through the causal forward, which fills an nn.KVCache (made here unless
-    given: one of exactly s0 + max_new_tokens positions); every further token is one `decode_step` on the last position only.
+def generate(model, ids, max_new_tokens, attention_mask=None, cache=None, graph=None, temperature=None, top_k=0, top_p=1.0):
+    """decoding of a model built with `causal=True`: (b, s0) prompt ids -> (b, s0 + max_new_tokens) int32 ids on the
+    prompt's backend.  temperature=None is greedy; with a temperature every token - the prompt's own first one included - is
+    `logits.sample(temperature, top_k, top_p)`, drawn from the backend's random stream (`light.manual_seed`): one call of the
+    stream per token, eager or captured alike.
+    The prompt is prefilled once through the causal forward, which fills an nn.KVCache (made here unless given: one of exactly
+    s0 + max_new_tokens positions); every further token is one `decode_step` on the last position only.
     Nothing is read back to the host - the caller's `.numpy()` is the first read.  attention_mask: a key-padding mask (b, s0)
     over the prompt.  graph: an empty HipGraph (HipTensor only) - the decode step is captured into it once after the prefill
     and replayed for each of the max_new_tokens - 1 tokens behind the prompt's own."""
@@ -445,24 +462,27 @@ def generate(model, ids, max_new_tokens, attention_mask=None, cache=None, graph=
     out_ids = ids.__class__.from_numpy(np.zeros((b, s0 + max_new_tokens), np.int32), requires_grad=False)
     out_ids[:, :s0] = ids32
     mask = decode_mask(attention_mask, cache.capacity)
+    sampler = None if temperature is None else (temperature, top_k, top_p)
     # the prompt: every position at once; only its last row goes through the head
     token = ids.__class__.from_numpy(np.zeros((b, 1), np.int32), requires_grad=False)      # the id buffer every step reads and writes
     with light.no_grad():
         hidden = model.bert(ids32, attention_mask=attention_mask, cache=cache)
-        token[:, :] = model.head(hidden[:, s0 - 1:s0]).argmax(-1).astype(np.int32)          # the first new token, position s0
+        token[:, :] = next_token(model.head(hidden[:, s0 - 1:s0]), sampler)                 # the first new token, position s0
     out_ids[:, s0:s0 + 1] = token
     steps = max_new_tokens - 1                        # the last new token is fed to nobody
     if graph is None or steps == 0:
         for _ in range(steps):
-            decode_step(model, cache, token, out_ids, mask)
+            decode_step(model, cache, token, out_ids, mask, sampler)
         return out_ids
     # the first step once eagerly - it loads the kernels, fills the memory pool and uploads the constants of a (b, 1) forward -,
-    # then back to where the prefill left off: the recorded step writes the same row, token and column again
+    # then back to where the prefill left off: the recorded step writes the same row, token and column again.  This step is
+    # greedy even when sampling (its token is overwritten): it must not take a call of the random stream, so that the replays
+    # draw the calls the eager steps would; the prefill's own token has loaded the sampling kernel already
     decode_step(model, cache, token, out_ids, mask)
     cache.set_length(s0)
     token[:, :] = out_ids[:, s0:s0 + 1]
     with graph.capture():
-        decode_step(model, cache, token, out_ids, mask)           # recorded, not run: the host mirror moved on, the device position not
+        decode_step(model, cache, token, out_ids, mask, sampler)           # recorded, not run: the host mirror moved on, the device position not
     for i in range(steps):
         graph.replay()
         if i:
@@ -485,8 +505,15 @@ if __name__ == "__main__":
         if "--graph" in sys.argv and not cpu and n_new > 1:
             from lightgrad_amd.autograd.hip import HipGraph
             recorded = HipGraph()
+        sampling = {}
+        if "--sample" in sys.argv:
+            option = lambda name, kind, default: kind(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default     # noqa: E731
+            sampling = dict(temperature=option("--temperature", float, 1.0), top_k=option("--top-k", int, 0), top_p=option("--top-p", float, 1.0))
+            light.manual_seed(option("--seed", int, 0))
         t0 = time.perf_counter()
-        new_ids = generate(lm, prompt, n_new, graph=recorded).numpy()          # the only host read
+        new_ids = generate(lm, prompt, n_new, graph=recorded, **sampling).numpy()          # the only host read
+        if sampling:
+            print("sampled: temperature %(temperature)g, top_k %(top_k)d, top_p %(top_p)g" % sampling)
         print("generated %d tokens per sequence in %.1f ms (%s)" % (
             n_new, 1e3 * (time.perf_counter() - t0),
             "decode step captured once, %d kernels, replayed %d times" % (recorded.kernel_count(), n_new - 1) if recorded else "eager decode steps"))

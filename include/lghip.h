@@ -843,6 +843,36 @@ int lg_dropout_bwd_f32(const float* g, float* dx, int64_t n, double p, const uin
 int lg_mlm_mask(const void* ids, int itemsize, void* masked, void* labels, int64_t n, double p, int64_t mask_token_id,
                 int64_t vocab_size, const int64_t* special_ids, int n_special, int64_t ignore_index, uint64_t* base_out);
 
+/* ---- sampled decoding from the same stream (csrc/sample.hip) --------------------------------------------
+ * One token per row of fp32 logits [rows, cols] (row r at logits + r * row_pitch, the vocabulary contiguous) with temperature,
+ * top-k and top-p, in ONE launch.  ONE call of the stream: `draws` advances by exactly one, whatever the shape (rows == 0
+ * included: one workgroup is launched), and the value read is written to base_out[0].  For the call with draws == b, row r takes
+ * word 0 of philox4x32_10(counter = (lo32(r), hi32(r), lo32(b), hi32(b)), key = (lo32(seed), hi32(seed))) and
+ * u = ((word >> 8) + 0.5) * 2^-24, strictly inside (0, 1).  For a row x of V = cols logits:
+ *   1. m = max(x).  A DEGENERATE row - one that holds a NaN, or has m == +inf or m == -inf - answers its argmax under the rules
+ *      of lg_argreduce_f32 (the first NaN, the lowest index).  No status flag is raised; the output is always a valid index.
+ *   2. top-k, when 1 <= top_k < V (0 and >= V: off): v_k = the k-th largest value counted with multiplicity,
+ *      K = {j : x_j >= v_k} - ties at the boundary are all kept; comparisons on x only, -0.0 == +0.0.  Off: K is everything.
+ *   3. w_j = exp((x_j - m) * inv_T) for j in K, else 0;  inv_T = float(1.0 / temperature);  W = sum of w.
+ *   4. top-p, when 0 < top_p < 1 (1.0: off, tested explicitly): t = the largest value v occurring in K with
+ *      sum{w_j : x_j >= v} >= top_p * W;  N = {j in K : x_j >= t}.  Off: N = K.
+ *   5. the token is the lowest i in N with sum{w_j : j in N, j <= i} >= u * W', W' = the sum over N.  A -inf logit has weight 0
+ *      and is never returned.
+ * lightgrad_amd/random.py `sample_tokens` evaluates this in float64 and is the numpy backend.  The kernel holds every weight as
+ * the integer floor(2^40 * w_j) (2^(62 - bits(cols)) for rows of 2^22 elements and more): all its sums are exact and
+ * order-free, so the same logits, seed and call number give the same token on every run, and its token agrees with the
+ * float64 definition wherever u is further than the weights' rounding (about 1e-6 of cumulative probability) from a boundary.
+ * out: rows tokens of out_itemsize 4 (int32) or 8 (int64).  Seed and draws are read by the kernel and no host scalar depends on
+ * the data: the launch is legal under capture and draws fresh numbers on every replay.
+ * temperature > 0, finite, 1 / temperature finite in float; top_k >= 0; 0 < top_p <= 1; 0 <= rows <= 2^24; 1 <= cols < 2^31;
+ * row_pitch >= cols. */
+int lg_sample_f32(const float* logits, int64_t rows, int64_t cols, int64_t row_pitch, double temperature, int64_t top_k,
+                  double top_p, void* out, int out_itemsize, uint64_t* base_out);
+/* What the most recent lg_sample_f32 call of the calling thread launched: host bookkeeping for tests, no device work.
+ *   out[0] kernel: 0 = the row is held in LDS, 1 = the row is re-read from memory, -1 = nothing (a refused call)
+ *   out[1] threads per workgroup   out[2] passes over the row   out[3] 1 when the row is staged with 16-byte loads */
+int lg_sample_last_plan(int32_t out[4]);
+
 /* ---- hidden dropout inside the LayerNorm launches (csrc/rowwise.hip) ----------------------------------
  * A dropout that sits directly in front of or behind a LayerNorm over dense fp32 [rows, cols], drawn where the LayerNorm
  * kernel loads or stores its row.  ONE call of the stream above per forward; element i = row * cols + col of the dense operand

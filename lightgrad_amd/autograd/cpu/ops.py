@@ -389,6 +389,21 @@ def _mlm_mask(ids, p, mask_token_id, vocab_size, special_ids=(), ignore_index=-1
 CpuTensor.mlm_mask = _mlm_mask
 
 
+def _sample(logits, temperature=1.0, top_k=0, top_p=1.0, dtype=np.int64):
+    """ logits.sample(temperature=1.0, top_k=0, top_p=1.0, dtype=np.int64) -> one token per row of the last axis, drawn from
+    softmax(logits / temperature) restricted by top-k and top-p: `lightgrad_amd.random.sample_tokens` for this call's number - one
+    call of the stream, whatever the shape.  The result has the leading shape and is a constant of the tape. """
+    shape = logits.shape
+    temperature, top_k, top_p, dtype = _random.check_sample_arguments(logits.dtype, shape[-1] if len(shape) else None, temperature, top_k,
+                                                                      top_p, dtype)
+    seed, draw = _random._CpuGenerator.seed, _random._CpuGenerator.next_draw()
+    tokens = _random.sample_tokens(seed, draw, logits.data, temperature, top_k, top_p)
+    return CpuTensor.from_numpy(np.asarray(tokens, dtype=dtype), requires_grad=False)
+
+
+CpuTensor.sample = _sample
+
+
 def _next_token_labels(ids, ignore_index=-100):
     """ ids.next_token_labels(ignore_index=-100): the labels of the next-token objective - `ids` shifted left by one along the last
     axis, `ignore_index` in the last column; same dtype and shape, a constant of the tape. """

@@ -2419,6 +2419,32 @@ def _mlm_mask(ids, p, mask_token_id, vocab_size, special_ids=(), ignore_index=-1
 HipTensor.mlm_mask = _mlm_mask
 
 
+def _sample(logits, temperature=1.0, top_k=0, top_p=1.0, dtype=np.int64):
+    """ logits.sample(temperature=1.0, top_k=0, top_p=1.0, dtype=np.int64) -> one token per row of the last axis, drawn from
+    softmax(logits / temperature) restricted by top-k and top-p as `lightgrad_amd.random.sample_tokens` defines it: ONE launch of
+    csrc/sample.hip, which reads the generator's state from device memory and advances it by one call (a captured decode step
+    draws fresh numbers at every replay).  The result has the leading shape and is a constant of the tape; float32 only. """
+    if logits._dtype != _F32:
+        raise TypeError("sample is float32-only on HipTensor (got %s)" % logits._dtype)
+    shape = logits._shape
+    temperature, top_k, top_p, dtype = _random.check_sample_arguments(logits._dtype, shape[-1] if shape else None, temperature, top_k,
+                                                                      top_p, dtype)
+    cols, lead = shape[-1], shape[:-1]
+    rows = int(np.prod(lead, dtype=np.int64))
+    src = logits
+    walked = [st for n, st in zip(lead, src._strides[:-1]) if n != 1]
+    pitch = walked[-1] if walked else cols
+    if rows > 0 and ((cols > 1 and src._strides[-1] != 1) or pitch < cols or not _one_stride(lead, src._strides[:-1])):
+        src, pitch = logits.contiguous(), cols           # the vocabulary contiguous, one pitch from row to row
+    out = HipTensor.empty(lead, dtype=dtype, requires_grad=False)
+    base = _dropout_base()
+    _l.check(_l.lib().lg_sample_f32(src.ptr, rows, cols, _py.max(pitch, cols), temperature, top_k, top_p, out.ptr, dtype.itemsize, base.ptr))
+    return out
+
+
+HipTensor.sample = _sample
+
+
 def _next_token_labels(ids, ignore_index=-100):
     """ ids.next_token_labels(ignore_index=-100): the labels of the next-token objective - `ids` shifted left by one along the last
     axis, `ignore_index` in the last column; same dtype and shape, a constant of the tape.  One strided copy and one strided fill

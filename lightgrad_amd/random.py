@@ -21,6 +21,11 @@ and gets the label `ignore_index`; a selected one gets its id as label and becom
 the uniform token (uint64(w[2]) * vocab_size) >> 32 if w[1] < floor(0.9 * 2**32), and stays as it is otherwise.
 `mlm_mask_words` below is the definition; csrc/mlm.hip evaluates it on the device.
 
+`Tensor.sample` (sampled decoding: temperature, top-k, top-p) is one call of the same stream too: for the call with draws == b,
+ROW r of the logits takes word 0 of the block of counter r and u = ((word >> 8) + 0.5) * 2**-24.  `sample_tokens` below is the
+definition, in float64, and is the numpy backend; csrc/sample.hip evaluates it on the device with float32 weights held as
+integers - its token is the definition's wherever u is further than that rounding from a boundary of the cumulative weights.
+
     manual_seed(seed)        seed every backend's generator, draws back to 0
     get_state(backend)       (seed, draws) of "cpu" or "hip"
 """
@@ -100,6 +105,89 @@ def mlm_mask_words(seed: int, draw: int, ids, p: float, mask_token_id: int, voca
     masked = np.where(selected, replaced, flat).astype(ids.dtype)
     labels = np.where(selected, flat, ids.dtype.type(ignore_index)).astype(ids.dtype)
     return masked.reshape(ids.shape), labels.reshape(ids.shape)
+
+
+def check_sample_arguments(logits_dtype, vocab, temperature, top_k, top_p, dtype):
+    """the validated (temperature, top_k, top_p, dtype) of a `sample` call on logits of `logits_dtype` whose last axis is `vocab` wide"""
+    if not np.issubdtype(np.dtype(logits_dtype), np.floating):
+        raise ValueError("sample: the logits must be floating point (got %s)" % np.dtype(logits_dtype))
+    if vocab is None or vocab < 1:
+        raise ValueError("sample: the logits need a last axis of at least one element")
+    temperature, top_k, top_p = float(temperature), int(top_k), float(top_p)
+    if not (temperature > 0.0 and np.isfinite(temperature) and np.isfinite(np.float32(1.0 / temperature))):
+        raise ValueError("sample: temperature must be positive and finite, with 1 / temperature finite in float32 (got %r)" % temperature)
+    if top_k < 0:
+        raise ValueError("sample: top_k must be >= 0, 0 = off (got %r)" % top_k)
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError("sample: top_p must satisfy 0 < top_p <= 1, 1 = off (got %r)" % top_p)
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+        raise ValueError("sample: the tokens are int32 or int64 (got %s)" % dtype)
+    return temperature, top_k, top_p, dtype
+
+
+def sample_uniforms(seed: int, draw: int, rows: int) -> np.ndarray:
+    """u of rows 0 .. rows - 1 of call number `draw`: ((word 0 of the row's own block >> 8) + 0.5) * 2**-24, strictly inside (0, 1)"""
+    w0 = words(seed, draw, 4 * rows).reshape(rows, 4)[:, 0]                 # row r: the block of counter r
+    return ((w0 >> np.uint32(8)).astype(np.float64) + 0.5) * 2.0 ** -24
+
+
+def sample_tokens(seed: int, draw: int, logits, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0) -> np.ndarray:
+    """The definition of `Tensor.sample`, in float64: one token (int64) per row of `logits` (the last axis is the vocabulary,
+    the leading axes are the rows) for call number `draw` of the stream - ONE call, whatever the shape.  Row r draws
+    u = sample_uniforms(seed, draw, rows)[r].  For a row x with maximum m:
+      * a degenerate row (a NaN, m == +inf or m == -inf) answers numpy's argmax (the first NaN, the lowest index);
+      * top-k (1 <= top_k < V): K = {j : x_j >= the k-th largest value}, ties at the boundary kept; otherwise K is everything;
+      * w_j = exp((x_j - m) * float32(1 / temperature)) on K, 0 elsewhere; W = sum w;
+      * top-p (0 < top_p < 1): t = the largest value v occurring in K with sum{w_j : x_j >= v} >= top_p * W, N = {j in K : x_j >= t};
+        otherwise N = K;
+      * the token is the lowest i in N with sum{w_j : j in N, j <= i} >= u * W', W' = sum over N (if rounding leaves none: the
+        highest index of N with w > 0).  A -inf logit has weight 0 and is never returned."""
+    x = np.asarray(logits)
+    temperature, top_k, top_p, _ = check_sample_arguments(x.dtype, x.shape[-1] if x.ndim else None, temperature, top_k, top_p, np.int64)
+    lead, V = x.shape[:-1], x.shape[-1]
+    x = x.reshape(-1, V).astype(np.float64)
+    rows = x.shape[0]
+    tokens = np.zeros(rows, np.int64)
+    if rows == 0:
+        return tokens.reshape(lead)
+    u = sample_uniforms(seed, draw, rows)
+    inv_t = np.float64(np.float32(1.0 / np.float64(temperature)))
+    block = max(1, (1 << 21) // V)                                          # rows at a time: a bound on the temporaries
+    for r0 in range(0, rows, block):
+        xb, ub = x[r0:r0 + block], u[r0:r0 + block]
+        nan = np.isnan(xb).any(axis=1)
+        m = np.where(nan, np.nan, np.max(np.where(np.isnan(xb), 0.0, xb), axis=1))
+        degenerate = nan | np.isinf(m)
+        tok = np.argmax(xb, axis=1).astype(np.int64)                        # numpy's rules: what a degenerate row answers
+        live = np.flatnonzero(~degenerate)
+        if live.size:
+            xl, ml = xb[live], m[live][:, None]
+            if 1 <= top_k < V:
+                keep = xl >= np.partition(xl, V - top_k, axis=1)[:, V - top_k][:, None]
+            else:
+                keep = np.ones(xl.shape, bool)
+            w = np.where(keep, np.exp((xl - ml) * inv_t), 0.0)
+            if 0.0 < top_p < 1.0:
+                order = np.argsort(-xl, axis=1, kind="stable")
+                xs, cs = np.take_along_axis(xl, order, axis=1), np.cumsum(np.take_along_axis(w, order, axis=1), axis=1)
+                # the mass at or above a value: the running sum at the END of its run of equal values
+                last = np.concatenate([xs[:, 1:] != xs[:, :-1], np.ones((xs.shape[0], 1), bool)], axis=1)
+                ends = np.where(last, np.arange(V)[None, :], V)
+                ends = np.minimum.accumulate(ends[:, ::-1], axis=1)[:, ::-1]
+                mass = np.take_along_axis(cs, ends, axis=1)
+                reached = (mass >= top_p * w.sum(axis=1)[:, None]) & np.take_along_axis(keep, order, axis=1)
+                first = np.argmax(reached, axis=1)
+                t = np.where(reached.any(axis=1), xs[np.arange(xs.shape[0]), first], -np.inf)
+                keep &= xl >= t[:, None]
+                w = np.where(keep, w, 0.0)
+            c = np.cumsum(w, axis=1)
+            hit = c >= (ub[live] * w.sum(axis=1))[:, None]
+            hit &= w > 0.0
+            highest = V - 1 - np.argmax((w > 0.0)[:, ::-1], axis=1)
+            tok[live] = np.where(hit.any(axis=1), np.argmax(hit, axis=1), highest)
+        tokens[r0:r0 + block] = tok
+    return tokens.reshape(lead)
 
 
 def check_probability(p) -> float:
