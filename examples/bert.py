@@ -31,6 +31,10 @@ Differences from the reference, on purpose:
                                                        # sampled decoding: every token is `logits.sample(T, K, P)` - one launch
                                                        # (csrc/sample.hip) in place of argmax + astype, drawn from the random stream
                                                        # after light.manual_seed(S); under --graph every replay draws fresh numbers
+    python examples/bert.py --generate 16 --prefill-chunk 3 [--graph] [--cpu]
+                                                       # the prompt goes into the cache in pieces of at most 3 tokens, each piece
+                                                       # one attention launch per layer against the filled cache (csrc/extend.hip,
+                                                       # `model(ids, cache=cache, append=True)`): the same tokens
     python examples/bert.py --mlm --bf16-decoder       # the decoder onto the vocabulary (forward, dx, dW) on the bf16 matrix cores:
                                                        # config key `decoder_precision="bf16"`; tensors stay float32
 """
@@ -83,13 +87,19 @@ class BertEmbedding(nn.Module):
                     t.freeze()              # constants of the model: a backend may keep what it derives from them (and record it in graphs)
         return self._const_ids[key]
 
-    def forward(self, input_ids, token_type_ids=None, token_position=None):
+    def forward(self, input_ids, token_type_ids=None, token_position=None, token_positions=None):
         """`token_position`: an int32 tensor of one element on the ids' backend - the position of the ONE token per sequence that
-        `input_ids` (b, 1) holds (a decode step: looked up where the tensor lives, no host read); None: positions 0 .. s - 1"""
+        `input_ids` (b, 1) holds (a decode step: looked up where the tensor lives, no host read); `token_positions`: an int32 tensor
+        (m,) on the ids' backend - the positions of the m tokens per sequence of `input_ids` (b, m), shared by the batch (an append
+        to a filled cache: nn.KVCache.positions); neither: positions 0 .. s - 1"""
         zeros, position_ids = self._constant_ids(input_ids.__class__, input_ids.shape)
         if token_position is not None:
             assert input_ids.shape[-1] == 1, "a position goes with one token per sequence, got ids of shape %s" % (tuple(input_ids.shape),)
             position_ids = token_position
+        if token_positions is not None:
+            assert token_position is None and tuple(token_positions.shape) == (input_ids.shape[-1],), \
+                "position ids of shape %s do not go with ids of shape %s" % (tuple(token_positions.shape), tuple(input_ids.shape))
+            position_ids = token_positions
         if token_type_ids is None:
             token_type_ids = zeros
         word, position, kind = self.word_embeddings.weight, self.position_embeddings.weight, self.token_type_embeddings.weight
@@ -158,9 +168,57 @@ class BertSelfAttention(nn.Module):
         probs = scores.softmax(axis=-1)
         return (probs @ v).transpose(0, 2, 1, 3).reshape(b, 1, self.h * self.d), probs
 
-    def forward(self, hidden, attention_mask=None, cache=None, index=None):
+    def _triangle_behind(self, like, t, m):
+        """rows t .. t + m - 1 of the lower-triangular constant of t + m positions, (1, 1, m, t + m): query t + i sees keys 0 .. t + i"""
+        key = (like.__class__, t, m, np.dtype(like.dtype))
+        if key not in self._tril:
+            tri = like.__class__.from_numpy(np.tril(np.ones((1, 1, m, t + m), dtype=like.dtype), k=t), requires_grad=False)
+            if hasattr(tri, "freeze"):
+                tri.freeze()
+            self._tril[key] = tri
+        return self._tril[key]
+
+    def _extend(self, hidden, attention_mask, cache, index):
+        """m new tokens per sequence behind the cache's position t (any t >= 0): query row i at position t + i attends to keys
+        0 .. t + i - the rows the causal forward computes for queries t .. t + m - 1.  attention_mask: None or (b, capacity) over
+        the cache's rows"""
+        b, m = hidden.shape[0], hidden.shape[1]
+        scale = math.sqrt(self.d) ** -1
+        k_cache, v_cache = cache.k[index], cache.v[index]
+        mask_ok = attention_mask is None or (attention_mask.dtype == np.float32 and not attention_mask.requires_grad and
+                                             tuple(attention_mask.shape) in ((b, cache.capacity), (1, cache.capacity)))
+        if hasattr(hidden, "self_attention_extend") and mask_ok and hidden.self_attention_extend_supported(self.query.weight, self.h, cache.capacity):
+            # the backend's one-node form: one launch for the three projections, one for the attention, which reads the position on
+            # the device and writes the m new key / value rows into the cache itself
+            extra = {"mask": attention_mask} if attention_mask is not None else {}
+            context = hidden.self_attention_extend(self.query.weight, self.query.bias, self.key.weight, self.key.bias, self.value.weight,
+                                                   self.value.bias, k_cache, v_cache, cache.pos, heads=self.h, scale=scale, **extra)
+            return context, None
+        # the same over the tensor API: the host mirror of the position slices the cache
+        t = cache.length
+        n = t + m
+        assert n <= cache.capacity, "the cache holds %d of %d positions: no room for %d more" % (t, cache.capacity, m)
+        q, k, v = self.query(hidden), self.key(hidden), self.value(hidden)
+        k_cache[:, t:n] = k
+        v_cache[:, t:n] = v
+        q = q.reshape(b, m, self.h, self.d).transpose(0, 2, 1, 3)
+        k = k_cache[:, :n].reshape(b, n, self.h, self.d).transpose(0, 2, 3, 1)
+        v = v_cache[:, :n].reshape(b, n, self.h, self.d).transpose(0, 2, 1, 3)
+        scores = (q @ k) / math.sqrt(self.d)
+        if attention_mask is not None:
+            mask = attention_mask[:, :n]
+            scores = scores + ((1.0 - mask.reshape(mask.shape[0], 1, 1, n)) * -10000.0).detach()
+        scores = scores + ((1.0 - self._triangle_behind(scores, t, m)) * -10000.0).detach()
+        probs = scores.softmax(axis=-1)
+        return (probs @ v).transpose(0, 2, 1, 3).reshape(b, m, self.h * self.d), probs
+
+    def forward(self, hidden, attention_mask=None, cache=None, index=None, append=False):
         """cache (nn.KVCache) and index (this layer's): with tokens in the cache, `hidden` is one new token per sequence (`_decode`);
-        with an empty one, the prompt takes the path below and its keys and values become the cache's first rows"""
+        with an empty one, the prompt takes the path below and its keys and values become the cache's first rows.  append=True:
+        `hidden` is m >= 1 new tokens per sequence behind whatever the cache holds (`_extend`)"""
+        if cache is not None and append:
+            assert self.causal, "appending to a cache takes a causal model"
+            return self._extend(hidden, attention_mask, cache, index)
         if cache is not None and cache.length > 0:
             assert self.causal and hidden.shape[1] == 1, "a decode step is one token per sequence of a causal model"
             return self._decode(hidden, attention_mask, cache, index)
@@ -236,9 +294,11 @@ class BertAttention(nn.Module):
         self.output.dense = nn.Linear(hidden_size, hidden_size)
         self.output.LayerNorm = nn.LayerNorm(hidden_size)
 
-    def forward(self, hidden_in, attention_mask=None, cache=None, index=None):
+    def forward(self, hidden_in, attention_mask=None, cache=None, index=None, append=False):
         if cache is None:
             hidden, probs = self.self(hidden_in, attention_mask=attention_mask)
+        elif append:
+            hidden, probs = self.self(hidden_in, attention_mask=attention_mask, cache=cache, index=index, append=True)
         else:
             hidden, probs = self.self(hidden_in, attention_mask=attention_mask, cache=cache, index=index)
         if self.training and self.dropout.p > 0:
@@ -265,9 +325,11 @@ class BertLayer(nn.Module):
         self.output.dense = nn.Linear(intermediate_size, hidden_size)
         self.output.LayerNorm = nn.LayerNorm(hidden_size)
 
-    def forward(self, hidden, attention_mask=None, cache=None, index=None):
+    def forward(self, hidden, attention_mask=None, cache=None, index=None, append=False):
         if cache is None:
             hidden, probs = self.attention(hidden, attention_mask)
+        elif append:
+            hidden, probs = self.attention(hidden, attention_mask, cache=cache, index=index, append=True)
         else:
             hidden, probs = self.attention(hidden, attention_mask, cache=cache, index=index)
         if self.training and self.dropout.p > 0:
@@ -299,12 +361,33 @@ class BertModel(nn.Module):
                                                        attention_probs_dropout_prob, causal=causal)
                                              for _ in range(num_hidden_layers)])
 
-    def forward(self, input_ids, attention_mask=None, token_type_ids=None, cache=None):
+    def forward(self, input_ids, attention_mask=None, token_type_ids=None, cache=None, append=False):
         if cache is not None:
+            if append:
+                return self._forward_append(input_ids, attention_mask, token_type_ids, cache)
             return self._forward_cached(input_ids, attention_mask, token_type_ids, cache)
+        assert not append, "append=True goes with a cache"
         hidden = self.embeddings(input_ids, token_type_ids=token_type_ids)
         for layer in self.encoder.layer:
             hidden, _ = layer(hidden, attention_mask=attention_mask)
+        return hidden
+
+    def _forward_append(self, input_ids, attention_mask, token_type_ids, cache):
+        """inference with an nn.KVCache that may hold tokens already, outside the tape: `input_ids` (b, m) are the next m >= 1
+        tokens at the cache's position, whatever it is (attention_mask: None or (b, capacity) over the cache's rows, as a decode
+        step reads it).  Their keys and values become the cache's next m rows and every one of the m rows comes back; the caller
+        moves the position on with `cache.advance(m)`"""
+        b, m = input_ids.shape
+        positions = self.embeddings.position_embeddings.weight.shape[0]
+        assert cache.layers == len(self.encoder.layer) and cache.batch == b, "the cache was made for %d layers and a batch of %d" % (cache.layers, cache.batch)
+        assert m >= 1 and cache.length + m <= cache.capacity, \
+            "the cache holds %d of its %d positions: %d more tokens do not fit" % (cache.length, cache.capacity, m)
+        assert cache.length + m <= positions, \
+            "%d tokens behind the %d in the cache exceed the model's %d position embeddings" % (m, cache.length, positions)
+        with light.no_grad():
+            hidden = self.embeddings(input_ids, token_type_ids=token_type_ids, token_positions=cache.positions(m))
+            for index, layer in enumerate(self.encoder.layer):
+                hidden, _ = layer(hidden, attention_mask=attention_mask, cache=cache, index=index, append=True)
         return hidden
 
     def _forward_cached(self, input_ids, attention_mask, token_type_ids, cache):
@@ -343,10 +426,12 @@ class BertForMaskedLM(nn.Module):
         self.cls.predictions.decoder = nn.Linear(hidden_size, vocab_size, bias=False, precision=decoder_precision)
         self.cls.predictions.bias = light.zeros(vocab_size)
 
-    def forward(self, input_ids, attention_mask=None, token_type_ids=None, masked_positions=None, cache=None):
+    def forward(self, input_ids, attention_mask=None, token_type_ids=None, masked_positions=None, cache=None, append=False):
         if cache is not None:
-            # inference through an nn.KVCache (BertModel._forward_cached): the logits of every row given, outside the tape
-            h = self.bert(input_ids=input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids, cache=cache)
+            # inference through an nn.KVCache (BertModel._forward_cached, append=True: _forward_append): the logits of every row
+            # given, outside the tape
+            extra = {"append": True} if append else {}
+            h = self.bert(input_ids=input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids, cache=cache, **extra)
             with light.no_grad():
                 return self.head(h)
         h = self.bert(input_ids=input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids)
@@ -437,7 +522,30 @@ def decode_step(model, cache, token, out_ids, mask=None, sampler=None):
     out_ids[:, cache.pos] = nxt                                             # the column is the device position: s0 + steps done
 
 
-def generate(model, ids, max_new_tokens, attention_mask=None, cache=None, graph=None, temperature=None, top_k=0, top_p=1.0):
+def prefill_in_pieces(model, cache, ids32, mask, piece):
+    """(b, s0) ids through the append path (`model.bert(..., cache=cache, append=True)`) in pieces of at most `piece` tokens,
+    behind whatever the cache holds: each piece attends to the cache's rows and to itself, so the probabilities a layer holds at
+    a time are (b, heads, piece, capacity), not (b, heads, s0, s0).  Returns the hidden row (b, 1, hidden) of the last token -
+    the only one the head is asked about; the position has moved on by s0.  mask: None or (b, capacity) over the cache's rows"""
+    b, s0 = ids32.shape
+    hidden, n, buffers = None, 0, {}
+    for lo in range(0, s0, piece):
+        n = min(piece, s0 - lo)
+        if n == s0:
+            ids = ids32
+        else:
+            # an id buffer per piece length (ids are constants of a forward: a slice made under no_grad would not say so)
+            if n not in buffers:
+                buffers[n] = ids32.__class__.from_numpy(np.zeros((b, n), np.int32), requires_grad=False)
+            ids = buffers[n]
+            ids[:, :] = ids32[:, lo:lo + n]
+        hidden = model.bert(ids, attention_mask=mask, cache=cache, append=True)
+        cache.advance(n)
+    return hidden[:, n - 1:n]
+
+
+def generate(model, ids, max_new_tokens, attention_mask=None, cache=None, graph=None, temperature=None, top_k=0, top_p=1.0,
+             prefill_chunk=None, append=False):
     """decoding of a model built with `causal=True`: (b, s0) prompt ids -> (b, s0 + max_new_tokens) int32 ids on the
     prompt's backend.  temperature=None is greedy; with a temperature every token - the prompt's own first one included - is
     `logits.sample(temperature, top_k, top_p)`, drawn from the backend's random stream (`light.manual_seed`): one call of the
@@ -446,48 +554,67 @@ def generate(model, ids, max_new_tokens, attention_mask=None, cache=None, graph=
     s0 + max_new_tokens positions); every further token is one `decode_step` on the last position only.
     Nothing is read back to the host - the caller's `.numpy()` is the first read.  attention_mask: a key-padding mask (b, s0)
     over the prompt.  graph: an empty HipGraph (HipTensor only) - the decode step is captured into it once after the prefill
-    and replayed for each of the max_new_tokens - 1 tokens behind the prompt's own."""
+    and replayed for each of the max_new_tokens - 1 tokens behind the prompt's own.
+    prefill_chunk=c: the prompt goes through the append path in pieces of at most c tokens (`prefill_in_pieces`) - the same
+    tokens, with a layer's probabilities bounded by (b, heads, c, capacity).  append=True: `cache` (required) is NOT reset -
+    `ids` are appended behind the `cache.length` tokens it already holds (a second turn of a conversation; one piece unless
+    prefill_chunk is given) and decoding goes on from there; the result is the appended ids followed by the new ones, and
+    attention_mask, if given, is (b, capacity) over the cache's rows as a decode step reads it."""
     b, s0 = ids.shape
     positions = model.bert.embeddings.position_embeddings.weight.shape[0]
     layer0 = model.bert.encoder.layer[0].attention.self
     assert layer0.causal, "generate needs a model built with causal=True"
     assert max_new_tokens >= 1 and s0 >= 1
+    assert prefill_chunk is None or prefill_chunk >= 1, "prefill_chunk is a number of tokens >= 1"
+    assert not append or cache is not None, "append=True continues a cache: pass the one that holds the tokens so far"
     if cache is None:
         cache = nn.KVCache(len(model.bert.encoder.layer), b, s0 + max_new_tokens, layer0.h * layer0.d, like=model.bert.embeddings.word_embeddings.weight)
-    assert s0 + max_new_tokens <= cache.capacity <= positions, \
-        "a prompt of %d tokens and %d new ones need a cache of at least %d positions, and the model has %d position embeddings (cache: %d)" % (
-            s0, max_new_tokens, s0 + max_new_tokens, positions, cache.capacity)
-    cache.reset()
+    start = cache.length if append else 0               # tokens in front of `ids`
+    if append:
+        assert start + s0 + max_new_tokens <= cache.capacity <= positions, \
+            "%d tokens in the cache, %d appended and %d new ones need a cache of at least %d positions, and the model has %d position embeddings (cache: %d)" % (
+                start, s0, max_new_tokens, start + s0 + max_new_tokens, positions, cache.capacity)
+    else:
+        assert s0 + max_new_tokens <= cache.capacity <= positions, \
+            "a prompt of %d tokens and %d new ones need a cache of at least %d positions, and the model has %d position embeddings (cache: %d)" % (
+                s0, max_new_tokens, s0 + max_new_tokens, positions, cache.capacity)
+        cache.reset()
+    end = start + s0                                    # the position of the first new token
     ids32 = ids if ids.dtype == np.int32 else ids.astype(np.int32)
-    out_ids = ids.__class__.from_numpy(np.zeros((b, s0 + max_new_tokens), np.int32), requires_grad=False)
-    out_ids[:, :s0] = ids32
-    mask = decode_mask(attention_mask, cache.capacity)
+    # a column per position of the cache's sequence (a step writes column = device position); what is returned starts at `ids`
+    out_ids = ids.__class__.from_numpy(np.zeros((b, end + max_new_tokens), np.int32), requires_grad=False)
+    out_ids[:, start:end] = ids32
+    mask = attention_mask if append else decode_mask(attention_mask, cache.capacity)
     sampler = None if temperature is None else (temperature, top_k, top_p)
     # the prompt: every position at once; only its last row goes through the head
     token = ids.__class__.from_numpy(np.zeros((b, 1), np.int32), requires_grad=False)      # the id buffer every step reads and writes
     with light.no_grad():
-        hidden = model.bert(ids32, attention_mask=attention_mask, cache=cache)
-        token[:, :] = next_token(model.head(hidden[:, s0 - 1:s0]), sampler)                 # the first new token, position s0
-    out_ids[:, s0:s0 + 1] = token
+        if append or prefill_chunk is not None:
+            last = prefill_in_pieces(model, cache, ids32, mask, s0 if prefill_chunk is None else int(prefill_chunk))
+        else:
+            last = model.bert(ids32, attention_mask=attention_mask, cache=cache)[:, s0 - 1:s0]
+        token[:, :] = next_token(model.head(last), sampler)                                 # the first new token, position `end`
+    out_ids[:, end:end + 1] = token
+    result = (lambda: out_ids[:, start:]) if start else (lambda: out_ids)       # taken when every column is written: a slice may be a copy
     steps = max_new_tokens - 1                        # the last new token is fed to nobody
     if graph is None or steps == 0:
         for _ in range(steps):
             decode_step(model, cache, token, out_ids, mask, sampler)
-        return out_ids
+        return result()
     # the first step once eagerly - it loads the kernels, fills the memory pool and uploads the constants of a (b, 1) forward -,
     # then back to where the prefill left off: the recorded step writes the same row, token and column again.  This step is
     # greedy even when sampling (its token is overwritten): it must not take a call of the random stream, so that the replays
     # draw the calls the eager steps would; the prefill's own token has loaded the sampling kernel already
     decode_step(model, cache, token, out_ids, mask)
-    cache.set_length(s0)
-    token[:, :] = out_ids[:, s0:s0 + 1]
+    cache.set_length(end)
+    token[:, :] = out_ids[:, end:end + 1]
     with graph.capture():
         decode_step(model, cache, token, out_ids, mask, sampler)           # recorded, not run: the host mirror moved on, the device position not
     for i in range(steps):
         graph.replay()
         if i:
             cache.replayed()
-    return out_ids
+    return result()
 
 
 if __name__ == "__main__":
@@ -511,7 +638,12 @@ if __name__ == "__main__":
             sampling = dict(temperature=option("--temperature", float, 1.0), top_k=option("--top-k", int, 0), top_p=option("--top-p", float, 1.0))
             light.manual_seed(option("--seed", int, 0))
         t0 = time.perf_counter()
-        new_ids = generate(lm, prompt, n_new, graph=recorded, **sampling).numpy()          # the only host read
+        if "--prefill-chunk" in sys.argv:
+            pieces = dict(prefill_chunk=int(sys.argv[sys.argv.index("--prefill-chunk") + 1]))
+            print("prompt prefilled through the append path in pieces of at most %d tokens" % pieces["prefill_chunk"])
+        else:
+            pieces = {}
+        new_ids = generate(lm, prompt, n_new, graph=recorded, **sampling, **pieces).numpy()          # the only host read
         if sampling:
             print("sampled: temperature %(temperature)g, top_k %(top_k)d, top_p %(top_p)g" % sampling)
         print("generated %d tokens per sequence in %.1f ms (%s)" % (

@@ -648,6 +648,32 @@ int lg_attention_decode_f32(const float* q, int64_t sbq,             /* the new 
                             int64_t batch, int64_t heads, int64_t capacity, int64_t D, float scale,
                             const float* mask, int64_t sbm);         /* key-padding mask over the capacity; NULL = none */
 
+/* ---- attention of m NEW tokens against a filled key / value cache (csrc/extend.hip) --------------------------
+ * Appending to a cache that already holds t = *pos tokens (a second prompt, a prompt prefilled in pieces, a continuation to
+ * score, drafted tokens to verify): t is read BY THE KERNEL from one word in device memory, m is a host argument, and
+ *   - rows i = 0 .. m - 1 of k_new / v_new are written to rows t + i of k_cache / v_cache, bit for bit;
+ *   - for query row i: o_i = softmax(scale * q_i K[0..t+i]^T + (1 - mask[0..t+i]) * -10000) V[0..t+i] per (batch, head), where
+ *     K[j] / V[j] is the cache's row for j < t and row j - t of k_new / v_new for j >= t - taken from the new-token buffers,
+ *     never read back from the cache; keys j > t + i take no part in row i's max or sum, as in lg_attention_causal_fwd_f32;
+ *   - p, if given, is dense (batch, heads, m, capacity): row i holds its t + i + 1 probabilities, then exact +0.0 up to `capacity`.
+ * Cache rows >= t + m are neither read nor written, rows t .. t + m - 1 are written and never read: what they hold before the
+ * launch (NaN included) reaches nothing.  One workgroup per (block of 32 query rows, head, batch) on the fp32 matrix cores, K
+ * then V streamed through LDS in chunks of 128 rows up to the block's last visible key; every fold in a fixed order (same bits
+ * every run).  t < 0 or t + m > capacity: the launch writes nothing and raises the device status flag - LG_EINDEX at the next
+ * lg_sync / lg_memcpy_d2h, as for the decode and index kernels.  Supported: D = 32 or 64, 1 <= m <= capacity <= 512
+ * (lg_attention_extend_supported, pure host code).  Checked in this order, each LG_EINVAL, before anything is launched: D / m /
+ * capacity; (batch == 0 returns LG_OK here;) a pitch that is negative or no multiple of 4, or a base (p included) that is not
+ * 16-byte aligned; ldc < heads * D; a mask with 0 < sbm < capacity; k_new or v_new overlapping a cache. */
+int lg_attention_extend_supported(int64_t m, int64_t capacity, int64_t D);
+int lg_attention_extend_f32(const float* q, int64_t ldq, int64_t sbq,   /* the new tokens' rows: element (b, i, head, d) at x + b*sb + i*ld + head*D + d */
+                            const float* k_new, int64_t ldk, int64_t sbk, const float* v_new, int64_t ldv, int64_t sbv,
+                            float* k_cache, float* v_cache, int64_t ldc, int64_t sbc,   /* (batch, capacity, heads*D) */
+                            const int32_t* pos,                      /* ONE word in device memory: the position of new token 0 */
+                            float* o, int64_t ldo, int64_t sbo,      /* context (batch, m, heads*D), addressed like q */
+                            float* p,                                /* NULL, or probabilities (batch, heads, m, capacity), dense */
+                            int64_t batch, int64_t heads, int64_t m, int64_t capacity, int64_t D, float scale,
+                            const float* mask, int64_t sbm);         /* key-padding mask over the capacity; NULL = none */
+
 /* ---- two independent products in one launch ----------------------------------------------------------
  * lg_gemm_pair_begin(); <product 1>; <product 2>; lg_gemm_pair_end();   with products issued through
  * lg_gemm_f32 / lg_gemm_rowsum_f32 / lg_gemm_fused_f32.  If the first resolves to the 64x64 tile with an

@@ -395,3 +395,102 @@ def self_attention_decode_supported(x, wq, heads, capacity):
 
 HipTensor.decode_attention, HipTensor.decode_attention_supported = decode_attention, decode_attention_supported
 HipTensor.self_attention_decode, HipTensor.self_attention_decode_supported = self_attention_decode, self_attention_decode_supported
+
+
+""" Appending several tokens to a filled key / value cache in one attention launch (csrc/extend.hip) """
+
+
+def _token_rows_in_place(t, name):
+    """(tensor, row pitch, batch pitch) of (b, m, width) rows as the extend kernel addresses them: width contiguous, pitches that
+    are multiples of 4, 16-byte aligned - a slice of a projection buffer is taken in place, anything else is copied once"""
+    assert len(t._shape) == 3, "%s: expected (b, m, width), got %s" % (name, t._shape)
+    st = t._strides
+    if (t._shape[2] > 1 and st[2] != 1) or (t._shape[1] > 1 and (st[1] % 4 or st[1] < 0)) or (t._shape[0] > 1 and (st[0] % 4 or st[0] < 0)) \
+            or t._byte_offset % 16:
+        t = t.contiguous()
+        st = t._strides
+    return t, (st[1] if t._shape[1] > 1 else 0), (st[0] if t._shape[0] > 1 else 0)
+
+
+def _launch_extend(name, q3, k3, v3, m, k_cache, v_cache, pos, out, heads, scale, mask, probs):
+    """q3, k3, v3: (address, row pitch, batch pitch); out: (b, m, width) dense.  Returns the probabilities (b, heads, m, capacity) or None"""
+    b, capacity, width = k_cache._shape
+    mask3 = _key_mask(mask, b, capacity, name)
+    p = HipTensor.empty((b, heads, m, capacity), requires_grad=False) if probs else None
+    flush_lazy_readers(k_cache)
+    flush_lazy_readers(v_cache)
+    _l.check(_l.lib().lg_attention_extend_f32(*q3, *k3, *v3, k_cache.ptr, v_cache.ptr, k_cache._strides[1], k_cache._strides[0], pos.ptr,
+                                              out.ptr, width, m * width, p.ptr if probs else None, b, heads, m, capacity, width // heads,
+                                              float(scale), mask3[1], mask3[2]))
+    return p
+
+
+def extend_attention_supported(q, heads, capacity):
+    """does `q.extend_attention(k_new, v_new, k_cache, v_cache, pos, heads, scale)` exist for this shape?  (b, m, heads * d) float32
+    with d = 32 or 64, b >= 1 and 1 <= m <= capacity <= 512"""
+    sh = q._shape
+    return (len(sh) == 3 and q._dtype == _F32 and sh[0] > 0 and sh[2] % heads == 0
+            and bool(_l.lib().lg_attention_extend_supported(sh[1], capacity, sh[2] // heads)))
+
+
+def extend_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False):
+    """ attention of m NEW tokens per sequence against a filled key / value cache, one launch (lg_attention_extend_f32): with t =
+    the int32 word `pos` holds ON THE DEVICE, rows i of k_new / v_new become rows t + i of the caches (b, capacity, heads * d) and
+    row i of the result is softmax(scale * q_i K[0..t+i]^T + (1 - mask[0..t+i]) * -10000) V[0..t+i] per head - the rows the causal
+    forward computes for queries t .. t + m - 1.  q, k_new, v_new: (b, m, width); slices of one (b, m, 3 * width) projection
+    buffer are read in place.  mask: float32 (b, capacity) or (1, capacity) over the cache's rows, None for none.  probs=True:
+    `.attention_probs` (b, heads, m, capacity), exact zeros beyond column t + i of row i.  t < 0 or t + m > capacity writes
+    nothing and raises IndexError at the next synchronisation.  An inference op: the result is outside the tape. """
+    name = "extend_attention"
+    _inference_only(name, q, k_new, v_new)
+    _require_f32(q, k_new, v_new)
+    assert q._shape == k_new._shape == v_new._shape and extend_attention_supported(q, heads, k_cache._shape[1] if len(k_cache._shape) == 3 else 0), \
+        "%s: unsupported shapes %s / %s / %s with %d heads and caches %s" % (name, q._shape, k_new._shape, v_new._shape, heads, k_cache._shape)
+    _check_cache(name, k_cache, v_cache, pos, q._shape[0], q._shape[2])
+    m = q._shape[1]
+    (q, ldq, sbq), (k_new, ldk, sbk), (v_new, ldv, sbv) = (_token_rows_in_place(t, name) for t in (q, k_new, v_new))
+    out = HipTensor.empty(q._shape, requires_grad=False)
+    p = _launch_extend(name, (q.ptr, ldq, sbq), (k_new.ptr, ldk, sbk), (v_new.ptr, ldv, sbv), m, k_cache, v_cache, pos, out, heads, scale, mask, probs)
+    if probs:
+        out.attention_probs = p
+    return out
+
+
+def self_attention_extend(x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False):
+    """ the one-node form of an append's attention: the three projections of the m new tokens in ONE launch (lg_gemm_multi3_f32,
+    as in `self_attention`) into a (b, m, 3 * width) buffer that the extend launch reads in place - two launches per layer.
+    x: (b, m, hidden); everything else as for `extend_attention`. """
+    name = "self_attention_extend"
+    _inference_only(name, x, wq, bq, wk, bk, wv, bv)
+    _require_f32(x, wq, bq, wk, bk, wv, bv)
+    assert self_attention_extend_supported(x, wq, heads, k_cache._shape[1] if len(k_cache._shape) == 3 else 0) and \
+        wq._shape == wk._shape == wv._shape and bq._shape == bk._shape == bv._shape == (wq._shape[0],), \
+        "%s: unsupported shapes %s with weights %s / %s / %s, %d heads and caches %s" % (name, x._shape, wq._shape, wk._shape, wv._shape, heads, k_cache._shape)
+    b, m, hidden = x._shape
+    width = wq._shape[0]
+    _check_cache(name, k_cache, v_cache, pos, b, width)
+    x = x.contiguous()
+    ws, bs = [w.contiguous() for w in (wq, wk, wv)], [t.contiguous() for t in (bq, bk, bv)]
+    qkv = HipTensor.empty((b, m, 3 * width), requires_grad=False)
+    base = qkv.ptr
+    _l.check(_l.lib().lg_gemm_multi3_f32(0, 1, b * m, width, hidden, x.ptr, hidden, _ptr3(*(w.ptr for w in ws)), hidden,
+                                         _ptr3(base, base + 4 * width, base + 8 * width), 3 * width, _ptr3(*(t.ptr for t in bs))))
+    out = HipTensor.empty((b, m, width), requires_grad=False)
+    ld, sb = 3 * width, m * 3 * width
+    p = _launch_extend(name, (base, ld, sb), (base + 4 * width, ld, sb), (base + 8 * width, ld, sb), m, k_cache, v_cache, pos, out, heads, scale,
+                       mask, probs)
+    if probs:
+        out.attention_probs = p
+    return out
+
+
+def self_attention_extend_supported(x, wq, heads, capacity):
+    """does `x.self_attention_extend(...)` exist for these shapes?  (b, m, hidden) input, (width, hidden) weights with width =
+    heads * d, d = 32 or 64, width a multiple of 64, 1 <= m <= capacity <= 512"""
+    return (len(x._shape) == 3 and x._dtype == _F32 and len(wq._shape) == 2 and wq._shape[1] == x._shape[2]
+            and wq._shape[0] % heads == 0 and wq._shape[0] % 64 == 0 and x._shape[2] % 4 == 0 and x._shape[0] > 0
+            and bool(_l.lib().lg_attention_extend_supported(x._shape[1], capacity, wq._shape[0] // heads)))
+
+
+HipTensor.extend_attention, HipTensor.extend_attention_supported = extend_attention, extend_attention_supported
+HipTensor.self_attention_extend, HipTensor.self_attention_extend_supported = self_attention_extend, self_attention_extend_supported

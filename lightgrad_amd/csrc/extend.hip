@@ -1,0 +1,300 @@
+// Attention of m NEW tokens against a filled key / value cache in one launch (gfx950, fp32 MFMA): lg_attention_extend_f32.
+//
+// Between the causal forward (the whole prompt, an empty cache: attention.hip / attention_long.hip) and the decode kernel (one
+// token, a filled cache: decode.hip).  With t = the word `pos` holds on the device, query row i sits at position t + i and
+// sees keys 0 .. t + i: the cache's rows 0 .. t - 1, then rows 0 .. i of k_new / v_new - which this launch also writes to rows
+// t .. t + m - 1 of the caches, and which it always takes from the new-token buffers, never back from the cache (other
+// workgroups of the same launch write those rows).  m query rows against up to 512 keys is a matrix-matrix problem: the
+// kernel is attn_long_fwd<D, false, CAUSAL = true> (attention_long.hip) with four differences.
+//
+//   partition   one workgroup of 256 threads (4 waves) per (block of 32 query rows, head, batch)
+//   bound       the chunk loops end at Kend = round32(t + q0 + rows of the block): formed on the device from t; LDS is sized on
+//               the host by round32(capacity), which Kend never exceeds (t + m <= capacity)
+//   seam        key j of a streamed chunk comes from the cache (j < t), from k_new / v_new (t <= j < t + m) or is ZERO in LDS
+//               (j >= t + m): the address is selected per float4, so the seam can fall anywhere inside a chunk; a row that does
+//               not exist is never multiplied - cache rows >= t may hold NaN
+//   diagonal    row i of the block sees the columns [0, t + q0 + i]: the softmax selects, nothing is multiplied by a mask
+//   cache rows  the workgroup stores the 32 new K / V rows of its own block and head to rows t + q0 .. of the caches
+//
+// Everything else is the model's: Q rows of the block (pitch D + 4), the 32 x (Cp + 4) tile of scores / probabilities, ONE chunk
+// buffer of 128 rows through which K (pitch D + 4), then V (pitch D + 8) stream with the next chunk's global loads issued ahead
+// of the MFMAs, wave w on keys [32 w, 32 w + 32) of a chunk for the scores, the three-pass softmax with 8 threads per row,
+// context tiles split over the waves with the partial sums in registers across the chunks and ONE fold through LDS in wave
+// order: the same bits every run, and a (batch, head, block) triple's bits depend on its own data and t only.
+// LDS at D = 64, capacity = 512: 32 * 68 + 32 * 516 + 128 * 72 + 3072 + 512 floats = 126 KB - one workgroup per CU.
+#include "attention_common.h"
+
+namespace lg {
+
+constexpr int kExtChunk = 128;         // rows of a streamed operand in LDS at a time
+constexpr int kExtMaxBlocks = 16;      // 32-column blocks of the longest row (512 / 32)
+constexpr int kExtMaxKeys = 512;
+
+struct ExtendArgs {
+    const float *q, *k_new, *v_new;      // element (b, i, head, d) at x + b * sbX + i * ldX + head * D + d
+    int64_t ldq, sbq, ldk, sbk, ldv, sbv;
+    float *k_cache, *v_cache;            // element (b, j, head, d) at x + b * sbc + j * ldc + head * D + d
+    int64_t ldc, sbc;
+    const int32_t* pos;
+    float* o;                            // context, addressed like q
+    int64_t ldo, sbo;
+    float* p;                            // NULL, or (batch, heads, m, capacity) dense
+    int heads, capacity, m;
+    float scale;
+    const float* mask;                   // element (b, j) at mask + b * sbm + j; NULL = none
+    int64_t sbm;
+    int* status;
+};
+
+template <int D>
+constexpr int attn_extend_lds_floats(int Cp) { return 32 * (D + 4) + 32 * (Cp + 4) + kExtChunk * (D + 8) + 3 * 1024 + Cp; }
+
+// keys [c0, c0 + 128) of the stream: global -> registers.  Key j < t is the cache's row j, key j >= t row j - t of the new
+// tokens (clamped to a row that exists: what a key >= t + m loads is dropped by seam_store); no branch, all loads in flight
+template <int D, int N>
+__device__ __forceinline__ void seam_load(af32x4 (&v)[N], const float* cache, int64_t ldc, const float* fresh, int64_t ldn, int c0, int t, int m) {
+    constexpr int Q = D / 4;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const int f = threadIdx.x + i * 256, j = c0 + f / Q;
+        const int jn = j - t < 0 ? 0 : (j - t < m ? j - t : m - 1);
+        const float* src = j < t ? cache + int64_t(j) * ldc : fresh + int64_t(jn) * ldn;
+        v[i] = *reinterpret_cast<const af32x4*>(src + (f % Q) * 4);
+    }
+}
+// ... and registers -> LDS: keys [t + m, Kend) of the chunk ZERO
+template <int D, int N>
+__device__ __forceinline__ void seam_store(const af32x4 (&v)[N], float* dst, int pitch, int c0, int keys, int Kend) {
+    const int left = keys - c0, rows = left < 0 ? 0 : (left < kExtChunk ? left : kExtChunk);
+    const int padded = Kend - c0 < kExtChunk ? Kend - c0 : kExtChunk;
+    store_rows_padded<D, N>(v, dst, pitch, rows, padded);
+}
+
+template <int D>
+__global__ void __launch_bounds__(256) attn_extend(const ExtendArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int m = a.m, C = a.capacity, Cp = round32(C), PP = Cp + 4;
+    constexpr int PQ = D + 4, PV = D + 8, Q4 = D / 4;
+    constexpr int NB = 32 * Q4 / 256, NA = kExtChunk * Q4 / 256;
+    const int t = *a.pos;
+    const int tid = threadIdx.x;
+    if (t < 0 || t > C - m) {
+        // a bounds check, never a fault: nothing is written, the next synchronising call reports LG_EINDEX
+        if (tid == 0) __hip_atomic_fetch_or(a.status, LG_STATUS_BAD_INDEX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        return;
+    }
+    float* Qs = lds;                      // Q rows of the block                    32 x PQ
+    float* Ps = Qs + 32 * PQ;             // scores, then probabilities             32 x PP
+    float* Buf = Ps + 32 * PP;            // a chunk of K (pitch PQ), then of V (pitch PV)
+    float* Red = Buf + kExtChunk * PV;
+    float* Bias = Red + 3 * 1024;         // what key j adds to every score of its column
+    const int lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+    const int q0 = blockIdx.x * 32, head = blockIdx.y, b = blockIdx.z;
+    const int qrows = m - q0 < 32 ? m - q0 : 32;                      // rows of this block that exist
+    const int keys = t + m;                                           // keys that exist in this launch
+    const int Kend = round32(t + q0 + qrows);                         // the key columns the chunk loops cover (<= Cp)
+    const float* kc = a.k_cache + int64_t(b) * a.sbc + head * D;
+    const float* vc = a.v_cache + int64_t(b) * a.sbc + head * D;
+    const float* kn = a.k_new + int64_t(b) * a.sbk + head * D;
+    const float* vn = a.v_new + int64_t(b) * a.sbv + head * D;
+
+    af32x4 rc[NA];
+    {
+        af32x4 rq[NB], rk[NB], rv[NB];
+        load_rows<D, NB>(rq, a.q + int64_t(b) * a.sbq + int64_t(q0) * a.ldq + head * D, a.ldq, qrows);
+        load_rows<D, NB>(rk, kn + int64_t(q0) * a.ldk, a.ldk, qrows);
+        load_rows<D, NB>(rv, vn + int64_t(q0) * a.ldv, a.ldv, qrows);
+        seam_load<D, NA>(rc, kc, a.ldc, kn, a.ldk, 0, t, m);
+        store_rows_padded<D, NB>(rq, Qs, PQ, qrows, 32);
+        // the block's own new rows become rows t + q0 .. of the caches, bit for bit; nothing in this launch reads them there
+        float* kd = a.k_cache + int64_t(b) * a.sbc + int64_t(t + q0) * a.ldc + head * D;
+        float* vd = a.v_cache + int64_t(b) * a.sbc + int64_t(t + q0) * a.ldc + head * D;
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            const int f = tid + i * 256;
+            if (f < qrows * Q4) {
+                *reinterpret_cast<af32x4*>(kd + int64_t(f / Q4) * a.ldc + (f % Q4) * 4) = rk[i];
+                *reinterpret_cast<af32x4*>(vd + int64_t(f / Q4) * a.ldc + (f % Q4) * 4) = rv[i];
+            }
+        }
+        // (1.0 - mask) * -10000.0 in fp32, the composite's own arithmetic; -0.0f where the mask is 1 or absent or the key does
+        // not exist: adding it changes no bit of a score
+        for (int j = tid; j < Kend; j += 256) Bias[j] = (j < keys && a.mask) ? (1.0f - a.mask[int64_t(b) * a.sbm + j]) * -10000.0f : -0.0f;
+    }
+
+    // scores: the keys arrive in chunks of 128; wave w takes keys [c0 + 32 w, c0 + 32 w + 32) of the chunk, scaled (the product
+    // rounded to fp32 first, like `scores * c`).  Columns [Kend, Cp) of the tile are never written and never read
+    for (int c0 = 0; c0 < Kend; c0 += kExtChunk) {
+        seam_store<D, NA>(rc, Buf, PQ, c0, keys, Kend);
+        __syncthreads();
+        if (c0 + kExtChunk < Kend) seam_load<D, NA>(rc, kc, a.ldc, kn, a.ldk, c0 + kExtChunk, t, m);
+        else                       seam_load<D, NA>(rc, vc, a.ldc, vn, a.ldv, 0, t, m);      // the first chunk of V flies behind the softmax
+        const int rows = Kend - c0 < kExtChunk ? Kend - c0 : kExtChunk;
+        if (32 * wave < rows) {
+            af32x16 acc = zero16();
+            wave_mma<true, true>(acc, Qs, PQ, Buf + 32 * wave * PQ, PQ, D, r, h);
+            const int col = c0 + 32 * wave + r;
+            const float bias = Bias[col];
+#pragma unroll
+            for (int e = 0; e < 16; ++e) Ps[acc_row(e, h) * PP + col] = acc[e] * a.scale + bias;
+        }
+        __syncthreads();
+    }
+
+    // softmax of each row: 8 threads per row, float4 columns sub, sub + 8, ... held in registers between the three passes;
+    // exp(x - max) * (1 / sum) over the keys the row sees, [0, t + q0 + row]: a key beyond is no part of the max or the sum, its
+    // column of the LDS tile becomes 0 (it is an MFMA operand of the context) and +0.0 is what `p` holds for it up to the capacity
+    {
+        const int row = tid >> 3, sub = tid & 7;
+        const int vis = t + q0 + row + 1 < keys ? t + q0 + row + 1 : keys;       // key 0 is always one of them
+        float* pr = Ps + row * PP;
+        af32x4 x[kExtMaxBlocks];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < kExtMaxBlocks; ++i) {
+            const int c = sub * 4 + 32 * i;
+            x[i] = af32x4{0.f, 0.f, 0.f, 0.f};
+            if (c < Kend) {
+                x[i] = *reinterpret_cast<const af32x4*>(pr + c);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (c + e < vis) mx = (x[i][e] > mx || x[i][e] != x[i][e]) ? x[i][e] : mx;
+            }
+        }
+#pragma unroll
+        for (int off = 1; off < 8; off <<= 1) { const float o = __shfl_xor(mx, off, 64); mx = (o > mx || o != o) ? o : mx; }
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < kExtMaxBlocks; ++i) {
+            const int c = sub * 4 + 32 * i;
+            if (c < Kend) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (c + e < vis) { x[i][e] = expf(x[i][e] + (-mx)); s += x[i][e]; }
+                    else x[i][e] = 0.f;
+                }
+            }
+        }
+#pragma unroll
+        for (int off = 1; off < 8; off <<= 1) s += __shfl_xor(s, off, 64);
+        const float inv = 1.0f / s;
+        const bool stored = a.p != nullptr && row < qrows;
+        float* pg = a.p + ((int64_t(b) * a.heads + head) * m + q0 + (row < qrows ? row : 0)) * C;
+#pragma unroll
+        for (int i = 0; i < kExtMaxBlocks; ++i) {
+            const int c = sub * 4 + 32 * i;
+            if (c < Cp) {
+                if (c < Kend) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) x[i][e] *= inv;
+                    *reinterpret_cast<af32x4*>(pr + c) = x[i];
+                }
+                if (stored) {
+                    if ((C & 3) == 0) {
+                        if (c < C) *reinterpret_cast<af32x4*>(pg + c) = x[i];
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (c + e < C) pg[c + e] = x[i][e];
+                    }
+                }
+            }
+        }
+    }
+
+    // context = P @ V: D / 32 column tiles, the keys of every chunk split over the remaining waves; the partial sums stay in
+    // registers across the chunks and fold in wave order at the end
+    constexpr int NT = D / 32, KP = 4 / NT;
+    const int n = wave % NT, kp = wave / NT;
+    af32x16 acc = zero16();
+    for (int c0 = 0; c0 < Kend; c0 += kExtChunk) {
+        seam_store<D, NA>(rc, Buf, PV, c0, keys, Kend);
+        __syncthreads();                                              // (the first one also publishes the probabilities in LDS)
+        if (c0 + kExtChunk < Kend) seam_load<D, NA>(rc, vc, a.ldc, vn, a.ldv, c0 + kExtChunk, t, m);
+        const int rows = Kend - c0 < kExtChunk ? Kend - c0 : kExtChunk, kspan = rows / KP;
+        wave_mma<true, false>(acc, Ps + c0 + kp * kspan, PP, Buf + kp * kspan * PV + 32 * n, PV, kspan, r, h);
+        __syncthreads();
+    }
+    if (kp > 0) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) Red[((kp - 1) * NT + n) * 1024 + e * 64 + lane] = acc[e];
+    }
+    __syncthreads();
+    if (kp == 0) {
+        for (int q = 1; q < KP; ++q) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[e] += Red[((q - 1) * NT + n) * 1024 + e * 64 + lane];
+        }
+        float* og = a.o + int64_t(b) * a.sbo + int64_t(q0) * a.ldo + head * D + 32 * n + r;
+#pragma unroll
+        for (int e = 0; e < 16; ++e)
+            if (acc_row(e, h) < qrows) og[int64_t(acc_row(e, h)) * a.ldo] = acc[e];
+    }
+}
+
+static bool extend_operand(const void* p, int64_t ld, int64_t sb) { return p && aligned16(p) && ld >= 0 && sb >= 0 && ld % 4 == 0 && sb % 4 == 0; }
+
+// do the floats [x, x + (batch - 1) sb + (rows - 1) ld + w) and [y, ...) share an address?
+static bool extend_overlap(const float* x, int64_t ldx, int64_t sbx, int64_t rowsx, const float* y, int64_t ldy, int64_t sby, int64_t rowsy,
+                           int64_t batch, int64_t w) {
+    const float* xe = x + (batch - 1) * sbx + (rowsx - 1) * ldx + w;
+    const float* ye = y + (batch - 1) * sby + (rowsy - 1) * ldy + w;
+    return x < ye && y < xe;
+}
+
+template <int D>
+static int launch_extend(const ExtendArgs& a, dim3 grid) {
+    const size_t bytes = size_t(attn_extend_lds_floats<D>(round32(a.capacity))) * 4;
+    int rc = allow_lds(&attn_extend<D>, bytes);
+    if (rc != LG_OK) return rc;
+    hipLaunchKernelGGL(attn_extend<D>, grid, dim3(256), bytes, rt().stream, a);
+    return LG_OK;
+}
+
+}  // namespace lg
+
+using namespace lg;
+
+extern "C" int lg_attention_extend_supported(int64_t m, int64_t capacity, int64_t D) {
+    return (D == 32 || D == 64) && m >= 1 && m <= capacity && capacity <= kExtMaxKeys;
+}
+
+extern "C" int lg_attention_extend_f32(const float* q, int64_t ldq, int64_t sbq, const float* k_new, int64_t ldk, int64_t sbk,
+                                       const float* v_new, int64_t ldv, int64_t sbv, float* k_cache, float* v_cache, int64_t ldc,
+                                       int64_t sbc, const int32_t* pos, float* o, int64_t ldo, int64_t sbo, float* p, int64_t batch,
+                                       int64_t heads, int64_t m, int64_t capacity, int64_t D, float scale, const float* mask, int64_t sbm) {
+    LG_REQUIRE_INIT();
+    const char* name = "lg_attention_extend_f32";
+    LG_ARG(lg_attention_extend_supported(m, capacity, D), "%s: m = %lld (1 .. capacity), capacity = %lld (1 .. 512), D = %lld (32 or 64) unsupported",
+           name, (long long)m, (long long)capacity, (long long)D);
+    LG_ARG(batch >= 0 && heads >= 1 && batch <= 65535 && heads <= 65535, "%s: bad batch / heads", name);
+    if (batch == 0) return LG_OK;
+    LG_ARG(extend_operand(q, ldq, sbq) && extend_operand(k_new, ldk, sbk) && extend_operand(v_new, ldv, sbv) && extend_operand(k_cache, ldc, sbc) &&
+               extend_operand(v_cache, ldc, sbc) && extend_operand(o, ldo, sbo) && pos && (reinterpret_cast<uintptr_t>(pos) & 3u) == 0 && aligned16(p),
+           "%s: operands must be non-NULL and 16-byte aligned with pitches that are non-negative multiples of 4", name);
+    const int64_t w = heads * D;
+    LG_ARG(ldc >= w, "%s: cache row pitch %lld below heads * D = %lld", name, (long long)ldc, (long long)w);
+    LG_ARG(!mask || sbm == 0 || sbm >= capacity, "%s: mask batch pitch %lld is neither 0 (one row for the batch) nor >= capacity", name,
+           (long long)sbm);
+    LG_ARG(!extend_overlap(k_new, ldk, sbk, m, k_cache, ldc, sbc, capacity, batch, w) && !extend_overlap(k_new, ldk, sbk, m, v_cache, ldc, sbc, capacity, batch, w) &&
+               !extend_overlap(v_new, ldv, sbv, m, k_cache, ldc, sbc, capacity, batch, w) && !extend_overlap(v_new, ldv, sbv, m, v_cache, ldc, sbc, capacity, batch, w),
+           "%s: k_new / v_new overlap a cache: the launch writes the caches while other workgroups read the new rows", name);
+    {
+        const int64_t rows[3] = {batch, m, w}, row_strides[3] = {sbo, ldo, 1};
+        int rc = adam_epilogue_check_strided(o, 4, 3, rows, row_strides);
+        if (rc != LG_OK) return rc;
+        const int64_t crows[3] = {batch, capacity, w}, strides[3] = {sbc, ldc, 1};
+        rc = adam_epilogue_check_strided(k_cache, 4, 3, crows, strides);
+        if (rc != LG_OK) return rc;
+        rc = adam_epilogue_check_strided(v_cache, 4, 3, crows, strides);
+        if (rc != LG_OK) return rc;
+        if (p) { rc = adam_epilogue_check_write(p, batch * heads * m * capacity * 4); if (rc != LG_OK) return rc; }
+    }
+    const ExtendArgs a{q, k_new, v_new, ldq, sbq, ldk, sbk, ldv, sbv, k_cache, v_cache, ldc, sbc, pos, o, ldo, sbo, p,
+                       int(heads), int(capacity), int(m), scale, mask, sbm, rt().status_dev};
+    const dim3 grid{unsigned((m + 31) / 32), unsigned(heads), unsigned(batch)};
+    const int rc = D == 64 ? launch_extend<64>(a, grid) : launch_extend<32>(a, grid);
+    if (rc != LG_OK) return rc;
+    LG_CHECK_LAUNCH();
+    return LG_OK;
+}

@@ -302,6 +302,21 @@ class KVCache(object):
         self.v = [cls.from_numpy(np.zeros(shape, dtype), requires_grad=False) for _ in range(self.layers)]
         self.pos = cls.from_numpy(np.zeros(1, np.int32), requires_grad=False)
         self.length = 0
+        self._arange = {}           # m -> the int32 constant 0 .. m - 1 on the cache's backend
+
+    def positions(self, m: int):
+        """the int32 position ids `pos + arange(m)` of the next m tokens, shape (m,): one broadcast add on the cache's backend -
+        no host read, and inside a hipGraph capture it is recorded like any kernel (a replay reads the position as it is then)"""
+        m = int(m)
+        assert m >= 1
+        if m not in self._arange:
+            t = type(self.pos).from_numpy(np.arange(m, dtype=np.int32), requires_grad=False)
+            if hasattr(t, "freeze"):
+                t.freeze()          # a constant, like a model's position ids
+            self._arange[m] = t
+        ids = self.pos + self._arange[m]
+        ids._requires_grad = False  # ids are state like `pos`: they go into lookups by keyword and take no gradient
+        return ids
 
     def advance(self, n: int = 1) -> None:
         """the next token's position, + n: on the device, and in the host mirror"""
