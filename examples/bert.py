@@ -35,6 +35,10 @@ Differences from the reference, on purpose:
                                                        # the prompt goes into the cache in pieces of at most 3 tokens, each piece
                                                        # one attention launch per layer against the filled cache (csrc/extend.hip,
                                                        # `model(ids, cache=cache, append=True)`): the same tokens
+    python examples/bert.py --generate 16 --ragged [--eos ID] [--graph] [--sample ...] [--cpu]
+                                                       # a ragged batch in one run: prompts of different lengths, right-padded, every
+                                                       # sequence at its own positions (nn.KVCache(per_row=True), `generate(lengths=)`);
+                                                       # --eos ID: a row that draws ID stops, the others go on
     python examples/bert.py --mlm --bf16-decoder       # the decoder onto the vocabulary (forward, dx, dW) on the bf16 matrix cores:
                                                        # config key `decoder_precision="bf16"`; tensors stay float32
 """
@@ -91,13 +95,17 @@ class BertEmbedding(nn.Module):
         """`token_position`: an int32 tensor of one element on the ids' backend - the position of the ONE token per sequence that
         `input_ids` (b, 1) holds (a decode step: looked up where the tensor lives, no host read); `token_positions`: an int32 tensor
         (m,) on the ids' backend - the positions of the m tokens per sequence of `input_ids` (b, m), shared by the batch (an append
-        to a filled cache: nn.KVCache.positions); neither: positions 0 .. s - 1"""
+        to a filled cache: nn.KVCache.positions) - or (b, m): a position per token (a cache with a position per sequence; a
+        `token_position` of shape (b,) with b > 1 is the (b, 1) case); neither: positions 0 .. s - 1"""
         zeros, position_ids = self._constant_ids(input_ids.__class__, input_ids.shape)
         if token_position is not None:
             assert input_ids.shape[-1] == 1, "a position goes with one token per sequence, got ids of shape %s" % (tuple(input_ids.shape),)
             position_ids = token_position
+            if tuple(token_position.shape) == (input_ids.shape[0],) and input_ids.shape[0] > 1:
+                position_ids = token_position.reshape(input_ids.shape[0], 1)           # a view: one position per sequence
+                position_ids._requires_grad = False     # ids are state like the position: they go into lookups by keyword
         if token_positions is not None:
-            assert token_position is None and tuple(token_positions.shape) == (input_ids.shape[-1],), \
+            assert token_position is None and tuple(token_positions.shape) in ((input_ids.shape[-1],), tuple(input_ids.shape)), \
                 "position ids of shape %s do not go with ids of shape %s" % (tuple(token_positions.shape), tuple(input_ids.shape))
             position_ids = token_positions
         if token_type_ids is None:
@@ -139,7 +147,8 @@ class BertSelfAttention(nn.Module):
 
     def _decode(self, hidden, attention_mask, cache, index):
         """one new token per sequence against the cached keys and values: position t = the cache's position attends to keys 0 .. t
-        - the row the causal forward computes for query t.  attention_mask: None or (b, capacity) over the cache's rows"""
+        - the row the causal forward computes for query t.  attention_mask: None or (b, capacity) over the cache's rows.  A cache
+        with a position per sequence (per_row): the fused route passes `cache.pos` (b,) as it is - sequence r at its own t_r"""
         b = hidden.shape[0]
         scale = math.sqrt(self.d) ** -1
         k_cache, v_cache = cache.k[index], cache.v[index]
@@ -152,6 +161,8 @@ class BertSelfAttention(nn.Module):
             context = hidden.self_attention_decode(self.query.weight, self.query.bias, self.key.weight, self.key.bias, self.value.weight,
                                                    self.value.bias, k_cache, v_cache, cache.pos, heads=self.h, scale=scale, **extra)
             return context, None
+        if getattr(cache, "per_row", False):
+            return self._rows_composite(hidden, attention_mask, cache, index)
         # the same over the tensor API: the host mirror of the position slices the cache
         t = cache.length
         assert t < cache.capacity, "the cache holds %d positions: no room for position %d" % (cache.capacity, t)
@@ -167,6 +178,36 @@ class BertSelfAttention(nn.Module):
             scores = scores + ((1.0 - mask.reshape(mask.shape[0], 1, 1, t + 1)) * -10000.0).detach()
         probs = scores.softmax(axis=-1)
         return (probs @ v).transpose(0, 2, 1, 3).reshape(b, 1, self.h * self.d), probs
+
+    def _rows_composite(self, hidden, attention_mask, cache, index):
+        """`_decode` (m = 1) and `_extend` over the tensor API for a cache with a position per sequence (nn.KVCache(per_row=True)):
+        CpuTensor, float64 tapes and head sizes the kernels refuse.  Sequence r writes its m new rows at positions t_r .. t_r + m - 1
+        and its query i sees keys 0 .. t_r + i; keys beyond - the other sequences' reach, and whatever the cache holds there - are
+        hidden with the usual -10000 bias.  The positions are taken from the cache's host mirror while it is valid; otherwise
+        they are READ from `cache.pos`: free on CpuTensor, a synchronising device read on any other backend."""
+        b, m = hidden.shape[0], hidden.shape[1]
+        k_cache, v_cache = cache.k[index], cache.v[index]
+        t = cache.lengths if cache.lengths is not None else np.asarray(cache.pos.numpy(), np.int64)
+        assert (t >= 0).all() and (t + m <= cache.capacity).all(), \
+            "the cache holds %s of %d positions: no room for %d more in every row" % (t.tolist(), cache.capacity, m)
+        n = int(t.max()) + m
+        q, k, v = self.query(hidden), self.key(hidden), self.value(hidden)
+        for r in range(b):
+            k_cache[r:r + 1, int(t[r]):int(t[r]) + m] = k[r:r + 1]
+            v_cache[r:r + 1, int(t[r]):int(t[r]) + m] = v[r:r + 1]
+        q = q.reshape(b, m, self.h, self.d).transpose(0, 2, 1, 3)
+        k = k_cache[:, :n].reshape(b, n, self.h, self.d).transpose(0, 2, 3, 1)
+        v = v_cache[:, :n].reshape(b, n, self.h, self.d).transpose(0, 2, 1, 3)
+        scores = (q @ k) / math.sqrt(self.d)
+        if attention_mask is not None:
+            mask = attention_mask[:, :n]
+            scores = scores + ((1.0 - mask.reshape(mask.shape[0], 1, 1, n)) * -10000.0).detach()
+        # (b, 1, m, n): key j is visible to query i of sequence r where j <= t_r + i
+        visible = (np.arange(n)[None, None, :] <= (t[:, None, None] + np.arange(m)[None, :, None])).astype(scores.dtype)
+        visible = scores.__class__.from_numpy(visible.reshape(b, 1, m, n), requires_grad=False)
+        scores = scores + ((1.0 - visible) * -10000.0).detach()
+        probs = scores.softmax(axis=-1)
+        return (probs @ v).transpose(0, 2, 1, 3).reshape(b, m, self.h * self.d), probs
 
     def _triangle_behind(self, like, t, m):
         """rows t .. t + m - 1 of the lower-triangular constant of t + m positions, (1, 1, m, t + m): query t + i sees keys 0 .. t + i"""
@@ -194,6 +235,8 @@ class BertSelfAttention(nn.Module):
             context = hidden.self_attention_extend(self.query.weight, self.query.bias, self.key.weight, self.key.bias, self.value.weight,
                                                    self.value.bias, k_cache, v_cache, cache.pos, heads=self.h, scale=scale, **extra)
             return context, None
+        if getattr(cache, "per_row", False):
+            return self._rows_composite(hidden, attention_mask, cache, index)
         # the same over the tensor API: the host mirror of the position slices the cache
         t = cache.length
         n = t + m
@@ -380,10 +423,16 @@ class BertModel(nn.Module):
         b, m = input_ids.shape
         positions = self.embeddings.position_embeddings.weight.shape[0]
         assert cache.layers == len(self.encoder.layer) and cache.batch == b, "the cache was made for %d layers and a batch of %d" % (cache.layers, cache.batch)
-        assert m >= 1 and cache.length + m <= cache.capacity, \
-            "the cache holds %d of its %d positions: %d more tokens do not fit" % (cache.length, cache.capacity, m)
-        assert cache.length + m <= positions, \
-            "%d tokens behind the %d in the cache exceed the model's %d position embeddings" % (m, cache.length, positions)
+        if getattr(cache, "per_row", False):
+            # a position per sequence: checked on the host where the mirror is valid, by the launches' own bounds checks otherwise
+            assert m >= 1 and cache.capacity <= positions and (cache.lengths is None or (cache.lengths + m <= cache.capacity).all()), \
+                "the cache holds %s of its %d positions: %d more tokens do not fit every row" % (
+                    None if cache.lengths is None else cache.lengths.tolist(), cache.capacity, m)
+        else:
+            assert m >= 1 and cache.length + m <= cache.capacity, \
+                "the cache holds %d of its %d positions: %d more tokens do not fit" % (cache.length, cache.capacity, m)
+            assert cache.length + m <= positions, \
+                "%d tokens behind the %d in the cache exceed the model's %d position embeddings" % (m, cache.length, positions)
         with light.no_grad():
             hidden = self.embeddings(input_ids, token_type_ids=token_type_ids, token_positions=cache.positions(m))
             for index, layer in enumerate(self.encoder.layer):
@@ -408,6 +457,7 @@ class BertModel(nn.Module):
             for index, layer in enumerate(self.encoder.layer):
                 hidden, _ = layer(hidden, attention_mask=attention_mask, cache=cache, index=index)
             if prefill:
+                # (a cache with a position per sequence: every row holds s tokens until the caller says otherwise - set_lengths)
                 cache.set_length(s)
         return hidden
 
@@ -544,8 +594,133 @@ def prefill_in_pieces(model, cache, ids32, mask, piece):
     return hidden[:, n - 1:n]
 
 
+def decode_step_rows(model, cache, token, out_ids, done, mask=None, sampler=None, eos=None):
+    """`decode_step` for a cache with a position per sequence: the token (b, 1) of every sequence goes through the decode forward
+    at its own position, and ONE `decode_commit` does the bookkeeping per row - a live row's position moves on, its new token
+    becomes its input and the next column of its ids, a row that drew `eos` is marked in `done`; a finished row is recomputed at
+    its frozen position (the same cache row, the same bits) and nothing of it is written.  No host read, one shape whatever has
+    finished: a captured step replays as it stands."""
+    logits = model(token, attention_mask=mask, cache=cache)                 # (b, 1, vocab)
+    next_token(logits, sampler).decode_commit(token, out_ids, cache.pos, done, eos=eos)
+    cache.committed(1, eos=eos is not None)
+
+
+def prefill_rows_in_pieces(model, cache, ids32, lengths, mask, piece):
+    """`prefill_in_pieces` for right-padded rows: (b, s0) ids of which `lengths[r]` lead row r, behind whatever the cache holds
+    in each row.  Every piece is (b, n) for all rows - what a row has no tokens for is padding whose keys and values land beyond
+    the row's position, where nothing reads them - and the position moves on by the row's own tokens of the piece.  Returns the
+    hidden row (b, 1, hidden) of each row's LAST token, gathered on the device from the piece that holds it."""
+    b, s0 = ids32.shape
+    last, buffers = None, {}
+    for lo in range(0, s0, piece):
+        n = min(piece, s0 - lo)
+        if n == s0:
+            ids = ids32
+        else:
+            if n not in buffers:
+                buffers[n] = ids32.__class__.from_numpy(np.zeros((b, n), np.int32), requires_grad=False)
+            ids = buffers[n]
+            ids[:, :] = ids32[:, lo:lo + n]
+        hidden = model.bert(ids, attention_mask=mask, cache=cache, append=True)
+        if last is None:
+            last = hidden.__class__.from_numpy(np.zeros((b, 1, hidden.shape[2]), hidden.dtype), requires_grad=False)
+        for r in range(b):
+            if lo < lengths[r] <= lo + n:
+                i = int(lengths[r]) - 1 - lo
+                last[r:r + 1] = hidden[r:r + 1, i:i + 1]
+        cache.advance(np.clip(lengths - lo, 0, n))
+    return last
+
+
+def generate_rows(model, ids, max_new_tokens, lengths, eos_token_id, pad_token_id, attention_mask, cache, graph, sampler, prefill_chunk,
+                  append):
+    """the per-row path of `generate` (see there): right-padded prompts with a length per row, rows that stop at `eos_token_id`"""
+    b, s0 = ids.shape
+    cls = ids.__class__
+    lengths = np.full(b, s0, np.int64) if lengths is None else np.asarray(lengths, np.int64)
+    assert lengths.shape == (b,) and (lengths >= 1).all() and (lengths <= s0).all(), \
+        "lengths: %d ints within 1 .. %d, the real tokens that lead each right-padded row" % (b, s0)
+    eos = None if eos_token_id is None else int(eos_token_id)
+    positions = model.bert.embeddings.position_embeddings.weight.shape[0]
+    layer0 = model.bert.encoder.layer[0].attention.self
+    width = int(lengths.max()) + max_new_tokens                         # columns of the result
+    if cache is None:
+        cache = nn.KVCache(len(model.bert.encoder.layer), b, s0 + max_new_tokens, layer0.h * layer0.d,
+                           like=model.bert.embeddings.word_embeddings.weight, per_row=True)
+    assert cache.per_row, "lengths= / eos_token_id= take a cache with a position per sequence: nn.KVCache(..., per_row=True)"
+    if append:
+        if cache.lengths is None:
+            # rows stopped where only the device knows (a run with an end-of-sequence id): one read brings the mirror back
+            cache.lengths = np.asarray(cache.pos.numpy(), np.int64)
+            cache.length = int(cache.lengths.max())
+        start = cache.lengths.copy()                                    # tokens in front of `ids`, per row
+        assert attention_mask is None or tuple(attention_mask.shape) in ((b, cache.capacity), (1, cache.capacity))
+        mask = attention_mask
+    else:
+        assert attention_mask is None, "right-padded prompts need no mask: under the causal rule a real token never sees the padding behind it"
+        cache.reset()
+        start, mask = np.zeros(b, np.int64), None
+    assert ((start + s0 <= cache.capacity) & (start + lengths + max_new_tokens <= cache.capacity)).all() and cache.capacity <= positions, \
+        "rows of %s tokens in the cache, %d appended (%s real) and %d new ones do not fit a cache of %d positions and a model of %d position embeddings" % (
+            start.tolist(), s0, lengths.tolist(), max_new_tokens, cache.capacity, positions)
+    ids32 = ids if ids.dtype == np.int32 else ids.astype(np.int32)
+    # a column per position of a row's sequence (the commit writes column = the row's device position), padding everywhere else
+    columns = int(start.max()) + width
+    out_ids = cls.from_numpy(np.full((b, columns), int(pad_token_id), np.int32), requires_grad=False)
+    for r in range(b):
+        out_ids[r:r + 1, int(start[r]):int(start[r] + lengths[r])] = ids32[r:r + 1, :int(lengths[r])]
+    token = cls.from_numpy(np.zeros((b, 1), np.int32), requires_grad=False)        # the id buffer every step reads and writes
+    done = cls.from_numpy(np.zeros(b, np.int32), requires_grad=False)              # 1 where a row has drawn the end-of-sequence id
+    with light.no_grad():
+        if append or prefill_chunk is not None:
+            last = prefill_rows_in_pieces(model, cache, ids32, lengths, mask, s0 if prefill_chunk is None else int(prefill_chunk))
+        else:
+            hidden = model.bert(ids32, cache=cache)                                 # (b, s0, hidden); the padding's rows land beyond ...
+            cache.set_lengths(lengths)                                              # ... each row's position
+            rows = cls.from_numpy((np.arange(b) * s0 + lengths - 1).astype(np.int32), requires_grad=False)
+            last = hidden.reshape(-1, hidden.shape[-1])[rows].reshape(b, 1, hidden.shape[-1])      # row lengths[r] - 1 of each sequence
+        first = next_token(model.head(last), sampler)
+    # the first new token goes the way of every later one: from position lengths - 1 the commit lands it in column lengths[r]
+    cache.advance(-1)
+    first.decode_commit(token, out_ids, cache.pos, done, eos=eos)
+    cache.committed(1, eos=eos is not None)
+
+    def result():
+        if not append:
+            return out_ids
+        behind = cls.from_numpy(np.zeros((b, width), np.int32), requires_grad=False)        # row r from its own first appended column
+        for r in range(b):
+            behind[r:r + 1, :] = out_ids[r:r + 1, int(start[r]):int(start[r]) + width]
+        return behind
+
+    steps = max_new_tokens - 1
+    if graph is None or steps == 0:
+        for _ in range(steps):
+            decode_step_rows(model, cache, token, out_ids, done, mask, sampler, eos)
+        return result()
+    # as in `generate`: the first step once eagerly (greedy: no call of the random stream), then back to where the commit of the
+    # first token left off - positions, flags and token are copies on the device, the host mirror a copy on the host
+    def clone(t):
+        c = cls.from_numpy(np.zeros(tuple(t.shape), np.int32), requires_grad=False)
+        c[tuple(slice(None) for _ in t.shape)] = t
+        return c
+    saved = (clone(cache.pos), clone(done), clone(token), cache.length, None if cache.lengths is None else cache.lengths.copy())
+    decode_step_rows(model, cache, token, out_ids, done, mask, None, eos)
+    cache.pos[:] = saved[0]
+    done[:] = saved[1]
+    token[:, :] = saved[2]
+    cache.length, cache.lengths = saved[3], saved[4]
+    with graph.capture():
+        decode_step_rows(model, cache, token, out_ids, done, mask, sampler, eos)    # recorded, not run: only the host mirror moved
+    for i in range(steps):
+        graph.replay()
+        if i:
+            cache.committed(1, eos=eos is not None)
+    return result()
+
+
 def generate(model, ids, max_new_tokens, attention_mask=None, cache=None, graph=None, temperature=None, top_k=0, top_p=1.0,
-             prefill_chunk=None, append=False):
+             prefill_chunk=None, append=False, lengths=None, eos_token_id=None, pad_token_id=0):
     """decoding of a model built with `causal=True`: (b, s0) prompt ids -> (b, s0 + max_new_tokens) int32 ids on the
     prompt's backend.  temperature=None is greedy; with a temperature every token - the prompt's own first one included - is
     `logits.sample(temperature, top_k, top_p)`, drawn from the backend's random stream (`light.manual_seed`): one call of the
@@ -559,7 +734,24 @@ def generate(model, ids, max_new_tokens, attention_mask=None, cache=None, graph=
     tokens, with a layer's probabilities bounded by (b, heads, c, capacity).  append=True: `cache` (required) is NOT reset -
     `ids` are appended behind the `cache.length` tokens it already holds (a second turn of a conversation; one piece unless
     prefill_chunk is given) and decoding goes on from there; the result is the appended ids followed by the new ones, and
-    attention_mask, if given, is (b, capacity) over the cache's rows as a decode step reads it."""
+    attention_mask, if given, is (b, capacity) over the cache's rows as a decode step reads it.
+    lengths= (a host sequence of b ints) or eos_token_id= select the per-row path, a ragged batch in one run: `ids` is (b, s0)
+    RIGHT-padded and lengths[r] real tokens lead row r (default: s0 for every row).  The prompt goes through the causal forward
+    without a mask - a real token never sees the padding behind it, and the padding's keys and values land in the cache beyond
+    each row's position, where nothing reads them -, the head runs on row lengths[r] - 1 of each sequence, and every sequence
+    is embedded and attends at its own positions (nn.KVCache(per_row=True); a cache given must be one): row r decodes as it does
+    alone.  A row that draws eos_token_id stops: the result, (b, max(lengths) + max_new_tokens) filled with pad_token_id, holds
+    each row's prompt, then its new tokens up to and including the end-of-sequence id.  A finished row keeps being recomputed at
+    its frozen position (`decode_step_rows`), and the sampler draws for it too (one call of the stream per step): the step never
+    changes shape and is captured once with graph=.  prefill_chunk= and append=True work as above, with pieces that are
+    right-padded and a position that moves by `lengths` per row (append after a run with an end-of-sequence id reads the
+    positions back once: only the device knows where the rows stopped)."""
+    if lengths is not None or eos_token_id is not None:
+        assert max_new_tokens >= 1 and ids.shape[1] >= 1 and (prefill_chunk is None or prefill_chunk >= 1)
+        assert model.bert.encoder.layer[0].attention.self.causal, "generate needs a model built with causal=True"
+        assert not append or cache is not None, "append=True continues a cache: pass the one that holds the tokens so far"
+        return generate_rows(model, ids, max_new_tokens, lengths, eos_token_id, pad_token_id, attention_mask, cache, graph,
+                             None if temperature is None else (temperature, top_k, top_p), prefill_chunk, append)
     b, s0 = ids.shape
     positions = model.bert.embeddings.position_embeddings.weight.shape[0]
     layer0 = model.bert.encoder.layer[0].attention.self
@@ -643,14 +835,19 @@ if __name__ == "__main__":
             print("prompt prefilled through the append path in pieces of at most %d tokens" % pieces["prefill_chunk"])
         else:
             pieces = {}
+        if "--ragged" in sys.argv:
+            # prompts of 8, 7, 6, .. tokens (at least 1): what lies behind a row's length is padding that nothing reads
+            row_lengths = [max(1, 8 - r) for r in range(batch)]
+            pieces = dict(pieces, lengths=row_lengths, eos_token_id=int(sys.argv[sys.argv.index("--eos") + 1]) if "--eos" in sys.argv else None)
+            print("ragged batch: prompts of %s tokens%s" % (row_lengths, ", stopping at id %d" % pieces["eos_token_id"] if "--eos" in sys.argv else ""))
         new_ids = generate(lm, prompt, n_new, graph=recorded, **sampling, **pieces).numpy()          # the only host read
         if sampling:
             print("sampled: temperature %(temperature)g, top_k %(top_k)d, top_p %(top_p)g" % sampling)
         print("generated %d tokens per sequence in %.1f ms (%s)" % (
             n_new, 1e3 * (time.perf_counter() - t0),
             "decode step captured once, %d kernels, replayed %d times" % (recorded.kernel_count(), n_new - 1) if recorded else "eager decode steps"))
-        for row in new_ids:
-            print(" ".join(str(i) for i in row[8:]))
+        for r, row in enumerate(new_ids):
+            print(" ".join(str(i) for i in row[pieces["lengths"][r] if "lengths" in pieces else 8:]))
         sys.exit(0)
     if "--mlm" in sys.argv:
         light.manual_seed(0)

@@ -674,6 +674,37 @@ int lg_attention_extend_f32(const float* q, int64_t ldq, int64_t sbq,   /* the n
                             int64_t batch, int64_t heads, int64_t m, int64_t capacity, int64_t D, float scale,
                             const float* mask, int64_t sbm);         /* key-padding mask over the capacity; NULL = none */
 
+/* ---- a position per sequence: ragged batches in the key / value cache (csrc/decode.hip, extend.hip, commit.hip) -------------
+ * lg_attention_decode_rows_f32 / lg_attention_extend_rows_f32 take the arguments of lg_attention_decode_f32 / _extend_f32 with ONE
+ * difference: `pos` points to `batch` contiguous int32 words in device memory and batch element b uses t = pos[b].  Everything
+ * said above holds per batch element with its own t - the rows read and written, row t .. from the new-token buffers and never
+ * read back, cache rows beyond reaching nothing (NaN included), +0.0 beyond the diagonal of p, every fold in a fixed order: a
+ * batch element's bits are those of the one-word entry called on it alone at batch 1.  They are the same kernels (the position
+ * is addressed with a pitch of 1 word in place of 0).  A batch element whose t is out of range (t < 0, t >= capacity for decode,
+ * t + m > capacity for extend) writes nothing and raises the status flag; the OTHER elements of the launch are computed as
+ * usual.  Host refusals as for the one-word entries; all four also refuse (LG_EINVAL) position words that overlap a cache. */
+int lg_attention_decode_rows_f32(const float* q, int64_t sbq, const float* k_new, int64_t sbk, const float* v_new, int64_t sbv,
+                                 float* k_cache, float* v_cache, int64_t ldc, int64_t sbc,
+                                 const int32_t* pos,                 /* `batch` words in device memory: the position of each new token */
+                                 float* o, int64_t sbo, float* p, int64_t batch, int64_t heads, int64_t capacity, int64_t D, float scale,
+                                 const float* mask, int64_t sbm);
+int lg_attention_extend_rows_f32(const float* q, int64_t ldq, int64_t sbq, const float* k_new, int64_t ldk, int64_t sbk,
+                                 const float* v_new, int64_t ldv, int64_t sbv, float* k_cache, float* v_cache, int64_t ldc, int64_t sbc,
+                                 const int32_t* pos,                 /* `batch` words in device memory: the position of each row's new token 0 */
+                                 float* o, int64_t ldo, int64_t sbo, float* p, int64_t batch, int64_t heads, int64_t m, int64_t capacity,
+                                 int64_t D, float scale, const float* mask, int64_t sbm);
+/* The per-row bookkeeping of one decode step in one launch, one thread per row, any batch >= 1.  For each row r with
+ * done[r] == 0: p = pos[r] + 1; if p < 0 or p >= columns the status flag is raised (LG_EINDEX at the next lg_sync /
+ * lg_memcpy_d2h) and the row is left untouched; otherwise pos[r] = p, token[r] = nxt[r * nxt_pitch], out_ids[r * out_pitch + p] =
+ * that id, and done[r] = 1 if eos_id >= 0 and the id equals it.  A row with done[r] != 0: nothing is written at all.  Refused
+ * (LG_EINVAL): a NULL operand (`done` included), a misaligned one, nxt_pitch < 1, out_pitch < columns, any two operands that
+ * overlap. */
+int lg_decode_commit_i32(const int32_t* nxt, int64_t nxt_pitch,      /* the step's new ids, row r at nxt + r * nxt_pitch */
+                         int32_t* token,                             /* (batch) the step's input ids */
+                         int32_t* out_ids, int64_t out_pitch, int64_t columns,   /* (batch, columns), row pitch in elements */
+                         int32_t* pos, int32_t* done,                /* (batch) each */
+                         int64_t batch, int32_t eos_id);             /* eos_id < 0: none */
+
 /* ---- two independent products in one launch ----------------------------------------------------------
  * lg_gemm_pair_begin(); <product 1>; <product 2>; lg_gemm_pair_end();   with products issued through
  * lg_gemm_f32 / lg_gemm_rowsum_f32 / lg_gemm_fused_f32.  If the first resolves to the 64x64 tile with an

@@ -404,6 +404,47 @@ def _sample(logits, temperature=1.0, top_k=0, top_p=1.0, dtype=np.int64):
 CpuTensor.sample = _sample
 
 
+def _decode_commit(nxt, token, out_ids, pos, done, eos=None):
+    """ nxt.decode_commit(token, out_ids, pos, done, eos=None): the per-row bookkeeping of one decode step, in place and outside
+    the tape - the definition of the op.  nxt (b,) or (b, 1), token (b, 1), out_ids (b, columns), pos (b,), done (b,), all int32.
+    For each row r with done[r] == 0: p = pos[r] + 1; pos[r] = p, token[r] = nxt[r], out_ids[r, p] = nxt[r], and done[r] = 1 if
+    `eos` is an id >= 0 and nxt[r] equals it.  A row with done[r] != 0 is not touched at all.  A live row whose p is no column
+    of out_ids is left untouched as well and the call raises IndexError - after the other rows have been committed, as the
+    device flag of the HipTensor op does at its next synchronisation. """
+    b = _check_decode_commit(nxt, token, out_ids, pos, done, eos)
+    arrays = [t.data for t in (nxt, token, out_ids, pos, done)]
+    assert not any(np.shares_memory(x, y) for i, x in enumerate(arrays) for y in arrays[i + 1:]), "decode_commit: two operands overlap"
+    new, columns = nxt.data.reshape(b), out_ids.shape[1]
+    p = pos.data.astype(np.int64) + 1
+    live = done.data == 0
+    bad = live & ((p < 0) | (p >= columns))
+    rows = np.nonzero(live & ~bad)[0]
+    pos.data[rows] = p[rows]
+    token.data[rows, 0] = new[rows]
+    out_ids.data[rows, p[rows]] = new[rows]
+    if eos is not None and int(eos) >= 0:
+        done.data[rows[new[rows] == int(eos)]] = 1
+    if bad.any():
+        raise IndexError("decode_commit: position %d + 1 of row %d is no column of out_ids (%d columns)" % (
+            int(pos.data[np.nonzero(bad)[0][0]]), int(np.nonzero(bad)[0][0]), columns))
+
+
+def _check_decode_commit(nxt, token, out_ids, pos, done, eos):
+    """the operand shapes and dtypes of `decode_commit`, on any backend; returns the batch"""
+    b = pos.shape[0] if len(pos.shape) == 1 else -1
+    i32 = np.dtype(np.int32)
+    assert b >= 1 and tuple(nxt.shape) in ((b,), (b, 1)) and tuple(token.shape) == (b, 1) and len(out_ids.shape) == 2 and out_ids.shape[0] == b \
+        and out_ids.shape[1] >= 1 and tuple(done.shape) == (b,), \
+        "decode_commit: nxt (b,) or (b, 1), token (b, 1), out_ids (b, columns), pos (b,), done (b,) - got %s, %s, %s, %s, %s" % (
+            tuple(nxt.shape), tuple(token.shape), tuple(out_ids.shape), tuple(pos.shape), tuple(done.shape))
+    assert all(np.dtype(t.dtype) == i32 for t in (nxt, token, out_ids, pos, done)), "decode_commit: every operand is int32"
+    assert eos is None or int(eos) == eos, "decode_commit: eos is an int or None"
+    return b
+
+
+CpuTensor.decode_commit = _decode_commit
+
+
 def _next_token_labels(ids, ignore_index=-100):
     """ ids.next_token_labels(ignore_index=-100): the labels of the next-token objective - `ids` shifted left by one along the last
     axis, `ignore_index` in the last column; same dtype and shape, a constant of the tape. """

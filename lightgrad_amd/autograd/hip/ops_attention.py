@@ -312,7 +312,34 @@ def _check_cache(name, k_cache, v_cache, pos, b, width):
     st = k_cache._strides
     assert st[2] == 1 and st[1] % 4 == 0 and st[0] % 4 == 0 and st[1] >= width and k_cache._byte_offset % 16 == 0 and v_cache._byte_offset % 16 == 0, \
         "%s: cache rows must be contiguous and 16-byte aligned with pitches that are multiples of 4 (strides %s)" % (name, st)
-    assert isinstance(pos, HipTensor) and pos._dtype == _I32 and pos.numel() == 1, "%s: pos is an int32 HipTensor of one element" % name
+    assert isinstance(pos, HipTensor) and pos._dtype == _I32 and (pos.numel() == 1 or pos._shape == (b,)), \
+        "%s: pos is an int32 HipTensor of one element (one position for the batch) or of shape (batch,) = (%d,) (a position per sequence), got %s %s" % (
+            name, b, getattr(pos, "_dtype", type(pos).__name__), getattr(pos, "_shape", ""))
+    for c in (k_cache, v_cache):
+        assert not _shares_bytes(pos, c), "%s: pos overlaps a cache (the launch writes the caches while it reads the positions)" % name
+
+
+def _shares_bytes(x, y):
+    """do two HipTensors of one allocation span common bytes?  (extents of the views, whatever their strides)"""
+    if x._data is None or x._data is not y._data:
+        return False
+    def span(t):
+        lo = hi = 0
+        for n, st in zip(t._shape, t._strides):
+            if n == 0:
+                return t._byte_offset, t._byte_offset
+            lo, hi = lo + min(0, (n - 1) * st), hi + max(0, (n - 1) * st)
+        return t._byte_offset + lo * t._dtype.itemsize, t._byte_offset + (hi + 1) * t._dtype.itemsize
+    (a0, a1), (b0, b1) = span(x), span(y)
+    return a0 < b1 and b0 < a1
+
+
+def _positions(pos, b):
+    """(contiguous tensor, per-row?) of the position operand: one word keeps the one-word entry - at batch 1 the two mean the same -,
+    (batch,) words take the `_rows` entry"""
+    if pos.numel() == 1 or b == 1:
+        return pos, False
+    return (pos if pos._strides[0] == 1 else pos.contiguous()), True
 
 
 def _launch_decode(name, q2, k2, v2, k_cache, v_cache, pos, out, heads, scale, mask, probs):
@@ -322,9 +349,10 @@ def _launch_decode(name, q2, k2, v2, k_cache, v_cache, pos, out, heads, scale, m
     p = HipTensor.empty((b, heads, 1, capacity), requires_grad=False) if probs else None
     flush_lazy_readers(k_cache)
     flush_lazy_readers(v_cache)
-    _l.check(_l.lib().lg_attention_decode_f32(*q2, *k2, *v2, k_cache.ptr, v_cache.ptr, k_cache._strides[1], k_cache._strides[0], pos.ptr,
-                                              out.ptr, width, p.ptr if probs else None, b, heads, capacity, width // heads, float(scale),
-                                              mask3[1], mask3[2]))
+    pos, per_row = _positions(pos, b)
+    entry = _l.lib().lg_attention_decode_rows_f32 if per_row else _l.lib().lg_attention_decode_f32
+    _l.check(entry(*q2, *k2, *v2, k_cache.ptr, v_cache.ptr, k_cache._strides[1], k_cache._strides[0], pos.ptr,
+                   out.ptr, width, p.ptr if probs else None, b, heads, capacity, width // heads, float(scale), mask3[1], mask3[2]))
     return p
 
 
@@ -338,7 +366,9 @@ def decode_attention_supported(q, heads, capacity):
 
 def decode_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False):
     """ attention of ONE new token per sequence against a key / value cache, one launch (lg_attention_decode_f32): with t = the
-    int32 word `pos` holds ON THE DEVICE, k_new / v_new become row t of the caches (b, capacity, heads * d) and the result is
+    int32 word `pos` holds ON THE DEVICE (`pos` of shape (b,): a position per sequence, t = pos[r] for sequence r, everything
+    below per sequence - lg_attention_decode_rows_f32; a sequence whose position is outside the cache writes nothing, the others
+    are computed), k_new / v_new become row t of the caches (b, capacity, heads * d) and the result is
     softmax(scale * q K[0..t]^T + (1 - mask[0..t]) * -10000) V[0..t] per head - the row the causal forward computes for query t.
     q, k_new, v_new: (b, 1, width) or (b, width); slices of one (b, 1, 3 * width) projection buffer are read in place.  mask:
     float32 (b, capacity) or (1, capacity) over the cache's rows, None for none.  probs=True: `.attention_probs` (b, heads, 1,
@@ -419,9 +449,10 @@ def _launch_extend(name, q3, k3, v3, m, k_cache, v_cache, pos, out, heads, scale
     p = HipTensor.empty((b, heads, m, capacity), requires_grad=False) if probs else None
     flush_lazy_readers(k_cache)
     flush_lazy_readers(v_cache)
-    _l.check(_l.lib().lg_attention_extend_f32(*q3, *k3, *v3, k_cache.ptr, v_cache.ptr, k_cache._strides[1], k_cache._strides[0], pos.ptr,
-                                              out.ptr, width, m * width, p.ptr if probs else None, b, heads, m, capacity, width // heads,
-                                              float(scale), mask3[1], mask3[2]))
+    pos, per_row = _positions(pos, b)
+    entry = _l.lib().lg_attention_extend_rows_f32 if per_row else _l.lib().lg_attention_extend_f32
+    _l.check(entry(*q3, *k3, *v3, k_cache.ptr, v_cache.ptr, k_cache._strides[1], k_cache._strides[0], pos.ptr,
+                   out.ptr, width, m * width, p.ptr if probs else None, b, heads, m, capacity, width // heads, float(scale), mask3[1], mask3[2]))
     return p
 
 
@@ -435,7 +466,8 @@ def extend_attention_supported(q, heads, capacity):
 
 def extend_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False):
     """ attention of m NEW tokens per sequence against a filled key / value cache, one launch (lg_attention_extend_f32): with t =
-    the int32 word `pos` holds ON THE DEVICE, rows i of k_new / v_new become rows t + i of the caches (b, capacity, heads * d) and
+    the int32 word `pos` holds ON THE DEVICE (`pos` of shape (b,): a position per sequence, t = pos[r] for sequence r, everything
+    below per sequence - lg_attention_extend_rows_f32; a sequence with t + m beyond the cache writes nothing, the others are computed), rows i of k_new / v_new become rows t + i of the caches (b, capacity, heads * d) and
     row i of the result is softmax(scale * q_i K[0..t+i]^T + (1 - mask[0..t+i]) * -10000) V[0..t+i] per head - the rows the causal
     forward computes for queries t .. t + m - 1.  q, k_new, v_new: (b, m, width); slices of one (b, m, 3 * width) projection
     buffer are read in place.  mask: float32 (b, capacity) or (1, capacity) over the cache's rows, None for none.  probs=True:
@@ -494,3 +526,36 @@ def self_attention_extend_supported(x, wq, heads, capacity):
 
 HipTensor.extend_attention, HipTensor.extend_attention_supported = extend_attention, extend_attention_supported
 HipTensor.self_attention_extend, HipTensor.self_attention_extend_supported = self_attention_extend, self_attention_extend_supported
+
+
+""" The per-row bookkeeping of a decode step in one launch (csrc/commit.hip) """
+
+
+def decode_commit(nxt, token, out_ids, pos, done, eos=None):
+    """ nxt.decode_commit(token, out_ids, pos, done, eos=None): what `CpuTensor.decode_commit` defines, in ONE launch
+    (lg_decode_commit_i32), in place and outside the tape.  For each row r with done[r] == 0: p = pos[r] + 1; pos[r] = p,
+    token[r] = nxt[r], out_ids[r, p] = nxt[r], and done[r] = 1 if `eos` is an id >= 0 that nxt[r] equals; a row with done[r] != 0
+    is not touched.  nxt (b,) or (b, 1), token (b, 1), out_ids (b, columns) with any row pitch, pos (b,), done (b,): int32
+    HipTensors that do not overlap.  A live row whose p is no column of out_ids keeps its bytes and raises IndexError at the next
+    synchronisation.  No host read: a captured step replays it as it stands. """
+    from ..cpu.ops import _check_decode_commit
+    name = "decode_commit"
+    assert all(isinstance(t, HipTensor) for t in (nxt, token, out_ids, pos, done)), "%s: every operand is a HipTensor" % name
+    b = _check_decode_commit(nxt, token, out_ids, pos, done, eos)
+    columns = out_ids._shape[1]
+    if b > 1 and nxt._strides[0] < 1:
+        nxt = nxt.contiguous()
+    # the launch writes these where they lie: a layout it cannot address is an error, never a copy
+    assert (b == 1 or (token._strides[0] == 1 and pos._strides[0] == 1 and done._strides[0] == 1)) and (columns == 1 or out_ids._strides[1] == 1) \
+        and (b == 1 or out_ids._strides[0] >= columns), "%s: token, pos and done must be dense and the rows of out_ids contiguous" % name
+    written = (token, out_ids, pos, done)
+    for i, x in enumerate(written):
+        assert not _shares_bytes(nxt, x), "%s: nxt overlaps an operand that is written" % name
+        for y in written[i + 1:]:
+            assert not _shares_bytes(x, y), "%s: two of token, out_ids, pos and done overlap" % name
+        flush_lazy_readers(x)
+    _l.check(_l.lib().lg_decode_commit_i32(nxt.ptr, nxt._strides[0] if b > 1 else 1, token.ptr, out_ids.ptr, out_ids._strides[0] if b > 1 else columns,
+                                           columns, pos.ptr, done.ptr, b, -1 if eos is None else int(eos)))
+
+
+HipTensor.decode_commit = decode_commit

@@ -3,7 +3,8 @@
 // A single query row is a matrix-vector problem bound by the read of K and V, so nothing here is shared with the MFMA prefill
 // kernels of attention.hip / attention_long.hip: no matrix cores, no LDS staging of K or V.  One workgroup of 256 threads (4
 // waves) per (batch, head) pair.  The position t of the new token is ONE word in device memory that the kernel reads - a
-// captured step replays with whatever the word holds then.
+// captured step replays with whatever the word holds then.  lg_attention_decode_rows_f32 is the same kernel with a word per batch
+// element (DecodeArgs::pos_pitch = 1 in place of 0): everything below holds per element with its own t.
 //
 // Partition of the keys 0 .. t.  A key row of D floats is read by G = D / 4 neighbouring lanes, one 16-byte load each, so a
 // wave covers KW = 64 / G rows per load instruction (D = 64: 4, D = 32: 8) and the workgroup KP = 4 KW rows per PASS (16 / 32):
@@ -39,7 +40,8 @@ struct DecodeArgs {
     int64_t sbq, sbk, sbv;
     float *k_cache, *v_cache;            // element (b, j, head, d) at x + b * sbc + j * ldc + head * D + d
     int64_t ldc, sbc;
-    const int32_t* pos;
+    const int32_t* pos;                  // batch element b reads pos[b * pos_pitch]: pitch 0 = one word for the batch, 1 = a word per row
+    int64_t pos_pitch;
     float* o;
     int64_t sbo;
     float* p;                            // NULL, or (batch, heads, capacity) dense
@@ -98,10 +100,11 @@ __global__ __launch_bounds__(256) void attn_decode(const DecodeArgs a) {
     __shared__ __attribute__((aligned(16))) float Part[4][64];            // per-wave partial contexts
     __shared__ float Red[8];                 // per-wave maxima [0, 4), sums [4, 8)
 
-    const int t = *a.pos;
     const int tid = threadIdx.x, head = blockIdx.x, b = blockIdx.y;
+    const int t = a.pos[int64_t(b) * a.pos_pitch];       // uniform over the workgroup either way: a scalar load
     if (t < 0 || t >= a.capacity) {
-        // a bounds check, never a fault: nothing is written, the next synchronising call reports LG_EINDEX
+        // a bounds check, never a fault: nothing is written for this batch element (the others of a per-row launch are computed
+        // as usual), the next synchronising call reports LG_EINDEX
         if (tid == 0) __hip_atomic_fetch_or(a.status, LG_STATUS_BAD_INDEX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         return;
     }
@@ -206,6 +209,13 @@ __global__ __launch_bounds__(256) void attn_decode(const DecodeArgs a) {
 
 static bool decode_operand(const void* p, int64_t sb) { return p && aligned16(p) && sb % 4 == 0; }
 
+// do the `words` position words share an address with the floats [c, c + (batch - 1) sbc + (capacity - 1) ldc + w) of a cache?
+static bool positions_overlap(const int32_t* pos, int64_t words, const float* c, int64_t ldc, int64_t sbc, int64_t capacity, int64_t batch, int64_t w) {
+    const char *x = reinterpret_cast<const char*>(pos), *xe = x + 4 * words;
+    const char *y = reinterpret_cast<const char*>(c), *ye = reinterpret_cast<const char*>(c + (batch - 1) * sbc + (capacity - 1) * ldc + w);
+    return x < ye && y < xe;
+}
+
 }  // namespace lg
 
 using namespace lg;
@@ -214,12 +224,10 @@ extern "C" int lg_attention_decode_supported(int64_t capacity, int64_t D) {
     return (D == 32 || D == 64) && capacity >= 1 && capacity <= kDecodeMaxKeys;
 }
 
-extern "C" int lg_attention_decode_f32(const float* q, int64_t sbq, const float* k_new, int64_t sbk, const float* v_new, int64_t sbv,
-                                       float* k_cache, float* v_cache, int64_t ldc, int64_t sbc, const int32_t* pos, float* o, int64_t sbo,
-                                       float* p, int64_t batch, int64_t heads, int64_t capacity, int64_t D, float scale,
-                                       const float* mask, int64_t sbm) {
-    LG_REQUIRE_INIT();
-    const char* name = "lg_attention_decode_f32";
+// both entries: `pos_pitch` words between the positions of neighbouring batch elements (0: one word for the batch)
+static int decode_entry(const char* name, int64_t pos_pitch, const float* q, int64_t sbq, const float* k_new, int64_t sbk, const float* v_new,
+                        int64_t sbv, float* k_cache, float* v_cache, int64_t ldc, int64_t sbc, const int32_t* pos, float* o, int64_t sbo,
+                        float* p, int64_t batch, int64_t heads, int64_t capacity, int64_t D, float scale, const float* mask, int64_t sbm) {
     LG_ARG(lg_attention_decode_supported(capacity, D), "%s: capacity = %lld (1 .. 512), D = %lld (32 or 64) unsupported", name,
            (long long)capacity, (long long)D);
     LG_ARG(batch >= 0 && heads >= 1 && batch <= 65535 && heads <= 65535, "%s: bad batch / heads", name);
@@ -232,6 +240,9 @@ extern "C" int lg_attention_decode_f32(const float* q, int64_t sbq, const float*
     LG_ARG(ldc >= w, "%s: cache row pitch %lld below heads * D = %lld", name, (long long)ldc, (long long)w);
     LG_ARG(!mask || sbm == 0 || sbm >= capacity, "%s: mask batch pitch %lld is neither 0 (one row for the batch) nor >= capacity", name,
            (long long)sbm);
+    LG_ARG(!positions_overlap(pos, pos_pitch ? batch : 1, k_cache, ldc, sbc, capacity, batch, w) &&
+               !positions_overlap(pos, pos_pitch ? batch : 1, v_cache, ldc, sbc, capacity, batch, w),
+           "%s: pos overlaps a cache: the launch writes the caches while other workgroups read their positions", name);
     {
         const int64_t row[2] = {batch, w}, row_strides[2] = {sbo, 1};
         int rc = adam_epilogue_check_strided(o, 4, 2, row, row_strides);
@@ -243,11 +254,35 @@ extern "C" int lg_attention_decode_f32(const float* q, int64_t sbq, const float*
         if (rc != LG_OK) return rc;
         if (p) { rc = adam_epilogue_check_write(p, batch * heads * capacity * 4); if (rc != LG_OK) return rc; }
     }
-    const DecodeArgs a{q, k_new, v_new, sbq, sbk, sbv, k_cache, v_cache, ldc, sbc, pos, o, sbo, p, int(heads), int(capacity), scale,
+    const DecodeArgs a{q, k_new, v_new, sbq, sbk, sbv, k_cache, v_cache, ldc, sbc, pos, pos_pitch, o, sbo, p, int(heads), int(capacity), scale,
                        mask, sbm, rt().status_dev};
     const dim3 grid{unsigned(heads), unsigned(batch)};
     if (D == 64) hipLaunchKernelGGL(attn_decode<64>, grid, dim3(256), 0, rt().stream, a);
     else         hipLaunchKernelGGL(attn_decode<32>, grid, dim3(256), 0, rt().stream, a);
+    return LG_OK;
+}
+
+extern "C" int lg_attention_decode_f32(const float* q, int64_t sbq, const float* k_new, int64_t sbk, const float* v_new, int64_t sbv,
+                                       float* k_cache, float* v_cache, int64_t ldc, int64_t sbc, const int32_t* pos, float* o, int64_t sbo,
+                                       float* p, int64_t batch, int64_t heads, int64_t capacity, int64_t D, float scale,
+                                       const float* mask, int64_t sbm) {
+    LG_REQUIRE_INIT();
+    const int rc = decode_entry("lg_attention_decode_f32", 0, q, sbq, k_new, sbk, v_new, sbv, k_cache, v_cache, ldc, sbc, pos, o, sbo, p, batch, heads,
+                        capacity, D, scale, mask, sbm);
+    if (rc != LG_OK || batch == 0) return rc;
+    LG_CHECK_LAUNCH();
+    return LG_OK;
+}
+
+// the same launch with a position per batch element: pos holds `batch` contiguous words, element b uses t = pos[b]
+extern "C" int lg_attention_decode_rows_f32(const float* q, int64_t sbq, const float* k_new, int64_t sbk, const float* v_new, int64_t sbv,
+                                            float* k_cache, float* v_cache, int64_t ldc, int64_t sbc, const int32_t* pos, float* o, int64_t sbo,
+                                            float* p, int64_t batch, int64_t heads, int64_t capacity, int64_t D, float scale,
+                                            const float* mask, int64_t sbm) {
+    LG_REQUIRE_INIT();
+    const int rc = decode_entry("lg_attention_decode_rows_f32", 1, q, sbq, k_new, sbk, v_new, sbv, k_cache, v_cache, ldc, sbc, pos, o, sbo, p, batch,
+                        heads, capacity, D, scale, mask, sbm);
+    if (rc != LG_OK || batch == 0) return rc;
     LG_CHECK_LAUNCH();
     return LG_OK;
 }

@@ -1,7 +1,8 @@
 // Attention of m NEW tokens against a filled key / value cache in one launch (gfx950, fp32 MFMA): lg_attention_extend_f32.
 //
 // Between the causal forward (the whole prompt, an empty cache: attention.hip / attention_long.hip) and the decode kernel (one
-// token, a filled cache: decode.hip).  With t = the word `pos` holds on the device, query row i sits at position t + i and
+// token, a filled cache: decode.hip).  lg_attention_extend_rows_f32 is the same kernel with a position word per batch element
+// (ExtendArgs::pos_pitch = 1 in place of 0): everything below holds per element with its own t.  With t = the word `pos` holds on the device, query row i sits at position t + i and
 // sees keys 0 .. t + i: the cache's rows 0 .. t - 1, then rows 0 .. i of k_new / v_new - which this launch also writes to rows
 // t .. t + m - 1 of the caches, and which it always takes from the new-token buffers, never back from the cache (other
 // workgroups of the same launch write those rows).  m query rows against up to 512 keys is a matrix-matrix problem: the
@@ -35,7 +36,8 @@ struct ExtendArgs {
     int64_t ldq, sbq, ldk, sbk, ldv, sbv;
     float *k_cache, *v_cache;            // element (b, j, head, d) at x + b * sbc + j * ldc + head * D + d
     int64_t ldc, sbc;
-    const int32_t* pos;
+    const int32_t* pos;                  // batch element b reads pos[b * pos_pitch]: pitch 0 = one word for the batch, 1 = a word per row
+    int64_t pos_pitch;
     float* o;                            // context, addressed like q
     int64_t ldo, sbo;
     float* p;                            // NULL, or (batch, heads, m, capacity) dense
@@ -76,10 +78,11 @@ __global__ void __launch_bounds__(256) attn_extend(const ExtendArgs a) {
     const int m = a.m, C = a.capacity, Cp = round32(C), PP = Cp + 4;
     constexpr int PQ = D + 4, PV = D + 8, Q4 = D / 4;
     constexpr int NB = 32 * Q4 / 256, NA = kExtChunk * Q4 / 256;
-    const int t = *a.pos;
+    const int t = a.pos[int64_t(blockIdx.z) * a.pos_pitch];       // uniform over the workgroup either way: a scalar load
     const int tid = threadIdx.x;
     if (t < 0 || t > C - m) {
-        // a bounds check, never a fault: nothing is written, the next synchronising call reports LG_EINDEX
+        // a bounds check, never a fault: nothing is written for this batch element (the others of a per-row launch are computed
+        // as usual), the next synchronising call reports LG_EINDEX
         if (tid == 0) __hip_atomic_fetch_or(a.status, LG_STATUS_BAD_INDEX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         return;
     }
@@ -242,6 +245,13 @@ static bool extend_overlap(const float* x, int64_t ldx, int64_t sbx, int64_t row
     return x < ye && y < xe;
 }
 
+// do the `words` position words share an address with the floats [c, c + (batch - 1) sbc + (capacity - 1) ldc + w) of a cache?
+static bool positions_overlap(const int32_t* pos, int64_t words, const float* c, int64_t ldc, int64_t sbc, int64_t capacity, int64_t batch, int64_t w) {
+    const char *x = reinterpret_cast<const char*>(pos), *xe = x + 4 * words;
+    const char *y = reinterpret_cast<const char*>(c), *ye = reinterpret_cast<const char*>(c + (batch - 1) * sbc + (capacity - 1) * ldc + w);
+    return x < ye && y < xe;
+}
+
 template <int D>
 static int launch_extend(const ExtendArgs& a, dim3 grid) {
     const size_t bytes = size_t(attn_extend_lds_floats<D>(round32(a.capacity))) * 4;
@@ -259,12 +269,11 @@ extern "C" int lg_attention_extend_supported(int64_t m, int64_t capacity, int64_
     return (D == 32 || D == 64) && m >= 1 && m <= capacity && capacity <= kExtMaxKeys;
 }
 
-extern "C" int lg_attention_extend_f32(const float* q, int64_t ldq, int64_t sbq, const float* k_new, int64_t ldk, int64_t sbk,
-                                       const float* v_new, int64_t ldv, int64_t sbv, float* k_cache, float* v_cache, int64_t ldc,
-                                       int64_t sbc, const int32_t* pos, float* o, int64_t ldo, int64_t sbo, float* p, int64_t batch,
-                                       int64_t heads, int64_t m, int64_t capacity, int64_t D, float scale, const float* mask, int64_t sbm) {
-    LG_REQUIRE_INIT();
-    const char* name = "lg_attention_extend_f32";
+// both entries: `pos_pitch` words between the positions of neighbouring batch elements (0: one word for the batch)
+static int extend_entry(const char* name, int64_t pos_pitch, const float* q, int64_t ldq, int64_t sbq, const float* k_new, int64_t ldk, int64_t sbk,
+                        const float* v_new, int64_t ldv, int64_t sbv, float* k_cache, float* v_cache, int64_t ldc, int64_t sbc,
+                        const int32_t* pos, float* o, int64_t ldo, int64_t sbo, float* p, int64_t batch, int64_t heads, int64_t m,
+                        int64_t capacity, int64_t D, float scale, const float* mask, int64_t sbm) {
     LG_ARG(lg_attention_extend_supported(m, capacity, D), "%s: m = %lld (1 .. capacity), capacity = %lld (1 .. 512), D = %lld (32 or 64) unsupported",
            name, (long long)m, (long long)capacity, (long long)D);
     LG_ARG(batch >= 0 && heads >= 1 && batch <= 65535 && heads <= 65535, "%s: bad batch / heads", name);
@@ -279,6 +288,9 @@ extern "C" int lg_attention_extend_f32(const float* q, int64_t ldq, int64_t sbq,
     LG_ARG(!extend_overlap(k_new, ldk, sbk, m, k_cache, ldc, sbc, capacity, batch, w) && !extend_overlap(k_new, ldk, sbk, m, v_cache, ldc, sbc, capacity, batch, w) &&
                !extend_overlap(v_new, ldv, sbv, m, k_cache, ldc, sbc, capacity, batch, w) && !extend_overlap(v_new, ldv, sbv, m, v_cache, ldc, sbc, capacity, batch, w),
            "%s: k_new / v_new overlap a cache: the launch writes the caches while other workgroups read the new rows", name);
+    LG_ARG(!positions_overlap(pos, pos_pitch ? batch : 1, k_cache, ldc, sbc, capacity, batch, w) &&
+               !positions_overlap(pos, pos_pitch ? batch : 1, v_cache, ldc, sbc, capacity, batch, w),
+           "%s: pos overlaps a cache: the launch writes the caches while other workgroups read their positions", name);
     {
         const int64_t rows[3] = {batch, m, w}, row_strides[3] = {sbo, ldo, 1};
         int rc = adam_epilogue_check_strided(o, 4, 3, rows, row_strides);
@@ -290,11 +302,34 @@ extern "C" int lg_attention_extend_f32(const float* q, int64_t ldq, int64_t sbq,
         if (rc != LG_OK) return rc;
         if (p) { rc = adam_epilogue_check_write(p, batch * heads * m * capacity * 4); if (rc != LG_OK) return rc; }
     }
-    const ExtendArgs a{q, k_new, v_new, ldq, sbq, ldk, sbk, ldv, sbv, k_cache, v_cache, ldc, sbc, pos, o, ldo, sbo, p,
+    const ExtendArgs a{q, k_new, v_new, ldq, sbq, ldk, sbk, ldv, sbv, k_cache, v_cache, ldc, sbc, pos, pos_pitch, o, ldo, sbo, p,
                        int(heads), int(capacity), int(m), scale, mask, sbm, rt().status_dev};
     const dim3 grid{unsigned((m + 31) / 32), unsigned(heads), unsigned(batch)};
     const int rc = D == 64 ? launch_extend<64>(a, grid) : launch_extend<32>(a, grid);
-    if (rc != LG_OK) return rc;
+    return rc;
+}
+
+extern "C" int lg_attention_extend_f32(const float* q, int64_t ldq, int64_t sbq, const float* k_new, int64_t ldk, int64_t sbk,
+                                       const float* v_new, int64_t ldv, int64_t sbv, float* k_cache, float* v_cache, int64_t ldc,
+                                       int64_t sbc, const int32_t* pos, float* o, int64_t ldo, int64_t sbo, float* p, int64_t batch,
+                                       int64_t heads, int64_t m, int64_t capacity, int64_t D, float scale, const float* mask, int64_t sbm) {
+    LG_REQUIRE_INIT();
+    const int rc = extend_entry("lg_attention_extend_f32", 0, q, ldq, sbq, k_new, ldk, sbk, v_new, ldv, sbv, k_cache, v_cache, ldc, sbc, pos, o, ldo, sbo,
+                        p, batch, heads, m, capacity, D, scale, mask, sbm);
+    if (rc != LG_OK || batch == 0) return rc;
+    LG_CHECK_LAUNCH();
+    return LG_OK;
+}
+
+// the same launch with a position per batch element: pos holds `batch` contiguous words, element b uses t = pos[b]
+extern "C" int lg_attention_extend_rows_f32(const float* q, int64_t ldq, int64_t sbq, const float* k_new, int64_t ldk, int64_t sbk,
+                                            const float* v_new, int64_t ldv, int64_t sbv, float* k_cache, float* v_cache, int64_t ldc,
+                                            int64_t sbc, const int32_t* pos, float* o, int64_t ldo, int64_t sbo, float* p, int64_t batch,
+                                            int64_t heads, int64_t m, int64_t capacity, int64_t D, float scale, const float* mask, int64_t sbm) {
+    LG_REQUIRE_INIT();
+    const int rc = extend_entry("lg_attention_extend_rows_f32", 1, q, ldq, sbq, k_new, ldk, sbk, v_new, ldv, sbv, k_cache, v_cache, ldc, sbc, pos, o, ldo,
+                        sbo, p, batch, heads, m, capacity, D, scale, mask, sbm);
+    if (rc != LG_OK || batch == 0) return rc;
     LG_CHECK_LAUNCH();
     return LG_OK;
 }

@@ -290,9 +290,17 @@ class KVCache(object):
     host for the backends that have no decode op (they slice the cache with it).  `advance()` adds 1 on the device with the
     in-place int32 add - inside a hipGraph capture it is recorded like any kernel, and every replay moves the position on.
     State, not parameters: not a Module, so it is in no `parameters()` / `buffers()` and never reaches an optimizer.  Not a
-    class of the reference (its model has no decoder)."""
+    class of the reference (its model has no decoder).
 
-    def __init__(self, layers: int, batch: int, capacity: int, width: int, like=None):
+    `per_row=True`: every sequence of the batch has a position of its own (a ragged batch: prompts of different lengths, rows
+    that stop at an end-of-sequence token).  `pos` then has shape (batch,) - the backend's attention launches read word r for
+    sequence r -, `positions(m)` is (batch, m), `set_lengths` takes a length per row and `advance` an int or a length per row.
+    The host mirror is `lengths`, an int64 array: valid only while every change came from the host, None once the device moved
+    the positions by values the host has not seen (`committed` with an end-of-sequence id).  `length` is then an upper bound of
+    every row's position - what the routing between prefill and decode step and the capacity checks need, never an index.
+    Without `per_row` every attribute, shape and launch is as it was."""
+
+    def __init__(self, layers: int, batch: int, capacity: int, width: int, like=None, per_row: bool = False):
         cls = Tensor if like is None else type(like)
         dtype = np.dtype(np.float32 if like is None else like.dtype)
         assert layers >= 1 and batch >= 1 and capacity >= 1 and width >= 1
@@ -300,13 +308,16 @@ class KVCache(object):
         shape = (self.batch, self.capacity, self.width)          # (an array of its own each: CpuTensor.from_numpy adopts what it is given)
         self.k = [cls.from_numpy(np.zeros(shape, dtype), requires_grad=False) for _ in range(self.layers)]
         self.v = [cls.from_numpy(np.zeros(shape, dtype), requires_grad=False) for _ in range(self.layers)]
-        self.pos = cls.from_numpy(np.zeros(1, np.int32), requires_grad=False)
+        self.per_row = bool(per_row)
+        self.pos = cls.from_numpy(np.zeros(self.batch if self.per_row else 1, np.int32), requires_grad=False)
         self.length = 0
+        self.lengths = np.zeros(self.batch, np.int64) if self.per_row else None
         self._arange = {}           # m -> the int32 constant 0 .. m - 1 on the cache's backend
 
     def positions(self, m: int):
         """the int32 position ids `pos + arange(m)` of the next m tokens, shape (m,): one broadcast add on the cache's backend -
-        no host read, and inside a hipGraph capture it is recorded like any kernel (a replay reads the position as it is then)"""
+        no host read, and inside a hipGraph capture it is recorded like any kernel (a replay reads the position as it is then).
+        per_row: shape (batch, m), `pos[:, None] + arange(m)` - still one broadcast add"""
         m = int(m)
         assert m >= 1
         if m not in self._arange:
@@ -314,24 +325,64 @@ class KVCache(object):
             if hasattr(t, "freeze"):
                 t.freeze()          # a constant, like a model's position ids
             self._arange[m] = t
-        ids = self.pos + self._arange[m]
+        ids = (self.pos.reshape(self.batch, 1) if self.per_row else self.pos) + self._arange[m]
         ids._requires_grad = False  # ids are state like `pos`: they go into lookups by keyword and take no gradient
         return ids
 
-    def advance(self, n: int = 1) -> None:
-        """the next token's position, + n: on the device, and in the host mirror"""
+    def advance(self, n=1) -> None:
+        """the next token's position, + n: on the device, and in the host mirror.  per_row: n is an int for every row, or a
+        length per row - a host sequence / array of `batch` ints (uploaded; the mirror stays valid) or an int32 tensor (batch,)
+        on the cache's backend (nothing is read back: the mirror stays valid only where reading is free, on the numpy backend)"""
+        if self.per_row and not isinstance(n, (int, np.integer)):
+            if hasattr(n, "shape") and not isinstance(n, np.ndarray):
+                assert tuple(n.shape) == (self.batch,) and np.dtype(n.dtype) == np.int32, "KVCache.advance: a tensor of lengths is int32 (batch,)"
+                step, host = n, (np.asarray(n.data, np.int64) if isinstance(getattr(n, "data", None), np.ndarray) else None)
+            else:
+                host = np.asarray(n, np.int64)
+                assert host.shape == (self.batch,) and (host >= 0).all(), "KVCache.advance: %d lengths >= 0, one per row" % self.batch
+                step = type(self.pos).from_numpy(host.astype(np.int32), requires_grad=False)
+            self.pos += step
+            self.lengths = None if host is None or self.lengths is None else self.lengths + host
+            if self.lengths is not None:
+                self.length = int(self.lengths.max())
+            else:               # the upper bound moves by the largest step the host knows of
+                self.length = self.capacity if host is None else min(self.capacity, self.length + int(host.max()))
+            return
         self.pos += int(n)
         self.length += int(n)
+        if self.lengths is not None:
+            self.lengths = self.lengths + int(n)
+
+    def committed(self, n: int = 1, eos: bool = False) -> None:
+        """per_row: `decode_commit` moved the positions on the device n times (eagerly, or as replays of a captured step): the host
+        follows.  Without an end-of-sequence id every row moved; with one (eos=True) which rows moved is known on the device
+        only - `lengths` is None from here on and `length` stays the upper bound"""
+        assert self.per_row, "KVCache.committed goes with per_row=True"
+        self.length += int(n)
+        self.lengths = None if eos or self.lengths is None else self.lengths + int(n)
+
+    def set_lengths(self, lengths) -> None:
+        """per_row: rows 0 .. lengths[r] - 1 of sequence r have been filled: its next token's position is lengths[r]"""
+        assert self.per_row, "KVCache.set_lengths goes with per_row=True (set_length: one position for the batch)"
+        host = np.asarray(lengths, np.int64)
+        assert host.shape == (self.batch,) and (host >= 0).all() and (host <= self.capacity).all(), \
+            "KVCache: %d lengths within 0 .. %d, one per row, got %s" % (self.batch, self.capacity, lengths)
+        self.pos[:] = type(self.pos).from_numpy(host.astype(np.int32), requires_grad=False)
+        self.lengths, self.length = host.copy(), int(host.max())
 
     def replayed(self, n: int = 1) -> None:
         """a captured step that holds `advance()` was replayed n more times: the device position moved, the host mirror follows"""
         self.length += int(n)
+        if self.lengths is not None:
+            self.lengths = self.lengths + int(n)
 
     def set_length(self, n: int) -> None:
         """rows 0 .. n - 1 have been filled (a prompt): the next token's position is n"""
         assert 0 <= n <= self.capacity, "KVCache: %d positions do not fit a capacity of %d" % (n, self.capacity)
         self.pos.fill(int(n))
         self.length = int(n)
+        if self.per_row:
+            self.lengths = np.full(self.batch, int(n), np.int64)
 
     def reset(self) -> None:
         """forget every token: the position goes back to 0 (the rows stay as they are - nothing reads beyond the position)"""
