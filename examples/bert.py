@@ -39,6 +39,13 @@ Differences from the reference, on purpose:
                                                        # a ragged batch in one run: prompts of different lengths, right-padded, every
                                                        # sequence at its own positions (nn.KVCache(per_row=True), `generate(lengths=)`);
                                                        # --eos ID: a row that draws ID stops, the others go on
+    python examples/bert.py --serve 16 --slots 4 --chunk 16 [--eos ID] [--graph] [--sample ...] [--cpu]
+                                                       # continuous batching: 16 requests of different lengths and budgets through 4
+                                                       # cache slots (`serve`, nn.RequestPool) - a slot whose request has finished takes
+                                                       # the next waiting prompt, in pieces of at most 16 tokens, while the other slots
+                                                       # go on decoding; one attention launch per layer for all of them (a token count
+                                                       # per slot, csrc/extend.hip), one launch of bookkeeping per step (csrc/serve.hip),
+                                                       # one word read back every few steps; --graph: the step is captured once
     python examples/bert.py --mlm --bf16-decoder       # the decoder onto the vocabulary (forward, dx, dW) on the bf16 matrix cores:
                                                        # config key `decoder_precision="bf16"`; tensors stay float32
 """
@@ -179,12 +186,16 @@ class BertSelfAttention(nn.Module):
         probs = scores.softmax(axis=-1)
         return (probs @ v).transpose(0, 2, 1, 3).reshape(b, 1, self.h * self.d), probs
 
-    def _rows_composite(self, hidden, attention_mask, cache, index):
+    def _rows_composite(self, hidden, attention_mask, cache, index, count=None):
         """`_decode` (m = 1) and `_extend` over the tensor API for a cache with a position per sequence (nn.KVCache(per_row=True)):
         CpuTensor, float64 tapes and head sizes the kernels refuse.  Sequence r writes its m new rows at positions t_r .. t_r + m - 1
         and its query i sees keys 0 .. t_r + i; keys beyond - the other sequences' reach, and whatever the cache holds there - are
         hidden with the usual -10000 bias.  The positions are taken from the cache's host mirror while it is valid; otherwise
-        they are READ from `cache.pos`: free on CpuTensor, a synchronising device read on any other backend."""
+        they are READ from `cache.pos`: free on CpuTensor, a synchronising device read on any other backend.
+        count (int32 (b,), READ like the positions): sequence r has count[r] real tokens among its m rows - only those are
+        written to the cache (at t_r .. t_r + count[r] - 1: only they have to fit it), and the context rows of the others are 0."""
+        if count is not None:
+            return self._counted_composite(hidden, attention_mask, cache, index, count)
         b, m = hidden.shape[0], hidden.shape[1]
         k_cache, v_cache = cache.k[index], cache.v[index]
         t = cache.lengths if cache.lengths is not None else np.asarray(cache.pos.numpy(), np.int64)
@@ -209,6 +220,38 @@ class BertSelfAttention(nn.Module):
         probs = scores.softmax(axis=-1)
         return (probs @ v).transpose(0, 2, 1, 3).reshape(b, m, self.h * self.d), probs
 
+    def _counted_composite(self, hidden, attention_mask, cache, index, count):
+        """`_rows_composite` with a token count per sequence - the definition of `self_attention_extend(count=)`.  Positions and
+        counts are read from the tensors (whoever moved them: `advance`, `serve_commit`)"""
+        b, m = hidden.shape[0], hidden.shape[1]
+        k_cache, v_cache = cache.k[index], cache.v[index]
+        t, c = np.asarray(cache.pos.numpy(), np.int64), np.asarray(count.numpy(), np.int64)
+        assert c.shape == (b,) and (c >= 0).all() and (c <= m).all() and (t >= 0).all() and (t + c <= cache.capacity).all(), \
+            "the cache holds %s of %d positions: no room for %s more of the %d rows given" % (t.tolist(), cache.capacity, c.tolist(), m)
+        n = max(int((t + c).max()), 1)
+        q, k, v = self.query(hidden), self.key(hidden), self.value(hidden)
+        for r in range(b):
+            if c[r]:
+                k_cache[r:r + 1, int(t[r]):int(t[r] + c[r])] = k[r:r + 1, :int(c[r])]
+                v_cache[r:r + 1, int(t[r]):int(t[r] + c[r])] = v[r:r + 1, :int(c[r])]
+        q = q.reshape(b, m, self.h, self.d).transpose(0, 2, 1, 3)
+        k = k_cache[:, :n].reshape(b, n, self.h, self.d).transpose(0, 2, 3, 1)
+        v = v_cache[:, :n].reshape(b, n, self.h, self.d).transpose(0, 2, 1, 3)
+        scores = (q @ k) / math.sqrt(self.d)
+        if attention_mask is not None:
+            mask = attention_mask[:, :n]
+            scores = scores + ((1.0 - mask.reshape(mask.shape[0], 1, 1, n)) * -10000.0).detach()
+        # (b, 1, m, n): key j is visible to query i of sequence r where j <= t_r + i (a row without a token: as its last real one)
+        reach = t[:, None, None] + np.minimum(np.arange(m)[None, :, None], np.maximum(c - 1, 0)[:, None, None])
+        visible = (np.arange(n)[None, None, :] <= reach).astype(scores.dtype)
+        visible = scores.__class__.from_numpy(visible.reshape(b, 1, m, n), requires_grad=False)
+        scores = scores + ((1.0 - visible) * -10000.0).detach()
+        probs = scores.softmax(axis=-1)
+        real = (np.arange(m)[None, :] < c[:, None]).astype(scores.dtype)
+        constant = lambda a: scores.__class__.from_numpy(np.ascontiguousarray(a), requires_grad=False)       # noqa: E731
+        context = (probs @ v).transpose(0, 2, 1, 3).reshape(b, m, self.h * self.d)
+        return context * constant(real.reshape(b, m, 1)), probs * constant(real.reshape(b, 1, m, 1))
+
     def _triangle_behind(self, like, t, m):
         """rows t .. t + m - 1 of the lower-triangular constant of t + m positions, (1, 1, m, t + m): query t + i sees keys 0 .. t + i"""
         key = (like.__class__, t, m, np.dtype(like.dtype))
@@ -219,10 +262,14 @@ class BertSelfAttention(nn.Module):
             self._tril[key] = tri
         return self._tril[key]
 
-    def _extend(self, hidden, attention_mask, cache, index):
+    def _extend(self, hidden, attention_mask, cache, index, count=None):
         """m new tokens per sequence behind the cache's position t (any t >= 0): query row i at position t + i attends to keys
         0 .. t + i - the rows the causal forward computes for queries t .. t + m - 1.  attention_mask: None or (b, capacity) over
-        the cache's rows"""
+        the cache's rows.  count: None, or an int32 tensor (b,) next to a cache with a position per sequence - sequence r has
+        count[r] real tokens among its m rows (a step that mixes decoding, prefilling and idle sequences): the fused route passes
+        it to the launch as it is, the composite reads it"""
+        counted = {} if count is None else {"count": count}
+        assert count is None or getattr(cache, "per_row", False), "count= takes a cache with a position per sequence: nn.KVCache(..., per_row=True)"
         b, m = hidden.shape[0], hidden.shape[1]
         scale = math.sqrt(self.d) ** -1
         k_cache, v_cache = cache.k[index], cache.v[index]
@@ -233,10 +280,10 @@ class BertSelfAttention(nn.Module):
             # the device and writes the m new key / value rows into the cache itself
             extra = {"mask": attention_mask} if attention_mask is not None else {}
             context = hidden.self_attention_extend(self.query.weight, self.query.bias, self.key.weight, self.key.bias, self.value.weight,
-                                                   self.value.bias, k_cache, v_cache, cache.pos, heads=self.h, scale=scale, **extra)
+                                                   self.value.bias, k_cache, v_cache, cache.pos, heads=self.h, scale=scale, **extra, **counted)
             return context, None
         if getattr(cache, "per_row", False):
-            return self._rows_composite(hidden, attention_mask, cache, index)
+            return self._rows_composite(hidden, attention_mask, cache, index, **counted)
         # the same over the tensor API: the host mirror of the position slices the cache
         t = cache.length
         n = t + m
@@ -255,13 +302,14 @@ class BertSelfAttention(nn.Module):
         probs = scores.softmax(axis=-1)
         return (probs @ v).transpose(0, 2, 1, 3).reshape(b, m, self.h * self.d), probs
 
-    def forward(self, hidden, attention_mask=None, cache=None, index=None, append=False):
+    def forward(self, hidden, attention_mask=None, cache=None, index=None, append=False, count=None):
         """cache (nn.KVCache) and index (this layer's): with tokens in the cache, `hidden` is one new token per sequence (`_decode`);
         with an empty one, the prompt takes the path below and its keys and values become the cache's first rows.  append=True:
-        `hidden` is m >= 1 new tokens per sequence behind whatever the cache holds (`_extend`)"""
+        `hidden` is m >= 1 new tokens per sequence behind whatever the cache holds (`_extend`), count= its tokens per sequence"""
+        assert count is None or (cache is not None and append), "count= goes with cache= and append=True"
         if cache is not None and append:
             assert self.causal, "appending to a cache takes a causal model"
-            return self._extend(hidden, attention_mask, cache, index)
+            return self._extend(hidden, attention_mask, cache, index, **({} if count is None else {"count": count}))
         if cache is not None and cache.length > 0:
             assert self.causal and hidden.shape[1] == 1, "a decode step is one token per sequence of a causal model"
             return self._decode(hidden, attention_mask, cache, index)
@@ -337,11 +385,12 @@ class BertAttention(nn.Module):
         self.output.dense = nn.Linear(hidden_size, hidden_size)
         self.output.LayerNorm = nn.LayerNorm(hidden_size)
 
-    def forward(self, hidden_in, attention_mask=None, cache=None, index=None, append=False):
+    def forward(self, hidden_in, attention_mask=None, cache=None, index=None, append=False, count=None):
         if cache is None:
             hidden, probs = self.self(hidden_in, attention_mask=attention_mask)
         elif append:
-            hidden, probs = self.self(hidden_in, attention_mask=attention_mask, cache=cache, index=index, append=True)
+            hidden, probs = self.self(hidden_in, attention_mask=attention_mask, cache=cache, index=index, append=True,
+                                      **({} if count is None else {"count": count}))
         else:
             hidden, probs = self.self(hidden_in, attention_mask=attention_mask, cache=cache, index=index)
         if self.training and self.dropout.p > 0:
@@ -368,11 +417,11 @@ class BertLayer(nn.Module):
         self.output.dense = nn.Linear(intermediate_size, hidden_size)
         self.output.LayerNorm = nn.LayerNorm(hidden_size)
 
-    def forward(self, hidden, attention_mask=None, cache=None, index=None, append=False):
+    def forward(self, hidden, attention_mask=None, cache=None, index=None, append=False, count=None):
         if cache is None:
             hidden, probs = self.attention(hidden, attention_mask)
         elif append:
-            hidden, probs = self.attention(hidden, attention_mask, cache=cache, index=index, append=True)
+            hidden, probs = self.attention(hidden, attention_mask, cache=cache, index=index, append=True, **({} if count is None else {"count": count}))
         else:
             hidden, probs = self.attention(hidden, attention_mask, cache=cache, index=index)
         if self.training and self.dropout.p > 0:
@@ -404,10 +453,11 @@ class BertModel(nn.Module):
                                                        attention_probs_dropout_prob, causal=causal)
                                              for _ in range(num_hidden_layers)])
 
-    def forward(self, input_ids, attention_mask=None, token_type_ids=None, cache=None, append=False):
+    def forward(self, input_ids, attention_mask=None, token_type_ids=None, cache=None, append=False, count=None, token_positions=None):
+        assert (count is None and token_positions is None) or (cache is not None and append), "count= and token_positions= go with cache= and append=True"
         if cache is not None:
             if append:
-                return self._forward_append(input_ids, attention_mask, token_type_ids, cache)
+                return self._forward_append(input_ids, attention_mask, token_type_ids, cache, count, token_positions)
             return self._forward_cached(input_ids, attention_mask, token_type_ids, cache)
         assert not append, "append=True goes with a cache"
         hidden = self.embeddings(input_ids, token_type_ids=token_type_ids)
@@ -415,14 +465,32 @@ class BertModel(nn.Module):
             hidden, _ = layer(hidden, attention_mask=attention_mask)
         return hidden
 
-    def _forward_append(self, input_ids, attention_mask, token_type_ids, cache):
+    def _forward_append(self, input_ids, attention_mask, token_type_ids, cache, count=None, token_positions=None):
         """inference with an nn.KVCache that may hold tokens already, outside the tape: `input_ids` (b, m) are the next m >= 1
         tokens at the cache's position, whatever it is (attention_mask: None or (b, capacity) over the cache's rows, as a decode
         step reads it).  Their keys and values become the cache's next m rows and every one of the m rows comes back; the caller
-        moves the position on with `cache.advance(m)`"""
+        moves the position on with `cache.advance(m)`.
+        count (int32 (b,), a cache with a position per sequence): sequence r has count[r] real tokens among its m rows - a step
+        that mixes decoding (1), prefilling (up to m) and idle (0) sequences.  Only the real tokens' keys and values reach the
+        cache and only they have to fit it; the rows behind them come back as whatever the layers make of an attention context
+        of zeros - nobody reads them.  The caller moves the positions on (`cache.advance(count)`, or `serve_commit`).
+        token_positions (int32 (b, m)): the position ids to embed at, in place of `cache.positions(m)` - nn.RequestPool's, which
+        are 0 where a row holds no token and so never index past the position table"""
         b, m = input_ids.shape
         positions = self.embeddings.position_embeddings.weight.shape[0]
         assert cache.layers == len(self.encoder.layer) and cache.batch == b, "the cache was made for %d layers and a batch of %d" % (cache.layers, cache.batch)
+        if count is not None or token_positions is not None:
+            assert getattr(cache, "per_row", False), "count= / token_positions= take a cache with a position per sequence: nn.KVCache(..., per_row=True)"
+            assert m >= 1 and cache.capacity <= positions and (token_positions is not None or cache.capacity + m - 1 <= positions), \
+                "a cache of %d positions and rows of %d tokens reach position %d of %d position embeddings: pass token_positions=" % (
+                    cache.capacity, m, cache.capacity + m - 1, positions)
+            counted = {} if count is None else {"count": count}
+            with light.no_grad():
+                hidden = self.embeddings(input_ids, token_type_ids=token_type_ids,
+                                         token_positions=cache.positions(m) if token_positions is None else token_positions)
+                for index, layer in enumerate(self.encoder.layer):
+                    hidden, _ = layer(hidden, attention_mask=attention_mask, cache=cache, index=index, append=True, **counted)
+            return hidden
         if getattr(cache, "per_row", False):
             # a position per sequence: checked on the host where the mirror is valid, by the launches' own bounds checks otherwise
             assert m >= 1 and cache.capacity <= positions and (cache.lengths is None or (cache.lengths + m <= cache.capacity).all()), \
@@ -476,11 +544,16 @@ class BertForMaskedLM(nn.Module):
         self.cls.predictions.decoder = nn.Linear(hidden_size, vocab_size, bias=False, precision=decoder_precision)
         self.cls.predictions.bias = light.zeros(vocab_size)
 
-    def forward(self, input_ids, attention_mask=None, token_type_ids=None, masked_positions=None, cache=None, append=False):
+    def forward(self, input_ids, attention_mask=None, token_type_ids=None, masked_positions=None, cache=None, append=False, count=None,
+                token_positions=None):
         if cache is not None:
             # inference through an nn.KVCache (BertModel._forward_cached, append=True: _forward_append): the logits of every row
             # given, outside the tape
             extra = {"append": True} if append else {}
+            if count is not None:
+                extra["count"] = count
+            if token_positions is not None:
+                extra["token_positions"] = token_positions
             h = self.bert(input_ids=input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids, cache=cache, **extra)
             with light.no_grad():
                 return self.head(h)
@@ -809,8 +882,121 @@ def generate(model, ids, max_new_tokens, attention_mask=None, cache=None, graph=
     return result()
 
 
+def serve_step(model, pool, sampler=None, eos=None):
+    """one step of `serve`, all on the model's backend and the same function whatever the slots hold: the pool's (slots, chunk)
+    ids go through the append forward with the pool's token count per slot - a decoding slot has 1 real token, a prefilling one
+    up to `chunk`, an idle one none -, ONE gather takes each slot's last real row to the head, and ONE `serve_commit` stores the
+    tokens drawn for the decoding slots, frees the slots whose request has finished, admits waiting requests to them and lays
+    out the next step's ids.  No host read, no value from the host: a captured step replays as it stands."""
+    hidden = model.bert(pool.ids, cache=pool.cache, append=True, count=pool.count, token_positions=pool.position_ids)
+    width = hidden.shape[-1]
+    rows = hidden.reshape(-1, width)[pool.last].reshape(pool.slots, 1, width)
+    pool.commit(next_token(model.head(rows), sampler), eos=eos)
+
+
+def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, pad_token_id=0, graph=None, temperature=None, top_k=0,
+          top_p=1.0, poll=8, lengths=None, cache=None):
+    """continuous batching: N requests through `slots` cache slots, a finished slot refilled at once from the queue while the
+    others go on decoding.  prompts: a list of N int sequences, or (N, P) right-padded ids (an array or a tensor) with lengths=;
+    max_new_tokens: an int, or N ints - a budget per request.  Returns (out (N, G) int32 with G = the largest budget, filled with
+    pad_token_id behind each request's tokens; out_len (N,) int32) on the model's backend, and a dict of statistics: `steps`.
+    A request ends with eos_token_id (stored, then fed to nobody) or when its budget is used up.
+
+    Every step is `serve_step`: prompts enter the cache in pieces of at most `chunk` tokens next to the slots that decode, one
+    launch of attention per layer for all of them (csrc/extend.hip, a token count per slot), and the bookkeeping between two steps
+    is one launch (csrc/serve.hip, `nn.RequestPool`).  The host reads ONE word every `poll` steps - the number of finished
+    requests - and stops when it is N; nothing else is read back (the caller's `.numpy()` is the first read of the tokens).  Up
+    to poll - 1 steps run after the last request has finished: every slot is idle then and nothing changes.  graph: an empty
+    HipGraph - the first step runs eagerly (a real step), the second is captured and then replayed; no state is saved or
+    restored, since every step is the same function of the device state.
+    Greedy results depend on a request's own data only: not on slots, chunk or the order of admission.  With a temperature every
+    step takes ONE call of the random stream for all slots, idle ones included, and a slot's numbers depend on its index: a
+    sampled run is reproducible for a given seed, slots and chunk (eager or captured), but NOT independent of the schedule.
+    cache: an nn.KVCache(per_row=True) of `slots` rows to use (default: one whose capacity is the longest request's need)."""
+    weight = model.bert.embeddings.word_embeddings.weight
+    cls = weight.__class__
+    layer0 = model.bert.encoder.layer[0].attention.self
+    assert layer0.causal, "serve needs a model built with causal=True"
+    if lengths is None:
+        rows = [np.asarray(p, np.int64).reshape(-1) for p in prompts]
+        assert len(rows) >= 1 and all(len(p) >= 1 for p in rows), "serve: at least one prompt, each of at least one token"
+        lengths = np.array([len(p) for p in rows], np.int64)
+        padded = np.zeros((len(rows), int(lengths.max())), np.int32)
+        for r, p in enumerate(rows):
+            padded[r, :len(p)] = p
+    else:
+        padded, lengths = np.asarray(prompts.numpy() if hasattr(prompts, "numpy") else prompts), np.asarray(lengths, np.int64)
+    n = padded.shape[0]
+    budgets = np.full(n, max_new_tokens, np.int64) if np.ndim(max_new_tokens) == 0 else np.asarray(max_new_tokens, np.int64)
+    assert budgets.shape == (n,) and (budgets >= 1).all(), "serve: max_new_tokens is an int >= 1 or one per request"
+    assert int(poll) == poll and poll >= 1 and slots >= 1 and chunk >= 1
+    positions = model.bert.embeddings.position_embeddings.weight.shape[0]
+    if cache is None:
+        cache = nn.KVCache(len(model.bert.encoder.layer), int(slots), int((lengths + budgets - 1).max()), layer0.h * layer0.d, like=weight, per_row=True)
+    assert cache.batch == slots, "serve: the cache has %d rows for %d slots" % (cache.batch, slots)
+    chunk = min(int(chunk), cache.capacity)                 # (a piece never exceeds the cache; the results do not depend on it)
+    pool = nn.RequestPool(cache, padded, lengths, budgets, chunk, pad_token_id=pad_token_id, max_positions=positions)
+    eos = None if eos_token_id is None else int(eos_token_id)
+    sampler = None if temperature is None else (temperature, top_k, top_p)
+    stats = {"steps": 0, "requests": n, "slots": int(slots), "chunk": chunk}
+
+    def done():
+        # the poll: one word read every `poll` steps, and at the step count no schedule exceeds (every request alone in turn)
+        if stats["steps"] % poll and stats["steps"] < pool.max_steps:
+            return False
+        finished = pool.finished()
+        assert finished == n or stats["steps"] < pool.max_steps, "serve: %d requests unfinished after the %d steps that every schedule ends within" % (
+            n - finished, pool.max_steps)
+        return finished == n
+
+    with light.no_grad():
+        pool.admit(eos)
+        serve_step(model, pool, sampler, eos)
+        stats["steps"] = 1
+        if graph is None:
+            while not done():
+                serve_step(model, pool, sampler, eos)
+                stats["steps"] += 1
+        elif not done():
+            with graph.capture():
+                serve_step(model, pool, sampler, eos)               # recorded, not run
+            while True:
+                graph.replay()
+                stats["steps"] += 1
+                if done():
+                    break
+    return (pool.out, pool.out_len), stats
+
+
 if __name__ == "__main__":
     cpu = "--cpu" in sys.argv
+    if "--serve" in sys.argv:
+        option = lambda name, kind, default: kind(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default     # noqa: E731
+        n_requests, n_slots, piece = option("--serve", int, 16), option("--slots", int, 4), option("--chunk", int, 16)
+        np.random.seed(0)
+        lm = BertForMaskedLM(**dict(TINY, causal=True)).eval()
+        if not cpu:
+            lm.map_parameters(lambda t: t.hip())
+        requests = [np.random.randint(0, TINY["vocab_size"], np.random.randint(4, 48)) for _ in range(n_requests)]
+        new = [int(x) for x in np.random.randint(4, 32, n_requests)]
+        recorded = None
+        if "--graph" in sys.argv and not cpu:
+            from lightgrad_amd.autograd.hip import HipGraph
+            recorded = HipGraph()
+        sampling = {}
+        if "--sample" in sys.argv:
+            sampling = dict(temperature=option("--temperature", float, 1.0), top_k=option("--top-k", int, 0), top_p=option("--top-p", float, 1.0))
+            light.manual_seed(option("--seed", int, 0))
+        t0 = time.perf_counter()
+        (tokens, counts), info = serve(lm, requests, new, slots=n_slots, chunk=piece, eos_token_id=option("--eos", int, None), graph=recorded, **sampling)
+        tokens, counts = tokens.numpy(), counts.numpy()             # the first read of anything but the poll word
+        seconds = time.perf_counter() - t0
+        print("%d requests (prompts of %d .. %d tokens, budgets of %d .. %d) through %d slots in pieces of %d: %d steps, %d tokens in %.1f ms (%s)" % (
+            n_requests, min(map(len, requests)), max(map(len, requests)), min(new), max(new), n_slots, info["chunk"], info["steps"], int(counts.sum()),
+            1e3 * seconds, "step captured once, %d kernels" % recorded.kernel_count() if recorded else "eager steps"))
+        for r in range(min(n_requests, 8)):
+            print("request %d: %s" % (r, " ".join(str(i) for i in tokens[r, :counts[r]])))
+        sys.exit(0)
     if "--generate" in sys.argv:
         n_new = int(sys.argv[sys.argv.index("--generate") + 1])
         batch = int(sys.argv[sys.argv.index("--batch") + 1]) if "--batch" in sys.argv else 2

@@ -693,6 +693,21 @@ int lg_attention_extend_rows_f32(const float* q, int64_t ldq, int64_t sbq, const
                                  const int32_t* pos,                 /* `batch` words in device memory: the position of each row's new token 0 */
                                  float* o, int64_t ldo, int64_t sbo, float* p, int64_t batch, int64_t heads, int64_t m, int64_t capacity,
                                  int64_t D, float scale, const float* mask, int64_t sbm);
+/* lg_attention_extend_counts_f32: the `_rows` entry with `count`, `batch` contiguous int32 words in device memory.  Batch element b
+ * has n = count[b] real new tokens among the m rows it is given; with t = pos[b]:
+ *   - n < 0, n > m, t < 0 or t + n > capacity raises the status flag, nothing is written for that element, the others are
+ *     computed; n = 0 is legal for any 0 <= t <= capacity, and t + m > capacity is no error when t + n fits;
+ *   - query rows 0 .. n - 1 (context, p, cache rows t .. t + n - 1) are bit for bit what lg_attention_extend_rows_f32 gives for
+ *     that element alone with m = n; no other cache row is written (NaN there stays NaN);
+ *   - rows i >= n of o and of p (if given) are +0.0: what the launch returns is fully determined.  A workgroup whose 32 query rows
+ *     start at or beyond n clears them and returns: no load, no MFMA.
+ * Host refusals as for the `_rows` entry, then: count NULL or not 4-byte aligned, count overlapping a cache, count overlapping pos. */
+int lg_attention_extend_counts_f32(const float* q, int64_t ldq, int64_t sbq, const float* k_new, int64_t ldk, int64_t sbk,
+                                   const float* v_new, int64_t ldv, int64_t sbv, float* k_cache, float* v_cache, int64_t ldc, int64_t sbc,
+                                   const int32_t* pos,               /* `batch` words: the position of each row's new token 0 */
+                                   const int32_t* count,             /* `batch` words: the real new tokens of each row, 0 .. m */
+                                   float* o, int64_t ldo, int64_t sbo, float* p, int64_t batch, int64_t heads, int64_t m, int64_t capacity,
+                                   int64_t D, float scale, const float* mask, int64_t sbm);
 /* The per-row bookkeeping of one decode step in one launch, one thread per row, any batch >= 1.  For each row r with
  * done[r] == 0: p = pos[r] + 1; if p < 0 or p >= columns the status flag is raised (LG_EINDEX at the next lg_sync /
  * lg_memcpy_d2h) and the row is left untouched; otherwise pos[r] = p, token[r] = nxt[r * nxt_pitch], out_ids[r * out_pitch + p] =
@@ -704,6 +719,29 @@ int lg_decode_commit_i32(const int32_t* nxt, int64_t nxt_pitch,      /* the step
                          int32_t* out_ids, int64_t out_pitch, int64_t columns,   /* (batch, columns), row pitch in elements */
                          int32_t* pos, int32_t* done,                /* (batch) each */
                          int64_t batch, int32_t eos_id);             /* eos_id < 0: none */
+/* The slot bookkeeping of one step of continuous batching in one launch (csrc/serve.hip): one workgroup, one thread per cache
+ * slot, 1 <= slots <= 1024.  The definition is the sequential loop of `CpuTensor.serve_commit` (autograd/cpu/ops.py), for slot
+ * s = 0 .. slots - 1 in this order: (1) r = req[s]; if r >= 0, t = pos[s] + count[s]; with t < prompt_len[r] the slot takes the next
+ * n = min(m, prompt_len[r] - t) tokens of its prompt, otherwise nxt[s] becomes out[r, out_len[r]++] and - eos_id, or the budget
+ * used up - finishes the request (queue[1] += 1, the slot is free) or is the slot's one token (n = 1).  (2) A free slot takes
+ * request queue[0]++ while that is < N: t = 0, the first n = min(m, prompt_len[r]) tokens of its prompt.  (3) Otherwise n = 0,
+ * t = 0.  (4) req[s] = r, pos[s] = t, count[s] = n, ids[s] = the n tokens then 0, position_ids[s] = t .. t + n - 1 then 0,
+ * last[s] = s * m + max(n - 1, 0).  The kernel decides the slots in parallel and takes the admission order from an exclusive
+ * scan over the free slots: the result equals the loop's, a slot freed in a launch is admitted to in the same launch.
+ * A slot that would leave its bounds (t + n > capacity, a token beyond column G of out, r >= N, t < 0, prompt tokens beyond column
+ * P) raises the status flag - LG_EINDEX at the next lg_sync / lg_memcpy_d2h -, gets count[s] = 0 and nothing else of the slot is
+ * written.  Refused (LG_EINVAL): sizes outside their ranges, a NULL or misaligned operand, prompt_pitch < P, out_pitch < G,
+ * nxt_pitch < 1, any two operands that overlap.  ids and position_ids are dense (slots, m). */
+int lg_serve_commit_i32(const int32_t* nxt, int64_t nxt_pitch,       /* the tokens just drawn, slot s at nxt + s * nxt_pitch */
+                        const int32_t* prompts, int64_t prompt_pitch, int64_t P,   /* (N, P) right-padded ids, row pitch in elements */
+                        const int32_t* prompt_len, const int32_t* budget,          /* (N) each */
+                        int32_t* out, int64_t out_pitch, int64_t G,  /* (N, G) generated tokens, row pitch in elements */
+                        int32_t* out_len,                            /* (N) */
+                        int32_t* queue, int64_t N,                   /* {next request to admit, requests finished} */
+                        int32_t* req, int32_t* pos, int32_t* count,  /* (slots) each */
+                        int32_t* ids, int32_t* position_ids,         /* (slots, m) dense each */
+                        int32_t* last,                               /* (slots) */
+                        int64_t slots, int64_t m, int64_t capacity, int32_t eos_id);   /* eos_id < 0: none */
 
 /* ---- two independent products in one launch ----------------------------------------------------------
  * lg_gemm_pair_begin(); <product 1>; <product 2>; lg_gemm_pair_end();   with products issued through

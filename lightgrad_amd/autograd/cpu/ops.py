@@ -445,6 +445,96 @@ def _check_decode_commit(nxt, token, out_ids, pos, done, eos):
 CpuTensor.decode_commit = _decode_commit
 
 
+def _serve_commit(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last, capacity, eos=None):
+    """ nxt.serve_commit(prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last, capacity,
+    eos=None): the slot bookkeeping of one step of continuous batching, in place and outside the tape - the definition of the op,
+    written as the loop it is.  All int32: prompts (N, P) right-padded ids, prompt_len (N,), budget (N,) new tokens per request
+    (>= 1), out (N, G) generated tokens, out_len (N,), queue (2,) = {next request to admit, requests finished}, req (b,) the
+    request each slot holds (-1: free), pos (b,) the cache's positions, count (b,) the real new tokens of the step, ids and
+    position_ids (b, m) the step's inputs, last (b,) the row of the flattened (b * m) hidden rows that goes to the head; nxt (b,) or
+    (b, 1) the tokens just drawn.  For slot s = 0 .. b - 1, in this order:
+      1. r = req[s].  If r >= 0: t = pos[s] + count[s] (the step's tokens are in the cache now).  t < prompt_len[r]: the slot goes
+         on prefilling, n = min(m, prompt_len[r] - t) tokens prompts[r, t:t + n], and nxt[s] is ignored.  Otherwise nxt[s] is the
+         request's next token: out[r, out_len[r]] = nxt[s], out_len[r] += 1; if it is `eos` (an id >= 0) or the budget is used
+         up, queue[1] += 1 and the slot is free (r = -1: the last token is fed to nobody), else n = 1 and the token is nxt[s].
+      2. A free slot while queue[0] < N: r = queue[0], queue[0] += 1, t = 0, n = min(m, prompt_len[r]) tokens prompts[r, :n].
+      3. Still free: n = 0, t = 0.
+      4. req[s] = r, pos[s] = t, count[s] = n, ids[s] = the n tokens then 0, position_ids[s] = t .. t + n - 1 then 0,
+         last[s] = s * m + max(n - 1, 0).
+    A slot that would leave its bounds - t + n > capacity, a token beyond the columns of out, a request id >= N, t < 0, prompt
+    tokens beyond the columns of prompts - gets count[s] = 0 and nothing else of the slot (req, pos, ids, position_ids, last) is
+    written; the call raises IndexError after every other slot has been committed, as the device flag of the HipTensor op does at
+    its next synchronisation.  (What step 1 wrote to out, out_len and queue for that slot before step 4 found t + n > capacity
+    stays written.) """
+    b, m, N = _check_serve_commit(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last, capacity, eos)
+    arrays = [t.data for t in (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last)]
+    assert not any(np.shares_memory(x, y) for i, x in enumerate(arrays) for y in arrays[i + 1:]), "serve_commit: two operands overlap"
+    new, P, G = nxt.data.reshape(b), prompts.shape[1], out.shape[1]
+    eos, capacity = (-1 if eos is None else int(eos)), int(capacity)
+    bad = []
+    for s in range(b):
+        r, t, n, row, fault = int(req.data[s]), 0, 0, (), False
+        if r >= 0:
+            t = int(pos.data[s]) + int(count.data[s])
+            if r >= N or t < 0 or t > capacity:
+                fault = True
+            elif t < int(prompt_len.data[r]):
+                n = np.minimum(m, int(prompt_len.data[r]) - t).item()
+                fault = t + n > P
+                row = () if fault else prompts.data[r, t:t + n]
+            else:
+                g = int(out_len.data[r])
+                if g < 0 or g >= G:
+                    fault = True
+                else:
+                    out.data[r, g], out_len.data[r] = new[s], g + 1
+                    if (eos >= 0 and int(new[s]) == eos) or g + 1 == int(budget.data[r]):
+                        queue.data[1] += 1
+                        r = -1
+                    else:
+                        n, row = 1, new[s:s + 1]
+        if not fault and r < 0:
+            t = 0
+            if 0 <= int(queue.data[0]) < N:
+                r = int(queue.data[0])
+                queue.data[0] += 1
+                n = np.minimum(m, int(prompt_len.data[r])).item()
+                fault = n < 0 or n > P
+                row = () if fault else prompts.data[r, :n]
+        if fault or t + n > capacity:
+            count.data[s] = 0
+            bad.append(s)
+            continue
+        req.data[s], pos.data[s], count.data[s] = r, t, n
+        ids.data[s, :n], ids.data[s, n:] = row, 0
+        position_ids.data[s, :n], position_ids.data[s, n:] = t + np.arange(n), 0
+        last.data[s] = s * m + (n - 1 if n > 0 else 0)
+    if bad:
+        raise IndexError("serve_commit: slot %d (of %d that did) would leave the cache, its prompt or its row of out" % (bad[0], len(bad)))
+
+
+def _check_serve_commit(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last, capacity, eos):
+    """the operand shapes and dtypes of `serve_commit`, on any backend; returns (slots b, tokens per slot m, requests N)"""
+    b = req.shape[0] if len(req.shape) == 1 else -1
+    m = ids.shape[1] if len(ids.shape) == 2 else -1
+    N = prompts.shape[0] if len(prompts.shape) == 2 else -1
+    i32 = np.dtype(np.int32)
+    shapes = [tuple(t.shape) for t in (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last)]
+    assert 1 <= b <= 1024 and m >= 1 and N >= 1 and prompts.shape[1] >= 1 and shapes[0] in ((b,), (b, 1)) and shapes[2] == shapes[3] == shapes[5] == (N,) \
+        and len(out.shape) == 2 and out.shape[0] == N and out.shape[1] >= 1 and shapes[6] == (2,) and shapes[8] == shapes[9] == shapes[12] == (b,) \
+        and shapes[10] == shapes[11] == (b, m), \
+        "serve_commit: nxt (b,) or (b, 1), prompts (N, P), prompt_len / budget / out_len (N,), out (N, G), queue (2,), req / pos / count / last (b,) " \
+        "with 1 <= b <= 1024, ids / position_ids (b, m) - got %s" % (shapes,)
+    assert all(np.dtype(t.dtype) == i32 for t in (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last)), \
+        "serve_commit: every operand is int32"
+    assert eos is None or int(eos) == eos, "serve_commit: eos is an int or None"
+    assert int(capacity) == capacity and 1 <= capacity < 2 ** 31, "serve_commit: capacity is an int >= 1"
+    return b, m, N
+
+
+CpuTensor.serve_commit = _serve_commit
+
+
 def _next_token_labels(ids, ignore_index=-100):
     """ ids.next_token_labels(ignore_index=-100): the labels of the next-token objective - `ids` shifted left by one along the last
     axis, `ignore_index` in the last column; same dtype and shape, a constant of the tape. """

@@ -442,16 +442,34 @@ def _token_rows_in_place(t, name):
     return t, (st[1] if t._shape[1] > 1 else 0), (st[0] if t._shape[0] > 1 else 0)
 
 
-def _launch_extend(name, q3, k3, v3, m, k_cache, v_cache, pos, out, heads, scale, mask, probs):
+def _token_counts(name, count, pos, b, k_cache, v_cache):
+    """the `count=` operand of the extend ops as the launch reads it: int32 (b,) next to a `pos` of shape (b,), dense, apart
+    from the caches and from pos"""
+    assert isinstance(count, HipTensor) and count._dtype == _I32 and count._shape == (b,) and pos._shape == (b,), \
+        "%s: count is an int32 HipTensor of shape (batch,) = (%d,) and goes with a pos of that shape, got count %s %s and pos %s" % (
+            name, b, getattr(count, "_dtype", type(count).__name__), getattr(count, "_shape", ""), pos._shape)
+    for other in (k_cache, v_cache, pos):
+        assert not _shares_bytes(count, other), "%s: count overlaps a cache or pos" % name
+    return count if b == 1 or count._strides[0] == 1 else count.contiguous()
+
+
+def _launch_extend(name, q3, k3, v3, m, k_cache, v_cache, pos, out, heads, scale, mask, probs, count=None):
     """q3, k3, v3: (address, row pitch, batch pitch); out: (b, m, width) dense.  Returns the probabilities (b, heads, m, capacity) or None"""
     b, capacity, width = k_cache._shape
+    if count is not None:
+        count = _token_counts(name, count, pos, b, k_cache, v_cache)
     mask3 = _key_mask(mask, b, capacity, name)
     p = HipTensor.empty((b, heads, m, capacity), requires_grad=False) if probs else None
     flush_lazy_readers(k_cache)
     flush_lazy_readers(v_cache)
-    pos, per_row = _positions(pos, b)
-    entry = _l.lib().lg_attention_extend_rows_f32 if per_row else _l.lib().lg_attention_extend_f32
-    _l.check(entry(*q3, *k3, *v3, k_cache.ptr, v_cache.ptr, k_cache._strides[1], k_cache._strides[0], pos.ptr,
+    if count is not None:
+        # a token count per sequence next to its position: the counts entry, at any batch
+        pos = pos if b == 1 or pos._strides[0] == 1 else pos.contiguous()
+        entry, words = _l.lib().lg_attention_extend_counts_f32, (pos.ptr, count.ptr)
+    else:
+        pos, per_row = _positions(pos, b)
+        entry, words = (_l.lib().lg_attention_extend_rows_f32 if per_row else _l.lib().lg_attention_extend_f32), (pos.ptr,)
+    _l.check(entry(*q3, *k3, *v3, k_cache.ptr, v_cache.ptr, k_cache._strides[1], k_cache._strides[0], *words,
                    out.ptr, width, m * width, p.ptr if probs else None, b, heads, m, capacity, width // heads, float(scale), mask3[1], mask3[2]))
     return p
 
@@ -464,7 +482,7 @@ def extend_attention_supported(q, heads, capacity):
             and bool(_l.lib().lg_attention_extend_supported(sh[1], capacity, sh[2] // heads)))
 
 
-def extend_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False):
+def extend_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False, count=None):
     """ attention of m NEW tokens per sequence against a filled key / value cache, one launch (lg_attention_extend_f32): with t =
     the int32 word `pos` holds ON THE DEVICE (`pos` of shape (b,): a position per sequence, t = pos[r] for sequence r, everything
     below per sequence - lg_attention_extend_rows_f32; a sequence with t + m beyond the cache writes nothing, the others are computed), rows i of k_new / v_new become rows t + i of the caches (b, capacity, heads * d) and
@@ -472,7 +490,11 @@ def extend_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0,
     forward computes for queries t .. t + m - 1.  q, k_new, v_new: (b, m, width); slices of one (b, m, 3 * width) projection
     buffer are read in place.  mask: float32 (b, capacity) or (1, capacity) over the cache's rows, None for none.  probs=True:
     `.attention_probs` (b, heads, m, capacity), exact zeros beyond column t + i of row i.  t < 0 or t + m > capacity writes
-    nothing and raises IndexError at the next synchronisation.  An inference op: the result is outside the tape. """
+    nothing and raises IndexError at the next synchronisation.  An inference op: the result is outside the tape.
+    count= (an int32 HipTensor (b,), with a per-sequence `pos`): sequence r has n = count[r] real tokens among its m rows - one
+    launch of lg_attention_extend_counts_f32.  Its rows < n are those of the call on it alone with m = n, only cache rows
+    t .. t + n - 1 are written, only t + n has to fit the cache (n = 0: an idle sequence), and rows >= n of the result and of
+    `.attention_probs` are +0.0.  Without count= the call is the one it was. """
     name = "extend_attention"
     _inference_only(name, q, k_new, v_new)
     _require_f32(q, k_new, v_new)
@@ -482,16 +504,17 @@ def extend_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0,
     m = q._shape[1]
     (q, ldq, sbq), (k_new, ldk, sbk), (v_new, ldv, sbv) = (_token_rows_in_place(t, name) for t in (q, k_new, v_new))
     out = HipTensor.empty(q._shape, requires_grad=False)
-    p = _launch_extend(name, (q.ptr, ldq, sbq), (k_new.ptr, ldk, sbk), (v_new.ptr, ldv, sbv), m, k_cache, v_cache, pos, out, heads, scale, mask, probs)
+    p = _launch_extend(name, (q.ptr, ldq, sbq), (k_new.ptr, ldk, sbk), (v_new.ptr, ldv, sbv), m, k_cache, v_cache, pos, out, heads, scale, mask, probs,
+                       **({} if count is None else {"count": count}))
     if probs:
         out.attention_probs = p
     return out
 
 
-def self_attention_extend(x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False):
+def self_attention_extend(x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False, count=None):
     """ the one-node form of an append's attention: the three projections of the m new tokens in ONE launch (lg_gemm_multi3_f32,
     as in `self_attention`) into a (b, m, 3 * width) buffer that the extend launch reads in place - two launches per layer.
-    x: (b, m, hidden); everything else as for `extend_attention`. """
+    x: (b, m, hidden); everything else as for `extend_attention`, `count=` included (the projections take all b * m rows). """
     name = "self_attention_extend"
     _inference_only(name, x, wq, bq, wk, bk, wv, bv)
     _require_f32(x, wq, bq, wk, bk, wv, bv)
@@ -510,7 +533,7 @@ def self_attention_extend(x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, head
     out = HipTensor.empty((b, m, width), requires_grad=False)
     ld, sb = 3 * width, m * 3 * width
     p = _launch_extend(name, (base, ld, sb), (base + 4 * width, ld, sb), (base + 8 * width, ld, sb), m, k_cache, v_cache, pos, out, heads, scale,
-                       mask, probs)
+                       mask, probs, **({} if count is None else {"count": count}))
     if probs:
         out.attention_probs = p
     return out
@@ -559,3 +582,43 @@ def decode_commit(nxt, token, out_ids, pos, done, eos=None):
 
 
 HipTensor.decode_commit = decode_commit
+
+
+""" The slot bookkeeping of a serving step in one launch (csrc/serve.hip) """
+
+
+def serve_commit(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last, capacity, eos=None):
+    """ nxt.serve_commit(prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last, capacity,
+    eos=None): what `CpuTensor.serve_commit` defines - a finished slot freed, the next waiting request admitted to it, the next
+    piece of a prompt or the token just drawn made the step's input - in ONE launch (lg_serve_commit_i32), in place and outside the
+    tape.  Int32 HipTensors that do not overlap; prompts and out may have any row pitch, everything that is written per slot is
+    dense.  A slot that would leave its bounds gets count 0, keeps its other bytes and raises IndexError at the next
+    synchronisation.  No host read: a captured step replays it as it stands. """
+    from ..cpu.ops import _check_serve_commit
+    name = "serve_commit"
+    operands = (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last)
+    assert all(isinstance(t, HipTensor) for t in operands), "%s: every operand is a HipTensor" % name
+    b, m, N = _check_serve_commit(*operands, capacity, eos)
+    if b > 1 and nxt._strides[0] < 1:
+        nxt = nxt.contiguous()
+    # what is only read may be copied once into a layout the launch addresses
+    if (prompts._shape[1] > 1 and prompts._strides[1] != 1) or (N > 1 and prompts._strides[0] < prompts._shape[1]):
+        prompts = prompts.contiguous()
+    prompt_len, budget = (t if N == 1 or t._strides[0] == 1 else t.contiguous() for t in (prompt_len, budget))
+    # the launch writes these where they lie: a layout it cannot address is an error, never a copy
+    assert all(t.is_contiguous() for t in (out_len, queue, req, pos, count, last, ids, position_ids)) and \
+        (out._shape[1] == 1 or out._strides[1] == 1) and (N == 1 or out._strides[0] >= out._shape[1]), \
+        "%s: out_len, queue, req, pos, count, last, ids and position_ids must be dense and the rows of out contiguous" % name
+    operands = (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last)
+    for i, x in enumerate(operands):
+        for y in operands[i + 1:]:
+            assert not _shares_bytes(x, y), "%s: two operands overlap" % name
+    for x in operands[4:]:
+        flush_lazy_readers(x)
+    P, G = prompts._shape[1], out._shape[1]
+    _l.check(_l.lib().lg_serve_commit_i32(nxt.ptr, nxt._strides[0] if b > 1 else 1, prompts.ptr, prompts._strides[0] if N > 1 else P, P, prompt_len.ptr,
+                                          budget.ptr, out.ptr, out._strides[0] if N > 1 else G, G, out_len.ptr, queue.ptr, N, req.ptr, pos.ptr,
+                                          count.ptr, ids.ptr, position_ids.ptr, last.ptr, b, m, int(capacity), -1 if eos is None else int(eos)))
+
+
+HipTensor.serve_commit = serve_commit

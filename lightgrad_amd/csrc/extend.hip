@@ -22,6 +22,10 @@
 // of the MFMAs, wave w on keys [32 w, 32 w + 32) of a chunk for the scores, the three-pass softmax with 8 threads per row,
 // context tiles split over the waves with the partial sums in registers across the chunks and ONE fold through LDS in wave
 // order: the same bits every run, and a (batch, head, block) triple's bits depend on its own data and t only.
+// lg_attention_extend_counts_f32 is the per-element kernel once more with a word count[b] per batch element (ExtendArgs::count, NULL
+// for the other two entries): of the m rows given, the first n = count[b] are tokens.  The element is computed as by a launch of
+// its own with m = n (keys = t + n, Kend and the seam from n, cache rows t .. t + n - 1 written), only t + n must fit the capacity,
+// rows >= n of the context and of p become +0.0, and a block that starts at q0 >= n returns after clearing its rows.
 // LDS at D = 64, capacity = 512: 32 * 68 + 32 * 516 + 128 * 72 + 3072 + 512 floats = 126 KB - one workgroup per CU.
 #include "attention_common.h"
 
@@ -38,6 +42,7 @@ struct ExtendArgs {
     int64_t ldc, sbc;
     const int32_t* pos;                  // batch element b reads pos[b * pos_pitch]: pitch 0 = one word for the batch, 1 = a word per row
     int64_t pos_pitch;
+    const int32_t* count;                // NULL: each of the m rows is a new token; else batch element b has count[b] real ones (0 .. m)
     float* o;                            // context, addressed like q
     int64_t ldo, sbo;
     float* p;                            // NULL, or (batch, heads, m, capacity) dense
@@ -80,7 +85,10 @@ __global__ void __launch_bounds__(256) attn_extend(const ExtendArgs a) {
     constexpr int NB = 32 * Q4 / 256, NA = kExtChunk * Q4 / 256;
     const int t = a.pos[int64_t(blockIdx.z) * a.pos_pitch];       // uniform over the workgroup either way: a scalar load
     const int tid = threadIdx.x;
-    if (t < 0 || t > C - m) {
+    // the element's real new tokens: each of the launch's m rows, or - lg_attention_extend_counts_f32 - the first count[b] of them.
+    // From here on the element is computed as by a launch of its own with m = real; `m` stays the pitch of `p` and the rows to clear
+    const int real = a.count ? a.count[blockIdx.z] : m;
+    if (t < 0 || real < 0 || real > m || t > C - real) {
         // a bounds check, never a fault: nothing is written for this batch element (the others of a per-row launch are computed
         // as usual), the next synchronising call reports LG_EINDEX
         if (tid == 0) __hip_atomic_fetch_or(a.status, LG_STATUS_BAD_INDEX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -93,8 +101,26 @@ __global__ void __launch_bounds__(256) attn_extend(const ExtendArgs a) {
     float* Bias = Red + 3 * 1024;         // what key j adds to every score of its column
     const int lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     const int q0 = blockIdx.x * 32, head = blockIdx.y, b = blockIdx.z;
-    const int qrows = m - q0 < 32 ? m - q0 : 32;                      // rows of this block that exist
-    const int keys = t + m;                                           // keys that exist in this launch
+    if (real < m) {
+        // rows of the block that are given but hold no token: +0.0 in the context and in p, so that what the launch returns is
+        // determined.  A block without a real row is done then: uniform over the workgroup, before any load, MFMA or barrier
+        const int lo = q0 > real ? q0 : real, hi = q0 + 32 < m ? q0 + 32 : m;
+        const af32x4 zero{0.f, 0.f, 0.f, 0.f};
+        float* oz = a.o + int64_t(b) * a.sbo + head * D;
+        for (int f = tid; f < (hi - lo) * Q4; f += 256) *reinterpret_cast<af32x4*>(oz + int64_t(lo + f / Q4) * a.ldo + (f % Q4) * 4) = zero;
+        if (a.p != nullptr && hi > lo) {
+            float* pz = a.p + ((int64_t(b) * a.heads + head) * m + lo) * C;       // rows lo .. hi - 1 of p are one dense run of floats
+            const int total = (hi - lo) * C;
+            const int ahead = int((4 - ((reinterpret_cast<uintptr_t>(pz) >> 2) & 3)) & 3);       // floats in front of the first aligned float4
+            const int lead = ahead < total ? ahead : total, quads = (total - lead) / 4;
+            for (int f = tid; f < lead; f += 256) pz[f] = 0.f;
+            for (int f = tid; f < quads; f += 256) *reinterpret_cast<af32x4*>(pz + lead + 4 * f) = zero;
+            for (int f = lead + 4 * quads + tid; f < total; f += 256) pz[f] = 0.f;
+        }
+        if (q0 >= real) return;
+    }
+    const int qrows = real - q0 < 32 ? real - q0 : 32;                // rows of this block that exist
+    const int keys = t + real;                                        // keys that exist in this launch
     const int Kend = round32(t + q0 + qrows);                         // the key columns the chunk loops cover (<= Cp)
     const float* kc = a.k_cache + int64_t(b) * a.sbc + head * D;
     const float* vc = a.v_cache + int64_t(b) * a.sbc + head * D;
@@ -107,7 +133,7 @@ __global__ void __launch_bounds__(256) attn_extend(const ExtendArgs a) {
         load_rows<D, NB>(rq, a.q + int64_t(b) * a.sbq + int64_t(q0) * a.ldq + head * D, a.ldq, qrows);
         load_rows<D, NB>(rk, kn + int64_t(q0) * a.ldk, a.ldk, qrows);
         load_rows<D, NB>(rv, vn + int64_t(q0) * a.ldv, a.ldv, qrows);
-        seam_load<D, NA>(rc, kc, a.ldc, kn, a.ldk, 0, t, m);
+        seam_load<D, NA>(rc, kc, a.ldc, kn, a.ldk, 0, t, real);
         store_rows_padded<D, NB>(rq, Qs, PQ, qrows, 32);
         // the block's own new rows become rows t + q0 .. of the caches, bit for bit; nothing in this launch reads them there
         float* kd = a.k_cache + int64_t(b) * a.sbc + int64_t(t + q0) * a.ldc + head * D;
@@ -130,8 +156,8 @@ __global__ void __launch_bounds__(256) attn_extend(const ExtendArgs a) {
     for (int c0 = 0; c0 < Kend; c0 += kExtChunk) {
         seam_store<D, NA>(rc, Buf, PQ, c0, keys, Kend);
         __syncthreads();
-        if (c0 + kExtChunk < Kend) seam_load<D, NA>(rc, kc, a.ldc, kn, a.ldk, c0 + kExtChunk, t, m);
-        else                       seam_load<D, NA>(rc, vc, a.ldc, vn, a.ldv, 0, t, m);      // the first chunk of V flies behind the softmax
+        if (c0 + kExtChunk < Kend) seam_load<D, NA>(rc, kc, a.ldc, kn, a.ldk, c0 + kExtChunk, t, real);
+        else                       seam_load<D, NA>(rc, vc, a.ldc, vn, a.ldv, 0, t, real);      // the first chunk of V flies behind the softmax
         const int rows = Kend - c0 < kExtChunk ? Kend - c0 : kExtChunk;
         if (32 * wave < rows) {
             af32x16 acc = zero16();
@@ -213,7 +239,7 @@ __global__ void __launch_bounds__(256) attn_extend(const ExtendArgs a) {
     for (int c0 = 0; c0 < Kend; c0 += kExtChunk) {
         seam_store<D, NA>(rc, Buf, PV, c0, keys, Kend);
         __syncthreads();                                              // (the first one also publishes the probabilities in LDS)
-        if (c0 + kExtChunk < Kend) seam_load<D, NA>(rc, vc, a.ldc, vn, a.ldv, c0 + kExtChunk, t, m);
+        if (c0 + kExtChunk < Kend) seam_load<D, NA>(rc, vc, a.ldc, vn, a.ldv, c0 + kExtChunk, t, real);
         const int rows = Kend - c0 < kExtChunk ? Kend - c0 : kExtChunk, kspan = rows / KP;
         wave_mma<true, false>(acc, Ps + c0 + kp * kspan, PP, Buf + kp * kspan * PV + 32 * n, PV, kspan, r, h);
         __syncthreads();
@@ -269,8 +295,9 @@ extern "C" int lg_attention_extend_supported(int64_t m, int64_t capacity, int64_
     return (D == 32 || D == 64) && m >= 1 && m <= capacity && capacity <= kExtMaxKeys;
 }
 
-// both entries: `pos_pitch` words between the positions of neighbouring batch elements (0: one word for the batch)
-static int extend_entry(const char* name, int64_t pos_pitch, const float* q, int64_t ldq, int64_t sbq, const float* k_new, int64_t ldk, int64_t sbk,
+// every entry: `pos_pitch` words between the positions of neighbouring batch elements (0: one word for the batch); `counts`: the
+// entry takes a word per batch element in `count` (NULL for the others)
+static int extend_entry(const char* name, int64_t pos_pitch, bool counts, const int32_t* count, const float* q, int64_t ldq, int64_t sbq, const float* k_new, int64_t ldk, int64_t sbk,
                         const float* v_new, int64_t ldv, int64_t sbv, float* k_cache, float* v_cache, int64_t ldc, int64_t sbc,
                         const int32_t* pos, float* o, int64_t ldo, int64_t sbo, float* p, int64_t batch, int64_t heads, int64_t m,
                         int64_t capacity, int64_t D, float scale, const float* mask, int64_t sbm) {
@@ -291,6 +318,12 @@ static int extend_entry(const char* name, int64_t pos_pitch, const float* q, int
     LG_ARG(!positions_overlap(pos, pos_pitch ? batch : 1, k_cache, ldc, sbc, capacity, batch, w) &&
                !positions_overlap(pos, pos_pitch ? batch : 1, v_cache, ldc, sbc, capacity, batch, w),
            "%s: pos overlaps a cache: the launch writes the caches while other workgroups read their positions", name);
+    if (counts) {
+        LG_ARG(count && (reinterpret_cast<uintptr_t>(count) & 3u) == 0, "%s: count must be non-NULL and 4-byte aligned", name);
+        LG_ARG(!positions_overlap(count, batch, k_cache, ldc, sbc, capacity, batch, w) && !positions_overlap(count, batch, v_cache, ldc, sbc, capacity, batch, w),
+               "%s: count overlaps a cache: the launch writes the caches while other workgroups read their counts", name);
+        LG_ARG(!(count < pos + (pos_pitch ? batch : 1) && pos < count + batch), "%s: count overlaps pos", name);
+    }
     {
         const int64_t rows[3] = {batch, m, w}, row_strides[3] = {sbo, ldo, 1};
         int rc = adam_epilogue_check_strided(o, 4, 3, rows, row_strides);
@@ -302,7 +335,7 @@ static int extend_entry(const char* name, int64_t pos_pitch, const float* q, int
         if (rc != LG_OK) return rc;
         if (p) { rc = adam_epilogue_check_write(p, batch * heads * m * capacity * 4); if (rc != LG_OK) return rc; }
     }
-    const ExtendArgs a{q, k_new, v_new, ldq, sbq, ldk, sbk, ldv, sbv, k_cache, v_cache, ldc, sbc, pos, pos_pitch, o, ldo, sbo, p,
+    const ExtendArgs a{q, k_new, v_new, ldq, sbq, ldk, sbk, ldv, sbv, k_cache, v_cache, ldc, sbc, pos, pos_pitch, counts ? count : nullptr, o, ldo, sbo, p,
                        int(heads), int(capacity), int(m), scale, mask, sbm, rt().status_dev};
     const dim3 grid{unsigned((m + 31) / 32), unsigned(heads), unsigned(batch)};
     const int rc = D == 64 ? launch_extend<64>(a, grid) : launch_extend<32>(a, grid);
@@ -314,7 +347,7 @@ extern "C" int lg_attention_extend_f32(const float* q, int64_t ldq, int64_t sbq,
                                        int64_t sbc, const int32_t* pos, float* o, int64_t ldo, int64_t sbo, float* p, int64_t batch,
                                        int64_t heads, int64_t m, int64_t capacity, int64_t D, float scale, const float* mask, int64_t sbm) {
     LG_REQUIRE_INIT();
-    const int rc = extend_entry("lg_attention_extend_f32", 0, q, ldq, sbq, k_new, ldk, sbk, v_new, ldv, sbv, k_cache, v_cache, ldc, sbc, pos, o, ldo, sbo,
+    const int rc = extend_entry("lg_attention_extend_f32", 0, false, nullptr, q, ldq, sbq, k_new, ldk, sbk, v_new, ldv, sbv, k_cache, v_cache, ldc, sbc, pos, o, ldo, sbo,
                         p, batch, heads, m, capacity, D, scale, mask, sbm);
     if (rc != LG_OK || batch == 0) return rc;
     LG_CHECK_LAUNCH();
@@ -327,8 +360,23 @@ extern "C" int lg_attention_extend_rows_f32(const float* q, int64_t ldq, int64_t
                                             int64_t sbc, const int32_t* pos, float* o, int64_t ldo, int64_t sbo, float* p, int64_t batch,
                                             int64_t heads, int64_t m, int64_t capacity, int64_t D, float scale, const float* mask, int64_t sbm) {
     LG_REQUIRE_INIT();
-    const int rc = extend_entry("lg_attention_extend_rows_f32", 1, q, ldq, sbq, k_new, ldk, sbk, v_new, ldv, sbv, k_cache, v_cache, ldc, sbc, pos, o, ldo,
+    const int rc = extend_entry("lg_attention_extend_rows_f32", 1, false, nullptr, q, ldq, sbq, k_new, ldk, sbk, v_new, ldv, sbv, k_cache, v_cache, ldc, sbc, pos, o, ldo,
                         sbo, p, batch, heads, m, capacity, D, scale, mask, sbm);
+    if (rc != LG_OK || batch == 0) return rc;
+    LG_CHECK_LAUNCH();
+    return LG_OK;
+}
+
+// the `_rows` entry with a token count per batch element: count holds `batch` contiguous words, element b has n = count[b] real new
+// tokens among the m rows it is given and is computed as by the `_rows` entry on it alone with m = n; rows >= n of o and p are +0.0
+extern "C" int lg_attention_extend_counts_f32(const float* q, int64_t ldq, int64_t sbq, const float* k_new, int64_t ldk, int64_t sbk,
+                                              const float* v_new, int64_t ldv, int64_t sbv, float* k_cache, float* v_cache, int64_t ldc,
+                                              int64_t sbc, const int32_t* pos, const int32_t* count, float* o, int64_t ldo, int64_t sbo, float* p,
+                                              int64_t batch, int64_t heads, int64_t m, int64_t capacity, int64_t D, float scale, const float* mask,
+                                              int64_t sbm) {
+    LG_REQUIRE_INIT();
+    const int rc = extend_entry("lg_attention_extend_counts_f32", 1, true, count, q, ldq, sbq, k_new, ldk, sbk, v_new, ldv, sbv, k_cache, v_cache, ldc, sbc,
+                                pos, o, ldo, sbo, p, batch, heads, m, capacity, D, scale, mask, sbm);
     if (rc != LG_OK || batch == 0) return rc;
     LG_CHECK_LAUNCH();
     return LG_OK;

@@ -395,3 +395,71 @@ class KVCache(object):
             "KVCache: keys / values of shape %s / %s do not fit (%d, <= %d, %d)" % (tuple(k.shape), tuple(v.shape), self.batch, self.capacity, self.width)
         self.k[layer][:, :s] = k
         self.v[layer][:, :s] = v
+
+
+class RequestPool(object):
+    """the requests of a serving loop and the state of the cache slots that work through them (continuous batching): N prompts
+    wait in a queue, each of the cache's `batch` slots holds one request at a time, and a slot whose request has finished takes
+    the next one while the other slots go on.  Everything is an int32 tensor on the cache's backend, moved by ONE op per step,
+    `serve_commit` (the numpy backend's is the definition: autograd/cpu/ops.py) - nothing is read back:
+        prompts (N, P) right-padded, prompt_len (N,), budget (N,) new tokens per request,
+        out (N, G) the generated tokens (pre-filled with `pad_token_id`), out_len (N,),
+        queue (2,) = {next request to admit, requests finished},
+        req (b,) the request each slot holds, -1 = free; `cache.pos` (b,); count (b,) the real new tokens of the step;
+        ids, position_ids (b, chunk) the step's inputs; last (b,) the row of the flattened (b * chunk) hidden rows for the head.
+    `cache` must be per_row.  A request needs lengths[r] + budgets[r] - 1 cache rows (its last token is fed to nobody): checked
+    here, on the host, against the capacity.  State, not parameters, like the cache.  Not a class of the reference."""
+
+    def __init__(self, cache, prompts, lengths, budgets, chunk: int, pad_token_id: int = 0, max_positions=None):
+        """max_positions: the model's position embeddings, if the caller knows them - the capacity must not exceed them"""
+        assert isinstance(cache, KVCache) and cache.per_row, "RequestPool takes a cache with a position per sequence: nn.KVCache(..., per_row=True)"
+        assert max_positions is None or cache.capacity <= max_positions, \
+            "RequestPool: a cache of %d positions exceeds the model's %s position embeddings" % (cache.capacity, max_positions)
+        cls = type(cache.pos)
+        prompts = np.asarray(prompts.numpy() if hasattr(prompts, "numpy") else prompts)
+        assert prompts.ndim == 2 and prompts.shape[0] >= 1 and prompts.shape[1] >= 1 and np.issubdtype(prompts.dtype, np.integer), \
+            "RequestPool: prompts are (N, P) right-padded integer ids, got %s %s" % (prompts.dtype, prompts.shape)
+        n = prompts.shape[0]
+        lengths, budgets = np.asarray(lengths, np.int64), np.asarray(budgets, np.int64)
+        assert lengths.shape == budgets.shape == (n,) and (lengths >= 1).all() and (lengths <= prompts.shape[1]).all() and (budgets >= 1).all(), \
+            "RequestPool: %d lengths within 1 .. %d and %d budgets >= 1, one per request" % (n, prompts.shape[1], n)
+        assert int(chunk) == chunk and chunk >= 1, "RequestPool: chunk is a number of tokens >= 1"
+        assert (lengths + budgets - 1 <= cache.capacity).all(), \
+            "RequestPool: a request of %d prompt tokens and %d new ones does not fit a cache of %d positions" % (
+                int(lengths[np.argmax(lengths + budgets)]), int(budgets[np.argmax(lengths + budgets)]), cache.capacity)
+        self.cache, self.requests, self.slots, self.chunk, self.pad_token_id = cache, n, cache.batch, int(chunk), int(pad_token_id)
+        tensor = lambda a: cls.from_numpy(np.ascontiguousarray(a, np.int32), requires_grad=False)        # noqa: E731
+        self.prompts, self.prompt_len, self.budget = tensor(prompts), tensor(lengths), tensor(budgets)
+        self.out = tensor(np.full((n, int(budgets.max())), int(pad_token_id)))
+        self.out_len, self.queue = tensor(np.zeros(n)), tensor(np.zeros(2))
+        self.req, self.count, self.last = tensor(np.full(self.slots, -1)), tensor(np.zeros(self.slots)), tensor(np.zeros(self.slots))
+        self._no_tokens = tensor(np.zeros(self.slots))
+        # queue[1] as a tensor of its own that shares the word (indexing a tensor copies: the poll would be a launch and a read)
+        if isinstance(getattr(self.queue, "data", None), np.ndarray):
+            self._finished = cls.from_numpy(self.queue.data[1:2], requires_grad=False)
+        else:
+            from .autograd.hip.ops import _idx_view
+            self._finished = _idx_view(self.queue, (slice(1, 2),))
+        self.ids, self.position_ids = tensor(np.zeros((self.slots, self.chunk))), tensor(np.zeros((self.slots, self.chunk)))
+        self.max_steps = int((-(-lengths // self.chunk) + budgets).sum())          # every request alone in turn: no schedule takes longer
+        cache.reset()
+        cache.lengths = None            # the positions move on the device from here on: the host mirror is an upper bound only
+        cache.length = cache.capacity
+
+    @property
+    def pos(self):
+        return self.cache.pos
+
+    def commit(self, nxt, eos=None) -> None:
+        """one `serve_commit`: `nxt` (slots,) or (slots, 1) int32 are the tokens the step has just drawn (ignored for slots that
+        are free or prefilling)"""
+        nxt.serve_commit(self.prompts, self.prompt_len, self.budget, self.out, self.out_len, self.queue, self.req, self.cache.pos, self.count,
+                         self.ids, self.position_ids, self.last, self.cache.capacity, eos=eos)
+
+    def admit(self, eos=None) -> None:
+        """the first admissions: one commit with every slot free (what it is given as `nxt` is ignored)"""
+        self.commit(self._no_tokens, eos=eos)
+
+    def finished(self) -> int:
+        """requests finished so far: a host READ of one word, queue[1]"""
+        return int(self._finished.numpy()[0])
