@@ -705,9 +705,92 @@ def prefill_rows_in_pieces(model, cache, ids32, lengths, mask, piece):
     return last
 
 
+class NgramDrafter(object):
+    """the drafter of `generate(speculate=k)`: prompt lookup.  A row's guess at its next tokens is the continuation of the most
+    recent earlier occurrence of its last n-gram (max_ngram down to min_ngram tokens) in its own ids - no second model, no second
+    cache.  It sits inside `speculate_commit`, the launch that also accepts the last step's drafts.  A drafter is whatever has
+    this `commit`: given the tokens `tgt` (b, m) drawn from the step's logits, it moves `state` on to the next step's inputs."""
+
+    def __init__(self, draft, max_ngram=3, min_ngram=1):
+        assert int(draft) == draft and draft >= 1 and int(max_ngram) == max_ngram and int(min_ngram) == min_ngram and 1 <= min_ngram <= max_ngram, \
+            "speculate=k drafts k >= 1 tokens per step from n-grams of 1 <= min_ngram <= max_ngram tokens"
+        self.draft, self.max_ngram, self.min_ngram = int(draft), int(max_ngram), int(min_ngram)
+
+    def commit(self, tgt, state, cache, eos=None):
+        tgt.speculate_commit(state["ids"], state["count"], state["position_ids"], state["out_ids"], cache.pos, state["end"], state["done"],
+                             state["stats"], self.draft, max_ngram=self.max_ngram, min_ngram=self.min_ngram, eos=eos)
+
+
+def speculate_step(model, cache, state, drafter, mask=None, sampler=None, eos=None):
+    """one step of `generate(speculate=k)`, all on the ids' backend and one shape whatever the rows hold: each row's last token and
+    its drafts - `count` real tokens among m = k + 1 - go through the append forward at the row's own positions, a token is drawn
+    from EVERY one of the b * m rows of logits (the argmax, or one call of `sample`), and ONE `speculate_commit` keeps what the
+    model agrees with and lays out the next step.  No host read, no value from the host: a captured step replays as it stands."""
+    logits = model(state["ids"], cache=cache, append=True, count=state["count"], token_positions=state["position_ids"], attention_mask=mask)
+    drafter.commit(next_token(logits, sampler), state, cache, eos=eos)
+
+
+def speculate_rows(model, cache, out_ids, first, end, drafter, steps, mask, sampler, eos, graph, poll, info):
+    """the decoding loop of `generate(speculate=k)` behind the prefill: `first` (b, 1) is the prompt's own first token, the
+    cache's positions are those of each row's last prompt token, `end` (b,) the last column a row may write"""
+    cls, b, m = out_ids.__class__, out_ids.shape[0], drafter.draft + 1
+    i32 = lambda a: cls.from_numpy(np.ascontiguousarray(a, np.int32), requires_grad=False)       # noqa: E731
+    state = dict(ids=i32(np.zeros((b, m))), count=i32(np.ones(b)), position_ids=i32(np.zeros((b, m))), out_ids=out_ids, end=i32(end),
+                 done=i32(np.zeros(b)), stats=i32(np.zeros(3)))
+    # stats[0] as a tensor of its own that shares the word (indexing a tensor copies: the poll would be a launch and a read)
+    if isinstance(getattr(state["stats"], "data", None), np.ndarray):
+        finished = cls.from_numpy(state["stats"].data[0:1], requires_grad=False)
+    else:
+        from lightgrad_amd.autograd.hip.ops import _idx_view
+        finished = _idx_view(state["stats"], (slice(0, 1),))
+    # the first new token goes the way of every later one: a step of one real token per row whose commit lands it in the column
+    # behind the prompt and lays out the first speculative step
+    tgt = i32(np.zeros((b, m)))
+    tgt[:, 0:1] = first
+    drafter.commit(tgt, state, cache, eos=eos)
+    # the positions move on the device by what is accepted: the host keeps an upper bound only, as after an end-of-sequence run
+    cache.lengths, cache.length = None, int(np.max(end))
+    taken = 0
+
+    def all_done():
+        return taken % poll == 0 and int(finished.numpy()[0]) == b          # a host READ of one word every `poll` steps
+
+    with light.no_grad():
+        if graph is None or steps == 0:
+            while taken < steps:
+                speculate_step(model, cache, state, drafter, mask, sampler, eos)
+                taken += 1
+                if all_done():
+                    break
+        else:
+            # one step eagerly (greedy: no call of the random stream) - it loads the kernels and fills the memory pool -, then back to
+            # where the first commit left off: every int tensor the step writes is restored from a copy on the device (the ids too:
+            # a greedy step may keep more drafts than the sampled one that takes its place)
+            def clone(t):
+                c = cls.from_numpy(np.zeros(tuple(t.shape), np.int32), requires_grad=False)
+                c[tuple(slice(None) for _ in t.shape)] = t
+                return c
+            mutated = [state[k] for k in ("ids", "count", "position_ids", "out_ids", "done", "stats")] + [cache.pos]
+            saved = [clone(t) for t in mutated]
+            speculate_step(model, cache, state, drafter, mask, None, eos)
+            for t, s in zip(mutated, saved):
+                t[tuple(slice(None) for _ in t.shape)] = s
+            with graph.capture():
+                speculate_step(model, cache, state, drafter, mask, sampler, eos)         # recorded, not run
+            while taken < steps:
+                graph.replay()
+                taken += 1
+                if all_done():
+                    break
+    if info is not None:
+        totals = state["stats"].numpy()
+        info.update(steps=taken, drafted=int(totals[1]), accepted=int(totals[2]))
+
+
 def generate_rows(model, ids, max_new_tokens, lengths, eos_token_id, pad_token_id, attention_mask, cache, graph, sampler, prefill_chunk,
-                  append):
-    """the per-row path of `generate` (see there): right-padded prompts with a length per row, rows that stop at `eos_token_id`"""
+                  append, drafter=None, poll=4, info=None):
+    """the per-row path of `generate` (see there): right-padded prompts with a length per row, rows that stop at `eos_token_id`;
+    with a drafter, the speculative loop behind the same prefill"""
     b, s0 = ids.shape
     cls = ids.__class__
     lengths = np.full(b, s0, np.int64) if lengths is None else np.asarray(lengths, np.int64)
@@ -753,10 +836,6 @@ def generate_rows(model, ids, max_new_tokens, lengths, eos_token_id, pad_token_i
             rows = cls.from_numpy((np.arange(b) * s0 + lengths - 1).astype(np.int32), requires_grad=False)
             last = hidden.reshape(-1, hidden.shape[-1])[rows].reshape(b, 1, hidden.shape[-1])      # row lengths[r] - 1 of each sequence
         first = next_token(model.head(last), sampler)
-    # the first new token goes the way of every later one: from position lengths - 1 the commit lands it in column lengths[r]
-    cache.advance(-1)
-    first.decode_commit(token, out_ids, cache.pos, done, eos=eos)
-    cache.committed(1, eos=eos is not None)
 
     def result():
         if not append:
@@ -765,6 +844,16 @@ def generate_rows(model, ids, max_new_tokens, lengths, eos_token_id, pad_token_i
         for r in range(b):
             behind[r:r + 1, :] = out_ids[r:r + 1, int(start[r]):int(start[r]) + width]
         return behind
+
+    # the first new token goes the way of every later one: from position lengths - 1 the commit lands it in column lengths[r]
+    cache.advance(-1)
+    if drafter is not None:
+        # row r may write the columns up to that of its last new token
+        speculate_rows(model, cache, out_ids, first, start + lengths + max_new_tokens - 1, drafter, max_new_tokens - 1, mask, sampler, eos, graph,
+                       int(poll), info)
+        return result()
+    first.decode_commit(token, out_ids, cache.pos, done, eos=eos)
+    cache.committed(1, eos=eos is not None)
 
     steps = max_new_tokens - 1
     if graph is None or steps == 0:
@@ -793,7 +882,8 @@ def generate_rows(model, ids, max_new_tokens, lengths, eos_token_id, pad_token_i
 
 
 def generate(model, ids, max_new_tokens, attention_mask=None, cache=None, graph=None, temperature=None, top_k=0, top_p=1.0,
-             prefill_chunk=None, append=False, lengths=None, eos_token_id=None, pad_token_id=0):
+             prefill_chunk=None, append=False, lengths=None, eos_token_id=None, pad_token_id=0, speculate=None, max_ngram=3, min_ngram=1,
+             poll=4, stats=None):
     """decoding of a model built with `causal=True`: (b, s0) prompt ids -> (b, s0 + max_new_tokens) int32 ids on the
     prompt's backend.  temperature=None is greedy; with a temperature every token - the prompt's own first one included - is
     `logits.sample(temperature, top_k, top_p)`, drawn from the backend's random stream (`light.manual_seed`): one call of the
@@ -818,13 +908,32 @@ def generate(model, ids, max_new_tokens, attention_mask=None, cache=None, graph=
     its frozen position (`decode_step_rows`), and the sampler draws for it too (one call of the stream per step): the step never
     changes shape and is captured once with graph=.  prefill_chunk= and append=True work as above, with pieces that are
     right-padded and a position that moves by `lengths` per row (append after a run with an end-of-sequence id reads the
-    positions back once: only the device knows where the rows stopped)."""
-    if lengths is not None or eos_token_id is not None:
+    positions back once: only the device knows where the rows stopped).
+    speculate=k >= 1 selects the per-row path too and decodes speculatively by prompt lookup: every step feeds a row's last token
+    and up to k drafts - the continuation of the most recent earlier occurrence of the row's last n-gram (max_ngram down to
+    min_ngram tokens) in its own ids - through ONE append forward of shape (b, k + 1) with a token count per row, draws a token
+    from every row of logits, and ONE `speculate_commit` keeps the drafts the model agrees with plus one token of its own and looks
+    up the next drafts (`speculate_step`, `NgramDrafter`): a row gains 1 .. k + 1 tokens per step.  The host reads one word every
+    `poll` steps - the rows finished - and stops when it is b, or after max_new_tokens - 1 steps; graph= captures the step once.
+    The result has the shape and padding of the per-row path; afterwards the cache's host mirror `lengths` is None and `length`
+    an upper bound, as after an end-of-sequence run.  stats: a dict that receives `steps`, `drafted` and `accepted` (one more
+    read, at the end).  Greedy, the tokens are those of the run without speculate= wherever no step is a near-tie (the (b, k + 1)
+    forward rounds differently from the (b, 1) one).  Sampled, every one of the k + 1 rows is sampled and a draft is accepted when
+    it EQUALS the sample: the drafts are a function of the prefix only, so every emitted token is a draw from the model's own
+    distribution given its prefix and the output distribution is exact.  A sampled run repeats for a given seed, k and n-gram
+    bounds (eager or captured); it does NOT reproduce the run without speculate=, because it takes one call of the random stream
+    per step, not per token."""
+    if lengths is not None or eos_token_id is not None or speculate is not None:
         assert max_new_tokens >= 1 and ids.shape[1] >= 1 and (prefill_chunk is None or prefill_chunk >= 1)
         assert model.bert.encoder.layer[0].attention.self.causal, "generate needs a model built with causal=True"
         assert not append or cache is not None, "append=True continues a cache: pass the one that holds the tokens so far"
-        return generate_rows(model, ids, max_new_tokens, lengths, eos_token_id, pad_token_id, attention_mask, cache, graph,
-                             None if temperature is None else (temperature, top_k, top_p), prefill_chunk, append)
+        sampler = None if temperature is None else (temperature, top_k, top_p)
+        if speculate is None:
+            return generate_rows(model, ids, max_new_tokens, lengths, eos_token_id, pad_token_id, attention_mask, cache, graph, sampler,
+                                 prefill_chunk, append)
+        assert int(poll) == poll and poll >= 1 and (stats is None or isinstance(stats, dict)), "poll is a number of steps >= 1, stats a dict"
+        return generate_rows(model, ids, max_new_tokens, lengths, eos_token_id, pad_token_id, attention_mask, cache, graph, sampler,
+                             prefill_chunk, append, drafter=NgramDrafter(speculate, max_ngram, min_ngram), poll=poll, info=stats)
     b, s0 = ids.shape
     positions = model.bert.embeddings.position_embeddings.weight.shape[0]
     layer0 = model.bert.encoder.layer[0].attention.self
@@ -1026,12 +1135,23 @@ if __name__ == "__main__":
             row_lengths = [max(1, 8 - r) for r in range(batch)]
             pieces = dict(pieces, lengths=row_lengths, eos_token_id=int(sys.argv[sys.argv.index("--eos") + 1]) if "--eos" in sys.argv else None)
             print("ragged batch: prompts of %s tokens%s" % (row_lengths, ", stopping at id %d" % pieces["eos_token_id"] if "--eos" in sys.argv else ""))
-        new_ids = generate(lm, prompt, n_new, graph=recorded, **sampling, **pieces).numpy()          # the only host read
+        counters = {}
+        if "--speculate" in sys.argv:
+            option = lambda name, kind, default: kind(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default     # noqa: E731
+            if "--eos" in sys.argv:
+                pieces = dict(pieces, eos_token_id=option("--eos", int, None))
+            pieces = dict(pieces, speculate=option("--speculate", int, 3), max_ngram=option("--max-ngram", int, 3),
+                          min_ngram=option("--min-ngram", int, 1), stats=counters)
+        new_ids = generate(lm, prompt, n_new, graph=recorded, **sampling, **pieces).numpy()          # the only host read of the tokens
+        if counters:
+            print("speculative decoding by prompt lookup, up to %d drafts per step: %d steps, %d of %d drafts accepted" % (
+                pieces["speculate"], counters["steps"], counters["accepted"], counters["drafted"]))
         if sampling:
             print("sampled: temperature %(temperature)g, top_k %(top_k)d, top_p %(top_p)g" % sampling)
         print("generated %d tokens per sequence in %.1f ms (%s)" % (
             n_new, 1e3 * (time.perf_counter() - t0),
-            "decode step captured once, %d kernels, replayed %d times" % (recorded.kernel_count(), n_new - 1) if recorded else "eager decode steps"))
+            "decode step captured once, %d kernels, replayed %d times" % (recorded.kernel_count(), counters.get("steps", n_new - 1)) if recorded
+            else "eager decode steps"))
         for r, row in enumerate(new_ids):
             print(" ".join(str(i) for i in row[pieces["lengths"][r] if "lengths" in pieces else 8:]))
         sys.exit(0)

@@ -742,6 +742,28 @@ int lg_serve_commit_i32(const int32_t* nxt, int64_t nxt_pitch,       /* the toke
                         int32_t* ids, int32_t* position_ids,         /* (slots, m) dense each */
                         int32_t* last,                               /* (slots) */
                         int64_t slots, int64_t m, int64_t capacity, int32_t eos_id);   /* eos_id < 0: none */
+/* The bookkeeping of one step of speculative decoding by prompt lookup in one launch (csrc/speculate.hip): one workgroup of 256
+ * threads per row, 1 <= batch < 2^24.  The definition is the loop of `CpuTensor.speculate_commit` (autograd/cpu/ops.py), for each
+ * row r on its own: (1) done[r] != 0: count[r] = 0, nothing else.  (2) c = count[r], p = pos[r]; unless 1 <= c <= m, p >= 0 and
+ * p + c <= end[r] <= columns - 1 the status flag is raised - LG_EINDEX at the next lg_sync / lg_memcpy_d2h -, count[r] = 0 and
+ * nothing else of the row is written.  (3) a = the leading j in 0 .. c - 2 with ids[r, j + 1] == tgt[r, j]; the row emits
+ * e = a + 1 tokens tgt[r, 0 .. e), cut behind the first one that equals eos_id >= 0 (the row then stops).  (4) out_ids[r, p + 1 ..
+ * p + e] = those tokens, pos[r] = p += e, stats[1] += c - 1, stats[2] += a.  (5) Stopped or p == end[r]: done[r] = 1, stats[0] += 1,
+ * count[r] = 0.  (6) Otherwise, with L = p + 1, seq = out_ids[r, 0 .. L) and cap = min(draft, end[r] - p - 1): for n = max_ngram
+ * down to min_ngram with L >= n + 1 the largest q <= L - n - 1 with seq[q .. q + n) == seq[L - n .. L), the first n that has one
+ * wins, the drafts are seq[q + n .. min(q + n + cap, L)); ids[r] = seq[p], the drafts, then 0; count[r] = 1 + their number;
+ * position_ids[r, i] = p + i for i < count[r], else 0.  The candidate starts are split over the threads and the largest match is
+ * a fold of fixed shape over integers; stats takes integer atomic adds.  The sequence is staged in LDS for columns <= 4096; wider
+ * rows are served as well, read from memory.  Refused (LG_EINVAL): sizes outside their ranges, draft outside 0 .. m - 1, n-gram
+ * bounds that are not 1 <= min <= max, a NULL or misaligned operand, out_pitch < columns, any two operands that overlap.  Every
+ * operand but out_ids is dense. */
+int lg_speculate_commit_i32(const int32_t* tgt,                      /* (batch, m) the tokens drawn from the step's logits */
+                            int32_t* ids, int32_t* count, int32_t* position_ids,   /* (batch, m), (batch), (batch, m): the step's inputs, then the next step's */
+                            int32_t* out_ids, int64_t out_pitch, int64_t columns,  /* (batch, columns), row pitch in elements */
+                            int32_t* pos, const int32_t* end, int32_t* done,       /* (batch) each */
+                            int32_t* stats,                          /* {rows finished, tokens drafted, drafts accepted} */
+                            int64_t batch, int64_t m, int64_t draft, int64_t max_ngram, int64_t min_ngram,
+                            int32_t eos_id);                         /* eos_id < 0: none */
 
 /* ---- two independent products in one launch ----------------------------------------------------------
  * lg_gemm_pair_begin(); <product 1>; <product 2>; lg_gemm_pair_end();   with products issued through

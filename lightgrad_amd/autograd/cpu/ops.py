@@ -535,6 +535,96 @@ def _check_serve_commit(nxt, prompts, prompt_len, budget, out, out_len, queue, r
 CpuTensor.serve_commit = _serve_commit
 
 
+def _speculate_commit(tgt, ids, count, position_ids, out_ids, pos, end, done, stats, draft, max_ngram=3, min_ngram=1, eos=None):
+    """ tgt.speculate_commit(ids, count, position_ids, out_ids, pos, end, done, stats, draft, max_ngram=3, min_ngram=1, eos=None):
+    the bookkeeping of one step of speculative decoding by prompt lookup, in place and outside the tape - the definition of the
+    op, written as the loop it is.  All int32: tgt (b, m) the tokens drawn from the logits of the step's m rows; ids and
+    position_ids (b, m) and count (b,) the step's inputs on entry and the next step's on exit; out_ids (b, columns) a column per
+    position of each row's sequence; pos (b,) the position of each row's input token (the cache's positions, as in
+    `decode_commit`); end (b,) the last column a row may write; done (b,); stats (3,) = {rows finished, tokens drafted, drafts
+    accepted}.  0 <= draft <= m - 1 drafts per step at most, n-grams of min_ngram .. max_ngram tokens.  For each row r on its own:
+      1. done[r] != 0: count[r] = 0 and nothing else of the row is written.
+      2. c = count[r], p = pos[r].  Unless 1 <= c <= m, p >= 0 and p + c <= end[r] <= columns - 1: count[r] = 0, nothing else of
+         the row is written and the call raises IndexError after every other row has been committed, as the device flag of the
+         HipTensor op does at its next synchronisation.
+      3. a = the number of leading j in 0 .. c - 2 with ids[r, j + 1] == tgt[r, j]: the drafts the model agrees with.  The row
+         emits e = a + 1 tokens tgt[r, :e]; if `eos` (an id >= 0) is among them, e ends at the first one and the row stops.
+      4. out_ids[r, p + 1 .. p + e] = tgt[r, :e]; p += e, pos[r] = p; stats[1] += c - 1, stats[2] += a (before the cut at eos).
+      5. The row stopped, or p == end[r]: done[r] = 1, stats[0] += 1, count[r] = 0.  Otherwise:
+      6. L = p + 1, seq = out_ids[r, :L], cap = min(draft, end[r] - p - 1).  For n = max_ngram down to min_ngram with L >= n + 1:
+         the largest q in 0 .. L - n - 1 with seq[q:q + n] == seq[L - n:L]; the first n that has one wins and the drafts are
+         seq[q + n:min(q + n + cap, L)]; no such n, or cap == 0: no drafts.  ids[r] = [seq[p]] + drafts then 0,
+         count[r] = 1 + len(drafts), position_ids[r, i] = p + i for i < count[r], else 0.
+    Rejected drafts have left keys and values in the cache beyond the new position: nothing reads them (nn.KVCache). """
+    b, m = _check_speculate_commit(tgt, ids, count, position_ids, out_ids, pos, end, done, stats, draft, max_ngram, min_ngram, eos)
+    arrays = [t.data for t in (tgt, ids, count, position_ids, out_ids, pos, end, done, stats)]
+    assert not any(np.shares_memory(x, y) for i, x in enumerate(arrays) for y in arrays[i + 1:]), "speculate_commit: two operands overlap"
+    columns = out_ids.shape[1]
+    eos, draft, max_ngram, min_ngram = (-1 if eos is None else int(eos)), int(draft), int(max_ngram), int(min_ngram)
+    bad = []
+    for r in range(b):
+        if done.data[r] != 0:
+            count.data[r] = 0
+            continue
+        c, p, last = int(count.data[r]), int(pos.data[r]), int(end.data[r])
+        if not (1 <= c <= m and p >= 0 and p + c <= last <= columns - 1):
+            count.data[r] = 0
+            bad.append(r)
+            continue
+        a = 0
+        while a < c - 1 and ids.data[r, a + 1] == tgt.data[r, a]:
+            a += 1
+        e, stopped = a + 1, False
+        if eos >= 0 and (tgt.data[r, :e] == eos).any():
+            e, stopped = int(np.argmax(tgt.data[r, :e] == eos)) + 1, True
+        out_ids.data[r, p + 1:p + 1 + e] = tgt.data[r, :e]
+        p += e
+        pos.data[r] = p
+        stats.data[1] += c - 1
+        stats.data[2] += a
+        if stopped or p == last:
+            done.data[r] = 1
+            stats.data[0] += 1
+            count.data[r] = 0
+            continue
+        # (this module's `min` is the tensor op)
+        L, cap, drafts = p + 1, (draft if draft < last - p - 1 else last - p - 1), ()
+        seq = out_ids.data[r, :L]
+        if cap > 0:
+            for n in range(max_ngram if max_ngram < L - 1 else L - 1, min_ngram - 1, -1):
+                q = next((q for q in range(L - n - 1, -1, -1) if (seq[q:q + n] == seq[L - n:]).all()), -1)
+                if q >= 0:
+                    drafts = seq[q + n:q + n + cap].copy()       # (the slice ends at L by itself)
+                    break
+        k = 1 + len(drafts)
+        ids.data[r, 0], ids.data[r, 1:k], ids.data[r, k:] = seq[p], drafts, 0
+        position_ids.data[r, :k], position_ids.data[r, k:] = p + np.arange(k), 0
+        count.data[r] = k
+    if bad:
+        raise IndexError("speculate_commit: row %d (of %d that did) holds a count, a position or an end outside its bounds" % (bad[0], len(bad)))
+
+
+def _check_speculate_commit(tgt, ids, count, position_ids, out_ids, pos, end, done, stats, draft, max_ngram, min_ngram, eos):
+    """the operand shapes and dtypes of `speculate_commit`, on any backend; returns (rows b, tokens per row m)"""
+    b = pos.shape[0] if len(pos.shape) == 1 else -1
+    m = ids.shape[1] if len(ids.shape) == 2 else -1
+    i32 = np.dtype(np.int32)
+    operands = (tgt, ids, count, position_ids, out_ids, pos, end, done, stats)
+    shapes = [tuple(t.shape) for t in operands]
+    assert b >= 1 and m >= 1 and shapes[0] == shapes[1] == shapes[3] == (b, m) and shapes[2] == shapes[6] == shapes[7] == (b,) \
+        and len(out_ids.shape) == 2 and out_ids.shape[0] == b and out_ids.shape[1] >= 1 and shapes[8] == (3,), \
+        "speculate_commit: tgt / ids / position_ids (b, m), count / pos / end / done (b,), out_ids (b, columns), stats (3,) - got %s" % (shapes,)
+    assert all(np.dtype(t.dtype) == i32 for t in operands), "speculate_commit: every operand is int32"
+    assert eos is None or int(eos) == eos, "speculate_commit: eos is an int or None"
+    assert int(draft) == draft and 0 <= draft <= m - 1, "speculate_commit: draft is an int within 0 .. m - 1 = %d (got %s)" % (m - 1, draft)
+    assert int(min_ngram) == min_ngram and int(max_ngram) == max_ngram and 1 <= min_ngram <= max_ngram < 2 ** 31, \
+        "speculate_commit: 1 <= min_ngram <= max_ngram are ints (got %s, %s)" % (min_ngram, max_ngram)
+    return b, m
+
+
+CpuTensor.speculate_commit = _speculate_commit
+
+
 def _next_token_labels(ids, ignore_index=-100):
     """ ids.next_token_labels(ignore_index=-100): the labels of the next-token objective - `ids` shifted left by one along the last
     axis, `ignore_index` in the last column; same dtype and shape, a constant of the tape. """

@@ -167,6 +167,7 @@ PROTOTYPES = {
     "lg_decode_commit_i32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, ctypes.c_int32]),
     "lg_serve_commit_i32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
                                     c_int64] + [c_void_p] * 6 + [c_int64] * 3 + [ctypes.c_int32]),
+    "lg_speculate_commit_i32": (c_int, [c_void_p] * 5 + [c_int64, c_int64] + [c_void_p] * 4 + [c_int64] * 5 + [ctypes.c_int32]),
     "lg_layernorm_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_double]),
     "lg_layernorm_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64]),
     "lg_cross_entropy_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int64]),

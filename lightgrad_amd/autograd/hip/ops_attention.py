@@ -622,3 +622,40 @@ def serve_commit(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos
 
 
 HipTensor.serve_commit = serve_commit
+
+
+""" The bookkeeping of a speculative decoding step in one launch (csrc/speculate.hip) """
+
+
+def speculate_commit(tgt, ids, count, position_ids, out_ids, pos, end, done, stats, draft, max_ngram=3, min_ngram=1, eos=None):
+    """ tgt.speculate_commit(ids, count, position_ids, out_ids, pos, end, done, stats, draft, max_ngram=3, min_ngram=1, eos=None):
+    what `CpuTensor.speculate_commit` defines - per row the longest prefix of its drafts that the model agrees with is kept with
+    one token of the model's own, a row that draws `eos` or reaches `end` is finished, and the next step's drafts are looked up in
+    the row's own ids - in ONE launch (lg_speculate_commit_i32), in place and outside the tape.  Int32 HipTensors that do not
+    overlap; out_ids may have any row pitch, every other operand is dense.  A row whose count, position or end is out of bounds
+    gets count 0, keeps its other bytes and raises IndexError at the next synchronisation.  No host read: a captured step replays
+    it as it stands. """
+    from ..cpu.ops import _check_speculate_commit
+    name = "speculate_commit"
+    operands = (tgt, ids, count, position_ids, out_ids, pos, end, done, stats)
+    assert all(isinstance(t, HipTensor) for t in operands), "%s: every operand is a HipTensor" % name
+    b, m = _check_speculate_commit(*operands, draft, max_ngram, min_ngram, eos)
+    columns = out_ids._shape[1]
+    # what is only read may be copied once into a layout the launch addresses
+    tgt, end = (t if t.is_contiguous() else t.contiguous() for t in (tgt, end))
+    # the launch writes these where they lie: a layout it cannot address is an error, never a copy
+    assert all(t.is_contiguous() for t in (ids, count, position_ids, pos, done, stats)) and (columns == 1 or out_ids._strides[1] == 1) \
+        and (b == 1 or out_ids._strides[0] >= columns), \
+        "%s: ids, count, position_ids, pos, done and stats must be dense and the rows of out_ids contiguous" % name
+    operands = (tgt, ids, count, position_ids, out_ids, pos, end, done, stats)
+    for i, x in enumerate(operands):
+        for y in operands[i + 1:]:
+            assert not _shares_bytes(x, y), "%s: two operands overlap" % name
+    for x in (ids, count, position_ids, out_ids, pos, done, stats):
+        flush_lazy_readers(x)
+    _l.check(_l.lib().lg_speculate_commit_i32(tgt.ptr, ids.ptr, count.ptr, position_ids.ptr, out_ids.ptr, out_ids._strides[0] if b > 1 else columns,
+                                              columns, pos.ptr, end.ptr, done.ptr, stats.ptr, b, m, int(draft), int(max_ngram), int(min_ngram),
+                                              -1 if eos is None else int(eos)))
+
+
+HipTensor.speculate_commit = speculate_commit

@@ -298,6 +298,8 @@ class KVCache(object):
     The host mirror is `lengths`, an int64 array: valid only while every change came from the host, None once the device moved
     the positions by values the host has not seen (`committed` with an end-of-sequence id).  `length` is then an upper bound of
     every row's position - what the routing between prefill and decode step and the capacity checks need, never an index.
+    Rejected drafts (speculative decoding: `speculate_commit`) leave key and value rows in the cache beyond the new position.
+    Nothing reads beyond the position, and the next step overwrites them.
     Without `per_row` every attribute, shape and launch is as it was."""
 
     def __init__(self, layers: int, batch: int, capacity: int, width: int, like=None, per_row: bool = False):
