@@ -881,9 +881,134 @@ def generate_rows(model, ids, max_new_tokens, lengths, eos_token_id, pad_token_i
     return result()
 
 
+def beam_search_step(model, cache, state, num_beams, eos=None):
+    """one step of `generate(num_beams=w)`, all on the ids' backend and one shape whatever the beams hold: the token (b * w, 1) of
+    every beam goes through the decode forward at its own position (`decode_step_rows`' forward, at batch b * w), ONE `beam_step`
+    keeps the best w continuations of every group of w beams - a finished beam competes as itself - and ONE `cache.reorder` makes
+    the cache rows follow the beams that survived.  No host read, no value from the host: a captured step replays as it stands."""
+    logits = model(state["token"], cache=cache)                             # (b * w, 1, vocab)
+    logits.beam_step(state["scores"], state["parent"], state["token"], state["out_ids"], cache.pos, state["done"], state["stats"], num_beams, eos=eos)
+    cache.reorder(state["parent"], num_beams)
+    cache.committed(1, eos=True)
+
+
+def generate_beams(model, ids, max_new_tokens, lengths, eos_token_id, pad_token_id, cache, graph, prefill_chunk, num_beams, length_penalty,
+                   poll, beams):
+    """the beam-search path of `generate` (see there): the beams of prompt g are rows g * w .. g * w + w - 1 of a per-row cache,
+    best first.  The prompt is prefilled ONCE per prompt, at batch b, into a cache of b rows and exactly s0 positions; one strided
+    copy per cache tensor takes it to the group leaders (rows g * w) of the big cache and one `cache.reorder` with every parent the
+    leader to the other w - 1 rows."""
+    b, s0 = ids.shape
+    cls, w = ids.__class__, int(num_beams)
+    rows = b * w
+    lengths = np.full(b, s0, np.int64) if lengths is None else np.asarray(lengths, np.int64)
+    assert lengths.shape == (b,) and (lengths >= 1).all() and (lengths <= s0).all(), \
+        "lengths: %d ints within 1 .. %d, the real tokens that lead each right-padded row" % (b, s0)
+    eos = None if eos_token_id is None else int(eos_token_id)
+    positions = model.bert.embeddings.position_embeddings.weight.shape[0]
+    layer0 = model.bert.encoder.layer[0].attention.self
+    weight = model.bert.embeddings.word_embeddings.weight
+    layers, hidden_width = len(model.bert.encoder.layer), layer0.h * layer0.d
+    assert weight.shape[0] >= w, "num_beams = %d exceeds the vocabulary of %d" % (w, weight.shape[0])
+    columns = int(lengths.max()) + max_new_tokens                       # of the result, and of every beam's ids
+    if cache is None:
+        cache = nn.KVCache(layers, rows, s0 + max_new_tokens, hidden_width, like=weight, per_row=True)
+    assert cache.per_row and cache.batch == rows, "num_beams = %d over %d prompts takes a per-row cache of %d rows: nn.KVCache(..., per_row=True)" % (w, b, rows)
+    assert (lengths + max_new_tokens <= cache.capacity).all() and s0 <= cache.capacity <= positions, \
+        "prompts of %s tokens (padded to %d) and %d new ones do not fit a cache of %d positions and a model of %d position embeddings" % (
+            lengths.tolist(), s0, max_new_tokens, cache.capacity, positions)
+    cache.reset()
+    cache.num_beams = w
+    ids32 = ids if ids.dtype == np.int32 else ids.astype(np.int32)
+    i32 = lambda a: cls.from_numpy(np.ascontiguousarray(a, np.int32), requires_grad=False)       # noqa: E731
+    leader = np.repeat(np.arange(b) * w, w)                             # the first row of each row's group
+    scores0 = np.full((b, w), -np.inf, np.float32)
+    scores0[:, 0] = 0.0                                                 # w copies of a prompt are one hypothesis: only the leader counts
+    state = dict(token=i32(np.zeros((rows, 1))), out_ids=i32(np.full((rows, columns), int(pad_token_id))), done=i32(np.zeros(rows)),
+                 parent=i32(leader), stats=i32(np.zeros(2)), scores=cls.from_numpy(scores0.reshape(rows), requires_grad=False))
+    for g in range(b):                                                  # the prompt: the leader's row (a winner copies its parent's columns)
+        state["out_ids"][g * w:g * w + 1, :int(lengths[g])] = ids32[g:g + 1, :int(lengths[g])]
+    # stats[0] as a tensor of its own that shares the word (indexing a tensor copies: the poll would be a launch and a read)
+    if isinstance(getattr(state["stats"], "data", None), np.ndarray):
+        finished = cls.from_numpy(state["stats"].data[0:1], requires_grad=False)
+    else:
+        from lightgrad_amd.autograd.hip.ops import _idx_view
+        finished = _idx_view(state["stats"], (slice(0, 1),))
+    with light.no_grad():
+        small = nn.KVCache(layers, b, s0, hidden_width, like=weight, per_row=True)
+        if prefill_chunk is not None:
+            last = prefill_rows_in_pieces(model, small, ids32, lengths, None, int(prefill_chunk))
+        else:
+            hidden = model.bert(ids32, cache=small)                                 # (b, s0, hidden), as in `generate_rows`
+            at = cls.from_numpy((np.arange(b) * s0 + lengths - 1).astype(np.int32), requires_grad=False)
+            last = hidden.reshape(-1, hidden.shape[-1])[at].reshape(b, 1, hidden.shape[-1])
+        for layer in range(layers):
+            cache.k[layer][0::w, :s0] = small.k[layer]
+            cache.v[layer][0::w, :s0] = small.v[layer]
+        cache.set_lengths(np.repeat(lengths, w))
+        cache.reorder(state["parent"], w)                               # every row of a group holds its leader's prompt
+        # the first new token goes the way of every later one: the head on the leader's row, once per beam, and a `beam_step` from
+        # position lengths - 1 in which only the leaders' candidates are finite
+        first = model.head(last.reshape(b, last.shape[-1])[i32(np.repeat(np.arange(b), w))].reshape(rows, 1, last.shape[-1]))
+        cache.advance(-1)
+        first.beam_step(state["scores"], state["parent"], state["token"], state["out_ids"], cache.pos, state["done"], state["stats"], w, eos=eos)
+        cache.committed(1, eos=True)                                    # (no reorder: every row of a group holds the same prompt)
+        steps, taken = max_new_tokens - 1, 0
+
+        def all_done():
+            return taken % poll == 0 and int(finished.numpy()[0]) == b          # a host READ of one word every `poll` steps
+
+        if graph is None or steps == 0:
+            while taken < steps:
+                beam_search_step(model, cache, state, w, eos)
+                taken += 1
+                if all_done():
+                    break
+        else:
+            # one step eagerly - it loads the kernels and fills the memory pool -, then back to where the first `beam_step` left
+            # off: every tensor the step writes is restored from a copy on the device.  The cache rows need none: below each row's
+            # position a group's rows are still equal, and a row's own position is rewritten by the forward of every step
+            def clone(t):
+                c = cls.from_numpy(np.zeros(tuple(t.shape), t.dtype), requires_grad=False)
+                c[tuple(slice(None) for _ in t.shape)] = t
+                return c
+            mutated = [state[k] for k in ("scores", "parent", "token", "out_ids", "done", "stats")] + [cache.pos]
+            saved, length = [clone(t) for t in mutated], cache.length
+            beam_search_step(model, cache, state, w, eos)
+            for t, s in zip(mutated, saved):
+                t[tuple(slice(None) for _ in t.shape)] = s
+            cache.length = length
+            with graph.capture():
+                beam_search_step(model, cache, state, w, eos)               # recorded, not run: only the host mirror moved
+            while taken < steps:
+                graph.replay()
+                if taken:
+                    cache.committed(1, eos=True)
+                taken += 1
+                if all_done():
+                    break
+        # the result: per prompt the beam with the largest scores / n ** length_penalty, n its new tokens (the end-of-sequence id
+        # included) - the first of equals, like every argmax here
+        n = (cache.pos + i32(-(np.repeat(lengths, w) - 1))).astype(np.float32)
+        if length_penalty == 0:
+            ranked = state["scores"]
+        else:
+            ranked = state["scores"] / (n if length_penalty == 1 else (n.log() * float(length_penalty)).exp())
+        best = ranked.reshape(b, w).argmax(-1).astype(np.int32) + i32(np.arange(b) * w)
+        # a slot keeps what it held beyond its beam's position (a finished beam may have moved into the slot of a longer one): the
+        # result is padded there - mask = min(relu(pos + 1 - column), 1), in float32, which holds every id below 2^24 exactly
+        chosen = state["out_ids"][best].astype(np.float32)
+        reach = ((cache.pos[best] + 1).astype(np.float32).reshape(b, 1) - cls.from_numpy(np.arange(columns, dtype=np.float32), requires_grad=False)).relu()
+        mask = 1.0 - (1.0 - reach).relu()
+        result = (chosen * mask + (1.0 - mask) * float(int(pad_token_id))).astype(np.int32)
+    if beams is not None:
+        beams.update(sequences=state["out_ids"].reshape(b, w, columns), scores=state["scores"].reshape(b, w), steps=taken)
+    return result
+
+
 def generate(model, ids, max_new_tokens, attention_mask=None, cache=None, graph=None, temperature=None, top_k=0, top_p=1.0,
              prefill_chunk=None, append=False, lengths=None, eos_token_id=None, pad_token_id=0, speculate=None, max_ngram=3, min_ngram=1,
-             poll=4, stats=None):
+             poll=4, stats=None, num_beams=None, length_penalty=1.0, beams=None):
     """decoding of a model built with `causal=True`: (b, s0) prompt ids -> (b, s0 + max_new_tokens) int32 ids on the
     prompt's backend.  temperature=None is greedy; with a temperature every token - the prompt's own first one included - is
     `logits.sample(temperature, top_k, top_p)`, drawn from the backend's random stream (`light.manual_seed`): one call of the
@@ -922,7 +1047,30 @@ def generate(model, ids, max_new_tokens, attention_mask=None, cache=None, graph=
     it EQUALS the sample: the drafts are a function of the prefix only, so every emitted token is a draw from the model's own
     distribution given its prefix and the output distribution is exact.  A sampled run repeats for a given seed, k and n-gram
     bounds (eager or captured); it does NOT reproduce the run without speculate=, because it takes one call of the random stream
-    per step, not per token."""
+    per step, not per token.
+    num_beams=w (1 .. 8) selects beam search: b prompts occupy b * w rows of a per-row cache (a cache given must have that many),
+    group g = rows g * w .. g * w + w - 1, best first.  The prompt is prefilled once per prompt at batch b and copied to its group;
+    every step is the per-row decode forward at batch b * w, ONE `beam_step` that keeps the w best of the group's w * vocab
+    continuations by cumulative log-probability (a beam that drew eos_token_id competes as itself and is never extended) and ONE
+    `cache.reorder` that makes the cache rows follow the surviving beams (`beam_search_step`); graph= captures it once.  The host
+    reads one word every `poll` steps - the groups whose beams have all finished - and stops when it is b, or after
+    max_new_tokens - 1 steps.  The result has the shape and padding of the per-row path and holds, per prompt, the beam that
+    maximises score / n ** length_penalty with n its new tokens (the end-of-sequence id included), the first of equals; it is
+    picked on the device.  beams: a dict that receives `sequences` (b, w, columns) and `scores` (b, w) as tensors, and `steps`.
+    lengths=, eos_token_id=, pad_token_id= and prefill_chunk= work as on the per-row path; temperature, speculate= and append=True
+    are refused.  num_beams=1 is greedy decoding, up to near-ties (its scores come from a different launch than argmax's logits)."""
+    if num_beams is not None:
+        assert int(num_beams) == num_beams and 1 <= num_beams <= 8, "num_beams is an int within 1 .. 8 (got %s)" % (num_beams,)
+        assert temperature is None, "beam search is deterministic: temperature= (sampling beams) is not supported with num_beams="
+        assert speculate is None, "speculate= drafts for one sequence per row: it is not supported with num_beams="
+        assert not append, "append=True (a second turn behind a filled cache) is not supported with num_beams="
+        assert attention_mask is None, "right-padded prompts need no mask: pass lengths= with num_beams="
+        assert max_new_tokens >= 1 and ids.shape[1] >= 1 and (prefill_chunk is None or prefill_chunk >= 1)
+        assert model.bert.encoder.layer[0].attention.self.causal, "generate needs a model built with causal=True"
+        assert int(poll) == poll and poll >= 1 and (beams is None or isinstance(beams, dict)), "poll is a number of steps >= 1, beams a dict"
+        assert float(length_penalty) == length_penalty and length_penalty >= 0, "length_penalty is a number >= 0"
+        return generate_beams(model, ids, max_new_tokens, lengths, eos_token_id, pad_token_id, cache, graph, prefill_chunk, int(num_beams),
+                              float(length_penalty), int(poll), beams)
     if lengths is not None or eos_token_id is not None or speculate is not None:
         assert max_new_tokens >= 1 and ids.shape[1] >= 1 and (prefill_chunk is None or prefill_chunk >= 1)
         assert model.bert.encoder.layer[0].attention.self.causal, "generate needs a model built with causal=True"
@@ -1142,6 +1290,12 @@ if __name__ == "__main__":
                 pieces = dict(pieces, eos_token_id=option("--eos", int, None))
             pieces = dict(pieces, speculate=option("--speculate", int, 3), max_ngram=option("--max-ngram", int, 3),
                           min_ngram=option("--min-ngram", int, 1), stats=counters)
+        if "--num-beams" in sys.argv:
+            option = lambda name, kind, default: kind(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default     # noqa: E731
+            if "--eos" in sys.argv:
+                pieces = dict(pieces, eos_token_id=option("--eos", int, None))
+            pieces = dict(pieces, num_beams=option("--num-beams", int, 4), length_penalty=option("--length-penalty", float, 1.0))
+            print("beam search: %d beams per prompt, length penalty %g" % (pieces["num_beams"], pieces["length_penalty"]))
         new_ids = generate(lm, prompt, n_new, graph=recorded, **sampling, **pieces).numpy()          # the only host read of the tokens
         if counters:
             print("speculative decoding by prompt lookup, up to %d drafts per step: %d steps, %d of %d drafts accepted" % (

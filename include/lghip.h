@@ -764,6 +764,38 @@ int lg_speculate_commit_i32(const int32_t* tgt,                      /* (batch, 
                             int32_t* stats,                          /* {rows finished, tokens drafted, drafts accepted} */
                             int64_t batch, int64_t m, int64_t draft, int64_t max_ngram, int64_t min_ngram,
                             int32_t eos_id);                         /* eos_id < 0: none */
+/* One step of beam search in one launch (csrc/beam.hip): beams are rows, group g is rows g * w .. g * w + w - 1 best first,
+ * w = num_beams in 1 .. 8, rows a multiple of w, w <= vocab < 2^22.  The definition is the loop of `CpuTensor.beam_step`
+ * (autograd/cpu/ops.py), for each group on its own: (1) a row with pos < 0 or a live row (done == 0) with pos + 1 >= columns: the
+ * group keeps every byte, parent is the identity and the status flag is raised - LG_EINDEX at the next lg_sync / lg_memcpy_d2h.
+ * (2) A group that is all done keeps every byte, parent is the identity.  (3) A live beam i offers scores[i] + log_softmax(x)[j]
+ * for every j, a done beam offers itself once, at flat index i * vocab.  (4) The w largest, ties to the smaller flat index
+ * i * vocab + j, best first.  (5) Slot n taking (s, i, j): parent[n] = g * w + i; from a done beam a copy of row i (score, token,
+ * pos, done = 1, out_ids columns 0 .. pos[i]); otherwise out_ids columns 0 .. pos[i] of row i, column pos[i] + 1 = j, pos =
+ * pos[i] + 1, token = j, scores = s, done = (j == eos_id >= 0).  (6) stats[0] += 1 when the group goes from some beam live to all
+ * done, stats[1] += the slots whose parent is not themselves.  Grid (w, rows / w): a workgroup per row reads it once in 16-byte
+ * loads, keeps its top w as integer keys, sums the exponentials as 64-bit integers (exact in any order) and publishes w keys and
+ * the beam's one constant c_i = scores[i] - max - log(sum), a double; a candidate is fp32(x[j] + c_i).  The last workgroup of a group to
+ * arrive (handoff.h) ranks the w * w survivors and commits, a thread per column of out_ids across the group's rows.  Refused
+ * (LG_EINVAL): sizes outside their ranges, a NULL or misaligned operand, a pitch below the row length, any two operands that
+ * overlap.  logits and out_ids may have any row pitch; every other operand is dense. */
+int lg_beam_step_f32(const float* logits, int64_t logits_pitch,      /* (rows, vocab), row pitch in elements */
+                     float* scores, int32_t* parent, int32_t* token, /* (rows) each */
+                     int32_t* out_ids, int64_t out_pitch, int64_t columns,  /* (rows, columns), row pitch in elements */
+                     int32_t* pos, int32_t* done,                    /* (rows) each */
+                     int32_t* stats,                                 /* {groups finished, slots that changed their beam} */
+                     int64_t rows, int64_t vocab, int64_t num_beams,
+                     int32_t eos_id);                                /* eos_id < 0: none */
+/* The rows of up to 64 cache tensors follow their beams in one launch (csrc/beam.hip; nn.KVCache.reorder, `CpuTensor.kv_reorder`):
+ * element (r, j, c) of tensor t at tensors[t] + r * sbc + j * ldc + c, `tensors` a HOST array of device pointers that travel by
+ * value in the kernel's arguments.  For each group of w = num_beams rows, with L = max pos over the group (at most capacity): row n
+ * becomes the old row parent[n] at positions j < L, in place; positions >= L and a group whose parents are the identity are not
+ * touched (no cache load).  A parent outside its group writes nothing for that group and raises the status flag.  Refused
+ * (LG_EINVAL): more than 64 tensors, num_beams outside 1 .. 8, rows no multiple of it, width no multiple of 4, pitches below the
+ * row / the sequence or no multiple of 4, a NULL or misaligned operand (tensors: 16 bytes), tensors that overlap each other or
+ * parent / pos. */
+int lg_beam_reorder_f32(float* const* tensors, int64_t n_tensors, int64_t ldc, int64_t sbc, int64_t capacity, int64_t width,
+                        const int32_t* parent, const int32_t* pos, int64_t rows, int64_t num_beams);
 
 /* ---- two independent products in one launch ----------------------------------------------------------
  * lg_gemm_pair_begin(); <product 1>; <product 2>; lg_gemm_pair_end();   with products issued through

@@ -625,6 +625,132 @@ def _check_speculate_commit(tgt, ids, count, position_ids, out_ids, pos, end, do
 CpuTensor.speculate_commit = _speculate_commit
 
 
+def _beam_step(logits, scores, parent, token, out_ids, pos, done, stats, num_beams, eos=None):
+    """ logits.beam_step(scores, parent, token, out_ids, pos, done, stats, num_beams, eos=None): one step of beam search, in place
+    and outside the tape - the definition of the op, written as the loop it is.  Beams are rows: `rows = b * w` with w =
+    num_beams (1 .. 8), group g is rows g * w .. g * w + w - 1, best first.  logits (rows, V) or (rows, 1, V) float32 with V >= w;
+    scores (rows,) float32, the cumulative log-probability; token (rows, 1), out_ids (rows, columns), pos (rows,), done (rows,),
+    parent (rows,), stats (2,) = {groups finished, slots that changed their beam}: int32.  The floating-point part is evaluated in
+    float64 from the float32 inputs.  For each group on its own:
+      1. Any row with pos < 0, or a live row (done == 0) with pos + 1 >= columns: the group keeps every byte, parent is the
+         identity and the call raises IndexError after every other group has been committed, as the device flag of the HipTensor
+         op does at its next synchronisation.
+      2. A group whose rows are all done keeps every byte; parent is the identity.
+      3. Candidates: a live beam i with logits x offers (scores[i] + x[j] - m - log sum_k exp(x[k] - m), i, j) for every j, with
+         m = max x; a done beam offers exactly one, (scores[i], i, -), itself, at flat index i * V.
+      4. The w largest candidates, ties to the smaller flat index i * V + j, best first.
+      5. Output slot n takes candidate (s, i, j): parent[n] = g * w + i.  Beam i done: slot n becomes a copy of row i - score, token,
+         pos, done = 1, out_ids columns 0 .. pos[i].  Otherwise p = pos[i] + 1: out_ids columns 0 .. pos[i] of row i, column p = j,
+         pos = p, token = j, scores = float32(s), done = (eos is an id >= 0 and j == eos).  Columns beyond the slot's new pos keep
+         what they held.
+      6. stats[0] += 1 when the step takes the group from "some beam live" to "all done"; stats[1] += the slots with
+         parent[n] != g * w + n. """
+    rows, V, w = _check_beam_step(logits, scores, parent, token, out_ids, pos, done, stats, num_beams, eos)
+    arrays = [t.data for t in (logits, scores, parent, token, out_ids, pos, done, stats)]
+    assert not any(np.shares_memory(x, y) for i, x in enumerate(arrays) for y in arrays[i + 1:]), "beam_step: two operands overlap"
+    x_all, columns, eos = logits.data.reshape(rows, V), out_ids.shape[1], (-1 if eos is None else int(eos))
+    bad = []
+    for lo in range(0, rows, w):
+        group = slice(lo, lo + w)
+        parent.data[group] = np.arange(lo, lo + w)
+        p_old, d_old = pos.data[group].astype(np.int64), done.data[group] != 0
+        if (p_old < 0).any() or (~d_old & (p_old + 1 >= columns)).any():
+            bad.append(lo // w)
+            continue
+        if d_old.all():
+            continue
+        value, beam, tok = [], [], []
+        with np.errstate(all="ignore"):
+            for i in range(w):
+                s = np.float64(scores.data[lo + i])
+                if d_old[i]:
+                    value.append(np.array([s])), beam.append(np.array([i])), tok.append(np.array([-1]))
+                    continue
+                x = x_all[lo + i].astype(np.float64)
+                m = x.max()
+                value.append(s + (x - m - np.log(np.exp(x - m).sum())))
+                beam.append(np.full(V, i)), tok.append(np.arange(V))
+        value, beam, tok = np.concatenate(value), np.concatenate(beam), np.concatenate(tok)
+        # candidates lie in flat-index order: a stable sort by descending value leaves ties to the smaller index (NaN: last)
+        best = np.argsort(-value, kind="stable")[:w]
+        s_old, t_old, ids_old = scores.data[group].copy(), token.data[group, 0].copy(), out_ids.data[group].copy()
+        for n, c in enumerate(best):
+            i, j = int(beam[c]), int(tok[c])
+            parent.data[lo + n] = lo + i
+            out_ids.data[lo + n, :p_old[i] + 1] = ids_old[i, :p_old[i] + 1]
+            if d_old[i]:
+                scores.data[lo + n], token.data[lo + n, 0], pos.data[lo + n], done.data[lo + n] = s_old[i], t_old[i], p_old[i], 1
+            else:
+                out_ids.data[lo + n, p_old[i] + 1] = j
+                scores.data[lo + n], token.data[lo + n, 0], pos.data[lo + n] = np.float32(value[c]), j, p_old[i] + 1
+                done.data[lo + n] = 1 if eos >= 0 and j == eos else 0
+        stats.data[0] += 1 if (done.data[group] != 0).all() else 0
+        stats.data[1] += int((parent.data[group] != np.arange(lo, lo + w)).sum())
+    if bad:
+        raise IndexError("beam_step: group %d (of %d that did) holds a position outside the columns of out_ids (%d)" % (bad[0], len(bad), columns))
+
+
+def _check_beam_step(logits, scores, parent, token, out_ids, pos, done, stats, num_beams, eos):
+    """the operand shapes and dtypes of `beam_step`, on any backend; returns (rows b * w, vocabulary V, beams w)"""
+    rows = pos.shape[0] if len(pos.shape) == 1 else -1
+    V = logits.shape[-1] if len(logits.shape) in (2, 3) else -1
+    assert int(num_beams) == num_beams and 1 <= num_beams <= 8, "beam_step: num_beams is an int within 1 .. 8 (got %s)" % (num_beams,)
+    w = int(num_beams)
+    shapes = [tuple(t.shape) for t in (logits, scores, parent, token, out_ids, pos, done, stats)]
+    assert rows >= 1 and rows % w == 0 and V >= w and shapes[0] in ((rows, V), (rows, 1, V)) and shapes[1] == shapes[2] == shapes[6] == (rows,) \
+        and shapes[3] == (rows, 1) and len(out_ids.shape) == 2 and out_ids.shape[0] == rows and out_ids.shape[1] >= 1 and shapes[7] == (2,), \
+        "beam_step: logits (rows, V) or (rows, 1, V) with V >= num_beams = %d and rows a multiple of it, scores / parent / pos / done (rows,), " \
+        "token (rows, 1), out_ids (rows, columns), stats (2,) - got %s" % (w, shapes)
+    assert np.dtype(logits.dtype) == np.float32 and np.dtype(scores.dtype) == np.float32, "beam_step: logits and scores are float32"
+    assert all(np.dtype(t.dtype) == np.int32 for t in (parent, token, out_ids, pos, done, stats)), \
+        "beam_step: parent, token, out_ids, pos, done and stats are int32"
+    assert eos is None or int(eos) == eos, "beam_step: eos is an int or None"
+    return rows, V, w
+
+
+CpuTensor.beam_step = _beam_step
+
+
+def _kv_reorder(tensors, parent, pos, num_beams):
+    """ CpuTensor.kv_reorder(tensors, parent, pos, num_beams): what nn.KVCache.reorder does - the definition.  tensors: (rows,
+    capacity, width) arrays with rows = b * w; parent, pos (rows,) int32.  For each group g of w rows, L = max pos over the group
+    (within 0 .. capacity): row n of the group becomes the old row parent[n] at cache positions j < L, in every tensor; positions
+    >= L are not touched.  A parent outside its group leaves the group as it is and raises IndexError after the other groups have
+    been moved.  One `take` per tensor and group. """
+    rows, w = _check_kv_reorder(tensors, parent, pos, num_beams)
+    capacity = tensors[0].shape[1]
+    bad = []
+    for lo in range(0, rows, w):
+        src = parent.data[lo:lo + w].astype(np.int64)
+        if ((src < lo) | (src >= lo + w)).any():
+            bad.append(lo // w)
+            continue
+        L = int(np.clip(pos.data[lo:lo + w].max(), 0, capacity))
+        if L == 0 or (src == np.arange(lo, lo + w)).all():
+            continue
+        for t in tensors:
+            t.data[lo:lo + w, :L] = np.take(t.data[:, :L], src, axis=0)
+    if bad:
+        raise IndexError("kv_reorder: group %d (of %d that did) names a parent outside its own rows" % (bad[0], len(bad)))
+
+
+def _check_kv_reorder(tensors, parent, pos, num_beams):
+    """the operands of `kv_reorder`, on any backend; returns (rows, beams w)"""
+    assert int(num_beams) == num_beams and 1 <= num_beams <= 8, "kv_reorder: num_beams is an int within 1 .. 8 (got %s)" % (num_beams,)
+    w = int(num_beams)
+    assert 1 <= len(tensors) <= 64, "kv_reorder: 1 .. 64 cache tensors in one call (got %d)" % len(tensors)
+    shape = tuple(tensors[0].shape)
+    rows = shape[0] if len(shape) == 3 else -1
+    assert rows >= 1 and rows % w == 0 and all(tuple(t.shape) == shape and np.dtype(t.dtype) == np.float32 for t in tensors) \
+        and tuple(parent.shape) == tuple(pos.shape) == (rows,) and np.dtype(parent.dtype) == np.dtype(pos.dtype) == np.int32, \
+        "kv_reorder: float32 tensors of one shape (rows, capacity, width) with rows a multiple of num_beams = %d, parent and pos int32 (rows,) - got " \
+        "%s, %s, %s" % (w, [tuple(t.shape) for t in tensors], tuple(parent.shape), tuple(pos.shape))
+    return rows, w
+
+
+CpuTensor.kv_reorder = staticmethod(_kv_reorder)
+
+
 def _next_token_labels(ids, ignore_index=-100):
     """ ids.next_token_labels(ignore_index=-100): the labels of the next-token objective - `ids` shifted left by one along the last
     axis, `ignore_index` in the last column; same dtype and shape, a constant of the tape. """

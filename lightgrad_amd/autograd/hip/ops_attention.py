@@ -659,3 +659,68 @@ def speculate_commit(tgt, ids, count, position_ids, out_ids, pos, end, done, sta
 
 
 HipTensor.speculate_commit = speculate_commit
+
+
+""" Beam search between two decode forwards in two launches (csrc/beam.hip) """
+
+
+def beam_step(logits, scores, parent, token, out_ids, pos, done, stats, num_beams, eos=None):
+    """ logits.beam_step(scores, parent, token, out_ids, pos, done, stats, num_beams, eos=None): what `CpuTensor.beam_step` defines
+    - per group of num_beams rows the best num_beams of its continuations (a live beam offers score + log_softmax(logits), a done
+    beam itself), ties to the smaller flat index, committed to scores, token, pos, done, parent and the rows of out_ids - in ONE
+    launch (lg_beam_step_f32), in place and outside the tape.  logits and out_ids may have any row pitch, every other operand is
+    dense; no two operands overlap.  A group with a position out of bounds keeps its bytes and raises IndexError at the next
+    synchronisation.  No host read: a captured step replays it as it stands. """
+    from ..cpu.ops import _check_beam_step
+    name = "beam_step"
+    operands = (logits, scores, parent, token, out_ids, pos, done, stats)
+    assert all(isinstance(t, HipTensor) for t in operands), "%s: every operand is a HipTensor" % name
+    rows, V, w = _check_beam_step(*operands, num_beams, eos)
+    columns = out_ids._shape[1]
+    # what is only read may be copied once into a layout the launch addresses
+    if (V > 1 and logits._strides[-1] != 1) or (rows > 1 and logits._strides[0] < V):
+        logits = logits.contiguous()
+    # the launch writes these where they lie: a layout it cannot address is an error, never a copy
+    assert all(t.is_contiguous() for t in (scores, parent, token, pos, done, stats)) and (columns == 1 or out_ids._strides[1] == 1) \
+        and (rows == 1 or out_ids._strides[0] >= columns), \
+        "%s: scores, parent, token, pos, done and stats must be dense and the rows of out_ids contiguous" % name
+    operands = (logits, scores, parent, token, out_ids, pos, done, stats)
+    for i, x in enumerate(operands):
+        for y in operands[i + 1:]:
+            assert not _shares_bytes(x, y), "%s: two operands overlap" % name
+    for x in operands[1:]:
+        flush_lazy_readers(x)
+    _l.check(_l.lib().lg_beam_step_f32(logits.ptr, logits._strides[0] if rows > 1 else V, scores.ptr, parent.ptr, token.ptr, out_ids.ptr,
+                                       out_ids._strides[0] if rows > 1 else columns, columns, pos.ptr, done.ptr, stats.ptr, rows, V, w,
+                                       -1 if eos is None else int(eos)))
+
+
+HipTensor.beam_step = beam_step
+
+
+def kv_reorder(tensors, parent, pos, num_beams):
+    """ HipTensor.kv_reorder(tensors, parent, pos, num_beams): what `CpuTensor.kv_reorder` defines - in every (rows, capacity,
+    width) tensor row n of each group of num_beams rows becomes the old row parent[n] at the cache positions below the group's
+    largest `pos` - in ONE launch for all tensors (lg_beam_reorder_f32), in place.  Dense float32 HipTensors of one shape (at most
+    64, width a multiple of 4) that overlap neither each other nor parent / pos.  A parent outside its group leaves the group as it
+    is and raises IndexError at the next synchronisation.  No host read: a captured step replays it as it stands. """
+    from ..cpu.ops import _check_kv_reorder
+    name = "kv_reorder"
+    tensors = list(tensors)
+    assert all(isinstance(t, HipTensor) for t in tensors + [parent, pos]), "%s: every operand is a HipTensor" % name
+    rows, w = _check_kv_reorder(tensors, parent, pos, num_beams)
+    _, capacity, width = tensors[0]._shape
+    assert width % 4 == 0, "%s: the cache's width %d is no multiple of 4" % (name, width)
+    # the launch moves rows where they lie: a layout it cannot address is an error, never a copy
+    assert all(t.is_contiguous() for t in tensors) and parent.is_contiguous() and pos.is_contiguous(), "%s: every operand must be dense" % name
+    for i, x in enumerate(tensors):
+        assert not _shares_bytes(x, parent) and not _shares_bytes(x, pos), "%s: parent / pos overlap a cache tensor" % name
+        for y in tensors[i + 1:]:
+            assert not _shares_bytes(x, y), "%s: two cache tensors overlap" % name
+        flush_lazy_readers(x)
+    assert not _shares_bytes(parent, pos), "%s: parent and pos overlap" % name
+    table = (ctypes.c_void_p * len(tensors))(*[t.ptr for t in tensors])
+    _l.check(_l.lib().lg_beam_reorder_f32(table, len(tensors), width, capacity * width, capacity, width, parent.ptr, pos.ptr, rows, w))
+
+
+HipTensor.kv_reorder = staticmethod(kv_reorder)

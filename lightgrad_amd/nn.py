@@ -300,6 +300,10 @@ class KVCache(object):
     every row's position - what the routing between prefill and decode step and the capacity checks need, never an index.
     Rejected drafts (speculative decoding: `speculate_commit`) leave key and value rows in the cache beyond the new position.
     Nothing reads beyond the position, and the next step overwrites them.
+    Beam search keeps the beams of a prompt in `num_beams` neighbouring rows (a group; `num_beams` is an attribute, 1 unless the
+    caller sets it, and `batch` is a multiple of it).  `reorder(parent)` makes the rows follow the beams that survived a
+    `beam_step`: row n of a group becomes the old row parent[n] (an absolute row index inside the same group; duplicates are the
+    normal case) at the positions below the group's largest `pos`; what lies at or beyond it is not touched, and nothing reads it.
     Without `per_row` every attribute, shape and launch is as it was."""
 
     def __init__(self, layers: int, batch: int, capacity: int, width: int, like=None, per_row: bool = False):
@@ -315,6 +319,18 @@ class KVCache(object):
         self.length = 0
         self.lengths = np.zeros(self.batch, np.int64) if self.per_row else None
         self._arange = {}           # m -> the int32 constant 0 .. m - 1 on the cache's backend
+        self.num_beams = 1          # rows per group of `reorder`
+
+    def reorder(self, parent, num_beams=None) -> None:
+        """per_row: the rows follow their beams.  parent: int32 (batch,) on the cache's backend; for every layer and for both k and v,
+        row n of each group of `num_beams` rows (default: the attribute) becomes the old row parent[n] at the cache positions
+        j < max(pos) of the group - the positions as they are now, after `beam_step`; positions beyond are not touched.  One op of
+        the backend for all 2 * layers tensors (`kv_reorder`: on HipTensor one launch, in place).  Neither the positions nor the
+        host mirror change."""
+        assert self.per_row, "KVCache.reorder goes with per_row=True"
+        w = self.num_beams if num_beams is None else int(num_beams)
+        assert 1 <= w <= 8 and self.batch % w == 0, "KVCache.reorder: %d rows are no groups of num_beams = %d (1 .. 8)" % (self.batch, w)
+        type(self.pos).kv_reorder(self.k + self.v, parent, self.pos, w)
 
     def positions(self, m: int):
         """the int32 position ids `pos + arange(m)` of the next m tokens, shape (m,): one broadcast add on the cache's backend -
