@@ -46,6 +46,10 @@ Differences from the reference, on purpose:
                                                        # go on decoding; one attention launch per layer for all of them (a token count
                                                        # per slot, csrc/extend.hip), one launch of bookkeeping per step (csrc/serve.hip),
                                                        # one word read back every few steps; --graph: the step is captured once
+    python examples/bert.py --serve 16 --slots 4 --chunk 16 --token-budget 24 [--graph] [--cpu]
+                                                       # the same through TOKEN-PACKED steps: every step has 24 token rows for all slots
+                                                       # together - one per decoding slot, the rest shared by the prefilling slots in
+                                                       # pieces of at most 16 (`serve(token_budget=)`, csrc/serve_packed.hip)
     python examples/bert.py --mlm --bf16-decoder       # the decoder onto the vocabulary (forward, dx, dW) on the bf16 matrix cores:
                                                        # config key `decoder_precision="bf16"`; tensors stay float32
 """
@@ -252,6 +256,42 @@ class BertSelfAttention(nn.Module):
         context = (probs @ v).transpose(0, 2, 1, 3).reshape(b, m, self.h * self.d)
         return context * constant(real.reshape(b, m, 1)), probs * constant(real.reshape(b, 1, m, 1))
 
+    def _packed_composite(self, hidden, attention_mask, cache, index, cu):
+        """a TOKEN-PACKED step over the tensor API - the definition of `self_attention_extend(cu=)`: `hidden` (1, T, hidden) holds the
+        step's tokens of all cache slots, slot s owns rows cu[s] .. cu[s + 1] - 1.  Every slot with a row is computed as
+        `_rows_composite` computes it alone on its rows, against its own cache rows at its own position; the rows behind
+        cu[slots], which belong to nobody, are 0 in the context.  Positions and cu are read from the tensors (whoever moved
+        them: `serve_commit_packed`)"""
+        T, slots = hidden.shape[1], cache.batch
+        k_cache, v_cache = cache.k[index], cache.v[index]
+        t, c = np.asarray(cache.pos.numpy(), np.int64), np.asarray(cu.numpy(), np.int64)
+        n = np.diff(c)
+        assert hidden.shape[0] == 1 and c.shape == (slots + 1,) and c[0] >= 0 and (n >= 0).all() and c[-1] <= T and (t >= 0).all() \
+            and (t + n <= cache.capacity).all(), \
+            "the cache holds %s of %d positions: no room for the rows %s of the %d given" % (t.tolist(), cache.capacity, c.tolist(), T)
+        q, k, v = self.query(hidden), self.key(hidden), self.value(hidden)
+        context = hidden.__class__.from_numpy(np.zeros((1, T, self.h * self.d), dtype=q.dtype), requires_grad=False)
+        for s in range(slots):
+            if n[s] == 0:
+                continue
+            lo, hi, ts, m = int(c[s]), int(c[s + 1]), int(t[s]), int(n[s])
+            keys = ts + m
+            k_cache[s:s + 1, ts:keys] = k[:, lo:hi]
+            v_cache[s:s + 1, ts:keys] = v[:, lo:hi]
+            qs = q[:, lo:hi].reshape(1, m, self.h, self.d).transpose(0, 2, 1, 3)
+            ks = k_cache[s:s + 1, :keys].reshape(1, keys, self.h, self.d).transpose(0, 2, 3, 1)
+            vs = v_cache[s:s + 1, :keys].reshape(1, keys, self.h, self.d).transpose(0, 2, 1, 3)
+            scores = (qs @ ks) / math.sqrt(self.d)
+            if attention_mask is not None:
+                mask = attention_mask[s:s + 1, :keys] if attention_mask.shape[0] > 1 else attention_mask[:, :keys]
+                scores = scores + ((1.0 - mask.reshape(1, 1, 1, keys)) * -10000.0).detach()
+            # (1, 1, m, keys): key j is visible to query i where j <= t + i
+            visible = (np.arange(keys)[None, :] <= (ts + np.arange(m))[:, None]).astype(scores.dtype)
+            visible = scores.__class__.from_numpy(visible.reshape(1, 1, m, keys), requires_grad=False)
+            scores = scores + ((1.0 - visible) * -10000.0).detach()
+            context[:, lo:hi] = (scores.softmax(axis=-1) @ vs).transpose(0, 2, 1, 3).reshape(1, m, self.h * self.d)
+        return context, None
+
     def _triangle_behind(self, like, t, m):
         """rows t .. t + m - 1 of the lower-triangular constant of t + m positions, (1, 1, m, t + m): query t + i sees keys 0 .. t + i"""
         key = (like.__class__, t, m, np.dtype(like.dtype))
@@ -262,14 +302,32 @@ class BertSelfAttention(nn.Module):
             self._tril[key] = tri
         return self._tril[key]
 
-    def _extend(self, hidden, attention_mask, cache, index, count=None):
+    def _extend(self, hidden, attention_mask, cache, index, count=None, cu=None):
         """m new tokens per sequence behind the cache's position t (any t >= 0): query row i at position t + i attends to keys
         0 .. t + i - the rows the causal forward computes for queries t .. t + m - 1.  attention_mask: None or (b, capacity) over
         the cache's rows.  count: None, or an int32 tensor (b,) next to a cache with a position per sequence - sequence r has
         count[r] real tokens among its m rows (a step that mixes decoding, prefilling and idle sequences): the fused route passes
-        it to the launch as it is, the composite reads it"""
+        it to the launch as it is, the composite reads it.  cu: None, or an int32 tensor (slots + 1,) - the step is token-packed:
+        `hidden` is (1, T, hidden), the tokens of all `cache.batch` slots, slot s owning rows cu[s] .. cu[s + 1] - 1
+        (`_packed_composite` is the definition; the fused route is one projection launch on the T rows and one attention launch)"""
         counted = {} if count is None else {"count": count}
         assert count is None or getattr(cache, "per_row", False), "count= takes a cache with a position per sequence: nn.KVCache(..., per_row=True)"
+        if cu is not None:
+            assert count is None, "cu= (token-packed rows) and count= (a count per batch row) exclude each other"
+            assert getattr(cache, "per_row", False), "cu= takes a cache with a position per sequence: nn.KVCache(..., per_row=True)"
+            assert hidden.shape[0] == 1 and tuple(cu.shape) == (cache.batch + 1,), \
+                "cu= goes with token rows (1, T, hidden) and %d + 1 words, got %s and %s" % (cache.batch, tuple(hidden.shape), tuple(cu.shape))
+            m_max = min(hidden.shape[1], cache.capacity)
+            mask_ok = attention_mask is None or (attention_mask.dtype == np.float32 and not attention_mask.requires_grad and
+                                                 tuple(attention_mask.shape) in ((cache.batch, cache.capacity), (1, cache.capacity)))
+            if hasattr(hidden, "self_attention_extend") and mask_ok and \
+                    hidden.self_attention_extend_supported(self.query.weight, self.h, cache.capacity, m_max):
+                extra = {"mask": attention_mask} if attention_mask is not None else {}
+                context = hidden.self_attention_extend(self.query.weight, self.query.bias, self.key.weight, self.key.bias, self.value.weight,
+                                                       self.value.bias, cache.k[index], cache.v[index], cache.pos, heads=self.h,
+                                                       scale=math.sqrt(self.d) ** -1, cu=cu, m_max=m_max, **extra)
+                return context, None
+            return self._packed_composite(hidden, attention_mask, cache, index, cu)
         b, m = hidden.shape[0], hidden.shape[1]
         scale = math.sqrt(self.d) ** -1
         k_cache, v_cache = cache.k[index], cache.v[index]
@@ -302,14 +360,15 @@ class BertSelfAttention(nn.Module):
         probs = scores.softmax(axis=-1)
         return (probs @ v).transpose(0, 2, 1, 3).reshape(b, m, self.h * self.d), probs
 
-    def forward(self, hidden, attention_mask=None, cache=None, index=None, append=False, count=None):
+    def forward(self, hidden, attention_mask=None, cache=None, index=None, append=False, count=None, cu=None):
         """cache (nn.KVCache) and index (this layer's): with tokens in the cache, `hidden` is one new token per sequence (`_decode`);
         with an empty one, the prompt takes the path below and its keys and values become the cache's first rows.  append=True:
-        `hidden` is m >= 1 new tokens per sequence behind whatever the cache holds (`_extend`), count= its tokens per sequence"""
-        assert count is None or (cache is not None and append), "count= goes with cache= and append=True"
+        `hidden` is m >= 1 new tokens per sequence behind whatever the cache holds (`_extend`), count= its tokens per sequence, or
+        - cu= - the token-packed rows of all cache slots"""
+        assert (count is None and cu is None) or (cache is not None and append), "count= and cu= go with cache= and append=True"
         if cache is not None and append:
             assert self.causal, "appending to a cache takes a causal model"
-            return self._extend(hidden, attention_mask, cache, index, **({} if count is None else {"count": count}))
+            return self._extend(hidden, attention_mask, cache, index, **({} if count is None else {"count": count}), **({} if cu is None else {"cu": cu}))
         if cache is not None and cache.length > 0:
             assert self.causal and hidden.shape[1] == 1, "a decode step is one token per sequence of a causal model"
             return self._decode(hidden, attention_mask, cache, index)
@@ -385,12 +444,12 @@ class BertAttention(nn.Module):
         self.output.dense = nn.Linear(hidden_size, hidden_size)
         self.output.LayerNorm = nn.LayerNorm(hidden_size)
 
-    def forward(self, hidden_in, attention_mask=None, cache=None, index=None, append=False, count=None):
+    def forward(self, hidden_in, attention_mask=None, cache=None, index=None, append=False, count=None, cu=None):
         if cache is None:
             hidden, probs = self.self(hidden_in, attention_mask=attention_mask)
         elif append:
             hidden, probs = self.self(hidden_in, attention_mask=attention_mask, cache=cache, index=index, append=True,
-                                      **({} if count is None else {"count": count}))
+                                      **({} if count is None else {"count": count}), **({} if cu is None else {"cu": cu}))
         else:
             hidden, probs = self.self(hidden_in, attention_mask=attention_mask, cache=cache, index=index)
         if self.training and self.dropout.p > 0:
@@ -417,11 +476,12 @@ class BertLayer(nn.Module):
         self.output.dense = nn.Linear(intermediate_size, hidden_size)
         self.output.LayerNorm = nn.LayerNorm(hidden_size)
 
-    def forward(self, hidden, attention_mask=None, cache=None, index=None, append=False, count=None):
+    def forward(self, hidden, attention_mask=None, cache=None, index=None, append=False, count=None, cu=None):
         if cache is None:
             hidden, probs = self.attention(hidden, attention_mask)
         elif append:
-            hidden, probs = self.attention(hidden, attention_mask, cache=cache, index=index, append=True, **({} if count is None else {"count": count}))
+            hidden, probs = self.attention(hidden, attention_mask, cache=cache, index=index, append=True, **({} if count is None else {"count": count}),
+                                           **({} if cu is None else {"cu": cu}))
         else:
             hidden, probs = self.attention(hidden, attention_mask, cache=cache, index=index)
         if self.training and self.dropout.p > 0:
@@ -453,10 +513,13 @@ class BertModel(nn.Module):
                                                        attention_probs_dropout_prob, causal=causal)
                                              for _ in range(num_hidden_layers)])
 
-    def forward(self, input_ids, attention_mask=None, token_type_ids=None, cache=None, append=False, count=None, token_positions=None):
-        assert (count is None and token_positions is None) or (cache is not None and append), "count= and token_positions= go with cache= and append=True"
+    def forward(self, input_ids, attention_mask=None, token_type_ids=None, cache=None, append=False, count=None, token_positions=None, cu=None):
+        assert (count is None and token_positions is None and cu is None) or (cache is not None and append), \
+            "count=, cu= and token_positions= go with cache= and append=True"
         if cache is not None:
             if append:
+                if cu is not None:
+                    return self._forward_packed(input_ids, attention_mask, token_type_ids, cache, count, token_positions, cu)
                 return self._forward_append(input_ids, attention_mask, token_type_ids, cache, count, token_positions)
             return self._forward_cached(input_ids, attention_mask, token_type_ids, cache)
         assert not append, "append=True goes with a cache"
@@ -507,6 +570,28 @@ class BertModel(nn.Module):
                 hidden, _ = layer(hidden, attention_mask=attention_mask, cache=cache, index=index, append=True)
         return hidden
 
+    def _forward_packed(self, input_ids, attention_mask, token_type_ids, cache, count, token_positions, cu):
+        """`_forward_append` for a TOKEN-PACKED step: `input_ids` (1, T) are the step's tokens of all `cache.batch` slots and cu
+        (int32 (slots + 1,)) says whose they are - slot s owns rows cu[s] .. cu[s + 1] - 1, behind its own position; rows
+        >= cu[slots] belong to nobody.  token_positions (int32 (1, T)) are the position ids to embed at (nn.RequestPool's: 0 where
+        a row holds no token).  Embeddings, Linears, LayerNorms and the feed-forward block run on T rows, whatever the slots
+        hold; attention_mask: None, or (slots, capacity) over the cache's rows.  Every one of the T rows comes back; the caller
+        moves the positions on (`serve_commit_packed`)"""
+        assert count is None, "cu= (token-packed rows) and count= (a count per batch row) exclude each other"
+        assert getattr(cache, "per_row", False), "cu= takes a cache with a position per sequence: nn.KVCache(..., per_row=True)"
+        positions = self.embeddings.position_embeddings.weight.shape[0]
+        assert len(input_ids.shape) == 2 and input_ids.shape[0] == 1 and input_ids.shape[1] >= 1, \
+            "a token-packed step takes ids of shape (1, T), got %s" % (tuple(input_ids.shape),)
+        assert cache.layers == len(self.encoder.layer) and tuple(cu.shape) == (cache.batch + 1,), \
+            "the cache was made for %d layers and %d slots: cu has slots + 1 words, got %s" % (cache.layers, cache.batch, tuple(cu.shape))
+        assert token_positions is not None and tuple(token_positions.shape) == tuple(input_ids.shape) and cache.capacity <= positions, \
+            "a token-packed step takes token_positions= of the ids' shape (1, T), and a cache within the %d position embeddings" % positions
+        with light.no_grad():
+            hidden = self.embeddings(input_ids, token_type_ids=token_type_ids, token_positions=token_positions)
+            for index, layer in enumerate(self.encoder.layer):
+                hidden, _ = layer(hidden, attention_mask=attention_mask, cache=cache, index=index, append=True, cu=cu)
+        return hidden
+
     def _forward_cached(self, input_ids, attention_mask, token_type_ids, cache):
         """inference with an nn.KVCache, outside the tape.  An empty cache: `input_ids` (b, s0) is the prompt - the causal forward
         as without a cache (attention_mask: None or (b, s0)), whose keys and values fill rows 0 .. s0 - 1 of every layer's cache
@@ -545,7 +630,7 @@ class BertForMaskedLM(nn.Module):
         self.cls.predictions.bias = light.zeros(vocab_size)
 
     def forward(self, input_ids, attention_mask=None, token_type_ids=None, masked_positions=None, cache=None, append=False, count=None,
-                token_positions=None):
+                token_positions=None, cu=None):
         if cache is not None:
             # inference through an nn.KVCache (BertModel._forward_cached, append=True: _forward_append): the logits of every row
             # given, outside the tape
@@ -554,6 +639,8 @@ class BertForMaskedLM(nn.Module):
                 extra["count"] = count
             if token_positions is not None:
                 extra["token_positions"] = token_positions
+            if cu is not None:
+                extra["cu"] = cu
             h = self.bert(input_ids=input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids, cache=cache, **extra)
             with light.no_grad():
                 return self.head(h)
@@ -1144,15 +1231,20 @@ def serve_step(model, pool, sampler=None, eos=None):
     ids go through the append forward with the pool's token count per slot - a decoding slot has 1 real token, a prefilling one
     up to `chunk`, an idle one none -, ONE gather takes each slot's last real row to the head, and ONE `serve_commit` stores the
     tokens drawn for the decoding slots, frees the slots whose request has finished, admits waiting requests to them and lays
-    out the next step's ids.  No host read, no value from the host: a captured step replays as it stands."""
-    hidden = model.bert(pool.ids, cache=pool.cache, append=True, count=pool.count, token_positions=pool.position_ids)
+    out the next step's ids.  No host read, no value from the host: a captured step replays as it stands.
+    With a pool that has a token budget (`pool.cu`) the step is token-packed: the pool's (1, T) ids go through the append forward
+    with `cu=`, T rows whatever the slots hold; gather, head, draw and commit (`serve_commit_packed`) follow as above."""
+    if pool.cu is not None:
+        hidden = model.bert(pool.ids, cache=pool.cache, append=True, cu=pool.cu, token_positions=pool.position_ids)
+    else:
+        hidden = model.bert(pool.ids, cache=pool.cache, append=True, count=pool.count, token_positions=pool.position_ids)
     width = hidden.shape[-1]
     rows = hidden.reshape(-1, width)[pool.last].reshape(pool.slots, 1, width)
     pool.commit(next_token(model.head(rows), sampler), eos=eos)
 
 
 def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, pad_token_id=0, graph=None, temperature=None, top_k=0,
-          top_p=1.0, poll=8, lengths=None, cache=None):
+          top_p=1.0, poll=8, lengths=None, cache=None, token_budget=None):
     """continuous batching: N requests through `slots` cache slots, a finished slot refilled at once from the queue while the
     others go on decoding.  prompts: a list of N int sequences, or (N, P) right-padded ids (an array or a tensor) with lengths=;
     max_new_tokens: an int, or N ints - a budget per request.  Returns (out (N, G) int32 with G = the largest budget, filled with
@@ -1169,7 +1261,12 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
     Greedy results depend on a request's own data only: not on slots, chunk or the order of admission.  With a temperature every
     step takes ONE call of the random stream for all slots, idle ones included, and a slot's numbers depend on its index: a
     sampled run is reproducible for a given seed, slots and chunk (eager or captured), but NOT independent of the schedule.
-    cache: an nn.KVCache(per_row=True) of `slots` rows to use (default: one whose capacity is the longest request's need)."""
+    cache: an nn.KVCache(per_row=True) of `slots` rows to use (default: one whose capacity is the longest request's need).
+    token_budget: None, or T >= slots - every step is TOKEN-PACKED: it has T token rows for all slots together in place of
+    (slots, chunk) rows.  A decoding slot takes one row; the rows left go to the prefilling slots in slot order, in pieces of at
+    most `chunk` (chunked prefill under a per-step token budget; csrc/serve_packed.hip, the packed launch of csrc/extend.hip).
+    Eight decoding slots cost 8 rows of every Linear, not 8 * chunk.  Greedy results are the same tokens; `stats` gains
+    `token_budget`.  Without it everything is as it was."""
     weight = model.bert.embeddings.word_embeddings.weight
     cls = weight.__class__
     layer0 = model.bert.encoder.layer[0].attention.self
@@ -1192,10 +1289,13 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
         cache = nn.KVCache(len(model.bert.encoder.layer), int(slots), int((lengths + budgets - 1).max()), layer0.h * layer0.d, like=weight, per_row=True)
     assert cache.batch == slots, "serve: the cache has %d rows for %d slots" % (cache.batch, slots)
     chunk = min(int(chunk), cache.capacity)                 # (a piece never exceeds the cache; the results do not depend on it)
-    pool = nn.RequestPool(cache, padded, lengths, budgets, chunk, pad_token_id=pad_token_id, max_positions=positions)
+    assert token_budget is None or (int(token_budget) == token_budget and token_budget >= slots), \
+        "serve: token_budget is a number of token rows >= slots = %d (every decoding slot gets its token), got %s" % (slots, token_budget)
+    packed = {} if token_budget is None else {"token_budget": int(token_budget)}
+    pool = nn.RequestPool(cache, padded, lengths, budgets, chunk, pad_token_id=pad_token_id, max_positions=positions, **packed)
     eos = None if eos_token_id is None else int(eos_token_id)
     sampler = None if temperature is None else (temperature, top_k, top_p)
-    stats = {"steps": 0, "requests": n, "slots": int(slots), "chunk": chunk}
+    stats = {"steps": 0, "requests": n, "slots": int(slots), "chunk": chunk, **packed}
 
     def done():
         # the poll: one word read every `poll` steps, and at the step count no schedule exceeds (every request alone in turn)
@@ -1245,11 +1345,14 @@ if __name__ == "__main__":
             sampling = dict(temperature=option("--temperature", float, 1.0), top_k=option("--top-k", int, 0), top_p=option("--top-p", float, 1.0))
             light.manual_seed(option("--seed", int, 0))
         t0 = time.perf_counter()
+        if "--token-budget" in sys.argv:
+            sampling["token_budget"] = option("--token-budget", int, None)
         (tokens, counts), info = serve(lm, requests, new, slots=n_slots, chunk=piece, eos_token_id=option("--eos", int, None), graph=recorded, **sampling)
         tokens, counts = tokens.numpy(), counts.numpy()             # the first read of anything but the poll word
         seconds = time.perf_counter() - t0
-        print("%d requests (prompts of %d .. %d tokens, budgets of %d .. %d) through %d slots in pieces of %d: %d steps, %d tokens in %.1f ms (%s)" % (
-            n_requests, min(map(len, requests)), max(map(len, requests)), min(new), max(new), n_slots, info["chunk"], info["steps"], int(counts.sum()),
+        print("%d requests (prompts of %d .. %d tokens, budgets of %d .. %d) through %d slots in pieces of %d%s: %d steps, %d tokens in %.1f ms (%s)" % (
+            n_requests, min(map(len, requests)), max(map(len, requests)), min(new), max(new), n_slots, info["chunk"],
+            " under a budget of %d token rows a step" % info["token_budget"] if "token_budget" in info else "", info["steps"], int(counts.sum()),
             1e3 * seconds, "step captured once, %d kernels" % recorded.kernel_count() if recorded else "eager steps"))
         for r in range(min(n_requests, 8)):
             print("request %d: %s" % (r, " ".join(str(i) for i in tokens[r, :counts[r]])))

@@ -742,6 +742,52 @@ int lg_serve_commit_i32(const int32_t* nxt, int64_t nxt_pitch,       /* the toke
                         int32_t* ids, int32_t* position_ids,         /* (slots, m) dense each */
                         int32_t* last,                               /* (slots) */
                         int64_t slots, int64_t m, int64_t capacity, int32_t eos_id);   /* eos_id < 0: none */
+/* ---- token-packed serving steps: one flat token budget for all slots (csrc/extend.hip, serve_packed.hip) -------------------------
+ * lg_attention_extend_packed_f32: the step's tokens of ALL cache slots lie in flat operands of T rows (q, k_new, v_new, o: row i
+ * at x + i * ld, no batch pitch; p NULL or (heads, T, capacity) dense), and `cu`, slots + 1 int32 words in device memory, says
+ * whose they are: slot z owns rows cu[z] .. cu[z + 1] - 1, n = cu[z + 1] - cu[z] of them, at most m_max; rows cu[slots] .. T - 1
+ * belong to nobody.  The caches (slots, capacity, heads * D), pos (slots words) and the mask are addressed by the slot as the
+ * `_rows` entry addresses them by the batch element.  It is the `_rows` kernel with the slot's first row in place of a batch
+ * pitch, grid (ceil(m_max / 32), heads, slots + 1):
+ *   - slot z with t = pos[z]: its context rows, its rows of p (exact +0.0 beyond column t + i of row cu[z] + i) and cache rows
+ *     t .. t + n - 1 are bit for bit what lg_attention_extend_rows_f32 gives for it alone at batch 1 with m = n on those rows; no
+ *     other cache row is written; a workgroup whose 32 query rows start at or beyond n returns before any load;
+ *   - the last slice of the grid sets rows cu[slots] .. T - 1 of o and of p (if given) to +0.0;
+ *   - a slot with cu[z] < 0, n < 0, n > m_max, cu[z + 1] > T, t < 0 or t + n > capacity raises the status flag (LG_EINDEX at the
+ *     next lg_sync / lg_memcpy_d2h) and writes nothing, the others are computed; cu[slots] outside 0 .. T: the flag, and the
+ *     clearing slice writes nothing.
+ * Supported: D = 32 or 64, 1 <= m_max <= capacity <= 512, 1 <= T < 2^30 (T may exceed the capacity), slots <= 65534.  Host
+ * refusals (LG_EINVAL) as for the `_counts` entry, with cu in place of count: cu NULL, misaligned, overlapping a cache, pos, q,
+ * k_new, v_new, o or p. */
+int lg_attention_extend_packed_f32(const float* q, int64_t ldq, const float* k_new, int64_t ldk, const float* v_new, int64_t ldv,   /* (T, heads*D) rows */
+                                   float* k_cache, float* v_cache, int64_t ldc, int64_t sbc,   /* (slots, capacity, heads*D) */
+                                   const int32_t* pos,               /* `slots` words: the position of each slot's new token 0 */
+                                   const int32_t* cu,                /* `slots + 1` words: the first row of each slot, then the rows in use */
+                                   float* o, int64_t ldo,            /* context (T, heads*D) */
+                                   float* p,                         /* NULL, or probabilities (heads, T, capacity), dense */
+                                   int64_t slots, int64_t heads, int64_t T, int64_t m_max, int64_t capacity, int64_t D, float scale,
+                                   const float* mask, int64_t sbm);  /* key-padding mask (slots, capacity); sbm = 0: one row for all */
+/* lg_serve_commit_packed_i32: lg_serve_commit_i32 for a token-packed step of T rows, T >= slots (csrc/serve_packed.hip).  The
+ * definition is the loop of `CpuTensor.serve_commit_packed` (autograd/cpu/ops.py).  Steps (1) and (2) are those of
+ * lg_serve_commit_i32 with m = chunk and give every slot its request r, its position t and the tokens it WANTS: min(chunk,
+ * prompt_len[r] - t) of its prompt (a prefilling slot, a slot just admitted included), the one token just drawn (a decoding
+ * slot), or none.  (3) The budget: a decoding slot gets its token; with R = T - (decoding slots), the prefilling slots take
+ * n = min(want, what is left of R) in slot order.  A prefilling slot granted 0 keeps its request and its position, gets
+ * count = 0 and asks again in the next step.  (4) cu = the exclusive sum of the n in slot order, cu[slots] = their total;
+ * req[s] = r, pos[s] = t, count[s] = n, ids[cu[s] + i] = token i of the slot, position_ids[cu[s] + i] = t + i, both 0 in rows
+ * >= cu[slots]; last[s] = min(cu[s] + max(n - 1, 0), T - 1).  A slot that would leave its bounds (those of lg_serve_commit_i32,
+ * with t + want > capacity) raises the status flag, gets count[s] = 0, takes no rows - it counts neither as decoding nor as
+ * prefilling - and nothing else of it is written.  One workgroup, one thread per slot; three exclusive sums in slot order (free
+ * slots, prefill wants, grants).  Refused (LG_EINVAL): as lg_serve_commit_i32, T < slots, chunk < 1, cu among the operands that
+ * must not overlap.  ids and position_ids are dense (T), cu dense (slots + 1). */
+int lg_serve_commit_packed_i32(const int32_t* nxt, int64_t nxt_pitch, const int32_t* prompts, int64_t prompt_pitch, int64_t P,
+                               const int32_t* prompt_len, const int32_t* budget, int32_t* out, int64_t out_pitch, int64_t G,
+                               int32_t* out_len, int32_t* queue, int64_t N,
+                               int32_t* req, int32_t* pos, int32_t* count,   /* (slots) each */
+                               int32_t* cu,                          /* (slots + 1) */
+                               int32_t* ids, int32_t* position_ids,  /* (T) dense each */
+                               int32_t* last,                        /* (slots) */
+                               int64_t slots, int64_t T, int64_t chunk, int64_t capacity, int32_t eos_id);   /* eos_id < 0: none */
 /* The bookkeeping of one step of speculative decoding by prompt lookup in one launch (csrc/speculate.hip): one workgroup of 256
  * threads per row, 1 <= batch < 2^24.  The definition is the loop of `CpuTensor.speculate_commit` (autograd/cpu/ops.py), for each
  * row r on its own: (1) done[r] != 0: count[r] = 0, nothing else.  (2) c = count[r], p = pos[r]; unless 1 <= c <= m, p >= 0 and

@@ -535,6 +535,109 @@ def _check_serve_commit(nxt, prompts, prompt_len, budget, out, out_len, queue, r
 CpuTensor.serve_commit = _serve_commit
 
 
+def _serve_commit_packed(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, cu, ids, position_ids, last, capacity, chunk, eos=None):
+    """ nxt.serve_commit_packed(prompts, prompt_len, budget, out, out_len, queue, req, pos, count, cu, ids, position_ids, last,
+    capacity, chunk, eos=None): `serve_commit` for a TOKEN-PACKED step, in place and outside the tape - the definition of the op,
+    written as the loops it is.  The step has T token rows for all slots together, the token budget: ids and position_ids are
+    (1, T) with T >= b, cu is (b + 1,) and slot s owns rows cu[s] .. cu[s + 1] - 1; every other operand is `serve_commit`'s.
+      1., 2. For slot s = 0 .. b - 1 in this order, steps 1 and 2 of `serve_commit` with m = chunk: the slot's request r, its
+         position t and the tokens it WANTS - min(chunk, prompt_len[r] - t) of its prompt (a prefilling slot, one just admitted
+         included), the one token just drawn (a decoding slot), none (a free slot nobody waits for: r = -1, t = 0).
+      3. The budget.  Every decoding slot gets its token: n = 1.  With R = T - the number of decoding slots, the prefilling slots
+         take n = min(want, what is left of R) in slot order.  A prefilling slot granted 0 keeps its request and its position: it
+         gets count 0 and asks again in the next step (if any slot prefills, R >= 1: some slot moves on).
+      4. cu = the exclusive sum of the n in slot order, cu[b] = their total; req[s] = r, pos[s] = t, count[s] = n; rows cu[s] + i
+         of ids / position_ids = token i of the slot / t + i; the rows >= cu[b] get id 0 and position 0;
+         last[s] = min(cu[s] + max(n - 1, 0), T - 1) (an idle slot behind a full buffer must not name row T).
+    A slot that would leave its bounds - those of `serve_commit`, with t + want > capacity - gets count[s] = 0, takes no rows (it
+    counts neither as decoding nor as prefilling) and nothing else of it (req, pos, last) is written; the call raises IndexError
+    after every other slot has been committed. """
+    b, T, N = _check_serve_commit_packed(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, cu, ids, position_ids, last, capacity,
+                                         chunk, eos)
+    arrays = [t.data for t in (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, cu, ids, position_ids, last)]
+    assert not any(np.shares_memory(x, y) for i, x in enumerate(arrays) for y in arrays[i + 1:]), "serve_commit_packed: two operands overlap"
+    new, P, G = nxt.data.reshape(b), prompts.shape[1], out.shape[1]
+    eos, capacity, chunk = (-1 if eos is None else int(eos)), int(capacity), int(chunk)
+    slots, bad = [], []
+    for s in range(b):
+        r, t, n, row, fault, decoding = int(req.data[s]), 0, 0, (), False, False
+        if r >= 0:
+            t = int(pos.data[s]) + int(count.data[s])
+            if r >= N or t < 0 or t > capacity:
+                fault = True
+            elif t < int(prompt_len.data[r]):
+                n = np.minimum(chunk, int(prompt_len.data[r]) - t).item()
+                fault = t + n > P
+                row = () if fault else prompts.data[r, t:t + n]
+            else:
+                g = int(out_len.data[r])
+                if g < 0 or g >= G:
+                    fault = True
+                else:
+                    out.data[r, g], out_len.data[r] = new[s], g + 1
+                    if (eos >= 0 and int(new[s]) == eos) or g + 1 == int(budget.data[r]):
+                        queue.data[1] += 1
+                        r = -1
+                    else:
+                        n, row, decoding = 1, new[s:s + 1], True
+        if not fault and r < 0:
+            t = 0
+            if 0 <= int(queue.data[0]) < N:
+                r = int(queue.data[0])
+                queue.data[0] += 1
+                n = np.minimum(chunk, int(prompt_len.data[r])).item()
+                fault = n < 0 or n > P
+                row = () if fault else prompts.data[r, :n]
+        if fault or t + n > capacity:
+            bad.append(s)
+            slots.append(None)
+        else:
+            slots.append((r, t, n, row, decoding))
+    left = T - len([x for x in slots if x is not None and x[4]])
+    ids.data[...], position_ids.data[...] = 0, 0
+    start = 0
+    for s, x in enumerate(slots):
+        cu.data[s] = start
+        if x is None:
+            count.data[s] = 0
+            continue
+        r, t, n, row, decoding = x
+        if not decoding:
+            n = np.minimum(n, left).item()
+            left -= n
+        req.data[s], pos.data[s], count.data[s] = r, t, n
+        ids.data[0, start:start + n] = row[:n]
+        position_ids.data[0, start:start + n] = t + np.arange(n)
+        last.data[s] = np.minimum(start + (n - 1 if n > 0 else 0), T - 1)
+        start += n
+    cu.data[b] = start
+    if bad:
+        raise IndexError("serve_commit_packed: slot %d (of %d that did) would leave the cache, its prompt or its row of out" % (bad[0], len(bad)))
+
+
+def _check_serve_commit_packed(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, cu, ids, position_ids, last, capacity, chunk, eos):
+    """the operand shapes and dtypes of `serve_commit_packed`, on any backend; returns (slots b, token rows T, requests N)"""
+    b = req.shape[0] if len(req.shape) == 1 else -1
+    T = ids.shape[1] if len(ids.shape) == 2 and ids.shape[0] == 1 else -1
+    N = prompts.shape[0] if len(prompts.shape) == 2 else -1
+    i32 = np.dtype(np.int32)
+    operands = (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, cu, ids, position_ids, last)
+    shapes = [tuple(t.shape) for t in operands]
+    assert 1 <= b <= 1024 and T >= b and N >= 1 and prompts.shape[1] >= 1 and shapes[0] in ((b,), (b, 1)) and shapes[2] == shapes[3] == shapes[5] == (N,) \
+        and len(out.shape) == 2 and out.shape[0] == N and out.shape[1] >= 1 and shapes[6] == (2,) and shapes[8] == shapes[9] == shapes[13] == (b,) \
+        and shapes[10] == (b + 1,) and shapes[11] == shapes[12] == (1, T), \
+        "serve_commit_packed: nxt (b,) or (b, 1), prompts (N, P), prompt_len / budget / out_len (N,), out (N, G), queue (2,), req / pos / count / last " \
+        "(b,) with 1 <= b <= 1024, cu (b + 1,), ids / position_ids (1, T) with T >= b - got %s" % (shapes,)
+    assert all(np.dtype(t.dtype) == i32 for t in operands), "serve_commit_packed: every operand is int32"
+    assert eos is None or int(eos) == eos, "serve_commit_packed: eos is an int or None"
+    assert int(capacity) == capacity and 1 <= capacity < 2 ** 31, "serve_commit_packed: capacity is an int >= 1"
+    assert int(chunk) == chunk and 1 <= chunk and b * chunk < 2 ** 31, "serve_commit_packed: chunk is an int >= 1"
+    return b, T, N
+
+
+CpuTensor.serve_commit_packed = _serve_commit_packed
+
+
 def _speculate_commit(tgt, ids, count, position_ids, out_ids, pos, end, done, stats, draft, max_ngram=3, min_ngram=1, eos=None):
     """ tgt.speculate_commit(ids, count, position_ids, out_ids, pos, end, done, stats, draft, max_ngram=3, min_ngram=1, eos=None):
     the bookkeeping of one step of speculative decoding by prompt lookup, in place and outside the tape - the definition of the

@@ -474,15 +474,48 @@ def _launch_extend(name, q3, k3, v3, m, k_cache, v_cache, pos, out, heads, scale
     return p
 
 
-def extend_attention_supported(q, heads, capacity):
-    """does `q.extend_attention(k_new, v_new, k_cache, v_cache, pos, heads, scale)` exist for this shape?  (b, m, heads * d) float32
+def _packed_rows(name, cu, count, pos, rows, k_cache, v_cache, m_max):
+    """the `cu=` operand of the extend ops as the packed launch reads it, and the largest piece: (cu, slots, m_max).  int32
+    (slots + 1,) next to flat (1, T, .) token rows, caches of `slots` rows and a `pos` of shape (slots,); dense, apart from the
+    caches and from pos"""
+    assert count is None, "%s: cu= (token-packed rows) and count= (a count per batch row) exclude each other" % name
+    slots, capacity = k_cache._shape[0], k_cache._shape[1]
+    assert isinstance(cu, HipTensor) and cu._dtype == _I32 and cu._shape == (slots + 1,) and pos._shape == (slots,) and rows[0] == 1, \
+        "%s: cu is an int32 HipTensor of shape (slots + 1,) = (%d,) and goes with token rows (1, T, .) and a pos of shape (slots,), got cu %s %s, rows %s and pos %s" % (
+            name, slots + 1, getattr(cu, "_dtype", type(cu).__name__), getattr(cu, "_shape", ""), rows, pos._shape)
+    for other in (k_cache, v_cache, pos):
+        assert not _shares_bytes(cu, other), "%s: cu overlaps a cache or pos" % name
+    m_max = min(rows[1], capacity) if m_max is None else int(m_max)
+    assert 1 <= m_max <= capacity, "%s: m_max = %d outside 1 .. capacity = %d" % (name, m_max, capacity)
+    return (cu if cu._strides[0] == 1 else cu.contiguous()), slots, m_max
+
+
+def _launch_extend_packed(name, q2, k2, v2, T, k_cache, v_cache, pos, cu, m_max, out, heads, scale, mask, probs):
+    """q2, k2, v2: (address, row pitch) of flat (T, width) rows; out: (1, T, width) dense.  Returns the probabilities
+    (heads, T, capacity) or None"""
+    slots, capacity, width = k_cache._shape
+    mask3 = _key_mask(mask, slots, capacity, name)
+    p = HipTensor.empty((heads, T, capacity), requires_grad=False) if probs else None
+    flush_lazy_readers(k_cache)
+    flush_lazy_readers(v_cache)
+    pos = pos if slots == 1 or pos._strides[0] == 1 else pos.contiguous()
+    _l.check(_l.lib().lg_attention_extend_packed_f32(*q2, *k2, *v2, k_cache.ptr, v_cache.ptr, k_cache._strides[1], k_cache._strides[0], pos.ptr, cu.ptr,
+                                                     out.ptr, width, p.ptr if probs else None, slots, heads, T, m_max, capacity, width // heads,
+                                                     float(scale), mask3[1], mask3[2]))
+    return p
+
+
+def extend_attention_supported(q, heads, capacity, m_max=None):
+    """(m_max: the call is token-packed - `cu=` -: (1, T, heads * d) rows with any T >= 1 and pieces of at most m_max, default
+    min(T, capacity))
+    does `q.extend_attention(k_new, v_new, k_cache, v_cache, pos, heads, scale)` exist for this shape?  (b, m, heads * d) float32
     with d = 32 or 64, b >= 1 and 1 <= m <= capacity <= 512"""
     sh = q._shape
     return (len(sh) == 3 and q._dtype == _F32 and sh[0] > 0 and sh[2] % heads == 0
-            and bool(_l.lib().lg_attention_extend_supported(sh[1], capacity, sh[2] // heads)))
+            and bool(_l.lib().lg_attention_extend_supported(sh[1] if m_max is None else m_max, capacity, sh[2] // heads)))
 
 
-def extend_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False, count=None):
+def extend_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False, count=None, cu=None, m_max=None):
     """ attention of m NEW tokens per sequence against a filled key / value cache, one launch (lg_attention_extend_f32): with t =
     the int32 word `pos` holds ON THE DEVICE (`pos` of shape (b,): a position per sequence, t = pos[r] for sequence r, everything
     below per sequence - lg_attention_extend_rows_f32; a sequence with t + m beyond the cache writes nothing, the others are computed), rows i of k_new / v_new become rows t + i of the caches (b, capacity, heads * d) and
@@ -494,10 +527,32 @@ def extend_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0,
     count= (an int32 HipTensor (b,), with a per-sequence `pos`): sequence r has n = count[r] real tokens among its m rows - one
     launch of lg_attention_extend_counts_f32.  Its rows < n are those of the call on it alone with m = n, only cache rows
     t .. t + n - 1 are written, only t + n has to fit the cache (n = 0: an idle sequence), and rows >= n of the result and of
-    `.attention_probs` are +0.0.  Without count= the call is the one it was. """
+    `.attention_probs` are +0.0.  Without count= the call is the one it was.
+    cu= (an int32 HipTensor (slots + 1,), with a `pos` of shape (slots,) and caches of `slots` rows): the call is TOKEN-PACKED - one
+    launch of lg_attention_extend_packed_f32.  q, k_new, v_new are (1, T, width), the step's tokens of all slots; slot s owns rows
+    cu[s] .. cu[s + 1] - 1 (at most m_max= of them, default min(T, capacity); T may exceed the capacity) and is computed as by the
+    call on those rows alone against its own cache rows at t = pos[s]; rows >= cu[slots] of the result are +0.0.
+    `.attention_probs` is (heads, T, capacity); mask is (slots, capacity) or (1, capacity).  cu= and count= exclude each other.
+    Without cu= the call is the one it was. """
     name = "extend_attention"
     _inference_only(name, q, k_new, v_new)
     _require_f32(q, k_new, v_new)
+    if cu is not None:
+        assert len(k_cache._shape) == 3 and len(q._shape) == 3, "%s: expected (1, T, width) rows and (slots, capacity, width) caches" % name
+        cu, slots, m_max = _packed_rows(name, cu, count, pos, q._shape, k_cache, v_cache, m_max)
+        assert q._shape == k_new._shape == v_new._shape and extend_attention_supported(q, heads, k_cache._shape[1], m_max), \
+            "%s: unsupported shapes %s / %s / %s with %d heads and caches %s" % (name, q._shape, k_new._shape, v_new._shape, heads, k_cache._shape)
+        _check_cache(name, k_cache, v_cache, pos, slots, q._shape[2])
+        T = q._shape[1]
+        (q, ldq, _), (k_new, ldk, _), (v_new, ldv, _) = (_token_rows_in_place(t, name) for t in (q, k_new, v_new))
+        width = q._shape[2]
+        out = HipTensor.empty(q._shape, requires_grad=False)
+        p = _launch_extend_packed(name, (q.ptr, ldq if T > 1 else width), (k_new.ptr, ldk if T > 1 else width), (v_new.ptr, ldv if T > 1 else width), T,
+                                  k_cache, v_cache, pos, cu, m_max, out, heads, scale, mask, probs)
+        if probs:
+            out.attention_probs = p
+        return out
+    assert m_max is None, "%s: m_max= goes with cu=" % name
     assert q._shape == k_new._shape == v_new._shape and extend_attention_supported(q, heads, k_cache._shape[1] if len(k_cache._shape) == 3 else 0), \
         "%s: unsupported shapes %s / %s / %s with %d heads and caches %s" % (name, q._shape, k_new._shape, v_new._shape, heads, k_cache._shape)
     _check_cache(name, k_cache, v_cache, pos, q._shape[0], q._shape[2])
@@ -511,19 +566,25 @@ def extend_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0,
     return out
 
 
-def self_attention_extend(x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False, count=None):
+def self_attention_extend(x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False, count=None, cu=None,
+                          m_max=None):
     """ the one-node form of an append's attention: the three projections of the m new tokens in ONE launch (lg_gemm_multi3_f32,
     as in `self_attention`) into a (b, m, 3 * width) buffer that the extend launch reads in place - two launches per layer.
-    x: (b, m, hidden); everything else as for `extend_attention`, `count=` included (the projections take all b * m rows). """
+    x: (b, m, hidden); everything else as for `extend_attention`, `count=` included (the projections take all b * m rows) and
+    `cu=` / `m_max=` too: x is (1, T, hidden) then, the projection launch runs on the T rows, the packed launch reads them in place. """
     name = "self_attention_extend"
     _inference_only(name, x, wq, bq, wk, bk, wv, bv)
     _require_f32(x, wq, bq, wk, bk, wv, bv)
-    assert self_attention_extend_supported(x, wq, heads, k_cache._shape[1] if len(k_cache._shape) == 3 else 0) and \
+    assert cu is not None or m_max is None, "%s: m_max= goes with cu=" % name
+    if cu is not None:
+        assert len(k_cache._shape) == 3 and len(x._shape) == 3, "%s: expected (1, T, hidden) rows and (slots, capacity, width) caches" % name
+        cu, slots, m_max = _packed_rows(name, cu, count, pos, x._shape, k_cache, v_cache, m_max)
+    assert self_attention_extend_supported(x, wq, heads, k_cache._shape[1] if len(k_cache._shape) == 3 else 0, m_max) and \
         wq._shape == wk._shape == wv._shape and bq._shape == bk._shape == bv._shape == (wq._shape[0],), \
         "%s: unsupported shapes %s with weights %s / %s / %s, %d heads and caches %s" % (name, x._shape, wq._shape, wk._shape, wv._shape, heads, k_cache._shape)
     b, m, hidden = x._shape
     width = wq._shape[0]
-    _check_cache(name, k_cache, v_cache, pos, b, width)
+    _check_cache(name, k_cache, v_cache, pos, b if cu is None else slots, width)
     x = x.contiguous()
     ws, bs = [w.contiguous() for w in (wq, wk, wv)], [t.contiguous() for t in (bq, bk, bv)]
     qkv = HipTensor.empty((b, m, 3 * width), requires_grad=False)
@@ -532,6 +593,12 @@ def self_attention_extend(x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, head
                                          _ptr3(base, base + 4 * width, base + 8 * width), 3 * width, _ptr3(*(t.ptr for t in bs))))
     out = HipTensor.empty((b, m, width), requires_grad=False)
     ld, sb = 3 * width, m * 3 * width
+    if cu is not None:
+        p = _launch_extend_packed(name, (base, ld), (base + 4 * width, ld), (base + 8 * width, ld), m, k_cache, v_cache, pos, cu, m_max, out, heads,
+                                  scale, mask, probs)
+        if probs:
+            out.attention_probs = p
+        return out
     p = _launch_extend(name, (base, ld, sb), (base + 4 * width, ld, sb), (base + 8 * width, ld, sb), m, k_cache, v_cache, pos, out, heads, scale,
                        mask, probs, **({} if count is None else {"count": count}))
     if probs:
@@ -539,12 +606,14 @@ def self_attention_extend(x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, head
     return out
 
 
-def self_attention_extend_supported(x, wq, heads, capacity):
-    """does `x.self_attention_extend(...)` exist for these shapes?  (b, m, hidden) input, (width, hidden) weights with width =
+def self_attention_extend_supported(x, wq, heads, capacity, m_max=None):
+    """(m_max: the call is token-packed - `cu=` -: x is (1, T, hidden) with any T >= 1 and pieces of at most m_max)
+    does `x.self_attention_extend(...)` exist for these shapes?  (b, m, hidden) input, (width, hidden) weights with width =
     heads * d, d = 32 or 64, width a multiple of 64, 1 <= m <= capacity <= 512"""
     return (len(x._shape) == 3 and x._dtype == _F32 and len(wq._shape) == 2 and wq._shape[1] == x._shape[2]
             and wq._shape[0] % heads == 0 and wq._shape[0] % 64 == 0 and x._shape[2] % 4 == 0 and x._shape[0] > 0
-            and bool(_l.lib().lg_attention_extend_supported(x._shape[1], capacity, wq._shape[0] // heads)))
+            and (m_max is None or x._shape[0] == 1)
+            and bool(_l.lib().lg_attention_extend_supported(x._shape[1] if m_max is None else m_max, capacity, wq._shape[0] // heads)))
 
 
 HipTensor.extend_attention, HipTensor.extend_attention_supported = extend_attention, extend_attention_supported
@@ -622,6 +691,45 @@ def serve_commit(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos
 
 
 HipTensor.serve_commit = serve_commit
+
+
+def serve_commit_packed(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, cu, ids, position_ids, last, capacity, chunk, eos=None):
+    """ nxt.serve_commit_packed(prompts, prompt_len, budget, out, out_len, queue, req, pos, count, cu, ids, position_ids, last,
+    capacity, chunk, eos=None): what `CpuTensor.serve_commit_packed` defines - `serve_commit` for a token-packed step: ids and
+    position_ids (1, T) hold the step's tokens of all slots, T >= slots is the token budget, cu (slots + 1,) says which rows are
+    whose; decoding slots get their token, prefilling slots share what is left in slot order - in ONE launch
+    (lg_serve_commit_packed_i32, csrc/serve_packed.hip), in place and outside the tape.  Operands as for `serve_commit`.  A slot
+    that would leave its bounds gets count 0, takes no rows, keeps its other bytes and raises IndexError at the next
+    synchronisation.  No host read: a captured step replays it as it stands. """
+    from ..cpu.ops import _check_serve_commit_packed
+    name = "serve_commit_packed"
+    operands = (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, cu, ids, position_ids, last)
+    assert all(isinstance(t, HipTensor) for t in operands), "%s: every operand is a HipTensor" % name
+    b, T, N = _check_serve_commit_packed(*operands, capacity, chunk, eos)
+    if b > 1 and nxt._strides[0] < 1:
+        nxt = nxt.contiguous()
+    # what is only read may be copied once into a layout the launch addresses
+    if (prompts._shape[1] > 1 and prompts._strides[1] != 1) or (N > 1 and prompts._strides[0] < prompts._shape[1]):
+        prompts = prompts.contiguous()
+    prompt_len, budget = (t if N == 1 or t._strides[0] == 1 else t.contiguous() for t in (prompt_len, budget))
+    # the launch writes these where they lie: a layout it cannot address is an error, never a copy
+    assert all(t.is_contiguous() for t in (out_len, queue, req, pos, count, cu, last, ids, position_ids)) and \
+        (out._shape[1] == 1 or out._strides[1] == 1) and (N == 1 or out._strides[0] >= out._shape[1]), \
+        "%s: out_len, queue, req, pos, count, cu, last, ids and position_ids must be dense and the rows of out contiguous" % name
+    operands = (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, cu, ids, position_ids, last)
+    for i, x in enumerate(operands):
+        for y in operands[i + 1:]:
+            assert not _shares_bytes(x, y), "%s: two operands overlap" % name
+    for x in operands[4:]:
+        flush_lazy_readers(x)
+    P, G = prompts._shape[1], out._shape[1]
+    _l.check(_l.lib().lg_serve_commit_packed_i32(nxt.ptr, nxt._strides[0] if b > 1 else 1, prompts.ptr, prompts._strides[0] if N > 1 else P, P,
+                                                 prompt_len.ptr, budget.ptr, out.ptr, out._strides[0] if N > 1 else G, G, out_len.ptr, queue.ptr, N,
+                                                 req.ptr, pos.ptr, count.ptr, cu.ptr, ids.ptr, position_ids.ptr, last.ptr, b, T, int(chunk),
+                                                 int(capacity), -1 if eos is None else int(eos)))
+
+
+HipTensor.serve_commit_packed = serve_commit_packed
 
 
 """ The bookkeeping of a speculative decoding step in one launch (csrc/speculate.hip) """

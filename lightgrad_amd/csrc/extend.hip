@@ -26,6 +26,10 @@
 // for the other two entries): of the m rows given, the first n = count[b] are tokens.  The element is computed as by a launch of
 // its own with m = n (keys = t + n, Kend and the seam from n, cache rows t .. t + n - 1 written), only t + n must fit the capacity,
 // rows >= n of the context and of p become +0.0, and a block that starts at q0 >= n returns after clearing its rows.
+// lg_attention_extend_packed_f32 is the body once more for a token-packed step (attn_packed<D>): the tokens of ALL cache slots lie in
+// flat (T, .) operands and `cu` (slots + 1 words) says whose they are - slot z owns rows cu[z] .. cu[z + 1] - 1 and is computed as by a
+// `_rows` launch of its own at batch 1 on those rows, against cache rows, position and mask of slot z; one more slice of the grid
+// clears the rows behind cu[slots], which belong to nobody.
 // LDS at D = 64, capacity = 512: 32 * 68 + 32 * 516 + 128 * 72 + 3072 + 512 floats = 126 KB - one workgroup per CU.
 #include "attention_common.h"
 
@@ -51,6 +55,8 @@ struct ExtendArgs {
     const float* mask;                   // element (b, j) at mask + b * sbm + j; NULL = none
     int64_t sbm;
     int* status;
+    const int32_t* cu;                   // NULL for the three (b, m) entries; lg_attention_extend_packed_f32: slots + 1 words, slot z owns rows cu[z] .. cu[z + 1] - 1
+    int tokens;                          // ... of the `tokens` rows of the flat (tokens, .) operands: no batch pitch, p is (heads, tokens, capacity)
 };
 
 template <int D>
@@ -77,18 +83,66 @@ __device__ __forceinline__ void seam_store(const af32x4 (&v)[N], float* dst, int
     store_rows_padded<D, N>(v, dst, pitch, rows, padded);
 }
 
+// the slice behind the last slot of a packed launch: token rows cu[slots] .. tokens - 1 belong to nobody and become +0.0 in the
+// context and in p, so that what the launch returns is determined whatever the projection buffer holds there.  The (x, head)
+// workgroups of the slice share the rows in runs of 32
 template <int D>
-__global__ void __launch_bounds__(256) attn_extend(const ExtendArgs a) {
+__device__ __forceinline__ void packed_clear(const ExtendArgs& a, int slots) {
+    constexpr int Q4 = D / 4;
+    const int tid = threadIdx.x, head = blockIdx.y, C = a.capacity, T = a.tokens;
+    const int used = a.cu[slots];
+    if (used < 0 || used > T) {
+        if (tid == 0) __hip_atomic_fetch_or(a.status, LG_STATUS_BAD_INDEX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        return;
+    }
+    const af32x4 zero{0.f, 0.f, 0.f, 0.f};
+    for (int lo = used + 32 * int(blockIdx.x); lo < T; lo += 32 * int(gridDim.x)) {
+        const int hi = lo + 32 < T ? lo + 32 : T;
+        float* oz = a.o + head * D;
+        for (int f = tid; f < (hi - lo) * Q4; f += 256) *reinterpret_cast<af32x4*>(oz + int64_t(lo + f / Q4) * a.ldo + (f % Q4) * 4) = zero;
+        if (a.p != nullptr) {
+            float* pz = a.p + (int64_t(head) * T + lo) * C;              // rows lo .. hi - 1 of p are one dense run of floats
+            const int total = (hi - lo) * C;
+            const int ahead = int((4 - ((reinterpret_cast<uintptr_t>(pz) >> 2) & 3)) & 3);
+            const int lead = ahead < total ? ahead : total, quads = (total - lead) / 4;
+            for (int f = tid; f < lead; f += 256) pz[f] = 0.f;
+            for (int f = tid; f < quads; f += 256) *reinterpret_cast<af32x4*>(pz + lead + 4 * f) = zero;
+            for (int f = lead + 4 * quads + tid; f < total; f += 256) pz[f] = 0.f;
+        }
+    }
+}
+
+// PACKED (attn_packed<D>, lg_attention_extend_packed_f32): blockIdx.z is a cache SLOT whose token rows are rows cu[z] .. cu[z + 1] - 1
+// of flat (tokens, .) operands; the caches, the positions and the mask are addressed by the slot as by a batch element, and the
+// first row of the slot's tokens is a scalar like t and count.  A flag of the template and not a branch on a kernel argument:
+// attn_extend<D>, the kernel of the three (b, m) entries, keeps the code, the registers and the time it had (the branch at run
+// time compiled to 4 VGPRs fewer and a launch 5 % slower: profiles/serve_packed.md)
+template <int D, bool PACKED>
+__device__ __forceinline__ void attn_extend_body(const ExtendArgs& a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int m = a.m, C = a.capacity, Cp = round32(C), PP = Cp + 4;
     constexpr int PQ = D + 4, PV = D + 8, Q4 = D / 4;
     constexpr int NB = 32 * Q4 / 256, NA = kExtChunk * Q4 / 256;
+    if constexpr (PACKED) {
+        if (blockIdx.z + 1 == gridDim.z) { packed_clear<D>(a, int(gridDim.z) - 1); return; }
+    }
     const int t = a.pos[int64_t(blockIdx.z) * a.pos_pitch];       // uniform over the workgroup either way: a scalar load
     const int tid = threadIdx.x;
     // the element's real new tokens: each of the launch's m rows, or - lg_attention_extend_counts_f32 - the first count[b] of them.
     // From here on the element is computed as by a launch of its own with m = real; `m` stays the pitch of `p` and the rows to clear
-    const int real = a.count ? a.count[blockIdx.z] : m;
-    if (t < 0 || real < 0 || real > m || t > C - real) {
+    // (packed: the slot's rows cu[z + 1] - cu[z], at most m = m_max of them; its first row is workgroup-uniform like t)
+    int real, row0 = 0;
+    bool bad;
+    if constexpr (PACKED) {
+        row0 = a.cu[blockIdx.z];
+        const int64_t n = int64_t(a.cu[blockIdx.z + 1]) - row0;
+        bad = row0 < 0 || n < 0 || n > m || n + row0 > a.tokens || t < 0 || t > C - n;
+        real = int(n);
+    } else {
+        real = a.count ? a.count[blockIdx.z] : m;
+        bad = t < 0 || real < 0 || real > m || t > C - real;
+    }
+    if (bad) {
         // a bounds check, never a fault: nothing is written for this batch element (the others of a per-row launch are computed
         // as usual), the next synchronising call reports LG_EINDEX
         if (tid == 0) __hip_atomic_fetch_or(a.status, LG_STATUS_BAD_INDEX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -101,7 +155,10 @@ __global__ void __launch_bounds__(256) attn_extend(const ExtendArgs a) {
     float* Bias = Red + 3 * 1024;         // what key j adds to every score of its column
     const int lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     const int q0 = blockIdx.x * 32, head = blockIdx.y, b = blockIdx.z;
-    if (real < m) {
+    if constexpr (PACKED) {
+        // a block without a row of the slot is done: uniform over the workgroup, before any load, MFMA or barrier
+        if (q0 >= real) return;
+    } else if (real < m) {
         // rows of the block that are given but hold no token: +0.0 in the context and in p, so that what the launch returns is
         // determined.  A block without a real row is done then: uniform over the workgroup, before any load, MFMA or barrier
         const int lo = q0 > real ? q0 : real, hi = q0 + 32 < m ? q0 + 32 : m;
@@ -124,13 +181,18 @@ __global__ void __launch_bounds__(256) attn_extend(const ExtendArgs a) {
     const int Kend = round32(t + q0 + qrows);                         // the key columns the chunk loops cover (<= Cp)
     const float* kc = a.k_cache + int64_t(b) * a.sbc + head * D;
     const float* vc = a.v_cache + int64_t(b) * a.sbc + head * D;
-    const float* kn = a.k_new + int64_t(b) * a.sbk + head * D;
-    const float* vn = a.v_new + int64_t(b) * a.sbv + head * D;
+    // the element's token rows: a batch pitch, or - packed - the slot's first row of the flat operands
+    const float* kn = a.k_new + (PACKED ? int64_t(row0) * a.ldk : int64_t(b) * a.sbk) + head * D;
+    const float* vn = a.v_new + (PACKED ? int64_t(row0) * a.ldv : int64_t(b) * a.sbv) + head * D;
+    const float* qn = a.q + (PACKED ? int64_t(row0) * a.ldq : int64_t(b) * a.sbq) + head * D;
+    float* on = a.o + (PACKED ? int64_t(row0) * a.ldo : int64_t(b) * a.sbo) + head * D;
+    // row 0 of the element in p: (batch, heads, m, capacity), or - packed - (heads, tokens, capacity)
+    const int64_t prow = PACKED ? int64_t(head) * a.tokens + row0 : (int64_t(b) * a.heads + head) * m;
 
     af32x4 rc[NA];
     {
         af32x4 rq[NB], rk[NB], rv[NB];
-        load_rows<D, NB>(rq, a.q + int64_t(b) * a.sbq + int64_t(q0) * a.ldq + head * D, a.ldq, qrows);
+        load_rows<D, NB>(rq, qn + int64_t(q0) * a.ldq, a.ldq, qrows);
         load_rows<D, NB>(rk, kn + int64_t(q0) * a.ldk, a.ldk, qrows);
         load_rows<D, NB>(rv, vn + int64_t(q0) * a.ldv, a.ldv, qrows);
         seam_load<D, NA>(rc, kc, a.ldc, kn, a.ldk, 0, t, real);
@@ -208,7 +270,7 @@ __global__ void __launch_bounds__(256) attn_extend(const ExtendArgs a) {
         for (int off = 1; off < 8; off <<= 1) s += __shfl_xor(s, off, 64);
         const float inv = 1.0f / s;
         const bool stored = a.p != nullptr && row < qrows;
-        float* pg = a.p + ((int64_t(b) * a.heads + head) * m + q0 + (row < qrows ? row : 0)) * C;
+        float* pg = a.p + (prow + q0 + (row < qrows ? row : 0)) * C;
 #pragma unroll
         for (int i = 0; i < kExtMaxBlocks; ++i) {
             const int c = sub * 4 + 32 * i;
@@ -254,12 +316,18 @@ __global__ void __launch_bounds__(256) attn_extend(const ExtendArgs a) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[e] += Red[((q - 1) * NT + n) * 1024 + e * 64 + lane];
         }
-        float* og = a.o + int64_t(b) * a.sbo + int64_t(q0) * a.ldo + head * D + 32 * n + r;
+        float* og = on + int64_t(q0) * a.ldo + 32 * n + r;
 #pragma unroll
         for (int e = 0; e < 16; ++e)
             if (acc_row(e, h) < qrows) og[int64_t(acc_row(e, h)) * a.ldo] = acc[e];
     }
 }
+
+template <int D>
+__global__ void __launch_bounds__(256) attn_extend(const ExtendArgs a) { attn_extend_body<D, false>(a); }
+
+template <int D>
+__global__ void __launch_bounds__(256) attn_packed(const ExtendArgs a) { attn_extend_body<D, true>(a); }
 
 static bool extend_operand(const void* p, int64_t ld, int64_t sb) { return p && aligned16(p) && ld >= 0 && sb >= 0 && ld % 4 == 0 && sb % 4 == 0; }
 
@@ -284,6 +352,15 @@ static int launch_extend(const ExtendArgs& a, dim3 grid) {
     int rc = allow_lds(&attn_extend<D>, bytes);
     if (rc != LG_OK) return rc;
     hipLaunchKernelGGL(attn_extend<D>, grid, dim3(256), bytes, rt().stream, a);
+    return LG_OK;
+}
+
+template <int D>
+static int launch_packed(const ExtendArgs& a, dim3 grid) {
+    const size_t bytes = size_t(attn_extend_lds_floats<D>(round32(a.capacity))) * 4;
+    int rc = allow_lds(&attn_packed<D>, bytes);
+    if (rc != LG_OK) return rc;
+    hipLaunchKernelGGL(attn_packed<D>, grid, dim3(256), bytes, rt().stream, a);
     return LG_OK;
 }
 
@@ -336,7 +413,7 @@ static int extend_entry(const char* name, int64_t pos_pitch, bool counts, const 
         if (p) { rc = adam_epilogue_check_write(p, batch * heads * m * capacity * 4); if (rc != LG_OK) return rc; }
     }
     const ExtendArgs a{q, k_new, v_new, ldq, sbq, ldk, sbk, ldv, sbv, k_cache, v_cache, ldc, sbc, pos, pos_pitch, counts ? count : nullptr, o, ldo, sbo, p,
-                       int(heads), int(capacity), int(m), scale, mask, sbm, rt().status_dev};
+                       int(heads), int(capacity), int(m), scale, mask, sbm, rt().status_dev, nullptr, 0};
     const dim3 grid{unsigned((m + 31) / 32), unsigned(heads), unsigned(batch)};
     const int rc = D == 64 ? launch_extend<64>(a, grid) : launch_extend<32>(a, grid);
     return rc;
@@ -378,6 +455,68 @@ extern "C" int lg_attention_extend_counts_f32(const float* q, int64_t ldq, int64
     const int rc = extend_entry("lg_attention_extend_counts_f32", 1, true, count, q, ldq, sbq, k_new, ldk, sbk, v_new, ldv, sbv, k_cache, v_cache, ldc, sbc,
                                 pos, o, ldo, sbo, p, batch, heads, m, capacity, D, scale, mask, sbm);
     if (rc != LG_OK || batch == 0) return rc;
+    LG_CHECK_LAUNCH();
+    return LG_OK;
+}
+
+// do the `words` int32 words at x share an address with the `bytes` bytes at y?
+static bool words_overlap(const int32_t* x, int64_t words, const void* y, int64_t bytes) {
+    const char *a = reinterpret_cast<const char*>(x), *ae = a + 4 * words, *b = static_cast<const char*>(y);
+    return y != nullptr && a < b + bytes && b < ae;
+}
+
+// the token-packed launch: the step's tokens of ALL slots in flat (T, .) operands, slot z owning rows cu[z] .. cu[z + 1] - 1 (at
+// most m_max of them) behind its own position pos[z] of its own cache rows.  The `_rows` kernel per slot, with the slot's first
+// row in place of a batch pitch; one more slice of the grid clears the rows behind cu[slots]
+extern "C" int lg_attention_extend_packed_f32(const float* q, int64_t ldq, const float* k_new, int64_t ldk, const float* v_new, int64_t ldv,
+                                              float* k_cache, float* v_cache, int64_t ldc, int64_t sbc, const int32_t* pos, const int32_t* cu,
+                                              float* o, int64_t ldo, float* p, int64_t slots, int64_t heads, int64_t T, int64_t m_max,
+                                              int64_t capacity, int64_t D, float scale, const float* mask, int64_t sbm) {
+    LG_REQUIRE_INIT();
+    const char* name = "lg_attention_extend_packed_f32";
+    LG_ARG(lg_attention_extend_supported(m_max, capacity, D), "%s: m_max = %lld (1 .. capacity), capacity = %lld (1 .. 512), D = %lld (32 or 64) unsupported",
+           name, (long long)m_max, (long long)capacity, (long long)D);
+    LG_ARG(T >= 1 && T < (int64_t(1) << 30), "%s: T = %lld token rows (1 .. 2^30 - 1) unsupported", name, (long long)T);
+    LG_ARG(slots >= 0 && heads >= 1 && slots <= 65534 && heads <= 65535, "%s: bad slots / heads", name);
+    if (slots == 0) return LG_OK;
+    LG_ARG(extend_operand(q, ldq, 0) && extend_operand(k_new, ldk, 0) && extend_operand(v_new, ldv, 0) && extend_operand(k_cache, ldc, sbc) &&
+               extend_operand(v_cache, ldc, sbc) && extend_operand(o, ldo, 0) && pos && (reinterpret_cast<uintptr_t>(pos) & 3u) == 0 && aligned16(p),
+           "%s: operands must be non-NULL and 16-byte aligned with pitches that are non-negative multiples of 4", name);
+    const int64_t w = heads * D;
+    LG_ARG(ldc >= w, "%s: cache row pitch %lld below heads * D = %lld", name, (long long)ldc, (long long)w);
+    LG_ARG(!mask || sbm == 0 || sbm >= capacity, "%s: mask slot pitch %lld is neither 0 (one row for every slot) nor >= capacity", name, (long long)sbm);
+    // (extend_overlap spans `slots` elements of both operands: the flat ones have no batch pitch)
+    LG_ARG(!extend_overlap(k_new, ldk, 0, T, k_cache, ldc, sbc, capacity, slots, w) && !extend_overlap(k_new, ldk, 0, T, v_cache, ldc, sbc, capacity, slots, w) &&
+               !extend_overlap(v_new, ldv, 0, T, k_cache, ldc, sbc, capacity, slots, w) && !extend_overlap(v_new, ldv, 0, T, v_cache, ldc, sbc, capacity, slots, w),
+           "%s: k_new / v_new overlap a cache: the launch writes the caches while other workgroups read the new rows", name);
+    LG_ARG(!positions_overlap(pos, slots, k_cache, ldc, sbc, capacity, slots, w) && !positions_overlap(pos, slots, v_cache, ldc, sbc, capacity, slots, w),
+           "%s: pos overlaps a cache: the launch writes the caches while other workgroups read their positions", name);
+    LG_ARG(cu && (reinterpret_cast<uintptr_t>(cu) & 3u) == 0, "%s: cu must be non-NULL and 4-byte aligned", name);
+    LG_ARG(!positions_overlap(cu, slots + 1, k_cache, ldc, sbc, capacity, slots, w) && !positions_overlap(cu, slots + 1, v_cache, ldc, sbc, capacity, slots, w),
+           "%s: cu overlaps a cache: the launch writes the caches while other workgroups read their rows' bounds", name);
+    LG_ARG(!(cu < pos + slots && pos < cu + slots + 1), "%s: cu overlaps pos", name);
+    {
+        const int64_t span[4] = {((T - 1) * ldq + w) * 4, ((T - 1) * ldk + w) * 4, ((T - 1) * ldv + w) * 4, ((T - 1) * ldo + w) * 4};
+        LG_ARG(!words_overlap(cu, slots + 1, q, span[0]) && !words_overlap(cu, slots + 1, k_new, span[1]) && !words_overlap(cu, slots + 1, v_new, span[2]) &&
+                   !words_overlap(cu, slots + 1, o, span[3]) && !words_overlap(cu, slots + 1, p, heads * T * capacity * 4),
+               "%s: cu overlaps an operand (q, k_new, v_new, o or p)", name);
+    }
+    {
+        const int64_t rows[2] = {T, w}, row_strides[2] = {ldo, 1};
+        int rc = adam_epilogue_check_strided(o, 4, 2, rows, row_strides);
+        if (rc != LG_OK) return rc;
+        const int64_t crows[3] = {slots, capacity, w}, strides[3] = {sbc, ldc, 1};
+        rc = adam_epilogue_check_strided(k_cache, 4, 3, crows, strides);
+        if (rc != LG_OK) return rc;
+        rc = adam_epilogue_check_strided(v_cache, 4, 3, crows, strides);
+        if (rc != LG_OK) return rc;
+        if (p) { rc = adam_epilogue_check_write(p, heads * T * capacity * 4); if (rc != LG_OK) return rc; }
+    }
+    const ExtendArgs a{q, k_new, v_new, ldq, 0, ldk, 0, ldv, 0, k_cache, v_cache, ldc, sbc, pos, 1, nullptr, o, ldo, 0, p,
+                       int(heads), int(capacity), int(m_max), scale, mask, sbm, rt().status_dev, cu, int(T)};
+    const dim3 grid{unsigned((m_max + 31) / 32), unsigned(heads), unsigned(slots + 1)};
+    const int rc = D == 64 ? launch_packed<64>(a, grid) : launch_packed<32>(a, grid);
+    if (rc != LG_OK) return rc;
     LG_CHECK_LAUNCH();
     return LG_OK;
 }

@@ -428,8 +428,12 @@ class RequestPool(object):
     `cache` must be per_row.  A request needs lengths[r] + budgets[r] - 1 cache rows (its last token is fed to nobody): checked
     here, on the host, against the capacity.  State, not parameters, like the cache.  Not a class of the reference."""
 
-    def __init__(self, cache, prompts, lengths, budgets, chunk: int, pad_token_id: int = 0, max_positions=None):
-        """max_positions: the model's position embeddings, if the caller knows them - the capacity must not exceed them"""
+    def __init__(self, cache, prompts, lengths, budgets, chunk: int, pad_token_id: int = 0, max_positions=None, token_budget=None):
+        """max_positions: the model's position embeddings, if the caller knows them - the capacity must not exceed them.
+        token_budget: None, or T >= slots - the steps are TOKEN-PACKED: ids and position_ids are (1, T), the step's tokens of all
+        slots in one flat buffer, `cu` (slots + 1,) says which rows are whose, `last` names rows of the T, and `commit` is
+        `serve_commit_packed`: a decoding slot takes one row, the prefilling slots share the rest in pieces of at most `chunk`.
+        `count` stays (pos + count is the commit's t).  Without it `cu` is None and everything is as it was"""
         assert isinstance(cache, KVCache) and cache.per_row, "RequestPool takes a cache with a position per sequence: nn.KVCache(..., per_row=True)"
         assert max_positions is None or cache.capacity <= max_positions, \
             "RequestPool: a cache of %d positions exceeds the model's %s position embeddings" % (cache.capacity, max_positions)
@@ -458,8 +462,17 @@ class RequestPool(object):
         else:
             from .autograd.hip.ops import _idx_view
             self._finished = _idx_view(self.queue, (slice(1, 2),))
-        self.ids, self.position_ids = tensor(np.zeros((self.slots, self.chunk))), tensor(np.zeros((self.slots, self.chunk)))
-        self.max_steps = int((-(-lengths // self.chunk) + budgets).sum())          # every request alone in turn: no schedule takes longer
+        self.token_budget, self.cu = None, None
+        if token_budget is None:
+            self.ids, self.position_ids = tensor(np.zeros((self.slots, self.chunk))), tensor(np.zeros((self.slots, self.chunk)))
+            self.max_steps = int((-(-lengths // self.chunk) + budgets).sum())      # every request alone in turn: no schedule takes longer
+        else:
+            assert int(token_budget) == token_budget and token_budget >= self.slots, \
+                "RequestPool: token_budget is a number of token rows >= the %d slots, got %s" % (self.slots, token_budget)
+            self.token_budget = int(token_budget)
+            self.ids, self.position_ids = tensor(np.zeros((1, self.token_budget))), tensor(np.zeros((1, self.token_budget)))
+            self.cu = tensor(np.zeros(self.slots + 1))
+            self.max_steps = int((lengths + budgets).sum())                        # a prompt token a step at the least: no schedule takes longer
         cache.reset()
         cache.lengths = None            # the positions move on the device from here on: the host mirror is an upper bound only
         cache.length = cache.capacity
@@ -470,7 +483,11 @@ class RequestPool(object):
 
     def commit(self, nxt, eos=None) -> None:
         """one `serve_commit`: `nxt` (slots,) or (slots, 1) int32 are the tokens the step has just drawn (ignored for slots that
-        are free or prefilling)"""
+        are free or prefilling); with a token budget, one `serve_commit_packed`"""
+        if self.cu is not None:
+            nxt.serve_commit_packed(self.prompts, self.prompt_len, self.budget, self.out, self.out_len, self.queue, self.req, self.cache.pos,
+                                    self.count, self.cu, self.ids, self.position_ids, self.last, self.cache.capacity, self.chunk, eos=eos)
+            return
         nxt.serve_commit(self.prompts, self.prompt_len, self.budget, self.out, self.out_len, self.queue, self.req, self.cache.pos, self.count,
                          self.ids, self.position_ids, self.last, self.cache.capacity, eos=eos)
 
