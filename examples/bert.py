@@ -256,6 +256,44 @@ class BertSelfAttention(nn.Module):
         context = (probs @ v).transpose(0, 2, 1, 3).reshape(b, m, self.h * self.d)
         return context * constant(real.reshape(b, m, 1)), probs * constant(real.reshape(b, 1, m, 1))
 
+    def _paged_composite(self, hidden, attention_mask, cache, index, count):
+        """a step against an nn.PagedKVCache over the tensor API - the definition of `self_attention_extend(count=, block_table=,
+        block_size=)`: every slot's rows below its position are gathered from the pool through its table into a contiguous
+        (slots, capacity, width) cache, `_counted_composite` runs on it, and the new rows t .. t + count - 1 of every slot are
+        scattered back to the pool.  Positions, counts and the table are READ from the tensors (whoever moved them:
+        `serve_commit_paged`); a table word the slot reaches must name a block of the pool"""
+        b, B, capacity = hidden.shape[0], cache.block_size, cache.capacity
+        t, c = np.asarray(cache.pos.numpy(), np.int64), np.asarray(count.numpy(), np.int64)
+        table = np.asarray(cache.block_table.numpy(), np.int64)
+        assert c.shape == (b,) and (c >= 0).all() and (t >= 0).all() and (t + c <= capacity).all(), \
+            "the paged cache holds %s of %d positions: no room for %s more" % (t.tolist(), capacity, c.tolist())
+        reach = -(-(t + c) // B)
+        for r in range(b):
+            if not ((table[r, :reach[r]] >= 0) & (table[r, :reach[r]] < cache.num_blocks)).all():
+                raise IndexError("slot %d reaches %d blocks and its table names %s: not blocks of a pool of %d" % (
+                    r, reach[r], table[r, :reach[r]].tolist(), cache.num_blocks))
+        cls = hidden.__class__
+        pools = (cache.k[index], cache.v[index])
+        rows = []
+        for pool in pools:
+            host = np.asarray(pool.numpy())
+            flat = np.zeros((b, capacity, cache.width), host.dtype)
+            for r in range(b):
+                if t[r]:
+                    flat[r, :t[r]] = host[table[r, :-(-t[r] // B)]].reshape(-1, cache.width)[:t[r]]
+            rows.append(cls.from_numpy(flat, requires_grad=False))
+
+        class _Gathered(object):
+            k, v, pos = [rows[0]], [rows[1]], cache.pos
+        _Gathered.capacity = capacity
+        context, probs = self._counted_composite(hidden, attention_mask, _Gathered, 0, count)
+        for r in range(b):
+            for j in range(int(t[r]), int(t[r] + c[r])):
+                block, at = int(table[r, j // B]), j % B
+                for pool, flat in zip(pools, rows):
+                    pool[block:block + 1, at:at + 1] = flat[r:r + 1, j:j + 1]
+        return context, probs
+
     def _packed_composite(self, hidden, attention_mask, cache, index, cu):
         """a TOKEN-PACKED step over the tensor API - the definition of `self_attention_extend(cu=)`: `hidden` (1, T, hidden) holds the
         step's tokens of all cache slots, slot s owns rows cu[s] .. cu[s + 1] - 1.  Every slot with a row is computed as
@@ -312,6 +350,21 @@ class BertSelfAttention(nn.Module):
         (`_packed_composite` is the definition; the fused route is one projection launch on the T rows and one attention launch)"""
         counted = {} if count is None else {"count": count}
         assert count is None or getattr(cache, "per_row", False), "count= takes a cache with a position per sequence: nn.KVCache(..., per_row=True)"
+        if isinstance(cache, nn.PagedKVCache):
+            # the cache's rows lie in blocks of a pool: the fused route passes the table to the paged launch (still two launches
+            # per layer), anything else gathers, runs the counted composite and scatters (`_paged_composite`, the definition)
+            assert count is not None and cu is None, "an nn.PagedKVCache serves the count= append path only (not cu=, not a step without count=)"
+            b = hidden.shape[0]
+            mask_ok = attention_mask is None or (attention_mask.dtype == np.float32 and not attention_mask.requires_grad and
+                                                 tuple(attention_mask.shape) in ((b, cache.capacity), (1, cache.capacity)))
+            if hasattr(hidden, "self_attention_extend") and mask_ok and hidden.self_attention_extend_supported(self.query.weight, self.h, cache.capacity):
+                extra = {"mask": attention_mask} if attention_mask is not None else {}
+                context = hidden.self_attention_extend(self.query.weight, self.query.bias, self.key.weight, self.key.bias, self.value.weight,
+                                                       self.value.bias, cache.k[index], cache.v[index], cache.pos, heads=self.h,
+                                                       scale=math.sqrt(self.d) ** -1, count=count, block_table=cache.block_table,
+                                                       block_size=cache.block_size, **extra)
+                return context, None
+            return self._paged_composite(hidden, attention_mask, cache, index, count)
         if cu is not None:
             assert count is None, "cu= (token-packed rows) and count= (a count per batch row) exclude each other"
             assert getattr(cache, "per_row", False), "cu= takes a cache with a position per sequence: nn.KVCache(..., per_row=True)"
@@ -516,6 +569,10 @@ class BertModel(nn.Module):
     def forward(self, input_ids, attention_mask=None, token_type_ids=None, cache=None, append=False, count=None, token_positions=None, cu=None):
         assert (count is None and token_positions is None and cu is None) or (cache is not None and append), \
             "count=, cu= and token_positions= go with cache= and append=True"
+        if isinstance(cache, nn.PagedKVCache):
+            assert append and count is not None and cu is None, \
+                "an nn.PagedKVCache serves the count= append path only: model(ids, cache=paged, append=True, count=...) - not the prompt / one-token " \
+                "decode route (no append=True) and not token-packed rows (cu=)"
         if cache is not None:
             if append:
                 if cu is not None:
@@ -1146,6 +1203,7 @@ def generate(model, ids, max_new_tokens, attention_mask=None, cache=None, graph=
     picked on the device.  beams: a dict that receives `sequences` (b, w, columns) and `scores` (b, w) as tensors, and `steps`.
     lengths=, eos_token_id=, pad_token_id= and prefill_chunk= work as on the per-row path; temperature, speculate= and append=True
     are refused.  num_beams=1 is greedy decoding, up to near-ties (its scores come from a different launch than argmax's logits)."""
+    assert not isinstance(cache, nn.PagedKVCache), "generate: an nn.PagedKVCache serves the count= append path only (serve): pass an nn.KVCache"
     if num_beams is not None:
         assert int(num_beams) == num_beams and 1 <= num_beams <= 8, "num_beams is an int within 1 .. 8 (got %s)" % (num_beams,)
         assert temperature is None, "beam search is deterministic: temperature= (sampling beams) is not supported with num_beams="
@@ -1243,8 +1301,30 @@ def serve_step(model, pool, sampler=None, eos=None):
     pool.commit(next_token(model.head(rows), sampler), eos=eos)
 
 
+def fill_shared_prefix(model, pool, tokens):
+    """the keys and values of the prefix every request shares, computed once: `tokens` (F * B of them) go through the paged append
+    path itself in pieces of at most `pool.chunk` - as slot 0, whose table names blocks 0 .. F - 1 for the while; the other slots
+    have no token.  Afterwards the table is -1 and the position 0 again: the blocks are in no table until `serve_commit_paged`
+    gives them to every request it admits, they are not on the stack of free blocks, and nothing writes them again.  Host values
+    are uploaded here, before the first step"""
+    cache, slots, chunk = pool.cache, pool.slots, pool.chunk
+    cls = type(cache.pos)
+    i32 = lambda a: cls.from_numpy(np.ascontiguousarray(a, np.int32), requires_grad=False)        # noqa: E731
+    table = np.full((slots, cache.max_blocks), -1, np.int32)
+    table[0, :pool.prefix_blocks] = np.arange(pool.prefix_blocks)
+    cache.block_table[:] = i32(table)
+    for t in range(0, len(tokens), chunk):
+        n = min(chunk, len(tokens) - t)
+        ids, at, count, pos = (np.zeros((slots, chunk), np.int32), np.zeros((slots, chunk), np.int32), np.zeros(slots, np.int32), np.zeros(slots, np.int32))
+        ids[0, :n], at[0, :n], count[0], pos[0] = tokens[t:t + n], t + np.arange(n), n, t
+        cache.pos[:] = i32(pos)
+        model.bert(i32(ids), cache=cache, append=True, count=i32(count), token_positions=i32(at))
+    cache.block_table[:] = i32(np.full((slots, cache.max_blocks), -1))
+    cache.pos.fill(0)
+
+
 def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, pad_token_id=0, graph=None, temperature=None, top_k=0,
-          top_p=1.0, poll=8, lengths=None, cache=None, token_budget=None):
+          top_p=1.0, poll=8, lengths=None, cache=None, token_budget=None, num_blocks=None, block_size=16, shared_prefix=0):
     """continuous batching: N requests through `slots` cache slots, a finished slot refilled at once from the queue while the
     others go on decoding.  prompts: a list of N int sequences, or (N, P) right-padded ids (an array or a tensor) with lengths=;
     max_new_tokens: an int, or N ints - a budget per request.  Returns (out (N, G) int32 with G = the largest budget, filled with
@@ -1266,7 +1346,16 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
     (slots, chunk) rows.  A decoding slot takes one row; the rows left go to the prefilling slots in slot order, in pieces of at
     most `chunk` (chunked prefill under a per-step token budget; csrc/serve_packed.hip, the packed launch of csrc/extend.hip).
     Eight decoding slots cost 8 rows of every Linear, not 8 * chunk.  Greedy results are the same tokens; `stats` gains
-    `token_budget`.  Without it everything is as it was."""
+    `token_budget`.  Without it everything is as it was.
+    num_blocks=N (or cache= an nn.PagedKVCache): the cache is PAGED - the keys and values lie in N blocks of `block_size` positions
+    per layer, shared by all slots, in place of slots * capacity rows.  A request is admitted when the blocks of its whole life
+    (prompt and budget) are free, holds exactly those, and returns them when it ends (csrc/serve_paged.hip; the attention launch
+    reads the rows through the slot's table, csrc/paged.hip).  With few blocks fewer requests run at once - more steps, the same
+    tokens.  N must hold the largest request.  shared_prefix=L declares that the first L tokens of every prompt are equal
+    (asserted): their keys and values are computed ONCE, into F = min(L // block_size, (shortest prompt - 1) // block_size) full
+    blocks that every slot's table names and nobody writes again, and every request starts at position F * block_size.  The step
+    has the launches of the step without paging and is captured once with graph=; `stats` gains `num_blocks`, `block_size` and
+    `prefix_blocks`.  token_budget= together with paging is refused.  Without num_blocks and a paged cache everything is as it was."""
     weight = model.bert.embeddings.word_embeddings.weight
     cls = weight.__class__
     layer0 = model.bert.encoder.layer[0].attention.self
@@ -1285,6 +1374,21 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
     assert budgets.shape == (n,) and (budgets >= 1).all(), "serve: max_new_tokens is an int >= 1 or one per request"
     assert int(poll) == poll and poll >= 1 and slots >= 1 and chunk >= 1
     positions = model.bert.embeddings.position_embeddings.weight.shape[0]
+    paged, prefix_blocks = num_blocks is not None or isinstance(cache, nn.PagedKVCache), 0
+    if paged:
+        assert token_budget is None, "serve: token_budget= (token-packed steps) together with a paged cache (num_blocks= / nn.PagedKVCache) is not supported"
+        if cache is None:
+            assert int(block_size) == block_size and block_size >= 1 and int(num_blocks) == num_blocks and num_blocks >= 1
+            cache = nn.PagedKVCache(len(model.bert.encoder.layer), int(slots), int(num_blocks), int(block_size), layer0.h * layer0.d,
+                                    int(-(-int((lengths + budgets - 1).max()) // int(block_size))), like=weight)
+        assert isinstance(cache, nn.PagedKVCache), "serve: num_blocks= makes its own nn.PagedKVCache, or takes one as cache=, got a %s" % type(cache).__name__
+        shared = int(shared_prefix)
+        assert shared == shared_prefix and 0 <= shared <= int(lengths.min()) and (padded[:, :shared] == padded[:1, :shared]).all(), \
+            "serve: shared_prefix=%s declares the first tokens of every prompt equal: they are not, or a prompt is shorter" % (shared_prefix,)
+        # full blocks only, and every request keeps a prompt token of its own
+        prefix_blocks = min(shared // cache.block_size, (int(lengths.min()) - 1) // cache.block_size)
+    else:
+        assert not shared_prefix, "serve: shared_prefix= goes with a paged cache (num_blocks=)"
     if cache is None:
         cache = nn.KVCache(len(model.bert.encoder.layer), int(slots), int((lengths + budgets - 1).max()), layer0.h * layer0.d, like=weight, per_row=True)
     assert cache.batch == slots, "serve: the cache has %d rows for %d slots" % (cache.batch, slots)
@@ -1292,10 +1396,14 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
     assert token_budget is None or (int(token_budget) == token_budget and token_budget >= slots), \
         "serve: token_budget is a number of token rows >= slots = %d (every decoding slot gets its token), got %s" % (slots, token_budget)
     packed = {} if token_budget is None else {"token_budget": int(token_budget)}
+    if paged:
+        packed = {"prefix_blocks": prefix_blocks}
     pool = nn.RequestPool(cache, padded, lengths, budgets, chunk, pad_token_id=pad_token_id, max_positions=positions, **packed)
     eos = None if eos_token_id is None else int(eos_token_id)
     sampler = None if temperature is None else (temperature, top_k, top_p)
     stats = {"steps": 0, "requests": n, "slots": int(slots), "chunk": chunk, **packed}
+    if paged:
+        stats.update(num_blocks=cache.num_blocks, block_size=cache.block_size)
 
     def done():
         # the poll: one word read every `poll` steps, and at the step count no schedule exceeds (every request alone in turn)
@@ -1307,6 +1415,8 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
         return finished == n
 
     with light.no_grad():
+        if prefix_blocks:
+            fill_shared_prefix(model, pool, padded[0, :prefix_blocks * cache.block_size])
         pool.admit(eos)
         serve_step(model, pool, sampler, eos)
         stats["steps"] = 1
@@ -1335,6 +1445,10 @@ if __name__ == "__main__":
         if not cpu:
             lm.map_parameters(lambda t: t.hip())
         requests = [np.random.randint(0, TINY["vocab_size"], np.random.randint(4, 48)) for _ in range(n_requests)]
+        if "--shared-prefix" in sys.argv:
+            # every prompt behind one common prefix (a system prompt) of that many tokens
+            common = np.random.randint(0, TINY["vocab_size"], option("--shared-prefix", int, 0))
+            requests = [np.concatenate([common, p]) for p in requests]
         new = [int(x) for x in np.random.randint(4, 32, n_requests)]
         recorded = None
         if "--graph" in sys.argv and not cpu:
@@ -1347,6 +1461,9 @@ if __name__ == "__main__":
         t0 = time.perf_counter()
         if "--token-budget" in sys.argv:
             sampling["token_budget"] = option("--token-budget", int, None)
+        if "--num-blocks" in sys.argv:
+            sampling.update(num_blocks=option("--num-blocks", int, None), block_size=option("--block-size", int, 16),
+                            shared_prefix=option("--shared-prefix", int, 0))
         (tokens, counts), info = serve(lm, requests, new, slots=n_slots, chunk=piece, eos_token_id=option("--eos", int, None), graph=recorded, **sampling)
         tokens, counts = tokens.numpy(), counts.numpy()             # the first read of anything but the poll word
         seconds = time.perf_counter() - t0
@@ -1354,6 +1471,9 @@ if __name__ == "__main__":
             n_requests, min(map(len, requests)), max(map(len, requests)), min(new), max(new), n_slots, info["chunk"],
             " under a budget of %d token rows a step" % info["token_budget"] if "token_budget" in info else "", info["steps"], int(counts.sum()),
             1e3 * seconds, "step captured once, %d kernels" % recorded.kernel_count() if recorded else "eager steps"))
+        if "num_blocks" in info:
+            print("paged cache: %d blocks of %d positions per layer, %d of them a prefix shared by every request" % (
+                info["num_blocks"], info["block_size"], info["prefix_blocks"]))
         for r in range(min(n_requests, 8)):
             print("request %d: %s" % (r, " ".join(str(i) for i in tokens[r, :counts[r]])))
         sys.exit(0)

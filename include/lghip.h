@@ -788,6 +788,47 @@ int lg_serve_commit_packed_i32(const int32_t* nxt, int64_t nxt_pitch, const int3
                                int32_t* ids, int32_t* position_ids,  /* (T) dense each */
                                int32_t* last,                        /* (slots) */
                                int64_t slots, int64_t T, int64_t chunk, int64_t capacity, int32_t eos_id);   /* eos_id < 0: none */
+/* ---- a paged key / value cache: block tables, a device allocator, a shared prefix (csrc/paged.hip, serve_paged.hip) -------------
+ * lg_attention_extend_paged_f32: lg_attention_extend_counts_f32 with the caches POOLS of num_blocks blocks of B = 1 << log2_block
+ * rows (pool row r at x + r * ldc, no batch pitch; 4 <= B <= 128) and `block_table`, (batch, max_blocks) dense int32 words in
+ * device memory: position j of batch element b is pool row block_table[b, j >> log2_block] * B + (j & (B - 1)), for the keys
+ * j < t that are streamed and for the count[b] new rows written at t ..; capacity = max_blocks * B <= 512.  Element b is bit for
+ * bit (o, p, the new rows' bytes) what the counts entry gives on a contiguous (capacity, width) cache that holds the same rows.
+ * Each workgroup reads its element's table once and checks words 0 .. ceil((t + count) / B) - 1 before it forms an address: a
+ * word outside 0 .. num_blocks - 1 makes the element bad like a bad position (nothing written, status flag raised, the other
+ * elements computed); the words behind may hold anything and are not used.  No row below t is written, so two elements may name
+ * the same block where it lies wholly below both positions; a block no table names is not touched.  Refused (LG_EINVAL): as
+ * the counts entry, B / max_blocks / num_blocks outside their ranges, and any overlap of what is written (pools, o, p) with
+ * another operand (pools, new rows, pos, count, block_table, o, p), or of pos with count. */
+int lg_attention_extend_paged_f32(const float* q, int64_t ldq, int64_t sbq, const float* k_new, int64_t ldk, int64_t sbk,
+                                  const float* v_new, int64_t ldv, int64_t sbv,
+                                  float* k_pool, float* v_pool, int64_t ldc,      /* (num_blocks * B, heads*D) rows each */
+                                  const int32_t* pos, const int32_t* count,       /* (batch) each */
+                                  const int32_t* block_table,                     /* (batch, max_blocks) dense */
+                                  float* o, int64_t ldo, int64_t sbo, float* p, int64_t batch, int64_t heads, int64_t m,
+                                  int64_t max_blocks, int64_t num_blocks, int64_t log2_block, int64_t D, float scale,
+                                  const float* mask, int64_t sbm);
+/* lg_serve_commit_paged_i32: lg_serve_commit_i32 over a paged cache (csrc/serve_paged.hip); capacity = max_blocks << log2_block.
+ * The definition is the loop of `CpuTensor.serve_commit_paged` (autograd/cpu/ops.py).  `free_stack` (num_blocks + 1): word 0 the
+ * number n of free blocks, words 1 .. n their indices, the top at word n; held (slots): the blocks a slot's table names;
+ * F = prefix_blocks: blocks 0 .. F - 1 are shared by every request and never on the stack.  A slot whose request has just
+ * finished pushes block_table[s, F .. held[s] - 1] (slot order, table order), its row becomes -1 and held[s] = 0.  Free slots
+ * are then offered the waiting requests in slot and queue order: request r needs ceil((prompt_len[r] + budget[r] - 1) / B) - F
+ * blocks; the first that needs more than the stack holds ends the admission of this commit (no overtaking); otherwise the slot
+ * pops them into table words F .., takes 0 .. F - 1 in front, held[s] = F + need, and starts at position F * B with the prompt's
+ * tokens F * B ...  Raises the status flag (count[s] = 0, nothing else of the slot written): the bounds of lg_serve_commit_i32,
+ * held outside 0 .. max_blocks, a released word outside 0 .. num_blocks - 1, free_stack[0] leaving 0 .. num_blocks, a request
+ * with need < 0, F + need > max_blocks or no prompt token behind the prefix.  One workgroup, one thread per slot. */
+int lg_serve_commit_paged_i32(const int32_t* nxt, int64_t nxt_pitch, const int32_t* prompts, int64_t prompt_pitch, int64_t P,
+                              const int32_t* prompt_len, const int32_t* budget, int32_t* out, int64_t out_pitch, int64_t G,
+                              int32_t* out_len, int32_t* queue, int64_t N,
+                              int32_t* req, int32_t* pos, int32_t* count,   /* (slots) each */
+                              int32_t* ids, int32_t* position_ids,  /* (slots, m) dense each */
+                              int32_t* last,                        /* (slots) */
+                              int32_t* block_table,                 /* (slots, max_blocks) dense */
+                              int32_t* held, int32_t* free_stack,   /* (slots), (num_blocks + 1) */
+                              int64_t slots, int64_t m, int64_t max_blocks, int64_t num_blocks, int64_t log2_block,
+                              int64_t prefix_blocks, int32_t eos_id);   /* eos_id < 0: none */
 /* The bookkeeping of one step of speculative decoding by prompt lookup in one launch (csrc/speculate.hip): one workgroup of 256
  * threads per row, 1 <= batch < 2^24.  The definition is the loop of `CpuTensor.speculate_commit` (autograd/cpu/ops.py), for each
  * row r on its own: (1) done[r] != 0: count[r] = 0, nothing else.  (2) c = count[r], p = pos[r]; unless 1 <= c <= m, p >= 0 and

@@ -638,6 +638,137 @@ def _check_serve_commit_packed(nxt, prompts, prompt_len, budget, out, out_len, q
 CpuTensor.serve_commit_packed = _serve_commit_packed
 
 
+def _serve_commit_paged(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last, block_table, held, free,
+                        block_size, prefix_blocks=0, eos=None):
+    """ nxt.serve_commit_paged(prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last,
+    block_table, held, free, block_size, prefix_blocks=0, eos=None): `serve_commit` over a PAGED cache (nn.PagedKVCache), in place
+    and outside the tape - the definition of the op.  block_table (b, max_blocks): word n of row s is the pool block that holds
+    positions n * B .. n * B + B - 1 of slot s, -1 = none; held (b,): the blocks a slot's table names; free (num_blocks + 1,): word
+    0 the number n of free blocks, words 1 .. n their indices, a stack whose top is word n.  B = block_size, F = prefix_blocks
+    (host ints): blocks 0 .. F - 1 hold a prefix every request shares.  capacity = max_blocks * B.  Every other operand is
+    `serve_commit`'s.  Two passes over the slots, each in slot order:
+      1. Step 1 of `serve_commit`.  A slot whose request has just finished then RELEASES its blocks: block_table[s, F ..
+         held[s] - 1] are pushed in table order (free[1 + free[0]] = block, free[0] += 1), its whole table row becomes -1 and
+         held[s] = 0.
+      2. ADMISSION: a free slot (one just released included) while queue[0] < N is offered r = queue[0], which needs
+         need = ceil((prompt_len[r] + budget[r] - 1) / B) - F blocks.  need > free[0]: admission stops for this commit - this
+         slot and every later free slot stay free, whatever the requests behind r need.  Otherwise queue[0] += 1, the slot pops
+         block_table[s, F + i] = free[free[0]], free[0] -= 1 for i = 0 .. need - 1, takes block_table[s, :F] = 0 .. F - 1,
+         held[s] = F + need, t = F * B and n = min(m, prompt_len[r] - t) tokens prompts[r, t:t + n].
+      Steps 3 and 4 of `serve_commit` follow for every slot.
+    Bounds, on top of `serve_commit`'s: a releasing slot whose held is outside 0 .. max_blocks or that names a block outside
+    0 .. num_blocks - 1 in the words it releases; free[0] outside 0 .. num_blocks before the commit (every releasing slot and every
+    offered request) or behind the pushes of all releasing slots together (every releasing slot); an offered request with
+    need < 0, F + need > max_blocks, or no prompt token at or behind F * B (it leaves the queue all the same).  Such a slot gets
+    count[s] = 0 and nothing else of it is written - no block is pushed or popped for it; the call raises IndexError after every
+    other slot has been committed. """
+    b, m, N = _check_serve_commit(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last, 1, eos)
+    MB, NB, B, F = _check_paged_state("serve_commit_paged", b, block_table, held, free, block_size, prefix_blocks)
+    arrays = [t.data for t in (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last, block_table, held, free)]
+    assert not any(np.shares_memory(x, y) for i, x in enumerate(arrays) for y in arrays[i + 1:]), "serve_commit_paged: two operands overlap"
+    new, P, G = nxt.data.reshape(b), prompts.shape[1], out.shape[1]
+    eos, capacity = (-1 if eos is None else int(eos)), MB * B
+    table, stack = block_table.data, free.data
+    stack_ok = 0 <= int(stack[0]) <= NB
+    state = []                      # per slot: [r, t, n, row, fault, finished]
+    for s in range(b):
+        r, t, n, row, fault, finished = int(req.data[s]), 0, 0, (), False, False
+        if r >= 0:
+            t = int(pos.data[s]) + int(count.data[s])
+            if r >= N or t < 0 or t > capacity:
+                fault = True
+            elif t < int(prompt_len.data[r]):
+                n = np.minimum(m, int(prompt_len.data[r]) - t).item()
+                fault = t + n > P
+                row = () if fault else prompts.data[r, t:t + n]
+            else:
+                g = int(out_len.data[r])
+                if g < 0 or g >= G:
+                    fault = True
+                else:
+                    out.data[r, g], out_len.data[r] = new[s], g + 1
+                    if (eos >= 0 and int(new[s]) == eos) or g + 1 == int(budget.data[r]):
+                        queue.data[1] += 1
+                        r, finished = -1, True
+                    else:
+                        n, row = 1, new[s:s + 1]
+        state.append([r, t, n, row, fault, finished])
+    # the release: which slots may push is settled first (the bounds of each, then the room for all of them together)
+    pushes = {}
+    for s in range(b):
+        if state[s][5]:
+            h = int(held.data[s])
+            if stack_ok and 0 <= h <= MB and all(0 <= int(e) < NB for e in table[s, F:h]):
+                pushes[s] = [int(e) for e in table[s, F:h]]
+            else:
+                state[s][4] = True
+    if stack_ok and int(stack[0]) + len([e for p in pushes.values() for e in p]) > NB:
+        for s in pushes:
+            state[s][4] = True
+        pushes = {}
+    for s in sorted(pushes):
+        for e in pushes[s]:
+            stack[1 + stack[0]] = e
+            stack[0] += 1
+        table[s, :], held.data[s] = -1, 0
+    # the admission
+    stopped = False
+    for s in range(b):
+        r, t, n, row, fault, _ = state[s]
+        if fault or r >= 0:
+            continue
+        t = 0
+        if not stopped and 0 <= int(queue.data[0]) < N:
+            k = int(queue.data[0])
+            need = -(-(int(prompt_len.data[k]) + int(budget.data[k]) - 1) // B) - F
+            n0 = np.minimum(m, int(prompt_len.data[k]) - F * B).item()
+            if not stack_ok or need < 0 or F + need > MB or n0 < 1 or F * B + n0 > P:
+                queue.data[0] += 1
+                fault = True
+            elif need > int(stack[0]):
+                stopped = True
+            else:
+                queue.data[0] += 1
+                for i in range(need):
+                    table[s, F + i] = stack[stack[0]]
+                    stack[0] -= 1
+                table[s, :F], held.data[s] = np.arange(F), F + need
+                r, t, n = k, F * B, n0
+                row = prompts.data[r, t:t + n]
+        state[s][:5] = r, t, n, row, fault
+    bad = []
+    for s in range(b):
+        r, t, n, row, fault, _ = state[s]
+        if fault or t + n > capacity:
+            count.data[s] = 0
+            bad.append(s)
+            continue
+        req.data[s], pos.data[s], count.data[s] = r, t, n
+        ids.data[s, :n], ids.data[s, n:] = row, 0
+        position_ids.data[s, :n], position_ids.data[s, n:] = t + np.arange(n), 0
+        last.data[s] = s * m + (n - 1 if n > 0 else 0)
+    if bad:
+        raise IndexError("serve_commit_paged: slot %d (of %d that did) would leave the cache, its prompt, its row of out or the block pool" % (bad[0], len(bad)))
+
+
+def _check_paged_state(name, b, block_table, held, free, block_size, prefix_blocks):
+    """the paging operands of `serve_commit_paged`, on any backend; returns (max_blocks, num_blocks, B, F)"""
+    i32 = np.dtype(np.int32)
+    assert len(block_table.shape) == 2 and block_table.shape[0] == b and tuple(held.shape) == (b,) and len(free.shape) == 1 and free.shape[0] >= 2 \
+        and all(np.dtype(t.dtype) == i32 for t in (block_table, held, free)), \
+        "%s: block_table (b, max_blocks), held (b,) and free (num_blocks + 1,) are int32 - got %s" % (
+            name, [(str(t.dtype), tuple(t.shape)) for t in (block_table, held, free)])
+    MB, NB = block_table.shape[1], free.shape[0] - 1
+    assert int(block_size) == block_size and 4 <= block_size <= 128 and block_size & (block_size - 1) == 0 and 1 <= MB and MB * block_size <= 512, \
+        "%s: block_size is a power of two within 4 .. 128 and max_blocks * block_size <= 512, got %s and %d blocks per table" % (name, block_size, MB)
+    assert int(prefix_blocks) == prefix_blocks and 0 <= prefix_blocks <= MB and prefix_blocks <= NB, \
+        "%s: prefix_blocks is an int within 0 .. max_blocks = %d and 0 .. num_blocks = %d, got %s" % (name, MB, NB, prefix_blocks)
+    return MB, NB, int(block_size), int(prefix_blocks)
+
+
+CpuTensor.serve_commit_paged = _serve_commit_paged
+
+
 def _speculate_commit(tgt, ids, count, position_ids, out_ids, pos, end, done, stats, draft, max_ngram=3, min_ngram=1, eos=None):
     """ tgt.speculate_commit(ids, count, position_ids, out_ids, pos, end, done, stats, draft, max_ngram=3, min_ngram=1, eos=None):
     the bookkeeping of one step of speculative decoding by prompt lookup, in place and outside the tape - the definition of the

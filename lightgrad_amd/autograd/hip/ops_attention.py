@@ -505,6 +505,54 @@ def _launch_extend_packed(name, q2, k2, v2, T, k_cache, v_cache, pos, cu, m_max,
     return p
 
 
+def _block_table(name, block_table, block_size, count, pos, rows, k_pool, v_pool):
+    """the `block_table=` / `block_size=` operands of the extend ops as the paged launch reads them: (table, B).  int32 (b, max_blocks)
+    next to (b, m, width) token rows, pools (num_blocks, B, width), a count and a pos of shape (b,); dense, apart from the pools, pos
+    and count"""
+    assert block_table is not None and block_size is not None and count is not None, \
+        "%s: a paged cache takes block_table=, block_size= and count= together" % name
+    B = int(block_size)
+    assert B == block_size and 4 <= B <= 128 and B & (B - 1) == 0, "%s: block_size is a power of two within 4 .. 128, got %s" % (name, block_size)
+    b, width = rows[0], rows[2]
+    assert isinstance(block_table, HipTensor) and block_table._dtype == _I32 and len(block_table._shape) == 2 and block_table._shape[0] == b \
+        and 1 <= block_table._shape[1] and block_table._shape[1] * B <= 512, \
+        "%s: block_table is an int32 HipTensor (batch, max_blocks) = (%d, *) with max_blocks * block_size <= 512, got %s %s" % (
+            name, b, getattr(block_table, "_dtype", type(block_table).__name__), getattr(block_table, "_shape", ""))
+    for c in (k_pool, v_pool):
+        assert isinstance(c, HipTensor) and c._dtype == _F32 and len(c._shape) == 3 and c._shape[0] >= 1 and c._shape[1] == B and c._shape[2] == width, \
+            "%s: the pools are float32 (num_blocks, block_size, width) = (*, %d, %d) tensors, got %s" % (name, B, width, getattr(c, "_shape", c))
+        assert not c.requires_grad, "%s: a cache is state, not a parameter (requires_grad must be False)" % name
+    assert k_pool._shape == v_pool._shape and k_pool._strides == v_pool._strides, "%s: the two pools must have one shape and one layout" % name
+    st = k_pool._strides
+    # the kernel writes rows in place and addresses the pool as (num_blocks * B) rows of one pitch
+    assert st[2] == 1 and st[1] % 4 == 0 and st[1] >= width and (k_pool._shape[0] == 1 or st[0] == B * st[1]) and k_pool._byte_offset % 16 == 0 \
+        and v_pool._byte_offset % 16 == 0, "%s: pool rows must be contiguous, 16-byte aligned and of one pitch across the blocks (strides %s)" % (name, st)
+    assert isinstance(pos, HipTensor) and pos._dtype == _I32 and pos._shape == (b,), "%s: a paged cache takes an int32 pos of shape (batch,) = (%d,)" % (name, b)
+    count = _token_counts(name, count, pos, b, k_pool, v_pool)
+    assert not _shares_bytes(k_pool, v_pool), "%s: the two pools overlap" % name
+    for other in (k_pool, v_pool, pos, count):
+        assert not _shares_bytes(block_table, other), "%s: block_table overlaps a pool, pos or count" % name
+        assert other is count or other is pos or not _shares_bytes(pos, other), "%s: pos overlaps a pool" % name
+    return (block_table if block_table.is_contiguous() else block_table.contiguous()), B
+
+
+def _launch_extend_paged(name, q3, k3, v3, m, k_pool, v_pool, pos, count, block_table, B, out, heads, scale, mask, probs):
+    """q3, k3, v3: (address, row pitch, batch pitch); out: (b, m, width) dense.  Returns the probabilities (b, heads, m, capacity) or None"""
+    b, max_blocks = block_table._shape
+    num_blocks, _, width = k_pool._shape
+    capacity = max_blocks * B
+    count = count if b == 1 or count._strides[0] == 1 else count.contiguous()
+    pos = pos if b == 1 or pos._strides[0] == 1 else pos.contiguous()
+    mask3 = _key_mask(mask, b, capacity, name)
+    p = HipTensor.empty((b, heads, m, capacity), requires_grad=False) if probs else None
+    flush_lazy_readers(k_pool)
+    flush_lazy_readers(v_pool)
+    _l.check(_l.lib().lg_attention_extend_paged_f32(*q3, *k3, *v3, k_pool.ptr, v_pool.ptr, k_pool._strides[1], pos.ptr, count.ptr, block_table.ptr,
+                                                    out.ptr, width, m * width, p.ptr if probs else None, b, heads, m, max_blocks, num_blocks,
+                                                    B.bit_length() - 1, width // heads, float(scale), mask3[1], mask3[2]))
+    return p
+
+
 def extend_attention_supported(q, heads, capacity, m_max=None):
     """(m_max: the call is token-packed - `cu=` -: (1, T, heads * d) rows with any T >= 1 and pieces of at most m_max, default
     min(T, capacity))
@@ -515,7 +563,8 @@ def extend_attention_supported(q, heads, capacity, m_max=None):
             and bool(_l.lib().lg_attention_extend_supported(sh[1] if m_max is None else m_max, capacity, sh[2] // heads)))
 
 
-def extend_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False, count=None, cu=None, m_max=None):
+def extend_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False, count=None, cu=None, m_max=None,
+                     block_table=None, block_size=None):
     """ attention of m NEW tokens per sequence against a filled key / value cache, one launch (lg_attention_extend_f32): with t =
     the int32 word `pos` holds ON THE DEVICE (`pos` of shape (b,): a position per sequence, t = pos[r] for sequence r, everything
     below per sequence - lg_attention_extend_rows_f32; a sequence with t + m beyond the cache writes nothing, the others are computed), rows i of k_new / v_new become rows t + i of the caches (b, capacity, heads * d) and
@@ -533,10 +582,30 @@ def extend_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0,
     cu[s] .. cu[s + 1] - 1 (at most m_max= of them, default min(T, capacity); T may exceed the capacity) and is computed as by the
     call on those rows alone against its own cache rows at t = pos[s]; rows >= cu[slots] of the result are +0.0.
     `.attention_probs` is (heads, T, capacity); mask is (slots, capacity) or (1, capacity).  cu= and count= exclude each other.
-    Without cu= the call is the one it was. """
+    Without cu= the call is the one it was.
+    block_table= (an int32 HipTensor (b, max_blocks)) with block_size= B (a power of two, 4 .. 128) and count=: the cache is PAGED -
+    one launch of lg_attention_extend_paged_f32.  k_cache / v_cache are pools (num_blocks, B, width) and position j of sequence r
+    is row j % B of block block_table[r, j // B]; capacity = max_blocks * B.  Sequence r is computed bit for bit as the count=
+    call computes it on a contiguous cache that holds the same rows.  A word outside 0 .. num_blocks - 1 among the first
+    ceil((t + n) / B) of a row makes that sequence write nothing and raises IndexError at the next synchronisation; the words
+    behind are not used.  Without block_table= the call is the one it was. """
     name = "extend_attention"
     _inference_only(name, q, k_new, v_new)
     _require_f32(q, k_new, v_new)
+    if block_table is not None or block_size is not None:
+        assert cu is None and m_max is None, "%s: block_table= (a paged cache) goes with count=, not with cu= (token-packed rows)" % name
+        block_table, B = _block_table(name, block_table, block_size, count, pos, q._shape, k_cache, v_cache)
+        capacity = block_table._shape[1] * B
+        assert q._shape == k_new._shape == v_new._shape and extend_attention_supported(q, heads, capacity), \
+            "%s: unsupported shapes %s / %s / %s with %d heads and a paged cache of %d positions" % (name, q._shape, k_new._shape, v_new._shape, heads, capacity)
+        m = q._shape[1]
+        (q, ldq, sbq), (k_new, ldk, sbk), (v_new, ldv, sbv) = (_token_rows_in_place(t, name) for t in (q, k_new, v_new))
+        out = HipTensor.empty(q._shape, requires_grad=False)
+        p = _launch_extend_paged(name, (q.ptr, ldq, sbq), (k_new.ptr, ldk, sbk), (v_new.ptr, ldv, sbv), m, k_cache, v_cache, pos, count, block_table, B, out,
+                                 heads, scale, mask, probs)
+        if probs:
+            out.attention_probs = p
+        return out
     if cu is not None:
         assert len(k_cache._shape) == 3 and len(q._shape) == 3, "%s: expected (1, T, width) rows and (slots, capacity, width) caches" % name
         cu, slots, m_max = _packed_rows(name, cu, count, pos, q._shape, k_cache, v_cache, m_max)
@@ -567,15 +636,40 @@ def extend_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0,
 
 
 def self_attention_extend(x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False, count=None, cu=None,
-                          m_max=None):
+                          m_max=None, block_table=None, block_size=None):
     """ the one-node form of an append's attention: the three projections of the m new tokens in ONE launch (lg_gemm_multi3_f32,
     as in `self_attention`) into a (b, m, 3 * width) buffer that the extend launch reads in place - two launches per layer.
     x: (b, m, hidden); everything else as for `extend_attention`, `count=` included (the projections take all b * m rows) and
-    `cu=` / `m_max=` too: x is (1, T, hidden) then, the projection launch runs on the T rows, the packed launch reads them in place. """
+    `cu=` / `m_max=` too: x is (1, T, hidden) then, the projection launch runs on the T rows, the packed launch reads them in place.
+    block_table= / block_size= with count=: the caches are pools and the second launch is the paged one - still two per layer. """
     name = "self_attention_extend"
     _inference_only(name, x, wq, bq, wk, bk, wv, bv)
     _require_f32(x, wq, bq, wk, bk, wv, bv)
     assert cu is not None or m_max is None, "%s: m_max= goes with cu=" % name
+    paged = block_table is not None or block_size is not None
+    if paged:
+        assert cu is None, "%s: block_table= (a paged cache) goes with count=, not with cu= (token-packed rows)" % name
+        assert len(x._shape) == 3 and len(wq._shape) == 2, "%s: expected (b, m, hidden) rows and (width, hidden) weights" % name
+        block_table, B = _block_table(name, block_table, block_size, count, pos, (x._shape[0], x._shape[1], wq._shape[0]), k_cache, v_cache)
+        assert self_attention_extend_supported(x, wq, heads, block_table._shape[1] * B) and \
+            wq._shape == wk._shape == wv._shape and bq._shape == bk._shape == bv._shape == (wq._shape[0],), \
+            "%s: unsupported shapes %s with weights %s / %s / %s, %d heads and a paged cache of %d positions" % (
+                name, x._shape, wq._shape, wk._shape, wv._shape, heads, block_table._shape[1] * B)
+        b, m, hidden = x._shape
+        width = wq._shape[0]
+        x = x.contiguous()
+        ws, bs = [w.contiguous() for w in (wq, wk, wv)], [t.contiguous() for t in (bq, bk, bv)]
+        qkv = HipTensor.empty((b, m, 3 * width), requires_grad=False)
+        base = qkv.ptr
+        _l.check(_l.lib().lg_gemm_multi3_f32(0, 1, b * m, width, hidden, x.ptr, hidden, _ptr3(*(w.ptr for w in ws)), hidden,
+                                             _ptr3(base, base + 4 * width, base + 8 * width), 3 * width, _ptr3(*(t.ptr for t in bs))))
+        out = HipTensor.empty((b, m, width), requires_grad=False)
+        ld, sb = 3 * width, m * 3 * width
+        p = _launch_extend_paged(name, (base, ld, sb), (base + 4 * width, ld, sb), (base + 8 * width, ld, sb), m, k_cache, v_cache, pos, count, block_table,
+                                 B, out, heads, scale, mask, probs)
+        if probs:
+            out.attention_probs = p
+        return out
     if cu is not None:
         assert len(k_cache._shape) == 3 and len(x._shape) == 3, "%s: expected (1, T, hidden) rows and (slots, capacity, width) caches" % name
         cu, slots, m_max = _packed_rows(name, cu, count, pos, x._shape, k_cache, v_cache, m_max)
@@ -730,6 +824,48 @@ def serve_commit_packed(nxt, prompts, prompt_len, budget, out, out_len, queue, r
 
 
 HipTensor.serve_commit_packed = serve_commit_packed
+
+
+def serve_commit_paged(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last, block_table, held, free,
+                       block_size, prefix_blocks=0, eos=None):
+    """ nxt.serve_commit_paged(prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last,
+    block_table, held, free, block_size, prefix_blocks=0, eos=None): what `CpuTensor.serve_commit_paged` defines - `serve_commit`
+    over a paged cache: a finished slot pushes its blocks back on the `free` stack, a free slot is admitted only if the blocks its
+    request needs for its whole life are there and pops them into its row of `block_table` behind the `prefix_blocks` shared
+    ones - in ONE launch (lg_serve_commit_paged_i32, csrc/serve_paged.hip), in place and outside the tape.  Operands as for
+    `serve_commit`; block_table (slots, max_blocks), held (slots,) and free (num_blocks + 1,) are dense int32 HipTensors.  A slot
+    that would leave its bounds gets count 0, keeps its other bytes and raises IndexError at the next synchronisation.  No host
+    read: a captured step replays it as it stands. """
+    from ..cpu.ops import _check_serve_commit, _check_paged_state
+    name = "serve_commit_paged"
+    operands = (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last, block_table, held, free)
+    assert all(isinstance(t, HipTensor) for t in operands), "%s: every operand is a HipTensor" % name
+    b, m, N = _check_serve_commit(*operands[:13], 1, eos)
+    MB, NB, B, F = _check_paged_state(name, b, block_table, held, free, block_size, prefix_blocks)
+    if b > 1 and nxt._strides[0] < 1:
+        nxt = nxt.contiguous()
+    # what is only read may be copied once into a layout the launch addresses
+    if (prompts._shape[1] > 1 and prompts._strides[1] != 1) or (N > 1 and prompts._strides[0] < prompts._shape[1]):
+        prompts = prompts.contiguous()
+    prompt_len, budget = (t if N == 1 or t._strides[0] == 1 else t.contiguous() for t in (prompt_len, budget))
+    # the launch writes these where they lie: a layout it cannot address is an error, never a copy
+    assert all(t.is_contiguous() for t in (out_len, queue, req, pos, count, last, ids, position_ids, block_table, held, free)) and \
+        (out._shape[1] == 1 or out._strides[1] == 1) and (N == 1 or out._strides[0] >= out._shape[1]), \
+        "%s: out_len, queue, req, pos, count, last, ids, position_ids, block_table, held and free must be dense and the rows of out contiguous" % name
+    operands = (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last, block_table, held, free)
+    for i, x in enumerate(operands):
+        for y in operands[i + 1:]:
+            assert not _shares_bytes(x, y), "%s: two operands overlap" % name
+    for x in operands[4:]:
+        flush_lazy_readers(x)
+    P, G = prompts._shape[1], out._shape[1]
+    _l.check(_l.lib().lg_serve_commit_paged_i32(nxt.ptr, nxt._strides[0] if b > 1 else 1, prompts.ptr, prompts._strides[0] if N > 1 else P, P, prompt_len.ptr,
+                                                budget.ptr, out.ptr, out._strides[0] if N > 1 else G, G, out_len.ptr, queue.ptr, N, req.ptr, pos.ptr,
+                                                count.ptr, ids.ptr, position_ids.ptr, last.ptr, block_table.ptr, held.ptr, free.ptr, b, m, MB, NB,
+                                                B.bit_length() - 1, F, -1 if eos is None else int(eos)))
+
+
+HipTensor.serve_commit_paged = serve_commit_paged
 
 
 """ The bookkeeping of a speculative decoding step in one launch (csrc/speculate.hip) """

@@ -415,6 +415,73 @@ class KVCache(object):
         self.v[layer][:, :s] = v
 
 
+class PagedKVCache(object):
+    """the keys and values of a serving loop in fixed-size BLOCKS drawn from one pool, in place of `capacity` contiguous rows per
+    slot (KVCache): `k[i]`, `v[i]` are pools of shape (num_blocks, block_size, width) on the backend (and in the dtype) of `like`,
+    and `block_table`, int32 (slots, max_blocks), says where a slot's rows are - word n of row s is the pool block that holds
+    positions n * B .. n * B + B - 1 of slot s (B = block_size), -1 = none.  `held` (slots,) counts the blocks a slot's table
+    names; `free` (num_blocks + 1,) is the allocator, a stack on the device: word 0 the number n of free blocks, words 1 .. n their
+    indices, the top at word n.  `pos` (slots,) is the position of each slot's next token (`per_row` is True, `batch` = slots),
+    `positions(m)` what KVCache.positions is, `capacity` = max_blocks * block_size the most a slot can hold.  A slot holds the
+    blocks its request needs, not the worst request's; blocks below the positions of every slot that names them may be SHARED
+    (a common prompt prefix: `reset(prefix_blocks=F)` keeps blocks 0 .. F - 1 off the stack for it) - the attention launch never
+    writes below a slot's position.  block_size is a power of two, 4 <= B <= 128 (small blocks reach multi-block tables at tiny
+    shapes), and capacity <= 512, the extend kernel's limit.  Tables and stack are moved by ONE op per step,
+    `serve_commit_paged` (nn.RequestPool); the cache serves the `count=` append path only: `reorder`, the one-token decode route,
+    token-packed steps (`cu=`) and `generate` refuse it.  State, not parameters, like KVCache.  Not a class of the reference."""
+
+    per_row = True
+    num_beams = 1
+
+    def __init__(self, layers: int, slots: int, num_blocks: int, block_size: int, width: int, max_blocks: int, like=None):
+        cls = Tensor if like is None else type(like)
+        dtype = np.dtype(np.float32 if like is None else like.dtype)
+        assert layers >= 1 and slots >= 1 and num_blocks >= 1 and width >= 1 and max_blocks >= 1
+        assert int(block_size) == block_size and 4 <= block_size <= 128 and block_size & (block_size - 1) == 0, \
+            "PagedKVCache: block_size is a power of two within 4 .. 128, got %s" % (block_size,)
+        assert max_blocks * block_size <= 512, "PagedKVCache: max_blocks * block_size = %d positions exceed the 512 of the extend kernel" % (max_blocks * block_size)
+        self.layers, self.batch, self.slots, self.width = int(layers), int(slots), int(slots), int(width)
+        self.num_blocks, self.block_size, self.max_blocks = int(num_blocks), int(block_size), int(max_blocks)
+        self.capacity = self.max_blocks * self.block_size
+        shape = (self.num_blocks, self.block_size, self.width)
+        self.k = [cls.from_numpy(np.zeros(shape, dtype), requires_grad=False) for _ in range(self.layers)]
+        self.v = [cls.from_numpy(np.zeros(shape, dtype), requires_grad=False) for _ in range(self.layers)]
+        i32 = lambda a: cls.from_numpy(np.ascontiguousarray(a, np.int32), requires_grad=False)        # noqa: E731
+        self.block_table, self.held = i32(np.full((self.batch, self.max_blocks), -1)), i32(np.zeros(self.batch))
+        self.free, self.pos = i32(np.zeros(self.num_blocks + 1)), i32(np.zeros(self.batch))
+        self.prefix_blocks = 0
+        self.length, self.lengths = 0, np.zeros(self.batch, np.int64)
+        self._arange = {}
+        self.reset()
+
+    positions = KVCache.positions
+    advance = KVCache.advance           # (tests and tools move the positions by hand; `serve` leaves it to serve_commit_paged)
+
+    def reset(self, prefix_blocks: int = 0) -> None:
+        """forget every token and every block: positions 0, tables -1, held 0, and the stack holds blocks num_blocks - 1 down to
+        `prefix_blocks` - block `prefix_blocks` is popped first; blocks 0 .. prefix_blocks - 1 stay off it (the pools stay as they are)"""
+        F = int(prefix_blocks)
+        assert 0 <= F <= min(self.num_blocks, self.max_blocks), \
+            "PagedKVCache.reset: prefix_blocks within 0 .. min(num_blocks, max_blocks) = %d, got %s" % (min(self.num_blocks, self.max_blocks), prefix_blocks)
+        stack = np.zeros(self.num_blocks + 1, np.int32)
+        stack[0] = self.num_blocks - F
+        stack[1:1 + self.num_blocks - F] = np.arange(self.num_blocks - 1, F - 1, -1)
+        i32 = lambda a: type(self.pos).from_numpy(np.ascontiguousarray(a, np.int32), requires_grad=False)        # noqa: E731
+        self.free[:] = i32(stack)
+        self.block_table[:] = i32(np.full((self.batch, self.max_blocks), -1))
+        self.held.fill(0)
+        self.pos.fill(0)
+        self.prefix_blocks = F
+        self.length, self.lengths = 0, np.zeros(self.batch, np.int64)
+
+    def reorder(self, parent, num_beams=None) -> None:
+        raise NotImplementedError("PagedKVCache.reorder: beams copy rows between slots; the paged cache serves the count= append path only")
+
+    def pool_bytes(self) -> int:
+        """bytes of the key and value pools of every layer"""
+        return 2 * self.layers * self.num_blocks * self.block_size * self.width * np.dtype(self.k[0].dtype).itemsize
+
+
 class RequestPool(object):
     """the requests of a serving loop and the state of the cache slots that work through them (continuous batching): N prompts
     wait in a queue, each of the cache's `batch` slots holds one request at a time, and a slot whose request has finished takes
@@ -428,13 +495,19 @@ class RequestPool(object):
     `cache` must be per_row.  A request needs lengths[r] + budgets[r] - 1 cache rows (its last token is fed to nobody): checked
     here, on the host, against the capacity.  State, not parameters, like the cache.  Not a class of the reference."""
 
-    def __init__(self, cache, prompts, lengths, budgets, chunk: int, pad_token_id: int = 0, max_positions=None, token_budget=None):
+    def __init__(self, cache, prompts, lengths, budgets, chunk: int, pad_token_id: int = 0, max_positions=None, token_budget=None, prefix_blocks: int = 0):
         """max_positions: the model's position embeddings, if the caller knows them - the capacity must not exceed them.
         token_budget: None, or T >= slots - the steps are TOKEN-PACKED: ids and position_ids are (1, T), the step's tokens of all
         slots in one flat buffer, `cu` (slots + 1,) says which rows are whose, `last` names rows of the T, and `commit` is
         `serve_commit_packed`: a decoding slot takes one row, the prefilling slots share the rest in pieces of at most `chunk`.
-        `count` stays (pos + count is the commit's t).  Without it `cu` is None and everything is as it was"""
-        assert isinstance(cache, KVCache) and cache.per_row, "RequestPool takes a cache with a position per sequence: nn.KVCache(..., per_row=True)"
+        `count` stays (pos + count is the commit's t).  Without it `cu` is None and everything is as it was.
+        cache: an nn.PagedKVCache in place of a KVCache - `commit` is `serve_commit_paged`, which also moves the cache's tables
+        and its stack of free blocks; prefix_blocks: the blocks 0 .. F - 1 every request shares (they hold the first F * B tokens
+        of every prompt already; the pool resets the cache with them off the stack)"""
+        assert isinstance(cache, (KVCache, PagedKVCache)) and cache.per_row, \
+            "RequestPool takes a cache with a position per sequence: nn.KVCache(..., per_row=True) or nn.PagedKVCache"
+        self.paged = isinstance(cache, PagedKVCache)
+        assert not self.paged or token_budget is None, "RequestPool: token_budget= (token-packed steps) does not go with a PagedKVCache"
         assert max_positions is None or cache.capacity <= max_positions, \
             "RequestPool: a cache of %d positions exceeds the model's %s position embeddings" % (cache.capacity, max_positions)
         cls = type(cache.pos)
@@ -449,6 +522,20 @@ class RequestPool(object):
         assert (lengths + budgets - 1 <= cache.capacity).all(), \
             "RequestPool: a request of %d prompt tokens and %d new ones does not fit a cache of %d positions" % (
                 int(lengths[np.argmax(lengths + budgets)]), int(budgets[np.argmax(lengths + budgets)]), cache.capacity)
+        if self.paged:
+            # a request reserves the blocks of its whole life when it is admitted: each must fit a table, and the pool once the
+            # running requests have ended (the head of the queue is then always admitted); its own tokens start behind the prefix
+            B, F = cache.block_size, int(prefix_blocks)
+            need = -(-(lengths + budgets - 1) // B) - F
+            assert 0 <= F <= min(cache.max_blocks, cache.num_blocks), "RequestPool: prefix_blocks within 0 .. %d, got %s" % (min(cache.max_blocks, cache.num_blocks), prefix_blocks)
+            assert (need + F <= cache.max_blocks).all(), "RequestPool: a request needs %d blocks of %d positions, a table of the PagedKVCache has %d" % (
+                int(need.max()) + F, B, cache.max_blocks)
+            assert (need <= cache.num_blocks - F).all(), "RequestPool: a request needs %d blocks behind the %d shared ones, the pool of the PagedKVCache has %d in all" % (
+                int(need.max()), F, cache.num_blocks)
+            assert (F * B < lengths).all(), "RequestPool: a shared prefix of %d blocks of %d tokens leaves a prompt of %d tokens none of its own" % (F, B, int(lengths.min()))
+            self.prefix_blocks = F
+        else:
+            assert not prefix_blocks, "RequestPool: prefix_blocks= goes with a PagedKVCache"
         self.cache, self.requests, self.slots, self.chunk, self.pad_token_id = cache, n, cache.batch, int(chunk), int(pad_token_id)
         tensor = lambda a: cls.from_numpy(np.ascontiguousarray(a, np.int32), requires_grad=False)        # noqa: E731
         self.prompts, self.prompt_len, self.budget = tensor(prompts), tensor(lengths), tensor(budgets)
@@ -473,7 +560,10 @@ class RequestPool(object):
             self.ids, self.position_ids = tensor(np.zeros((1, self.token_budget))), tensor(np.zeros((1, self.token_budget)))
             self.cu = tensor(np.zeros(self.slots + 1))
             self.max_steps = int((lengths + budgets).sum())                        # a prompt token a step at the least: no schedule takes longer
-        cache.reset()
+        if self.paged:
+            cache.reset(prefix_blocks=self.prefix_blocks)
+        else:
+            cache.reset()
         cache.lengths = None            # the positions move on the device from here on: the host mirror is an upper bound only
         cache.length = cache.capacity
 
@@ -483,7 +573,12 @@ class RequestPool(object):
 
     def commit(self, nxt, eos=None) -> None:
         """one `serve_commit`: `nxt` (slots,) or (slots, 1) int32 are the tokens the step has just drawn (ignored for slots that
-        are free or prefilling); with a token budget, one `serve_commit_packed`"""
+        are free or prefilling); with a token budget, one `serve_commit_packed`; with a paged cache, one `serve_commit_paged`"""
+        if self.paged:
+            c = self.cache
+            nxt.serve_commit_paged(self.prompts, self.prompt_len, self.budget, self.out, self.out_len, self.queue, self.req, c.pos, self.count,
+                                   self.ids, self.position_ids, self.last, c.block_table, c.held, c.free, c.block_size, self.prefix_blocks, eos=eos)
+            return
         if self.cu is not None:
             nxt.serve_commit_packed(self.prompts, self.prompt_len, self.budget, self.out, self.out_len, self.queue, self.req, self.cache.pos,
                                     self.count, self.cu, self.ids, self.position_ids, self.last, self.cache.capacity, self.chunk, eos=eos)
