@@ -62,6 +62,7 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import lightgrad_amd as light  # noqa: E402
 import lightgrad_amd.nn as nn  # noqa: E402
+from lightgrad_amd.autograd.cpu.ops import bf16_round_array  # noqa: E402
 
 TINY = dict(hidden_size=128, intermediate_size=512, num_hidden_layers=2, num_attention_heads=2,
             vocab_size=30522, max_position_embeddings=512, type_vocab_size=2)
@@ -131,6 +132,13 @@ class BertEmbedding(nn.Module):
             # the backend's one-launch form of the line below: the mask is drawn where the LayerNorm kernel stores its row
             return e.layer_norm_dropout(self.LayerNorm.weight, self.LayerNorm.bias, self.dropout.p, self.LayerNorm.eps)
         return self.dropout(self.LayerNorm(e))
+
+
+def _bf16_refusal(cache):
+    """what a refusal of a paged cache adds for one that holds bfloat16 words: the form the refused route does take"""
+    if getattr(cache, "kv_dtype", None) != "bf16":
+        return ""
+    return " (kv_dtype=\"bf16\": a bf16 cache is a form of the paged one - this route takes a float32 nn.KVCache)"
 
 
 class BertSelfAttention(nn.Module):
@@ -224,9 +232,11 @@ class BertSelfAttention(nn.Module):
         probs = scores.softmax(axis=-1)
         return (probs @ v).transpose(0, 2, 1, 3).reshape(b, m, self.h * self.d), probs
 
-    def _counted_composite(self, hidden, attention_mask, cache, index, count):
+    def _counted_composite(self, hidden, attention_mask, cache, index, count, round_kv=False):
         """`_rows_composite` with a token count per sequence - the definition of `self_attention_extend(count=)`.  Positions and
-        counts are read from the tensors (whoever moved them: `advance`, `serve_commit`)"""
+        counts are read from the tensors (whoever moved them: `advance`, `serve_commit`).  round_kv (a bfloat16 cache,
+        `_paged_composite`): the step's keys and values enter as r(key(hidden)), r(value(hidden)), r = `bf16_round_array` (a
+        float64 tape rounds through float32, as r does); the queries are not rounded"""
         b, m = hidden.shape[0], hidden.shape[1]
         k_cache, v_cache = cache.k[index], cache.v[index]
         t, c = np.asarray(cache.pos.numpy(), np.int64), np.asarray(count.numpy(), np.int64)
@@ -234,6 +244,9 @@ class BertSelfAttention(nn.Module):
             "the cache holds %s of %d positions: no room for %s more of the %d rows given" % (t.tolist(), cache.capacity, c.tolist(), m)
         n = max(int((t + c).max()), 1)
         q, k, v = self.query(hidden), self.key(hidden), self.value(hidden)
+        if round_kv:
+            # on the host, by the definition itself (the composite reads positions and pools there anyway): any backend, any float dtype
+            k, v = (x.__class__.from_numpy(bf16_round_array(np.asarray(x.numpy())), requires_grad=False) for x in (k, v))
         for r in range(b):
             if c[r]:
                 k_cache[r:r + 1, int(t[r]):int(t[r] + c[r])] = k[r:r + 1, :int(c[r])]
@@ -261,8 +274,12 @@ class BertSelfAttention(nn.Module):
         block_size=)`: every slot's rows below its position are gathered from the pool through its table into a contiguous
         (slots, capacity, width) cache, `_counted_composite` runs on it, and the new rows t .. t + count - 1 of every slot are
         scattered back to the pool.  Positions, counts and the table are READ from the tensors (whoever moved them:
-        `serve_commit_paged`); a table word the slot reaches must name a block of the pool"""
+        `serve_commit_paged`); a table word the slot reaches must name a block of the pool.
+        A bfloat16 cache (`cache.kv_dtype == "bf16"`: int16 pools, the definition of `kv_dtype="bf16"`): the gather WIDENS
+        (`light.bf16_widen`, into the dtype of `hidden`), the step's keys and values enter the counted composite as r(.) of what
+        the projections produced, and the scatter writes `light.bf16_bits` - of values that are r(.) already, so exactly"""
         b, B, capacity = hidden.shape[0], cache.block_size, cache.capacity
+        bf16 = getattr(cache, "kv_dtype", None) == "bf16"
         t, c = np.asarray(cache.pos.numpy(), np.int64), np.asarray(count.numpy(), np.int64)
         table = np.asarray(cache.block_table.numpy(), np.int64)
         assert c.shape == (b,) and (c >= 0).all() and (t >= 0).all() and (t + c <= capacity).all(), \
@@ -277,6 +294,8 @@ class BertSelfAttention(nn.Module):
         rows = []
         for pool in pools:
             host = np.asarray(pool.numpy())
+            if bf16:
+                host = light.bf16_widen(host).astype(np.dtype(hidden.dtype))
             flat = np.zeros((b, capacity, cache.width), host.dtype)
             for r in range(b):
                 if t[r]:
@@ -286,11 +305,12 @@ class BertSelfAttention(nn.Module):
         class _Gathered(object):
             k, v, pos = [rows[0]], [rows[1]], cache.pos
         _Gathered.capacity = capacity
-        context, probs = self._counted_composite(hidden, attention_mask, _Gathered, 0, count)
+        context, probs = self._counted_composite(hidden, attention_mask, _Gathered, 0, count, round_kv=bf16)
+        words = [cls.from_numpy(light.bf16_bits(np.asarray(flat.numpy())), requires_grad=False) for flat in rows] if bf16 else rows
         for r in range(b):
             for j in range(int(t[r]), int(t[r] + c[r])):
                 block, at = int(table[r, j // B]), j % B
-                for pool, flat in zip(pools, rows):
+                for pool, flat in zip(pools, words):
                     pool[block:block + 1, at:at + 1] = flat[r:r + 1, j:j + 1]
         return context, probs
 
@@ -353,12 +373,15 @@ class BertSelfAttention(nn.Module):
         if isinstance(cache, nn.PagedKVCache):
             # the cache's rows lie in blocks of a pool: the fused route passes the table to the paged launch (still two launches
             # per layer), anything else gathers, runs the counted composite and scatters (`_paged_composite`, the definition)
-            assert count is not None and cu is None, "an nn.PagedKVCache serves the count= append path only (not cu=, not a step without count=)"
+            assert count is not None and cu is None, "an nn.PagedKVCache serves the count= append path only (not cu=, not a step without count=)" + \
+                _bf16_refusal(cache)
             b = hidden.shape[0]
             mask_ok = attention_mask is None or (attention_mask.dtype == np.float32 and not attention_mask.requires_grad and
                                                  tuple(attention_mask.shape) in ((b, cache.capacity), (1, cache.capacity)))
             if hasattr(hidden, "self_attention_extend") and mask_ok and hidden.self_attention_extend_supported(self.query.weight, self.h, cache.capacity):
                 extra = {"mask": attention_mask} if attention_mask is not None else {}
+                if getattr(cache, "kv_dtype", None) is not None:
+                    extra["kv_dtype"] = cache.kv_dtype          # int16 pools of bfloat16 words: the bf16 paged launch
                 context = hidden.self_attention_extend(self.query.weight, self.query.bias, self.key.weight, self.key.bias, self.value.weight,
                                                        self.value.bias, cache.k[index], cache.v[index], cache.pos, heads=self.h,
                                                        scale=math.sqrt(self.d) ** -1, count=count, block_table=cache.block_table,
@@ -572,7 +595,7 @@ class BertModel(nn.Module):
         if isinstance(cache, nn.PagedKVCache):
             assert append and count is not None and cu is None, \
                 "an nn.PagedKVCache serves the count= append path only: model(ids, cache=paged, append=True, count=...) - not the prompt / one-token " \
-                "decode route (no append=True) and not token-packed rows (cu=)"
+                "decode route (no append=True) and not token-packed rows (cu=)" + _bf16_refusal(cache)
         if cache is not None:
             if append:
                 if cu is not None:
@@ -1203,7 +1226,8 @@ def generate(model, ids, max_new_tokens, attention_mask=None, cache=None, graph=
     picked on the device.  beams: a dict that receives `sequences` (b, w, columns) and `scores` (b, w) as tensors, and `steps`.
     lengths=, eos_token_id=, pad_token_id= and prefill_chunk= work as on the per-row path; temperature, speculate= and append=True
     are refused.  num_beams=1 is greedy decoding, up to near-ties (its scores come from a different launch than argmax's logits)."""
-    assert not isinstance(cache, nn.PagedKVCache), "generate: an nn.PagedKVCache serves the count= append path only (serve): pass an nn.KVCache"
+    assert not isinstance(cache, nn.PagedKVCache), "generate: an nn.PagedKVCache serves the count= append path only (serve): pass an nn.KVCache" + \
+        _bf16_refusal(cache)
     if num_beams is not None:
         assert int(num_beams) == num_beams and 1 <= num_beams <= 8, "num_beams is an int within 1 .. 8 (got %s)" % (num_beams,)
         assert temperature is None, "beam search is deterministic: temperature= (sampling beams) is not supported with num_beams="
@@ -1324,7 +1348,7 @@ def fill_shared_prefix(model, pool, tokens):
 
 
 def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, pad_token_id=0, graph=None, temperature=None, top_k=0,
-          top_p=1.0, poll=8, lengths=None, cache=None, token_budget=None, num_blocks=None, block_size=16, shared_prefix=0):
+          top_p=1.0, poll=8, lengths=None, cache=None, token_budget=None, num_blocks=None, block_size=16, shared_prefix=0, kv_dtype=None):
     """continuous batching: N requests through `slots` cache slots, a finished slot refilled at once from the queue while the
     others go on decoding.  prompts: a list of N int sequences, or (N, P) right-padded ids (an array or a tensor) with lengths=;
     max_new_tokens: an int, or N ints - a budget per request.  Returns (out (N, G) int32 with G = the largest budget, filled with
@@ -1355,7 +1379,12 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
     (asserted): their keys and values are computed ONCE, into F = min(L // block_size, (shortest prompt - 1) // block_size) full
     blocks that every slot's table names and nobody writes again, and every request starts at position F * block_size.  The step
     has the launches of the step without paging and is captured once with graph=; `stats` gains `num_blocks`, `block_size` and
-    `prefix_blocks`.  token_budget= together with paging is refused.  Without num_blocks and a paged cache everything is as it was."""
+    `prefix_blocks`.  token_budget= together with paging is refused.  Without num_blocks and a paged cache everything is as it was.
+    kv_dtype="bf16" (with num_blocks=, or cache= an nn.PagedKVCache(kv_dtype="bf16")): the pools hold bfloat16 words, half the bytes
+    (csrc/paged_bf16.hip).  Every key and value is attended to as r of what the projection produced (r = `bf16_round_array`),
+    whichever step, chunk or shared prefix brought it in, so greedy tokens still depend on a request's own data only - but they
+    are those of the rounded model, NOT promised to be the float32 run's.  `stats` gains `kv_dtype` and `pool_bytes` with any
+    paged cache.  kv_dtype= without paging is refused: the contiguous nn.KVCache is float32."""
     weight = model.bert.embeddings.word_embeddings.weight
     cls = weight.__class__
     layer0 = model.bert.encoder.layer[0].attention.self
@@ -1376,12 +1405,14 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
     positions = model.bert.embeddings.position_embeddings.weight.shape[0]
     paged, prefix_blocks = num_blocks is not None or isinstance(cache, nn.PagedKVCache), 0
     if paged:
-        assert token_budget is None, "serve: token_budget= (token-packed steps) together with a paged cache (num_blocks= / nn.PagedKVCache) is not supported"
+        assert token_budget is None, "serve: token_budget= (token-packed steps) together with a paged cache (num_blocks= / nn.PagedKVCache) is not supported" + (
+            " - kv_dtype=\"bf16\" included: the packed launch reads a float32 nn.KVCache" if kv_dtype == "bf16" or getattr(cache, "kv_dtype", None) == "bf16" else "")
         if cache is None:
             assert int(block_size) == block_size and block_size >= 1 and int(num_blocks) == num_blocks and num_blocks >= 1
             cache = nn.PagedKVCache(len(model.bert.encoder.layer), int(slots), int(num_blocks), int(block_size), layer0.h * layer0.d,
-                                    int(-(-int((lengths + budgets - 1).max()) // int(block_size))), like=weight)
+                                    int(-(-int((lengths + budgets - 1).max()) // int(block_size))), like=weight, kv_dtype=kv_dtype)
         assert isinstance(cache, nn.PagedKVCache), "serve: num_blocks= makes its own nn.PagedKVCache, or takes one as cache=, got a %s" % type(cache).__name__
+        assert kv_dtype is None or cache.kv_dtype == kv_dtype, "serve: kv_dtype=%r and a cache= whose kv_dtype is %r" % (kv_dtype, cache.kv_dtype)
         shared = int(shared_prefix)
         assert shared == shared_prefix and 0 <= shared <= int(lengths.min()) and (padded[:, :shared] == padded[:1, :shared]).all(), \
             "serve: shared_prefix=%s declares the first tokens of every prompt equal: they are not, or a prompt is shorter" % (shared_prefix,)
@@ -1389,6 +1420,8 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
         prefix_blocks = min(shared // cache.block_size, (int(lengths.min()) - 1) // cache.block_size)
     else:
         assert not shared_prefix, "serve: shared_prefix= goes with a paged cache (num_blocks=)"
+        assert kv_dtype is None, "serve: kv_dtype=%r goes with a paged cache (num_blocks=, or cache= an nn.PagedKVCache(kv_dtype=\"bf16\")): the contiguous " \
+            "nn.KVCache is float32" % (kv_dtype,)
     if cache is None:
         cache = nn.KVCache(len(model.bert.encoder.layer), int(slots), int((lengths + budgets - 1).max()), layer0.h * layer0.d, like=weight, per_row=True)
     assert cache.batch == slots, "serve: the cache has %d rows for %d slots" % (cache.batch, slots)
@@ -1403,7 +1436,7 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
     sampler = None if temperature is None else (temperature, top_k, top_p)
     stats = {"steps": 0, "requests": n, "slots": int(slots), "chunk": chunk, **packed}
     if paged:
-        stats.update(num_blocks=cache.num_blocks, block_size=cache.block_size)
+        stats.update(num_blocks=cache.num_blocks, block_size=cache.block_size, kv_dtype=cache.kv_dtype, pool_bytes=cache.pool_bytes())
 
     def done():
         # the poll: one word read every `poll` steps, and at the step count no schedule exceeds (every request alone in turn)
@@ -1464,6 +1497,8 @@ if __name__ == "__main__":
         if "--num-blocks" in sys.argv:
             sampling.update(num_blocks=option("--num-blocks", int, None), block_size=option("--block-size", int, 16),
                             shared_prefix=option("--shared-prefix", int, 0))
+            if "--kv-dtype" in sys.argv:
+                sampling["kv_dtype"] = option("--kv-dtype", str, None)           # bf16: the pools hold bfloat16 words, half the bytes
         (tokens, counts), info = serve(lm, requests, new, slots=n_slots, chunk=piece, eos_token_id=option("--eos", int, None), graph=recorded, **sampling)
         tokens, counts = tokens.numpy(), counts.numpy()             # the first read of anything but the poll word
         seconds = time.perf_counter() - t0
@@ -1472,8 +1507,8 @@ if __name__ == "__main__":
             " under a budget of %d token rows a step" % info["token_budget"] if "token_budget" in info else "", info["steps"], int(counts.sum()),
             1e3 * seconds, "step captured once, %d kernels" % recorded.kernel_count() if recorded else "eager steps"))
         if "num_blocks" in info:
-            print("paged cache: %d blocks of %d positions per layer, %d of them a prefix shared by every request" % (
-                info["num_blocks"], info["block_size"], info["prefix_blocks"]))
+            print("paged cache: %d blocks of %d positions per layer, %d of them a prefix shared by every request; %s pools of %d bytes" % (
+                info["num_blocks"], info["block_size"], info["prefix_blocks"], info["kv_dtype"] or "float32", info["pool_bytes"]))
         for r in range(min(n_requests, 8)):
             print("request %d: %s" % (r, " ".join(str(i) for i in tokens[r, :counts[r]])))
         sys.exit(0)

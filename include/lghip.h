@@ -808,6 +808,22 @@ int lg_attention_extend_paged_f32(const float* q, int64_t ldq, int64_t sbq, cons
                                   float* o, int64_t ldo, int64_t sbo, float* p, int64_t batch, int64_t heads, int64_t m,
                                   int64_t max_blocks, int64_t num_blocks, int64_t log2_block, int64_t D, float scale,
                                   const float* mask, int64_t sbm);
+/* lg_attention_extend_paged_bf16_f32 (csrc/paged_bf16.hip): lg_attention_extend_paged_f32 over pools of BFLOAT16 words, 2 bytes
+ * an element (ldc counts elements).  With r(x) = x rounded to bfloat16 (nearest, ties to even, kept as fp32), bits(x) = the
+ * upper 16 bits of r(x) ((u >> 16) | 0x0040 for a NaN) and widen(w) = w << 16 as fp32: o and p are bit for bit what
+ * lg_attention_extend_paged_f32 returns on (q, r(k_new), r(v_new), widen(pools), ...), and the launch writes bits(k_new[b, i]) /
+ * bits(v_new[b, i]) to the pool rows of positions t .. t + count[b] - 1 and no other byte of the pools.  Every key and value
+ * is attended to as r of what it was given as, whether an earlier launch stored it or this one brings it; q is not rounded.
+ * Bounds as lg_attention_extend_paged_f32.  Refused (LG_EINVAL, nothing launched): as lg_attention_extend_paged_f32, with the
+ * pools 8-byte aligned, ldc a multiple of 4 elements and >= heads * D, and the overlaps taken at 2 bytes a pool element. */
+int lg_attention_extend_paged_bf16_f32(const float* q, int64_t ldq, int64_t sbq, const float* k_new, int64_t ldk, int64_t sbk,
+                                       const float* v_new, int64_t ldv, int64_t sbv,
+                                       uint16_t* k_pool, uint16_t* v_pool, int64_t ldc,  /* (num_blocks * B, heads*D) rows each */
+                                       const int32_t* pos, const int32_t* count,       /* (batch) each */
+                                       const int32_t* block_table,                     /* (batch, max_blocks) dense */
+                                       float* o, int64_t ldo, int64_t sbo, float* p, int64_t batch, int64_t heads, int64_t m,
+                                       int64_t max_blocks, int64_t num_blocks, int64_t log2_block, int64_t D, float scale,
+                                       const float* mask, int64_t sbm);
 /* lg_serve_commit_paged_i32: lg_serve_commit_i32 over a paged cache (csrc/serve_paged.hip); capacity = max_blocks << log2_block.
  * The definition is the loop of `CpuTensor.serve_commit_paged` (autograd/cpu/ops.py).  `free_stack` (num_blocks + 1): word 0 the
  * number n of free blocks, words 1 .. n their indices, the top at word n; held (slots): the blocks a slot's table names;

@@ -13,3 +13,8 @@ def bf16_round(t):
     """every value of `t` rounded to bfloat16 (nearest, ties to even) and kept as float32: the rounding `dot_bf16` /
     `linear_bf16` apply to their operands (autograd/cpu/ops.py: bf16_round_array).  A tensor of t's backend, no gradient."""
     return t.bf16_round()
+
+
+# the storage form of a bfloat16 key / value cache (nn.PagedKVCache(kv_dtype="bf16")): array functions, THE definition for both
+# backends - bf16_bits(x) the int16 words of r(x), bf16_widen(w) the float32 values they stand for
+from .autograd.cpu.ops import bf16_bits, bf16_widen  # noqa: E402

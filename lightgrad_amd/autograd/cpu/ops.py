@@ -177,6 +177,23 @@ def bf16_round_array(x):
     return np.where(np.isnan(f), f, r).astype(x.dtype if x.dtype.kind == "f" else np.float32)
 
 
+def bf16_bits(x):
+    """bits(x): the upper 16 bits of r(x) = `bf16_round_array`(x) as int16 - the word a bfloat16 key / value cache stores.  A NaN
+    stores (u >> 16) | 0x0040: a NaN whatever its low half held.  A float64 array goes through float32, as in r."""
+    f = np.ascontiguousarray(np.asarray(x), dtype=np.float32)
+    u = f.view(np.uint32)
+    r = (u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)
+    return np.where(np.isnan(f), (u >> np.uint32(16)) | np.uint32(0x0040), r).astype(np.uint16).view(np.int16)
+
+
+def bf16_widen(w):
+    """widen(w): the float32 whose upper 16 bits are the int16 word w and whose lower 16 are 0 - what a word of a bfloat16 cache
+    stands for.  widen(bits(x)) == r(x) bit for bit for every x that is no NaN."""
+    w = np.ascontiguousarray(np.asarray(w))
+    assert w.dtype == np.int16, "bf16_widen takes int16 words, got %s" % w.dtype
+    return (w.view(np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
+
+
 def _require_bf16_operands(name, *operands):
     for t in operands:
         if t is not None and t.dtype != np.float32 and not (t.dtype == np.float64 and CpuTensor.default_dtype == np.float64):

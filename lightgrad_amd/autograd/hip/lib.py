@@ -173,6 +173,8 @@ PROTOTYPES = {
                                            c_int64] + [c_void_p] * 7 + [c_int64] * 4 + [ctypes.c_int32]),
     "lg_attention_extend_paged_f32": (c_int, [c_void_p, c_int64, c_int64] * 3 + [c_void_p, c_void_p, c_int64] + [c_void_p, c_void_p, c_void_p]
                                       + [c_void_p, c_int64, c_int64] + [c_void_p] + [c_int64] * 7 + [c_float] + [c_void_p, c_int64]),
+    "lg_attention_extend_paged_bf16_f32": (c_int, [c_void_p, c_int64, c_int64] * 3 + [c_void_p, c_void_p, c_int64] + [c_void_p, c_void_p, c_void_p]
+                                           + [c_void_p, c_int64, c_int64] + [c_void_p] + [c_int64] * 7 + [c_float] + [c_void_p, c_int64]),
     "lg_serve_commit_paged_i32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
                                           c_int64] + [c_void_p] * 9 + [c_int64] * 6 + [ctypes.c_int32]),
     "lg_speculate_commit_i32": (c_int, [c_void_p] * 5 + [c_int64, c_int64] + [c_void_p] * 4 + [c_int64] * 5 + [ctypes.c_int32]),

@@ -505,10 +505,22 @@ def _launch_extend_packed(name, q2, k2, v2, T, k_cache, v_cache, pos, cu, m_max,
     return p
 
 
-def _block_table(name, block_table, block_size, count, pos, rows, k_pool, v_pool):
+_I16 = np.dtype(np.int16)
+
+
+def _block_table(name, block_table, block_size, count, pos, rows, k_pool, v_pool, kv_dtype=None):
     """the `block_table=` / `block_size=` operands of the extend ops as the paged launch reads them: (table, B).  int32 (b, max_blocks)
     next to (b, m, width) token rows, pools (num_blocks, B, width), a count and a pos of shape (b,); dense, apart from the pools, pos
-    and count"""
+    and count.  kv_dtype: None - float32 pools -, or "bf16" - int16 pools of bfloat16 words; each form refuses the other's pools"""
+    assert kv_dtype in (None, "bf16"), "%s: kv_dtype is None (float32 pools) or \"bf16\" (int16 pools of bfloat16 words), got %r" % (name, kv_dtype)
+    for c in (k_pool, v_pool):
+        if isinstance(c, HipTensor) and c._dtype == _I16 and kv_dtype is None:
+            raise TypeError("%s: int16 pools hold bfloat16 words and go with kv_dtype=\"bf16\" (lg_attention_extend_paged_bf16_f32); "
+                            "without the keyword the pools are float32" % name)
+        if isinstance(c, HipTensor) and c._dtype == _F32 and kv_dtype == "bf16":
+            raise TypeError("%s: kv_dtype=\"bf16\" takes int16 pools of bfloat16 words (nn.PagedKVCache(..., kv_dtype=\"bf16\")); float32 pools "
+                            "go without the keyword (lg_attention_extend_paged_f32)" % name)
+    pool_dtype, align = (_I16, 8) if kv_dtype == "bf16" else (_F32, 16)
     assert block_table is not None and block_size is not None and count is not None, \
         "%s: a paged cache takes block_table=, block_size= and count= together" % name
     B = int(block_size)
@@ -519,14 +531,14 @@ def _block_table(name, block_table, block_size, count, pos, rows, k_pool, v_pool
         "%s: block_table is an int32 HipTensor (batch, max_blocks) = (%d, *) with max_blocks * block_size <= 512, got %s %s" % (
             name, b, getattr(block_table, "_dtype", type(block_table).__name__), getattr(block_table, "_shape", ""))
     for c in (k_pool, v_pool):
-        assert isinstance(c, HipTensor) and c._dtype == _F32 and len(c._shape) == 3 and c._shape[0] >= 1 and c._shape[1] == B and c._shape[2] == width, \
-            "%s: the pools are float32 (num_blocks, block_size, width) = (*, %d, %d) tensors, got %s" % (name, B, width, getattr(c, "_shape", c))
+        assert isinstance(c, HipTensor) and c._dtype == pool_dtype and len(c._shape) == 3 and c._shape[0] >= 1 and c._shape[1] == B and c._shape[2] == width, \
+            "%s: the pools are %s (num_blocks, block_size, width) = (*, %d, %d) tensors, got %s" % (name, pool_dtype, B, width, getattr(c, "_shape", c))
         assert not c.requires_grad, "%s: a cache is state, not a parameter (requires_grad must be False)" % name
     assert k_pool._shape == v_pool._shape and k_pool._strides == v_pool._strides, "%s: the two pools must have one shape and one layout" % name
     st = k_pool._strides
     # the kernel writes rows in place and addresses the pool as (num_blocks * B) rows of one pitch
-    assert st[2] == 1 and st[1] % 4 == 0 and st[1] >= width and (k_pool._shape[0] == 1 or st[0] == B * st[1]) and k_pool._byte_offset % 16 == 0 \
-        and v_pool._byte_offset % 16 == 0, "%s: pool rows must be contiguous, 16-byte aligned and of one pitch across the blocks (strides %s)" % (name, st)
+    assert st[2] == 1 and st[1] % 4 == 0 and st[1] >= width and (k_pool._shape[0] == 1 or st[0] == B * st[1]) and k_pool._byte_offset % align == 0 \
+        and v_pool._byte_offset % align == 0, "%s: pool rows must be contiguous, %d-byte aligned and of one pitch across the blocks (strides %s)" % (name, align, st)
     assert isinstance(pos, HipTensor) and pos._dtype == _I32 and pos._shape == (b,), "%s: a paged cache takes an int32 pos of shape (batch,) = (%d,)" % (name, b)
     count = _token_counts(name, count, pos, b, k_pool, v_pool)
     assert not _shares_bytes(k_pool, v_pool), "%s: the two pools overlap" % name
@@ -537,7 +549,8 @@ def _block_table(name, block_table, block_size, count, pos, rows, k_pool, v_pool
 
 
 def _launch_extend_paged(name, q3, k3, v3, m, k_pool, v_pool, pos, count, block_table, B, out, heads, scale, mask, probs):
-    """q3, k3, v3: (address, row pitch, batch pitch); out: (b, m, width) dense.  Returns the probabilities (b, heads, m, capacity) or None"""
+    """q3, k3, v3: (address, row pitch, batch pitch); out: (b, m, width) dense.  Returns the probabilities (b, heads, m, capacity) or None.
+    int16 pools (bfloat16 words; `_block_table` has matched them with kv_dtype=) take the bf16 entry, the same argument list"""
     b, max_blocks = block_table._shape
     num_blocks, _, width = k_pool._shape
     capacity = max_blocks * B
@@ -547,9 +560,10 @@ def _launch_extend_paged(name, q3, k3, v3, m, k_pool, v_pool, pos, count, block_
     p = HipTensor.empty((b, heads, m, capacity), requires_grad=False) if probs else None
     flush_lazy_readers(k_pool)
     flush_lazy_readers(v_pool)
-    _l.check(_l.lib().lg_attention_extend_paged_f32(*q3, *k3, *v3, k_pool.ptr, v_pool.ptr, k_pool._strides[1], pos.ptr, count.ptr, block_table.ptr,
-                                                    out.ptr, width, m * width, p.ptr if probs else None, b, heads, m, max_blocks, num_blocks,
-                                                    B.bit_length() - 1, width // heads, float(scale), mask3[1], mask3[2]))
+    entry = _l.lib().lg_attention_extend_paged_bf16_f32 if k_pool._dtype == _I16 else _l.lib().lg_attention_extend_paged_f32
+    _l.check(entry(*q3, *k3, *v3, k_pool.ptr, v_pool.ptr, k_pool._strides[1], pos.ptr, count.ptr, block_table.ptr,
+                   out.ptr, width, m * width, p.ptr if probs else None, b, heads, m, max_blocks, num_blocks,
+                   B.bit_length() - 1, width // heads, float(scale), mask3[1], mask3[2]))
     return p
 
 
@@ -564,7 +578,7 @@ def extend_attention_supported(q, heads, capacity, m_max=None):
 
 
 def extend_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False, count=None, cu=None, m_max=None,
-                     block_table=None, block_size=None):
+                     block_table=None, block_size=None, kv_dtype=None):
     """ attention of m NEW tokens per sequence against a filled key / value cache, one launch (lg_attention_extend_f32): with t =
     the int32 word `pos` holds ON THE DEVICE (`pos` of shape (b,): a position per sequence, t = pos[r] for sequence r, everything
     below per sequence - lg_attention_extend_rows_f32; a sequence with t + m beyond the cache writes nothing, the others are computed), rows i of k_new / v_new become rows t + i of the caches (b, capacity, heads * d) and
@@ -588,13 +602,20 @@ def extend_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0,
     is row j % B of block block_table[r, j // B]; capacity = max_blocks * B.  Sequence r is computed bit for bit as the count=
     call computes it on a contiguous cache that holds the same rows.  A word outside 0 .. num_blocks - 1 among the first
     ceil((t + n) / B) of a row makes that sequence write nothing and raises IndexError at the next synchronisation; the words
-    behind are not used.  Without block_table= the call is the one it was. """
+    behind are not used.  Without block_table= the call is the one it was.
+    kv_dtype="bf16" (with block_table=): the pools are int16 tensors of BFLOAT16 words - one launch of
+    lg_attention_extend_paged_bf16_f32.  With r = `bf16_round_array`, the result (and `.attention_probs`) is bit for bit that of
+    the paged call on r(k_new), r(v_new) and `bf16_widen` of the pools, and the new rows are stored as `bf16_bits`: a key counts as
+    r of it whichever call brought it in; q is not rounded.  int16 pools without the keyword, or the keyword with float32 pools,
+    are a TypeError. """
     name = "extend_attention"
     _inference_only(name, q, k_new, v_new)
     _require_f32(q, k_new, v_new)
+    assert kv_dtype is None or block_table is not None, "%s: kv_dtype= goes with a paged cache (block_table=, block_size=, count=): the contiguous " \
+        "caches are float32" % name
     if block_table is not None or block_size is not None:
         assert cu is None and m_max is None, "%s: block_table= (a paged cache) goes with count=, not with cu= (token-packed rows)" % name
-        block_table, B = _block_table(name, block_table, block_size, count, pos, q._shape, k_cache, v_cache)
+        block_table, B = _block_table(name, block_table, block_size, count, pos, q._shape, k_cache, v_cache, kv_dtype)
         capacity = block_table._shape[1] * B
         assert q._shape == k_new._shape == v_new._shape and extend_attention_supported(q, heads, capacity), \
             "%s: unsupported shapes %s / %s / %s with %d heads and a paged cache of %d positions" % (name, q._shape, k_new._shape, v_new._shape, heads, capacity)
@@ -636,21 +657,24 @@ def extend_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0,
 
 
 def self_attention_extend(x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False, count=None, cu=None,
-                          m_max=None, block_table=None, block_size=None):
+                          m_max=None, block_table=None, block_size=None, kv_dtype=None):
     """ the one-node form of an append's attention: the three projections of the m new tokens in ONE launch (lg_gemm_multi3_f32,
     as in `self_attention`) into a (b, m, 3 * width) buffer that the extend launch reads in place - two launches per layer.
     x: (b, m, hidden); everything else as for `extend_attention`, `count=` included (the projections take all b * m rows) and
     `cu=` / `m_max=` too: x is (1, T, hidden) then, the projection launch runs on the T rows, the packed launch reads them in place.
-    block_table= / block_size= with count=: the caches are pools and the second launch is the paged one - still two per layer. """
+    block_table= / block_size= with count=: the caches are pools and the second launch is the paged one - still two per layer;
+    kv_dtype="bf16": int16 pools of bfloat16 words, the second launch is lg_attention_extend_paged_bf16_f32 (see `extend_attention`). """
     name = "self_attention_extend"
     _inference_only(name, x, wq, bq, wk, bk, wv, bv)
     _require_f32(x, wq, bq, wk, bk, wv, bv)
     assert cu is not None or m_max is None, "%s: m_max= goes with cu=" % name
+    assert kv_dtype is None or block_table is not None, "%s: kv_dtype= goes with a paged cache (block_table=, block_size=, count=): the contiguous " \
+        "caches are float32" % name
     paged = block_table is not None or block_size is not None
     if paged:
         assert cu is None, "%s: block_table= (a paged cache) goes with count=, not with cu= (token-packed rows)" % name
         assert len(x._shape) == 3 and len(wq._shape) == 2, "%s: expected (b, m, hidden) rows and (width, hidden) weights" % name
-        block_table, B = _block_table(name, block_table, block_size, count, pos, (x._shape[0], x._shape[1], wq._shape[0]), k_cache, v_cache)
+        block_table, B = _block_table(name, block_table, block_size, count, pos, (x._shape[0], x._shape[1], wq._shape[0]), k_cache, v_cache, kv_dtype)
         assert self_attention_extend_supported(x, wq, heads, block_table._shape[1] * B) and \
             wq._shape == wk._shape == wv._shape and bq._shape == bk._shape == bv._shape == (wq._shape[0],), \
             "%s: unsupported shapes %s with weights %s / %s / %s, %d heads and a paged cache of %d positions" % (

@@ -1,6 +1,8 @@
-// The kernel body of the extend launches, attn_extend_body<D, PACKED, PAGED>, and the host checks their entries share: included by
-// extend.hip (the (b, m) entries and the token-packed one, PAGED = false) and by paged.hip (lg_attention_extend_paged_f32)
+// The kernel body of the extend launches, attn_extend_body<D, PACKED, PAGED, KV16>, and the host checks their entries share: included
+// by extend.hip (the (b, m) entries and the token-packed one, PAGED = false), by paged.hip (lg_attention_extend_paged_f32) and by
+// paged_bf16.hip (lg_attention_extend_paged_bf16_f32, KV16 = true: pools of bfloat16 words)
 #pragma once
+#include <type_traits>
 #include "attention_common.h"
 
 namespace lg {
@@ -71,6 +73,54 @@ __device__ __forceinline__ void seam_load_paged(af32x4 (&v)[N], const float* poo
         v[i] = *reinterpret_cast<const af32x4*>(src + (f % Q) * 4);
     }
 }
+// KV16: the pools hold bfloat16 words, the upper halves of fp32 values.  r(x) = `bf16_round_array` of autograd/cpu/ops.py as the
+// 16-bit word it keeps: nearest, ties to even, +-0 and +-Inf kept, a finite value beyond the largest bfloat16 -> +-Inf (the carry
+// runs into the exponent), a NaN -> (u >> 16) | 0x0040, a NaN whatever its low half held.  The one function of the seam load (a
+// key of the same launch is attended to as r of it) and of the row store (what a later launch reads is that very word, widened)
+__device__ __forceinline__ uint32_t bf16_word(float x) {
+    const uint32_t u = __float_as_uint(x);
+    return (u & 0x7FFFFFFFu) > 0x7F800000u ? (u >> 16) | 0x0040u : (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+typedef uint32_t au32x2 __attribute__((ext_vector_type(2)));
+// seam_load_paged with a pool of bfloat16 words (ldc counts them): the two sources take loads of different sizes, so a lane issues
+// BOTH, each from an address that is always valid, and seam_settle16 selects.  The pool side is ONE 8-byte load of 4 words from
+// row tab[j >> lb] << lb | (j & mask) (8-byte aligned: the entry checks the pools and ldc % 4) - for a key j >= t that is a row of a
+// checked word, or of block 0 behind the reach: inside the pool, its words dropped; the new-token side is the 16-byte fp32 load
+// from row j - t clamped to 0 .. m - 1 as in seam_load.  No branch, nothing converted here: all 2 N loads are in flight behind the
+// MFMAs of the chunk before.  (A branch per lane around the two loads made the compiler wait for every load in flight in front
+// of each pool load - the two sides shared destination registers -: profiles/paged_bf16.md)
+template <int D, int N>
+__device__ __forceinline__ void seam_load_paged16(af32x4 (&v)[N], au32x2 (&w)[N], const uint16_t* pool, int64_t ldc, const int* tab, int lb,
+                                                  const float* fresh, int64_t ldn, int c0, int t, int m) {
+    constexpr int Q = D / 4;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const int f = threadIdx.x + i * 256, j = c0 + f / Q;
+        const int jn = j - t < 0 ? 0 : (j - t < m ? j - t : m - 1);
+        const int row = (tab[(j >> lb) & (kPagedMaxTable - 1)] << lb) | (j & ((1 << lb) - 1));
+        w[i] = *reinterpret_cast<const au32x2*>(pool + int64_t(row) * ldc + (f % Q) * 4);
+        v[i] = *reinterpret_cast<const af32x4*>(fresh + int64_t(jn) * ldn + (f % Q) * 4);
+    }
+}
+// ... and what it left in the registers -> the fp32 values the tiles take: for a key j < t the 4 pool words widened (w << 16),
+// for a key t <= j < keys = t + m the 4 floats passed through r.  In registers, in front of seam_store with the c0 the load had
+template <int D, int N>
+__device__ __forceinline__ void seam_settle16(af32x4 (&v)[N], const au32x2 (&w)[N], int c0, int t, int keys) {
+    constexpr int Q = D / 4;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const int f = threadIdx.x + i * 256, j = c0 + f / Q;
+        // branches, not a select: the 64 lanes of a wave hold 64 / Q neighbouring keys, so only the waves that hold one of the
+        // launch's own keys run the rounding (some 40 VALU instructions a register quad) - one wave in a decoding step
+        if (j < t) {
+            v[i] = af32x4{__uint_as_float(w[i][0] << 16), __uint_as_float(w[i][0] & 0xFFFF0000u), __uint_as_float(w[i][1] << 16),
+                          __uint_as_float(w[i][1] & 0xFFFF0000u)};
+        } else if (j < keys) {                                        // (a key >= t + m does not exist: seam_store writes 0 for it)
+            v[i] = af32x4{__uint_as_float(bf16_word(v[i][0]) << 16), __uint_as_float(bf16_word(v[i][1]) << 16),
+                          __uint_as_float(bf16_word(v[i][2]) << 16), __uint_as_float(bf16_word(v[i][3]) << 16)};
+        }
+    }
+}
 // ... and registers -> LDS: keys [t + m, Kend) of the chunk ZERO
 template <int D, int N>
 __device__ __forceinline__ void seam_store(const af32x4 (&v)[N], float* dst, int pitch, int c0, int keys, int Kend) {
@@ -117,9 +167,17 @@ __device__ __forceinline__ void packed_clear(const ExtendArgs& a, int slots) {
 // table.  The slot's table (at most 128 words) is read ONCE into LDS by the first two waves, each word of the slot's reach
 // 0 .. ceil((t + count) / B) - 1 checked against the pool on its way (one barrier with a vote, uniform over the workgroup: a bad
 // word makes the slot bad like a bad position), the words behind the reach replaced by 0; every row address is formed from LDS
-template <int D, bool PACKED, bool PAGED = false>
+// KV16 (attn_paged_bf16<D>, lg_attention_extend_paged_bf16_f32, csrc/paged_bf16.hip): the paged form over pools of bfloat16 words -
+// `k_cache` / `v_cache` of the arguments point to uint16_t then and ldc counts them.  Three places differ: the streamed keys
+// (seam_load_paged16: 8 bytes per lane from the pool), their way into LDS (seam_settle16: widened, the launch's own keys rounded),
+// and the store of the block's new rows (packed by the same r, 8 bytes per lane).  The tiles, the MFMAs, the softmax, the bias
+// row, the fold order and the +0.0 rows are the text below, in fp32: the launch computes bit for bit what the paged one computes
+// on the rounded new rows and the widened pools.  With KV16 = false nothing of it is compiled
+template <int D, bool PACKED, bool PAGED = false, bool KV16 = false>
 __device__ __forceinline__ void attn_extend_body(const ExtendArgs& a) {
     static_assert(!(PACKED && PAGED), "the paged launch is the counts form");
+    static_assert(PAGED || !KV16, "the bfloat16 pools are a form of the paged launch");
+    using CacheT = std::conditional_t<KV16, uint16_t, float>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int m = a.m, C = a.capacity, Cp = round32(C), PP = Cp + 4;
     constexpr int PQ = D + 4, PV = D + 8, Q4 = D / 4;
@@ -198,12 +256,14 @@ __device__ __forceinline__ void attn_extend_body(const ExtendArgs& a) {
     const int qrows = real - q0 < 32 ? real - q0 : 32;                // rows of this block that exist
     const int keys = t + real;                                        // keys that exist in this launch
     const int Kend = round32(t + q0 + qrows);                         // the key columns the chunk loops cover (<= Cp)
-    const float* kc = a.k_cache + (PAGED ? 0 : int64_t(b) * a.sbc) + head * D;
-    const float* vc = a.v_cache + (PAGED ? 0 : int64_t(b) * a.sbc) + head * D;
+    const CacheT* kc = reinterpret_cast<const CacheT*>(a.k_cache) + (PAGED ? 0 : int64_t(b) * a.sbc) + head * D;
+    const CacheT* vc = reinterpret_cast<const CacheT*>(a.v_cache) + (PAGED ? 0 : int64_t(b) * a.sbc) + head * D;
+    [[maybe_unused]] au32x2 rw[KV16 ? NA : 1];                        // KV16: the pool side of the streamed chunk, 4 bfloat16 words a lane
     // the streamed keys / values of a chunk: the contiguous rows of the element, or the pool through the table
-    auto stream = [&](af32x4 (&v)[NA], const float* cache, const float* fresh, int64_t ldn, int c0) {
-        if constexpr (PAGED) seam_load_paged<D, NA>(v, cache, a.ldc, Tab, lb, fresh, ldn, c0, t, real);
-        else                 seam_load<D, NA>(v, cache, a.ldc, fresh, ldn, c0, t, real);
+    auto stream = [&](af32x4 (&v)[NA], const CacheT* cache, const float* fresh, int64_t ldn, int c0) {
+        if constexpr (KV16)       seam_load_paged16<D, NA>(v, rw, cache, a.ldc, Tab, lb, fresh, ldn, c0, t, real);
+        else if constexpr (PAGED) seam_load_paged<D, NA>(v, cache, a.ldc, Tab, lb, fresh, ldn, c0, t, real);
+        else                      seam_load<D, NA>(v, cache, a.ldc, fresh, ldn, c0, t, real);
     };
     // the element's token rows: a batch pitch, or - packed - the slot's first row of the flat operands
     const float* kn = a.k_new + (PACKED ? int64_t(row0) * a.ldk : int64_t(b) * a.sbk) + head * D;
@@ -222,7 +282,20 @@ __device__ __forceinline__ void attn_extend_body(const ExtendArgs& a) {
         stream(rc, kc, kn, a.ldk, 0);
         store_rows_padded<D, NB>(rq, Qs, PQ, qrows, 32);
         // the block's own new rows become rows t + q0 .. of the caches, bit for bit; nothing in this launch reads them there
-        if constexpr (PAGED) {
+        if constexpr (KV16) {
+            // ... of the bfloat16 pool: the same rows, each value as the word r leaves of it, one 8-byte store per lane and pool
+            uint16_t *k16 = reinterpret_cast<uint16_t*>(a.k_cache), *v16 = reinterpret_cast<uint16_t*>(a.v_cache);
+#pragma unroll
+            for (int i = 0; i < NB; ++i) {
+                const int f = tid + i * 256;
+                if (f < qrows * Q4) {
+                    const int j = t + q0 + f / Q4;
+                    const int64_t at = int64_t((Tab[j >> lb] << lb) | (j & ((1 << lb) - 1))) * a.ldc + head * D + (f % Q4) * 4;
+                    *reinterpret_cast<au32x2*>(k16 + at) = au32x2{bf16_word(rk[i][0]) | (bf16_word(rk[i][1]) << 16), bf16_word(rk[i][2]) | (bf16_word(rk[i][3]) << 16)};
+                    *reinterpret_cast<au32x2*>(v16 + at) = au32x2{bf16_word(rv[i][0]) | (bf16_word(rv[i][1]) << 16), bf16_word(rv[i][2]) | (bf16_word(rv[i][3]) << 16)};
+                }
+            }
+        } else if constexpr (PAGED) {
             // ... of the pool: position t + q0 + i through the table (its words up to the reach are checked), a row of its own block
 #pragma unroll
             for (int i = 0; i < NB; ++i) {
@@ -254,6 +327,7 @@ __device__ __forceinline__ void attn_extend_body(const ExtendArgs& a) {
     // scores: the keys arrive in chunks of 128; wave w takes keys [c0 + 32 w, c0 + 32 w + 32) of the chunk, scaled (the product
     // rounded to fp32 first, like `scores * c`).  Columns [Kend, Cp) of the tile are never written and never read
     for (int c0 = 0; c0 < Kend; c0 += kExtChunk) {
+        if constexpr (KV16) seam_settle16<D, NA>(rc, rw, c0, t, keys);
         seam_store<D, NA>(rc, Buf, PQ, c0, keys, Kend);
         __syncthreads();
         if (c0 + kExtChunk < Kend) stream(rc, kc, kn, a.ldk, c0 + kExtChunk);
@@ -337,6 +411,7 @@ __device__ __forceinline__ void attn_extend_body(const ExtendArgs& a) {
     const int n = wave % NT, kp = wave / NT;
     af32x16 acc = zero16();
     for (int c0 = 0; c0 < Kend; c0 += kExtChunk) {
+        if constexpr (KV16) seam_settle16<D, NA>(rc, rw, c0, t, keys);
         seam_store<D, NA>(rc, Buf, PV, c0, keys, Kend);
         __syncthreads();                                              // (the first one also publishes the probabilities in LDS)
         if (c0 + kExtChunk < Kend) stream(rc, vc, vn, a.ldv, c0 + kExtChunk);

@@ -428,14 +428,19 @@ class PagedKVCache(object):
     writes below a slot's position.  block_size is a power of two, 4 <= B <= 128 (small blocks reach multi-block tables at tiny
     shapes), and capacity <= 512, the extend kernel's limit.  Tables and stack are moved by ONE op per step,
     `serve_commit_paged` (nn.RequestPool); the cache serves the `count=` append path only: `reorder`, the one-token decode route,
-    token-packed steps (`cu=`) and `generate` refuse it.  State, not parameters, like KVCache.  Not a class of the reference."""
+    token-packed steps (`cu=`) and `generate` refuse it.  State, not parameters, like KVCache.  Not a class of the reference.
+    kv_dtype="bf16": the pools are int16 tensors of the same shape that hold BFLOAT16 words - `light.bf16_bits` of every key and
+    value, half the bytes (`pool_bytes`).  Every key and value is then attended to as r of what the projection produced
+    (r = `bf16_round_array`), whichever step brought it in; `kv_dtype` says which form the cache holds (None: the dtype of `like`)."""
 
     per_row = True
     num_beams = 1
 
-    def __init__(self, layers: int, slots: int, num_blocks: int, block_size: int, width: int, max_blocks: int, like=None):
+    def __init__(self, layers: int, slots: int, num_blocks: int, block_size: int, width: int, max_blocks: int, like=None, kv_dtype=None):
         cls = Tensor if like is None else type(like)
-        dtype = np.dtype(np.float32 if like is None else like.dtype)
+        assert kv_dtype in (None, "bf16"), "PagedKVCache: kv_dtype is None (the pools in the dtype of `like`) or \"bf16\", got %r" % (kv_dtype,)
+        self.kv_dtype = kv_dtype
+        dtype = np.dtype(np.int16) if kv_dtype == "bf16" else np.dtype(np.float32 if like is None else like.dtype)
         assert layers >= 1 and slots >= 1 and num_blocks >= 1 and width >= 1 and max_blocks >= 1
         assert int(block_size) == block_size and 4 <= block_size <= 128 and block_size & (block_size - 1) == 0, \
             "PagedKVCache: block_size is a power of two within 4 .. 128, got %s" % (block_size,)
@@ -475,6 +480,9 @@ class PagedKVCache(object):
         self.length, self.lengths = 0, np.zeros(self.batch, np.int64)
 
     def reorder(self, parent, num_beams=None) -> None:
+        if self.kv_dtype == "bf16":
+            raise NotImplementedError("PagedKVCache.reorder: a bf16 cache (kv_dtype=\"bf16\") serves the count= append path only; beams copy rows "
+                                      "between the slots of a float32 nn.KVCache")
         raise NotImplementedError("PagedKVCache.reorder: beams copy rows between slots; the paged cache serves the count= append path only")
 
     def pool_bytes(self) -> int:
@@ -507,7 +515,8 @@ class RequestPool(object):
         assert isinstance(cache, (KVCache, PagedKVCache)) and cache.per_row, \
             "RequestPool takes a cache with a position per sequence: nn.KVCache(..., per_row=True) or nn.PagedKVCache"
         self.paged = isinstance(cache, PagedKVCache)
-        assert not self.paged or token_budget is None, "RequestPool: token_budget= (token-packed steps) does not go with a PagedKVCache"
+        assert not self.paged or token_budget is None, "RequestPool: token_budget= (token-packed steps) does not go with a PagedKVCache%s" % (
+            " (kv_dtype=\"bf16\": the packed launch reads a float32 nn.KVCache)" if getattr(cache, "kv_dtype", None) == "bf16" else "")
         assert max_positions is None or cache.capacity <= max_positions, \
             "RequestPool: a cache of %d positions exceeds the model's %s position embeddings" % (cache.capacity, max_positions)
         cls = type(cache.pos)
