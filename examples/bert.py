@@ -50,6 +50,11 @@ Differences from the reference, on purpose:
                                                        # the same through TOKEN-PACKED steps: every step has 24 token rows for all slots
                                                        # together - one per decoding slot, the rest shared by the prefilling slots in
                                                        # pieces of at most 16 (`serve(token_budget=)`, csrc/serve_packed.hip)
+    python examples/bert.py --serve 16 --sample --per-request [--seed S] [--graph] [--cpu]
+                                                       # per-request sampling: request r has one of a short cycle of parameter sets
+                                                       # (one of them greedy) and the random stream seeded S + r, so its tokens do not
+                                                       # depend on slots, chunk or the other requests (`serve(seeds=)`,
+                                                       # `logits.sample_rows`, csrc/sample_rows.hip)
     python examples/bert.py --mlm --bf16-decoder       # the decoder onto the vocabulary (forward, dx, dW) on the bf16 matrix cores:
                                                        # config key `decoder_precision="bf16"`; tensors stay float32
 """
@@ -791,9 +796,13 @@ def decode_mask(attention_mask, capacity):
     return full
 
 
-def next_token(logits, sampler=None):
+def next_token(logits, sampler=None, pool=None):
     """(b, 1) int32 ids from (b, 1, vocab) logits: the argmax, or - sampler = (temperature, top_k, top_p) - one call of
-    `logits.sample`, which draws from the backend's random stream (one launch in place of argmax + astype)"""
+    `logits.sample`, which draws from the backend's random stream (one launch in place of argmax + astype); or - a pool with a
+    sampling table - one `logits.sample_rows`: slot s under the parameters and the seed of the request it holds, its counter the
+    number of tokens that request has stored.  Nothing of the backend's stream is taken then"""
+    if pool is not None and pool.sampling is not None:
+        return logits.sample_rows(pool.sampling, pool.req, pool.out_len)
     if sampler is None:
         return logits.argmax(-1).astype(np.int32)
     temperature, top_k, top_p = sampler
@@ -1322,7 +1331,7 @@ def serve_step(model, pool, sampler=None, eos=None):
         hidden = model.bert(pool.ids, cache=pool.cache, append=True, count=pool.count, token_positions=pool.position_ids)
     width = hidden.shape[-1]
     rows = hidden.reshape(-1, width)[pool.last].reshape(pool.slots, 1, width)
-    pool.commit(next_token(model.head(rows), sampler), eos=eos)
+    pool.commit(next_token(model.head(rows), sampler, pool), eos=eos)
 
 
 def fill_shared_prefix(model, pool, tokens):
@@ -1348,7 +1357,8 @@ def fill_shared_prefix(model, pool, tokens):
 
 
 def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, pad_token_id=0, graph=None, temperature=None, top_k=0,
-          top_p=1.0, poll=8, lengths=None, cache=None, token_budget=None, num_blocks=None, block_size=16, shared_prefix=0, kv_dtype=None):
+          top_p=1.0, poll=8, lengths=None, cache=None, token_budget=None, num_blocks=None, block_size=16, shared_prefix=0, kv_dtype=None,
+          seeds=None):
     """continuous batching: N requests through `slots` cache slots, a finished slot refilled at once from the queue while the
     others go on decoding.  prompts: a list of N int sequences, or (N, P) right-padded ids (an array or a tensor) with lengths=;
     max_new_tokens: an int, or N ints - a budget per request.  Returns (out (N, G) int32 with G = the largest budget, filled with
@@ -1365,6 +1375,14 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
     Greedy results depend on a request's own data only: not on slots, chunk or the order of admission.  With a temperature every
     step takes ONE call of the random stream for all slots, idle ones included, and a slot's numbers depend on its index: a
     sampled run is reproducible for a given seed, slots and chunk (eager or captured), but NOT independent of the schedule.
+    The PER-REQUEST route IS independent of it: with seeds= (an int s - request r draws from the stream seeded (s + r) mod 2**64 -
+    or N ints; seeds=None with a sequence among the parameters: s = the seed of the backend's generator, read once before the
+    first step), or with temperature, top_k or top_p a sequence of N (scalars broadcast; a temperature of 0 is a greedy request),
+    every request has its own parameters and its own random stream: its g-th token takes `random.sample_uniforms(seed, 0, g + 1)[g]`
+    (`logits.sample_rows`, csrc/sample_rows.hip, driven by the pool's `req` and `out_len`).  A request's tokens are then
+    `random.sample_tokens(seed, 0, its logits, T, k, p)` whatever slots, chunk, token_budget, num_blocks and the other requests
+    are; the backend's generator is neither read by a step nor advanced; `stats` gains `per_request_sampling`.  A float
+    temperature= without seeds= is the route above, unchanged.
     cache: an nn.KVCache(per_row=True) of `slots` rows to use (default: one whose capacity is the longest request's need).
     token_budget: None, or T >= slots - every step is TOKEN-PACKED: it has T token rows for all slots together in place of
     (slots, chunk) rows.  A decoding slot takes one row; the rows left go to the prefilling slots in slot order, in pieces of at
@@ -1431,10 +1449,23 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
     packed = {} if token_budget is None else {"token_budget": int(token_budget)}
     if paged:
         packed = {"prefix_blocks": prefix_blocks}
-    pool = nn.RequestPool(cache, padded, lengths, budgets, chunk, pad_token_id=pad_token_id, max_positions=positions, **packed)
+    table = None
+    if seeds is not None or any(np.ndim(v) for v in (temperature, top_k, top_p)):
+        # per request: a row of parameters and a seed each (s + r for an int s; the backend generator's seed, read here, for None)
+        assert temperature is not None, "serve: seeds= and per-request top_k / top_p go with temperature= (a float, or one per request; 0 is greedy)"
+        if seeds is None:
+            seeds = light.random.get_state("cpu" if cls is light.CpuTensor else "hip")[0]
+        if np.ndim(seeds) == 0:
+            seeds = [(int(seeds) + r) % (1 << 64) for r in range(n)]
+        assert all(np.ndim(v) == 0 or len(v) == n for v in (temperature, top_k, top_p, seeds)), \
+            "serve: temperature, top_k, top_p and seeds are scalars or one entry per request (%d)" % n
+        table = light.random.sampling_table(temperature, top_k, top_p, seeds)
+    pool = nn.RequestPool(cache, padded, lengths, budgets, chunk, pad_token_id=pad_token_id, max_positions=positions, sampling=table, **packed)
     eos = None if eos_token_id is None else int(eos_token_id)
-    sampler = None if temperature is None else (temperature, top_k, top_p)
+    sampler = None if temperature is None or table is not None else (temperature, top_k, top_p)
     stats = {"steps": 0, "requests": n, "slots": int(slots), "chunk": chunk, **packed}
+    if table is not None:
+        stats["per_request_sampling"] = True
     if paged:
         stats.update(num_blocks=cache.num_blocks, block_size=cache.block_size, kv_dtype=cache.kv_dtype, pool_bytes=cache.pool_bytes())
 
@@ -1491,6 +1522,11 @@ if __name__ == "__main__":
         if "--sample" in sys.argv:
             sampling = dict(temperature=option("--temperature", float, 1.0), top_k=option("--top-k", int, 0), top_p=option("--top-p", float, 1.0))
             light.manual_seed(option("--seed", int, 0))
+            if "--per-request" in sys.argv:
+                # request r takes one of a short cycle of parameter sets (one of them greedy) and the stream seeded S + r
+                cycle = ((0.0, 0, 1.0), (1.0, 0, 1.0), (0.8, 50, 0.95), (0.7, 5, 1.0), (1.3, 0, 0.9))
+                sets = [cycle[r % len(cycle)] for r in range(n_requests)]
+                sampling = dict(temperature=[s[0] for s in sets], top_k=[s[1] for s in sets], top_p=[s[2] for s in sets], seeds=option("--seed", int, 0))
         t0 = time.perf_counter()
         if "--token-budget" in sys.argv:
             sampling["token_budget"] = option("--token-budget", int, None)

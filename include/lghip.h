@@ -1120,10 +1120,33 @@ int lg_mlm_mask(const void* ids, int itemsize, void* masked, void* labels, int64
  * row_pitch >= cols. */
 int lg_sample_f32(const float* logits, int64_t rows, int64_t cols, int64_t row_pitch, double temperature, int64_t top_k,
                   double top_p, void* out, int out_itemsize, uint64_t* base_out);
-/* What the most recent lg_sample_f32 call of the calling thread launched: host bookkeeping for tests, no device work.
- *   out[0] kernel: 0 = the row is held in LDS, 1 = the row is re-read from memory, -1 = nothing (a refused call)
- *   out[1] threads per workgroup   out[2] passes over the row   out[3] 1 when the row is staged with 16-byte loads */
+/* What the most recent lg_sample_f32 or lg_sample_rows_f32 call of the calling thread launched: host bookkeeping for tests, no
+ * device work.
+ *   out[0] kernel: 0 = the row is held in LDS, 1 = the row is re-read from memory, -1 = nothing (a refused call, or no rows)
+ *   out[1] threads per workgroup   out[2] passes over the row   out[3] 1 when the row is staged with 16-byte loads
+ * lg_sample_rows_f32 reports the passes of a sampled row with every filter on (10): its table may turn them on per row. */
 int lg_sample_last_plan(int32_t out[4]);
+
+/* ---- per-request sampling: parameters, seed and counter per row (csrc/sample_rows.hip) --------------------
+ * One token per row of fp32 logits [rows, cols] (row r at logits + r * row_pitch) in ONE launch, every row under the parameters
+ * and the random stream of a table row of its own.  table: n rows of 8 int32 words (16-byte aligned) -
+ *   word 0     the bits of inv_T = float(1.0 / temperature); +0.0 means GREEDY
+ *   word 1     top_k             words 2, 3   the low and high half of the bits of top_p (a double)
+ *   words 4, 5 the low and high half of a 64-bit seed          words 6, 7   0
+ * index: rows int32 words, row r uses table row i = index[r]; counter: n int32 words, g = counter[i].  Per row, in this order:
+ *   1. i < 0: the token is 0; the row's logits are not read.
+ *   2. the row is BAD when i >= n, g < 0, top_k < 0, top_p is outside (0, 1], or inv_T has its sign set, is NaN or infinite: the
+ *      token is 0 and LG_STATUS_BAD_INDEX is raised (LG_EINDEX at the next synchronisation); the other rows are computed.
+ *   3. inv_T == +0.0: the row's argmax under the rules of lg_argreduce_f32, degenerate rows included.
+ *   4. otherwise steps 1 to 5 of lg_sample_f32 with u = ((word >> 8) + 0.5) * 2^-24, word = word 0 of
+ *      philox4x32_10(counter = (lo32(g), hi32(g), 0, 0), key = (lo32(seed), hi32(seed))): the number that call 0 of a stream seeded
+ *      `seed` gives its row g.
+ * The row body is lg_sample_f32's own: for equal (inv_T, top_k, top_p, u) the token is that launch's bit for bit.  The
+ * generator's (seed, draws) state is neither read nor advanced.  lightgrad_amd/random.py `sample_tokens_rows` is the definition
+ * in float64.  rows == 0 launches nothing.  0 <= rows <= 2^24; 1 <= cols < 2^31; row_pitch >= cols; n >= 1; out_itemsize 4 or
+ * 8; no NULL or misaligned operand; `out` overlaps none of the others. */
+int lg_sample_rows_f32(const float* logits, int64_t rows, int64_t cols, int64_t row_pitch, const int32_t* table, int64_t n,
+                       const int32_t* index, const int32_t* counter, void* out, int out_itemsize);
 
 /* ---- hidden dropout inside the LayerNorm launches (csrc/rowwise.hip) ----------------------------------
  * A dropout that sits directly in front of or behind a LayerNorm over dense fp32 [rows, cols], drawn where the LayerNorm

@@ -421,6 +421,25 @@ def _sample(logits, temperature=1.0, top_k=0, top_p=1.0, dtype=np.int64):
 CpuTensor.sample = _sample
 
 
+def _sample_rows(logits, table, index, counter, dtype=np.int32):
+    """ logits.sample_rows(table, index, counter, dtype=np.int32) -> one token per row, every row under the parameters and the
+    random stream of a table row of its own: `lightgrad_amd.random.sample_tokens_rows`.  logits (rows, V) or (rows, 1, V); table
+    int32 (n, 8) (`random.sampling_table`); index int32 (rows,), -1 = a free row (token 0, its logits are not read); counter int32
+    (n,).  The generator's state is neither read nor advanced.  A bad row (see the definition) answers 0 and the call raises
+    IndexError after every other row has been answered - `err.tokens` is the result.  A constant of the tape. """
+    shape, dtype = logits.shape, _random.check_sample_rows_operands(logits, table, index, counter, dtype)
+    tokens, bad = _random.sample_tokens_rows(logits.data.reshape(shape[0], shape[-1]), table.data, index.data, counter.data)
+    out = CpuTensor.from_numpy(np.asarray(tokens, dtype=dtype).reshape(shape[:-1]), requires_grad=False)
+    if bad.any():
+        err = IndexError("sample_rows: rows %s name no table row, or one whose counter or parameters are out of range" % np.flatnonzero(bad).tolist())
+        err.tokens = out
+        raise err
+    return out
+
+
+CpuTensor.sample_rows = _sample_rows
+
+
 def _decode_commit(nxt, token, out_ids, pos, done, eos=None):
     """ nxt.decode_commit(token, out_ids, pos, done, eos=None): the per-row bookkeeping of one decode step, in place and outside
     the tape - the definition of the op.  nxt (b,) or (b, 1), token (b, 1), out_ids (b, columns), pos (b,), done (b,), all int32.

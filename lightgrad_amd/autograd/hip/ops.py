@@ -2445,6 +2445,32 @@ def _sample(logits, temperature=1.0, top_k=0, top_p=1.0, dtype=np.int64):
 HipTensor.sample = _sample
 
 
+def _sample_rows(logits, table, index, counter, dtype=np.int32):
+    """ logits.sample_rows(table, index, counter, dtype=np.int32) -> one token per row, every row under the parameters and the
+    random stream of a table row of its own as `lightgrad_amd.random.sample_tokens_rows` defines it: ONE launch of
+    csrc/sample_rows.hip.  logits (rows, V) or (rows, 1, V) float32; table int32 (n, 8) (`random.sampling_table`, uploaded once);
+    index int32 (rows,), -1 = a free row; counter int32 (n,).  Everything the launch needs is device state - the generator is
+    neither read nor advanced, no host value enters: a captured step replays as it stands.  A bad row answers 0 and raises the
+    device's status flag (IndexError at the next synchronisation).  A constant of the tape. """
+    if logits._dtype != _F32:
+        raise TypeError("sample_rows is float32-only on HipTensor (got %s)" % logits._dtype)
+    dtype = _random.check_sample_rows_operands(logits, table, index, counter, dtype)
+    shape = logits._shape
+    rows, cols = shape[0], shape[-1]
+    src, pitch = logits, logits._strides[0]
+    if rows > 0 and ((cols > 1 and src._strides[-1] != 1) or pitch < cols):
+        src, pitch = logits.contiguous(), cols           # the vocabulary contiguous, one pitch from row to row
+    out = HipTensor.empty(shape[:-1], dtype=dtype, requires_grad=False)
+    if rows == 0:
+        return out                                       # no stream to advance: nothing to launch
+    _l.check(_l.lib().lg_sample_rows_f32(src.ptr, rows, cols, _py.max(pitch, cols), table.contiguous().ptr, table._shape[0],
+                                         index.contiguous().ptr, counter.contiguous().ptr, out.ptr, dtype.itemsize))
+    return out
+
+
+HipTensor.sample_rows = _sample_rows
+
+
 def _next_token_labels(ids, ignore_index=-100):
     """ ids.next_token_labels(ignore_index=-100): the labels of the next-token objective - `ids` shifted left by one along the last
     axis, `ignore_index` in the last column; same dtype and shape, a constant of the tape.  One strided copy and one strided fill

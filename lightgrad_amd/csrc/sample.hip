@@ -26,187 +26,12 @@
 //
 // Seed and `draws` are read by the kernel with dropout_fwd's protocol (read, two-level tickets, the last arriver advances): a
 // captured decode step draws fresh numbers at every replay, and no host scalar depends on the data.
-#include "common.h"
-#include "rng_common.h"
-#include <cmath>
-#include <climits>
+//
+// The row body and what it stands on live in sample_body.h, which sample_rows.hip (a set of parameters and a stream per row)
+// instantiates as well; this file keeps the launch that draws from the global stream: its two kernels and the ticket protocol.
+#include "sample_body.h"
 
 namespace lg {
-
-typedef unsigned long long u64;
-typedef unsigned __int128 u128;
-
-constexpr int kSampleBins = 2048;                                        // 11 bits of the key a pass (the last one: 10)
-constexpr int kSampleHistBytes = kSampleBins * 8;                        // 16 KiB
-constexpr int kSampleLdsBytes = 160 * 1024;                              // the CU's LDS: what one workgroup may declare
-constexpr int kSampleStaticBytes = 1024;                                 // SampleShared below, in front of the bins: all of the LDS is
-                                                                         // dynamic, so its base - and the staged row - is 16-byte aligned
-constexpr int64_t kSampleRowFloats = (kSampleLdsBytes - kSampleHistBytes - kSampleStaticBytes) / 4;
-constexpr int64_t kSampleMaxLdsCols = kSampleRowFloats - 4;              // up to three floats in front keep the row's 16-byte phase
-constexpr int kSampleMaxWaves = 16;
-constexpr int64_t kSampleNone = INT64_MAX;
-
-struct SampleShared {
-    u64       call[2];                                                   // seed, draws
-    u64       wave_total[kSampleMaxWaves];
-    long long wave_i[kSampleMaxWaves];
-    float     wave_v[kSampleMaxWaves];
-    u64       sel_rem;
-    uint32_t  sel_digit;
-};
-static_assert(sizeof(SampleShared) <= kSampleStaticBytes, "SampleShared outgrew its share of the LDS");
-
-// the combine of argreduce.hip: does (v, i) beat (w, j) for argmax?
-__device__ __forceinline__ bool sample_beats(float v, long long i, float w, long long j) {
-    const bool vn = v != v, wn = w != w;
-    if (vn || wn) return vn && (!wn || i < j);
-    return v > w || (!(w > v) && i < j);
-}
-
-// larger value <=> larger key; -0.0 and +0.0 share one key.  (No NaN reaches a key: such a row is degenerate.)
-__device__ __forceinline__ uint32_t sample_key(float x) {
-    uint32_t b = __float_as_uint(x);
-    if (b == 0x80000000u) b = 0u;
-    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-
-// the value whose key is k (no value has the key 0)
-__device__ __forceinline__ float sample_value(uint32_t k) {
-    return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu));
-}
-
-// the weight of the value x with key k as an integer: floor(scale * exp((x - m) * inv_t)); -inf gives 0.  One expression for
-// every pass.
-__device__ __forceinline__ u64 sample_q(uint32_t k, float m, float inv_t, float scale) {
-    return u64(__fmul_rn(__expf(__fmul_rn(__fsub_rn(sample_value(k), m), inv_t)), scale));
-}
-
-__device__ __forceinline__ u64 sample_wave_sum(u64 v) {                  // every lane ends with the wave's sum
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ u64 sample_wave_scan(u64 v, int lane) {      // inclusive, by increasing lane
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const u64 t = __shfl_up(v, off, 64);
-        if (lane >= off) v += t;
-    }
-    return v;
-}
-
-// the sum of one value per thread over the workgroup (ends with a barrier passed; sh.wave_total is free again after the next one)
-__device__ __forceinline__ u64 sample_block_sum(u64 v, SampleShared& sh, int lane, int wave, int nw) {
-    v = sample_wave_sum(v);
-    __syncthreads();                                                     // the previous user of wave_total is done
-    if (lane == 0) sh.wave_total[wave] = v;
-    __syncthreads();
-    u64 total = 0;
-    for (int w = 0; w < nw; ++w) total += sh.wave_total[w];
-    return total;
-}
-
-// The row as the passes read it: KEYS.  LDS: `p` is the 16-byte aligned buffer and the key of element i is its word off + i (the
-// staging converts once; the value comes back from the key where a weight is needed) - the passes walk it with 16-byte reads, four
-// elements each, with no test per element: the up to three words in front of element 0 and behind the last hold the key of -inf,
-// which every pass may see (weight 0; counted by the top-k select only where the k-th largest value is -inf itself and the
-// answer is "everything" either way; never returned, because the scan stops at a positive weight).  Memory: `p` is the row
-// itself, off == 0, scalar reads, the key computed on the way.
-template <bool LDS>
-struct SampleRow {
-    const void* p;
-    int off;
-    int64_t cols;
-
-    template <class F>
-    __device__ __forceinline__ void vector(int v, F& f) const {          // the four words of vector v (i < 0 or >= cols: -inf)
-        const uint4 k = reinterpret_cast<const uint4*>(p)[v];
-        const int i = 4 * v - off;
-        f(int64_t(i), k.x); f(int64_t(i + 1), k.y); f(int64_t(i + 2), k.z); f(int64_t(i + 3), k.w);
-    }
-
-    // f(i, key) over this thread's share of the row, by increasing i: the threads interleave
-    template <class F>
-    __device__ __forceinline__ void each(F f) const {
-        const int tid = threadIdx.x, T = blockDim.x;
-        if constexpr (LDS) {
-            const int nvec = (off + int(cols) + 3) >> 2;
-#pragma unroll 2
-            for (int v = tid; v < nvec; v += T) vector(v, f);
-        } else {
-            for (int64_t i = tid; i < cols; i += T) f(i, sample_key(static_cast<const float*>(p)[i]));
-        }
-    }
-
-    // f(i, key) over the contiguous run of this thread, by increasing i: thread t's run lies in front of thread t + 1's.  An odd
-    // number of vectors (elements) per run: the threads of a wave start on different LDS banks
-    template <class F>
-    __device__ __forceinline__ void run(F f) const {
-        const int tid = threadIdx.x, T = blockDim.x;
-        if constexpr (LDS) {
-            const int nvec = (off + int(cols) + 3) >> 2, per = ((nvec + T - 1) / T) | 1;
-            const int v0 = tid * per < nvec ? tid * per : nvec, v1 = v0 + per < nvec ? v0 + per : nvec;
-#pragma unroll 2
-            for (int v = v0; v < v1; ++v) vector(v, f);
-        } else {
-            const int64_t per = ((cols + T - 1) / T) | 1;
-            const int64_t i0 = int64_t(tid) * per < cols ? int64_t(tid) * per : cols, i1 = i0 + per < cols ? i0 + per : cols;
-            for (int64_t i = i0; i < i1; ++i) f(i, sample_key(static_cast<const float*>(p)[i]));
-        }
-    }
-};
-
-// The largest key v occurring in the row with sum{weight_j : key_j >= v} >= target, 1 <= target <= the sum of all weights
-// (integers: exact).  Three passes over the key's bits 31 .. 21, 20 .. 10 and 9 .. 0; a pass counts only the elements that match
-// the bits chosen so far.  (Eleven bits - sign, exponent and two bits of the mantissa - spread logits over enough bins that
-// the atomics of a wave rarely meet.)  blockDim.x divides kSampleBins.
-template <class Row, class WF>
-__device__ __forceinline__ uint32_t sample_select(const Row& row, u64 target, WF weight, u64* hist, SampleShared& sh) {
-    const int tid = threadIdx.x, T = blockDim.x, lane = tid & 63, wave = tid >> 6;
-    uint32_t prefix = 0;
-    u64 rem = target;
-#pragma unroll 1
-    for (int pass = 0; pass < 3; ++pass) {
-        const int low = pass == 0 ? 21 : pass == 1 ? 10 : 0;
-        const uint32_t digit = pass == 2 ? 1023u : 2047u, above = pass == 0 ? 0u : 0xFFFFFFFFu << (pass == 1 ? 21 : 10);
-        __syncthreads();                                                 // the bins' previous readers are done
-        for (int b = tid; b < kSampleBins; b += T) hist[b] = 0;
-        __syncthreads();
-        row.each([&](int64_t, uint32_t k) {
-            if ((k & above) == prefix) {
-                const u64 w = weight(k);
-                if (w != 0) atomicAdd(hist + ((k >> low) & digit), w);
-            }
-        });
-        __syncthreads();
-        // thread t holds the bins 2047 - t * per - j, j < per: an inclusive scan over the threads runs from the top bin down
-        const int per = kSampleBins / T;
-        const u64* const h = hist + (kSampleBins - 1 - tid * per);
-        u64 val = 0;
-        for (int j = 0; j < per; ++j) val += h[-j];
-        u64 incl = sample_wave_scan(val, lane);
-        if (lane == 63) sh.wave_total[wave] = incl;
-        __syncthreads();
-        for (int w = 0; w < wave; ++w) incl += sh.wave_total[w];
-        if (incl >= rem && incl - val < rem) {                           // exactly one thread: the target is reached in one of its bins
-            u64 c = incl - val;
-            for (int j = 0; j < per; ++j) {
-                const u64 b = h[-j];
-                if (c + b >= rem) {
-                    sh.sel_digit = uint32_t(kSampleBins - 1 - tid * per - j);
-                    sh.sel_rem = rem - c;
-                    break;
-                }
-                c += b;
-            }
-        }
-        __syncthreads();
-        prefix |= sh.sel_digit << low;
-        rem = sh.sel_rem;
-    }
-    return prefix;
-}
 
 template <bool LDS, typename OutT>
 __global__ void __launch_bounds__(1024) sample_kernel(const float* __restrict__ logits, int64_t rows, int64_t cols, int64_t pitch, float inv_t,
@@ -214,8 +39,7 @@ __global__ void __launch_bounds__(1024) sample_kernel(const float* __restrict__ 
                                                       u64* base_out, int group) {
     extern __shared__ __align__(16) unsigned char sample_dyn[];
     SampleShared& sh = *reinterpret_cast<SampleShared*>(sample_dyn);
-    u64* const hist = reinterpret_cast<u64*>(sample_dyn + kSampleStaticBytes);
-    const int tid = threadIdx.x, T = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = T >> 6;
+    const int tid = threadIdx.x;
 
     // the stream: thread 0 reads the call, takes its ticket and - as the last arriver - advances `draws`
     int* const tickets = rng_tickets(state);
@@ -233,119 +57,15 @@ __global__ void __launch_bounds__(1024) sample_kernel(const float* __restrict__ 
     }
     const int64_t row = blockIdx.x;
     if (row >= rows) return;                                             // rows == 0: the one workgroup only advances `draws`
-
-    const float* const g = logits + row * pitch;
-    SampleRow<LDS> r{g, 0, cols};                                        // (kernel 1: as it stands; kernel 0: the buffer, below)
-
-    // 0. and 1. stage the row (LDS) and find max and argmax.  A thread visits its elements by increasing index: the running
-    // update is rules 1 and 2 of the combine
-    float bv = -INFINITY;
-    long long bi = kSampleNone;
-    const auto absorb = [&](int64_t i, float x) {
-        const bool take = !(bv >= x) && bv == bv;
-        bv = take ? x : bv;
-        bi = take ? i : bi;
-    };
-    const auto absorb4 = [&](int64_t i, const float4& x) { absorb(i, x.x); absorb(i + 1, x.y); absorb(i + 2, x.z); absorb(i + 3, x.w); };
-    if constexpr (LDS) {
-        // global element i goes to word off + i of the buffer, off = the row's phase within 16 bytes
-        uint32_t* const buf = reinterpret_cast<uint32_t*>(sample_dyn + kSampleStaticBytes + kSampleHistBytes);
-        const auto keys = [](const float4& x) { return uint4{sample_key(x.x), sample_key(x.y), sample_key(x.z), sample_key(x.w)}; };
-        const int off = int((reinterpret_cast<uintptr_t>(g) >> 2) & 3);
-        int64_t head = (4 - off) & 3;
-        if (head > cols) head = cols;
-        if (tid < head) { const float x = g[tid]; buf[off + tid] = sample_key(x); absorb(tid, x); }
-        const int64_t nv = (cols - head) >> 2;
-        const float4* const g4 = reinterpret_cast<const float4*>(g + head);
-        uint4* const b4 = reinterpret_cast<uint4*>(buf + off + head);
-        int64_t v = tid;
-        for (; v + 3 * int64_t(T) < nv; v += 4 * int64_t(T)) {           // four loads in flight per thread
-            const float4 a0 = g4[v], a1 = g4[v + T], a2 = g4[v + 2 * int64_t(T)], a3 = g4[v + 3 * int64_t(T)];
-            b4[v] = keys(a0); b4[v + T] = keys(a1); b4[v + 2 * int64_t(T)] = keys(a2); b4[v + 3 * int64_t(T)] = keys(a3);
-            absorb4(head + 4 * v, a0); absorb4(head + 4 * (v + T), a1);
-            absorb4(head + 4 * (v + 2 * int64_t(T)), a2); absorb4(head + 4 * (v + 3 * int64_t(T)), a3);
-        }
-        for (; v < nv; v += T) { const float4 a = g4[v]; b4[v] = keys(a); absorb4(head + 4 * v, a); }
-        const int64_t t0 = head + 4 * nv;
-        if (t0 + tid < cols) { const float x = g[t0 + tid]; buf[off + t0 + tid] = sample_key(x); absorb(t0 + tid, x); }
-        if (tid < off) buf[tid] = sample_key(-INFINITY);                 // the words around the row that the 16-byte reads see
-        if (tid < 4 * ((off + int(cols) + 3) >> 2) - off - int(cols)) buf[off + cols + tid] = sample_key(-INFINITY);
-        r.p = buf;
-        r.off = off;
-    } else {
-        for (int64_t i = tid; i < cols; i += T) absorb(i, g[i]);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const long long oi = __shfl_xor(bi, o, 64);
-        if (sample_beats(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { sh.wave_v[wave] = bv; sh.wave_i[wave] = bi; }
-    __syncthreads();                                                     // (the staged row is complete, too)
-    bv = sh.wave_v[0]; bi = sh.wave_i[0];
-    for (int w = 1; w < nw; ++w)
-        if (sample_beats(sh.wave_v[w], sh.wave_i[w], bv, bi)) { bv = sh.wave_v[w]; bi = sh.wave_i[w]; }
-    if (bi == kSampleNone) bi = 0;                                       // nothing but -inf: the first index
-    if (bv != bv || bv == INFINITY || bv == -INFINITY) {                 // a degenerate row answers its argmax
-        if (tid == 0) out[row] = OutT(bi);
-        return;
-    }
-    const float m = bv;
-
-    // 2. top-k: K = {key >= kkey}
-    uint32_t nkey = 0;                                                   // N = {key >= nkey}; 0: everything
-    if (top_k >= 1 && top_k < cols)
-        nkey = sample_select(r, u64(top_k), [](uint32_t) { return u64(1); }, hist, sh);
-
-    // 3. and 4. top-p: the largest value whose mass at or above it reaches top_p * W
-    if (top_p < 1.0) {
-        u64 mine = 0;
-        const uint32_t kkey = nkey;
-        r.each([&](int64_t, uint32_t k) {
-            if (k >= kkey) mine += sample_q(k, m, inv_t, scale);
-        });
-        const u64 W = sample_block_sum(mine, sh, lane, wave, nw);
-        u64 target = u64(double(W) * top_p);
-        if (double(target) < double(W) * top_p) target += 1;             // the ceiling
-        if (target > W) target = W;
-        if (target < 1) target = 1;
-        nkey = sample_select(r, target, [=](uint32_t k) { return k >= kkey ? sample_q(k, m, inv_t, scale) : u64(0); }, hist, sh);
-    }
-
-    // 5. the blocked scan over N in index order: every thread sums its contiguous run
-    u64 s = 0;
-    r.run([&](int64_t, uint32_t k) {
-        if (k >= nkey) s += sample_q(k, m, inv_t, scale);
-    });
-    const u64 incl = sample_wave_scan(s, lane);
-    __syncthreads();                                                     // the previous user of wave_total is done
-    if (lane == 63) sh.wave_total[wave] = incl;
-    __syncthreads();
-    u64 before = 0, total = 0;
-    for (int w = 0; w < nw; ++w) {
-        const u64 t = sh.wave_total[w];
-        before += w < wave ? t : 0;
-        total += t;
-    }
-    uint32_t word[4];
-    philox4x32_10(uint32_t(row), uint32_t(u64(row) >> 32), uint32_t(base), uint32_t(base >> 32), uint32_t(seed), uint32_t(seed >> 32), word);
-    const u128 aim = u128(total) * u128(2u * (word[0] >> 8) + 1u);       // C_i * 2^25 >= aim  <=>  C_i >= u * W'
-    u64 c = before + incl - s;                                           // the running sum in front of this thread's run
-    if ((u128(c) << 25) < aim && aim <= (u128(c + s) << 25)) {           // exactly one thread: the target lies in its run
-        bool found = false;
-        r.run([&](int64_t i, uint32_t k) {
-            if (found) return;
-            if (k >= nkey) c += sample_q(k, m, inv_t, scale);
-            if ((u128(c) << 25) >= aim) { out[row] = OutT(i); found = true; }
-        });
-    }
+    // row r of the call with draws == base: the block of counter (r, base) under the key `seed`
+    sample_row_body<LDS, false, OutT>(sample_dyn, logits + row * pitch, row, cols, inv_t, top_k, top_p, scale, out, uint32_t(row),
+                                      uint32_t(u64(row) >> 32), uint32_t(base), uint32_t(base >> 32), uint32_t(seed), uint32_t(seed >> 32));
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------------
 static thread_local int32_t g_sample_plan[4] = {-1, 0, 0, 0};
 
-static void note_sample_plan(int kernel, int threads, int passes, int vec) {
+void note_sample_plan(int kernel, int threads, int passes, int vec) {
     g_sample_plan[0] = kernel; g_sample_plan[1] = threads; g_sample_plan[2] = passes; g_sample_plan[3] = vec;
 }
 
@@ -379,17 +99,13 @@ extern "C" int lg_sample_f32(const float* logits, int64_t rows, int64_t cols, in
     LG_ARG(top_p > 0.0 && top_p <= 1.0, "lg_sample_f32: top_p = %g outside (0, 1] (1: off)", top_p);
     { const int rc = adam_epilogue_check_write(out, rows * out_itemsize); if (rc != LG_OK) return rc; }
     const float inv_t = float(1.0 / temperature);
-    // 2^shift * cols < 2^63: the integer sums cannot overflow; 40 for every row of fewer than 2^22 elements
-    int bits = 0;
-    while ((int64_t(1) << bits) <= cols) ++bits;
-    const int shift = bits <= 22 ? 40 : 62 - bits;
-    const float scale = float(double(uint64_t(1) << shift));
-    const bool lds_row = cols <= kSampleMaxLdsCols;
-    const int threads = cols <= 8192 ? 256 : 1024;
-    const size_t lds = size_t(kSampleStaticBytes + kSampleHistBytes) + (lds_row ? size_t((cols + 4 + 3) & ~int64_t(3)) * 4 : 0);
+    const SampleShape shape = sample_shape(cols);
+    const float scale = shape.scale;
+    const bool lds_row = shape.lds_row;
+    const int threads = shape.threads, vec = shape.vec;
+    const size_t lds = shape.lds;
     const bool select_k = top_k >= 1 && top_k < cols, select_p = top_p < 1.0;
     const int passes = 1 + (select_k ? 3 : 0) + (select_p ? 4 : 0) + 2;  // (kernel 0 finds the maximum while it stages the row)
-    const int vec = lds_row && cols >= 7 ? 1 : 0;        // (a row of seven floats holds an aligned float4 wherever it starts)
     const dim3 grid(unsigned(rows < 1 ? 1 : rows)), block(threads);      // no rows: one workgroup, which advances `draws`
     u64* const base = reinterpret_cast<u64*>(base_out);
     int rc;

@@ -503,7 +503,8 @@ class RequestPool(object):
     `cache` must be per_row.  A request needs lengths[r] + budgets[r] - 1 cache rows (its last token is fed to nobody): checked
     here, on the host, against the capacity.  State, not parameters, like the cache.  Not a class of the reference."""
 
-    def __init__(self, cache, prompts, lengths, budgets, chunk: int, pad_token_id: int = 0, max_positions=None, token_budget=None, prefix_blocks: int = 0):
+    def __init__(self, cache, prompts, lengths, budgets, chunk: int, pad_token_id: int = 0, max_positions=None, token_budget=None, prefix_blocks: int = 0,
+                 sampling=None):
         """max_positions: the model's position embeddings, if the caller knows them - the capacity must not exceed them.
         token_budget: None, or T >= slots - the steps are TOKEN-PACKED: ids and position_ids are (1, T), the step's tokens of all
         slots in one flat buffer, `cu` (slots + 1,) says which rows are whose, `last` names rows of the T, and `commit` is
@@ -511,7 +512,12 @@ class RequestPool(object):
         `count` stays (pos + count is the commit's t).  Without it `cu` is None and everything is as it was.
         cache: an nn.PagedKVCache in place of a KVCache - `commit` is `serve_commit_paged`, which also moves the cache's tables
         and its stack of free blocks; prefix_blocks: the blocks 0 .. F - 1 every request shares (they hold the first F * B tokens
-        of every prompt already; the pool resets the cache with them off the stack)"""
+        of every prompt already; the pool resets the cache with them off the stack)
+        sampling: None, or an int32 (N, 8) numpy table of `random.sampling_table` - parameters and a seed per REQUEST, uploaded once
+        as `self.sampling`; a step then draws with `logits.sample_rows(pool.sampling, pool.req, pool.out_len)`: slot s under the row
+        of the request it holds, with the number of tokens that request has stored as its counter.  Both are the pool's own
+        state and right when the step draws (the previous commit laid the step out for req[s]; out_len[r] moves only when a
+        token is stored), so no commit changes.  None: `self.sampling` is None and everything is as it was."""
         assert isinstance(cache, (KVCache, PagedKVCache)) and cache.per_row, \
             "RequestPool takes a cache with a position per sequence: nn.KVCache(..., per_row=True) or nn.PagedKVCache"
         self.paged = isinstance(cache, PagedKVCache)
@@ -552,6 +558,12 @@ class RequestPool(object):
         self.out_len, self.queue = tensor(np.zeros(n)), tensor(np.zeros(2))
         self.req, self.count, self.last = tensor(np.full(self.slots, -1)), tensor(np.zeros(self.slots)), tensor(np.zeros(self.slots))
         self._no_tokens = tensor(np.zeros(self.slots))
+        self.sampling = None
+        if sampling is not None:
+            sampling = np.asarray(sampling)
+            assert sampling.dtype == np.int32 and sampling.shape == (n, 8), \
+                "RequestPool: sampling= is the int32 (%d, 8) table of random.sampling_table, a row per request (got %s %s)" % (n, sampling.dtype, sampling.shape)
+            self.sampling = tensor(sampling)
         # queue[1] as a tensor of its own that shares the word (indexing a tensor copies: the poll would be a launch and a read)
         if isinstance(getattr(self.queue, "data", None), np.ndarray):
             self._finished = cls.from_numpy(self.queue.data[1:2], requires_grad=False)

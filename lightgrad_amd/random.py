@@ -26,6 +26,11 @@ ROW r of the logits takes word 0 of the block of counter r and u = ((word >> 8) 
 definition, in float64, and is the numpy backend; csrc/sample.hip evaluates it on the device with float32 weights held as
 integers - its token is the definition's wherever u is further than that rounding from a boundary of the cumulative weights.
 
+`Tensor.sample_rows` (per-request sampling) takes NOTHING from the generator's state: every row names a row of a parameter table
+(`sampling_table`: temperature, top-k, top-p and a 64-bit seed of its own) and a counter g, and draws
+u = sample_uniforms(seed, 0, g + 1)[g] - the g-th number of a stream that belongs to the request alone.  `sample_tokens_rows` is
+the definition and the numpy backend; csrc/sample_rows.hip evaluates it with the row body of csrc/sample.hip.
+
     manual_seed(seed)        seed every backend's generator, draws back to 0
     get_state(backend)       (seed, draws) of "cpu" or "hip"
 """
@@ -132,6 +137,42 @@ def sample_uniforms(seed: int, draw: int, rows: int) -> np.ndarray:
     return ((w0 >> np.uint32(8)).astype(np.float64) + 0.5) * 2.0 ** -24
 
 
+def _sample_block(xb, ub, inv_t, top_k: int, top_p: float) -> np.ndarray:
+    """the tokens (int64) of the float64 rows `xb` (rows, V) for the uniform numbers `ub` (rows,): the steps of `sample_tokens`"""
+    V = xb.shape[1]
+    nan = np.isnan(xb).any(axis=1)
+    m = np.where(nan, np.nan, np.max(np.where(np.isnan(xb), 0.0, xb), axis=1))
+    degenerate = nan | np.isinf(m)
+    tok = np.argmax(xb, axis=1).astype(np.int64)                        # numpy's rules: what a degenerate row answers
+    live = np.flatnonzero(~degenerate)
+    if live.size:
+        xl, ml = xb[live], m[live][:, None]
+        if 1 <= top_k < V:
+            keep = xl >= np.partition(xl, V - top_k, axis=1)[:, V - top_k][:, None]
+        else:
+            keep = np.ones(xl.shape, bool)
+        w = np.where(keep, np.exp((xl - ml) * inv_t), 0.0)
+        if 0.0 < top_p < 1.0:
+            order = np.argsort(-xl, axis=1, kind="stable")
+            xs, cs = np.take_along_axis(xl, order, axis=1), np.cumsum(np.take_along_axis(w, order, axis=1), axis=1)
+            # the mass at or above a value: the running sum at the END of its run of equal values
+            last = np.concatenate([xs[:, 1:] != xs[:, :-1], np.ones((xs.shape[0], 1), bool)], axis=1)
+            ends = np.where(last, np.arange(V)[None, :], V)
+            ends = np.minimum.accumulate(ends[:, ::-1], axis=1)[:, ::-1]
+            mass = np.take_along_axis(cs, ends, axis=1)
+            reached = (mass >= top_p * w.sum(axis=1)[:, None]) & np.take_along_axis(keep, order, axis=1)
+            first = np.argmax(reached, axis=1)
+            t = np.where(reached.any(axis=1), xs[np.arange(xs.shape[0]), first], -np.inf)
+            keep &= xl >= t[:, None]
+            w = np.where(keep, w, 0.0)
+        c = np.cumsum(w, axis=1)
+        hit = c >= (ub[live] * w.sum(axis=1))[:, None]
+        hit &= w > 0.0
+        highest = V - 1 - np.argmax((w > 0.0)[:, ::-1], axis=1)
+        tok[live] = np.where(hit.any(axis=1), np.argmax(hit, axis=1), highest)
+    return tok
+
+
 def sample_tokens(seed: int, draw: int, logits, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0) -> np.ndarray:
     """The definition of `Tensor.sample`, in float64: one token (int64) per row of `logits` (the last axis is the vocabulary,
     the leading axes are the rows) for call number `draw` of the stream - ONE call, whatever the shape.  Row r draws
@@ -155,39 +196,113 @@ def sample_tokens(seed: int, draw: int, logits, temperature: float = 1.0, top_k:
     inv_t = np.float64(np.float32(1.0 / np.float64(temperature)))
     block = max(1, (1 << 21) // V)                                          # rows at a time: a bound on the temporaries
     for r0 in range(0, rows, block):
-        xb, ub = x[r0:r0 + block], u[r0:r0 + block]
-        nan = np.isnan(xb).any(axis=1)
-        m = np.where(nan, np.nan, np.max(np.where(np.isnan(xb), 0.0, xb), axis=1))
-        degenerate = nan | np.isinf(m)
-        tok = np.argmax(xb, axis=1).astype(np.int64)                        # numpy's rules: what a degenerate row answers
-        live = np.flatnonzero(~degenerate)
-        if live.size:
-            xl, ml = xb[live], m[live][:, None]
-            if 1 <= top_k < V:
-                keep = xl >= np.partition(xl, V - top_k, axis=1)[:, V - top_k][:, None]
-            else:
-                keep = np.ones(xl.shape, bool)
-            w = np.where(keep, np.exp((xl - ml) * inv_t), 0.0)
-            if 0.0 < top_p < 1.0:
-                order = np.argsort(-xl, axis=1, kind="stable")
-                xs, cs = np.take_along_axis(xl, order, axis=1), np.cumsum(np.take_along_axis(w, order, axis=1), axis=1)
-                # the mass at or above a value: the running sum at the END of its run of equal values
-                last = np.concatenate([xs[:, 1:] != xs[:, :-1], np.ones((xs.shape[0], 1), bool)], axis=1)
-                ends = np.where(last, np.arange(V)[None, :], V)
-                ends = np.minimum.accumulate(ends[:, ::-1], axis=1)[:, ::-1]
-                mass = np.take_along_axis(cs, ends, axis=1)
-                reached = (mass >= top_p * w.sum(axis=1)[:, None]) & np.take_along_axis(keep, order, axis=1)
-                first = np.argmax(reached, axis=1)
-                t = np.where(reached.any(axis=1), xs[np.arange(xs.shape[0]), first], -np.inf)
-                keep &= xl >= t[:, None]
-                w = np.where(keep, w, 0.0)
-            c = np.cumsum(w, axis=1)
-            hit = c >= (ub[live] * w.sum(axis=1))[:, None]
-            hit &= w > 0.0
-            highest = V - 1 - np.argmax((w > 0.0)[:, ::-1], axis=1)
-            tok[live] = np.where(hit.any(axis=1), np.argmax(hit, axis=1), highest)
-        tokens[r0:r0 + block] = tok
+        tokens[r0:r0 + block] = _sample_block(x[r0:r0 + block], u[r0:r0 + block], inv_t, top_k, top_p)
     return tokens.reshape(lead)
+
+
+SAMPLING_WORDS = 8
+
+
+def sampling_table(temperature=1.0, top_k=0, top_p=1.0, seeds=0) -> np.ndarray:
+    """The parameter table of `Tensor.sample_rows`: int32 (n, 8), one row per request.  Each argument is a scalar or a sequence
+    of n; scalars broadcast (all scalars: n = 1).  Row i holds
+        word 0      the bits of inv_T = float32(1 / float64(temperature_i)); +0.0 - temperature 0 - means GREEDY
+        word 1      top_k
+        words 2, 3  the low and high half of the bits of top_p as a float64
+        words 4, 5  the low and high half of the 64-bit seed
+        words 6, 7  0
+    Every entry passes `check_sample_arguments`, except that a temperature of 0 is allowed; a seed must fit 64 bits and top_k 31."""
+    columns = [np.atleast_1d(np.asarray(c, dtype=object)) for c in (temperature, top_k, top_p, seeds)]
+    if any(c.ndim != 1 for c in columns):
+        raise ValueError("sampling_table: temperature, top_k, top_p and seeds are scalars or sequences")
+    n = max(c.size for c in columns)
+    if n < 1 or any(c.size not in (1, n) for c in columns):
+        raise ValueError("sampling_table: sequences of one length >= 1 (got %s)" % [c.size for c in columns])
+    table = np.zeros((n, SAMPLING_WORDS), np.uint32)
+    for i in range(n):
+        t, k, p, s = (c[i if c.size == n else 0] for c in columns)
+        t = float(t)
+        if t == 0.0 and not np.signbit(t):
+            _, k, p, _ = check_sample_arguments(np.float32, 1, 1.0, k, p, np.int32)
+            inv_t = np.float32(0.0)
+        else:
+            t, k, p, _ = check_sample_arguments(np.float32, 1, t, k, p, np.int32)
+            inv_t = np.float32(1.0 / np.float64(t))
+        s = int(s)
+        if not 0 <= s < 1 << 64:
+            raise ValueError("sampling_table: a seed must fit 64 bits (got %r)" % s)
+        if k >= 1 << 31:
+            raise ValueError("sampling_table: top_k must fit an int32 (got %r)" % k)
+        p_bits = int(np.float64(p).view(np.uint64))
+        table[i] = (int(inv_t.view(np.uint32)), k, p_bits & 0xFFFFFFFF, p_bits >> 32, s & 0xFFFFFFFF, s >> 32, 0, 0)
+    return table.view(np.int32)
+
+
+def check_sample_rows_operands(logits, table, index, counter, dtype):
+    """the validated token dtype of a `sample_rows` call; the operands are tensors of either backend (shapes and dtypes only)"""
+    shape, i32 = tuple(logits.shape), np.dtype(np.int32)
+    if not np.issubdtype(np.dtype(logits.dtype), np.floating):
+        raise ValueError("sample_rows: the logits must be floating point (got %s)" % np.dtype(logits.dtype))
+    if not (len(shape) == 2 or (len(shape) == 3 and shape[1] == 1)) or shape[-1] < 1:
+        raise ValueError("sample_rows: the logits are (rows, V) or (rows, 1, V) with V >= 1 (got %s)" % (shape,))
+    for name, t in (("table", table), ("index", index), ("counter", counter)):
+        if np.dtype(t.dtype) != i32:
+            raise ValueError("sample_rows: %s must be int32 (got %s)" % (name, np.dtype(t.dtype)))
+    if len(table.shape) != 2 or table.shape[1] != SAMPLING_WORDS or table.shape[0] < 1:
+        raise ValueError("sample_rows: the table is (n, %d) with n >= 1, as sampling_table lays it out (got %s)" % (SAMPLING_WORDS, tuple(table.shape)))
+    if tuple(index.shape) != (shape[0],) or tuple(counter.shape) != (table.shape[0],):
+        raise ValueError("sample_rows: index is (rows,) = (%d,) and counter (n,) = (%d,) (got %s and %s)" % (
+            shape[0], table.shape[0], tuple(index.shape), tuple(counter.shape)))
+    dtype = np.dtype(dtype)
+    if dtype not in (i32, np.dtype(np.int64)):
+        raise ValueError("sample_rows: the tokens are int32 or int64 (got %s)" % dtype)
+    return dtype
+
+
+def sample_tokens_rows(logits, table, index, counter):
+    """The definition of `Tensor.sample_rows`, in float64: (tokens (rows,) int64, bad (rows,) bool).  logits (rows, V); table
+    int32 (n, 8) as `sampling_table` lays it out; index (rows,): row r uses table row i = index[r]; counter (n,): g = counter[i].
+    Per row, in this order:
+      1. i < 0 (a free slot): the token is 0 and the row's logits are not read (they may hold NaN);
+      2. the row is BAD if i >= n, g < 0, top_k < 0, top_p is not in (0, 1], or inv_T has its sign set, is NaN or infinite: the
+         token is 0 and bad[r] is set; the other rows are computed;
+      3. inv_T == +0.0 is GREEDY: numpy's argmax of the row (the first NaN, the lowest index);
+      4. otherwise the token is that of `sample_tokens` for the row under (inv_T, top_k, top_p) with
+         u = sample_uniforms(seed, 0, g + 1)[g]: the g-th number of a stream of the request's own."""
+    x = np.asarray(logits)
+    table = np.ascontiguousarray(table, np.int32)
+    index, counter = np.asarray(index, np.int64).reshape(-1), np.asarray(counter, np.int64).reshape(-1)
+    if x.ndim != 2 or table.ndim != 2 or table.shape[1] != SAMPLING_WORDS or index.shape != (x.shape[0],) or counter.shape != (table.shape[0],):
+        raise ValueError("sample_tokens_rows: logits (rows, V), table (n, 8), index (rows,), counter (n,), got %s %s %s %s" % (
+            x.shape, table.shape, index.shape, counter.shape))
+    rows, n = x.shape[0], table.shape[0]
+    words = table.view(np.uint32)
+    tokens, bad = np.zeros(rows, np.int64), np.zeros(rows, bool)
+    for r in range(rows):
+        i = int(index[r])
+        if i < 0:
+            continue
+        if i >= n:
+            bad[r] = True
+            continue
+        g, top_k = int(counter[i]), int(table[i, 1])
+        inv_t = words[i, 0:1].view(np.float32)[0]
+        top_p = float(np.array([int(words[i, 2]) | (int(words[i, 3]) << 32)], np.uint64).view(np.float64)[0])
+        seed = int(words[i, 4]) | (int(words[i, 5]) << 32)
+        if g < 0 or top_k < 0 or not 0.0 < top_p <= 1.0 or np.signbit(inv_t) or not np.isfinite(inv_t):
+            bad[r] = True
+            continue
+        if inv_t == 0.0:
+            tokens[r] = int(np.argmax(x[r]))
+            continue
+        tokens[r] = _sample_block(x[r:r + 1].astype(np.float64), np.array([_row_uniform(seed, g)]), np.float64(inv_t), top_k, top_p)[0]
+    return tokens, bad
+
+
+def _row_uniform(seed: int, g: int) -> float:
+    """sample_uniforms(seed, 0, g + 1)[g] without the g numbers in front of it"""
+    w0 = philox4x32_10((g & 0xFFFFFFFF, (g >> 32) & 0xFFFFFFFF, 0, 0), (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF))[..., 0]
+    return float(((np.uint32(w0) >> np.uint32(8)).astype(np.float64) + 0.5) * 2.0 ** -24)
 
 
 def check_probability(p) -> float:
