@@ -55,6 +55,10 @@ Differences from the reference, on purpose:
                                                        # (one of them greedy) and the random stream seeded S + r, so its tokens do not
                                                        # depend on slots, chunk or the other requests (`serve(seeds=)`,
                                                        # `logits.sample_rows`, csrc/sample_rows.hip)
+    python examples/bert.py --serve 16 --repetition-penalty 1.3 --frequency-penalty 0.3 [--presence-penalty A] [--min-new-tokens M] [--graph] [--cpu]
+                                                       # per-request penalties on the logits in front of the draw, from the request's
+                                                       # own prompt and tokens: the randomly initialised model stops repeating one id
+                                                       # (`serve(repetition_penalty=, ...)`, `logits.penalize_rows`, csrc/penalize.hip)
     python examples/bert.py --mlm --bf16-decoder       # the decoder onto the vocabulary (forward, dx, dW) on the bf16 matrix cores:
                                                        # config key `decoder_precision="bf16"`; tensors stay float32
 """
@@ -796,11 +800,16 @@ def decode_mask(attention_mask, capacity):
     return full
 
 
-def next_token(logits, sampler=None, pool=None):
+def next_token(logits, sampler=None, pool=None, eos=None):
     """(b, 1) int32 ids from (b, 1, vocab) logits: the argmax, or - sampler = (temperature, top_k, top_p) - one call of
     `logits.sample`, which draws from the backend's random stream (one launch in place of argmax + astype); or - a pool with a
     sampling table - one `logits.sample_rows`: slot s under the parameters and the seed of the request it holds, its counter the
-    number of tokens that request has stored.  Nothing of the backend's stream is taken then"""
+    number of tokens that request has stored.  Nothing of the backend's stream is taken then.  A pool with a penalty table passes
+    the logits through ONE `logits.penalize_rows` first, in place, whichever draw follows: slot s under the penalties and the
+    history (prompt and stored tokens) of the request it holds; `eos` is the id its `min_new_tokens` keeps away.  A slot that is
+    still prefilling draws a token nobody keeps: penalising its row is harmless and keeps the step one function"""
+    if pool is not None and pool.penalties is not None:
+        logits = logits.penalize_rows(pool.penalties, pool.req, pool.prompts, pool.prompt_len, pool.out, pool.out_len, eos=eos)
     if pool is not None and pool.sampling is not None:
         return logits.sample_rows(pool.sampling, pool.req, pool.out_len)
     if sampler is None:
@@ -1331,7 +1340,7 @@ def serve_step(model, pool, sampler=None, eos=None):
         hidden = model.bert(pool.ids, cache=pool.cache, append=True, count=pool.count, token_positions=pool.position_ids)
     width = hidden.shape[-1]
     rows = hidden.reshape(-1, width)[pool.last].reshape(pool.slots, 1, width)
-    pool.commit(next_token(model.head(rows), sampler, pool), eos=eos)
+    pool.commit(next_token(model.head(rows), sampler, pool, eos), eos=eos)
 
 
 def fill_shared_prefix(model, pool, tokens):
@@ -1358,7 +1367,7 @@ def fill_shared_prefix(model, pool, tokens):
 
 def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, pad_token_id=0, graph=None, temperature=None, top_k=0,
           top_p=1.0, poll=8, lengths=None, cache=None, token_budget=None, num_blocks=None, block_size=16, shared_prefix=0, kv_dtype=None,
-          seeds=None):
+          seeds=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, min_new_tokens=0):
     """continuous batching: N requests through `slots` cache slots, a finished slot refilled at once from the queue while the
     others go on decoding.  prompts: a list of N int sequences, or (N, P) right-padded ids (an array or a tensor) with lengths=;
     max_new_tokens: an int, or N ints - a budget per request.  Returns (out (N, G) int32 with G = the largest budget, filled with
@@ -1383,6 +1392,17 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
     `random.sample_tokens(seed, 0, its logits, T, k, p)` whatever slots, chunk, token_budget, num_blocks and the other requests
     are; the backend's generator is neither read by a step nor advanced; `stats` gains `per_request_sampling`.  A float
     temperature= without seeds= is the route above, unchanged.
+    repetition_penalty, presence_penalty, frequency_penalty, min_new_tokens: each a scalar or one per request.  With any of them
+    not neutral (1, 0, 0, 0) every step passes its logits through ONE `logits.penalize_rows` (csrc/penalize.hip) in front of the
+    draw, driven by the pool's `req`, `prompts`, `prompt_len`, `out` and `out_len`; `stats` gains `penalties` and the step has
+    exactly one kernel more.  The contract: the g-th token of request r is drawn from the logits behind its prompt and its first
+    g tokens, passed through `random.penalize_logits` with that same history (the ids of prompt and tokens divided or multiplied
+    by repetition_penalty, the tokens' logits lowered by frequency_penalty times their count and by presence_penalty, eos_token_id
+    at -inf while fewer than min_new_tokens are stored).  So a request alone defines its tokens: they do not depend on slots,
+    chunk, token_budget, num_blocks, block_size, shared_prefix or the other requests - for greedy and for per-request sampled
+    requests; with kv_dtype="bf16" they are those of the rounded model, as before; the global temperature= route stays
+    schedule-dependent, penalties or not.  min_new_tokens without eos_token_id is accepted and does nothing.  With every value
+    neutral no table is built and the step is launch for launch what it was.
     cache: an nn.KVCache(per_row=True) of `slots` rows to use (default: one whose capacity is the longest request's need).
     token_budget: None, or T >= slots - every step is TOKEN-PACKED: it has T token rows for all slots together in place of
     (slots, chunk) rows.  A decoding slot takes one row; the rows left go to the prefilling slots in slot order, in pieces of at
@@ -1460,12 +1480,23 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
         assert all(np.ndim(v) == 0 or len(v) == n for v in (temperature, top_k, top_p, seeds)), \
             "serve: temperature, top_k, top_p and seeds are scalars or one entry per request (%d)" % n
         table = light.random.sampling_table(temperature, top_k, top_p, seeds)
-    pool = nn.RequestPool(cache, padded, lengths, budgets, chunk, pad_token_id=pad_token_id, max_positions=positions, sampling=table, **packed)
+    penalties = None
+    if any(np.ndim(v) or v != neutral for v, neutral in ((repetition_penalty, 1.0), (presence_penalty, 0.0), (frequency_penalty, 0.0), (min_new_tokens, 0))):
+        assert all(np.ndim(v) == 0 or len(v) == n for v in (repetition_penalty, presence_penalty, frequency_penalty, min_new_tokens)), \
+            "serve: repetition_penalty, presence_penalty, frequency_penalty and min_new_tokens are scalars or one entry per request (%d)" % n
+        penalties = light.random.penalty_table(repetition_penalty, presence_penalty, frequency_penalty, min_new_tokens)
+        penalties = np.ascontiguousarray(np.broadcast_to(penalties, (n, penalties.shape[1])))
+        if (penalties == light.random.penalty_table()).all():
+            penalties = None                                # sequences of neutral values: no table either
+    pool = nn.RequestPool(cache, padded, lengths, budgets, chunk, pad_token_id=pad_token_id, max_positions=positions, sampling=table, penalties=penalties,
+                          **packed)
     eos = None if eos_token_id is None else int(eos_token_id)
     sampler = None if temperature is None or table is not None else (temperature, top_k, top_p)
     stats = {"steps": 0, "requests": n, "slots": int(slots), "chunk": chunk, **packed}
     if table is not None:
         stats["per_request_sampling"] = True
+    if penalties is not None:
+        stats["penalties"] = True
     if paged:
         stats.update(num_blocks=cache.num_blocks, block_size=cache.block_size, kv_dtype=cache.kv_dtype, pool_bytes=cache.pool_bytes())
 
@@ -1527,6 +1558,10 @@ if __name__ == "__main__":
                 cycle = ((0.0, 0, 1.0), (1.0, 0, 1.0), (0.8, 50, 0.95), (0.7, 5, 1.0), (1.3, 0, 0.9))
                 sets = [cycle[r % len(cycle)] for r in range(n_requests)]
                 sampling = dict(temperature=[s[0] for s in sets], top_k=[s[1] for s in sets], top_p=[s[2] for s in sets], seeds=option("--seed", int, 0))
+        for flag, key, kind in (("--repetition-penalty", "repetition_penalty", float), ("--presence-penalty", "presence_penalty", float),
+                                ("--frequency-penalty", "frequency_penalty", float), ("--min-new-tokens", "min_new_tokens", int)):
+            if flag in sys.argv:
+                sampling[key] = option(flag, kind, None)
         t0 = time.perf_counter()
         if "--token-budget" in sys.argv:
             sampling["token_budget"] = option("--token-budget", int, None)

@@ -1148,6 +1148,28 @@ int lg_sample_last_plan(int32_t out[4]);
 int lg_sample_rows_f32(const float* logits, int64_t rows, int64_t cols, int64_t row_pitch, const int32_t* table, int64_t n,
                        const int32_t* index, const int32_t* counter, void* out, int out_itemsize);
 
+/* ---- per-request penalties on the logits, in place (csrc/penalize.hip) -------------------------------------
+ * Repetition, presence and frequency penalties and a minimum of new tokens, per row of fp32 logits [rows, cols] (row r at
+ * logits + r * row_pitch), IN PLACE and in ONE launch, every row under the parameters and the history of a request of its own.
+ * table: n rows of 4 int32 words (16-byte aligned) - the bits of rho (repetition), alpha (presence), beta (frequency) as floats,
+ * and min_new.  index: rows int32 words, row r uses request i = index[r].  prompts [n, P] (row pitch prompt_pitch), prompt_len
+ * [n], out [n, G] (row pitch out_pitch), out_len [n]: int32, the history of request i is prompts[i, :len] and out[i, :g] with
+ * len = prompt_len[i], g = out_len[i]; words behind len and g are never read.  eos: -1 (none) or an id below cols.  Per row:
+ *   1. i < 0: nothing of the row is read or written.
+ *   2. the row is BAD when i >= n, len is outside [0, P], g is outside [0, G], rho is not finite, <= 0 or has its sign set, alpha
+ *      or beta is not finite, min_new < 0, or an id of the history lies outside [0, cols): NOTHING of the row is written and
+ *      LG_STATUS_BAD_INDEX is raised (LG_EINDEX at the next synchronisation); the other rows are computed.
+ *   3. every id v of the history, once however often it occurs: x = x < 0 ? x * rho : x / rho (correctly rounded).
+ *   4. every v with c > 0 occurrences in out[i, :g]: x = (x - beta * float(c)) - alpha, three roundings, nothing fused.
+ *   5. eos >= 0 and g < min_new: logits[r, eos] = -inf, whatever 3 and 4 left there.
+ * Only the logits at ids of the history (and eos) are touched: the cost does not grow with cols.  lightgrad_amd/random.py
+ * `penalize_logits` is the definition; the results are its float32 results bit for bit.  rows == 0 returns LG_OK at once.
+ * 1 <= rows <= 65535; 1 <= cols < 2^31; row_pitch >= cols; n >= 1; P, G >= 1 and P + G <= 4096 (the history is kept in LDS);
+ * no NULL or misaligned operand; the logits share no byte with any other operand. */
+int lg_penalize_rows_f32(float* logits, int64_t rows, int64_t cols, int64_t row_pitch, const int32_t* table, int64_t n,
+                         const int32_t* index, const int32_t* prompts, int64_t prompt_pitch, int64_t P, const int32_t* prompt_len,
+                         const int32_t* out, int64_t out_pitch, int64_t G, const int32_t* out_len, int32_t eos);
+
 /* ---- hidden dropout inside the LayerNorm launches (csrc/rowwise.hip) ----------------------------------
  * A dropout that sits directly in front of or behind a LayerNorm over dense fp32 [rows, cols], drawn where the LayerNorm
  * kernel loads or stores its row.  ONE call of the stream above per forward; element i = row * cols + col of the dense operand

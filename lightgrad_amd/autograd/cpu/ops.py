@@ -440,6 +440,28 @@ def _sample_rows(logits, table, index, counter, dtype=np.int32):
 CpuTensor.sample_rows = _sample_rows
 
 
+def _penalize_rows(logits, table, index, prompts, prompt_len, out, out_len, eos=None):
+    """ logits.penalize_rows(table, index, prompts, prompt_len, out, out_len, eos=None): the repetition, presence and frequency
+    penalties and the minimum of new tokens of `lightgrad_amd.random.penalize_logits`, IN PLACE and outside the tape; returns
+    `logits`, so that `logits.penalize_rows(...).sample_rows(...)` reads well.  logits (rows, V) or (rows, 1, V), which must not
+    require a gradient; table int32 (n, 4) (`random.penalty_table`); index int32 (rows,), -1 = a free row (untouched, unread);
+    prompts (n, P), prompt_len (n,), out (n, G), out_len (n,) int32: the history of every request.  A bad row (see the definition)
+    keeps its bits and the call raises IndexError after every other row has been computed. """
+    rows, V, _ = _random.check_penalize_operands(logits, table, index, prompts, prompt_len, out, out_len, eos)
+    from ..grads import Gradients
+    assert logits.ctx is None and not (Gradients._is_enabled() and logits.requires_grad), \
+        "penalize_rows writes the logits in place: they must not require a gradient (run it under Gradients.no_grad(), or pass requires_grad=False)"
+    y, bad = _random.penalize_logits(logits.data.reshape(rows, V), table.data, index.data, prompts.data, prompt_len.data, out.data, out_len.data, eos)
+    good = np.flatnonzero((index.data >= 0) & ~bad)
+    logits.data[good] = y[good].reshape((len(good),) + tuple(logits.shape[1:]))      # a view keeps the bytes between its rows
+    if bad.any():
+        raise IndexError("penalize_rows: rows %s name no request, or one whose lengths, parameters or history are out of range" % np.flatnonzero(bad).tolist())
+    return logits
+
+
+CpuTensor.penalize_rows = _penalize_rows
+
+
 def _decode_commit(nxt, token, out_ids, pos, done, eos=None):
     """ nxt.decode_commit(token, out_ids, pos, done, eos=None): the per-row bookkeeping of one decode step, in place and outside
     the tape - the definition of the op.  nxt (b,) or (b, 1), token (b, 1), out_ids (b, columns), pos (b,), done (b,), all int32.

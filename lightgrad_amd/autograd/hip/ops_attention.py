@@ -811,6 +811,49 @@ def serve_commit(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos
 HipTensor.serve_commit = serve_commit
 
 
+""" Per-request penalties on the logits of a serving step in one launch (csrc/penalize.hip) """
+
+
+def penalize_rows(logits, table, index, prompts, prompt_len, out, out_len, eos=None):
+    """ logits.penalize_rows(table, index, prompts, prompt_len, out, out_len, eos=None): what `CpuTensor.penalize_rows` defines
+    (`lightgrad_amd.random.penalize_logits`) - repetition, presence and frequency penalties and the minimum of new tokens, every
+    row under the parameters and the history of the request index[r] - in ONE launch (lg_penalize_rows_f32), IN PLACE and outside
+    the tape; returns `logits`.  logits float32 (rows, V) or (rows, 1, V) that require no gradient, the last stride 1 and the row
+    pitch at least V (rows of a wider tensor are fine; a lazy producer is computed first); the others int32 HipTensors that share
+    no byte with the logits.  Only the logits at ids of the history are touched.  Everything the launch needs is device state, no
+    host value enters: a captured step replays as it stands.  A bad row keeps its bytes and raises the device's status flag
+    (IndexError at the next synchronisation). """
+    name = "penalize_rows"
+    operands = (table, index, prompts, prompt_len, out, out_len)
+    assert all(isinstance(t, HipTensor) for t in (logits,) + operands), "%s: every operand is a HipTensor" % name
+    if logits._dtype != _F32:
+        raise TypeError("penalize_rows is float32-only on HipTensor (got %s)" % logits._dtype)
+    rows, cols, eos = _random.check_penalize_operands(logits, table, index, prompts, prompt_len, out, out_len, eos)
+    assert logits.ctx is None and not (Gradients._is_enabled() and logits.requires_grad), \
+        "penalize_rows writes the logits in place: they must not require a gradient (run it under Gradients.no_grad(), or pass requires_grad=False)"
+    assert rows <= 65535, "%s: at most 65535 rows in a launch (got %d)" % (name, rows)
+    if rows == 0:
+        return logits
+    n, P, G = table._shape[0], prompts._shape[1], out._shape[1]
+    logits.data                                          # a lazy producer is computed now: the launch writes into its result
+    pitch = logits._strides[0] if rows > 1 else cols
+    # the launch writes the logits where they lie: a layout it cannot address is an error, never a copy
+    assert (cols == 1 or logits._strides[-1] == 1) and pitch >= cols, \
+        "%s: the vocabulary must be contiguous and the row pitch at least V = %d (strides %s)" % (name, cols, logits._strides)
+    # what is only read may be copied once into a layout the launch addresses
+    table, index, prompt_len, out_len = (t.contiguous() for t in (table, index, prompt_len, out_len))
+    prompts, out = ((t if (t._shape[1] == 1 or t._strides[1] == 1) and (n == 1 or t._strides[0] >= t._shape[1]) else t.contiguous()) for t in (prompts, out))
+    for t in (table, index, prompts, prompt_len, out, out_len):
+        assert not _shares_bytes(logits, t), "%s: the logits overlap an integer operand" % name
+    flush_lazy_readers(logits)
+    _l.check(_l.lib().lg_penalize_rows_f32(logits.ptr, rows, cols, pitch, table.ptr, n, index.ptr, prompts.ptr, prompts._strides[0] if n > 1 else P, P,
+                                           prompt_len.ptr, out.ptr, out._strides[0] if n > 1 else G, G, out_len.ptr, eos))
+    return logits
+
+
+HipTensor.penalize_rows = penalize_rows
+
+
 def serve_commit_packed(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, cu, ids, position_ids, last, capacity, chunk, eos=None):
     """ nxt.serve_commit_packed(prompts, prompt_len, budget, out, out_len, queue, req, pos, count, cu, ids, position_ids, last,
     capacity, chunk, eos=None): what `CpuTensor.serve_commit_packed` defines - `serve_commit` for a token-packed step: ids and

@@ -504,7 +504,7 @@ class RequestPool(object):
     here, on the host, against the capacity.  State, not parameters, like the cache.  Not a class of the reference."""
 
     def __init__(self, cache, prompts, lengths, budgets, chunk: int, pad_token_id: int = 0, max_positions=None, token_budget=None, prefix_blocks: int = 0,
-                 sampling=None):
+                 sampling=None, penalties=None):
         """max_positions: the model's position embeddings, if the caller knows them - the capacity must not exceed them.
         token_budget: None, or T >= slots - the steps are TOKEN-PACKED: ids and position_ids are (1, T), the step's tokens of all
         slots in one flat buffer, `cu` (slots + 1,) says which rows are whose, `last` names rows of the T, and `commit` is
@@ -517,7 +517,12 @@ class RequestPool(object):
         as `self.sampling`; a step then draws with `logits.sample_rows(pool.sampling, pool.req, pool.out_len)`: slot s under the row
         of the request it holds, with the number of tokens that request has stored as its counter.  Both are the pool's own
         state and right when the step draws (the previous commit laid the step out for req[s]; out_len[r] moves only when a
-        token is stored), so no commit changes.  None: `self.sampling` is None and everything is as it was."""
+        token is stored), so no commit changes.  None: `self.sampling` is None and everything is as it was.
+        penalties: None, or an int32 (N, 4) numpy table of `random.penalty_table` - repetition, presence and frequency penalty and
+        the minimum of new tokens per REQUEST, uploaded once as `self.penalties`; a step then passes its logits through
+        `logits.penalize_rows(pool.penalties, pool.req, pool.prompts, pool.prompt_len, pool.out, pool.out_len, eos=)` in front of
+        the draw.  The history is the pool's own state and right when the step draws, for the reason above; the launch keeps it
+        in LDS, so P + G <= 4096 is asserted here.  None: `self.penalties` is None and everything is as it was."""
         assert isinstance(cache, (KVCache, PagedKVCache)) and cache.per_row, \
             "RequestPool takes a cache with a position per sequence: nn.KVCache(..., per_row=True) or nn.PagedKVCache"
         self.paged = isinstance(cache, PagedKVCache)
@@ -564,6 +569,17 @@ class RequestPool(object):
             assert sampling.dtype == np.int32 and sampling.shape == (n, 8), \
                 "RequestPool: sampling= is the int32 (%d, 8) table of random.sampling_table, a row per request (got %s %s)" % (n, sampling.dtype, sampling.shape)
             self.sampling = tensor(sampling)
+        self.penalties = None
+        if penalties is not None:
+            from .random import PENALTY_MAX_HISTORY, PENALTY_WORDS
+            penalties = np.asarray(penalties)
+            assert penalties.dtype == np.int32 and penalties.shape == (n, PENALTY_WORDS), \
+                "RequestPool: penalties= is the int32 (%d, %d) table of random.penalty_table, a row per request (got %s %s)" % (
+                    n, PENALTY_WORDS, penalties.dtype, penalties.shape)
+            assert prompts.shape[1] + int(budgets.max()) <= PENALTY_MAX_HISTORY, \
+                "RequestPool: penalties= keeps a request's history in LDS: P + G = %d + %d ids exceed %d" % (
+                    prompts.shape[1], int(budgets.max()), PENALTY_MAX_HISTORY)
+            self.penalties = tensor(penalties)
         # queue[1] as a tensor of its own that shares the word (indexing a tensor copies: the poll would be a launch and a read)
         if isinstance(getattr(self.queue, "data", None), np.ndarray):
             self._finished = cls.from_numpy(self.queue.data[1:2], requires_grad=False)

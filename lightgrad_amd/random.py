@@ -31,6 +31,10 @@ integers - its token is the definition's wherever u is further than that roundin
 u = sample_uniforms(seed, 0, g + 1)[g] - the g-th number of a stream that belongs to the request alone.  `sample_tokens_rows` is
 the definition and the numpy backend; csrc/sample_rows.hip evaluates it with the row body of csrc/sample.hip.
 
+`Tensor.penalize_rows` (per-request repetition, presence and frequency penalties, a minimum of new tokens) draws nothing: it
+rewrites the logits at the ids of a request's own history in front of the draw.  `penalty_table` lays the parameters out,
+`penalize_logits` is the definition and the numpy backend; csrc/penalize.hip evaluates it in float32 bit for bit.
+
     manual_seed(seed)        seed every backend's generator, draws back to 0
     get_state(backend)       (seed, draws) of "cpu" or "hip"
 """
@@ -303,6 +307,122 @@ def _row_uniform(seed: int, g: int) -> float:
     """sample_uniforms(seed, 0, g + 1)[g] without the g numbers in front of it"""
     w0 = philox4x32_10((g & 0xFFFFFFFF, (g >> 32) & 0xFFFFFFFF, 0, 0), (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF))[..., 0]
     return float(((np.uint32(w0) >> np.uint32(8)).astype(np.float64) + 0.5) * 2.0 ** -24)
+
+
+PENALTY_WORDS = 4
+PENALTY_MAX_HISTORY = 4096                                # P + G: what csrc/penalize.hip keeps in LDS (speculate.hip's bound for a sequence)
+
+
+def penalty_table(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, min_new_tokens=0) -> np.ndarray:
+    """The parameter table of `Tensor.penalize_rows`: int32 (n, 4), one row per request.  Each argument is a scalar or a sequence
+    of n; scalars broadcast (all scalars: n = 1).  Row i holds
+        word 0  the bits of rho = float32(repetition_penalty_i)       word 1  the bits of alpha = float32(presence_penalty_i)
+        word 2  the bits of beta = float32(frequency_penalty_i)       word 3  min_new_tokens_i
+    The float32 value IS the parameter: rho must be finite and > 0, alpha and beta finite, 0 <= min_new_tokens < 2**31."""
+    columns = [np.atleast_1d(np.asarray(c, dtype=object)) for c in (repetition_penalty, presence_penalty, frequency_penalty, min_new_tokens)]
+    if any(c.ndim != 1 for c in columns):
+        raise ValueError("penalty_table: the penalties and min_new_tokens are scalars or sequences")
+    n = max(c.size for c in columns)
+    if n < 1 or any(c.size not in (1, n) for c in columns):
+        raise ValueError("penalty_table: sequences of one length >= 1 (got %s)" % [c.size for c in columns])
+    table = np.zeros((n, PENALTY_WORDS), np.uint32)
+    for i in range(n):
+        rho, alpha, beta, m = (c[i if c.size == n else 0] for c in columns)
+        with np.errstate(over="ignore"):
+            rho, alpha, beta = np.float32(float(rho)), np.float32(float(alpha)), np.float32(float(beta))
+        if not (np.isfinite(rho) and rho > 0):
+            raise ValueError("penalty_table: repetition_penalty must be finite and > 0 as a float32 (got %r)" % (rho,))
+        if not (np.isfinite(alpha) and np.isfinite(beta)):
+            raise ValueError("penalty_table: presence_penalty and frequency_penalty must be finite as float32 (got %r, %r)" % (alpha, beta))
+        if int(m) != m or not 0 <= int(m) < 1 << 31:
+            raise ValueError("penalty_table: min_new_tokens must be an int in [0, 2**31) (got %r)" % (m,))
+        table[i] = (int(rho.view(np.uint32)), int(alpha.view(np.uint32)), int(beta.view(np.uint32)), int(m))
+    return table.view(np.int32)
+
+
+def check_penalize_operands(logits, table, index, prompts, prompt_len, out, out_len, eos):
+    """the validated (rows, V, eos or -1) of a `penalize_rows` call; the operands are tensors of either backend (shapes and dtypes
+    only)"""
+    shape, i32 = tuple(logits.shape), np.dtype(np.int32)
+    if not np.issubdtype(np.dtype(logits.dtype), np.floating):
+        raise ValueError("penalize_rows: the logits must be floating point (got %s)" % np.dtype(logits.dtype))
+    if not (len(shape) == 2 or (len(shape) == 3 and shape[1] == 1)) or shape[-1] < 1:
+        raise ValueError("penalize_rows: the logits are (rows, V) or (rows, 1, V) with V >= 1 (got %s)" % (shape,))
+    operands = (("table", table), ("index", index), ("prompts", prompts), ("prompt_len", prompt_len), ("out", out), ("out_len", out_len))
+    for name, t in operands:
+        if np.dtype(t.dtype) != i32:
+            raise ValueError("penalize_rows: %s must be int32 (got %s)" % (name, np.dtype(t.dtype)))
+    n = table.shape[0] if len(table.shape) == 2 else 0
+    if n < 1 or table.shape[1] != PENALTY_WORDS:
+        raise ValueError("penalize_rows: the table is (n, %d) with n >= 1, as penalty_table lays it out (got %s)" % (PENALTY_WORDS, tuple(table.shape)))
+    if tuple(index.shape) != (shape[0],) or tuple(prompt_len.shape) != (n,) or tuple(out_len.shape) != (n,) or len(prompts.shape) != 2 or \
+            len(out.shape) != 2 or prompts.shape[0] != n or out.shape[0] != n or prompts.shape[1] < 1 or out.shape[1] < 1:
+        raise ValueError("penalize_rows: index (rows,) = (%d,), prompts (n, P), out (n, G), prompt_len and out_len (n,) with n = %d, P, G >= 1 (got %s)" % (
+            shape[0], n, [tuple(t.shape) for _, t in operands[1:]]))
+    assert prompts.shape[1] + out.shape[1] <= PENALTY_MAX_HISTORY, \
+        "penalize_rows: a history of P + G = %d + %d ids exceeds the %d the launch keeps in LDS" % (prompts.shape[1], out.shape[1], PENALTY_MAX_HISTORY)
+    if eos is not None and (int(eos) != eos or not 0 <= int(eos) < shape[-1]):
+        raise ValueError("penalize_rows: eos is None or an id in 0 .. V - 1 = %d (got %r)" % (shape[-1] - 1, eos))
+    return shape[0], shape[-1], -1 if eos is None else int(eos)
+
+
+def penalize_logits(logits, table, index, prompts, prompt_len, out, out_len, eos=None):
+    """The definition of `Tensor.penalize_rows`: (y (rows, V), bad (rows,) bool).  logits (rows, V) float32 or float64; table int32
+    (n, 4) as `penalty_table` lays it out (rho, alpha, beta, min_new); index (rows,): row r uses request i = index[r]; prompts
+    (n, P), prompt_len (n,), out (n, G), out_len (n,): the request's history; eos: None or an id in 0 .. V - 1.  Float32 logits are
+    computed in float32, every operation rounded once and in this order; float64 logits by the same expressions in float64 with
+    the float32 parameters widened.  Per row:
+      1. i < 0 (a free slot): the row comes back as it is; its logits are not read (they may hold NaN);
+      2. with len = prompt_len[i], g = out_len[i], the row is BAD if i >= n, len is outside 0 .. P, g is outside 0 .. G, rho is
+         not finite, <= 0 or has its sign set, alpha or beta is not finite, min_new < 0, or any of prompts[i, :len], out[i, :g]
+         lies outside 0 .. V - 1: it comes back bit for bit and bad[r] is set; the other rows are computed.  Words behind len and
+         g are never read;
+      3. for every id v that occurs in prompts[i, :len] or out[i, :g], once however often: x = x * rho if x < 0 else x / rho (a NaN
+         stays one, -0.0 takes the division, an infinity stays itself);
+      4. for every v that occurs c_v > 0 times in out[i, :g]: x = (x - beta * c_v) - alpha (one product, two subtractions);
+      5. if eos is given and g < min_new: y[eos] = -inf, whatever steps 3 and 4 left there."""
+    x = np.asarray(logits)
+    if x.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError("penalize_logits: float32 or float64 logits (got %s)" % x.dtype)
+    table = np.ascontiguousarray(table, np.int32)
+    index, prompt_len, out_len = (np.asarray(a, np.int64).reshape(-1) for a in (index, prompt_len, out_len))
+    prompts, out = np.asarray(prompts), np.asarray(out)
+    if x.ndim != 2 or x.shape[1] < 1 or table.ndim != 2 or table.shape[1] != PENALTY_WORDS or prompts.ndim != 2 or out.ndim != 2 or \
+            index.shape != (x.shape[0],) or not (prompts.shape[0] == out.shape[0] == prompt_len.size == out_len.size == table.shape[0]):
+        raise ValueError("penalize_logits: logits (rows, V), table (n, 4), index (rows,), prompts (n, P), prompt_len (n,), out (n, G), out_len (n,), got %s" % (
+            [a.shape for a in (x, table, index, prompts, prompt_len, out, out_len)],))
+    (rows, V), n, P, G = x.shape, table.shape[0], prompts.shape[1], out.shape[1]
+    if eos is not None and (int(eos) != eos or not 0 <= int(eos) < V):
+        raise ValueError("penalize_logits: eos is None or an id in 0 .. V - 1 = %d (got %r)" % (V - 1, eos))
+    real = x.dtype.type
+    parameters = table.view(np.float32)
+    y, bad = x.copy(), np.zeros(rows, bool)
+    for r in range(rows):
+        i = int(index[r])
+        if i < 0:
+            continue
+        if i >= n:
+            bad[r] = True
+            continue
+        length, g = int(prompt_len[i]), int(out_len[i])
+        rho, alpha, beta, min_new = parameters[i, 0], parameters[i, 1], parameters[i, 2], int(table[i, 3])
+        if not (0 <= length <= P and 0 <= g <= G and np.isfinite(rho) and rho > 0 and np.isfinite(alpha) and np.isfinite(beta) and min_new >= 0):
+            bad[r] = True
+            continue
+        drawn = np.asarray(out[i, :g], np.int64)
+        history = np.concatenate([np.asarray(prompts[i, :length], np.int64), drawn])
+        if history.size and (history.min() < 0 or history.max() >= V):
+            bad[r] = True
+            continue
+        with np.errstate(all="ignore"):
+            seen = np.unique(history)
+            v = y[r, seen]
+            y[r, seen] = np.where(v < 0, v * real(rho), v / real(rho))
+            counted, counts = np.unique(drawn, return_counts=True)
+            y[r, counted] = (y[r, counted] - real(beta) * counts.astype(x.dtype)) - real(alpha)
+        if eos is not None and g < min_new:
+            y[r, int(eos)] = -np.inf
+    return y, bad
 
 
 def check_probability(p) -> float:
