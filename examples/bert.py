@@ -59,6 +59,10 @@ Differences from the reference, on purpose:
                                                        # per-request penalties on the logits in front of the draw, from the request's
                                                        # own prompt and tokens: the randomly initialised model stops repeating one id
                                                        # (`serve(repetition_penalty=, ...)`, `logits.penalize_rows`, csrc/penalize.hip)
+    python examples/bert.py --serve 16 --logprobs 3 [--graph] [--cpu]
+                                                       # the log-probability of every token and the 3 most likely ids of its step,
+                                                       # one launch a step behind the draw, nothing read back until the end
+                                                       # (`serve(logprobs=)`, `logits.logprob_rows`, csrc/logprob.hip)
     python examples/bert.py --mlm --bf16-decoder       # the decoder onto the vocabulary (forward, dx, dW) on the bf16 matrix cores:
                                                        # config key `decoder_precision="bf16"`; tensors stay float32
 """
@@ -807,15 +811,23 @@ def next_token(logits, sampler=None, pool=None, eos=None):
     number of tokens that request has stored.  Nothing of the backend's stream is taken then.  A pool with a penalty table passes
     the logits through ONE `logits.penalize_rows` first, in place, whichever draw follows: slot s under the penalties and the
     history (prompt and stored tokens) of the request it holds; `eos` is the id its `min_new_tokens` keeps away.  A slot that is
-    still prefilling draws a token nobody keeps: penalising its row is harmless and keeps the step one function"""
+    still prefilling draws a token nobody keeps: penalising its row is harmless and keeps the step one function.  A pool with
+    `logprobs` scores the token behind whichever draw it was with ONE `logits.logprob_rows`, against the logits the draw read
+    (penalised, in front of temperature, top-k and top-p), into column out_len[r] of the request r the slot holds - the caller's
+    `pool.commit` moves out_len afterwards.  A prefilling slot writes column 0 of its request with a value nobody keeps: the
+    request's first stored token overwrites it"""
     if pool is not None and pool.penalties is not None:
         logits = logits.penalize_rows(pool.penalties, pool.req, pool.prompts, pool.prompt_len, pool.out, pool.out_len, eos=eos)
     if pool is not None and pool.sampling is not None:
-        return logits.sample_rows(pool.sampling, pool.req, pool.out_len)
-    if sampler is None:
-        return logits.argmax(-1).astype(np.int32)
-    temperature, top_k, top_p = sampler
-    return logits.sample(temperature=temperature, top_k=top_k, top_p=top_p, dtype=np.int32)
+        nxt = logits.sample_rows(pool.sampling, pool.req, pool.out_len)
+    elif sampler is None:
+        nxt = logits.argmax(-1).astype(np.int32)
+    else:
+        temperature, top_k, top_p = sampler
+        nxt = logits.sample(temperature=temperature, top_k=top_k, top_p=top_p, dtype=np.int32)
+    if pool is not None and pool.logprobs is not None:
+        logits.logprob_rows(nxt, pool.logprobs, pool.req, pool.out_len, pool.logprob, pool.top_ids, pool.top_logprob)
+    return nxt
 
 
 def decode_step(model, cache, token, out_ids, mask=None, sampler=None):
@@ -1367,7 +1379,7 @@ def fill_shared_prefix(model, pool, tokens):
 
 def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, pad_token_id=0, graph=None, temperature=None, top_k=0,
           top_p=1.0, poll=8, lengths=None, cache=None, token_budget=None, num_blocks=None, block_size=16, shared_prefix=0, kv_dtype=None,
-          seeds=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, min_new_tokens=0):
+          seeds=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, min_new_tokens=0, logprobs=None):
     """continuous batching: N requests through `slots` cache slots, a finished slot refilled at once from the queue while the
     others go on decoding.  prompts: a list of N int sequences, or (N, P) right-padded ids (an array or a tensor) with lengths=;
     max_new_tokens: an int, or N ints - a budget per request.  Returns (out (N, G) int32 with G = the largest budget, filled with
@@ -1403,6 +1415,19 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
     requests; with kv_dtype="bf16" they are those of the rounded model, as before; the global temperature= route stays
     schedule-dependent, penalties or not.  min_new_tokens without eos_token_id is accepted and does nothing.  With every value
     neutral no table is built and the step is launch for launch what it was.
+    logprobs: None, an int 0 .. 8 for every request, or one entry per request (None or -1: none for that request; 0: the
+    log-probability of each of its tokens; k: also the k most likely ids of every step with theirs).  Every step then calls ONE
+    `logits.logprob_rows` (csrc/logprob.hip) behind the draw - argmax, `sample` or `sample_rows`, penalised or not - and in front
+    of the commit, driven by the pool's `req` and `out_len`: the step has exactly one kernel more and still no host read.
+    `stats["logprobs"]` is a dict of three tensors on the model's backend, not read back: `token` float32 (N, G), `top_ids` int32
+    (N, G, n) and `top` float32 (N, G, n) with n = max(the largest entry, 1); the returned tuple does not change.  The contract:
+    column g < out_len[r] of request r holds `random.token_logprobs_rows` applied to the logits behind its prompt and its first
+    g tokens - the logits the draw read: behind the penalties, in front of temperature, top-k and top-p -; columns from
+    out_len[r] on, the entries behind a request's own k, and the rows of a request without log-probabilities hold the fills
+    (+0.0, -1, +0.0).  The values do not depend on slots, chunk, token_budget, num_blocks, block_size or the other requests beyond
+    the float32 rounding of the forward (with kv_dtype="bf16": of the rounded model); the ids in `top_ids` are exact wherever the
+    gaps between the reference's ranks rule out a near-tie.  With logprobs=None nothing is built, `stats` has no such key and
+    the step is launch for launch what it was.
     cache: an nn.KVCache(per_row=True) of `slots` rows to use (default: one whose capacity is the longest request's need).
     token_budget: None, or T >= slots - every step is TOKEN-PACKED: it has T token rows for all slots together in place of
     (slots, chunk) rows.  A decoding slot takes one row; the rows left go to the prefilling slots in slot order, in pieces of at
@@ -1488,8 +1513,9 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
         penalties = np.ascontiguousarray(np.broadcast_to(penalties, (n, penalties.shape[1])))
         if (penalties == light.random.penalty_table()).all():
             penalties = None                                # sequences of neutral values: no table either
+    want = None if logprobs is None else light.random.logprob_want(logprobs, n)
     pool = nn.RequestPool(cache, padded, lengths, budgets, chunk, pad_token_id=pad_token_id, max_positions=positions, sampling=table, penalties=penalties,
-                          **packed)
+                          logprobs=want, **packed)
     eos = None if eos_token_id is None else int(eos_token_id)
     sampler = None if temperature is None or table is not None else (temperature, top_k, top_p)
     stats = {"steps": 0, "requests": n, "slots": int(slots), "chunk": chunk, **packed}
@@ -1497,6 +1523,8 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
         stats["per_request_sampling"] = True
     if penalties is not None:
         stats["penalties"] = True
+    if want is not None:
+        stats["logprobs"] = {"token": pool.logprob, "top_ids": pool.top_ids, "top": pool.top_logprob}
     if paged:
         stats.update(num_blocks=cache.num_blocks, block_size=cache.block_size, kv_dtype=cache.kv_dtype, pool_bytes=cache.pool_bytes())
 
@@ -1562,6 +1590,8 @@ if __name__ == "__main__":
                                 ("--frequency-penalty", "frequency_penalty", float), ("--min-new-tokens", "min_new_tokens", int)):
             if flag in sys.argv:
                 sampling[key] = option(flag, kind, None)
+        if "--logprobs" in sys.argv:
+            sampling["logprobs"] = option("--logprobs", int, 0)
         t0 = time.perf_counter()
         if "--token-budget" in sys.argv:
             sampling["token_budget"] = option("--token-budget", int, None)
@@ -1582,6 +1612,14 @@ if __name__ == "__main__":
                 info["num_blocks"], info["block_size"], info["prefix_blocks"], info["kv_dtype"] or "float32", info["pool_bytes"]))
         for r in range(min(n_requests, 8)):
             print("request %d: %s" % (r, " ".join(str(i) for i in tokens[r, :counts[r]])))
+        if "logprobs" in info:
+            # request 0, token by token: its log-probability and what else the model considered
+            scores, best, best_scores = (info["logprobs"][key].numpy() for key in ("token", "top_ids", "top"))
+            print("request 0, log-probability %.4f over %d tokens (perplexity %.2f):" % (
+                scores[0, :counts[0]].sum(), counts[0], np.exp(-scores[0, :counts[0]].mean())))
+            for g in range(counts[0]):
+                print("  token %6d  %9.4f   top: %s" % (tokens[0, g], scores[0, g], "  ".join(
+                    "%d (%.4f)" % (i, v) for i, v in zip(best[0, g], best_scores[0, g]) if i >= 0)))
         sys.exit(0)
     if "--generate" in sys.argv:
         n_new = int(sys.argv[sys.argv.index("--generate") + 1])

@@ -1170,6 +1170,30 @@ int lg_penalize_rows_f32(float* logits, int64_t rows, int64_t cols, int64_t row_
                          const int32_t* index, const int32_t* prompts, int64_t prompt_pitch, int64_t P, const int32_t* prompt_len,
                          const int32_t* out, int64_t out_pitch, int64_t G, const int32_t* out_len, int32_t eos);
 
+/* ---- per-token log-probabilities and top-n alternatives (csrc/logprob.hip) ------------------------------------
+ * The log-probability of the token just drawn, and the n most likely ids with theirs, per row of fp32 logits [rows, cols] (row r
+ * at logits + r * row_pitch) in ONE launch, every row into the cell of a request of its own.  token: rows int32, the id drawn
+ * from row r.  want [n] int32 per request: -1 nothing, 0 the token's only, k in 1 .. n_max also the k most likely ids.  index:
+ * rows int32, row r belongs to request i = index[r].  counter [n] int32: the column g = counter[i].  logprob fp32 [n, G], top_ids
+ * int32 and top_logprob fp32 [n, G, n_max], dense.  Per row:
+ *   1. i < 0, or i < n and want[i] == -1: nothing of the row is read, nothing is written.
+ *   2. the row is BAD when i >= n, g is outside [0, G), want[i] is outside [-1, n_max] or the token is outside [0, cols): NOTHING
+ *      is written and LG_STATUS_BAD_INDEX is raised (LG_EINDEX at the next synchronisation); the other rows are computed.
+ *   3. with m = max x and S = sum_j exp(x_j - m): logprob[i, g] = (x_token - m) - log S; top_ids[i, g, :k'] the k' = min(want[i],
+ *      cols) largest values' ids, descending, equal values (-0.0 == +0.0) to the lower index; top_logprob[i, g, :k'] their
+ *      (x_j - m) - log S.  The entries behind k' keep their bytes.  A -inf logit has -inf.
+ *   4. a row with a NaN, with +inf, or of nothing but -inf: NaN to logprob[i, g] and top_logprob[i, g, :want[i]], -1 to
+ *      top_ids[i, g, :want[i]].
+ * S is a sum of 64-bit integers floor(2^40 * __expf(x_j - m)): the same bits from run to run; the differences and log S are fp32.
+ * lightgrad_amd/random.py `token_logprobs_rows` is the definition, in float64.  Two rows of one request write one cell: the
+ * caller's rows name distinct requests.  rows == 0 returns LG_OK at once.  1 <= rows <= 65535; 1 <= cols < 2^31; row_pitch >=
+ * cols; n, G >= 1; 1 <= n_max <= 8; no NULL operand, every operand 4-byte aligned; an output shares no byte with any other
+ * operand.  A row of at most lg_logprob_lds_cols() floats is staged in LDS, a wider one is read again from memory. */
+int lg_logprob_rows_f32(const float* logits, int64_t rows, int64_t cols, int64_t row_pitch, const int32_t* token, const int32_t* want,
+                        int64_t n, const int32_t* index, const int32_t* counter, float* logprob, int64_t G, int32_t* top_ids,
+                        float* top_logprob, int64_t n_max);
+int lg_logprob_lds_cols(void);
+
 /* ---- hidden dropout inside the LayerNorm launches (csrc/rowwise.hip) ----------------------------------
  * A dropout that sits directly in front of or behind a LayerNorm over dense fp32 [rows, cols], drawn where the LayerNorm
  * kernel loads or stores its row.  ONE call of the stream above per forward; element i = row * cols + col of the dense operand

@@ -462,6 +462,23 @@ def _penalize_rows(logits, table, index, prompts, prompt_len, out, out_len, eos=
 CpuTensor.penalize_rows = _penalize_rows
 
 
+def _logprob_rows(logits, token, want, index, counter, logprob, top_ids, top_logprob):
+    """ logits.logprob_rows(token, want, index, counter, logprob, top_ids, top_logprob): the log-probability of the token just
+    drawn and the top-n alternatives of `lightgrad_amd.random.token_logprobs_rows`, written IN PLACE into the three outputs and
+    outside the tape - the definition of the op; returns None.  logits (rows, V) or (rows, 1, V): what the draw read; token int32
+    (rows,) or (rows, 1); want int32 (N,): -1 nothing, 0 the token's only, k also the k most likely ids; index int32 (rows,), -1 =
+    a free row (unread); counter int32 (N,): the column; logprob float32 (N, G), top_ids int32 and top_logprob float32 (N, G, n),
+    n <= 8.  A bad row (see the definition) writes nothing and the call raises IndexError after every other row has been written. """
+    rows, V, _, _, _ = _random.check_logprob_operands(logits, token, want, index, counter, logprob, top_ids, top_logprob)
+    bad = _random.token_logprobs_rows(logits.data.reshape(rows, V), token.data, want.data, index.data, counter.data, logprob.data, top_ids.data,
+                                      top_logprob.data)
+    if bad.any():
+        raise IndexError("logprob_rows: rows %s name no request, or one whose column, count of alternatives or token is out of range" % np.flatnonzero(bad).tolist())
+
+
+CpuTensor.logprob_rows = _logprob_rows
+
+
 def _decode_commit(nxt, token, out_ids, pos, done, eos=None):
     """ nxt.decode_commit(token, out_ids, pos, done, eos=None): the per-row bookkeeping of one decode step, in place and outside
     the tape - the definition of the op.  nxt (b,) or (b, 1), token (b, 1), out_ids (b, columns), pos (b,), done (b,), all int32.

@@ -854,6 +854,48 @@ def penalize_rows(logits, table, index, prompts, prompt_len, out, out_len, eos=N
 HipTensor.penalize_rows = penalize_rows
 
 
+""" Per-token log-probabilities and top-n alternatives of a serving step in one launch (csrc/logprob.hip) """
+
+
+def logprob_rows(logits, token, want, index, counter, logprob, top_ids, top_logprob):
+    """ logits.logprob_rows(token, want, index, counter, logprob, top_ids, top_logprob): what `CpuTensor.logprob_rows` defines
+    (`lightgrad_amd.random.token_logprobs_rows`) - the log-probability of the token just drawn from each row and the want[i] most
+    likely ids with theirs, into column counter[i] of request i = index[r] - in ONE launch (lg_logprob_rows_f32), IN PLACE on the
+    three outputs and outside the tape; returns None.  logits float32 (rows, V) or (rows, 1, V), the last stride 1 and the row
+    pitch at least V (rows of a wider tensor are fine; another layout is copied once: the logits are only read); token, want,
+    index, counter int32; logprob float32 (N, G), top_ids int32 and top_logprob float32 (N, G, n), dense, sharing no byte with
+    each other or with anything the launch reads.  Everything the launch needs is device state, no host value enters: a captured
+    step replays as it stands.  A bad row writes nothing and raises the device's status flag (IndexError at the next
+    synchronisation). """
+    name = "logprob_rows"
+    reads, writes = (token, want, index, counter), (logprob, top_ids, top_logprob)
+    assert all(isinstance(t, HipTensor) for t in (logits,) + reads + writes), "%s: every operand is a HipTensor" % name
+    if logits._dtype != _F32:
+        raise TypeError("logprob_rows is float32-only on HipTensor (got %s)" % logits._dtype)
+    rows, cols, n, G, n_max = _random.check_logprob_operands(logits, token, want, index, counter, logprob, top_ids, top_logprob)
+    assert rows <= 65535, "%s: at most 65535 rows in a launch (got %d)" % (name, rows)
+    if rows == 0:
+        return None
+    src, pitch = logits, logits._strides[0] if rows > 1 else cols
+    if (cols > 1 and src._strides[-1] != 1) or pitch < cols:
+        src, pitch = logits.contiguous(), cols           # the vocabulary contiguous, one pitch from row to row
+    token, want, index, counter = (t.contiguous() for t in reads)
+    for t in writes:
+        # the launch writes the outputs where they lie: a layout it cannot address is an error, never a copy
+        assert t.is_contiguous(), "%s: logprob, top_ids and top_logprob must be dense (shape %s, strides %s)" % (name, t._shape, t._strides)
+    for k, t in enumerate(writes):
+        for other in (src, token, want, index, counter) + writes[:k]:
+            assert not _shares_bytes(t, other), "%s: an output overlaps another operand" % name
+        t.data                                           # a lazy producer is computed now: the launch writes into its result
+        flush_lazy_readers(t)
+    _l.check(_l.lib().lg_logprob_rows_f32(src.ptr, rows, cols, pitch, token.ptr, want.ptr, n, index.ptr, counter.ptr, logprob.ptr, G, top_ids.ptr,
+                                          top_logprob.ptr, n_max))
+    return None
+
+
+HipTensor.logprob_rows = logprob_rows
+
+
 def serve_commit_packed(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, cu, ids, position_ids, last, capacity, chunk, eos=None):
     """ nxt.serve_commit_packed(prompts, prompt_len, budget, out, out_len, queue, req, pos, count, cu, ids, position_ids, last,
     capacity, chunk, eos=None): what `CpuTensor.serve_commit_packed` defines - `serve_commit` for a token-packed step: ids and

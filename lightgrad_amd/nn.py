@@ -504,7 +504,7 @@ class RequestPool(object):
     here, on the host, against the capacity.  State, not parameters, like the cache.  Not a class of the reference."""
 
     def __init__(self, cache, prompts, lengths, budgets, chunk: int, pad_token_id: int = 0, max_positions=None, token_budget=None, prefix_blocks: int = 0,
-                 sampling=None, penalties=None):
+                 sampling=None, penalties=None, logprobs=None):
         """max_positions: the model's position embeddings, if the caller knows them - the capacity must not exceed them.
         token_budget: None, or T >= slots - the steps are TOKEN-PACKED: ids and position_ids are (1, T), the step's tokens of all
         slots in one flat buffer, `cu` (slots + 1,) says which rows are whose, `last` names rows of the T, and `commit` is
@@ -522,7 +522,13 @@ class RequestPool(object):
         the minimum of new tokens per REQUEST, uploaded once as `self.penalties`; a step then passes its logits through
         `logits.penalize_rows(pool.penalties, pool.req, pool.prompts, pool.prompt_len, pool.out, pool.out_len, eos=)` in front of
         the draw.  The history is the pool's own state and right when the step draws, for the reason above; the launch keeps it
-        in LDS, so P + G <= 4096 is asserted here.  None: `self.penalties` is None and everything is as it was."""
+        in LDS, so P + G <= 4096 is asserted here.  None: `self.penalties` is None and everything is as it was.
+        logprobs: None, or N ints per REQUEST (`random.logprob_want`): -1 = none for it, 0 = the log-probability of each of its
+        tokens, k in 1 .. 8 = also the k most likely ids of every step.  They are uploaded once as `self.logprobs`, next to
+        `self.logprob` float32 (N, G), `self.top_ids` int32 (N, G, n) and `self.top_logprob` float32 (N, G, n) with n = max(k, 1),
+        filled with +0.0, -1 and +0.0; a step then calls `logits.logprob_rows(nxt, pool.logprobs, pool.req, pool.out_len,
+        pool.logprob, pool.top_ids, pool.top_logprob)` behind the draw and in front of `commit`, which moves out_len: token g of
+        request r is scored in column g.  None: the four attributes are None and everything is as it was."""
         assert isinstance(cache, (KVCache, PagedKVCache)) and cache.per_row, \
             "RequestPool takes a cache with a position per sequence: nn.KVCache(..., per_row=True) or nn.PagedKVCache"
         self.paged = isinstance(cache, PagedKVCache)
@@ -580,6 +586,14 @@ class RequestPool(object):
                 "RequestPool: penalties= keeps a request's history in LDS: P + G = %d + %d ids exceed %d" % (
                     prompts.shape[1], int(budgets.max()), PENALTY_MAX_HISTORY)
             self.penalties = tensor(penalties)
+        self.logprobs = self.logprob = self.top_ids = self.top_logprob = None
+        if logprobs is not None:
+            from .random import logprob_want
+            want = logprob_want(list(logprobs), n)
+            cells = (n, int(budgets.max()), max(int(want.max()), 1))
+            self.logprobs, self.top_ids = tensor(want), tensor(np.full(cells, -1))
+            self.logprob = cls.from_numpy(np.zeros(cells[:2], np.float32), requires_grad=False)
+            self.top_logprob = cls.from_numpy(np.zeros(cells, np.float32), requires_grad=False)
         # queue[1] as a tensor of its own that shares the word (indexing a tensor copies: the poll would be a launch and a read)
         if isinstance(getattr(self.queue, "data", None), np.ndarray):
             self._finished = cls.from_numpy(self.queue.data[1:2], requires_grad=False)

@@ -35,6 +35,10 @@ the definition and the numpy backend; csrc/sample_rows.hip evaluates it with the
 rewrites the logits at the ids of a request's own history in front of the draw.  `penalty_table` lays the parameters out,
 `penalize_logits` is the definition and the numpy backend; csrc/penalize.hip evaluates it in float32 bit for bit.
 
+`Tensor.logprob_rows` (per-token log-probabilities and the top-n alternatives) draws nothing either: behind the draw it scores
+the token against the logits the draw read.  `token_logprobs_rows` is the definition, in float64, and the numpy backend;
+csrc/logprob.hip evaluates it in float32 with the sum of exponentials held as integers.
+
     manual_seed(seed)        seed every backend's generator, draws back to 0
     get_state(backend)       (seed, draws) of "cpu" or "hip"
 """
@@ -423,6 +427,105 @@ def penalize_logits(logits, table, index, prompts, prompt_len, out, out_len, eos
         if eos is not None and g < min_new:
             y[r, int(eos)] = -np.inf
     return y, bad
+
+
+LOGPROB_MAX_TOP = 8                                      # n_max: the alternatives a thread of csrc/logprob.hip keeps in registers
+LOGPROB_LDS_COLS = 36864                                 # rows of up to this many floats are staged in LDS by csrc/logprob.hip
+
+
+def logprob_want(logprobs, n: int) -> np.ndarray:
+    """`want` (n,) int32 of `Tensor.logprob_rows` from what `serve(logprobs=)` takes: an int 0 .. 8 for every request, or one entry
+    per request - None or -1: no log-probabilities for it, 0: the chosen token's only, k in 1 .. 8: also the k most likely ids."""
+    entries = [logprobs] * n if logprobs is None or np.ndim(logprobs) == 0 else list(logprobs)
+    if len(entries) != n:
+        raise ValueError("logprobs: an int or one entry per request (%d), got %d" % (n, len(entries)))
+    want = np.zeros(n, np.int32)
+    for i, k in enumerate(entries):
+        k = -1 if k is None else k
+        if int(k) != k or not -1 <= int(k) <= LOGPROB_MAX_TOP:
+            raise ValueError("logprobs: every entry is None, -1 or an int in 0 .. %d (got %r)" % (LOGPROB_MAX_TOP, k))
+        want[i] = int(k)
+    return want
+
+
+def check_logprob_operands(logits, token, want, index, counter, logprob, top_ids, top_logprob):
+    """the validated (rows, V, N, G, n_max) of a `logprob_rows` call; the operands are tensors of either backend (shapes and dtypes
+    only)"""
+    shape, i32, f32 = tuple(logits.shape), np.dtype(np.int32), np.dtype(np.float32)
+    if not np.issubdtype(np.dtype(logits.dtype), np.floating):
+        raise ValueError("logprob_rows: the logits must be floating point (got %s)" % np.dtype(logits.dtype))
+    if not (len(shape) == 2 or (len(shape) == 3 and shape[1] == 1)) or shape[-1] < 1:
+        raise ValueError("logprob_rows: the logits are (rows, V) or (rows, 1, V) with V >= 1 (got %s)" % (shape,))
+    for name, t in (("token", token), ("want", want), ("index", index), ("counter", counter), ("top_ids", top_ids)):
+        if np.dtype(t.dtype) != i32:
+            raise ValueError("logprob_rows: %s must be int32 (got %s)" % (name, np.dtype(t.dtype)))
+    for name, t in (("logprob", logprob), ("top_logprob", top_logprob)):
+        if np.dtype(t.dtype) != f32:
+            raise ValueError("logprob_rows: %s must be float32 (got %s)" % (name, np.dtype(t.dtype)))
+    rows = shape[0]
+    if tuple(token.shape) not in ((rows,), (rows, 1)) or tuple(index.shape) != (rows,):
+        raise ValueError("logprob_rows: token is (rows,) or (rows, 1) and index (rows,) with rows = %d (got %s and %s)" % (
+            rows, tuple(token.shape), tuple(index.shape)))
+    if len(want.shape) != 1 or want.shape[0] < 1 or tuple(counter.shape) != tuple(want.shape):
+        raise ValueError("logprob_rows: want and counter are (N,) with N >= 1 (got %s and %s)" % (tuple(want.shape), tuple(counter.shape)))
+    N = want.shape[0]
+    if len(logprob.shape) != 2 or logprob.shape[0] != N or logprob.shape[1] < 1 or len(top_ids.shape) != 3 or tuple(top_ids.shape[:2]) != tuple(logprob.shape) or \
+            not 1 <= top_ids.shape[2] <= LOGPROB_MAX_TOP or tuple(top_logprob.shape) != tuple(top_ids.shape):
+        raise ValueError("logprob_rows: logprob (N, G), top_ids and top_logprob (N, G, n) with N = %d, G >= 1 and n in 1 .. %d (got %s, %s and %s)" % (
+            N, LOGPROB_MAX_TOP, tuple(logprob.shape), tuple(top_ids.shape), tuple(top_logprob.shape)))
+    return rows, shape[-1], N, logprob.shape[1], top_ids.shape[2]
+
+
+def token_logprobs_rows(logits, token, want, index, counter, logprob, top_ids, top_logprob):
+    """The definition of `Tensor.logprob_rows`, in float64: writes `logprob` (N, G), `top_ids` (N, G, n_max) and `top_logprob`
+    (N, G, n_max) IN PLACE (numpy arrays; float32 in a pool, any float type here) and returns bad (rows,) bool.  logits (rows, V)
+    float32 or float64 - the logits the draw reads: behind `penalize_rows`, in front of temperature, top-k and top-p; token (rows,)
+    the id just drawn; want (N,) per request: -1 = nothing, 0 = the chosen token's log-probability only, k in 1 .. n_max <= 8 =
+    also the k most likely ids; index (rows,): row r belongs to request i = index[r], -1 = a free row; counter (N,): the column
+    g = counter[i].  Per row, in this order:
+      1. i < 0 or (i < N and want[i] == -1): nothing is written and the row's logits are not read (they may hold NaN);
+      2. the row is BAD if i >= N, g < 0 or g >= G, want[i] is outside -1 .. n_max, or the token is outside 0 .. V - 1: nothing
+         is written and bad[r] is set; the other rows are computed;
+      3. with m = max x and L = m + log(sum_j exp(x_j - m)): logprob[i, g] = x_token - L, and for k = want[i], k' = min(k, V):
+         top_ids[i, g, :k'] = np.argsort(-x, kind="stable")[:k'] - descending value, equal values (-0.0 == +0.0) to the lower
+         index - and top_logprob[i, g, :k'] their x_j - L; the entries k' .. n_max - 1 keep what they hold.  A -inf logit has the
+         log-probability -inf;
+      4. a DEGENERATE row - a NaN in it, or m infinite - writes NaN to logprob[i, g], -1 to top_ids[i, g, :k] and NaN to
+         top_logprob[i, g, :k].
+    The fills a pool starts from: +0.0 in logprob and top_logprob, -1 in top_ids."""
+    x = np.asarray(logits)
+    token, index, want, counter = (np.asarray(a, np.int64).reshape(-1) for a in (token, index, want, counter))
+    if x.ndim != 2 or x.shape[1] < 1 or token.shape != (x.shape[0],) or index.shape != (x.shape[0],) or want.size < 1 or counter.shape != want.shape or \
+            logprob.ndim != 2 or logprob.shape[0] != want.size or top_ids.ndim != 3 or top_ids.shape[:2] != logprob.shape or top_logprob.shape != top_ids.shape or \
+            not 1 <= top_ids.shape[2] <= LOGPROB_MAX_TOP:
+        raise ValueError("token_logprobs_rows: logits (rows, V), token (rows,), want (N,), index (rows,), counter (N,), logprob (N, G), top_ids and "
+                         "top_logprob (N, G, n <= %d), got %s" % (LOGPROB_MAX_TOP, [np.shape(a) for a in (x, token, want, index, counter, logprob, top_ids, top_logprob)]))
+    (rows, V), N, G, n_max = x.shape, want.size, logprob.shape[1], top_ids.shape[2]
+    bad = np.zeros(rows, bool)
+    for r in range(rows):
+        i = int(index[r])
+        if i < 0:
+            continue
+        if i >= N:
+            bad[r] = True
+            continue
+        k, g, t = int(want[i]), int(counter[i]), int(token[r])
+        if k == -1:
+            continue
+        if not (0 <= k <= n_max and 0 <= g < G and 0 <= t < V):
+            bad[r] = True
+            continue
+        row = x[r].astype(np.float64)
+        m = row.max()                                    # (a NaN in the row makes it NaN)
+        if not np.isfinite(m):
+            logprob[i, g], top_ids[i, g, :k], top_logprob[i, g, :k] = np.nan, -1, np.nan
+            continue
+        with np.errstate(divide="ignore"):
+            L = m + np.log(np.exp(row - m).sum())
+        logprob[i, g] = row[t] - L
+        best = np.argsort(-row, kind="stable")[:min(k, V)]
+        top_ids[i, g, :best.size], top_logprob[i, g, :best.size] = best, row[best] - L
+    return bad
 
 
 def check_probability(p) -> float:
