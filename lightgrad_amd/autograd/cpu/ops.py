@@ -544,66 +544,90 @@ def _serve_commit(nxt, prompts, prompt_len, budget, out, out_len, queue, req, po
     b, m, N = _check_serve_commit(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last, capacity, eos)
     arrays = [t.data for t in (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last)]
     assert not any(np.shares_memory(x, y) for i, x in enumerate(arrays) for y in arrays[i + 1:]), "serve_commit: two operands overlap"
-    new, P, G = nxt.data.reshape(b), prompts.shape[1], out.shape[1]
     eos, capacity = (-1 if eos is None else int(eos)), int(capacity)
     bad = []
     for s in range(b):
-        r, t, n, row, fault = int(req.data[s]), 0, 0, (), False
-        if r >= 0:
-            t = int(pos.data[s]) + int(count.data[s])
-            if r >= N or t < 0 or t > capacity:
-                fault = True
-            elif t < int(prompt_len.data[r]):
-                n = np.minimum(m, int(prompt_len.data[r]) - t).item()
-                fault = t + n > P
-                row = () if fault else prompts.data[r, t:t + n]
-            else:
-                g = int(out_len.data[r])
-                if g < 0 or g >= G:
-                    fault = True
-                else:
-                    out.data[r, g], out_len.data[r] = new[s], g + 1
-                    if (eos >= 0 and int(new[s]) == eos) or g + 1 == int(budget.data[r]):
-                        queue.data[1] += 1
-                        r = -1
-                    else:
-                        n, row = 1, new[s:s + 1]
-        if not fault and r < 0:
-            t = 0
-            if 0 <= int(queue.data[0]) < N:
-                r = int(queue.data[0])
-                queue.data[0] += 1
-                n = np.minimum(m, int(prompt_len.data[r])).item()
-                fault = n < 0 or n > P
-                row = () if fault else prompts.data[r, :n]
-        if fault or t + n > capacity:
-            count.data[s] = 0
+        r, t, n, row, tok, fault, _ = _serve_slot_request(s, m, capacity, eos, nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count)
+        r, t, n, row, fault = _serve_slot_admit(m, r, t, n, row, fault, prompts, prompt_len, queue)
+        if not _serve_slot_write(s, m, capacity, r, t, n, row, tok, fault, prompts, req, pos, count, ids, position_ids, last):
             bad.append(s)
-            continue
-        req.data[s], pos.data[s], count.data[s] = r, t, n
-        ids.data[s, :n], ids.data[s, n:] = row, 0
-        position_ids.data[s, :n], position_ids.data[s, n:] = t + np.arange(n), 0
-        last.data[s] = s * m + (n - 1 if n > 0 else 0)
     if bad:
         raise IndexError("serve_commit: slot %d (of %d that did) would leave the cache, its prompt or its row of out" % (bad[0], len(bad)))
 
 
-def _check_serve_commit(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last, capacity, eos):
-    """the operand shapes and dtypes of `serve_commit`, on any backend; returns (slots b, tokens per slot m, requests N)"""
+def _serve_slot_request(s, m, capacity, eos, nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count):
+    """step 1 of `serve_commit` for slot s, once for the three commits (`m`: the most tokens a slot takes in a step).  Returns
+    (r, t, n, row, tok, fault, finished): the slot's request (-1: none), the position of its first token, how many tokens, where
+    they come from - the prompt of request `row`, or (row = -1) the one token `tok` just drawn -, whether the slot would leave its
+    bounds, whether its request has just finished"""
+    (N, P), G = prompts.shape, out.shape[1]
+    r, t, n, row, tok, fault, finished = int(req.data[s]), 0, 0, -1, 0, False, False
+    if r >= 0:
+        t = int(pos.data[s]) + int(count.data[s])
+        if r >= N or t < 0 or t > capacity:
+            fault = True
+        elif t < int(prompt_len.data[r]):
+            n, row = np.minimum(m, int(prompt_len.data[r]) - t).item(), r
+            fault = t + n > P
+        else:
+            g = int(out_len.data[r])
+            if g < 0 or g >= G:
+                fault = True
+            else:
+                tok = nxt.data.reshape(-1)[s]
+                out.data[r, g], out_len.data[r] = tok, g + 1
+                if (eos >= 0 and int(tok) == eos) or g + 1 == int(budget.data[r]):
+                    queue.data[1] += 1
+                    r, finished = -1, True
+                else:
+                    n = 1
+    return r, t, n, row, tok, fault, finished
+
+
+def _serve_slot_admit(m, r, t, n, row, fault, prompts, prompt_len, queue):
+    """steps 2 and 3 of `serve_commit`: a free slot takes the next waiting request, if there is one; returns (r, t, n, row, fault)"""
+    if not fault and r < 0:
+        t = 0
+        if 0 <= int(queue.data[0]) < prompts.shape[0]:
+            r = row = int(queue.data[0])
+            queue.data[0] += 1
+            n = np.minimum(m, int(prompt_len.data[r])).item()
+            fault = n < 0 or n > prompts.shape[1]
+    return r, t, n, row, fault
+
+
+def _serve_slot_write(s, m, capacity, r, t, n, row, tok, fault, prompts, req, pos, count, ids, position_ids, last):
+    """step 4 of `serve_commit` for slot s of a step of (b, m) rows; False, and count[s] = 0 alone, for a slot that would leave its
+    bounds"""
+    if fault or t + n > capacity:
+        count.data[s] = 0
+        return False
+    req.data[s], pos.data[s], count.data[s] = r, t, n
+    ids.data[s, :n], ids.data[s, n:] = (prompts.data[row, t:t + n] if row >= 0 else tok), 0
+    position_ids.data[s, :n], position_ids.data[s, n:] = t + np.arange(n), 0
+    last.data[s] = s * m + (n - 1 if n > 0 else 0)
+    return True
+
+
+def _check_serve_commit(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last, capacity, eos,
+                        name="serve_commit", cu=None):
+    """the operand shapes and dtypes of `serve_commit`, on any backend; returns (slots b, tokens per slot m, requests N).  With `cu`
+    those of `serve_commit_packed`: ids / position_ids are (1, T) with T >= b, cu is (b + 1,), and T is returned for m"""
+    packed = cu is not None
     b = req.shape[0] if len(req.shape) == 1 else -1
-    m = ids.shape[1] if len(ids.shape) == 2 else -1
+    m = ids.shape[1] if len(ids.shape) == 2 and (ids.shape[0] == 1 or not packed) else -1
     N = prompts.shape[0] if len(prompts.shape) == 2 else -1
     i32 = np.dtype(np.int32)
-    shapes = [tuple(t.shape) for t in (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last)]
-    assert 1 <= b <= 1024 and m >= 1 and N >= 1 and prompts.shape[1] >= 1 and shapes[0] in ((b,), (b, 1)) and shapes[2] == shapes[3] == shapes[5] == (N,) \
-        and len(out.shape) == 2 and out.shape[0] == N and out.shape[1] >= 1 and shapes[6] == (2,) and shapes[8] == shapes[9] == shapes[12] == (b,) \
-        and shapes[10] == shapes[11] == (b, m), \
-        "serve_commit: nxt (b,) or (b, 1), prompts (N, P), prompt_len / budget / out_len (N,), out (N, G), queue (2,), req / pos / count / last (b,) " \
-        "with 1 <= b <= 1024, ids / position_ids (b, m) - got %s" % (shapes,)
-    assert all(np.dtype(t.dtype) == i32 for t in (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last)), \
-        "serve_commit: every operand is int32"
-    assert eos is None or int(eos) == eos, "serve_commit: eos is an int or None"
-    assert int(capacity) == capacity and 1 <= capacity < 2 ** 31, "serve_commit: capacity is an int >= 1"
+    operands = (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last) + ((cu,) if packed else ())
+    shapes = [tuple(t.shape) for t in operands]
+    assert 1 <= b <= 1024 and m >= (b if packed else 1) and N >= 1 and prompts.shape[1] >= 1 and shapes[0] in ((b,), (b, 1)) \
+        and shapes[2] == shapes[3] == shapes[5] == (N,) and len(out.shape) == 2 and out.shape[0] == N and out.shape[1] >= 1 and shapes[6] == (2,) \
+        and shapes[8] == shapes[9] == shapes[12] == (b,) and shapes[10] == shapes[11] == ((1, m) if packed else (b, m)) and shapes[13:] in ([], [(b + 1,)]), \
+        "%s: nxt (b,) or (b, 1), prompts (N, P), prompt_len / budget / out_len (N,), out (N, G), queue (2,), req / pos / count / last (b,) " \
+        "with 1 <= b <= 1024, ids / position_ids %s - got %s" % (name, "(1, T) with T >= b, cu (b + 1,)" if packed else "(b, m)", shapes)
+    assert all(np.dtype(t.dtype) == i32 for t in operands), "%s: every operand is int32" % name
+    assert eos is None or int(eos) == eos, "%s: eos is an int or None" % name
+    assert int(capacity) == capacity and 1 <= capacity < 2 ** 31, "%s: capacity is an int >= 1" % name
     return b, m, N
 
 
@@ -631,44 +655,17 @@ def _serve_commit_packed(nxt, prompts, prompt_len, budget, out, out_len, queue, 
                                          chunk, eos)
     arrays = [t.data for t in (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, cu, ids, position_ids, last)]
     assert not any(np.shares_memory(x, y) for i, x in enumerate(arrays) for y in arrays[i + 1:]), "serve_commit_packed: two operands overlap"
-    new, P, G = nxt.data.reshape(b), prompts.shape[1], out.shape[1]
     eos, capacity, chunk = (-1 if eos is None else int(eos)), int(capacity), int(chunk)
     slots, bad = [], []
     for s in range(b):
-        r, t, n, row, fault, decoding = int(req.data[s]), 0, 0, (), False, False
-        if r >= 0:
-            t = int(pos.data[s]) + int(count.data[s])
-            if r >= N or t < 0 or t > capacity:
-                fault = True
-            elif t < int(prompt_len.data[r]):
-                n = np.minimum(chunk, int(prompt_len.data[r]) - t).item()
-                fault = t + n > P
-                row = () if fault else prompts.data[r, t:t + n]
-            else:
-                g = int(out_len.data[r])
-                if g < 0 or g >= G:
-                    fault = True
-                else:
-                    out.data[r, g], out_len.data[r] = new[s], g + 1
-                    if (eos >= 0 and int(new[s]) == eos) or g + 1 == int(budget.data[r]):
-                        queue.data[1] += 1
-                        r = -1
-                    else:
-                        n, row, decoding = 1, new[s:s + 1], True
-        if not fault and r < 0:
-            t = 0
-            if 0 <= int(queue.data[0]) < N:
-                r = int(queue.data[0])
-                queue.data[0] += 1
-                n = np.minimum(chunk, int(prompt_len.data[r])).item()
-                fault = n < 0 or n > P
-                row = () if fault else prompts.data[r, :n]
+        r, t, n, row, tok, fault, _ = _serve_slot_request(s, chunk, capacity, eos, nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count)
+        r, t, n, row, fault = _serve_slot_admit(chunk, r, t, n, row, fault, prompts, prompt_len, queue)
         if fault or t + n > capacity:
             bad.append(s)
             slots.append(None)
         else:
-            slots.append((r, t, n, row, decoding))
-    left = T - len([x for x in slots if x is not None and x[4]])
+            slots.append((r, t, n, row, tok))
+    left = T - len([x for x in slots if x is not None and x[3] < 0 and x[2] == 1])
     ids.data[...], position_ids.data[...] = 0, 0
     start = 0
     for s, x in enumerate(slots):
@@ -676,12 +673,12 @@ def _serve_commit_packed(nxt, prompts, prompt_len, budget, out, out_len, queue, 
         if x is None:
             count.data[s] = 0
             continue
-        r, t, n, row, decoding = x
-        if not decoding:
+        r, t, n, row, tok = x
+        if row >= 0:                # (a decoding slot: row < 0 and n = 1; an idle one: n = 0)
             n = np.minimum(n, left).item()
             left -= n
         req.data[s], pos.data[s], count.data[s] = r, t, n
-        ids.data[0, start:start + n] = row[:n]
+        ids.data[0, start:start + n] = prompts.data[row, t:t + n] if row >= 0 else tok
         position_ids.data[0, start:start + n] = t + np.arange(n)
         last.data[s] = np.minimum(start + (n - 1 if n > 0 else 0), T - 1)
         start += n
@@ -692,20 +689,8 @@ def _serve_commit_packed(nxt, prompts, prompt_len, budget, out, out_len, queue, 
 
 def _check_serve_commit_packed(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, cu, ids, position_ids, last, capacity, chunk, eos):
     """the operand shapes and dtypes of `serve_commit_packed`, on any backend; returns (slots b, token rows T, requests N)"""
-    b = req.shape[0] if len(req.shape) == 1 else -1
-    T = ids.shape[1] if len(ids.shape) == 2 and ids.shape[0] == 1 else -1
-    N = prompts.shape[0] if len(prompts.shape) == 2 else -1
-    i32 = np.dtype(np.int32)
-    operands = (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, cu, ids, position_ids, last)
-    shapes = [tuple(t.shape) for t in operands]
-    assert 1 <= b <= 1024 and T >= b and N >= 1 and prompts.shape[1] >= 1 and shapes[0] in ((b,), (b, 1)) and shapes[2] == shapes[3] == shapes[5] == (N,) \
-        and len(out.shape) == 2 and out.shape[0] == N and out.shape[1] >= 1 and shapes[6] == (2,) and shapes[8] == shapes[9] == shapes[13] == (b,) \
-        and shapes[10] == (b + 1,) and shapes[11] == shapes[12] == (1, T), \
-        "serve_commit_packed: nxt (b,) or (b, 1), prompts (N, P), prompt_len / budget / out_len (N,), out (N, G), queue (2,), req / pos / count / last " \
-        "(b,) with 1 <= b <= 1024, cu (b + 1,), ids / position_ids (1, T) with T >= b - got %s" % (shapes,)
-    assert all(np.dtype(t.dtype) == i32 for t in operands), "serve_commit_packed: every operand is int32"
-    assert eos is None or int(eos) == eos, "serve_commit_packed: eos is an int or None"
-    assert int(capacity) == capacity and 1 <= capacity < 2 ** 31, "serve_commit_packed: capacity is an int >= 1"
+    b, T, N = _check_serve_commit(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last, capacity, eos,
+                                  name="serve_commit_packed", cu=cu)
     assert int(chunk) == chunk and 1 <= chunk and b * chunk < 2 ** 31, "serve_commit_packed: chunk is an int >= 1"
     return b, T, N
 
@@ -741,45 +726,24 @@ def _serve_commit_paged(nxt, prompts, prompt_len, budget, out, out_len, queue, r
     MB, NB, B, F = _check_paged_state("serve_commit_paged", b, block_table, held, free, block_size, prefix_blocks)
     arrays = [t.data for t in (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last, block_table, held, free)]
     assert not any(np.shares_memory(x, y) for i, x in enumerate(arrays) for y in arrays[i + 1:]), "serve_commit_paged: two operands overlap"
-    new, P, G = nxt.data.reshape(b), prompts.shape[1], out.shape[1]
+    P = prompts.shape[1]
     eos, capacity = (-1 if eos is None else int(eos)), MB * B
     table, stack = block_table.data, free.data
     stack_ok = 0 <= int(stack[0]) <= NB
-    state = []                      # per slot: [r, t, n, row, fault, finished]
-    for s in range(b):
-        r, t, n, row, fault, finished = int(req.data[s]), 0, 0, (), False, False
-        if r >= 0:
-            t = int(pos.data[s]) + int(count.data[s])
-            if r >= N or t < 0 or t > capacity:
-                fault = True
-            elif t < int(prompt_len.data[r]):
-                n = np.minimum(m, int(prompt_len.data[r]) - t).item()
-                fault = t + n > P
-                row = () if fault else prompts.data[r, t:t + n]
-            else:
-                g = int(out_len.data[r])
-                if g < 0 or g >= G:
-                    fault = True
-                else:
-                    out.data[r, g], out_len.data[r] = new[s], g + 1
-                    if (eos >= 0 and int(new[s]) == eos) or g + 1 == int(budget.data[r]):
-                        queue.data[1] += 1
-                        r, finished = -1, True
-                    else:
-                        n, row = 1, new[s:s + 1]
-        state.append([r, t, n, row, fault, finished])
+    # per slot: [r, t, n, row, tok, fault, finished]
+    state = [list(_serve_slot_request(s, m, capacity, eos, nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count)) for s in range(b)]
     # the release: which slots may push is settled first (the bounds of each, then the room for all of them together)
     pushes = {}
     for s in range(b):
-        if state[s][5]:
+        if state[s][6]:
             h = int(held.data[s])
             if stack_ok and 0 <= h <= MB and all(0 <= int(e) < NB for e in table[s, F:h]):
                 pushes[s] = [int(e) for e in table[s, F:h]]
             else:
-                state[s][4] = True
+                state[s][5] = True
     if stack_ok and int(stack[0]) + len([e for p in pushes.values() for e in p]) > NB:
         for s in pushes:
-            state[s][4] = True
+            state[s][5] = True
         pushes = {}
     for s in sorted(pushes):
         for e in pushes[s]:
@@ -789,7 +753,7 @@ def _serve_commit_paged(nxt, prompts, prompt_len, budget, out, out_len, queue, r
     # the admission
     stopped = False
     for s in range(b):
-        r, t, n, row, fault, _ = state[s]
+        r, t, n, row, _, fault, _ = state[s]
         if fault or r >= 0:
             continue
         t = 0
@@ -808,20 +772,10 @@ def _serve_commit_paged(nxt, prompts, prompt_len, budget, out, out_len, queue, r
                     table[s, F + i] = stack[stack[0]]
                     stack[0] -= 1
                 table[s, :F], held.data[s] = np.arange(F), F + need
-                r, t, n = k, F * B, n0
-                row = prompts.data[r, t:t + n]
-        state[s][:5] = r, t, n, row, fault
-    bad = []
-    for s in range(b):
-        r, t, n, row, fault, _ = state[s]
-        if fault or t + n > capacity:
-            count.data[s] = 0
-            bad.append(s)
-            continue
-        req.data[s], pos.data[s], count.data[s] = r, t, n
-        ids.data[s, :n], ids.data[s, n:] = row, 0
-        position_ids.data[s, :n], position_ids.data[s, n:] = t + np.arange(n), 0
-        last.data[s] = s * m + (n - 1 if n > 0 else 0)
+                r, t, n, row = k, F * B, n0, k
+        state[s][:4], state[s][5] = (r, t, n, row), fault
+    bad = [s for s, (r, t, n, row, tok, fault, _) in enumerate(state)
+           if not _serve_slot_write(s, m, capacity, r, t, n, row, tok, fault, prompts, req, pos, count, ids, position_ids, last)]
     if bad:
         raise IndexError("serve_commit_paged: slot %d (of %d that did) would leave the cache, its prompt, its row of out or the block pool" % (bad[0], len(bad)))
 

@@ -774,6 +774,32 @@ HipTensor.decode_commit = decode_commit
 """ The slot bookkeeping of a serving step in one launch (csrc/serve.hip) """
 
 
+def _serve_commit_operands(name, b, N, reads, written, dense):
+    """the operands of a commit launch as it addresses them.  reads = (nxt, prompts, prompt_len, budget): what is only read may be
+    copied once into a layout the launch takes; written = (out, out_len, queue, req, pos, count, ...): the launch writes these
+    where they lie, so a layout it cannot address is an error, never a copy - the rows of out contiguous at any pitch, every other
+    one dense (`dense` names them for the message).  No two operands share bytes.  Returns the leading arguments all three
+    lg_serve_commit*_i32 entries take, nxt .. count."""
+    nxt, prompts, prompt_len, budget = reads
+    out, out_len, queue, req, pos, count = written[:6]
+    P, G = prompts._shape[1], out._shape[1]
+    if b > 1 and nxt._strides[0] < 1:
+        nxt = nxt.contiguous()
+    if (P > 1 and prompts._strides[1] != 1) or (N > 1 and prompts._strides[0] < P):
+        prompts = prompts.contiguous()
+    prompt_len, budget = (t if N == 1 or t._strides[0] == 1 else t.contiguous() for t in (prompt_len, budget))
+    assert all(t.is_contiguous() for t in written[1:]) and (G == 1 or out._strides[1] == 1) and (N == 1 or out._strides[0] >= G), \
+        "%s: %s must be dense and the rows of out contiguous" % (name, dense)
+    operands = (nxt, prompts, prompt_len, budget) + written
+    for i, x in enumerate(operands):
+        for y in operands[i + 1:]:
+            assert not _shares_bytes(x, y), "%s: two operands overlap" % name
+    for x in written:
+        flush_lazy_readers(x)
+    return (nxt.ptr, nxt._strides[0] if b > 1 else 1, prompts.ptr, prompts._strides[0] if N > 1 else P, P, prompt_len.ptr, budget.ptr,
+            out.ptr, out._strides[0] if N > 1 else G, G, out_len.ptr, queue.ptr, N, req.ptr, pos.ptr, count.ptr)
+
+
 def serve_commit(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last, capacity, eos=None):
     """ nxt.serve_commit(prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last, capacity,
     eos=None): what `CpuTensor.serve_commit` defines - a finished slot freed, the next waiting request admitted to it, the next
@@ -786,26 +812,8 @@ def serve_commit(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos
     operands = (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last)
     assert all(isinstance(t, HipTensor) for t in operands), "%s: every operand is a HipTensor" % name
     b, m, N = _check_serve_commit(*operands, capacity, eos)
-    if b > 1 and nxt._strides[0] < 1:
-        nxt = nxt.contiguous()
-    # what is only read may be copied once into a layout the launch addresses
-    if (prompts._shape[1] > 1 and prompts._strides[1] != 1) or (N > 1 and prompts._strides[0] < prompts._shape[1]):
-        prompts = prompts.contiguous()
-    prompt_len, budget = (t if N == 1 or t._strides[0] == 1 else t.contiguous() for t in (prompt_len, budget))
-    # the launch writes these where they lie: a layout it cannot address is an error, never a copy
-    assert all(t.is_contiguous() for t in (out_len, queue, req, pos, count, last, ids, position_ids)) and \
-        (out._shape[1] == 1 or out._strides[1] == 1) and (N == 1 or out._strides[0] >= out._shape[1]), \
-        "%s: out_len, queue, req, pos, count, last, ids and position_ids must be dense and the rows of out contiguous" % name
-    operands = (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last)
-    for i, x in enumerate(operands):
-        for y in operands[i + 1:]:
-            assert not _shares_bytes(x, y), "%s: two operands overlap" % name
-    for x in operands[4:]:
-        flush_lazy_readers(x)
-    P, G = prompts._shape[1], out._shape[1]
-    _l.check(_l.lib().lg_serve_commit_i32(nxt.ptr, nxt._strides[0] if b > 1 else 1, prompts.ptr, prompts._strides[0] if N > 1 else P, P, prompt_len.ptr,
-                                          budget.ptr, out.ptr, out._strides[0] if N > 1 else G, G, out_len.ptr, queue.ptr, N, req.ptr, pos.ptr,
-                                          count.ptr, ids.ptr, position_ids.ptr, last.ptr, b, m, int(capacity), -1 if eos is None else int(eos)))
+    leading = _serve_commit_operands(name, b, N, operands[:4], operands[4:], "out_len, queue, req, pos, count, last, ids and position_ids")
+    _l.check(_l.lib().lg_serve_commit_i32(*leading, ids.ptr, position_ids.ptr, last.ptr, b, m, int(capacity), -1 if eos is None else int(eos)))
 
 
 HipTensor.serve_commit = serve_commit
@@ -909,27 +917,9 @@ def serve_commit_packed(nxt, prompts, prompt_len, budget, out, out_len, queue, r
     operands = (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, cu, ids, position_ids, last)
     assert all(isinstance(t, HipTensor) for t in operands), "%s: every operand is a HipTensor" % name
     b, T, N = _check_serve_commit_packed(*operands, capacity, chunk, eos)
-    if b > 1 and nxt._strides[0] < 1:
-        nxt = nxt.contiguous()
-    # what is only read may be copied once into a layout the launch addresses
-    if (prompts._shape[1] > 1 and prompts._strides[1] != 1) or (N > 1 and prompts._strides[0] < prompts._shape[1]):
-        prompts = prompts.contiguous()
-    prompt_len, budget = (t if N == 1 or t._strides[0] == 1 else t.contiguous() for t in (prompt_len, budget))
-    # the launch writes these where they lie: a layout it cannot address is an error, never a copy
-    assert all(t.is_contiguous() for t in (out_len, queue, req, pos, count, cu, last, ids, position_ids)) and \
-        (out._shape[1] == 1 or out._strides[1] == 1) and (N == 1 or out._strides[0] >= out._shape[1]), \
-        "%s: out_len, queue, req, pos, count, cu, last, ids and position_ids must be dense and the rows of out contiguous" % name
-    operands = (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, cu, ids, position_ids, last)
-    for i, x in enumerate(operands):
-        for y in operands[i + 1:]:
-            assert not _shares_bytes(x, y), "%s: two operands overlap" % name
-    for x in operands[4:]:
-        flush_lazy_readers(x)
-    P, G = prompts._shape[1], out._shape[1]
-    _l.check(_l.lib().lg_serve_commit_packed_i32(nxt.ptr, nxt._strides[0] if b > 1 else 1, prompts.ptr, prompts._strides[0] if N > 1 else P, P,
-                                                 prompt_len.ptr, budget.ptr, out.ptr, out._strides[0] if N > 1 else G, G, out_len.ptr, queue.ptr, N,
-                                                 req.ptr, pos.ptr, count.ptr, cu.ptr, ids.ptr, position_ids.ptr, last.ptr, b, T, int(chunk),
-                                                 int(capacity), -1 if eos is None else int(eos)))
+    leading = _serve_commit_operands(name, b, N, operands[:4], operands[4:], "out_len, queue, req, pos, count, cu, last, ids and position_ids")
+    _l.check(_l.lib().lg_serve_commit_packed_i32(*leading, cu.ptr, ids.ptr, position_ids.ptr, last.ptr, b, T, int(chunk), int(capacity),
+                                                 -1 if eos is None else int(eos)))
 
 
 HipTensor.serve_commit_packed = serve_commit_packed
@@ -951,26 +941,9 @@ def serve_commit_paged(nxt, prompts, prompt_len, budget, out, out_len, queue, re
     assert all(isinstance(t, HipTensor) for t in operands), "%s: every operand is a HipTensor" % name
     b, m, N = _check_serve_commit(*operands[:13], 1, eos)
     MB, NB, B, F = _check_paged_state(name, b, block_table, held, free, block_size, prefix_blocks)
-    if b > 1 and nxt._strides[0] < 1:
-        nxt = nxt.contiguous()
-    # what is only read may be copied once into a layout the launch addresses
-    if (prompts._shape[1] > 1 and prompts._strides[1] != 1) or (N > 1 and prompts._strides[0] < prompts._shape[1]):
-        prompts = prompts.contiguous()
-    prompt_len, budget = (t if N == 1 or t._strides[0] == 1 else t.contiguous() for t in (prompt_len, budget))
-    # the launch writes these where they lie: a layout it cannot address is an error, never a copy
-    assert all(t.is_contiguous() for t in (out_len, queue, req, pos, count, last, ids, position_ids, block_table, held, free)) and \
-        (out._shape[1] == 1 or out._strides[1] == 1) and (N == 1 or out._strides[0] >= out._shape[1]), \
-        "%s: out_len, queue, req, pos, count, last, ids, position_ids, block_table, held and free must be dense and the rows of out contiguous" % name
-    operands = (nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, ids, position_ids, last, block_table, held, free)
-    for i, x in enumerate(operands):
-        for y in operands[i + 1:]:
-            assert not _shares_bytes(x, y), "%s: two operands overlap" % name
-    for x in operands[4:]:
-        flush_lazy_readers(x)
-    P, G = prompts._shape[1], out._shape[1]
-    _l.check(_l.lib().lg_serve_commit_paged_i32(nxt.ptr, nxt._strides[0] if b > 1 else 1, prompts.ptr, prompts._strides[0] if N > 1 else P, P, prompt_len.ptr,
-                                                budget.ptr, out.ptr, out._strides[0] if N > 1 else G, G, out_len.ptr, queue.ptr, N, req.ptr, pos.ptr,
-                                                count.ptr, ids.ptr, position_ids.ptr, last.ptr, block_table.ptr, held.ptr, free.ptr, b, m, MB, NB,
+    leading = _serve_commit_operands(name, b, N, operands[:4], operands[4:],
+                                     "out_len, queue, req, pos, count, last, ids, position_ids, block_table, held and free")
+    _l.check(_l.lib().lg_serve_commit_paged_i32(*leading, ids.ptr, position_ids.ptr, last.ptr, block_table.ptr, held.ptr, free.ptr, b, m, MB, NB,
                                                 B.bit_length() - 1, F, -1 if eos is None else int(eos)))
 
 

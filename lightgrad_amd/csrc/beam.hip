@@ -347,12 +347,6 @@ __global__ __launch_bounds__(256) void beam_reorder(const ReorderArgs a) {
     }
 }
 
-// do the bytes [x, x + nx) and [y, y + ny) share an address?
-static bool beam_overlap(const void* x, int64_t nx, const void* y, int64_t ny) {
-    const char *a = static_cast<const char*>(x), *b = static_cast<const char*>(y);
-    return a < b + ny && b < a + nx;
-}
-
 template <int W>
 static void launch_beam_step(const BeamArgs& a, int64_t groups, int threads) {
     hipLaunchKernelGGL(beam_step<W>, dim3(unsigned(a.w), unsigned(groups)), dim3(threads), 0, rt().stream, a);
@@ -395,7 +389,7 @@ extern "C" int lg_beam_step_f32(const float* logits, int64_t logits_pitch, float
                                   rows * 4, rows * 4, 8};
         for (int i = 0; i < 8; ++i)
             for (int j = i + 1; j < 8; ++j)
-                LG_ARG(!beam_overlap(ptr[i], bytes[i], ptr[j], bytes[j]),
+                LG_ARG(!bytes_overlap(ptr[i], bytes[i], ptr[j], bytes[j]),
                        "%s: operands %d and %d (of logits, scores, parent, token, out_ids, pos, done, stats) overlap", name, i, j);
         for (int i = 1; i < 8; ++i) {
             const int rc = adam_epilogue_check_write(ptr[i], bytes[i]);
@@ -436,15 +430,15 @@ extern "C" int lg_beam_reorder_f32(float* const* tensors, int64_t n_tensors, int
            "%s: pitches %lld (a cache row, >= width = %lld) / %lld (a sequence, >= (capacity - 1) * ldc + width), multiples of 4", name, (long long)ldc,
            (long long)width, (long long)sbc);
     const int64_t span = ((rows - 1) * sbc + (capacity - 1) * ldc + width) * 4;
-    LG_ARG(!beam_overlap(parent, rows * 4, pos, rows * 4), "%s: parent and pos overlap", name);
+    LG_ARG(!bytes_overlap(parent, rows * 4, pos, rows * 4), "%s: parent and pos overlap", name);
     for (int64_t t = 0; t < n_tensors; ++t) {
         LG_ARG(tensors[t] && aligned16(tensors[t]), "%s: cache tensor %lld is NULL or not 16-byte aligned", name, (long long)t);
         // a thread reads and writes its chunk of one tensor only: a tensor that shares bytes with another, or with the words every
         // workgroup reads first, would make the result depend on the order of the workgroups
-        LG_ARG(!beam_overlap(parent, rows * 4, tensors[t], span) && !beam_overlap(pos, rows * 4, tensors[t], span),
+        LG_ARG(!bytes_overlap(parent, rows * 4, tensors[t], span) && !bytes_overlap(pos, rows * 4, tensors[t], span),
                "%s: parent / pos overlap cache tensor %lld", name, (long long)t);
         for (int64_t u = t + 1; u < n_tensors; ++u)
-            LG_ARG(!beam_overlap(tensors[t], span, tensors[u], span), "%s: cache tensors %lld and %lld overlap", name, (long long)t, (long long)u);
+            LG_ARG(!bytes_overlap(tensors[t], span, tensors[u], span), "%s: cache tensors %lld and %lld overlap", name, (long long)t, (long long)u);
         const int rc = adam_epilogue_check_write(tensors[t], span);
         if (rc != LG_OK) return rc;
     }

@@ -32,12 +32,6 @@ __global__ __launch_bounds__(256) void decode_commit(const int32_t* __restrict__
     if (eos_id >= 0 && id == eos_id) done[r] = 1;
 }
 
-// do the bytes [x, x + nx) and [y, y + ny) share an address?
-static bool bytes_overlap(const void* x, int64_t nx, const void* y, int64_t ny) {
-    const char *a = static_cast<const char*>(x), *b = static_cast<const char*>(y);
-    return a < b + ny && b < a + nx;
-}
-
 }  // namespace lg
 
 using namespace lg;

@@ -118,6 +118,12 @@ bool build_iter(int ndim, const int64_t* shape, const int64_t* const* strides, i
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// do the bytes [x, x + nx) and [y, y + ny) share an address?  (a NULL operand or an empty range shares none)
+inline bool bytes_overlap(const void* x, int64_t nx, const void* y, int64_t ny) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(x), b = reinterpret_cast<uintptr_t>(y);
+    return x != nullptr && y != nullptr && nx > 0 && ny > 0 && a < b + uintptr_t(ny) && b < a + uintptr_t(nx);
+}
+
 // grid size for a memory-bound kernel: ONE work item (one float4) per thread.  Measured on MI355X for
 // c = a + b over 512 MiB tensors (tools/stream_bench.hip): one float4 per thread over 131072 workgroups streams
 // 6.08 TB/s, a grid-stride loop over 2048 workgroups 5.06 TB/s, 4-8 float4 per thread 5.5-5.6 TB/s.  The

@@ -155,11 +155,6 @@ __global__ void __launch_bounds__(1024) logprob_rows_kernel(const float* __restr
     }
 }
 
-static bool logprob_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a_bytes > 0 && b_bytes > 0 && a0 < b0 + uintptr_t(b_bytes) && b0 < a0 + uintptr_t(a_bytes);
-}
-
 }  // namespace lg
 
 using namespace lg;
@@ -186,7 +181,7 @@ extern "C" int lg_logprob_rows_f32(const float* logits, int64_t rows, int64_t co
         LG_ARG((reinterpret_cast<uintptr_t>(words[a]) & 3u) == 0, "lg_logprob_rows_f32: %s is not aligned to 4 bytes", names[a]);
     for (int a = 5; a < 8; ++a)                          // what the launch writes shares no byte with anything else
         for (int b = 0; b < a; ++b)
-            LG_ARG(!logprob_overlap(words[a], bytes[a], words[b], bytes[b]), "lg_logprob_rows_f32: %s overlaps %s", names[a], names[b]);
+            LG_ARG(!bytes_overlap(words[a], bytes[a], words[b], bytes[b]), "lg_logprob_rows_f32: %s overlaps %s", names[a], names[b]);
     for (int a = 5; a < 8; ++a) { const int rc = adam_epilogue_check_write(words[a], bytes[a]); if (rc != LG_OK) return rc; }
     const SampleShape shape = sample_shape(cols);        // the scale of the integer weights and the threads, as the sampling launches choose them
     const bool lds_row = cols <= kLogprobMaxLdsCols;

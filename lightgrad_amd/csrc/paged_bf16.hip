@@ -27,12 +27,6 @@ static int launch_paged_bf16(const ExtendArgs& a, dim3 grid) {
     return LG_OK;
 }
 
-// do the bytes [x, x + nx) and [y, y + ny) share an address?
-static bool paged16_overlap(const void* x, int64_t nx, const void* y, int64_t ny) {
-    const char *a = static_cast<const char*>(x), *b = static_cast<const char*>(y);
-    return x != nullptr && y != nullptr && a < b + ny && b < a + nx;
-}
-
 }  // namespace lg
 
 using namespace lg;
@@ -76,9 +70,9 @@ extern "C" int lg_attention_extend_paged_bf16_f32(const float* q, int64_t ldq, i
                                   ((batch - 1) * sbv + (m - 1) * ldv + w) * 4, batch * 4, batch * 4, batch * max_blocks * 4};
         for (int i = 0; i < 4; ++i)
             for (int j = i + 1; j < 9; ++j)
-                LG_ARG(!paged16_overlap(ptr[i], bytes[i], ptr[j], bytes[j]), "%s: %s overlaps %s: the launch writes the one while other workgroups use the other",
+                LG_ARG(!bytes_overlap(ptr[i], bytes[i], ptr[j], bytes[j]), "%s: %s overlaps %s: the launch writes the one while other workgroups use the other",
                        name, what[i], what[j]);
-        LG_ARG(!paged16_overlap(pos, bytes[6], count, bytes[7]), "%s: count overlaps pos", name);
+        LG_ARG(!bytes_overlap(pos, bytes[6], count, bytes[7]), "%s: count overlaps pos", name);
     }
     {
         const int64_t orows[3] = {batch, m, w}, row_strides[3] = {sbo, ldo, 1};

@@ -100,11 +100,6 @@ __global__ void __launch_bounds__(kPenalizeThreads) penalize_rows_kernel(float* 
     }
 }
 
-static bool penalize_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a_bytes > 0 && b_bytes > 0 && a0 < b0 + uintptr_t(b_bytes) && b0 < a0 + uintptr_t(a_bytes);
-}
-
 }  // namespace lg
 
 using namespace lg;
@@ -134,7 +129,7 @@ extern "C" int lg_penalize_rows_f32(float* logits, int64_t rows, int64_t cols, i
     const void* const words[6] = {table, index, prompts, prompt_len, out, out_len};
     const int64_t bytes[6] = {n * 16, rows * 4, ((n - 1) * prompt_pitch + P) * 4, n * 4, ((n - 1) * out_pitch + G) * 4, n * 4};
     for (int k = 0; k < 6; ++k)
-        LG_ARG(!penalize_overlap(logits, logit_bytes, words[k], bytes[k]),
+        LG_ARG(!bytes_overlap(logits, logit_bytes, words[k], bytes[k]),
                "lg_penalize_rows_f32: the logits overlap operand %d (of table, index, prompts, prompt_len, out, out_len)", k);
     { const int rc = adam_epilogue_check_write(logits, logit_bytes); if (rc != LG_OK) return rc; }
     int log_slots = 6;                                   // 2^k >= 2 (P + G), at least kPenalizeMinSlots: at most 8192 slots, 64 KiB

@@ -67,11 +67,6 @@ static int launch_sample_rows(dim3 grid, dim3 block, size_t lds, const float* lo
     return LG_OK;
 }
 
-static bool sample_rows_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + uintptr_t(b_bytes) && b0 < a0 + uintptr_t(a_bytes);
-}
-
 }  // namespace lg
 
 using namespace lg;
@@ -92,8 +87,8 @@ extern "C" int lg_sample_rows_f32(const float* logits, int64_t rows, int64_t col
     const int64_t out_bytes = rows * out_itemsize;
     if (rows > 0) {
         const int64_t logit_bytes = ((rows - 1) * row_pitch + cols) * 4;
-        LG_ARG(!sample_rows_overlap(out, out_bytes, logits, logit_bytes) && !sample_rows_overlap(out, out_bytes, table, n * 32) &&
-                   !sample_rows_overlap(out, out_bytes, index, rows * 4) && !sample_rows_overlap(out, out_bytes, counter, n * 4),
+        LG_ARG(!bytes_overlap(out, out_bytes, logits, logit_bytes) && !bytes_overlap(out, out_bytes, table, n * 32) &&
+                   !bytes_overlap(out, out_bytes, index, rows * 4) && !bytes_overlap(out, out_bytes, counter, n * 4),
                "lg_sample_rows_f32: the tokens overlap an operand");
     }
     { const int rc = adam_epilogue_check_write(out, out_bytes); if (rc != LG_OK) return rc; }

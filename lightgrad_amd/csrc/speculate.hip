@@ -140,12 +140,6 @@ __global__ __launch_bounds__(kSpecThreads) void speculate_commit(const SpecArgs 
     }
 }
 
-// do the bytes [x, x + nx) and [y, y + ny) share an address?
-static bool spec_overlap(const void* x, int64_t nx, const void* y, int64_t ny) {
-    const char *a = static_cast<const char*>(x), *b = static_cast<const char*>(y);
-    return a < b + ny && b < a + nx;
-}
-
 }  // namespace lg
 
 using namespace lg;
@@ -174,7 +168,7 @@ extern "C" int lg_speculate_commit_i32(const int32_t* tgt, int32_t* ids, int32_t
                                   batch * 4, 12};
         for (int i = 0; i < 9; ++i)
             for (int j = i + 1; j < 9; ++j)
-                LG_ARG(!spec_overlap(ptr[i], bytes[i], ptr[j], bytes[j]), "%s: operands %d and %d (of tgt, ids, count, position_ids, out_ids, pos, end, done, stats) overlap", name, i, j);
+                LG_ARG(!bytes_overlap(ptr[i], bytes[i], ptr[j], bytes[j]), "%s: operands %d and %d (of tgt, ids, count, position_ids, out_ids, pos, end, done, stats) overlap", name, i, j);
         for (int i = 1; i < 9; ++i) {
             if (i == 6) continue;               // `end` is read only
             const int rc = adam_epilogue_check_write(ptr[i], bytes[i]);

@@ -294,12 +294,12 @@ def test_paged_operands_that_overlap_are_refused_and_nothing_is_launched(hip, re
 
 # ---- serve_commit_paged ---------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("b", (1, 3, 7, 70))
+@pytest.mark.parametrize("b", (1, 3, 7, 64, 65, 70, 1024))
 @pytest.mark.parametrize("eos", [None, 3])
 @pytest.mark.parametrize("prefix_blocks", (0, 2))
 def test_serve_commit_paged_against_the_words_by_hand(hip, recorder, b, eos, prefix_blocks):
-    """the tables and the stack included: which block a slot gets is fixed by the definition.  70 slots: two waves, the scans
-    cross a wave"""
+    """the tables and the stack included: which block a slot gets is fixed by the definition.  64 slots fill a wave, 65 and 70
+    cross into a second - the scans cross a wave -, 1024 fill the workgroup"""
     for spare in (0, 2, 500):
         for waiting in (0, 2, b + 100):
             state, nxt = pg.commit_state(b, waiting, 10 * b + waiting, prefix_blocks, spare, eos=eos)

@@ -249,7 +249,7 @@ def test_counts_that_overlap_are_refused_and_nothing_is_launched(hip, recorder):
 
 # ---- serve_commit ---------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("b", [1, 5, 300])
+@pytest.mark.parametrize("b", [1, 5, 64, 65, 300, 1024])
 @pytest.mark.parametrize("eos", [None, 3])
 @pytest.mark.parametrize("strided", [False, True], ids=["dense", "strided-out"])
 def test_serve_commit_against_the_loop_by_hand(hip, recorder, b, eos, strided):

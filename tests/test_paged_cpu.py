@@ -52,7 +52,7 @@ def assert_commit_matches(state, nxt, prefix_blocks, eos, expect_flag=False):
     return want
 
 
-@pytest.mark.parametrize("b", (1, 3, 7))
+@pytest.mark.parametrize("b", (1, 3, 7, 64, 65, 70, 1024))
 @pytest.mark.parametrize("eos", (None, 3))
 @pytest.mark.parametrize("prefix_blocks", (0, 2))
 @pytest.mark.parametrize("spare", (0, 2, 40))

@@ -38,7 +38,7 @@ def assert_commit(T, state, nxt, capacity, eos, strided=False, sync=None):
     return want
 
 
-@pytest.mark.parametrize("b", [1, 5, 300])
+@pytest.mark.parametrize("b", [1, 5, 64, 65, 300, 1024])
 @pytest.mark.parametrize("eos", [None, 3])
 @pytest.mark.parametrize("strided", [False, True], ids=["dense", "strided-out"])
 def test_serve_commit_on_the_numpy_backend(b, eos, strided):
