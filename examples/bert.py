@@ -63,6 +63,11 @@ Differences from the reference, on purpose:
                                                        # the log-probability of every token and the 3 most likely ids of its step,
                                                        # one launch a step behind the draw, nothing read back until the end
                                                        # (`serve(logprobs=)`, `logits.logprob_rows`, csrc/logprob.hip)
+    python examples/bert.py --serve 16 --allow-only A,B,.. | --ban A,B,.. | --one-of "A B;C D E" | --stop-after "A B" [--eos E] [--graph] [--cpu]
+                                                       # guided decoding: one token automaton for every request - an allowed set,
+                                                       # banned ids, one of several sequences (then eos), or free text up to a
+                                                       # stop sequence (`serve(guide=)`, `light.guide`, `logits.guide_rows`,
+                                                       # csrc/guide.hip)
     python examples/bert.py --mlm --bf16-decoder       # the decoder onto the vocabulary (forward, dx, dW) on the bf16 matrix cores:
                                                        # config key `decoder_precision="bf16"`; tensors stay float32
 """
@@ -815,9 +820,14 @@ def next_token(logits, sampler=None, pool=None, eos=None):
     `logprobs` scores the token behind whichever draw it was with ONE `logits.logprob_rows`, against the logits the draw read
     (penalised, in front of temperature, top-k and top-p), into column out_len[r] of the request r the slot holds - the caller's
     `pool.commit` moves out_len afterwards.  A prefilling slot writes column 0 of its request with a value nobody keeps: the
-    request's first stored token overwrites it"""
+    request's first stored token overwrites it.  A pool with `guide` passes the logits through ONE `logits.guide_rows` behind the
+    penalties and in front of whichever draw follows: the automaton of the request the slot holds absorbs the token that request
+    stored last, the ids its state does not allow go to -inf and a forced id to +0.0 - so a forced end beats `min_new_tokens`, and
+    `logprob_rows` scores the guided logits.  A prefilling slot has stored nothing: its state stays at the start"""
     if pool is not None and pool.penalties is not None:
         logits = logits.penalize_rows(pool.penalties, pool.req, pool.prompts, pool.prompt_len, pool.out, pool.out_len, eos=eos)
+    if pool is not None and pool.guide is not None:
+        logits = logits.guide_rows(*pool.guide, pool.req, pool.out, pool.out_len, pool.guide_state)
     if pool is not None and pool.sampling is not None:
         nxt = logits.sample_rows(pool.sampling, pool.req, pool.out_len)
     elif sampler is None:
@@ -1209,7 +1219,8 @@ def generate(model, ids, max_new_tokens, attention_mask=None, cache=None, graph=
     """decoding of a model built with `causal=True`: (b, s0) prompt ids -> (b, s0 + max_new_tokens) int32 ids on the
     prompt's backend.  temperature=None is greedy; with a temperature every token - the prompt's own first one included - is
     `logits.sample(temperature, top_k, top_p)`, drawn from the backend's random stream (`light.manual_seed`): one call of the
-    stream per token, eager or captured alike.
+    stream per token, eager or captured alike.  Guided decoding (`serve(guide=)`) is a keyword of `serve` alone: `generate`
+    does not take it, and beams and speculation have no guides.
     The prompt is prefilled once through the causal forward, which fills an nn.KVCache (made here unless given: one of exactly
     s0 + max_new_tokens positions); every further token is one `decode_step` on the last position only.
     Nothing is read back to the host - the caller's `.numpy()` is the first read.  attention_mask: a key-padding mask (b, s0)
@@ -1379,7 +1390,7 @@ def fill_shared_prefix(model, pool, tokens):
 
 def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, pad_token_id=0, graph=None, temperature=None, top_k=0,
           top_p=1.0, poll=8, lengths=None, cache=None, token_budget=None, num_blocks=None, block_size=16, shared_prefix=0, kv_dtype=None,
-          seeds=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, min_new_tokens=0, logprobs=None):
+          seeds=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, min_new_tokens=0, logprobs=None, guide=None):
     """continuous batching: N requests through `slots` cache slots, a finished slot refilled at once from the queue while the
     others go on decoding.  prompts: a list of N int sequences, or (N, P) right-padded ids (an array or a tensor) with lengths=;
     max_new_tokens: an int, or N ints - a budget per request.  Returns (out (N, G) int32 with G = the largest budget, filled with
@@ -1428,6 +1439,21 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
     the float32 rounding of the forward (with kv_dtype="bf16": of the rounded model); the ids in `top_ids` are exact wherever the
     gaps between the reference's ranks rule out a near-tie.  With logprobs=None nothing is built, `stats` has no such key and
     the step is launch for launch what it was.
+    guide: None, one `light.guide.TokenAutomaton` for every request, or N entries that may include None - GUIDED DECODING: the
+    automaton (`guide.allow_only`, `ban_sequences`, `one_of`, `stop_after`, or one built by hand) advances with every token the
+    request stores, and the ids its state does not allow cannot be drawn; eos_token_id is allowed exactly in accepting states.
+    `guide.compile_guides` lays the automata out once; every step then calls ONE `logits.guide_rows` (csrc/guide.hip) behind the
+    penalties and in front of the draw - and so in front of `logprob_rows`, which scores the guided logits: the probabilities over
+    the allowed ids - driven by the pool's `req`, `out`, `out_len` and `guide_state`; `stats` gains `guide` and the step has
+    exactly one kernel more.  The contract: token g of request r is drawn from the logits behind its prompt and its first g
+    tokens, passed through the penalties and then through `guide.guide_logits` in the state its own automaton reaches on those g
+    tokens.  So a request alone defines its tokens, whatever slots, chunk, token_budget, num_blocks, block_size, shared_prefix and
+    the other requests are (with kv_dtype="bf16": the tokens of the rounded model).  Hence `automaton.walk(tokens)` is never -1;
+    a request that ended with eos has `automaton.accepts(tokens without the eos)`; a budget that ends it first leaves a valid
+    prefix; an unguided request in a guided run has the tokens of the run without guide=.  A state that allows one id alone forces
+    it (+0.0, log-probability 0.0), min_new_tokens or not.  An automaton of another vocabulary is refused by name, and so is one
+    with a state that only an end can follow when no eos_token_id is given.  With guide=None nothing is built and the step is
+    launch for launch what it was.  `generate` does not take the keyword.
     cache: an nn.KVCache(per_row=True) of `slots` rows to use (default: one whose capacity is the longest request's need).
     token_budget: None, or T >= slots - every step is TOKEN-PACKED: it has T token rows for all slots together in place of
     (slots, chunk) rows.  A decoding slot takes one row; the rows left go to the prefilling slots in slot order, in pieces of at
@@ -1514,9 +1540,20 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
         if (penalties == light.random.penalty_table()).all():
             penalties = None                                # sequences of neutral values: no table either
     want = None if logprobs is None else light.random.logprob_want(logprobs, n)
-    pool = nn.RequestPool(cache, padded, lengths, budgets, chunk, pad_token_id=pad_token_id, max_positions=positions, sampling=table, penalties=penalties,
-                          logprobs=want, **packed)
     eos = None if eos_token_id is None else int(eos_token_id)
+    guides = None
+    if guide is not None:
+        vocab = weight.shape[0]
+        entries = [guide] * n if isinstance(guide, light.guide.TokenAutomaton) else list(guide)
+        assert len(entries) == n and all(a is None or isinstance(a, light.guide.TokenAutomaton) for a in entries), \
+            "serve: guide= is None, one light.guide.TokenAutomaton, or one entry per request (%d), each an automaton or None" % n
+        for r, a in enumerate(entries):
+            assert a is None or a.vocab_size == vocab, "serve: the guide of request %d is over a vocabulary of %d ids, the model's has %d" % (r, a.vocab_size, vocab)
+            assert a is None or eos is not None or not light.guide.needs_eos(a), \
+                "serve: the guide of request %d has a state that only an end can follow: it needs eos_token_id" % r
+        guides = light.guide.compile_guides(entries, n, eos, vocab_size=vocab)                # None if every entry is None
+    pool = nn.RequestPool(cache, padded, lengths, budgets, chunk, pad_token_id=pad_token_id, max_positions=positions, sampling=table, penalties=penalties,
+                          logprobs=want, guide=None if guides is None else tuple(guides), **packed)
     sampler = None if temperature is None or table is not None else (temperature, top_k, top_p)
     stats = {"steps": 0, "requests": n, "slots": int(slots), "chunk": chunk, **packed}
     if table is not None:
@@ -1525,6 +1562,8 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
         stats["penalties"] = True
     if want is not None:
         stats["logprobs"] = {"token": pool.logprob, "top_ids": pool.top_ids, "top": pool.top_logprob}
+    if guides is not None:
+        stats["guide"] = True
     if paged:
         stats.update(num_blocks=cache.num_blocks, block_size=cache.block_size, kv_dtype=cache.kv_dtype, pool_bytes=cache.pool_bytes())
 
@@ -1592,6 +1631,17 @@ if __name__ == "__main__":
                 sampling[key] = option(flag, kind, None)
         if "--logprobs" in sys.argv:
             sampling["logprobs"] = option("--logprobs", int, 0)
+        ids_of = lambda text: [int(v) for v in text.replace(",", " ").split()]          # noqa: E731
+        for flag, builder, many in (("--allow-only", light.guide.allow_only, False), ("--ban", light.guide.ban_sequences, True),
+                                    ("--one-of", light.guide.one_of, True), ("--stop-after", light.guide.stop_after, True)):
+            if flag in sys.argv:
+                # one automaton for every request; sequences are separated by ";", ids by blanks or commas (--ban A,B,..: single ids)
+                text = option(flag, str, "")
+                if flag == "--ban" and ";" not in text and " " not in text.strip():
+                    wanted = [[v] for v in ids_of(text)]
+                else:
+                    wanted = [ids_of(part) for part in text.split(";") if part.strip()] if many else ids_of(text)
+                sampling["guide"] = builder(TINY["vocab_size"], wanted)
         t0 = time.perf_counter()
         if "--token-budget" in sys.argv:
             sampling["token_budget"] = option("--token-budget", int, None)

@@ -1194,6 +1194,32 @@ int lg_logprob_rows_f32(const float* logits, int64_t rows, int64_t cols, int64_t
                         float* top_logprob, int64_t n_max);
 int lg_logprob_lds_cols(void);
 
+/* ---- guided decoding: per-request token automata on the logits, in place (csrc/guide.hip) ------------------
+ * Per row of fp32 logits [rows, cols] (row r at logits + r * row_pitch), IN PLACE and in ONE launch: the ids that the state of the
+ * row's request does not allow go to -inf.  allow: S rows of W = ceil(cols / 32) int32 words, bit v % 32 of word v / 32 says id v
+ * is allowed in the state (the bits at and behind cols are 0).  states: S rows of 4 int32 words (16-byte aligned): the default next
+ * state or -1, the offset of the state's first exception in `edges`, the number of its exceptions, the forced id or -1.  edges: E
+ * rows of (id, next state), sorted by id within a state.  index: rows int32 words, row r names request i = index[r].  out [N, G]
+ * (row pitch out_pitch) and out_len [N]: the tokens request i has stored are out[i, :out_len[i]].  state [N, 2] (8-byte aligned):
+ * (q, k), the state of request i's automaton behind its first k stored tokens; q == -1: the request is unguided.  Per row:
+ *   1. i < 0, or q == -1: nothing of the row is read or written.
+ *   2. the row is BAD when i >= N, g = out_len[i] is outside [0, G], q is outside [0, S), k is outside [0, g]; when a token
+ *      out[i, j], j = k .. g - 1, lies outside [0, cols) or has its bit clear in the state that absorbs it; when a state's run of
+ *      exceptions leaves [0, E] or the next state - the exception's target, found by binary search, else the default - lies outside
+ *      [0, S); when the final state's forced id f is outside [-1, cols) or has its bit clear.  NOTHING of a bad row is written,
+ *      neither logits nor state, and LG_STATUS_BAD_INDEX is raised (LG_EINDEX at the next synchronisation); the others are computed.
+ *   3. state[i] = (q', g) as one 8-byte word; logits[r, v] = -inf wherever the bit of v is clear in q'; +0.0 at f if f >= 0.  No
+ *      logit is read: every allowed value keeps its bytes.
+ * lightgrad_amd/guide.py `guide_logits` is the definition; the results are its results bit for bit, whatever the grid.  The grid
+ * is (slices, rows) workgroups; lg_guide_rows_slices(s) sets the slices of a row for the calls that follow (0: chosen from cols,
+ * the default; at most 64) and returns the previous setting - the result does not depend on it.  rows == 0 returns LG_OK at once.
+ * 1 <= rows <= 65535; 1 <= cols < 2^31; row_pitch >= cols; S, E, N, G >= 1; out_pitch >= G; no NULL or misaligned operand; the
+ * logits share no byte with any other operand, and neither does `state`. */
+int lg_guide_rows_f32(float* logits, int64_t rows, int64_t cols, int64_t row_pitch, const int32_t* allow, const int32_t* states, int64_t S,
+                      const int32_t* edges, int64_t E, const int32_t* index, const int32_t* out, int64_t out_pitch, int64_t G,
+                      const int32_t* out_len, int32_t* state, int64_t N);
+int lg_guide_rows_slices(int slices);
+
 /* ---- hidden dropout inside the LayerNorm launches (csrc/rowwise.hip) ----------------------------------
  * A dropout that sits directly in front of or behind a LayerNorm over dense fp32 [rows, cols], drawn where the LayerNorm
  * kernel loads or stores its row.  ONE call of the stream above per forward; element i = row * cols + col of the dense operand

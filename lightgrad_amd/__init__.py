@@ -1,6 +1,6 @@
 """lightgrad_amd - an MI355X-native (gfx950) tensor backend behind lightgrad's
 autograd surface.  Top-level names follow the reference's `lightgrad/__init__.py:1-6`."""
-from . import autograd, data, loss, metrics, nn, optim, random
+from . import autograd, data, guide, loss, metrics, nn, optim, random
 from .autograd import Tensor, CpuTensor, HipTensor, Gradients, no_grad
 
 empty, zeros, ones = Tensor.empty, Tensor.zeros, Tensor.ones

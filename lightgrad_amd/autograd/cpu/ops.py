@@ -17,6 +17,7 @@ import numpy as np
 from ..func import Function
 from ..dropout import DropoutFunction
 from ... import random as _random
+from ... import guide as _guide
 from .tensor import CpuTensor
 
 
@@ -477,6 +478,30 @@ def _logprob_rows(logits, token, want, index, counter, logprob, top_ids, top_log
 
 
 CpuTensor.logprob_rows = _logprob_rows
+
+
+def _guide_rows(logits, allow, states, edges, index, out, out_len, state):
+    """ logits.guide_rows(allow, states, edges, index, out, out_len, state): the token automata of `lightgrad_amd.guide.guide_logits`,
+    IN PLACE and outside the tape; returns `logits`.  logits (rows, V) or (rows, 1, V), which must not require a gradient; allow
+    (S, W), states (S, 4), edges (E, 2) int32 (`guide.compile_guides`); index int32 (rows,), -1 = a free row (untouched, unread);
+    out (N, G), out_len (N,) int32: the tokens every request has stored; state int32 (N, 2): (q, k) per request, moved to
+    (the state behind the out_len[i] stored tokens, out_len[i]) in place.  The ids the state does not allow go to -inf, a forced
+    id to +0.0, everything else keeps its bytes.  A bad row (see the definition) keeps its bits and its state, and the call raises
+    IndexError after every other row has been computed. """
+    rows, V = _guide.check_guide_rows_operands(logits, allow, states, edges, index, out, out_len, state)[:2]
+    from ..grads import Gradients
+    assert logits.ctx is None and not (Gradients._is_enabled() and logits.requires_grad), \
+        "guide_rows writes the logits in place: they must not require a gradient (run it under Gradients.no_grad(), or pass requires_grad=False)"
+    y, new_state, bad = _guide.guide_logits(logits.data.reshape(rows, V), allow.data, states.data, edges.data, index.data, out.data, out_len.data, state.data)
+    good = np.flatnonzero((index.data >= 0) & ~bad)
+    logits.data[good] = y[good].reshape((len(good),) + tuple(logits.shape[1:]))      # a view keeps the bytes between its rows
+    state.data[...] = new_state
+    if bad.any():
+        raise IndexError("guide_rows: rows %s name no request, or one whose lengths, state or stored tokens its automaton does not allow" % np.flatnonzero(bad).tolist())
+    return logits
+
+
+CpuTensor.guide_rows = _guide_rows
 
 
 def _decode_commit(nxt, token, out_ids, pos, done, eos=None):

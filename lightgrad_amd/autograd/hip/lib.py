@@ -208,6 +208,9 @@ PROTOTYPES = {
     "lg_logprob_rows_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                     c_void_p, c_int64]),
     "lg_logprob_lds_cols": (c_int, []),
+    "lg_guide_rows_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64,
+                                  c_void_p, c_void_p, c_int64]),
+    "lg_guide_rows_slices": (c_int, [c_int]),
     "lg_dropout_layernorm_fwd_f32": (c_int, [c_void_p] * 7 + [c_int64, c_int64, c_float, c_double, c_int, c_void_p]),
     "lg_dropout_layernorm_bwd_f32": (c_int, [c_void_p] * 7 + [c_int64, c_int64, c_double, c_int, c_void_p]),
     "lg_conv2d_fwd_f32": (c_int, [c_void_p] * 4 + [c_int64] * 10 + [c_int]),

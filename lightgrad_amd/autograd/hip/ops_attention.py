@@ -14,6 +14,7 @@ import numpy as np
 from ..func import Function
 from ..grads import Gradients
 from ... import random as _random
+from ... import guide as _guide
 from .tensor import HipTensor, GradGroup, flush_lazy_readers
 from . import lib as _l
 from .ops import _F32, _require_f32, _dropout_base, linear
@@ -902,6 +903,54 @@ def logprob_rows(logits, token, want, index, counter, logprob, top_ids, top_logp
 
 
 HipTensor.logprob_rows = logprob_rows
+
+
+""" Guided decoding: per-request token automata on the logits of a serving step in one launch (csrc/guide.hip) """
+
+
+def guide_rows(logits, allow, states, edges, index, out, out_len, state):
+    """ logits.guide_rows(allow, states, edges, index, out, out_len, state): what `CpuTensor.guide_rows` defines
+    (`lightgrad_amd.guide.guide_logits`) - the automaton of request index[r] absorbs the tokens that request has stored since its
+    pair in `state`, the ids its state does not allow go to -inf and a forced id to +0.0 - in ONE launch (lg_guide_rows_f32), IN
+    PLACE on the logits and on `state` and outside the tape; returns `logits`.  logits float32 (rows, V) or (rows, 1, V) that
+    require no gradient, the last stride 1 and the row pitch at least V (rows of a wider tensor are fine, whatever their alignment;
+    a lazy producer is computed first); the others int32 HipTensors; `state` (N, 2) dense.  The logits and `state` share no byte
+    with any other operand.  No logit is read: an allowed value keeps its bytes.  Everything the launch needs is device state, no
+    host value enters: a captured step replays as it stands.  A bad row keeps its bytes and its state and raises the device's
+    status flag (IndexError at the next synchronisation). """
+    name = "guide_rows"
+    reads = (allow, states, edges, index, out, out_len)
+    assert all(isinstance(t, HipTensor) for t in (logits, state) + reads), "%s: every operand is a HipTensor" % name
+    if logits._dtype != _F32:
+        raise TypeError("guide_rows is float32-only on HipTensor (got %s)" % logits._dtype)
+    rows, cols, S, E, N, G = _guide.check_guide_rows_operands(logits, allow, states, edges, index, out, out_len, state)
+    assert logits.ctx is None and not (Gradients._is_enabled() and logits.requires_grad), \
+        "guide_rows writes the logits in place: they must not require a gradient (run it under Gradients.no_grad(), or pass requires_grad=False)"
+    assert rows <= 65535, "%s: at most 65535 rows in a launch (got %d)" % (name, rows)
+    if rows == 0:
+        return logits
+    logits.data                                          # a lazy producer is computed now: the launch writes into its result
+    state.data
+    pitch = logits._strides[0] if rows > 1 else cols
+    # the launch writes the logits and the state where they lie: a layout it cannot address is an error, never a copy
+    assert (cols == 1 or logits._strides[-1] == 1) and pitch >= cols, \
+        "%s: the vocabulary must be contiguous and the row pitch at least V = %d (strides %s)" % (name, cols, logits._strides)
+    assert state.is_contiguous(), "%s: state must be dense (shape %s, strides %s)" % (name, state._shape, state._strides)
+    # what is only read may be copied once into a layout the launch addresses
+    allow, states, edges, index, out_len = (t.contiguous() for t in (allow, states, edges, index, out_len))
+    out = out if (G == 1 or out._strides[1] == 1) and (N == 1 or out._strides[0] >= G) else out.contiguous()
+    for t in (allow, states, edges, index, out, out_len):
+        assert not _shares_bytes(logits, t), "%s: the logits overlap an integer operand" % name
+        assert not _shares_bytes(state, t), "%s: state overlaps another integer operand" % name
+    assert not _shares_bytes(logits, state), "%s: the logits overlap state" % name
+    flush_lazy_readers(logits)
+    flush_lazy_readers(state)
+    _l.check(_l.lib().lg_guide_rows_f32(logits.ptr, rows, cols, pitch, allow.ptr, states.ptr, S, edges.ptr, E, index.ptr, out.ptr,
+                                        out._strides[0] if N > 1 else G, G, out_len.ptr, state.ptr, N))
+    return logits
+
+
+HipTensor.guide_rows = guide_rows
 
 
 def serve_commit_packed(nxt, prompts, prompt_len, budget, out, out_len, queue, req, pos, count, cu, ids, position_ids, last, capacity, chunk, eos=None):

@@ -504,7 +504,7 @@ class RequestPool(object):
     here, on the host, against the capacity.  State, not parameters, like the cache.  Not a class of the reference."""
 
     def __init__(self, cache, prompts, lengths, budgets, chunk: int, pad_token_id: int = 0, max_positions=None, token_budget=None, prefix_blocks: int = 0,
-                 sampling=None, penalties=None, logprobs=None):
+                 sampling=None, penalties=None, logprobs=None, guide=None):
         """max_positions: the model's position embeddings, if the caller knows them - the capacity must not exceed them.
         token_budget: None, or T >= slots - the steps are TOKEN-PACKED: ids and position_ids are (1, T), the step's tokens of all
         slots in one flat buffer, `cu` (slots + 1,) says which rows are whose, `last` names rows of the T, and `commit` is
@@ -528,7 +528,13 @@ class RequestPool(object):
         `self.logprob` float32 (N, G), `self.top_ids` int32 (N, G, n) and `self.top_logprob` float32 (N, G, n) with n = max(k, 1),
         filled with +0.0, -1 and +0.0; a step then calls `logits.logprob_rows(nxt, pool.logprobs, pool.req, pool.out_len,
         pool.logprob, pool.top_ids, pool.top_logprob)` behind the draw and in front of `commit`, which moves out_len: token g of
-        request r is scored in column g.  None: the four attributes are None and everything is as it was."""
+        request r is scored in column g.  None: the four attributes are None and everything is as it was.
+        guide: None, or the tables of `guide.compile_guides` for the N requests (allow, states, edges, start) - the token automata
+        that restrict what each REQUEST may generate.  The three tables are uploaded once as `self.guide` (a tuple), next to
+        `self.guide_state` int32 (N, 2), initialised to (start[r], 0): the state of request r's automaton and the number of stored
+        tokens it has absorbed.  A step then passes its logits through `logits.guide_rows(*pool.guide, pool.req, pool.out,
+        pool.out_len, pool.guide_state)` behind the penalties and in front of the draw; the launch lets the state catch up with
+        `out_len` first, so no commit changes.  None: both attributes are None and everything is as it was."""
         assert isinstance(cache, (KVCache, PagedKVCache)) and cache.per_row, \
             "RequestPool takes a cache with a position per sequence: nn.KVCache(..., per_row=True) or nn.PagedKVCache"
         self.paged = isinstance(cache, PagedKVCache)
@@ -594,6 +600,16 @@ class RequestPool(object):
             self.logprobs, self.top_ids = tensor(want), tensor(np.full(cells, -1))
             self.logprob = cls.from_numpy(np.zeros(cells[:2], np.float32), requires_grad=False)
             self.top_logprob = cls.from_numpy(np.zeros(cells, np.float32), requires_grad=False)
+        self.guide = self.guide_state = None
+        if guide is not None:
+            allow, states, edges, start = (np.asarray(a) for a in guide)
+            assert all(a.dtype == np.int32 for a in (allow, states, edges, start)) and allow.ndim == 2 and allow.shape[0] >= 1 and \
+                states.shape == (allow.shape[0], 4) and edges.ndim == 2 and edges.shape[0] >= 1 and edges.shape[1] == 2 and start.shape == (n,) and \
+                (start >= -1).all() and (start < allow.shape[0]).all(), \
+                "RequestPool: guide= is the int32 tables of guide.compile_guides - allow (S, W), states (S, 4), edges (E, 2), start (%d,) within -1 .. S - 1 " \
+                "(got %s)" % (n, [(str(a.dtype), a.shape) for a in (allow, states, edges, start)])
+            self.guide = (tensor(allow), tensor(states), tensor(edges))
+            self.guide_state = tensor(np.stack([start, np.zeros(n, np.int32)], axis=1))
         # queue[1] as a tensor of its own that shares the word (indexing a tensor copies: the poll would be a launch and a read)
         if isinstance(getattr(self.queue, "data", None), np.ndarray):
             self._finished = cls.from_numpy(self.queue.data[1:2], requires_grad=False)
