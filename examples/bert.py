@@ -20,6 +20,9 @@ Differences from the reference, on purpose:
                                                        # capture with --graph), cross-entropy over the masked positions only
     python examples/bert.py --mlm --accuracy [--graph] # also counts the masked tokens predicted right (light.metrics.accuracy), on
                                                        # the device, over every step and replay: one host read at the end
+    python examples/bert.py --mlm|--clm --no-attention-probs   # config key `attention_probs=False`: nobody reads the attention
+                                                       # probabilities, so on HipTensor every layer takes the streaming attention node
+                                                       # (csrc/attention_stream.hip) - any length, no (b, heads, s, s) tensor
     python examples/bert.py --clm [--graph] [--cpu]    # a causal language model of the same parameters: config key `causal=True`
                                                        # (query i sees keys j <= i, inside the fused attention launches) and the
                                                        # next-token objective (light.data.next_token_labels)
@@ -160,12 +163,16 @@ def _bf16_refusal(cache):
 
 
 class BertSelfAttention(nn.Module):
-    def __init__(self, hidden_size, num_attention_heads, attention_probs_dropout_prob=0.0, causal=False):
+    def __init__(self, hidden_size, num_attention_heads, attention_probs_dropout_prob=0.0, causal=False, attention_probs=True):
         """`causal=True`: query i sees keys j <= i only - the decoder-style mask of a causal language model.  The values are those
-        of the composite branch below: one more additive constant, `(1 - tril) * -10000`, behind the key-padding bias"""
+        of the composite branch below: one more additive constant, `(1 - tril) * -10000`, behind the key-padding bias.
+        `attention_probs=False`: the caller does not want the (b, heads, s, s) probabilities - `forward` returns (context, None), and
+        a backend with the streaming node (`self_attention(probs=False)`) never writes them to memory: any length it takes, also
+        beyond 512 positions"""
         nn.Module.__init__(self)
         assert hidden_size % num_attention_heads == 0
         self.causal = bool(causal)
+        self.attention_probs = bool(attention_probs)
         self._tril = {}             # (backend class, s, dtype) -> the (1, 1, s, s) lower-triangular constant of ones
         self.dropout = nn.Dropout(attention_probs_dropout_prob)
         self.h, self.d = num_attention_heads, hidden_size // num_attention_heads
@@ -486,6 +493,18 @@ class BertSelfAttention(nn.Module):
         if self.causal:
             extra["causal"] = True
             drop = dict(drop, causal=True)
+        if not self.attention_probs and "dropout" not in drop and hasattr(hidden, "stream_attention") and (attention_mask is None or (
+                attention_mask.dtype == np.float32 and not attention_mask.requires_grad and tuple(attention_mask.shape) in ((b, s), (1, s)))) \
+                and hidden.self_attention_supported(self.query.weight, self.h, stream=True):
+            # nobody reads the probabilities: the one-node form over the streaming launches, which store a log-sum-exp per row instead
+            # (attention dropout is not in those kernels: with it active the paths below run, as they did)
+            extra = {"mask": attention_mask} if attention_mask is not None else {}
+            context = hidden.self_attention(self.query.weight, self.query.bias, self.key.weight, self.key.bias,
+                                            self.value.weight, self.value.bias, heads=self.h, scale=scale, causal=self.causal, probs=False, **extra)
+            if cache is not None:
+                width, qkv = self.h * self.d, context.attention_qkv
+                cache.fill(index, qkv[:, :, width:2 * width], qkv[:, :, 2 * width:])
+            return context, None
         if fused and hidden.self_attention_supported(self.query.weight, self.h, **extra):
             # the backend's one-node form of this whole method: one launch for the three projections, one for the attention
             extra = {"mask": attention_mask} if attention_mask is not None else {}
@@ -495,7 +514,7 @@ class BertSelfAttention(nn.Module):
                 # the projection launch's q | k | v buffer: its key and value columns go to the cache on the device
                 width, qkv = self.h * self.d, context.attention_qkv
                 cache.fill(index, qkv[:, :, width:2 * width], qkv[:, :, 2 * width:])
-            return context, context.attention_probs
+            return context, (context.attention_probs if self.attention_probs else None)
         q, k, v = self.query(hidden), self.key(hidden), self.value(hidden)
         if cache is not None:
             cache.fill(index, k, v)
@@ -506,7 +525,7 @@ class BertSelfAttention(nn.Module):
             context = q.long_attention(k, v, heads=self.h, scale=scale, mask=attention_mask, **drop) if long else \
                 q.masked_attention(k, v, heads=self.h, scale=scale, mask=attention_mask, **drop) if masked else \
                 q.attention(k, v, heads=self.h, scale=scale, **drop)
-            return context, context.attention_probs
+            return context, (context.attention_probs if self.attention_probs else None)
         # head split: (b, s, h*d) -> (b, h, s, d) as stride permutations, no copies
         q = q.reshape(b, s, self.h, self.d).transpose(0, 2, 1, 3)
         k = k.reshape(b, s, self.h, self.d).transpose(0, 2, 3, 1)
@@ -526,13 +545,14 @@ class BertSelfAttention(nn.Module):
                 scores = scores + ((1.0 - self._lower_triangle(scores, s)) * -10000.0).detach()
             probs = scores.softmax(axis=-1)
         context = (self.dropout(probs) @ v).transpose(0, 2, 1, 3).reshape(b, s, self.h * self.d)
-        return context, probs
+        return context, (probs if self.attention_probs else None)
 
 
 class BertAttention(nn.Module):
-    def __init__(self, hidden_size, num_attention_heads, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0, causal=False):
+    def __init__(self, hidden_size, num_attention_heads, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0, causal=False,
+                 attention_probs=True):
         nn.Module.__init__(self)
-        self.self = BertSelfAttention(hidden_size, num_attention_heads, attention_probs_dropout_prob, causal=causal)
+        self.self = BertSelfAttention(hidden_size, num_attention_heads, attention_probs_dropout_prob, causal=causal, attention_probs=attention_probs)
         self.dropout = nn.Dropout(hidden_dropout_prob)
         self.output = nn.Module()
         self.output.dense = nn.Linear(hidden_size, hidden_size)
@@ -560,9 +580,10 @@ class BertAttention(nn.Module):
 
 class BertLayer(nn.Module):
     def __init__(self, hidden_size, intermediate_size, num_attention_heads, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0,
-                 causal=False):
+                 causal=False, attention_probs=True):
         nn.Module.__init__(self)
-        self.attention = BertAttention(hidden_size, num_attention_heads, hidden_dropout_prob, attention_probs_dropout_prob, causal=causal)
+        self.attention = BertAttention(hidden_size, num_attention_heads, hidden_dropout_prob, attention_probs_dropout_prob, causal=causal,
+                                       attention_probs=attention_probs)
         self.dropout = nn.Dropout(hidden_dropout_prob)
         self.intermediate = nn.Module()
         self.intermediate.dense = nn.Linear(hidden_size, intermediate_size)
@@ -597,14 +618,16 @@ class BertLayer(nn.Module):
 class BertModel(nn.Module):
     def __init__(self, hidden_size, intermediate_size, num_hidden_layers, num_attention_heads, vocab_size,
                  max_position_embeddings, type_vocab_size, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0, causal=False,
-                 **unused):
+                 attention_probs=True, **unused):
         """`causal=True`: every layer's attention is causal - with the next-token objective (`clm_forward_backward`) a decoder-style
-        language model of the same parameters"""
+        language model of the same parameters.  `attention_probs=False`: no layer hands back its attention probabilities
+        (BertSelfAttention) - on a backend with the streaming node they are never stored, and sequences beyond 512 positions stay
+        on the fused path"""
         nn.Module.__init__(self)
         self.embeddings = BertEmbedding(hidden_size, vocab_size, max_position_embeddings, type_vocab_size, hidden_dropout_prob)
         self.encoder = nn.Module()
         self.encoder.layer = nn.ModuleList(*[BertLayer(hidden_size, intermediate_size, num_attention_heads, hidden_dropout_prob,
-                                                       attention_probs_dropout_prob, causal=causal)
+                                                       attention_probs_dropout_prob, causal=causal, attention_probs=attention_probs)
                                              for _ in range(num_hidden_layers)])
 
     def forward(self, input_ids, attention_mask=None, token_type_ids=None, cache=None, append=False, count=None, token_positions=None, cu=None):
@@ -1736,8 +1759,12 @@ if __name__ == "__main__":
     to_device = (lambda t: t) if cpu else (lambda t: t.hip())
     np.random.seed(0)
     config = dict(TINY, decoder_precision="bf16" if "--bf16-decoder" in sys.argv else None, causal="--clm" in sys.argv)
+    if "--no-attention-probs" in sys.argv:
+        assert "--mlm" in sys.argv or "--clm" in sys.argv, "--no-attention-probs goes with the --mlm and --clm steps"
+        config["attention_probs"] = False                  # the streaming attention node: no (b, heads, s, s) tensor per layer
     model = BertForMaskedLM(**config).map_parameters(to_device)
     ids = to_device(light.from_numpy(np.random.randint(0, TINY["vocab_size"], (batch, 128)).astype(np.int32), requires_grad=False))
+    ids._requires_grad = False                             # ids are state on either backend: they go into the lookups by keyword
     total = None
     if "--accuracy" in sys.argv:
         assert "--mlm" in sys.argv, "--accuracy counts the masked tokens of the --mlm objective"

@@ -625,6 +625,30 @@ int lg_attention_causal_fwd_f32(const float* q, int64_t ldq, int64_t sbq, const 
                                 int64_t batch, int64_t heads, int64_t S, int64_t D, float scale,
                                 const float* mask, int64_t sbm, double prob, uint64_t* base_out);
 
+/* Streaming attention: any length, no stored probabilities (csrc/attention_stream.hip).  The forward runs an online softmax over
+ * key chunks of 128 and writes, next to the context, ONE float per row: lse[b][head][i] = log sum_j exp(score_ij), a dense
+ * (batch, heads, S) tensor.  The backward forms the probabilities again from it, P = exp(score - lse), in two launches in stream
+ * order: the query role writes delta[b][head][i] = sum_d dO o O (dense like lse, scratch of the call) and dQ, the key role reads
+ * it and writes dK and dV.  Nothing of size S x S touches memory.  Scores as in the masked forms: fl(fl(acc * scale) + fl(fl(1 -
+ * mask) * -10000)); mask NULL for none; causal != 0: query i sees keys j <= i, keys beyond take no part in the max or the sum and
+ * key chunks wholly above the diagonal cost nothing.  The backward takes the forward's mask, scale and causal again (it has no P
+ * to read them from) and the forward's o and lse.  Rows >= S are neither read nor written; every fold runs in a fixed order (the
+ * same bits every run, no float atomics).  Supported: D = 32 or 64, 1 <= S <= 16384 (lg_attention_stream_supported, pure host
+ * code; the bound is the largest length the kernels' index arithmetic has been checked for).  Operands of q .. dv 16-byte aligned
+ * with pitches that are multiples of 4 and row pitches >= heads * D; lse and delta non-NULL; a non-NULL mask needs sbm == 0 or
+ * sbm >= S; batch == 0 returns LG_OK. */
+int lg_attention_stream_supported(int64_t S, int64_t D);
+int lg_attention_stream_fwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
+                                const float* v, int64_t ldv, int64_t sbv, float* o, int64_t ldo, int64_t sbo, float* lse,
+                                int64_t batch, int64_t heads, int64_t S, int64_t D, float scale,
+                                const float* mask, int64_t sbm, int causal);
+int lg_attention_stream_bwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
+                                const float* v, int64_t ldv, int64_t sbv, const float* o, int64_t ldo, int64_t sbo,
+                                const float* g, int64_t ldg, int64_t sbg, const float* lse, float* delta,
+                                float* dq, int64_t lddq, int64_t sbdq, float* dk, int64_t lddk, int64_t sbdk,
+                                float* dv, int64_t lddv, int64_t sbdv, int64_t batch, int64_t heads, int64_t S, int64_t D,
+                                float scale, const float* mask, int64_t sbm, int causal);
+
 /* ---- attention of ONE new token against a key / value cache (csrc/decode.hip) -----------------------------
  * Incremental decoding of the causal model: with t = *pos, the position of the new token, read BY THE KERNEL from one word in
  * device memory (a captured step replays with what the word holds then),

@@ -6,6 +6,10 @@ goes through the same two helpers, `_launch_attention_fwd` / `_launch_attention_
 takes the dropout entries instead.  That rule, and each symbol's name, stand here once.  `causal=True` on any op swaps the
 forward launch for the causal entry (one for every form, with or without dropout); the backward launch stays the form's own.
 
+`stream_attention` (and `self_attention(probs=False)`) is the form that stores no probabilities: an online softmax at any length
+the predicate accepts, a log-sum-exp per row on the result, its own forward and backward entries (csrc/attention_stream.hip;
+`_launch_stream_fwd` / `_launch_stream_bwd`).
+
 `decode_attention` / `self_attention_decode` are the inference ops of incremental decoding: one new token against a key / value
 cache, over lg_attention_decode_f32 (csrc/decode.hip).  They share nothing with the forms above and stay outside the tape.
 """
@@ -173,15 +177,88 @@ long_attention = _attention_op(
     `.attention_probs` (b, heads, s, s) as there, outside the tape. """)
 
 
-def self_attention_supported(x, wq, heads, masked=False, long=False, causal=False):
+def _stream_fits(s, d):
+    return bool(_l.lib().lg_attention_stream_supported(s, d))
+
+
+def _launch_stream_fwd(q3, k3, v3, out, dims, scale, mask3, causal):
+    """the streaming forward (lg_attention_stream_fwd_f32); operands as for `_launch_attention_fwd`.  Returns the log-sum-exp of
+    every row, (b, heads, s), outside the tape"""
+    b, heads, s, d = dims
+    lse = HipTensor.empty((b, heads, s), requires_grad=False)
+    _l.check(_l.lib().lg_attention_stream_fwd_f32(*q3, *k3, *v3, out.ptr, heads * d, s * heads * d, lse.ptr, b, heads, s, d, scale,
+                                                  mask3[1], mask3[2], int(causal)))
+    return lse
+
+
+def _launch_stream_bwd(q3, k3, v3, out, g3, lse, dq3, dk3, dv3, dims, scale, mask3, causal):
+    """the two streaming backward launches (lg_attention_stream_bwd_f32): they form the probabilities again from `lse`, so they
+    take the forward's context, mask, scale and causal flag; `delta` is scratch of the call"""
+    b, heads, s, d = dims
+    delta = HipTensor.empty((b, heads, s), requires_grad=False)
+    _l.check(_l.lib().lg_attention_stream_bwd_f32(*q3, *k3, *v3, out.ptr, heads * d, s * heads * d, *g3, lse.ptr, delta.ptr, *dq3, *dk3, *dv3,
+                                                  b, heads, s, d, scale, mask3[1], mask3[2], int(causal)))
+
+
+def _untaped(t):
+    """the same bytes without the tape node: what a node keeps of its own result"""
+    return HipTensor(t.data, t._shape, t._strides, t._offset, t._dtype, requires_grad=False)
+
+
+def stream_attention_supported(q, heads):
+    """does `q.stream_attention(k, v, heads, scale, mask, causal)` exist for this shape? (b, s, heads * d) with d = 32 or 64, b >= 1 and
+    any s the streaming kernels take (lg_attention_stream_supported: 1 .. 16384)"""
+    return len(q._shape) == 3 and q._dtype == _F32 and q._shape[2] % heads == 0 and q._shape[0] > 0 and \
+        _stream_fits(q._shape[1], q._shape[2] // heads)
+
+
+@HipTensor.register_op()
+class stream_attention(Function):
+    """ `long_attention` without the probabilities and without its length limit: softmax((q k^T) * scale + bias) v per head by an
+    online softmax over key chunks (csrc/attention_stream.hip), one launch forward, two backward, nothing of size s x s in
+    memory.  The result carries `.attention_lse` (b, heads, s): the log-sum-exp of every row of biased scores, outside the tape -
+    what the backward forms the probabilities from again; `.attention_probs` is None.  mask: float32 (b, s) or (1, s), no
+    gradient, None for none (the bits of a mask of ones).  causal=True: query i sees keys j <= i, in both directions' launches. """
+    def forward(ctx, q, k, v, heads=1, scale=1.0, mask=None, causal=False):
+        _require_f32(q, k, v)
+        assert q._shape == k._shape == v._shape and stream_attention_supported(q, heads), \
+            "stream_attention: unsupported shapes %s / %s / %s with %d heads" % (q._shape, k._shape, v._shape, heads)
+        b, s, width = q._shape
+        dims = (b, heads, s, width // heads)
+        mask3 = _key_mask(mask, b, s, "stream_attention")
+        (q, ldq, sbq), (k, ldk, sbk), (v, ldv, sbv) = _token_rows(q), _token_rows(k), _token_rows(v)
+        out = HipTensor.empty((b, s, width))
+        lse = _launch_stream_fwd((q.ptr, ldq, sbq), (k.ptr, ldk, sbk), (v.ptr, ldv, sbv), out, dims, float(scale), mask3, bool(causal))
+        ctx.save_for_backward(q, k, v, _untaped(out), lse, dims, float(scale), mask3, bool(causal))
+        out.attention_lse, out.attention_probs = lse, None
+        return out
+
+    def backward(ctx, out_grad):
+        q, k, v, out, lse, dims, scale, mask3, causal = ctx.get_saved_tensors()
+        b, s, width = q._shape
+        (q, ldq, sbq), (k, ldk, sbk), (v, ldv, sbv), (g, ldg, sbg) = _token_rows(q), _token_rows(k), _token_rows(v), _token_rows(out_grad)
+        dq, dk, dv = HipTensor.empty((b, s, width)), HipTensor.empty((b, s, width)), HipTensor.empty((b, s, width))
+        _launch_stream_bwd((q.ptr, ldq, sbq), (k.ptr, ldk, sbk), (v.ptr, ldv, sbv), out, (g.ptr, ldg, sbg), lse,
+                           (dq.ptr, width, s * width), (dk.ptr, width, s * width), (dv.ptr, width, s * width), dims, scale, mask3, causal)
+        return dq, dk, dv
+
+
+HipTensor.stream_attention_supported = stream_attention_supported
+
+
+def self_attention_supported(x, wq, heads, masked=False, long=False, causal=False, stream=False):
     """does `x.self_attention(wq, bq, wk, bk, wv, bv, heads, scale)` exist for these shapes?  (b, s, hidden) input, three
     (width, hidden) weights with width = heads * d, d = 32 or 64, width a multiple of 64, s = 32 .. 128 in 32s; masked=True:
     the same question for the form with `mask=` or a length that is no multiple of 32 - any s in 1 .. 128; long=True: the
-    same question for the lengths beyond - any s in 129 .. 512, with or without a mask; causal=True: and with `causal=True`"""
+    same question for the lengths beyond - any s in 129 .. 512, with or without a mask; causal=True: and with `causal=True`;
+    stream=True: the question of the node with `probs=False` - any s the streaming kernels take, mask or none, causal or not"""
     form = "long" if long else "masked" if masked else "plain"
-    return (len(x._shape) == 3 and x._dtype == _F32 and len(wq._shape) == 2 and wq._shape[1] == x._shape[2] and wq._shape[0] % heads == 0
-            and wq._shape[0] % 64 == 0 and x._shape[2] % 4 == 0 and x.numel() > 0
-            and _fits(form, x._shape[1], wq._shape[0] // heads) and (not causal or _fits("causal", x._shape[1], wq._shape[0] // heads)))
+    if not (len(x._shape) == 3 and x._dtype == _F32 and len(wq._shape) == 2 and wq._shape[1] == x._shape[2] and wq._shape[0] % heads == 0
+            and wq._shape[0] % 64 == 0 and x._shape[2] % 4 == 0 and x.numel() > 0):
+        return False
+    if stream:
+        return _stream_fits(x._shape[1], wq._shape[0] // heads)
+    return _fits(form, x._shape[1], wq._shape[0] // heads) and (not causal or _fits("causal", x._shape[1], wq._shape[0] // heads))
 
 
 def _ptr3(a, b, c):
@@ -198,15 +275,20 @@ class self_attention(Function):
     the weight / bias gradients take the routes of `linear`.  `.attention_probs` as for `attention`.  With a key-padding
     `mask` (as for `masked_attention`) or a length that is no multiple of 32 the attention launches are the masked / tail ones,
     beyond 128 positions (up to 512, mask or none) the long ones of csrc/attention_long.hip; everything else about the node is
-    the same - also with causal=True, which only picks the causal forward launch of the attention. """
-    def forward(ctx, x, wq, bq, wk, bk, wv, bv, heads=1, scale=1.0, mask=None, dropout=0.0, causal=False):
+    the same - also with causal=True, which only picks the causal forward launch of the attention.
+    probs=False: the same node over the streaming launches of `stream_attention` in place of the stored-P ones - any length they
+    take, `.attention_probs` None, `.attention_lse` in its place; projections, input gradient and weight gradients as before.
+    Dropout of the probabilities is not part of the streaming kernels: dropout > 0 with probs=False is refused. """
+    def forward(ctx, x, wq, bq, wk, bk, wv, bv, heads=1, scale=1.0, mask=None, dropout=0.0, causal=False, probs=True):
         dropout = _attention_dropout(dropout)           # > 0: `probs.dropout(p)` inside the attention launches, as for `attention`
         _require_f32(x, wq, bq, wk, bk, wv, bv)
+        stream = not probs
+        assert not (stream and dropout > 0.0), "self_attention: dropout > 0 with probs=False (the streaming kernels draw no attention dropout)"
         long = len(x._shape) == 3 and x._shape[1] > 128
         tail = mask is not None or (len(x._shape) == 3 and x._shape[1] % 32 != 0)
-        assert self_attention_supported(x, wq, heads, masked=tail, long=long, causal=causal) and wq._shape == wk._shape == wv._shape and bq._shape == bk._shape == bv._shape == (wq._shape[0],), \
+        assert self_attention_supported(x, wq, heads, masked=tail, long=long, causal=causal, stream=stream) and wq._shape == wk._shape == wv._shape and bq._shape == bk._shape == bv._shape == (wq._shape[0],), \
             "self_attention: unsupported shapes %s with weights %s / %s / %s and %d heads" % (x._shape, wq._shape, wk._shape, wv._shape, heads)
-        form = "long" if long else "masked" if tail else "plain"
+        form = "stream" if stream else "long" if long else "masked" if tail else "plain"
         b, s, hidden = x._shape
         width = wq._shape[0]
         x = x.contiguous()
@@ -216,9 +298,17 @@ class self_attention(Function):
         _l.check(_l.lib().lg_gemm_multi3_f32(0, 1, b * s, width, hidden, x.ptr, hidden, _ptr3(*(w.ptr for w in ws)), hidden,
                                              _ptr3(base, base + 4 * width, base + 8 * width), 3 * width, _ptr3(*(t.ptr for t in bs))))
         out = HipTensor.empty((b, s, width))
-        probs = HipTensor.empty((b, heads, s, s), requires_grad=False)
         ld, sb = 3 * width, s * 3 * width
         mask3 = _key_mask(mask, b, s, "self_attention")
+        if stream:
+            lse = _launch_stream_fwd((base, ld, sb), (base + 4 * width, ld, sb), (base + 8 * width, ld, sb), out, (b, heads, s, width // heads),
+                                     float(scale), mask3, bool(causal))
+            # where the stored-P forms keep the probabilities: what the streaming backward needs in their place
+            ctx.save_for_backward(x, qkv, (_untaped(out), lse, mask3, bool(causal)), heads, float(scale), form, dropout, None)
+            out.attention_lse, out.attention_probs = lse, None
+            out.attention_qkv = qkv
+            return out
+        probs = HipTensor.empty((b, heads, s, s), requires_grad=False)
         drop_base = _launch_attention_fwd(form, (base, ld, sb), (base + 4 * width, ld, sb), (base + 8 * width, ld, sb), out, probs,
                                           (b, heads, s, width // heads), float(scale), mask3, dropout, bool(causal))
         ctx.save_for_backward(x, qkv, probs, heads, float(scale), form, dropout, drop_base)
@@ -236,9 +326,15 @@ class self_attention(Function):
         dqkv = HipTensor.empty((b, s, 3 * width), requires_grad=False)
         base, dbase = qkv.ptr, dqkv.ptr
         ld, sb = 3 * width, s * 3 * width
-        _launch_attention_bwd(form, (base, ld, sb), (base + 4 * width, ld, sb), (base + 8 * width, ld, sb), (g.ptr, ldg, sbg), probs,
-                              (dbase, ld, sb), (dbase + 4 * width, ld, sb), (dbase + 8 * width, ld, sb),
-                              (b, heads, s, width // heads), scale, dropout, drop_base)
+        if form == "stream":
+            out, lse, mask3, causal = probs
+            _launch_stream_bwd((base, ld, sb), (base + 4 * width, ld, sb), (base + 8 * width, ld, sb), out, (g.ptr, ldg, sbg), lse,
+                               (dbase, ld, sb), (dbase + 4 * width, ld, sb), (dbase + 8 * width, ld, sb),
+                               (b, heads, s, width // heads), scale, mask3, causal)
+        else:
+            _launch_attention_bwd(form, (base, ld, sb), (base + 4 * width, ld, sb), (base + 8 * width, ld, sb), (g.ptr, ldg, sbg), probs,
+                                  (dbase, ld, sb), (dbase + 4 * width, ld, sb), (dbase + 8 * width, ld, sb),
+                                  (b, heads, s, width // heads), scale, dropout, drop_base)
         x2 = x.reshape(-1, hidden)
         grads = []
         for i in range(3):
