@@ -30,6 +30,10 @@ Differences from the reference, on purpose:
                                                        # the causal forward, then one token per step against the cache - on HipTensor
                                                        # two launches of attention per layer (csrc/decode.hip), nothing read back until
                                                        # the ids are printed; --graph: the step is captured once and replayed
+    python examples/bert.py --generate 16 --no-attention-probs --prompt-length 2000 --positions 2048 [--graph]
+                                                       # a prompt beyond 512 tokens (--prompt-length, default 8) in a model of
+                                                       # --positions position embeddings: prefilled by the streaming attention node,
+                                                       # decoded by the split-key launch (csrc/decode_split.hip, caches to 16384 rows)
     python examples/bert.py --generate 16 --sample [--temperature T] [--top-k K] [--top-p P] [--seed S] [--graph] [--cpu]
                                                        # sampled decoding: every token is `logits.sample(T, K, P)` - one launch
                                                        # (csrc/sample.hip) in place of argmax + astype, drawn from the random stream
@@ -204,6 +208,14 @@ class BertSelfAttention(nn.Module):
             extra = {"mask": attention_mask} if attention_mask is not None else {}
             context = hidden.self_attention_decode(self.query.weight, self.query.bias, self.key.weight, self.key.bias, self.value.weight,
                                                    self.value.bias, k_cache, v_cache, cache.pos, heads=self.h, scale=scale, **extra)
+            return context, None
+        if hasattr(hidden, "self_attention_decode") and mask_ok and \
+                hidden.self_attention_decode_supported(self.query.weight, self.h, cache.capacity, split=True):
+            # a cache beyond the 512 rows of that launch (what a prefill through the streaming node fills): the split-key launch,
+            # the keys of a sequence over workgroups of 256 and merged inside the launch - one-word and per-row positions alike
+            extra = {"mask": attention_mask} if attention_mask is not None else {}
+            context = hidden.self_attention_decode(self.query.weight, self.query.bias, self.key.weight, self.key.bias, self.value.weight,
+                                                   self.value.bias, k_cache, v_cache, cache.pos, heads=self.h, scale=scale, split=True, **extra)
             return context, None
         if getattr(cache, "per_row", False):
             return self._rows_composite(hidden, attention_mask, cache, index)
@@ -1698,8 +1710,15 @@ if __name__ == "__main__":
         n_new = int(sys.argv[sys.argv.index("--generate") + 1])
         batch = int(sys.argv[sys.argv.index("--batch") + 1]) if "--batch" in sys.argv else 2
         np.random.seed(0)
-        lm = BertForMaskedLM(**dict(TINY, causal=True)).eval()
-        prompt = light.from_numpy(np.random.randint(0, TINY["vocab_size"], (batch, 8)).astype(np.int32), requires_grad=False)
+        # --prompt-length P (default 8) and --positions M (the model's position embeddings, default TINY's 512): with
+        # --no-attention-probs a prompt beyond 512 tokens is prefilled by the streaming attention node and decoded by the split-key
+        # launch (csrc/decode_split.hip) - `--generate 16 --no-attention-probs --prompt-length 2000 --positions 2048`
+        prompt_length = int(sys.argv[sys.argv.index("--prompt-length") + 1]) if "--prompt-length" in sys.argv else 8
+        long_config = {"max_position_embeddings": int(sys.argv[sys.argv.index("--positions") + 1])} if "--positions" in sys.argv else {}
+        if "--no-attention-probs" in sys.argv:
+            long_config["attention_probs"] = False
+        lm = BertForMaskedLM(**dict(TINY, causal=True, **long_config)).eval()
+        prompt = light.from_numpy(np.random.randint(0, TINY["vocab_size"], (batch, prompt_length)).astype(np.int32), requires_grad=False)
         if not cpu:
             lm.map_parameters(lambda t: t.hip())
             prompt = prompt.hip(requires_grad=False)
@@ -1720,7 +1739,7 @@ if __name__ == "__main__":
             pieces = {}
         if "--ragged" in sys.argv:
             # prompts of 8, 7, 6, .. tokens (at least 1): what lies behind a row's length is padding that nothing reads
-            row_lengths = [max(1, 8 - r) for r in range(batch)]
+            row_lengths = [max(1, prompt_length - r) for r in range(batch)]
             pieces = dict(pieces, lengths=row_lengths, eos_token_id=int(sys.argv[sys.argv.index("--eos") + 1]) if "--eos" in sys.argv else None)
             print("ragged batch: prompts of %s tokens%s" % (row_lengths, ", stopping at id %d" % pieces["eos_token_id"] if "--eos" in sys.argv else ""))
         counters = {}
@@ -1747,7 +1766,7 @@ if __name__ == "__main__":
             "decode step captured once, %d kernels, replayed %d times" % (recorded.kernel_count(), counters.get("steps", n_new - 1)) if recorded
             else "eager decode steps"))
         for r, row in enumerate(new_ids):
-            print(" ".join(str(i) for i in row[pieces["lengths"][r] if "lengths" in pieces else 8:]))
+            print(" ".join(str(i) for i in row[pieces["lengths"][r] if "lengths" in pieces else prompt_length:]))
         sys.exit(0)
     if "--mlm" in sys.argv:
         light.manual_seed(0)

@@ -672,6 +672,34 @@ int lg_attention_decode_f32(const float* q, int64_t sbq,             /* the new 
                             int64_t batch, int64_t heads, int64_t capacity, int64_t D, float scale,
                             const float* mask, int64_t sbm);         /* key-padding mask over the capacity; NULL = none */
 
+/* ---- the same against a cache of up to 16384 rows, the keys split over workgroups (csrc/decode_split.hip) ------
+ * lg_attention_decode_split_f32 takes the operands of lg_attention_decode_f32 (same pitches and alignment rules, `pos` one word
+ * in device memory) with ONE difference: in place of p, `lse` - NULL, or a dense (batch, heads) tensor that receives
+ * log sum_{j <= t} exp(score_j).  No probabilities are returned.  The grid is (ceil(capacity / L), heads, batch) with L =
+ * lg_attention_decode_split_slice() keys per workgroup; workgroups whose keys lie beyond t return before any load; the partial
+ * softmaxes {max, sum, unnormalised context} of a pair's live workgroups are merged inside the launch by the last of them to
+ * arrive (a per-launch workspace, the runtime's ticket pool; every ticket is zero again when the launch ends).  Every fold runs
+ * in a fixed order: the same bits every run, whoever arrives last, and a batch element's bits are those it has alone.  Row t is
+ * taken from k_new / v_new and written to the caches by the workgroup that owns it; rows j > t are neither read nor written.
+ * t < 0 or t >= capacity: nothing is written for that batch element and the device status flag is raised (LG_EINDEX at the
+ * next lg_sync / lg_memcpy_d2h).  lg_attention_decode_split_rows_f32: `pos` points to `batch` contiguous words, element b uses
+ * t = pos[b]; an element out of range writes nothing, the others are computed.  Supported: D = 32 or 64, 1 <= capacity <= 16384
+ * (lg_attention_decode_split_supported, pure host code: the range of lg_attention_stream_supported).  Checked in this order,
+ * each LG_EINVAL, before anything is launched: D / capacity; a pitch that is no multiple of 4 or a base that is not 16-byte
+ * aligned; ldc < heads * D; a mask with 0 < sbm < capacity; pos overlapping a cache; batch * heads beyond the ticket pool. */
+int lg_attention_decode_split_supported(int64_t capacity, int64_t D);
+int lg_attention_decode_split_slice(void);
+int lg_attention_decode_split_f32(const float* q, int64_t sbq, const float* k_new, int64_t sbk, const float* v_new, int64_t sbv,
+                                  float* k_cache, float* v_cache, int64_t ldc, int64_t sbc, const int32_t* pos, float* o, int64_t sbo,
+                                  float* lse,                        /* NULL, or log-sum-exp (batch, heads), dense */
+                                  int64_t batch, int64_t heads, int64_t capacity, int64_t D, float scale,
+                                  const float* mask, int64_t sbm);
+int lg_attention_decode_split_rows_f32(const float* q, int64_t sbq, const float* k_new, int64_t sbk, const float* v_new, int64_t sbv,
+                                       float* k_cache, float* v_cache, int64_t ldc, int64_t sbc,
+                                       const int32_t* pos,           /* `batch` words in device memory: the position of each new token */
+                                       float* o, int64_t sbo, float* lse, int64_t batch, int64_t heads, int64_t capacity, int64_t D,
+                                       float scale, const float* mask, int64_t sbm);
+
 /* ---- attention of m NEW tokens against a filled key / value cache (csrc/extend.hip) --------------------------
  * Appending to a cache that already holds t = *pos tokens (a second prompt, a prompt prefilled in pieces, a continuation to
  * score, drafted tokens to verify): t is read BY THE KERNEL from one word in device memory, m is a host argument, and

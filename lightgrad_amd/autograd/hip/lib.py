@@ -161,6 +161,12 @@ PROTOTYPES = {
                                 + [c_void_p] + [c_int64] * 4 + [c_float] + [c_void_p, c_int64]),
     "lg_attention_decode_rows_f32": (c_int, [c_void_p, c_int64] * 3 + [c_void_p, c_void_p, c_int64, c_int64] + [c_void_p] + [c_void_p, c_int64]
                                      + [c_void_p] + [c_int64] * 4 + [c_float] + [c_void_p, c_int64]),
+    "lg_attention_decode_split_supported": (c_int, [c_int64, c_int64]),
+    "lg_attention_decode_split_slice": (c_int, []),
+    "lg_attention_decode_split_f32": (c_int, [c_void_p, c_int64] * 3 + [c_void_p, c_void_p, c_int64, c_int64] + [c_void_p] + [c_void_p, c_int64]
+                                      + [c_void_p] + [c_int64] * 4 + [c_float] + [c_void_p, c_int64]),
+    "lg_attention_decode_split_rows_f32": (c_int, [c_void_p, c_int64] * 3 + [c_void_p, c_void_p, c_int64, c_int64] + [c_void_p] + [c_void_p, c_int64]
+                                           + [c_void_p] + [c_int64] * 4 + [c_float] + [c_void_p, c_int64]),
     "lg_attention_extend_supported": (c_int, [c_int64, c_int64, c_int64]),
     "lg_attention_extend_f32": (c_int, [c_void_p, c_int64, c_int64] * 3 + [c_void_p, c_void_p, c_int64, c_int64] + [c_void_p]
                                 + [c_void_p, c_int64, c_int64] + [c_void_p] + [c_int64] * 5 + [c_float] + [c_void_p, c_int64]),

@@ -11,7 +11,8 @@ the predicate accepts, a log-sum-exp per row on the result, its own forward and 
 `_launch_stream_fwd` / `_launch_stream_bwd`).
 
 `decode_attention` / `self_attention_decode` are the inference ops of incremental decoding: one new token against a key / value
-cache, over lg_attention_decode_f32 (csrc/decode.hip).  They share nothing with the forms above and stay outside the tape.
+cache, over lg_attention_decode_f32 (csrc/decode.hip) or, with `split=True`, the split-key launch for caches of up to 16384 rows
+(lg_attention_decode_split_f32, csrc/decode_split.hip).  They share nothing with the forms above and stay outside the tape.
 """
 import ctypes
 import numpy as np
@@ -439,29 +440,44 @@ def _positions(pos, b):
     return (pos if pos._strides[0] == 1 else pos.contiguous()), True
 
 
-def _launch_decode(name, q2, k2, v2, k_cache, v_cache, pos, out, heads, scale, mask, probs):
-    """q2, k2, v2: (address, batch pitch); out: (b, ..., width) dense.  Returns the probabilities (b, heads, 1, capacity) or None"""
+def _launch_decode(name, q2, k2, v2, k_cache, v_cache, pos, out, heads, scale, mask, probs, split=False, lse=False):
+    """q2, k2, v2: (address, batch pitch); out: (b, ..., width) dense.  Returns the probabilities (b, heads, 1, capacity) or None;
+    split=True (csrc/decode_split.hip): the log-sum-exp (b, heads) or None in their place"""
     b, capacity, width = k_cache._shape
     mask3 = _key_mask(mask, b, capacity, name)
-    p = HipTensor.empty((b, heads, 1, capacity), requires_grad=False) if probs else None
+    if split:
+        extra = HipTensor.empty((b, heads), requires_grad=False) if lse else None
+    else:
+        extra = HipTensor.empty((b, heads, 1, capacity), requires_grad=False) if probs else None
     flush_lazy_readers(k_cache)
     flush_lazy_readers(v_cache)
     pos, per_row = _positions(pos, b)
-    entry = _l.lib().lg_attention_decode_rows_f32 if per_row else _l.lib().lg_attention_decode_f32
+    entry = getattr(_l.lib(), "lg_attention_decode%s%s_f32" % ("_split" if split else "", "_rows" if per_row else ""))
     _l.check(entry(*q2, *k2, *v2, k_cache.ptr, v_cache.ptr, k_cache._strides[1], k_cache._strides[0], pos.ptr,
-                   out.ptr, width, p.ptr if probs else None, b, heads, capacity, width // heads, float(scale), mask3[1], mask3[2]))
-    return p
+                   out.ptr, width, extra.ptr if extra is not None else None, b, heads, capacity, width // heads, float(scale), mask3[1], mask3[2]))
+    return extra
 
 
-def decode_attention_supported(q, heads, capacity):
+def _decode_fits(capacity, d, split):
+    """the 512-row launch of csrc/decode.hip, or with split=True the split-key launch of csrc/decode_split.hip (1 .. 16384 rows)"""
+    return bool((_l.lib().lg_attention_decode_split_supported if split else _l.lib().lg_attention_decode_supported)(capacity, d))
+
+
+def _split_options(name, probs, split, lse):
+    assert not (split and probs), "%s: probs=True with split=True (the split-key launch returns a log-sum-exp, lse=True, never probabilities)" % name
+    assert split or not lse, "%s: lse=True needs split=True (the 512-row launch returns probabilities, probs=True)" % name
+
+
+def decode_attention_supported(q, heads, capacity, split=False):
     """does `q.decode_attention(k_new, v_new, k_cache, v_cache, pos, heads, scale)` exist for this shape?  (b, 1, heads * d) or
-    (b, heads * d) float32 with d = 32 or 64, b >= 1 and a cache of 1 .. 512 rows"""
+    (b, heads * d) float32 with d = 32 or 64, b >= 1 and a cache of 1 .. 512 rows.  split=True: the question of
+    `decode_attention(..., split=True)` - a cache of 1 .. 16384 rows"""
     sh = q._shape
     return (len(sh) in (2, 3) and (len(sh) == 2 or sh[1] == 1) and q._dtype == _F32 and sh[0] > 0 and sh[-1] % heads == 0
-            and bool(_l.lib().lg_attention_decode_supported(capacity, sh[-1] // heads)))
+            and _decode_fits(capacity, sh[-1] // heads, split))
 
 
-def decode_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False):
+def decode_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False, split=False, lse=False):
     """ attention of ONE new token per sequence against a key / value cache, one launch (lg_attention_decode_f32): with t = the
     int32 word `pos` holds ON THE DEVICE (`pos` of shape (b,): a position per sequence, t = pos[r] for sequence r, everything
     below per sequence - lg_attention_decode_rows_f32; a sequence whose position is outside the cache writes nothing, the others
@@ -470,29 +486,37 @@ def decode_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0,
     q, k_new, v_new: (b, 1, width) or (b, width); slices of one (b, 1, 3 * width) projection buffer are read in place.  mask:
     float32 (b, capacity) or (1, capacity) over the cache's rows, None for none.  probs=True: `.attention_probs` (b, heads, 1,
     capacity), exact zeros beyond t.  A position outside the cache writes nothing and raises IndexError at the next
-    synchronisation.  An inference op: the result is outside the tape. """
+    synchronisation.  An inference op: the result is outside the tape.
+    split=True: the split-key launch (lg_attention_decode_split_f32 / _rows_f32, csrc/decode_split.hip) - caches of 1 .. 16384
+    rows, the keys of a sequence spread over workgroups of 256 keys and merged inside the launch.  It returns no probabilities
+    (probs=True is refused); lse=True: `.attention_lse` (b, heads), the log of the sum of the exponentials of the scores 0 .. t. """
     name = "decode_attention"
+    _split_options(name, probs, split, lse)
     _inference_only(name, q, k_new, v_new)
     _require_f32(q, k_new, v_new)
-    assert q._shape == k_new._shape == v_new._shape and decode_attention_supported(q, heads, k_cache._shape[1] if len(k_cache._shape) == 3 else 0), \
+    assert q._shape == k_new._shape == v_new._shape and decode_attention_supported(q, heads, k_cache._shape[1] if len(k_cache._shape) == 3 else 0, split=split), \
         "%s: unsupported shapes %s / %s / %s with %d heads and caches %s" % (name, q._shape, k_new._shape, v_new._shape, heads, k_cache._shape)
     _check_cache(name, k_cache, v_cache, pos, q._shape[0], q._shape[-1])
     (q, sbq), (k_new, sbk), (v_new, sbv) = _token_row(q, name), _token_row(k_new, name), _token_row(v_new, name)
     out = HipTensor.empty(q._shape, requires_grad=False)
-    p = _launch_decode(name, (q.ptr, sbq), (k_new.ptr, sbk), (v_new.ptr, sbv), k_cache, v_cache, pos, out, heads, scale, mask, probs)
+    p = _launch_decode(name, (q.ptr, sbq), (k_new.ptr, sbk), (v_new.ptr, sbv), k_cache, v_cache, pos, out, heads, scale, mask, probs, split, lse)
     if probs:
         out.attention_probs = p
+    if lse:
+        out.attention_lse = p
     return out
 
 
-def self_attention_decode(x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False):
+def self_attention_decode(x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False, split=False,
+                          lse=False):
     """ the one-node form of a decode step's attention: the three projections of the new token in ONE launch (lg_gemm_multi3_f32,
     as in `self_attention`) into a (b, 1, 3 * width) buffer that the decode launch reads in place - two launches per layer.
-    x: (b, 1, hidden); everything else as for `decode_attention`. """
+    x: (b, 1, hidden); everything else, `split` and `lse` included, as for `decode_attention`. """
     name = "self_attention_decode"
+    _split_options(name, probs, split, lse)
     _inference_only(name, x, wq, bq, wk, bk, wv, bv)
     _require_f32(x, wq, bq, wk, bk, wv, bv)
-    assert self_attention_decode_supported(x, wq, heads, k_cache._shape[1] if len(k_cache._shape) == 3 else 0) and \
+    assert self_attention_decode_supported(x, wq, heads, k_cache._shape[1] if len(k_cache._shape) == 3 else 0, split=split) and \
         wq._shape == wk._shape == wv._shape and bq._shape == bk._shape == bv._shape == (wq._shape[0],), \
         "%s: unsupported shapes %s with weights %s / %s / %s, %d heads and caches %s" % (name, x._shape, wq._shape, wk._shape, wv._shape, heads, k_cache._shape)
     b, _, hidden = x._shape
@@ -506,18 +530,22 @@ def self_attention_decode(x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, head
                                          _ptr3(base, base + 4 * width, base + 8 * width), 3 * width, _ptr3(*(t.ptr for t in bs))))
     out = HipTensor.empty((b, 1, width), requires_grad=False)
     sb = 3 * width
-    p = _launch_decode(name, (base, sb), (base + 4 * width, sb), (base + 8 * width, sb), k_cache, v_cache, pos, out, heads, scale, mask, probs)
+    p = _launch_decode(name, (base, sb), (base + 4 * width, sb), (base + 8 * width, sb), k_cache, v_cache, pos, out, heads, scale, mask, probs,
+                       split, lse)
     if probs:
         out.attention_probs = p
+    if lse:
+        out.attention_lse = p
     return out
 
 
-def self_attention_decode_supported(x, wq, heads, capacity):
+def self_attention_decode_supported(x, wq, heads, capacity, split=False):
     """does `x.self_attention_decode(...)` exist for these shapes?  (b, 1, hidden) input, (width, hidden) weights with width =
-    heads * d, d = 32 or 64, width a multiple of 64, a cache of 1 .. 512 rows"""
+    heads * d, d = 32 or 64, width a multiple of 64, a cache of 1 .. 512 rows (split=True: of 1 .. 16384 rows, the question of
+    `self_attention_decode(..., split=True)`)"""
     return (len(x._shape) == 3 and x._shape[1] == 1 and x._dtype == _F32 and len(wq._shape) == 2 and wq._shape[1] == x._shape[2]
             and wq._shape[0] % heads == 0 and wq._shape[0] % 64 == 0 and x._shape[2] % 4 == 0 and x._shape[0] > 0
-            and bool(_l.lib().lg_attention_decode_supported(capacity, wq._shape[0] // heads)))
+            and _decode_fits(capacity, wq._shape[0] // heads, split))
 
 
 HipTensor.decode_attention, HipTensor.decode_attention_supported = decode_attention, decode_attention_supported
