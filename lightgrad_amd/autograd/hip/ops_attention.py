@@ -432,25 +432,38 @@ def _shares_bytes(x, y):
     return a0 < b1 and b0 < a1
 
 
+def _dense_words(t, n):
+    """the n int32 words of a (n,) operand (pos, count) as a launch reads them: one word apart"""
+    return t if n == 1 or t._strides[0] == 1 else t.contiguous()
+
+
 def _positions(pos, b):
     """(contiguous tensor, per-row?) of the position operand: one word keeps the one-word entry - at batch 1 the two mean the same -,
     (batch,) words take the `_rows` entry"""
     if pos.numel() == 1 or b == 1:
         return pos, False
-    return (pos if pos._strides[0] == 1 else pos.contiguous()), True
+    return _dense_words(pos, b), True
+
+
+def _cache_launch(name, mask, rows, capacity, k_cache, v_cache, extra_shape):
+    """what every launch against a cache starts with: (mask triple of `_key_mask`, the optional extra output - probabilities or
+    log-sum-exp - of extra_shape, None for none), and nothing lazy left reading the caches (or pools) the launch writes"""
+    mask3 = _key_mask(mask, rows, capacity, name)
+    extra = HipTensor.empty(extra_shape, requires_grad=False) if extra_shape is not None else None
+    flush_lazy_readers(k_cache)
+    flush_lazy_readers(v_cache)
+    return mask3, extra
 
 
 def _launch_decode(name, q2, k2, v2, k_cache, v_cache, pos, out, heads, scale, mask, probs, split=False, lse=False):
     """q2, k2, v2: (address, batch pitch); out: (b, ..., width) dense.  Returns the probabilities (b, heads, 1, capacity) or None;
     split=True (csrc/decode_split.hip): the log-sum-exp (b, heads) or None in their place"""
     b, capacity, width = k_cache._shape
-    mask3 = _key_mask(mask, b, capacity, name)
     if split:
-        extra = HipTensor.empty((b, heads), requires_grad=False) if lse else None
+        shape = (b, heads) if lse else None
     else:
-        extra = HipTensor.empty((b, heads, 1, capacity), requires_grad=False) if probs else None
-    flush_lazy_readers(k_cache)
-    flush_lazy_readers(v_cache)
+        shape = (b, heads, 1, capacity) if probs else None
+    mask3, extra = _cache_launch(name, mask, b, capacity, k_cache, v_cache, shape)
     pos, per_row = _positions(pos, b)
     entry = getattr(_l.lib(), "lg_attention_decode%s%s_f32" % ("_split" if split else "", "_rows" if per_row else ""))
     _l.check(entry(*q2, *k2, *v2, k_cache.ptr, v_cache.ptr, k_cache._strides[1], k_cache._strides[0], pos.ptr,
@@ -575,7 +588,7 @@ def _token_counts(name, count, pos, b, k_cache, v_cache):
             name, b, getattr(count, "_dtype", type(count).__name__), getattr(count, "_shape", ""), pos._shape)
     for other in (k_cache, v_cache, pos):
         assert not _shares_bytes(count, other), "%s: count overlaps a cache or pos" % name
-    return count if b == 1 or count._strides[0] == 1 else count.contiguous()
+    return _dense_words(count, b)
 
 
 def _launch_extend(name, q3, k3, v3, m, k_cache, v_cache, pos, out, heads, scale, mask, probs, count=None):
@@ -583,13 +596,10 @@ def _launch_extend(name, q3, k3, v3, m, k_cache, v_cache, pos, out, heads, scale
     b, capacity, width = k_cache._shape
     if count is not None:
         count = _token_counts(name, count, pos, b, k_cache, v_cache)
-    mask3 = _key_mask(mask, b, capacity, name)
-    p = HipTensor.empty((b, heads, m, capacity), requires_grad=False) if probs else None
-    flush_lazy_readers(k_cache)
-    flush_lazy_readers(v_cache)
+    mask3, p = _cache_launch(name, mask, b, capacity, k_cache, v_cache, (b, heads, m, capacity) if probs else None)
     if count is not None:
         # a token count per sequence next to its position: the counts entry, at any batch
-        pos = pos if b == 1 or pos._strides[0] == 1 else pos.contiguous()
+        pos = _dense_words(pos, b)
         entry, words = _l.lib().lg_attention_extend_counts_f32, (pos.ptr, count.ptr)
     else:
         pos, per_row = _positions(pos, b)
@@ -619,11 +629,8 @@ def _launch_extend_packed(name, q2, k2, v2, T, k_cache, v_cache, pos, cu, m_max,
     """q2, k2, v2: (address, row pitch) of flat (T, width) rows; out: (1, T, width) dense.  Returns the probabilities
     (heads, T, capacity) or None"""
     slots, capacity, width = k_cache._shape
-    mask3 = _key_mask(mask, slots, capacity, name)
-    p = HipTensor.empty((heads, T, capacity), requires_grad=False) if probs else None
-    flush_lazy_readers(k_cache)
-    flush_lazy_readers(v_cache)
-    pos = pos if slots == 1 or pos._strides[0] == 1 else pos.contiguous()
+    mask3, p = _cache_launch(name, mask, slots, capacity, k_cache, v_cache, (heads, T, capacity) if probs else None)
+    pos = _dense_words(pos, slots)
     _l.check(_l.lib().lg_attention_extend_packed_f32(*q2, *k2, *v2, k_cache.ptr, v_cache.ptr, k_cache._strides[1], k_cache._strides[0], pos.ptr, cu.ptr,
                                                      out.ptr, width, p.ptr if probs else None, slots, heads, T, m_max, capacity, width // heads,
                                                      float(scale), mask3[1], mask3[2]))
@@ -679,12 +686,8 @@ def _launch_extend_paged(name, q3, k3, v3, m, k_pool, v_pool, pos, count, block_
     b, max_blocks = block_table._shape
     num_blocks, _, width = k_pool._shape
     capacity = max_blocks * B
-    count = count if b == 1 or count._strides[0] == 1 else count.contiguous()
-    pos = pos if b == 1 or pos._strides[0] == 1 else pos.contiguous()
-    mask3 = _key_mask(mask, b, capacity, name)
-    p = HipTensor.empty((b, heads, m, capacity), requires_grad=False) if probs else None
-    flush_lazy_readers(k_pool)
-    flush_lazy_readers(v_pool)
+    count, pos = _dense_words(count, b), _dense_words(pos, b)
+    mask3, p = _cache_launch(name, mask, b, capacity, k_pool, v_pool, (b, heads, m, capacity) if probs else None)
     entry = _l.lib().lg_attention_extend_paged_bf16_f32 if k_pool._dtype == _I16 else _l.lib().lg_attention_extend_paged_f32
     _l.check(entry(*q3, *k3, *v3, k_pool.ptr, v_pool.ptr, k_pool._strides[1], pos.ptr, count.ptr, block_table.ptr,
                    out.ptr, width, m * width, p.ptr if probs else None, b, heads, m, max_blocks, num_blocks,

@@ -25,12 +25,12 @@
 // Every fold has a fixed order and depends on t, D and the (batch, head) pair's own data only: the same bits from run to run
 // and whatever else the launch computes.  Registers: q, k_new, v_new chunks (3 float4), kUnroll float4 of K and kUnroll of V in
 // flight, one float4 accumulator.  LDS: 512 + 4 * 64 + 8 floats, static.
-#include "common.h"
+// The lane folds (wave_max, wave_sum, row_sum) are decode_lanes.h's, the host checks cache_entry.h's: both shared with decode_split.hip.
+#include "cache_entry.h"
+#include "decode_lanes.h"
 #include <cmath>
 
 namespace lg {
-
-typedef float df32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kDecodeMaxKeys = 512;
 constexpr int kDecodeUnroll = 16;
@@ -51,36 +51,6 @@ struct DecodeArgs {
     int64_t sbm;
     int* status;
 };
-
-__device__ __forceinline__ float wave_max(float m) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const float o = __shfl_xor(m, off, 64); m = (o > m || o != o) ? o : m; }
-    return m;
-}
-
-__device__ __forceinline__ float wave_sum(float s) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) s += __shfl_xor(s, off, 64);
-    return s;
-}
-
-// the sum over the G = 8 or 16 neighbouring lanes of a key row, in every one of them: the xor butterfly 1, 2, 4 (, 8) as data-parallel
-// moves inside a row of 16 lanes - after the two quad steps the lanes of a quad agree, so mirroring 8 (then 16) lanes brings each
-// the other quad's (then the other half's) sum.  Same pairs, same order, same bits as __shfl_xor, without its trips through LDS:
-// with one key per lane group and pass, these folds - not the loads - were what a lane waited for
-template <int CTRL>
-__device__ __forceinline__ float lane_move(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
-}
-
-template <int G>
-__device__ __forceinline__ float row_sum(float s) {
-    s += lane_move<0xB1>(s);                 // quad_perm [1, 0, 3, 2]: lane ^ 1
-    s += lane_move<0x4E>(s);                 // quad_perm [2, 3, 0, 1]: lane ^ 2
-    s += lane_move<0x141>(s);                // row_half_mirror: the other quad of 8 lanes
-    if constexpr (G == 16) s += lane_move<0x140>(s);      // row_mirror: the other half of 16 lanes
-    return s;
-}
 
 // rows j0, j0 + KP, ... of a cache (this lane's chunk) for one group of passes: below t from the cache, at t the new token's
 template <int KP>
@@ -207,53 +177,23 @@ __global__ __launch_bounds__(256) void attn_decode(const DecodeArgs a) {
     }
 }
 
-static bool decode_operand(const void* p, int64_t sb) { return p && aligned16(p) && sb % 4 == 0; }
-
-// do the `words` position words share an address with the floats [c, c + (batch - 1) sbc + (capacity - 1) ldc + w) of a cache?
-static bool positions_overlap(const int32_t* pos, int64_t words, const float* c, int64_t ldc, int64_t sbc, int64_t capacity, int64_t batch, int64_t w) {
-    const char *x = reinterpret_cast<const char*>(pos), *xe = x + 4 * words;
-    const char *y = reinterpret_cast<const char*>(c), *ye = reinterpret_cast<const char*>(c + (batch - 1) * sbc + (capacity - 1) * ldc + w);
-    return x < ye && y < xe;
-}
-
 }  // namespace lg
 
 using namespace lg;
 
 extern "C" int lg_attention_decode_supported(int64_t capacity, int64_t D) {
-    return (D == 32 || D == 64) && capacity >= 1 && capacity <= kDecodeMaxKeys;
+    return cache_head_dim(D) && capacity >= 1 && capacity <= kDecodeMaxKeys;
 }
 
 // both entries: `pos_pitch` words between the positions of neighbouring batch elements (0: one word for the batch)
 static int decode_entry(const char* name, int64_t pos_pitch, const float* q, int64_t sbq, const float* k_new, int64_t sbk, const float* v_new,
                         int64_t sbv, float* k_cache, float* v_cache, int64_t ldc, int64_t sbc, const int32_t* pos, float* o, int64_t sbo,
                         float* p, int64_t batch, int64_t heads, int64_t capacity, int64_t D, float scale, const float* mask, int64_t sbm) {
-    LG_ARG(lg_attention_decode_supported(capacity, D), "%s: capacity = %lld (1 .. 512), D = %lld (32 or 64) unsupported", name,
-           (long long)capacity, (long long)D);
-    LG_ARG(batch >= 0 && heads >= 1 && batch <= 65535 && heads <= 65535, "%s: bad batch / heads", name);
-    if (batch == 0) return LG_OK;
-    LG_ARG(decode_operand(q, sbq) && decode_operand(k_new, sbk) && decode_operand(v_new, sbv) && decode_operand(k_cache, sbc) &&
-               decode_operand(v_cache, sbc) && decode_operand(o, sbo) && ldc % 4 == 0 && pos && (reinterpret_cast<uintptr_t>(pos) & 3u) == 0 &&
-               (reinterpret_cast<uintptr_t>(p) & 3u) == 0,
-           "%s: operands must be non-NULL and 16-byte aligned with pitches that are multiples of 4", name);
-    const int64_t w = heads * D;
-    LG_ARG(ldc >= w, "%s: cache row pitch %lld below heads * D = %lld", name, (long long)ldc, (long long)w);
-    LG_ARG(!mask || sbm == 0 || sbm >= capacity, "%s: mask batch pitch %lld is neither 0 (one row for the batch) nor >= capacity", name,
-           (long long)sbm);
-    LG_ARG(!positions_overlap(pos, pos_pitch ? batch : 1, k_cache, ldc, sbc, capacity, batch, w) &&
-               !positions_overlap(pos, pos_pitch ? batch : 1, v_cache, ldc, sbc, capacity, batch, w),
-           "%s: pos overlaps a cache: the launch writes the caches while other workgroups read their positions", name);
-    {
-        const int64_t row[2] = {batch, w}, row_strides[2] = {sbo, 1};
-        int rc = adam_epilogue_check_strided(o, 4, 2, row, row_strides);
-        if (rc != LG_OK) return rc;
-        const int64_t rows[3] = {batch, capacity, w}, strides[3] = {sbc, ldc, 1};
-        rc = adam_epilogue_check_strided(k_cache, 4, 3, rows, strides);
-        if (rc != LG_OK) return rc;
-        rc = adam_epilogue_check_strided(v_cache, 4, 3, rows, strides);
-        if (rc != LG_OK) return rc;
-        if (p) { rc = adam_epilogue_check_write(p, batch * heads * capacity * 4); if (rc != LG_OK) return rc; }
-    }
+    int rc = decode_check_operands(name, kDecodeMaxKeys, pos_pitch, q, sbq, k_new, sbk, v_new, sbv, k_cache, v_cache, ldc, sbc, pos, o, sbo, p, batch,
+                                   heads, capacity, D, mask, sbm);
+    if (rc != LG_OK || batch == 0) return rc;
+    rc = cache_check_writes(o, batch, sbo, 1, 0, k_cache, v_cache, 4, batch, sbc, capacity, ldc, heads * D, p, batch * heads * capacity * 4);
+    if (rc != LG_OK) return rc;
     const DecodeArgs a{q, k_new, v_new, sbq, sbk, sbv, k_cache, v_cache, ldc, sbc, pos, pos_pitch, o, sbo, p, int(heads), int(capacity), scale,
                        mask, sbm, rt().status_dev};
     const dim3 grid{unsigned(heads), unsigned(batch)};

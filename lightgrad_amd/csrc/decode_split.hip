@@ -33,13 +33,14 @@
 //
 // Registers: q, k_new, v_new chunks, U float4 of K and U of V in flight, U mask words, one float4 accumulator.  LDS: 256 + 256 +
 // 8 floats and the hand-off word, static.
-#include "common.h"
+// The lane folds (wave_max, wave_sum, row_sum) are decode_lanes.h's, the host checks cache_entry.h's: both shared with decode.hip;
+// the ticket pool's bound and the workspace around the launch are this file's own.
+#include "cache_entry.h"
+#include "decode_lanes.h"
 #include "handoff.h"
 #include <cmath>
 
 namespace lg {
-
-typedef float sf32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kSplitSlice = 256;                 // L: keys per workgroup, one load group for both head sizes
 constexpr int kSplitMaxKeys = 16384;             // the range of lg_attention_stream_supported
@@ -65,34 +66,6 @@ struct SplitArgs {
     int* status;
 };
 
-__device__ __forceinline__ float split_wave_max(float m) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const float o = __shfl_xor(m, off, 64); m = (o > m || o != o) ? o : m; }
-    return m;
-}
-
-__device__ __forceinline__ float split_wave_sum(float s) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) s += __shfl_xor(s, off, 64);
-    return s;
-}
-
-template <int CTRL>
-__device__ __forceinline__ float split_lane_move(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
-}
-
-// the sum over the G = 8 or 16 neighbouring lanes of a key row, in every one of them: the xor butterfly 1, 2, 4 (, 8) as
-// data-parallel moves inside a row of 16 lanes (the pairs and the order of decode.hip's row_sum)
-template <int G>
-__device__ __forceinline__ float split_row_sum(float s) {
-    s += split_lane_move<0xB1>(s);           // quad_perm [1, 0, 3, 2]: lane ^ 1
-    s += split_lane_move<0x4E>(s);           // quad_perm [2, 3, 0, 1]: lane ^ 2
-    s += split_lane_move<0x141>(s);          // row_half_mirror: the other quad of 8 lanes
-    if constexpr (G == 16) s += split_lane_move<0x140>(s);        // row_mirror: the other half of 16 lanes
-    return s;
-}
-
 template <int D>
 __global__ __launch_bounds__(256) void attn_decode_split(const SplitArgs a) {
     constexpr int L = kSplitSlice, G = D / 4, KW = 64 / G, KP = 4 * KW, U = L / KP;
@@ -116,9 +89,9 @@ __global__ __launch_bounds__(256) void attn_decode_split(const SplitArgs a) {
 
     const int wave = tid >> 6, lane = tid & 63, g = lane / G, c = lane % G;
     const int col = head * D + 4 * c;
-    const sf32x4 q4 = *reinterpret_cast<const sf32x4*>(a.q + int64_t(b) * a.sbq + col);
-    const sf32x4 kn = *reinterpret_cast<const sf32x4*>(a.k_new + int64_t(b) * a.sbk + col);
-    const sf32x4 vn = *reinterpret_cast<const sf32x4*>(a.v_new + int64_t(b) * a.sbv + col);
+    const df32x4 q4 = *reinterpret_cast<const df32x4*>(a.q + int64_t(b) * a.sbq + col);
+    const df32x4 kn = *reinterpret_cast<const df32x4*>(a.k_new + int64_t(b) * a.sbk + col);
+    const df32x4 vn = *reinterpret_cast<const df32x4*>(a.v_new + int64_t(b) * a.sbv + col);
     float* kc = a.k_cache + int64_t(b) * a.sbc + col;
     float* vc = a.v_cache + int64_t(b) * a.sbc + col;
     const float* mrow = a.mask ? a.mask + int64_t(b) * a.sbm : nullptr;
@@ -126,18 +99,18 @@ __global__ __launch_bounds__(256) void attn_decode_split(const SplitArgs a) {
 
     // row t of the caches, in the slice that holds it (L is a multiple of KP): the lanes that own key t hold its chunks already
     if (slice == live - 1 && first % KP == t % KP) {
-        *reinterpret_cast<sf32x4*>(kc + int64_t(t) * a.ldc) = kn;
-        *reinterpret_cast<sf32x4*>(vc + int64_t(t) * a.ldc) = vn;
+        *reinterpret_cast<df32x4*>(kc + int64_t(t) * a.ldc) = kn;
+        *reinterpret_cast<df32x4*>(vc + int64_t(t) * a.ldc) = vn;
     }
 
     // ---- the slice's K rows, mask words and V rows: everything in flight before the first use ------------------------------------
-    sf32x4 k4[U], v4[U];
+    df32x4 k4[U], v4[U];
     float mk[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const int j = j_lo + first + u * KP;
         k4[u] = kn;
-        if (j < t) k4[u] = *reinterpret_cast<const sf32x4*>(kc + int64_t(j) * a.ldc);
+        if (j < t) k4[u] = *reinterpret_cast<const df32x4*>(kc + int64_t(j) * a.ldc);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -149,14 +122,14 @@ __global__ __launch_bounds__(256) void attn_decode_split(const SplitArgs a) {
     for (int u = 0; u < U; ++u) {
         const int j = j_lo + first + u * KP;
         v4[u] = vn;
-        if (j < t) v4[u] = *reinterpret_cast<const sf32x4*>(vc + int64_t(j) * a.ldc);
+        if (j < t) v4[u] = *reinterpret_cast<const df32x4*>(vc + int64_t(j) * a.ldc);
     }
 
     // ---- scores ------------------------------------------------------------------------------------------------------------------
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const int i = first + u * KP;
-        const float s = split_row_sum<G>(((q4[0] * k4[u][0] + q4[1] * k4[u][1]) + q4[2] * k4[u][2]) + q4[3] * k4[u][3]);
+        const float s = row_sum<G>(((q4[0] * k4[u][0] + q4[1] * k4[u][1]) + q4[2] * k4[u][2]) + q4[3] * k4[u][3]);
         // (1.0 - mask) * -10000.0 in fp32, the composite's own arithmetic; -0.0f for a mask of 1 or none: it changes no bit
         if (c == 0 && j_lo + i <= t) Sc[i] = s * a.scale + (1.0f - mk[u]) * -10000.0f;
     }
@@ -165,7 +138,7 @@ __global__ __launch_bounds__(256) void attn_decode_split(const SplitArgs a) {
     // ---- the slice's softmax pieces: thread i owns key j_lo + i ------------------------------------------------------------------
     const bool mine = j_lo + tid <= t;
     const float x = mine ? Sc[tid] : -INFINITY;
-    float m = split_wave_max(x);
+    float m = wave_max(x);
     if (lane == 0) Red[wave] = m;
     __syncthreads();
     m = Red[0];
@@ -173,13 +146,13 @@ __global__ __launch_bounds__(256) void attn_decode_split(const SplitArgs a) {
     for (int w = 1; w < 4; ++w) { const float o = Red[w]; m = (o > m || o != o) ? o : m; }
     const float e = mine ? expf(x + (-m)) : 0.f;
     Sc[tid] = e;                             // (the thread's own word: nobody else reads it before the barrier)
-    float l = split_wave_sum(e);
+    float l = wave_sum(e);
     if (lane == 0) Red[4 + wave] = l;
     __syncthreads();
     l = ((Red[4] + Red[5]) + Red[6]) + Red[7];
 
     // ---- the unnormalised context of the slice -----------------------------------------------------------------------------------
-    sf32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    df32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const int i = first + u * KP;
@@ -194,7 +167,7 @@ __global__ __launch_bounds__(256) void attn_decode_split(const SplitArgs a) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) acc[k] += __shfl_xor(acc[k], off, 64);
     }
-    if (g == 0) *reinterpret_cast<sf32x4*>(&Part[wave * 64 + 4 * c]) = acc;
+    if (g == 0) *reinterpret_cast<df32x4*>(&Part[wave * 64 + 4 * c]) = acc;
     __syncthreads();
     float mine_a = 0.f;                      // thread d < D: column d of a_s, the waves in wave order
     if (tid < D) mine_a = ((Part[tid] + Part[64 + tid]) + Part[128 + tid]) + Part[192 + tid];
@@ -230,10 +203,10 @@ __global__ __launch_bounds__(256) void attn_decode_split(const SplitArgs a) {
     if (wave == 0) {
         float ms = -INFINITY, ls = 0.f;
         if (lane < live) { ms = handoff::fetch<float>(slots + int64_t(lane) * SW + D); ls = handoff::fetch<float>(slots + int64_t(lane) * SW + D + 1); }
-        const float M = split_wave_max(ms);
+        const float M = wave_max(ms);
         const float w = lane < live ? expf(ms + (-M)) : 0.f;     // a fully masked slice next to a visible one: +0
         Sc[lane] = w;
-        const float Lsum = split_wave_sum(w * ls);
+        const float Lsum = wave_sum(w * ls);
         if (lane == 0) { Red[0] = M; Red[1] = Lsum; }
     }
     __syncthreads();
@@ -254,20 +227,12 @@ __global__ __launch_bounds__(256) void attn_decode_split(const SplitArgs a) {
     if (tid == 0 && lse_out) *lse_out = Red[0] + logf(Red[1]);
 }
 
-static bool split_operand(const void* p, int64_t sb) { return p && aligned16(p) && sb % 4 == 0; }
-
-// do the `words` position words share an address with the floats [c, c + (batch - 1) sbc + (capacity - 1) ldc + w) of a cache?
-static bool split_positions_overlap(const int32_t* pos, int64_t words, const float* c, int64_t ldc, int64_t sbc, int64_t capacity, int64_t batch,
-                                    int64_t w) {
-    return bytes_overlap(pos, 4 * words, c, 4 * ((batch - 1) * sbc + (capacity - 1) * ldc + w));
-}
-
 }  // namespace lg
 
 using namespace lg;
 
 extern "C" int lg_attention_decode_split_supported(int64_t capacity, int64_t D) {
-    return (D == 32 || D == 64) && capacity >= 1 && capacity <= kSplitMaxKeys;
+    return cache_head_dim(D) && capacity >= 1 && capacity <= kSplitMaxKeys;
 }
 
 extern "C" int lg_attention_decode_split_slice(void) { return kSplitSlice; }
@@ -276,38 +241,17 @@ extern "C" int lg_attention_decode_split_slice(void) { return kSplitSlice; }
 static int split_entry(const char* name, int64_t pos_pitch, const float* q, int64_t sbq, const float* k_new, int64_t sbk, const float* v_new,
                        int64_t sbv, float* k_cache, float* v_cache, int64_t ldc, int64_t sbc, const int32_t* pos, float* o, int64_t sbo,
                        float* lse, int64_t batch, int64_t heads, int64_t capacity, int64_t D, float scale, const float* mask, int64_t sbm) {
-    LG_ARG(lg_attention_decode_split_supported(capacity, D), "%s: capacity = %lld (1 .. %d), D = %lld (32 or 64) unsupported", name,
-           (long long)capacity, kSplitMaxKeys, (long long)D);
-    LG_ARG(batch >= 0 && heads >= 1 && batch <= 65535 && heads <= 65535, "%s: bad batch / heads", name);
-    if (batch == 0) return LG_OK;
-    LG_ARG(split_operand(q, sbq) && split_operand(k_new, sbk) && split_operand(v_new, sbv) && split_operand(k_cache, sbc) &&
-               split_operand(v_cache, sbc) && split_operand(o, sbo) && ldc % 4 == 0 && pos && (reinterpret_cast<uintptr_t>(pos) & 3u) == 0 &&
-               (reinterpret_cast<uintptr_t>(lse) & 3u) == 0,
-           "%s: operands must be non-NULL and 16-byte aligned with pitches that are multiples of 4", name);
-    const int64_t w = heads * D;
-    LG_ARG(ldc >= w, "%s: cache row pitch %lld below heads * D = %lld", name, (long long)ldc, (long long)w);
-    LG_ARG(!mask || sbm == 0 || sbm >= capacity, "%s: mask batch pitch %lld is neither 0 (one row for the batch) nor >= capacity", name,
-           (long long)sbm);
-    LG_ARG(!split_positions_overlap(pos, pos_pitch ? batch : 1, k_cache, ldc, sbc, capacity, batch, w) &&
-               !split_positions_overlap(pos, pos_pitch ? batch : 1, v_cache, ldc, sbc, capacity, batch, w),
-           "%s: pos overlaps a cache: the launch writes the caches while other workgroups read their positions", name);
+    int rc = decode_check_operands(name, kSplitMaxKeys, pos_pitch, q, sbq, k_new, sbk, v_new, sbv, k_cache, v_cache, ldc, sbc, pos, o, sbo, lse, batch,
+                                   heads, capacity, D, mask, sbm);
+    if (rc != LG_OK || batch == 0) return rc;
     const int64_t pairs = batch * heads, slices = (capacity + kSplitSlice - 1) / kSplitSlice;
     LG_ARG(pairs <= rt().n_tickets, "%s: the ticket pool holds %d counters, %lld (batch, head) pairs need one each", name, rt().n_tickets,
            (long long)pairs);
-    {
-        const int64_t row[2] = {batch, w}, row_strides[2] = {sbo, 1};
-        int rc = adam_epilogue_check_strided(o, 4, 2, row, row_strides);
-        if (rc != LG_OK) return rc;
-        const int64_t rows[3] = {batch, capacity, w}, strides[3] = {sbc, ldc, 1};
-        rc = adam_epilogue_check_strided(k_cache, 4, 3, rows, strides);
-        if (rc != LG_OK) return rc;
-        rc = adam_epilogue_check_strided(v_cache, 4, 3, rows, strides);
-        if (rc != LG_OK) return rc;
-        if (lse) { rc = adam_epilogue_check_write(lse, pairs * 4); if (rc != LG_OK) return rc; }
-    }
+    rc = cache_check_writes(o, batch, sbo, 1, 0, k_cache, v_cache, 4, batch, sbc, capacity, ldc, heads * D, lse, pairs * 4);
+    if (rc != LG_OK) return rc;
     float* ws = nullptr;                             // a cache of one slice never hands anything over
     if (slices > 1) {
-        const int rc = lg_malloc(reinterpret_cast<void**>(&ws), size_t(pairs * slices * (D + 2)) * sizeof(float));
+        rc = lg_malloc(reinterpret_cast<void**>(&ws), size_t(pairs * slices * (D + 2)) * sizeof(float));
         if (rc != LG_OK) return rc;
     }
     const SplitArgs a{q, k_new, v_new, sbq, sbk, sbv, k_cache, v_cache, ldc, sbc, pos, pos_pitch, o, sbo, lse, int(heads), int(capacity), int(slices),
@@ -315,7 +259,7 @@ static int split_entry(const char* name, int64_t pos_pitch, const float* q, int6
     const dim3 grid{unsigned(slices), unsigned(heads), unsigned(batch)};
     if (D == 64) hipLaunchKernelGGL(attn_decode_split<64>, grid, dim3(256), 0, rt().stream, a);
     else         hipLaunchKernelGGL(attn_decode_split<32>, grid, dim3(256), 0, rt().stream, a);
-    if (ws) { const int rc = lg_free(ws); if (rc != LG_OK) return rc; }      // stream-ordered: the block is only reused by later launches
+    if (ws) { rc = lg_free(ws); if (rc != LG_OK) return rc; }      // stream-ordered: the block is only reused by later launches
     return LG_OK;
 }
 

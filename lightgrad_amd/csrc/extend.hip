@@ -31,8 +31,9 @@
 // `_rows` launch of its own at batch 1 on those rows, against cache rows, position and mask of slot z; one more slice of the grid
 // clears the rows behind cu[slots], which belong to nobody.
 // LDS at D = 64, capacity = 512: 32 * 68 + 32 * 516 + 128 * 72 + 3072 + 512 floats = 126 KB - one workgroup per CU.
-// The body, attn_extend_body<D, PACKED, PAGED>, and the host checks live in extend_body.h: paged.hip instantiates the body once
-// more with the caches reached through a block table (lg_attention_extend_paged_f32); this file keeps its four kernels.
+// The body, attn_extend_body<D, PACKED, PAGED>, and its launch live in extend_body.h: paged.hip instantiates the body once more
+// with the caches reached through a block table (lg_attention_extend_paged_f32); this file keeps its four kernels.  The host
+// checks of every entry of the family are cache_entry.h's, called here in each entry's order of refusal.
 #include "extend_body.h"
 
 namespace lg {
@@ -43,30 +44,12 @@ __global__ void __launch_bounds__(256) attn_extend(const ExtendArgs a) { attn_ex
 template <int D>
 __global__ void __launch_bounds__(256) attn_packed(const ExtendArgs a) { attn_extend_body<D, true>(a); }
 
-template <int D>
-static int launch_extend(const ExtendArgs& a, dim3 grid) {
-    const size_t bytes = size_t(attn_extend_lds_floats<D>(round32(a.capacity))) * 4;
-    int rc = allow_lds(&attn_extend<D>, bytes);
-    if (rc != LG_OK) return rc;
-    hipLaunchKernelGGL(attn_extend<D>, grid, dim3(256), bytes, rt().stream, a);
-    return LG_OK;
-}
-
-template <int D>
-static int launch_packed(const ExtendArgs& a, dim3 grid) {
-    const size_t bytes = size_t(attn_extend_lds_floats<D>(round32(a.capacity))) * 4;
-    int rc = allow_lds(&attn_packed<D>, bytes);
-    if (rc != LG_OK) return rc;
-    hipLaunchKernelGGL(attn_packed<D>, grid, dim3(256), bytes, rt().stream, a);
-    return LG_OK;
-}
-
 }  // namespace lg
 
 using namespace lg;
 
 extern "C" int lg_attention_extend_supported(int64_t m, int64_t capacity, int64_t D) {
-    return (D == 32 || D == 64) && m >= 1 && m <= capacity && capacity <= kExtMaxKeys;
+    return cache_head_dim(D) && m >= 1 && m <= capacity && capacity <= kExtMaxKeys;
 }
 
 // every entry: `pos_pitch` words between the positions of neighbouring batch elements (0: one word for the batch); `counts`: the
@@ -75,45 +58,28 @@ static int extend_entry(const char* name, int64_t pos_pitch, bool counts, const 
                         const float* v_new, int64_t ldv, int64_t sbv, float* k_cache, float* v_cache, int64_t ldc, int64_t sbc,
                         const int32_t* pos, float* o, int64_t ldo, int64_t sbo, float* p, int64_t batch, int64_t heads, int64_t m,
                         int64_t capacity, int64_t D, float scale, const float* mask, int64_t sbm) {
-    LG_ARG(lg_attention_extend_supported(m, capacity, D), "%s: m = %lld (1 .. capacity), capacity = %lld (1 .. 512), D = %lld (32 or 64) unsupported",
-           name, (long long)m, (long long)capacity, (long long)D);
-    LG_ARG(batch >= 0 && heads >= 1 && batch <= 65535 && heads <= 65535, "%s: bad batch / heads", name);
-    if (batch == 0) return LG_OK;
-    LG_ARG(extend_operand(q, ldq, sbq) && extend_operand(k_new, ldk, sbk) && extend_operand(v_new, ldv, sbv) && extend_operand(k_cache, ldc, sbc) &&
-               extend_operand(v_cache, ldc, sbc) && extend_operand(o, ldo, sbo) && pos && (reinterpret_cast<uintptr_t>(pos) & 3u) == 0 && aligned16(p),
-           "%s: operands must be non-NULL and 16-byte aligned with pitches that are non-negative multiples of 4", name);
-    const int64_t w = heads * D;
-    LG_ARG(ldc >= w, "%s: cache row pitch %lld below heads * D = %lld", name, (long long)ldc, (long long)w);
-    LG_ARG(!mask || sbm == 0 || sbm >= capacity, "%s: mask batch pitch %lld is neither 0 (one row for the batch) nor >= capacity", name,
-           (long long)sbm);
-    LG_ARG(!extend_overlap(k_new, ldk, sbk, m, k_cache, ldc, sbc, capacity, batch, w) && !extend_overlap(k_new, ldk, sbk, m, v_cache, ldc, sbc, capacity, batch, w) &&
-               !extend_overlap(v_new, ldv, sbv, m, k_cache, ldc, sbc, capacity, batch, w) && !extend_overlap(v_new, ldv, sbv, m, v_cache, ldc, sbc, capacity, batch, w),
-           "%s: k_new / v_new overlap a cache: the launch writes the caches while other workgroups read the new rows", name);
-    LG_ARG(!positions_overlap(pos, pos_pitch ? batch : 1, k_cache, ldc, sbc, capacity, batch, w) &&
-               !positions_overlap(pos, pos_pitch ? batch : 1, v_cache, ldc, sbc, capacity, batch, w),
-           "%s: pos overlaps a cache: the launch writes the caches while other workgroups read their positions", name);
+    int rc = extend_check_shape(name, "m", m, capacity, D);
+    if (rc != LG_OK) return rc;
+    rc = cache_check_grid(name, "batch", batch, 65535, heads);
+    if (rc != LG_OK || batch == 0) return rc;
+    const int64_t w = heads * D, pos_words = pos_pitch ? batch : 1;
+    rc = extend_check_caches(name, q, k_new, v_new, o, {ldq, ldk, ldv, ldo}, {sbq, sbk, sbv, sbo}, k_cache, v_cache, ldc, sbc, pos, pos_words, p, batch, m,
+                             capacity, w, mask, sbm, "batch", "the batch");
+    if (rc != LG_OK) return rc;
     if (counts) {
-        LG_ARG(count && (reinterpret_cast<uintptr_t>(count) & 3u) == 0, "%s: count must be non-NULL and 4-byte aligned", name);
-        LG_ARG(!positions_overlap(count, batch, k_cache, ldc, sbc, capacity, batch, w) && !positions_overlap(count, batch, v_cache, ldc, sbc, capacity, batch, w),
+        LG_ARG(cache_words(count), "%s: count must be non-NULL and 4-byte aligned", name);
+        LG_ARG(!words_overlap_caches(count, batch, k_cache, v_cache, 4 * cache_span(batch, sbc, capacity, ldc, w)),
                "%s: count overlaps a cache: the launch writes the caches while other workgroups read their counts", name);
-        LG_ARG(!(count < pos + (pos_pitch ? batch : 1) && pos < count + batch), "%s: count overlaps pos", name);
+        LG_ARG(!bytes_overlap(count, 4 * batch, pos, 4 * pos_words), "%s: count overlaps pos", name);
     }
-    {
-        const int64_t rows[3] = {batch, m, w}, row_strides[3] = {sbo, ldo, 1};
-        int rc = adam_epilogue_check_strided(o, 4, 3, rows, row_strides);
-        if (rc != LG_OK) return rc;
-        const int64_t crows[3] = {batch, capacity, w}, strides[3] = {sbc, ldc, 1};
-        rc = adam_epilogue_check_strided(k_cache, 4, 3, crows, strides);
-        if (rc != LG_OK) return rc;
-        rc = adam_epilogue_check_strided(v_cache, 4, 3, crows, strides);
-        if (rc != LG_OK) return rc;
-        if (p) { rc = adam_epilogue_check_write(p, batch * heads * m * capacity * 4); if (rc != LG_OK) return rc; }
-    }
+    rc = cache_check_writes(o, batch, sbo, m, ldo, k_cache, v_cache, 4, batch, sbc, capacity, ldc, w, p, batch * heads * m * capacity * 4);
+    if (rc != LG_OK) return rc;
     const ExtendArgs a{q, k_new, v_new, ldq, sbq, ldk, sbk, ldv, sbv, k_cache, v_cache, ldc, sbc, pos, pos_pitch, counts ? count : nullptr, o, ldo, sbo, p,
                        int(heads), int(capacity), int(m), scale, mask, sbm, rt().status_dev, nullptr, 0};
     const dim3 grid{unsigned((m + 31) / 32), unsigned(heads), unsigned(batch)};
-    const int rc = D == 64 ? launch_extend<64>(a, grid) : launch_extend<32>(a, grid);
-    return rc;
+    const int Cp = round32(a.capacity);
+    return D == 64 ? launch_extend_body(&attn_extend<64>, size_t(attn_extend_lds_floats<64>(Cp)) * 4, a, grid)
+                   : launch_extend_body(&attn_extend<32>, size_t(attn_extend_lds_floats<32>(Cp)) * 4, a, grid);
 }
 
 extern "C" int lg_attention_extend_f32(const float* q, int64_t ldq, int64_t sbq, const float* k_new, int64_t ldk, int64_t sbk,
@@ -166,48 +132,35 @@ extern "C" int lg_attention_extend_packed_f32(const float* q, int64_t ldq, const
                                               int64_t capacity, int64_t D, float scale, const float* mask, int64_t sbm) {
     LG_REQUIRE_INIT();
     const char* name = "lg_attention_extend_packed_f32";
-    LG_ARG(lg_attention_extend_supported(m_max, capacity, D), "%s: m_max = %lld (1 .. capacity), capacity = %lld (1 .. 512), D = %lld (32 or 64) unsupported",
-           name, (long long)m_max, (long long)capacity, (long long)D);
+    int rc = extend_check_shape(name, "m_max", m_max, capacity, D);
+    if (rc != LG_OK) return rc;
     LG_ARG(T >= 1 && T < (int64_t(1) << 30), "%s: T = %lld token rows (1 .. 2^30 - 1) unsupported", name, (long long)T);
-    LG_ARG(slots >= 0 && heads >= 1 && slots <= 65534 && heads <= 65535, "%s: bad slots / heads", name);
-    if (slots == 0) return LG_OK;
-    LG_ARG(extend_operand(q, ldq, 0) && extend_operand(k_new, ldk, 0) && extend_operand(v_new, ldv, 0) && extend_operand(k_cache, ldc, sbc) &&
-               extend_operand(v_cache, ldc, sbc) && extend_operand(o, ldo, 0) && pos && (reinterpret_cast<uintptr_t>(pos) & 3u) == 0 && aligned16(p),
-           "%s: operands must be non-NULL and 16-byte aligned with pitches that are non-negative multiples of 4", name);
+    rc = cache_check_grid(name, "slots", slots, 65534, heads);          // the grid has slots + 1 slices
+    if (rc != LG_OK || slots == 0) return rc;
     const int64_t w = heads * D;
-    LG_ARG(ldc >= w, "%s: cache row pitch %lld below heads * D = %lld", name, (long long)ldc, (long long)w);
-    LG_ARG(!mask || sbm == 0 || sbm >= capacity, "%s: mask slot pitch %lld is neither 0 (one row for every slot) nor >= capacity", name, (long long)sbm);
-    // (extend_overlap spans `slots` elements of both operands: the flat ones have no batch pitch)
-    LG_ARG(!extend_overlap(k_new, ldk, 0, T, k_cache, ldc, sbc, capacity, slots, w) && !extend_overlap(k_new, ldk, 0, T, v_cache, ldc, sbc, capacity, slots, w) &&
-               !extend_overlap(v_new, ldv, 0, T, k_cache, ldc, sbc, capacity, slots, w) && !extend_overlap(v_new, ldv, 0, T, v_cache, ldc, sbc, capacity, slots, w),
-           "%s: k_new / v_new overlap a cache: the launch writes the caches while other workgroups read the new rows", name);
-    LG_ARG(!positions_overlap(pos, slots, k_cache, ldc, sbc, capacity, slots, w) && !positions_overlap(pos, slots, v_cache, ldc, sbc, capacity, slots, w),
-           "%s: pos overlaps a cache: the launch writes the caches while other workgroups read their positions", name);
-    LG_ARG(cu && (reinterpret_cast<uintptr_t>(cu) & 3u) == 0, "%s: cu must be non-NULL and 4-byte aligned", name);
-    LG_ARG(!positions_overlap(cu, slots + 1, k_cache, ldc, sbc, capacity, slots, w) && !positions_overlap(cu, slots + 1, v_cache, ldc, sbc, capacity, slots, w),
+    // (the spans of the new rows cover `slots` elements of both operands: the flat ones have no batch pitch)
+    rc = extend_check_caches(name, q, k_new, v_new, o, {ldq, ldk, ldv, ldo}, {0, 0, 0, 0}, k_cache, v_cache, ldc, sbc, pos, slots, p, slots, T, capacity, w,
+                             mask, sbm, "slot", "every slot");
+    if (rc != LG_OK) return rc;
+    LG_ARG(cache_words(cu), "%s: cu must be non-NULL and 4-byte aligned", name);
+    LG_ARG(!words_overlap_caches(cu, slots + 1, k_cache, v_cache, 4 * cache_span(slots, sbc, capacity, ldc, w)),
            "%s: cu overlaps a cache: the launch writes the caches while other workgroups read their rows' bounds", name);
-    LG_ARG(!(cu < pos + slots && pos < cu + slots + 1), "%s: cu overlaps pos", name);
+    LG_ARG(!bytes_overlap(cu, 4 * (slots + 1), pos, 4 * slots), "%s: cu overlaps pos", name);
     {
-        const int64_t span[4] = {((T - 1) * ldq + w) * 4, ((T - 1) * ldk + w) * 4, ((T - 1) * ldv + w) * 4, ((T - 1) * ldo + w) * 4};
-        LG_ARG(!words_overlap(cu, slots + 1, q, span[0]) && !words_overlap(cu, slots + 1, k_new, span[1]) && !words_overlap(cu, slots + 1, v_new, span[2]) &&
-                   !words_overlap(cu, slots + 1, o, span[3]) && !words_overlap(cu, slots + 1, p, heads * T * capacity * 4),
-               "%s: cu overlaps an operand (q, k_new, v_new, o or p)", name);
+        const void* operand[5] = {q, k_new, v_new, o, p};
+        const int64_t bytes[5] = {4 * cache_span(1, 0, T, ldq, w), 4 * cache_span(1, 0, T, ldk, w), 4 * cache_span(1, 0, T, ldv, w),
+                                  4 * cache_span(1, 0, T, ldo, w), heads * T * capacity * 4};
+        for (int i = 0; i < 5; ++i)
+            LG_ARG(!bytes_overlap(cu, 4 * (slots + 1), operand[i], bytes[i]), "%s: cu overlaps an operand (q, k_new, v_new, o or p)", name);
     }
-    {
-        const int64_t rows[2] = {T, w}, row_strides[2] = {ldo, 1};
-        int rc = adam_epilogue_check_strided(o, 4, 2, rows, row_strides);
-        if (rc != LG_OK) return rc;
-        const int64_t crows[3] = {slots, capacity, w}, strides[3] = {sbc, ldc, 1};
-        rc = adam_epilogue_check_strided(k_cache, 4, 3, crows, strides);
-        if (rc != LG_OK) return rc;
-        rc = adam_epilogue_check_strided(v_cache, 4, 3, crows, strides);
-        if (rc != LG_OK) return rc;
-        if (p) { rc = adam_epilogue_check_write(p, heads * T * capacity * 4); if (rc != LG_OK) return rc; }
-    }
+    rc = cache_check_writes(o, 1, 0, T, ldo, k_cache, v_cache, 4, slots, sbc, capacity, ldc, w, p, heads * T * capacity * 4);
+    if (rc != LG_OK) return rc;
     const ExtendArgs a{q, k_new, v_new, ldq, 0, ldk, 0, ldv, 0, k_cache, v_cache, ldc, sbc, pos, 1, nullptr, o, ldo, 0, p,
                        int(heads), int(capacity), int(m_max), scale, mask, sbm, rt().status_dev, cu, int(T)};
     const dim3 grid{unsigned((m_max + 31) / 32), unsigned(heads), unsigned(slots + 1)};
-    const int rc = D == 64 ? launch_packed<64>(a, grid) : launch_packed<32>(a, grid);
+    const int Cp = round32(a.capacity);
+    rc = D == 64 ? launch_extend_body(&attn_packed<64>, size_t(attn_extend_lds_floats<64>(Cp)) * 4, a, grid)
+                 : launch_extend_body(&attn_packed<32>, size_t(attn_extend_lds_floats<32>(Cp)) * 4, a, grid);
     if (rc != LG_OK) return rc;
     LG_CHECK_LAUNCH();
     return LG_OK;

@@ -1,9 +1,11 @@
-// The kernel body of the extend launches, attn_extend_body<D, PACKED, PAGED, KV16>, and the host checks their entries share: included
-// by extend.hip (the (b, m) entries and the token-packed one, PAGED = false), by paged.hip (lg_attention_extend_paged_f32) and by
-// paged_bf16.hip (lg_attention_extend_paged_bf16_f32, KV16 = true: pools of bfloat16 words)
+// The kernel body of the extend launches, attn_extend_body<D, PACKED, PAGED, KV16>, and the one launch of its four kernels
+// (launch_extend_body): included by extend.hip (the (b, m) entries and the token-packed one, PAGED = false), by paged.hip
+// (lg_attention_extend_paged_f32) and by paged_bf16.hip (lg_attention_extend_paged_bf16_f32, KV16 = true: pools of bfloat16
+// words).  The host checks of their entries are cache_entry.h's
 #pragma once
 #include <type_traits>
 #include "attention_common.h"
+#include "cache_entry.h"
 
 namespace lg {
 
@@ -436,27 +438,13 @@ __device__ __forceinline__ void attn_extend_body(const ExtendArgs& a) {
     }
 }
 
-static bool extend_operand(const void* p, int64_t ld, int64_t sb) { return p && aligned16(p) && ld >= 0 && sb >= 0 && ld % 4 == 0 && sb % 4 == 0; }
-
-// do the floats [x, x + (batch - 1) sb + (rows - 1) ld + w) and [y, ...) share an address?
-static bool extend_overlap(const float* x, int64_t ldx, int64_t sbx, int64_t rowsx, const float* y, int64_t ldy, int64_t sby, int64_t rowsy,
-                           int64_t batch, int64_t w) {
-    const float* xe = x + (batch - 1) * sbx + (rowsx - 1) * ldx + w;
-    const float* ye = y + (batch - 1) * sby + (rowsy - 1) * ldy + w;
-    return x < ye && y < xe;
-}
-
-// do the `words` position words share an address with the floats [c, c + (batch - 1) sbc + (capacity - 1) ldc + w) of a cache?
-static bool positions_overlap(const int32_t* pos, int64_t words, const float* c, int64_t ldc, int64_t sbc, int64_t capacity, int64_t batch, int64_t w) {
-    const char *x = reinterpret_cast<const char*>(pos), *xe = x + 4 * words;
-    const char *y = reinterpret_cast<const char*>(c), *ye = reinterpret_cast<const char*>(c + (batch - 1) * sbc + (capacity - 1) * ldc + w);
-    return x < ye && y < xe;
-}
-
-// do the `words` int32 words at x share an address with the `bytes` bytes at y?
-static bool words_overlap(const int32_t* x, int64_t words, const void* y, int64_t bytes) {
-    const char *a = reinterpret_cast<const char*>(x), *ae = a + 4 * words, *b = static_cast<const char*>(y);
-    return y != nullptr && a < b + bytes && b < ae;
+// attn_extend<D>, attn_packed<D>, attn_paged<D> or attn_paged_bf16<D> with lds_bytes of dynamic LDS
+template <class K>
+static int launch_extend_body(K kernel, size_t lds_bytes, const ExtendArgs& a, dim3 grid) {
+    const int rc = allow_lds(kernel, lds_bytes);
+    if (rc != LG_OK) return rc;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), lds_bytes, rt().stream, a);
+    return LG_OK;
 }
 
 }  // namespace lg

@@ -257,7 +257,9 @@ def test_position_out_of_range_is_reported_not_a_fault(hip, bad):
 REFUSALS = [("D", dict(D=48)), ("D16", dict(D=16)), ("capacity0", dict(capacity=0)), ("capacity513", dict(capacity=513)),
             ("pitch-q", dict(sbq=66)), ("pitch-cache-row", dict(ldc=66)), ("pitch-cache-batch", dict(sbc=8 * 64 + 2)), ("pitch-o", dict(sbo=65)),
             ("base-q", "q"), ("base-k_new", "k_new"), ("base-v_new", "v_new"), ("base-k_cache", "k_cache"), ("base-v_cache", "v_cache"),
-            ("base-o", "o"), ("row-pitch-below-width", dict(ldc=32)), ("mask-pitch", dict(mask=True, sbm=7)), ("mask-pitch-1", dict(mask=True, sbm=1))]
+            ("base-o", "o"), ("row-pitch-below-width", dict(ldc=32)), ("mask-pitch", dict(mask=True, sbm=7)), ("mask-pitch-1", dict(mask=True, sbm=1)),
+            ("heads0", dict(heads=0)), ("pos-null", dict(pos=None)), ("base-p-2", dict(p="p+2")), ("pos-in-k_cache", dict(pos="k_cache")),
+            ("pos-in-v_cache", dict(pos="v_cache+64"))]
 
 
 @pytest.mark.parametrize("name,change", REFUSALS, ids=[r[0] for r in REFUSALS])
@@ -267,10 +269,39 @@ def test_host_refusals_launch_nothing(hip, name, change):
         change = {change: call.args[change] + 4}                          # a base that is not 16-byte aligned
     if change.get("mask") is True:
         change = dict(change, mask=call.mask.ptr)
+    for key, value in list(change.items()):
+        if isinstance(value, str):                                        # another operand's address, some bytes in
+            other, _, offset = value.partition("+")
+            change[key] = call.args[other] + int(offset or 0)
     assert call(**change) == LG_EINVAL, name
     assert b"lg_attention_decode_f32" in call.lib.lg_last_error()
+    if name.startswith("pos-in"):
+        assert b"pos overlaps a cache" in call.lib.lg_last_error()
     HipDevice.synchronize()
     assert call.untouched(), name
+
+
+def test_a_negative_batch_pitch_and_probabilities_at_a_4_byte_address_are_taken(hip):
+    """what this entry accepts and lg_attention_extend_f32 refuses (test_hip_extend.py: pitch-v_new-negative, base-p).  Batch 2 with
+    q at its second row and sbq = -width is the launch of the two query rows swapped, bit for bit; p needs 4-byte alignment only"""
+    call, width = Call(hip), 64
+    swapped = hip.from_numpy(np.ascontiguousarray(call.q.numpy()[::-1]), requires_grad=False)
+    assert call(q=swapped.ptr) == 0
+    HipDevice.synchronize()
+    want, want_p = call.o.numpy().copy(), call.p.numpy().copy()
+    assert not (want == SENTINEL).any()
+    call.o.upload_(np.full_like(want, SENTINEL))
+    call.p.upload_(np.full_like(want_p, SENTINEL))
+    assert call(q=call.args["q"] + 4 * width, sbq=-width) == 0
+    HipDevice.synchronize()
+    np.testing.assert_array_equal(bits(call.o.numpy()), bits(want))
+    np.testing.assert_array_equal(bits(call.p.numpy()), bits(want_p))
+    call.p.upload_(np.full_like(want_p, SENTINEL))
+    assert call(q=swapped.ptr, batch=1, p=call.args["p"] + 4) == 0         # one element: heads * capacity floats, one float in
+    HipDevice.synchronize()
+    flat, n = call.p.numpy().ravel(), want_p[0].size
+    np.testing.assert_array_equal(bits(flat[1:1 + n]), bits(want_p[0].ravel()))
+    assert flat[0] == SENTINEL and (flat[1 + n:] == SENTINEL).all()
 
 
 def test_first_refusal_wins_and_a_shared_mask_row_is_taken(hip):

@@ -174,7 +174,12 @@ def test_a_row_out_of_range_is_reported_once_and_the_others_are_computed(hip):
 
 
 REFUSALS = [("capacity0", dict(capacity=0)), ("capacity16385", dict(capacity=16385)), ("D48", dict(D=48)), ("base-q", "q"),
-            ("row-pitch-below-width", dict(ldc=32)), ("mask-pitch-1", dict(mask=True, sbm=1))]
+            ("row-pitch-below-width", dict(ldc=32)), ("mask-pitch-1", dict(mask=True, sbm=1)),
+            # the rows of test_hip_decode.py's table: the entries run the same host checks
+            ("heads0", dict(heads=0)), ("pitch-q", dict(sbq=66)), ("pitch-cache-row", dict(ldc=66)), ("pitch-cache-batch", dict(sbc=8 * 64 + 2)),
+            ("pitch-o", dict(sbo=65)), ("base-k_new", "k_new"), ("base-v_new", "v_new"), ("base-k_cache", "k_cache"), ("base-v_cache", "v_cache"),
+            ("base-o", "o"), ("pos-null", dict(pos=None)), ("mask-pitch", dict(mask=True, sbm=7)), ("pos-in-k_cache", dict(pos="k_cache")),
+            ("pos-in-v_cache", dict(pos="v_cache+"))]
 
 
 @pytest.mark.parametrize("name,change", REFUSALS, ids=[r[0] for r in REFUSALS])
@@ -183,10 +188,41 @@ def test_host_refusals_launch_nothing(hip, name, change):
     if isinstance(change, str):
         change = {change: call.args[change] + 4}                          # a base that is not 16-byte aligned
     change = dict(change, mask=call.mask.ptr) if change.get("mask") is True else change
+    for key, value in list(change.items()):
+        if isinstance(value, str):                                        # the position word inside a cache: at its base, or 64 bytes in
+            change[key] = call.args[value.rstrip("+")] + (64 if value.endswith("+") else 0)
     assert call(**change) == LG_EINVAL, name
     assert b"lg_attention_decode_split_f32" in call.lib.lg_last_error()
+    if name.startswith("pos-in"):
+        assert b"pos overlaps a cache" in call.lib.lg_last_error()
     HipDevice.synchronize()
     assert call.untouched(), name
+
+
+@pytest.mark.parametrize("entry", ["lg_attention_decode_split_f32", "lg_attention_decode_split_rows_f32"])
+def test_an_empty_batch_is_fine_and_launches_nothing(hip, entry):
+    """batch == 0 returns before the operands are looked at, after the shape and the heads; `_rows` refuses under its own name"""
+    call = Call(hip, [3, 3, 3], entry=entry)
+    assert call(batch=0) == 0 and call(batch=0, q=call.args["q"] + 4, pos=None) == 0
+    assert call(batch=0, D=48) == LG_EINVAL and call(batch=0, heads=0) == LG_EINVAL
+    assert call(pos=call.args["k_cache"]) == LG_EINVAL and entry.encode() + b": pos overlaps a cache" in call.lib.lg_last_error()
+    HipDevice.synchronize()
+    assert call.untouched()
+
+
+def test_a_negative_batch_pitch_is_taken(hip):
+    """batch 2 with q at its second row and sbq = -width: the launch of the two query rows swapped, bit for bit"""
+    call, width = Call(hip, [3], b=2), 64
+    swapped = tensor(hip, call.q.numpy()[::-1])
+    assert call(q=swapped.ptr) == 0
+    HipDevice.synchronize()
+    want, want_lse = call.o.numpy().copy(), call.lse.numpy().copy()
+    assert not (want == SENTINEL).any()
+    call.o.upload_(np.full_like(want, SENTINEL))
+    assert call(q=call.args["q"] + 4 * width, sbq=-width) == 0
+    HipDevice.synchronize()
+    np.testing.assert_array_equal(bits(call.o.numpy()), bits(want))
+    np.testing.assert_array_equal(bits(call.lse.numpy()), bits(want_lse))
 
 
 def test_probabilities_are_refused_by_name(hip):

@@ -324,7 +324,8 @@ REFUSALS = [("D", dict(D=48)), ("D16", dict(D=16)), ("capacity0", dict(capacity=
             ("pitch-o", dict(ldo=65)), ("base-q", "q"), ("base-k_new", "k_new"), ("base-v_new", "v_new"), ("base-k_cache", "k_cache"),
             ("base-v_cache", "v_cache"), ("base-o", "o"), ("base-p", "p"), ("row-pitch-below-width", dict(ldc=32)),
             ("mask-pitch", dict(mask=True, sbm=7)), ("mask-pitch-1", dict(mask=True, sbm=1)), ("k_new-in-k_cache", dict(k_new="k_cache")),
-            ("v_new-in-k_cache", dict(v_new="k_cache")), ("k_new-in-v_cache", dict(k_new="v_cache")), ("v_new-behind-row-0", dict(v_new="v_cache+"))]
+            ("v_new-in-k_cache", dict(v_new="k_cache")), ("k_new-in-v_cache", dict(k_new="v_cache")), ("v_new-behind-row-0", dict(v_new="v_cache+")),
+            ("heads0", dict(heads=0)), ("pos-null", dict(pos=None)), ("pitch-q-batch-negative", dict(sbq=-3 * 64))]
 
 
 @pytest.mark.parametrize("name,change", REFUSALS, ids=[r[0] for r in REFUSALS])
