@@ -453,6 +453,14 @@ class BertSelfAttention(nn.Module):
             context = hidden.self_attention_extend(self.query.weight, self.query.bias, self.key.weight, self.key.bias, self.value.weight,
                                                    self.value.bias, k_cache, v_cache, cache.pos, heads=self.h, scale=scale, **extra, **counted)
             return context, None
+        if hasattr(hidden, "self_attention_extend") and mask_ok and \
+                hidden.self_attention_extend_supported(self.query.weight, self.h, cache.capacity, split=True):
+            # a cache beyond the 512 rows of that launch: the split-key launch (up to 128 new rows behind up to 16384), the keys of
+            # a block of rows over workgroups and merged inside the launch - one-word, per-row and count= caches alike
+            extra = {"mask": attention_mask} if attention_mask is not None else {}
+            context = hidden.self_attention_extend(self.query.weight, self.query.bias, self.key.weight, self.key.bias, self.value.weight,
+                                                   self.value.bias, k_cache, v_cache, cache.pos, heads=self.h, scale=scale, split=True, **extra, **counted)
+            return context, None
         if getattr(cache, "per_row", False):
             return self._rows_composite(hidden, attention_mask, cache, index, **counted)
         # the same over the tensor API: the host mirror of the position slices the cache
@@ -1712,7 +1720,9 @@ if __name__ == "__main__":
         np.random.seed(0)
         # --prompt-length P (default 8) and --positions M (the model's position embeddings, default TINY's 512): with
         # --no-attention-probs a prompt beyond 512 tokens is prefilled by the streaming attention node and decoded by the split-key
-        # launch (csrc/decode_split.hip) - `--generate 16 --no-attention-probs --prompt-length 2000 --positions 2048`
+        # launch (csrc/decode_split.hip) - `--generate 16 --no-attention-probs --prompt-length 2000 --positions 2048`; with
+        # `--prefill-chunk 64` behind it the prompt goes through the append path, whose pieces behind 512 cached rows take the
+        # split-key extend launch (csrc/extend_split.hip)
         prompt_length = int(sys.argv[sys.argv.index("--prompt-length") + 1]) if "--prompt-length" in sys.argv else 8
         long_config = {"max_position_embeddings": int(sys.argv[sys.argv.index("--positions") + 1])} if "--positions" in sys.argv else {}
         if "--no-attention-probs" in sys.argv:

@@ -760,6 +760,48 @@ int lg_attention_extend_counts_f32(const float* q, int64_t ldq, int64_t sbq, con
                                    const int32_t* count,             /* `batch` words: the real new tokens of each row, 0 .. m */
                                    float* o, int64_t ldo, int64_t sbo, float* p, int64_t batch, int64_t heads, int64_t m, int64_t capacity,
                                    int64_t D, float scale, const float* mask, int64_t sbm);
+/* ---- the same three entries against a cache of up to 16384 rows, the keys split over workgroups (csrc/extend_split.hip) ------
+ * lg_attention_extend_split_f32 / _rows_f32 / _counts_f32 take the operands of lg_attention_extend_f32 / _rows_f32 / _counts_f32 and
+ * mean what they mean - the rows read and written, the seam at t, NaN beyond t reaching nothing, +0.0 rows behind a count, an
+ * element's bits those it has alone - with ONE difference: in place of p, `lse` - NULL, or a dense (batch, heads, m) tensor that
+ * receives log sum_{j <= t + i} exp(score_ij) of row i (+0.0 for a row behind the count).  No probabilities are returned.
+ * The grid is (ceil(capacity / L), ceil(m / 32) * heads, batch) with L = lg_attention_extend_split_slice() keys per workgroup: block
+ * q0 of an element reaches keys [0, t + q0 + rows), a workgroup whose keys lie beyond returns before any load; each of the others
+ * runs an online softmax over its keys on the fp32 matrix cores (LDS does not depend on the capacity), and the partial {max,
+ * sum, unnormalised context} of a block's live workgroups are merged inside the launch by the last of them to arrive (a
+ * per-launch workspace, the runtime's ticket pool; every ticket is zero again when the launch ends; a block with one live
+ * workgroup needs neither).  Every fold runs in a fixed order: the same bits every run, whoever arrives last.  New row i is
+ * written to the caches once, by the workgroup that owns position t + i.  An element out of range (t < 0, t + n > capacity, a
+ * count outside 0 .. m) writes nothing - o, lse, caches - and raises the device status flag once; the others are computed.
+ * Supported (lg_attention_extend_split_supported, pure host code): D = 32 or 64, 1 <= capacity <= 16384, 1 <= m <= min(capacity,
+ * 128).  THE CAP m <= 128 bounds the workspace of a launch, batch * heads * 4 * ceil(capacity / L) * 32 * (D + 2) floats; a longer
+ * append is several launches.  Checked in this order, each LG_EINVAL under the entry's name, before anything is launched: D / m /
+ * capacity; batch / heads, heads * ceil(m / 32) beyond 65535; (batch == 0 returns LG_OK here;) a pitch that is negative or no
+ * multiple of 4, or a base that is not 16-byte aligned; ldc < heads * D; a mask with 0 < sbm < capacity; k_new or v_new
+ * overlapping a cache; pos overlapping a cache; count NULL, misaligned, overlapping a cache or pos; lse not 4-byte aligned; lse
+ * overlapping o or a cache; batch * heads * ceil(m / 32) beyond the ticket pool.
+ * lg_attention_extend_split_set_slice(L), L one of 256, 512, 1024, is for experiments (tools/extend_split_time.py). */
+int lg_attention_extend_split_supported(int64_t m, int64_t capacity, int64_t D);
+int lg_attention_extend_split_slice(void);
+int lg_attention_extend_split_set_slice(int64_t L);
+int lg_attention_extend_split_f32(const float* q, int64_t ldq, int64_t sbq, const float* k_new, int64_t ldk, int64_t sbk,
+                                  const float* v_new, int64_t ldv, int64_t sbv, float* k_cache, float* v_cache, int64_t ldc, int64_t sbc,
+                                  const int32_t* pos,                /* ONE word in device memory: the position of new token 0 */
+                                  float* o, int64_t ldo, int64_t sbo,
+                                  float* lse,                        /* NULL, or log-sum-exp (batch, heads, m), dense */
+                                  int64_t batch, int64_t heads, int64_t m, int64_t capacity, int64_t D, float scale,
+                                  const float* mask, int64_t sbm);
+int lg_attention_extend_split_rows_f32(const float* q, int64_t ldq, int64_t sbq, const float* k_new, int64_t ldk, int64_t sbk,
+                                       const float* v_new, int64_t ldv, int64_t sbv, float* k_cache, float* v_cache, int64_t ldc, int64_t sbc,
+                                       const int32_t* pos,           /* `batch` words: the position of each row's new token 0 */
+                                       float* o, int64_t ldo, int64_t sbo, float* lse, int64_t batch, int64_t heads, int64_t m,
+                                       int64_t capacity, int64_t D, float scale, const float* mask, int64_t sbm);
+int lg_attention_extend_split_counts_f32(const float* q, int64_t ldq, int64_t sbq, const float* k_new, int64_t ldk, int64_t sbk,
+                                         const float* v_new, int64_t ldv, int64_t sbv, float* k_cache, float* v_cache, int64_t ldc, int64_t sbc,
+                                         const int32_t* pos,         /* `batch` words: the position of each row's new token 0 */
+                                         const int32_t* count,       /* `batch` words: the real new tokens of each row, 0 .. m */
+                                         float* o, int64_t ldo, int64_t sbo, float* lse, int64_t batch, int64_t heads, int64_t m,
+                                         int64_t capacity, int64_t D, float scale, const float* mask, int64_t sbm);
 /* The per-row bookkeeping of one decode step in one launch, one thread per row, any batch >= 1.  For each row r with
  * done[r] == 0: p = pos[r] + 1; if p < 0 or p >= columns the status flag is raised (LG_EINDEX at the next lg_sync /
  * lg_memcpy_d2h) and the row is left untouched; otherwise pos[r] = p, token[r] = nxt[r * nxt_pitch], out_ids[r * out_pitch + p] =

@@ -174,6 +174,15 @@ PROTOTYPES = {
                                      + [c_void_p, c_int64, c_int64] + [c_void_p] + [c_int64] * 5 + [c_float] + [c_void_p, c_int64]),
     "lg_attention_extend_counts_f32": (c_int, [c_void_p, c_int64, c_int64] * 3 + [c_void_p, c_void_p, c_int64, c_int64] + [c_void_p, c_void_p]
                                        + [c_void_p, c_int64, c_int64] + [c_void_p] + [c_int64] * 5 + [c_float] + [c_void_p, c_int64]),
+    "lg_attention_extend_split_supported": (c_int, [c_int64, c_int64, c_int64]),
+    "lg_attention_extend_split_slice": (c_int, []),
+    "lg_attention_extend_split_set_slice": (c_int, [c_int64]),
+    "lg_attention_extend_split_f32": (c_int, [c_void_p, c_int64, c_int64] * 3 + [c_void_p, c_void_p, c_int64, c_int64] + [c_void_p]
+                                      + [c_void_p, c_int64, c_int64] + [c_void_p] + [c_int64] * 5 + [c_float] + [c_void_p, c_int64]),
+    "lg_attention_extend_split_rows_f32": (c_int, [c_void_p, c_int64, c_int64] * 3 + [c_void_p, c_void_p, c_int64, c_int64] + [c_void_p]
+                                           + [c_void_p, c_int64, c_int64] + [c_void_p] + [c_int64] * 5 + [c_float] + [c_void_p, c_int64]),
+    "lg_attention_extend_split_counts_f32": (c_int, [c_void_p, c_int64, c_int64] * 3 + [c_void_p, c_void_p, c_int64, c_int64] + [c_void_p, c_void_p]
+                                             + [c_void_p, c_int64, c_int64] + [c_void_p] + [c_int64] * 5 + [c_float] + [c_void_p, c_int64]),
     "lg_decode_commit_i32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, ctypes.c_int32]),
     "lg_serve_commit_i32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
                                     c_int64] + [c_void_p] * 6 + [c_int64] * 3 + [ctypes.c_int32]),

@@ -13,6 +13,7 @@ the predicate accepts, a log-sum-exp per row on the result, its own forward and 
 `decode_attention` / `self_attention_decode` are the inference ops of incremental decoding: one new token against a key / value
 cache, over lg_attention_decode_f32 (csrc/decode.hip) or, with `split=True`, the split-key launch for caches of up to 16384 rows
 (lg_attention_decode_split_f32, csrc/decode_split.hip).  They share nothing with the forms above and stay outside the tape.
+`extend_attention` / `self_attention_extend` append m tokens the same way (csrc/extend.hip; `split=True`: csrc/extend_split.hip).
 """
 import ctypes
 import numpy as np
@@ -565,7 +566,8 @@ HipTensor.decode_attention, HipTensor.decode_attention_supported = decode_attent
 HipTensor.self_attention_decode, HipTensor.self_attention_decode_supported = self_attention_decode, self_attention_decode_supported
 
 
-""" Appending several tokens to a filled key / value cache in one attention launch (csrc/extend.hip) """
+""" Appending several tokens to a filled key / value cache in one attention launch (csrc/extend.hip; split=True: caches of up to
+16384 rows, csrc/extend_split.hip) """
 
 
 def _token_rows_in_place(t, name):
@@ -591,22 +593,39 @@ def _token_counts(name, count, pos, b, k_cache, v_cache):
     return _dense_words(count, b)
 
 
-def _launch_extend(name, q3, k3, v3, m, k_cache, v_cache, pos, out, heads, scale, mask, probs, count=None):
-    """q3, k3, v3: (address, row pitch, batch pitch); out: (b, m, width) dense.  Returns the probabilities (b, heads, m, capacity) or None"""
+def _launch_extend(name, q3, k3, v3, m, k_cache, v_cache, pos, out, heads, scale, mask, probs, count=None, split=False, lse=False):
+    """q3, k3, v3: (address, row pitch, batch pitch); out: (b, m, width) dense.  Returns the probabilities (b, heads, m, capacity) or None;
+    split=True (csrc/extend_split.hip): the log-sum-exp (b, heads, m) or None in their place"""
     b, capacity, width = k_cache._shape
     if count is not None:
         count = _token_counts(name, count, pos, b, k_cache, v_cache)
-    mask3, p = _cache_launch(name, mask, b, capacity, k_cache, v_cache, (b, heads, m, capacity) if probs else None)
+    if split:
+        shape = (b, heads, m) if lse else None
+    else:
+        shape = (b, heads, m, capacity) if probs else None
+    mask3, p = _cache_launch(name, mask, b, capacity, k_cache, v_cache, shape)
+    family = "lg_attention_extend_split" if split else "lg_attention_extend"
     if count is not None:
         # a token count per sequence next to its position: the counts entry, at any batch
         pos = _dense_words(pos, b)
-        entry, words = _l.lib().lg_attention_extend_counts_f32, (pos.ptr, count.ptr)
+        entry, words = getattr(_l.lib(), family + "_counts_f32"), (pos.ptr, count.ptr)
     else:
         pos, per_row = _positions(pos, b)
-        entry, words = (_l.lib().lg_attention_extend_rows_f32 if per_row else _l.lib().lg_attention_extend_f32), (pos.ptr,)
+        entry, words = getattr(_l.lib(), family + ("_rows_f32" if per_row else "_f32")), (pos.ptr,)
     _l.check(entry(*q3, *k3, *v3, k_cache.ptr, v_cache.ptr, k_cache._strides[1], k_cache._strides[0], *words,
-                   out.ptr, width, m * width, p.ptr if probs else None, b, heads, m, capacity, width // heads, float(scale), mask3[1], mask3[2]))
+                   out.ptr, width, m * width, p.ptr if p is not None else None, b, heads, m, capacity, width // heads, float(scale), mask3[1], mask3[2]))
     return p
+
+
+def _extend_fits(m, capacity, d, split):
+    """the 512-row launches of csrc/extend.hip, or with split=True the split-key launch of csrc/extend_split.hip (1 .. 16384 rows, m <= 128)"""
+    return bool((_l.lib().lg_attention_extend_split_supported if split else _l.lib().lg_attention_extend_supported)(m, capacity, d))
+
+
+def _extend_split_options(name, probs, split, lse, cu, m_max, block_table, block_size, kv_dtype):
+    _split_options(name, probs, split, lse)
+    for keyword, value in (("cu", cu), ("m_max", m_max), ("block_table", block_table), ("block_size", block_size), ("kv_dtype", kv_dtype)):
+        assert not split or value is None, "%s: %s= with split=True (the split-key launch takes contiguous float32 caches with pos and count= only)" % (name, keyword)
 
 
 def _packed_rows(name, cu, count, pos, rows, k_cache, v_cache, m_max):
@@ -695,18 +714,19 @@ def _launch_extend_paged(name, q3, k3, v3, m, k_pool, v_pool, pos, count, block_
     return p
 
 
-def extend_attention_supported(q, heads, capacity, m_max=None):
+def extend_attention_supported(q, heads, capacity, m_max=None, split=False):
     """(m_max: the call is token-packed - `cu=` -: (1, T, heads * d) rows with any T >= 1 and pieces of at most m_max, default
     min(T, capacity))
     does `q.extend_attention(k_new, v_new, k_cache, v_cache, pos, heads, scale)` exist for this shape?  (b, m, heads * d) float32
-    with d = 32 or 64, b >= 1 and 1 <= m <= capacity <= 512"""
+    with d = 32 or 64, b >= 1 and 1 <= m <= capacity <= 512.  split=True: the question of `extend_attention(..., split=True)` -
+    a cache of 1 .. 16384 rows and 1 <= m <= min(capacity, 128); never with m_max="""
     sh = q._shape
-    return (len(sh) == 3 and q._dtype == _F32 and sh[0] > 0 and sh[2] % heads == 0
-            and bool(_l.lib().lg_attention_extend_supported(sh[1] if m_max is None else m_max, capacity, sh[2] // heads)))
+    return (len(sh) == 3 and q._dtype == _F32 and sh[0] > 0 and sh[2] % heads == 0 and not (split and m_max is not None)
+            and _extend_fits(sh[1] if m_max is None else m_max, capacity, sh[2] // heads, split))
 
 
 def extend_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False, count=None, cu=None, m_max=None,
-                     block_table=None, block_size=None, kv_dtype=None):
+                     block_table=None, block_size=None, kv_dtype=None, split=False, lse=False):
     """ attention of m NEW tokens per sequence against a filled key / value cache, one launch (lg_attention_extend_f32): with t =
     the int32 word `pos` holds ON THE DEVICE (`pos` of shape (b,): a position per sequence, t = pos[r] for sequence r, everything
     below per sequence - lg_attention_extend_rows_f32; a sequence with t + m beyond the cache writes nothing, the others are computed), rows i of k_new / v_new become rows t + i of the caches (b, capacity, heads * d) and
@@ -735,8 +755,14 @@ def extend_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0,
     lg_attention_extend_paged_bf16_f32.  With r = `bf16_round_array`, the result (and `.attention_probs`) is bit for bit that of
     the paged call on r(k_new), r(v_new) and `bf16_widen` of the pools, and the new rows are stored as `bf16_bits`: a key counts as
     r of it whichever call brought it in; q is not rounded.  int16 pools without the keyword, or the keyword with float32 pools,
-    are a TypeError. """
+    are a TypeError.
+    split=True: the split-key launch (lg_attention_extend_split_f32 / _rows_f32 / _counts_f32, csrc/extend_split.hip) - caches of
+    1 .. 16384 rows and 1 <= m <= min(capacity, 128), the keys of a block of 32 rows spread over workgroups and merged inside the
+    launch; `pos` and count= choose the entry as without it.  It returns no probabilities (probs=True is refused, and so are cu=,
+    m_max=, block_table=, block_size= and kv_dtype=); lse=True: `.attention_lse` (b, heads, m), the log of the sum of the
+    exponentials of the scores 0 .. t + i of row i, +0.0 for a row behind its count.  Without split= the call is the one it was. """
     name = "extend_attention"
+    _extend_split_options(name, probs, split, lse, cu, m_max, block_table, block_size, kv_dtype)
     _inference_only(name, q, k_new, v_new)
     _require_f32(q, k_new, v_new)
     assert kv_dtype is None or block_table is not None, "%s: kv_dtype= goes with a paged cache (block_table=, block_size=, count=): the contiguous " \
@@ -771,28 +797,33 @@ def extend_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0,
             out.attention_probs = p
         return out
     assert m_max is None, "%s: m_max= goes with cu=" % name
-    assert q._shape == k_new._shape == v_new._shape and extend_attention_supported(q, heads, k_cache._shape[1] if len(k_cache._shape) == 3 else 0), \
+    assert q._shape == k_new._shape == v_new._shape and \
+        extend_attention_supported(q, heads, k_cache._shape[1] if len(k_cache._shape) == 3 else 0, split=split), \
         "%s: unsupported shapes %s / %s / %s with %d heads and caches %s" % (name, q._shape, k_new._shape, v_new._shape, heads, k_cache._shape)
     _check_cache(name, k_cache, v_cache, pos, q._shape[0], q._shape[2])
     m = q._shape[1]
     (q, ldq, sbq), (k_new, ldk, sbk), (v_new, ldv, sbv) = (_token_rows_in_place(t, name) for t in (q, k_new, v_new))
     out = HipTensor.empty(q._shape, requires_grad=False)
     p = _launch_extend(name, (q.ptr, ldq, sbq), (k_new.ptr, ldk, sbk), (v_new.ptr, ldv, sbv), m, k_cache, v_cache, pos, out, heads, scale, mask, probs,
-                       **({} if count is None else {"count": count}))
+                       **({} if count is None else {"count": count}), **({"split": True, "lse": lse} if split else {}))
     if probs:
         out.attention_probs = p
+    if lse:
+        out.attention_lse = p
     return out
 
 
 def self_attention_extend(x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False, count=None, cu=None,
-                          m_max=None, block_table=None, block_size=None, kv_dtype=None):
+                          m_max=None, block_table=None, block_size=None, kv_dtype=None, split=False, lse=False):
     """ the one-node form of an append's attention: the three projections of the m new tokens in ONE launch (lg_gemm_multi3_f32,
     as in `self_attention`) into a (b, m, 3 * width) buffer that the extend launch reads in place - two launches per layer.
     x: (b, m, hidden); everything else as for `extend_attention`, `count=` included (the projections take all b * m rows) and
     `cu=` / `m_max=` too: x is (1, T, hidden) then, the projection launch runs on the T rows, the packed launch reads them in place.
     block_table= / block_size= with count=: the caches are pools and the second launch is the paged one - still two per layer;
-    kv_dtype="bf16": int16 pools of bfloat16 words, the second launch is lg_attention_extend_paged_bf16_f32 (see `extend_attention`). """
+    kv_dtype="bf16": int16 pools of bfloat16 words, the second launch is lg_attention_extend_paged_bf16_f32 (see `extend_attention`).
+    split=True / lse=True: the second launch is the split-key one (csrc/extend_split.hip), as for `extend_attention`. """
     name = "self_attention_extend"
+    _extend_split_options(name, probs, split, lse, cu, m_max, block_table, block_size, kv_dtype)
     _inference_only(name, x, wq, bq, wk, bk, wv, bv)
     _require_f32(x, wq, bq, wk, bk, wv, bv)
     assert cu is not None or m_max is None, "%s: m_max= goes with cu=" % name
@@ -825,7 +856,7 @@ def self_attention_extend(x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, head
     if cu is not None:
         assert len(k_cache._shape) == 3 and len(x._shape) == 3, "%s: expected (1, T, hidden) rows and (slots, capacity, width) caches" % name
         cu, slots, m_max = _packed_rows(name, cu, count, pos, x._shape, k_cache, v_cache, m_max)
-    assert self_attention_extend_supported(x, wq, heads, k_cache._shape[1] if len(k_cache._shape) == 3 else 0, m_max) and \
+    assert self_attention_extend_supported(x, wq, heads, k_cache._shape[1] if len(k_cache._shape) == 3 else 0, m_max, split=split) and \
         wq._shape == wk._shape == wv._shape and bq._shape == bk._shape == bv._shape == (wq._shape[0],), \
         "%s: unsupported shapes %s with weights %s / %s / %s, %d heads and caches %s" % (name, x._shape, wq._shape, wk._shape, wv._shape, heads, k_cache._shape)
     b, m, hidden = x._shape
@@ -846,20 +877,23 @@ def self_attention_extend(x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, head
             out.attention_probs = p
         return out
     p = _launch_extend(name, (base, ld, sb), (base + 4 * width, ld, sb), (base + 8 * width, ld, sb), m, k_cache, v_cache, pos, out, heads, scale,
-                       mask, probs, **({} if count is None else {"count": count}))
+                       mask, probs, **({} if count is None else {"count": count}), **({"split": True, "lse": lse} if split else {}))
     if probs:
         out.attention_probs = p
+    if lse:
+        out.attention_lse = p
     return out
 
 
-def self_attention_extend_supported(x, wq, heads, capacity, m_max=None):
+def self_attention_extend_supported(x, wq, heads, capacity, m_max=None, split=False):
     """(m_max: the call is token-packed - `cu=` -: x is (1, T, hidden) with any T >= 1 and pieces of at most m_max)
     does `x.self_attention_extend(...)` exist for these shapes?  (b, m, hidden) input, (width, hidden) weights with width =
-    heads * d, d = 32 or 64, width a multiple of 64, 1 <= m <= capacity <= 512"""
+    heads * d, d = 32 or 64, width a multiple of 64, 1 <= m <= capacity <= 512 (split=True: a cache of 1 .. 16384 rows and
+    1 <= m <= min(capacity, 128), the question of `self_attention_extend(..., split=True)`; never with m_max=)"""
     return (len(x._shape) == 3 and x._dtype == _F32 and len(wq._shape) == 2 and wq._shape[1] == x._shape[2]
             and wq._shape[0] % heads == 0 and wq._shape[0] % 64 == 0 and x._shape[2] % 4 == 0 and x._shape[0] > 0
-            and (m_max is None or x._shape[0] == 1)
-            and bool(_l.lib().lg_attention_extend_supported(x._shape[1] if m_max is None else m_max, capacity, wq._shape[0] // heads)))
+            and (m_max is None or (x._shape[0] == 1 and not split))
+            and _extend_fits(x._shape[1] if m_max is None else m_max, capacity, wq._shape[0] // heads, split))
 
 
 HipTensor.extend_attention, HipTensor.extend_attention_supported = extend_attention, extend_attention_supported

@@ -1,6 +1,6 @@
 // The host checks of the KV-cache attention entries: lg_attention_decode{,_rows}_f32 (decode.hip), lg_attention_decode_split{,_rows}_f32
-// (decode_split.hip), lg_attention_extend{,_rows,_counts,_packed}_f32 (extend.hip) and lg_attention_extend_paged{,_bf16}_f32
-// (paged.hip, paged_bf16.hip).  Host only; each entry calls these in its own order of refusal - shape, batch / heads, an empty
+// (decode_split.hip), lg_attention_extend{,_rows,_counts,_packed}_f32 (extend.hip), lg_attention_extend_split{,_rows,_counts}_f32
+// (extend_split.hip) and lg_attention_extend_paged{,_bf16}_f32 (paged.hip, paged_bf16.hip).  Host only; each entry calls these in its own order of refusal - shape, batch / heads, an empty
 // batch, operands, row pitch, mask pitch, overlaps, applied updates - and every message starts with the entry's own name.
 #pragma once
 #include "common.h"
