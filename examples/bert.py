@@ -57,6 +57,11 @@ Differences from the reference, on purpose:
                                                        # the same through TOKEN-PACKED steps: every step has 24 token rows for all slots
                                                        # together - one per decoding slot, the rest shared by the prefilling slots in
                                                        # pieces of at most 16 (`serve(token_budget=)`, csrc/serve_packed.hip)
+    python examples/bert.py --serve 8 --slots 4 --chunk 64 --num-blocks 96 --block-size 64 --no-attention-probs --prompt-length 1500 --positions 2048
+                                                       # a PAGED cache (`serve(num_blocks=)`, nn.PagedKVCache) beyond 512 positions: prompts
+                                                       # of some 1500 tokens from a pool of 96 blocks of 64 positions, every step one
+                                                       # paged split-key launch per layer (csrc/paged_split.hip, tables to 16384 positions);
+                                                       # [--shared-prefix L] [--kv-dtype bf16] as with short requests
     python examples/bert.py --serve 16 --sample --per-request [--seed S] [--graph] [--cpu]
                                                        # per-request sampling: request r has one of a short cycle of parameter sets
                                                        # (one of them greedy) and the random stream seeded S + r, so its tokens do not
@@ -423,6 +428,18 @@ class BertSelfAttention(nn.Module):
                                                        self.value.bias, cache.k[index], cache.v[index], cache.pos, heads=self.h,
                                                        scale=math.sqrt(self.d) ** -1, count=count, block_table=cache.block_table,
                                                        block_size=cache.block_size, **extra)
+                return context, None
+            if hasattr(hidden, "self_attention_extend") and mask_ok and \
+                    hidden.self_attention_extend_supported(self.query.weight, self.h, cache.capacity, split=True, block_size=cache.block_size):
+                # a table beyond the 512 positions of that launch (nn.PagedKVCache(..., split=True)): the paged split-key launch, up to
+                # 128 new rows behind up to 16384 positions read through the table (csrc/paged_split.hip) - float32 and bf16 pools alike
+                extra = {"mask": attention_mask} if attention_mask is not None else {}
+                if getattr(cache, "kv_dtype", None) is not None:
+                    extra["kv_dtype"] = cache.kv_dtype
+                context = hidden.self_attention_extend(self.query.weight, self.query.bias, self.key.weight, self.key.bias, self.value.weight,
+                                                       self.value.bias, cache.k[index], cache.v[index], cache.pos, heads=self.h,
+                                                       scale=math.sqrt(self.d) ** -1, count=count, block_table=cache.block_table,
+                                                       block_size=cache.block_size, split=True, **extra)
                 return context, None
             return self._paged_composite(hidden, attention_mask, cache, index, count)
         if cu is not None:
@@ -1512,6 +1529,9 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
     blocks that every slot's table names and nobody writes again, and every request starts at position F * block_size.  The step
     has the launches of the step without paging and is captured once with graph=; `stats` gains `num_blocks`, `block_size` and
     `prefix_blocks`.  token_budget= together with paging is refused.  Without num_blocks and a paged cache everything is as it was.
+    A request beyond 512 positions (prompt + budget - 1, rounded up to blocks): the cache is built with split=True and every step
+    takes the paged split-key launch (csrc/paged_split.hip), tables of up to 16384 positions; the model then has
+    attention_probs=False and that many position embeddings, and chunk <= 128.  token_budget= stays at 512 positions.
     kv_dtype="bf16" (with num_blocks=, or cache= an nn.PagedKVCache(kv_dtype="bf16")): the pools hold bfloat16 words, half the bytes
     (csrc/paged_bf16.hip).  Every key and value is attended to as r of what the projection produced (r = `bf16_round_array`),
     whichever step, chunk or shared prefix brought it in, so greedy tokens still depend on a request's own data only - but they
@@ -1541,8 +1561,11 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
             " - kv_dtype=\"bf16\" included: the packed launch reads a float32 nn.KVCache" if kv_dtype == "bf16" or getattr(cache, "kv_dtype", None) == "bf16" else "")
         if cache is None:
             assert int(block_size) == block_size and block_size >= 1 and int(num_blocks) == num_blocks and num_blocks >= 1
+            longest = int((lengths + budgets - 1).max())
+            # a request beyond the 512 positions of the paged launch: tables of up to 16384, served by the paged split-key launch
+            wide = -(-longest // int(block_size)) * int(block_size) > 512
             cache = nn.PagedKVCache(len(model.bert.encoder.layer), int(slots), int(num_blocks), int(block_size), layer0.h * layer0.d,
-                                    int(-(-int((lengths + budgets - 1).max()) // int(block_size))), like=weight, kv_dtype=kv_dtype)
+                                    int(-(-longest // int(block_size))), like=weight, kv_dtype=kv_dtype, **({"split": True} if wide else {}))
         assert isinstance(cache, nn.PagedKVCache), "serve: num_blocks= makes its own nn.PagedKVCache, or takes one as cache=, got a %s" % type(cache).__name__
         assert kv_dtype is None or cache.kv_dtype == kv_dtype, "serve: kv_dtype=%r and a cache= whose kv_dtype is %r" % (kv_dtype, cache.kv_dtype)
         shared = int(shared_prefix)
@@ -1550,6 +1573,11 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
             "serve: shared_prefix=%s declares the first tokens of every prompt equal: they are not, or a prompt is shorter" % (shared_prefix,)
         # full blocks only, and every request keeps a prompt token of its own
         prefix_blocks = min(shared // cache.block_size, (int(lengths.min()) - 1) // cache.block_size)
+        if cache.capacity > 512:
+            assert cache.capacity <= positions, "serve: a paged cache of %d positions exceeds the model's %d position embeddings" % (cache.capacity, positions)
+            assert not layer0.attention_probs, "serve: a paged cache beyond 512 positions takes the split-key launch, which stores no probabilities: " \
+                "build the model with attention_probs=False"
+            assert chunk <= 128, "serve: chunk=%d with a paged cache beyond 512 positions - the paged split-key launch appends at most 128 rows a step" % chunk
     else:
         assert not shared_prefix, "serve: shared_prefix= goes with a paged cache (num_blocks=)"
         assert kv_dtype is None, "serve: kv_dtype=%r goes with a paged cache (num_blocks=, or cache= an nn.PagedKVCache(kv_dtype=\"bf16\")): the contiguous " \
@@ -1646,10 +1674,16 @@ if __name__ == "__main__":
         option = lambda name, kind, default: kind(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default     # noqa: E731
         n_requests, n_slots, piece = option("--serve", int, 16), option("--slots", int, 4), option("--chunk", int, 16)
         np.random.seed(0)
-        lm = BertForMaskedLM(**dict(TINY, causal=True)).eval()
+        # --prompt-length P: prompts of P - 44 .. P - 1 tokens (default 48); --positions M: the model's position embeddings; with
+        # --no-attention-probs and --num-blocks, requests beyond 512 positions are served from the pool (csrc/paged_split.hip)
+        longest = option("--prompt-length", int, 48)
+        long_config = {"max_position_embeddings": option("--positions", int, 0)} if "--positions" in sys.argv else {}
+        if "--no-attention-probs" in sys.argv:
+            long_config["attention_probs"] = False
+        lm = BertForMaskedLM(**dict(TINY, causal=True, **long_config)).eval()
         if not cpu:
             lm.map_parameters(lambda t: t.hip())
-        requests = [np.random.randint(0, TINY["vocab_size"], np.random.randint(4, 48)) for _ in range(n_requests)]
+        requests = [np.random.randint(0, TINY["vocab_size"], np.random.randint(max(longest - 44, 1), longest)) for _ in range(n_requests)]
         if "--shared-prefix" in sys.argv:
             # every prompt behind one common prefix (a system prompt) of that many tokens
             common = np.random.randint(0, TINY["vocab_size"], option("--shared-prefix", int, 0))

@@ -939,6 +939,48 @@ int lg_serve_commit_paged_i32(const int32_t* nxt, int64_t nxt_pitch, const int32
                               int32_t* held, int32_t* free_stack,   /* (slots), (num_blocks + 1) */
                               int64_t slots, int64_t m, int64_t max_blocks, int64_t num_blocks, int64_t log2_block,
                               int64_t prefix_blocks, int32_t eos_id);   /* eos_id < 0: none */
+/* ---- the paged cache beyond 512 positions: the split-key launch through a block table (csrc/paged_split.hip) ---------------------
+ * lg_attention_extend_paged_split_f32: lg_attention_extend_split_counts_f32 with the caches POOLS reached through `block_table`, as
+ * lg_attention_extend_paged_f32 reaches them - the operands of that entry with `lse` (NULL, or (batch, heads, m) dense) in place
+ * of p; capacity = max_blocks << log2_block <= 16384.  Element b is bit for bit - o, lse, the new rows - what the contiguous counts
+ * entry computes on a (capacity, heads * D) cache that holds the same rows.  The grid is (ceil(capacity / L), ceil(m / 32) * heads,
+ * batch), L = lg_attention_extend_split_slice(); a workgroup stages the at most L / 4 table words of its own keys in LDS.  An
+ * element with a word outside 0 .. num_blocks - 1 among words 0 .. ceil((t + count[b]) / B) - 1 of its row (or with t < 0,
+ * t + count[b] > capacity, a count outside 0 .. m) writes NOTHING - no row of o, lse or a pool, no +0.0 row: each of its workgroups
+ * checks the whole live row before its first store and before it takes a ticket - and raises the status flag once; the others
+ * are computed; every ticket is zero when the launch ends.  Only pool rows of positions t .. t + count[b] - 1 are written.
+ * lg_attention_extend_paged_split_bf16_f32: the same over pools of BFLOAT16 words by the rule of lg_attention_extend_paged_bf16_f32 -
+ * o and lse bit for bit those of the fp32 entry on (q, r(k_new), r(v_new), widen(pools)), the new rows stored as bits(.).
+ * Supported (lg_attention_extend_paged_split_supported, pure host code): D = 32 or 64, 2 <= log2_block <= 7,
+ * 1 <= max_blocks << log2_block <= 16384, 1 <= m <= min(capacity, 128).  Checked in this order, each LG_EINVAL under the entry's
+ * name, before anything is launched: that shape; num_blocks; batch / heads, heads * ceil(m / 32) beyond 65535; (batch == 0 returns
+ * LG_OK here;) operands NULL, off their alignment (16 bytes, the bfloat16 pools 8) or with a pitch that is negative or no multiple
+ * of 4; count / block_table; lse not 4-byte aligned; ldc < heads * D; a mask with 0 < sbm < capacity; any overlap of what is
+ * written (pools, o, lse) with another operand (pools, new rows, pos, count, block_table, o, lse), or of pos with count; the
+ * ticket pool; a write into a gradient whose update has been applied. */
+int lg_attention_extend_paged_split_supported(int64_t m, int64_t max_blocks, int64_t log2_block, int64_t D);
+int lg_attention_extend_paged_split_f32(const float* q, int64_t ldq, int64_t sbq, const float* k_new, int64_t ldk, int64_t sbk,
+                                        const float* v_new, int64_t ldv, int64_t sbv,
+                                        float* k_pool, float* v_pool, int64_t ldc,      /* (num_blocks * B, heads*D) rows each */
+                                        const int32_t* pos, const int32_t* count,       /* (batch) each */
+                                        const int32_t* block_table,                     /* (batch, max_blocks) dense */
+                                        float* o, int64_t ldo, int64_t sbo,
+                                        float* lse,                                     /* NULL, or (batch, heads, m) dense */
+                                        int64_t batch, int64_t heads, int64_t m, int64_t max_blocks, int64_t num_blocks,
+                                        int64_t log2_block, int64_t D, float scale, const float* mask, int64_t sbm);
+int lg_attention_extend_paged_split_bf16_f32(const float* q, int64_t ldq, int64_t sbq, const float* k_new, int64_t ldk, int64_t sbk,
+                                             const float* v_new, int64_t ldv, int64_t sbv, uint16_t* k_pool, uint16_t* v_pool, int64_t ldc,
+                                             const int32_t* pos, const int32_t* count, const int32_t* block_table, float* o, int64_t ldo,
+                                             int64_t sbo, float* lse, int64_t batch, int64_t heads, int64_t m, int64_t max_blocks,
+                                             int64_t num_blocks, int64_t log2_block, int64_t D, float scale, const float* mask, int64_t sbm);
+/* lg_serve_commit_paged_wide_i32: lg_serve_commit_paged_i32 - the same kernel, the same checks - for tables of up to 16384
+ * positions (max_blocks << log2_block <= 16384), those of the launch above. */
+int lg_serve_commit_paged_wide_i32(const int32_t* nxt, int64_t nxt_pitch, const int32_t* prompts, int64_t prompt_pitch, int64_t P,
+                                   const int32_t* prompt_len, const int32_t* budget, int32_t* out, int64_t out_pitch, int64_t G,
+                                   int32_t* out_len, int32_t* queue, int64_t N, int32_t* req, int32_t* pos, int32_t* count, int32_t* ids,
+                                   int32_t* position_ids, int32_t* last, int32_t* block_table, int32_t* held, int32_t* free_stack,
+                                   int64_t slots, int64_t m, int64_t max_blocks, int64_t num_blocks, int64_t log2_block,
+                                   int64_t prefix_blocks, int32_t eos_id);
 /* The bookkeeping of one step of speculative decoding by prompt lookup in one launch (csrc/speculate.hip): one workgroup of 256
  * threads per row, 1 <= batch < 2^24.  The definition is the loop of `CpuTensor.speculate_commit` (autograd/cpu/ops.py), for each
  * row r on its own: (1) done[r] != 0: count[r] = 0, nothing else.  (2) c = count[r], p = pos[r]; unless 1 <= c <= m, p >= 0 and

@@ -813,8 +813,8 @@ def _check_paged_state(name, b, block_table, held, free, block_size, prefix_bloc
         "%s: block_table (b, max_blocks), held (b,) and free (num_blocks + 1,) are int32 - got %s" % (
             name, [(str(t.dtype), tuple(t.shape)) for t in (block_table, held, free)])
     MB, NB = block_table.shape[1], free.shape[0] - 1
-    assert int(block_size) == block_size and 4 <= block_size <= 128 and block_size & (block_size - 1) == 0 and 1 <= MB and MB * block_size <= 512, \
-        "%s: block_size is a power of two within 4 .. 128 and max_blocks * block_size <= 512, got %s and %d blocks per table" % (name, block_size, MB)
+    assert int(block_size) == block_size and 4 <= block_size <= 128 and block_size & (block_size - 1) == 0 and 1 <= MB and MB * block_size <= 16384, \
+        "%s: block_size is a power of two within 4 .. 128 and max_blocks * block_size <= 16384, got %s and %d blocks per table" % (name, block_size, MB)
     assert int(prefix_blocks) == prefix_blocks and 0 <= prefix_blocks <= MB and prefix_blocks <= NB, \
         "%s: prefix_blocks is an int within 0 .. max_blocks = %d and 0 .. num_blocks = %d, got %s" % (name, MB, NB, prefix_blocks)
     return MB, NB, int(block_size), int(prefix_blocks)

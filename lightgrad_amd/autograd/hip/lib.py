@@ -196,6 +196,13 @@ PROTOTYPES = {
                                            + [c_void_p, c_int64, c_int64] + [c_void_p] + [c_int64] * 7 + [c_float] + [c_void_p, c_int64]),
     "lg_serve_commit_paged_i32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
                                           c_int64] + [c_void_p] * 9 + [c_int64] * 6 + [ctypes.c_int32]),
+    "lg_attention_extend_paged_split_supported": (c_int, [c_int64] * 4),
+    "lg_attention_extend_paged_split_f32": (c_int, [c_void_p, c_int64, c_int64] * 3 + [c_void_p, c_void_p, c_int64] + [c_void_p, c_void_p, c_void_p]
+                                            + [c_void_p, c_int64, c_int64] + [c_void_p] + [c_int64] * 7 + [c_float] + [c_void_p, c_int64]),
+    "lg_attention_extend_paged_split_bf16_f32": (c_int, [c_void_p, c_int64, c_int64] * 3 + [c_void_p, c_void_p, c_int64] + [c_void_p, c_void_p, c_void_p]
+                                                 + [c_void_p, c_int64, c_int64] + [c_void_p] + [c_int64] * 7 + [c_float] + [c_void_p, c_int64]),
+    "lg_serve_commit_paged_wide_i32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
+                                               c_int64] + [c_void_p] * 9 + [c_int64] * 6 + [ctypes.c_int32]),
     "lg_speculate_commit_i32": (c_int, [c_void_p] * 5 + [c_int64, c_int64] + [c_void_p] * 4 + [c_int64] * 5 + [ctypes.c_int32]),
     "lg_beam_step_f32": (c_int, [c_void_p, c_int64] + [c_void_p] * 4 + [c_int64, c_int64] + [c_void_p] * 3 + [c_int64] * 3 + [ctypes.c_int32]),
     "lg_beam_reorder_f32": (c_int, [POINTER(c_void_p)] + [c_int64] * 5 + [c_void_p, c_void_p, c_int64, c_int64]),

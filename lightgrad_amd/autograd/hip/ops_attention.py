@@ -617,15 +617,28 @@ def _launch_extend(name, q3, k3, v3, m, k_cache, v_cache, pos, out, heads, scale
     return p
 
 
-def _extend_fits(m, capacity, d, split):
-    """the 512-row launches of csrc/extend.hip, or with split=True the split-key launch of csrc/extend_split.hip (1 .. 16384 rows, m <= 128)"""
+def _extend_fits(m, capacity, d, split, block_size=None):
+    """the 512-row launches of csrc/extend.hip, or with split=True the split-key launch of csrc/extend_split.hip (1 .. 16384 rows, m <= 128);
+    split=True with block_size=: the paged split-key launch of csrc/paged_split.hip (tables of capacity / block_size words)"""
+    if split and block_size is not None:
+        B = int(block_size)
+        return B == block_size and B >= 1 and B & (B - 1) == 0 and capacity % B == 0 and \
+            bool(_l.lib().lg_attention_extend_paged_split_supported(m, capacity // B, B.bit_length() - 1, d))
     return bool((_l.lib().lg_attention_extend_split_supported if split else _l.lib().lg_attention_extend_supported)(m, capacity, d))
 
 
-def _extend_split_options(name, probs, split, lse, cu, m_max, block_table, block_size, kv_dtype):
+def _extend_split_options(name, probs, split, lse, cu, m_max, block_table, block_size, kv_dtype, count):
     _split_options(name, probs, split, lse)
-    for keyword, value in (("cu", cu), ("m_max", m_max), ("block_table", block_table), ("block_size", block_size), ("kv_dtype", kv_dtype)):
-        assert not split or value is None, "%s: %s= with split=True (the split-key launch takes contiguous float32 caches with pos and count= only)" % (name, keyword)
+    if not split:
+        return
+    for keyword, value in (("cu", cu), ("m_max", m_max)):
+        assert value is None, "%s: %s= with split=True (the split-key launches take pos and count=, over contiguous caches or a block table, never " \
+            "token-packed rows)" % (name, keyword)
+    assert block_table is None or (isinstance(block_table, HipTensor) and block_table._dtype == _I32 and block_size is not None and count is not None), \
+        "%s: block_table= with split=True takes an int32 HipTensor with block_size= and count= (csrc/paged_split.hip)" % name
+    assert block_size is None or block_table is not None, "%s: block_size= with split=True goes with block_table= and count=" % name
+    assert kv_dtype is None or (kv_dtype == "bf16" and block_table is not None), \
+        "%s: kv_dtype= with split=True is \"bf16\" next to block_table=, block_size= and count= (int16 pools of bfloat16 words)" % name
 
 
 def _packed_rows(name, cu, count, pos, rows, k_cache, v_cache, m_max):
@@ -659,10 +672,11 @@ def _launch_extend_packed(name, q2, k2, v2, T, k_cache, v_cache, pos, cu, m_max,
 _I16 = np.dtype(np.int16)
 
 
-def _block_table(name, block_table, block_size, count, pos, rows, k_pool, v_pool, kv_dtype=None):
+def _block_table(name, block_table, block_size, count, pos, rows, k_pool, v_pool, kv_dtype=None, positions=512):
     """the `block_table=` / `block_size=` operands of the extend ops as the paged launch reads them: (table, B).  int32 (b, max_blocks)
     next to (b, m, width) token rows, pools (num_blocks, B, width), a count and a pos of shape (b,); dense, apart from the pools, pos
-    and count.  kv_dtype: None - float32 pools -, or "bf16" - int16 pools of bfloat16 words; each form refuses the other's pools"""
+    and count.  kv_dtype: None - float32 pools -, or "bf16" - int16 pools of bfloat16 words; each form refuses the other's pools.
+    positions: the most a table may cover - 512, or 16384 for the split-key launch"""
     assert kv_dtype in (None, "bf16"), "%s: kv_dtype is None (float32 pools) or \"bf16\" (int16 pools of bfloat16 words), got %r" % (name, kv_dtype)
     for c in (k_pool, v_pool):
         if isinstance(c, HipTensor) and c._dtype == _I16 and kv_dtype is None:
@@ -678,9 +692,9 @@ def _block_table(name, block_table, block_size, count, pos, rows, k_pool, v_pool
     assert B == block_size and 4 <= B <= 128 and B & (B - 1) == 0, "%s: block_size is a power of two within 4 .. 128, got %s" % (name, block_size)
     b, width = rows[0], rows[2]
     assert isinstance(block_table, HipTensor) and block_table._dtype == _I32 and len(block_table._shape) == 2 and block_table._shape[0] == b \
-        and 1 <= block_table._shape[1] and block_table._shape[1] * B <= 512, \
-        "%s: block_table is an int32 HipTensor (batch, max_blocks) = (%d, *) with max_blocks * block_size <= 512, got %s %s" % (
-            name, b, getattr(block_table, "_dtype", type(block_table).__name__), getattr(block_table, "_shape", ""))
+        and 1 <= block_table._shape[1] and block_table._shape[1] * B <= positions, \
+        "%s: block_table is an int32 HipTensor (batch, max_blocks) = (%d, *) with max_blocks * block_size <= %d, got %s %s" % (
+            name, b, positions, getattr(block_table, "_dtype", type(block_table).__name__), getattr(block_table, "_shape", ""))
     for c in (k_pool, v_pool):
         assert isinstance(c, HipTensor) and c._dtype == pool_dtype and len(c._shape) == 3 and c._shape[0] >= 1 and c._shape[1] == B and c._shape[2] == width, \
             "%s: the pools are %s (num_blocks, block_size, width) = (*, %d, %d) tensors, got %s" % (name, pool_dtype, B, width, getattr(c, "_shape", c))
@@ -699,30 +713,36 @@ def _block_table(name, block_table, block_size, count, pos, rows, k_pool, v_pool
     return (block_table if block_table.is_contiguous() else block_table.contiguous()), B
 
 
-def _launch_extend_paged(name, q3, k3, v3, m, k_pool, v_pool, pos, count, block_table, B, out, heads, scale, mask, probs):
-    """q3, k3, v3: (address, row pitch, batch pitch); out: (b, m, width) dense.  Returns the probabilities (b, heads, m, capacity) or None.
+def _launch_extend_paged(name, q3, k3, v3, m, k_pool, v_pool, pos, count, block_table, B, out, heads, scale, mask, probs, split=False, lse=False):
+    """q3, k3, v3: (address, row pitch, batch pitch); out: (b, m, width) dense.  Returns the probabilities (b, heads, m, capacity) or None;
+    split=True (csrc/paged_split.hip): the log-sum-exp (b, heads, m) or None in their place.
     int16 pools (bfloat16 words; `_block_table` has matched them with kv_dtype=) take the bf16 entry, the same argument list"""
     b, max_blocks = block_table._shape
     num_blocks, _, width = k_pool._shape
     capacity = max_blocks * B
     count, pos = _dense_words(count, b), _dense_words(pos, b)
-    mask3, p = _cache_launch(name, mask, b, capacity, k_pool, v_pool, (b, heads, m, capacity) if probs else None)
-    entry = _l.lib().lg_attention_extend_paged_bf16_f32 if k_pool._dtype == _I16 else _l.lib().lg_attention_extend_paged_f32
+    if split:
+        shape = (b, heads, m) if lse else None
+    else:
+        shape = (b, heads, m, capacity) if probs else None
+    mask3, p = _cache_launch(name, mask, b, capacity, k_pool, v_pool, shape)
+    entry = getattr(_l.lib(), "lg_attention_extend_paged%s%s_f32" % ("_split" if split else "", "_bf16" if k_pool._dtype == _I16 else ""))
     _l.check(entry(*q3, *k3, *v3, k_pool.ptr, v_pool.ptr, k_pool._strides[1], pos.ptr, count.ptr, block_table.ptr,
-                   out.ptr, width, m * width, p.ptr if probs else None, b, heads, m, max_blocks, num_blocks,
+                   out.ptr, width, m * width, p.ptr if p is not None else None, b, heads, m, max_blocks, num_blocks,
                    B.bit_length() - 1, width // heads, float(scale), mask3[1], mask3[2]))
     return p
 
 
-def extend_attention_supported(q, heads, capacity, m_max=None, split=False):
+def extend_attention_supported(q, heads, capacity, m_max=None, split=False, block_size=None):
     """(m_max: the call is token-packed - `cu=` -: (1, T, heads * d) rows with any T >= 1 and pieces of at most m_max, default
     min(T, capacity))
     does `q.extend_attention(k_new, v_new, k_cache, v_cache, pos, heads, scale)` exist for this shape?  (b, m, heads * d) float32
     with d = 32 or 64, b >= 1 and 1 <= m <= capacity <= 512.  split=True: the question of `extend_attention(..., split=True)` -
-    a cache of 1 .. 16384 rows and 1 <= m <= min(capacity, 128); never with m_max="""
+    a cache of 1 .. 16384 rows and 1 <= m <= min(capacity, 128); never with m_max=.  split=True with block_size= B: the question of
+    `extend_attention(..., count=, block_table=, block_size=B, split=True)` - a table of capacity / B blocks of B = 4 .. 128 rows"""
     sh = q._shape
     return (len(sh) == 3 and q._dtype == _F32 and sh[0] > 0 and sh[2] % heads == 0 and not (split and m_max is not None)
-            and _extend_fits(sh[1] if m_max is None else m_max, capacity, sh[2] // heads, split))
+            and _extend_fits(sh[1] if m_max is None else m_max, capacity, sh[2] // heads, split, block_size if split else None))
 
 
 def extend_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False, count=None, cu=None, m_max=None,
@@ -758,28 +778,32 @@ def extend_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0,
     are a TypeError.
     split=True: the split-key launch (lg_attention_extend_split_f32 / _rows_f32 / _counts_f32, csrc/extend_split.hip) - caches of
     1 .. 16384 rows and 1 <= m <= min(capacity, 128), the keys of a block of 32 rows spread over workgroups and merged inside the
-    launch; `pos` and count= choose the entry as without it.  It returns no probabilities (probs=True is refused, and so are cu=,
-    m_max=, block_table=, block_size= and kv_dtype=); lse=True: `.attention_lse` (b, heads, m), the log of the sum of the
+    launch; `pos` and count= choose the entry as without it.  It returns no probabilities (probs=True is refused, and so are cu= and
+    m_max=).  With count=, block_table= and block_size= the cache is PAGED there too - one launch of lg_attention_extend_paged_split_f32
+    (csrc/paged_split.hip; kv_dtype="bf16": lg_attention_extend_paged_split_bf16_f32), tables of up to 16384 positions, sequence r bit
+    for bit what the contiguous split call computes on the same rows, a bad table word as without split=; lse=True: `.attention_lse` (b, heads, m), the log of the sum of the
     exponentials of the scores 0 .. t + i of row i, +0.0 for a row behind its count.  Without split= the call is the one it was. """
     name = "extend_attention"
-    _extend_split_options(name, probs, split, lse, cu, m_max, block_table, block_size, kv_dtype)
+    _extend_split_options(name, probs, split, lse, cu, m_max, block_table, block_size, kv_dtype, count)
     _inference_only(name, q, k_new, v_new)
     _require_f32(q, k_new, v_new)
     assert kv_dtype is None or block_table is not None, "%s: kv_dtype= goes with a paged cache (block_table=, block_size=, count=): the contiguous " \
         "caches are float32" % name
     if block_table is not None or block_size is not None:
         assert cu is None and m_max is None, "%s: block_table= (a paged cache) goes with count=, not with cu= (token-packed rows)" % name
-        block_table, B = _block_table(name, block_table, block_size, count, pos, q._shape, k_cache, v_cache, kv_dtype)
+        block_table, B = _block_table(name, block_table, block_size, count, pos, q._shape, k_cache, v_cache, kv_dtype, 16384 if split else 512)
         capacity = block_table._shape[1] * B
-        assert q._shape == k_new._shape == v_new._shape and extend_attention_supported(q, heads, capacity), \
+        assert q._shape == k_new._shape == v_new._shape and extend_attention_supported(q, heads, capacity, split=split, block_size=B), \
             "%s: unsupported shapes %s / %s / %s with %d heads and a paged cache of %d positions" % (name, q._shape, k_new._shape, v_new._shape, heads, capacity)
         m = q._shape[1]
         (q, ldq, sbq), (k_new, ldk, sbk), (v_new, ldv, sbv) = (_token_rows_in_place(t, name) for t in (q, k_new, v_new))
         out = HipTensor.empty(q._shape, requires_grad=False)
         p = _launch_extend_paged(name, (q.ptr, ldq, sbq), (k_new.ptr, ldk, sbk), (v_new.ptr, ldv, sbv), m, k_cache, v_cache, pos, count, block_table, B, out,
-                                 heads, scale, mask, probs)
+                                 heads, scale, mask, probs, split, lse)
         if probs:
             out.attention_probs = p
+        if lse:
+            out.attention_lse = p
         return out
     if cu is not None:
         assert len(k_cache._shape) == 3 and len(q._shape) == 3, "%s: expected (1, T, width) rows and (slots, capacity, width) caches" % name
@@ -821,9 +845,10 @@ def self_attention_extend(x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, head
     `cu=` / `m_max=` too: x is (1, T, hidden) then, the projection launch runs on the T rows, the packed launch reads them in place.
     block_table= / block_size= with count=: the caches are pools and the second launch is the paged one - still two per layer;
     kv_dtype="bf16": int16 pools of bfloat16 words, the second launch is lg_attention_extend_paged_bf16_f32 (see `extend_attention`).
-    split=True / lse=True: the second launch is the split-key one (csrc/extend_split.hip), as for `extend_attention`. """
+    split=True / lse=True: the second launch is the split-key one (csrc/extend_split.hip; with block_table=: csrc/paged_split.hip), as
+    for `extend_attention`. """
     name = "self_attention_extend"
-    _extend_split_options(name, probs, split, lse, cu, m_max, block_table, block_size, kv_dtype)
+    _extend_split_options(name, probs, split, lse, cu, m_max, block_table, block_size, kv_dtype, count)
     _inference_only(name, x, wq, bq, wk, bk, wv, bv)
     _require_f32(x, wq, bq, wk, bk, wv, bv)
     assert cu is not None or m_max is None, "%s: m_max= goes with cu=" % name
@@ -833,8 +858,9 @@ def self_attention_extend(x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, head
     if paged:
         assert cu is None, "%s: block_table= (a paged cache) goes with count=, not with cu= (token-packed rows)" % name
         assert len(x._shape) == 3 and len(wq._shape) == 2, "%s: expected (b, m, hidden) rows and (width, hidden) weights" % name
-        block_table, B = _block_table(name, block_table, block_size, count, pos, (x._shape[0], x._shape[1], wq._shape[0]), k_cache, v_cache, kv_dtype)
-        assert self_attention_extend_supported(x, wq, heads, block_table._shape[1] * B) and \
+        block_table, B = _block_table(name, block_table, block_size, count, pos, (x._shape[0], x._shape[1], wq._shape[0]), k_cache, v_cache, kv_dtype,
+                                      16384 if split else 512)
+        assert self_attention_extend_supported(x, wq, heads, block_table._shape[1] * B, split=split, block_size=B) and \
             wq._shape == wk._shape == wv._shape and bq._shape == bk._shape == bv._shape == (wq._shape[0],), \
             "%s: unsupported shapes %s with weights %s / %s / %s, %d heads and a paged cache of %d positions" % (
                 name, x._shape, wq._shape, wk._shape, wv._shape, heads, block_table._shape[1] * B)
@@ -849,9 +875,11 @@ def self_attention_extend(x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, head
         out = HipTensor.empty((b, m, width), requires_grad=False)
         ld, sb = 3 * width, m * 3 * width
         p = _launch_extend_paged(name, (base, ld, sb), (base + 4 * width, ld, sb), (base + 8 * width, ld, sb), m, k_cache, v_cache, pos, count, block_table,
-                                 B, out, heads, scale, mask, probs)
+                                 B, out, heads, scale, mask, probs, split, lse)
         if probs:
             out.attention_probs = p
+        if lse:
+            out.attention_lse = p
         return out
     if cu is not None:
         assert len(k_cache._shape) == 3 and len(x._shape) == 3, "%s: expected (1, T, hidden) rows and (slots, capacity, width) caches" % name
@@ -885,15 +913,16 @@ def self_attention_extend(x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, head
     return out
 
 
-def self_attention_extend_supported(x, wq, heads, capacity, m_max=None, split=False):
+def self_attention_extend_supported(x, wq, heads, capacity, m_max=None, split=False, block_size=None):
     """(m_max: the call is token-packed - `cu=` -: x is (1, T, hidden) with any T >= 1 and pieces of at most m_max)
     does `x.self_attention_extend(...)` exist for these shapes?  (b, m, hidden) input, (width, hidden) weights with width =
     heads * d, d = 32 or 64, width a multiple of 64, 1 <= m <= capacity <= 512 (split=True: a cache of 1 .. 16384 rows and
-    1 <= m <= min(capacity, 128), the question of `self_attention_extend(..., split=True)`; never with m_max=)"""
+    1 <= m <= min(capacity, 128), the question of `self_attention_extend(..., split=True)`; never with m_max=; with block_size= B
+    the question of the paged call `self_attention_extend(..., count=, block_table=, block_size=B, split=True)`)"""
     return (len(x._shape) == 3 and x._dtype == _F32 and len(wq._shape) == 2 and wq._shape[1] == x._shape[2]
             and wq._shape[0] % heads == 0 and wq._shape[0] % 64 == 0 and x._shape[2] % 4 == 0 and x._shape[0] > 0
             and (m_max is None or (x._shape[0] == 1 and not split))
-            and _extend_fits(x._shape[1] if m_max is None else m_max, capacity, wq._shape[0] // heads, split))
+            and _extend_fits(x._shape[1] if m_max is None else m_max, capacity, wq._shape[0] // heads, split, block_size if split else None))
 
 
 HipTensor.extend_attention, HipTensor.extend_attention_supported = extend_attention, extend_attention_supported
@@ -1153,8 +1182,10 @@ def serve_commit_paged(nxt, prompts, prompt_len, budget, out, out_len, queue, re
     MB, NB, B, F = _check_paged_state(name, b, block_table, held, free, block_size, prefix_blocks)
     leading = _serve_commit_operands(name, b, N, operands[:4], operands[4:],
                                      "out_len, queue, req, pos, count, last, ids, position_ids, block_table, held and free")
-    _l.check(_l.lib().lg_serve_commit_paged_i32(*leading, ids.ptr, position_ids.ptr, last.ptr, block_table.ptr, held.ptr, free.ptr, b, m, MB, NB,
-                                                B.bit_length() - 1, F, -1 if eos is None else int(eos)))
+    # tables beyond 512 positions (nn.PagedKVCache(..., split=True)): the same kernel behind the entry with the wide bound
+    entry = _l.lib().lg_serve_commit_paged_wide_i32 if MB * B > 512 else _l.lib().lg_serve_commit_paged_i32
+    _l.check(entry(*leading, ids.ptr, position_ids.ptr, last.ptr, block_table.ptr, held.ptr, free.ptr, b, m, MB, NB,
+                   B.bit_length() - 1, F, -1 if eos is None else int(eos)))
 
 
 HipTensor.serve_commit_paged = serve_commit_paged

@@ -1,6 +1,7 @@
 // The host checks of the KV-cache attention entries: lg_attention_decode{,_rows}_f32 (decode.hip), lg_attention_decode_split{,_rows}_f32
 // (decode_split.hip), lg_attention_extend{,_rows,_counts,_packed}_f32 (extend.hip), lg_attention_extend_split{,_rows,_counts}_f32
-// (extend_split.hip) and lg_attention_extend_paged{,_bf16}_f32 (paged.hip, paged_bf16.hip).  Host only; each entry calls these in its own order of refusal - shape, batch / heads, an empty
+// (extend_split.hip), lg_attention_extend_paged{,_bf16}_f32 (paged.hip, paged_bf16.hip) and lg_attention_extend_paged_split{,_bf16}_f32
+// (paged_split.hip).  Host only; each entry calls these in its own order of refusal - shape, batch / heads, an empty
 // batch, operands, row pitch, mask pitch, overlaps, applied updates - and every message starts with the entry's own name.
 #pragma once
 #include "common.h"
@@ -121,6 +122,50 @@ inline int extend_check_caches(const char* name, const float* q, const float* k_
     return cache_check_pos(name, pos, pos_words, k_cache, v_cache, bytes);
 }
 
+// The paged entries behind their shape checks (batch >= 1): operands, row pitch, mask pitch, overlaps, the ticket pool, applied
+// updates.  `item` / `align`: bytes of a pool element and the alignment of the pools; `extra`: the dense optional output - "p" of
+// the 512-row launches, 16-byte aligned, or "lse" of the split-key ones, 4-byte aligned -, `extra_bytes` of it; `other`: the entry
+// that takes float32 pools where this one takes bfloat16 words; `triples`: the tickets the launch counts on (0: none)
+inline int paged_check_operands(const char* name, int item, int align, const char* other, const float* q, int64_t ldq, int64_t sbq, const float* k_new,
+                                int64_t ldk, int64_t sbk, const float* v_new, int64_t ldv, int64_t sbv, const void* k_pool, const void* v_pool,
+                                int64_t ldc, const int32_t* pos, const int32_t* count, const int32_t* block_table, const float* o, int64_t ldo,
+                                int64_t sbo, const float* extra, const char* extra_what, int64_t extra_bytes, int64_t batch, int64_t heads, int64_t m,
+                                int64_t max_blocks, int64_t num_blocks, int64_t log2_block, int64_t D, const float* mask, int64_t sbm, int64_t triples) {
+    const int64_t B = int64_t(1) << log2_block, capacity = max_blocks * B;
+    const bool is_p = extra_what[0] == 'p';
+    const bool pools = k_pool && v_pool && ((reinterpret_cast<uintptr_t>(k_pool) | reinterpret_cast<uintptr_t>(v_pool)) & uintptr_t(align - 1)) == 0 &&
+                       ldc >= 0 && ldc % 4 == 0;
+    int rc = extend_check_operands(name, q, k_new, v_new, o, {ldq, ldk, ldv, ldo}, {sbq, sbk, sbv, sbo}, item == 2 || pools, pos, is_p ? extra : nullptr);
+    if (rc != LG_OK) return rc;
+    // (float32 pools were refused with the operands above)
+    LG_ARG(pools, "%s: the bfloat16 pools must be non-NULL and 8-byte aligned with a row pitch that is a non-negative multiple of 4 elements (the float32 pools "
+           "go to %s)", name, other);
+    LG_ARG(cache_words(count) && cache_words(block_table), "%s: count and block_table must be non-NULL and 4-byte aligned", name);
+    LG_ARG(is_p || (reinterpret_cast<uintptr_t>(extra) & 3u) == 0, "%s: lse must be 4-byte aligned (or NULL)", name);
+    const int64_t w = heads * D, rows = num_blocks * B;
+    rc = cache_check_row_pitch(name, "pool", ldc, w);
+    if (rc != LG_OK) return rc;
+    rc = cache_check_mask(name, mask, sbm, capacity, "batch", "the batch");
+    if (rc != LG_OK) return rc;
+    {
+        // what the launch writes - the pools (`item` bytes an element), o, p or lse - shares no byte with any other operand it reads or
+        // writes: other workgroups of the launch read the new rows, the positions, the counts and the tables while the pools are written
+        const void* ptr[9] = {k_pool, v_pool, o, extra, k_new, v_new, pos, count, block_table};
+        const char* what[9] = {"k_pool", "v_pool", "o", extra_what, "k_new", "v_new", "pos", "count", "block_table"};
+        const int64_t pool_bytes = cache_span(1, 0, rows, ldc, w) * item;
+        const int64_t bytes[9] = {pool_bytes, pool_bytes, cache_span(batch, sbo, m, ldo, w) * 4, extra_bytes,
+                                  cache_span(batch, sbk, m, ldk, w) * 4, cache_span(batch, sbv, m, ldv, w) * 4, batch * 4, batch * 4, batch * max_blocks * 4};
+        for (int i = 0; i < 4; ++i)
+            for (int j = i + 1; j < 9; ++j)
+                LG_ARG(!bytes_overlap(ptr[i], bytes[i], ptr[j], bytes[j]), "%s: %s overlaps %s: the launch writes the one while other workgroups use the other",
+                       name, what[i], what[j]);
+        LG_ARG(!bytes_overlap(pos, bytes[6], count, bytes[7]), "%s: count overlaps pos", name);
+    }
+    LG_ARG(triples <= rt().n_tickets, "%s: the ticket pool holds %d counters, %lld (batch, head, query block) triples need one each", name,
+           rt().n_tickets, (long long)triples);
+    return cache_check_writes(o, batch, sbo, m, ldo, k_pool, v_pool, item, 1, 0, rows, ldc, w, extra, extra_bytes);
+}
+
 // Everything lg_attention_extend_paged_f32 (item = 4 bytes a pool element, pools aligned to align = 16) and
 // lg_attention_extend_paged_bf16_f32 (2, 8: a lane loads and stores 4 pool words = 8 bytes at once) refuse, in their order.
 // max_table / max_keys: kPagedMaxTable / kExtMaxKeys of extend_body.h.  *capacity = max_blocks << log2_block.  The caller returns
@@ -140,34 +185,32 @@ inline int paged_check(const char* name, int item, int align, int max_table, int
            (long long)num_blocks, (long long)B);
     rc = cache_check_grid(name, "batch", batch, 65535, heads);
     if (rc != LG_OK || batch == 0) return rc;
-    const bool pools = k_pool && v_pool && ((reinterpret_cast<uintptr_t>(k_pool) | reinterpret_cast<uintptr_t>(v_pool)) & uintptr_t(align - 1)) == 0 &&
-                       ldc >= 0 && ldc % 4 == 0;
-    rc = extend_check_operands(name, q, k_new, v_new, o, {ldq, ldk, ldv, ldo}, {sbq, sbk, sbv, sbo}, item == 2 || pools, pos, p);
+    return paged_check_operands(name, item, align, "lg_attention_extend_paged_f32", q, ldq, sbq, k_new, ldk, sbk, v_new, ldv, sbv, k_pool, v_pool, ldc, pos,
+                                count, block_table, o, ldo, sbo, p, "p", batch * heads * m * capacity * 4, batch, heads, m, max_blocks, num_blocks,
+                                log2_block, D, mask, sbm, 0);
+}
+
+// ... and lg_attention_extend_paged_split_f32 / _bf16_f32 (paged_split.hip): tables of up to 16384 positions, m <= 128 rows, lse
+// (NULL, or (batch, heads, m)) in place of p, a ticket per (batch, head, query block) triple.  *capacity and the return as above
+inline int paged_split_check(const char* name, int item, int align, const float* q, int64_t ldq, int64_t sbq, const float* k_new, int64_t ldk, int64_t sbk,
+                             const float* v_new, int64_t ldv, int64_t sbv, const void* k_pool, const void* v_pool, int64_t ldc, const int32_t* pos,
+                             const int32_t* count, const int32_t* block_table, const float* o, int64_t ldo, int64_t sbo, const float* lse, int64_t batch,
+                             int64_t heads, int64_t m, int64_t max_blocks, int64_t num_blocks, int64_t log2_block, int64_t D, const float* mask,
+                             int64_t sbm, int64_t* capacity_out) {
+    LG_ARG(lg_attention_extend_paged_split_supported(m, max_blocks, log2_block, D),
+           "%s: m = %lld (1 .. min(capacity, 128)), blocks of 1 << %lld rows (4 .. 128), %lld of them per table (capacity 1 .. 16384), D = %lld (32 or 64) "
+           "unsupported", name, (long long)m, (long long)log2_block, (long long)max_blocks, (long long)D);
+    const int64_t B = int64_t(1) << log2_block, blocks = (m + 31) / 32;
+    *capacity_out = max_blocks * B;
+    LG_ARG(num_blocks >= 1 && num_blocks * B < (int64_t(1) << 31), "%s: a pool of %lld blocks of %lld rows (1 .. 2^31 - 1 rows) unsupported", name,
+           (long long)num_blocks, (long long)B);
+    const int rc = cache_check_grid(name, "batch", batch, 65535, heads);
     if (rc != LG_OK) return rc;
-    // (float32 pools were refused with the operands above)
-    LG_ARG(pools, "%s: the bfloat16 pools must be non-NULL and 8-byte aligned with a row pitch that is a non-negative multiple of 4 elements (the float32 pools "
-           "go to lg_attention_extend_paged_f32)", name);
-    LG_ARG(cache_words(count) && cache_words(block_table), "%s: count and block_table must be non-NULL and 4-byte aligned", name);
-    const int64_t w = heads * D, rows = num_blocks * B;
-    rc = cache_check_row_pitch(name, "pool", ldc, w);
-    if (rc != LG_OK) return rc;
-    rc = cache_check_mask(name, mask, sbm, capacity, "batch", "the batch");
-    if (rc != LG_OK) return rc;
-    {
-        // what the launch writes - the pools (`item` bytes an element), o, p - shares no byte with any other operand it reads or
-        // writes: other workgroups of the launch read the new rows, the positions, the counts and the tables while the pools are written
-        const void* ptr[9] = {k_pool, v_pool, o, p, k_new, v_new, pos, count, block_table};
-        const char* what[9] = {"k_pool", "v_pool", "o", "p", "k_new", "v_new", "pos", "count", "block_table"};
-        const int64_t pool_bytes = cache_span(1, 0, rows, ldc, w) * item;
-        const int64_t bytes[9] = {pool_bytes, pool_bytes, cache_span(batch, sbo, m, ldo, w) * 4, batch * heads * m * capacity * 4,
-                                  cache_span(batch, sbk, m, ldk, w) * 4, cache_span(batch, sbv, m, ldv, w) * 4, batch * 4, batch * 4, batch * max_blocks * 4};
-        for (int i = 0; i < 4; ++i)
-            for (int j = i + 1; j < 9; ++j)
-                LG_ARG(!bytes_overlap(ptr[i], bytes[i], ptr[j], bytes[j]), "%s: %s overlaps %s: the launch writes the one while other workgroups use the other",
-                       name, what[i], what[j]);
-        LG_ARG(!bytes_overlap(pos, bytes[6], count, bytes[7]), "%s: count overlaps pos", name);
-    }
-    return cache_check_writes(o, batch, sbo, m, ldo, k_pool, v_pool, item, 1, 0, rows, ldc, w, p, batch * heads * m * capacity * 4);
+    LG_ARG(heads * blocks <= 65535, "%s: %lld heads x %lld query blocks exceed a grid dimension of 65535", name, (long long)heads, (long long)blocks);
+    if (batch == 0) return LG_OK;
+    return paged_check_operands(name, item, align, "lg_attention_extend_paged_split_f32", q, ldq, sbq, k_new, ldk, sbk, v_new, ldv, sbv, k_pool, v_pool, ldc,
+                                pos, count, block_table, o, ldo, sbo, lse, "lse", batch * heads * m * 4, batch, heads, m, max_blocks, num_blocks, log2_block,
+                                D, mask, sbm, batch * heads * blocks);
 }
 
 }  // namespace lg

@@ -136,22 +136,20 @@ __global__ __launch_bounds__(kServeMaxSlots) void serve_commit_paged(const Paged
 
 using namespace lg;
 
-extern "C" int lg_serve_commit_paged_i32(const int32_t* nxt, int64_t nxt_pitch, const int32_t* prompts, int64_t prompt_pitch, int64_t P,
-                                         const int32_t* prompt_len, const int32_t* budget, int32_t* out, int64_t out_pitch, int64_t G,
-                                         int32_t* out_len, int32_t* queue, int64_t N, int32_t* req, int32_t* pos, int32_t* count, int32_t* ids,
-                                         int32_t* position_ids, int32_t* last, int32_t* block_table, int32_t* held, int32_t* free_stack,
-                                         int64_t slots, int64_t m, int64_t max_blocks, int64_t num_blocks, int64_t log2_block,
-                                         int64_t prefix_blocks, int32_t eos_id) {
-    LG_REQUIRE_INIT();
-    const char* name = "lg_serve_commit_paged_i32";
+// both entries: the kernel does not depend on the width of a table; `max_keys` is the capacity the entry's attention launch reaches
+static int serve_commit_paged_entry(const char* name, int64_t max_keys, const int32_t* nxt, int64_t nxt_pitch, const int32_t* prompts, int64_t prompt_pitch,
+                                    int64_t P, const int32_t* prompt_len, const int32_t* budget, int32_t* out, int64_t out_pitch, int64_t G,
+                                    int32_t* out_len, int32_t* queue, int64_t N, int32_t* req, int32_t* pos, int32_t* count, int32_t* ids,
+                                    int32_t* position_ids, int32_t* last, int32_t* block_table, int32_t* held, int32_t* free_stack, int64_t slots,
+                                    int64_t m, int64_t max_blocks, int64_t num_blocks, int64_t log2_block, int64_t prefix_blocks, int32_t eos_id) {
     const int64_t lim = int64_t(1) << 31;
     LG_ARG(slots >= 0 && slots <= kServeMaxSlots && m >= 1 && slots * m < lim && N >= 1 && N < lim && P >= 1 && P < lim && G >= 1 && G < lim,
            "%s: slots = %lld (0 .. 1024), m = %lld, N = %lld, P = %lld, G = %lld (each 1 .. 2^31 - 1, slots * m too) unsupported", name,
            (long long)slots, (long long)m, (long long)N, (long long)P, (long long)G);
-    LG_ARG(log2_block >= 2 && log2_block <= 7 && max_blocks >= 1 && (max_blocks << log2_block) <= 512 && num_blocks >= 1 &&
+    LG_ARG(log2_block >= 2 && log2_block <= 7 && max_blocks >= 1 && max_blocks <= max_keys && (max_blocks << log2_block) <= max_keys && num_blocks >= 1 &&
                (num_blocks << log2_block) < lim && prefix_blocks >= 0 && prefix_blocks <= max_blocks && prefix_blocks <= num_blocks,
-           "%s: blocks of 1 << %lld rows (4 .. 128), %lld per table (capacity 1 .. 512), %lld in the pool, %lld of them a shared prefix unsupported", name,
-           (long long)log2_block, (long long)max_blocks, (long long)num_blocks, (long long)prefix_blocks);
+           "%s: blocks of 1 << %lld rows (4 .. 128), %lld per table (capacity 1 .. %lld), %lld in the pool, %lld of them a shared prefix unsupported", name,
+           (long long)log2_block, (long long)max_blocks, (long long)max_keys, (long long)num_blocks, (long long)prefix_blocks);
     if (slots == 0) return LG_OK;
     const ServeOperands o{nxt, nxt_pitch, prompts, prompt_len, budget, prompt_pitch, out, out_len, out_pitch, queue, req, pos, count, ids, position_ids, last,
                           int(P), int(G), int(N), int(slots), eos_id, rt().status_dev};
@@ -166,4 +164,29 @@ extern "C" int lg_serve_commit_paged_i32(const int32_t* nxt, int64_t nxt_pitch, 
     hipLaunchKernelGGL(serve_commit_paged, dim3(1), dim3(unsigned((slots + 63) / 64 * 64)), 0, rt().stream, a);
     LG_CHECK_LAUNCH();
     return LG_OK;
+}
+
+extern "C" int lg_serve_commit_paged_i32(const int32_t* nxt, int64_t nxt_pitch, const int32_t* prompts, int64_t prompt_pitch, int64_t P,
+                                         const int32_t* prompt_len, const int32_t* budget, int32_t* out, int64_t out_pitch, int64_t G,
+                                         int32_t* out_len, int32_t* queue, int64_t N, int32_t* req, int32_t* pos, int32_t* count, int32_t* ids,
+                                         int32_t* position_ids, int32_t* last, int32_t* block_table, int32_t* held, int32_t* free_stack,
+                                         int64_t slots, int64_t m, int64_t max_blocks, int64_t num_blocks, int64_t log2_block,
+                                         int64_t prefix_blocks, int32_t eos_id) {
+    LG_REQUIRE_INIT();
+    return serve_commit_paged_entry("lg_serve_commit_paged_i32", 512, nxt, nxt_pitch, prompts, prompt_pitch, P, prompt_len, budget, out, out_pitch, G, out_len,
+                                    queue, N, req, pos, count, ids, position_ids, last, block_table, held, free_stack, slots, m, max_blocks, num_blocks,
+                                    log2_block, prefix_blocks, eos_id);
+}
+
+// the same launch for tables of up to 16384 positions, those of lg_attention_extend_paged_split_f32 (csrc/paged_split.hip)
+extern "C" int lg_serve_commit_paged_wide_i32(const int32_t* nxt, int64_t nxt_pitch, const int32_t* prompts, int64_t prompt_pitch, int64_t P,
+                                              const int32_t* prompt_len, const int32_t* budget, int32_t* out, int64_t out_pitch, int64_t G,
+                                              int32_t* out_len, int32_t* queue, int64_t N, int32_t* req, int32_t* pos, int32_t* count, int32_t* ids,
+                                              int32_t* position_ids, int32_t* last, int32_t* block_table, int32_t* held, int32_t* free_stack,
+                                              int64_t slots, int64_t m, int64_t max_blocks, int64_t num_blocks, int64_t log2_block,
+                                              int64_t prefix_blocks, int32_t eos_id) {
+    LG_REQUIRE_INIT();
+    return serve_commit_paged_entry("lg_serve_commit_paged_wide_i32", 16384, nxt, nxt_pitch, prompts, prompt_pitch, P, prompt_len, budget, out, out_pitch, G,
+                                    out_len, queue, N, req, pos, count, ids, position_ids, last, block_table, held, free_stack, slots, m, max_blocks,
+                                    num_blocks, log2_block, prefix_blocks, eos_id);
 }

@@ -431,12 +431,14 @@ class PagedKVCache(object):
     token-packed steps (`cu=`) and `generate` refuse it.  State, not parameters, like KVCache.  Not a class of the reference.
     kv_dtype="bf16": the pools are int16 tensors of the same shape that hold BFLOAT16 words - `light.bf16_bits` of every key and
     value, half the bytes (`pool_bytes`).  Every key and value is then attended to as r of what the projection produced
-    (r = `bf16_round_array`), whichever step brought it in; `kv_dtype` says which form the cache holds (None: the dtype of `like`)."""
+    (r = `bf16_round_array`), whichever step brought it in; `kv_dtype` says which form the cache holds (None: the dtype of `like`).
+    split=True: capacity <= 16384 - a step against the cache takes the paged split-key launch (csrc/paged_split.hip: up to 128 new
+    rows a step, no stored probabilities) wherever the 512-row launch does not reach; `split` says so."""
 
     per_row = True
     num_beams = 1
 
-    def __init__(self, layers: int, slots: int, num_blocks: int, block_size: int, width: int, max_blocks: int, like=None, kv_dtype=None):
+    def __init__(self, layers: int, slots: int, num_blocks: int, block_size: int, width: int, max_blocks: int, like=None, kv_dtype=None, split=False):
         cls = Tensor if like is None else type(like)
         assert kv_dtype in (None, "bf16"), "PagedKVCache: kv_dtype is None (the pools in the dtype of `like`) or \"bf16\", got %r" % (kv_dtype,)
         self.kv_dtype = kv_dtype
@@ -444,7 +446,10 @@ class PagedKVCache(object):
         assert layers >= 1 and slots >= 1 and num_blocks >= 1 and width >= 1 and max_blocks >= 1
         assert int(block_size) == block_size and 4 <= block_size <= 128 and block_size & (block_size - 1) == 0, \
             "PagedKVCache: block_size is a power of two within 4 .. 128, got %s" % (block_size,)
-        assert max_blocks * block_size <= 512, "PagedKVCache: max_blocks * block_size = %d positions exceed the 512 of the extend kernel" % (max_blocks * block_size)
+        self.split = bool(split)
+        assert max_blocks * block_size <= (16384 if self.split else 512), \
+            "PagedKVCache: max_blocks * block_size = %d positions exceed the %s" % (
+                max_blocks * block_size, "16384 of the split-key extend kernel" if self.split else "512 of the extend kernel (split=True: 16384)")
         self.layers, self.batch, self.slots, self.width = int(layers), int(slots), int(slots), int(width)
         self.num_blocks, self.block_size, self.max_blocks = int(num_blocks), int(block_size), int(max_blocks)
         self.capacity = self.max_blocks * self.block_size
