@@ -83,6 +83,7 @@ Differences from the reference, on purpose:
     python examples/bert.py --mlm --bf16-decoder       # the decoder onto the vocabulary (forward, dx, dW) on the bf16 matrix cores:
                                                        # config key `decoder_precision="bf16"`; tensors stay float32
 """
+import inspect
 import math
 import os
 import sys
@@ -162,6 +163,12 @@ class BertEmbedding(nn.Module):
             # the backend's one-launch form of the line below: the mask is drawn where the LayerNorm kernel stores its row
             return e.layer_norm_dropout(self.LayerNorm.weight, self.LayerNorm.bias, self.dropout.p, self.LayerNorm.eps)
         return self.dropout(self.LayerNorm(e))
+
+
+def _op_takes(method, keyword):
+    """does the backend's op behind a tensor method take this keyword?  (asked of the op's own `forward`, never of the backend's class)"""
+    op = getattr(method, "op", None)
+    return op is not None and keyword in inspect.signature(op.forward).parameters
 
 
 def _bf16_refusal(cache):
@@ -530,12 +537,16 @@ class BertSelfAttention(nn.Module):
         if self.causal:
             extra["causal"] = True
             drop = dict(drop, causal=True)
-        if not self.attention_probs and "dropout" not in drop and hasattr(hidden, "stream_attention") and (attention_mask is None or (
+        # attention dropout in training mode: the streaming node draws it inside its launches where the backend's op has the keyword
+        stream_drop = "dropout" in drop and _op_takes(getattr(hidden, "self_attention", None), "stream_dropout")
+        if not self.attention_probs and ("dropout" not in drop or stream_drop) and hasattr(hidden, "stream_attention") and (attention_mask is None or (
                 attention_mask.dtype == np.float32 and not attention_mask.requires_grad and tuple(attention_mask.shape) in ((b, s), (1, s)))) \
                 and hidden.self_attention_supported(self.query.weight, self.h, stream=True):
             # nobody reads the probabilities: the one-node form over the streaming launches, which store a log-sum-exp per row instead
-            # (attention dropout is not in those kernels: with it active the paths below run, as they did)
+            # (a backend whose node has no `stream_dropout=` runs the paths below when attention dropout is active, as it did)
             extra = {"mask": attention_mask} if attention_mask is not None else {}
+            if stream_drop:
+                extra.update(dropout=self.dropout.p, stream_dropout=True)
             context = hidden.self_attention(self.query.weight, self.query.bias, self.key.weight, self.key.bias,
                                             self.value.weight, self.value.bias, heads=self.h, scale=scale, causal=self.causal, probs=False, **extra)
             if cache is not None:

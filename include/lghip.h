@@ -649,6 +649,31 @@ int lg_attention_stream_bwd_f32(const float* q, int64_t ldq, int64_t sbq, const 
                                 float* dv, int64_t lddv, int64_t sbdv, int64_t batch, int64_t heads, int64_t S, int64_t D,
                                 float scale, const float* mask, int64_t sbm, int causal);
 
+/* The streaming launches with dropout of the probabilities inside them: `probs.dropout(p)` of the composite form between the
+ * softmax and the product with V, at every length the streaming entries take.  With keep / s / T of the random stream below:
+ *   forward    lse, and the running maximum and sum behind it, from the UNDROPPED scores;  O = Pd V,  Pd = keep ? fl(P * s) : +0.0
+ *   backward   dV = Pd^T dO;  dP = keep ? fl((dO V^T) * s) : +0.0;  dS = P o (dP - delta) * scale with the undropped P
+ * One forward is ONE call of the stream: `draws` advances by 1, read by the launch from device memory (a captured graph draws a
+ * fresh mask at every replay), element i of the call is the flat index ((b * heads + head) * S + row) * S + col into the dense
+ * (batch, heads, S, S) probabilities that are never stored - the mask `P.dropout(p)` draws.  No probability is kept, so each of
+ * the three launches forms the words of the tiles it visits again; tiles the causal bounds skip draw nothing.  The forward writes
+ * the call's number to `base` (one word of device memory); the two backward launches read the seed from the generator's state and
+ * the number from `base`, and draw nothing.  Arguments before `p` as for lg_attention_stream_fwd_f32 / _bwd_f32 and under their
+ * rules, checked first; then 0 <= p < 1 (p == 0 keeps everything and still draws once; a double, like every p of this header:
+ * T = floor(p * 2^32) is taken from it), base non-NULL, batch * heads * S * S <= 2^34 (what one call of the stream covers), and
+ * batch >= 1 in the forward: each LG_EINVAL. */
+int lg_attention_stream_dropout_fwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
+                                        const float* v, int64_t ldv, int64_t sbv, float* o, int64_t ldo, int64_t sbo, float* lse,
+                                        int64_t batch, int64_t heads, int64_t S, int64_t D, float scale,
+                                        const float* mask, int64_t sbm, int causal, double p, unsigned long long* base);
+int lg_attention_stream_dropout_bwd_f32(const float* q, int64_t ldq, int64_t sbq, const float* k, int64_t ldk, int64_t sbk,
+                                        const float* v, int64_t ldv, int64_t sbv, const float* o, int64_t ldo, int64_t sbo,
+                                        const float* g, int64_t ldg, int64_t sbg, const float* lse, float* delta,
+                                        float* dq, int64_t lddq, int64_t sbdq, float* dk, int64_t lddk, int64_t sbdk,
+                                        float* dv, int64_t lddv, int64_t sbdv, int64_t batch, int64_t heads, int64_t S, int64_t D,
+                                        float scale, const float* mask, int64_t sbm, int causal, double p,
+                                        const unsigned long long* base);
+
 /* ---- attention of ONE new token against a key / value cache (csrc/decode.hip) -----------------------------
  * Incremental decoding of the causal model: with t = *pos, the position of the new token, read BY THE KERNEL from one word in
  * device memory (a captured step replays with what the word holds then),

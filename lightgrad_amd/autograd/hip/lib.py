@@ -156,6 +156,10 @@ PROTOTYPES = {
     "lg_attention_stream_fwd_f32": (c_int, [c_void_p, c_int64, c_int64] * 4 + [c_void_p] + [c_int64] * 4 + [c_float] + [c_void_p, c_int64, c_int]),
     "lg_attention_stream_bwd_f32": (c_int, [c_void_p, c_int64, c_int64] * 5 + [c_void_p, c_void_p] + [c_void_p, c_int64, c_int64] * 3 + [c_int64] * 4
                                     + [c_float] + [c_void_p, c_int64, c_int]),
+    "lg_attention_stream_dropout_fwd_f32": (c_int, [c_void_p, c_int64, c_int64] * 4 + [c_void_p] + [c_int64] * 4 + [c_float]
+                                            + [c_void_p, c_int64, c_int] + [c_double, c_void_p]),
+    "lg_attention_stream_dropout_bwd_f32": (c_int, [c_void_p, c_int64, c_int64] * 5 + [c_void_p, c_void_p] + [c_void_p, c_int64, c_int64] * 3
+                                            + [c_int64] * 4 + [c_float] + [c_void_p, c_int64, c_int] + [c_double, c_void_p]),
     "lg_attention_decode_supported": (c_int, [c_int64, c_int64]),
     "lg_attention_decode_f32": (c_int, [c_void_p, c_int64] * 3 + [c_void_p, c_void_p, c_int64, c_int64] + [c_void_p] + [c_void_p, c_int64]
                                 + [c_void_p] + [c_int64] * 4 + [c_float] + [c_void_p, c_int64]),

@@ -8,7 +8,7 @@ forward launch for the causal entry (one for every form, with or without dropout
 
 `stream_attention` (and `self_attention(probs=False)`) is the form that stores no probabilities: an online softmax at any length
 the predicate accepts, a log-sum-exp per row on the result, its own forward and backward entries (csrc/attention_stream.hip;
-`_launch_stream_fwd` / `_launch_stream_bwd`).
+`_launch_stream_fwd` / `_launch_stream_bwd`); `dropout=p` takes their dropout entries: the composite's mask drawn inside the same launches.
 
 `decode_attention` / `self_attention_decode` are the inference ops of incremental decoding: one new token against a key / value
 cache, over lg_attention_decode_f32 (csrc/decode.hip) or, with `split=True`, the split-key launch for caches of up to 16384 rows
@@ -183,23 +183,33 @@ def _stream_fits(s, d):
     return bool(_l.lib().lg_attention_stream_supported(s, d))
 
 
-def _launch_stream_fwd(q3, k3, v3, out, dims, scale, mask3, causal):
-    """the streaming forward (lg_attention_stream_fwd_f32); operands as for `_launch_attention_fwd`.  Returns the log-sum-exp of
-    every row, (b, heads, s), outside the tape"""
+def _launch_stream_fwd(q3, k3, v3, out, dims, scale, mask3, causal, dropout=0.0):
+    """the streaming forward (lg_attention_stream_fwd_f32; dropout > 0: lg_attention_stream_dropout_fwd_f32); operands as for
+    `_launch_attention_fwd`.  Returns (the log-sum-exp of every row, (b, heads, s), outside the tape; the word the dropout launch
+    wrote the call's number to, None without dropout)"""
     b, heads, s, d = dims
     lse = HipTensor.empty((b, heads, s), requires_grad=False)
-    _l.check(_l.lib().lg_attention_stream_fwd_f32(*q3, *k3, *v3, out.ptr, heads * d, s * heads * d, lse.ptr, b, heads, s, d, scale,
-                                                  mask3[1], mask3[2], int(causal)))
-    return lse
+    args = (*q3, *k3, *v3, out.ptr, heads * d, s * heads * d, lse.ptr, b, heads, s, d, scale, mask3[1], mask3[2], int(causal))
+    if dropout > 0.0:
+        base = _dropout_base()
+        _l.check(_l.lib().lg_attention_stream_dropout_fwd_f32(*args, dropout, base.ptr))
+        return lse, base
+    _l.check(_l.lib().lg_attention_stream_fwd_f32(*args))
+    return lse, None
 
 
-def _launch_stream_bwd(q3, k3, v3, out, g3, lse, dq3, dk3, dv3, dims, scale, mask3, causal):
-    """the two streaming backward launches (lg_attention_stream_bwd_f32): they form the probabilities again from `lse`, so they
-    take the forward's context, mask, scale and causal flag; `delta` is scratch of the call"""
+def _launch_stream_bwd(q3, k3, v3, out, g3, lse, dq3, dk3, dv3, dims, scale, mask3, causal, dropout=0.0, base=None):
+    """the two streaming backward launches (lg_attention_stream_bwd_f32; with the `base` of a dropout forward:
+    lg_attention_stream_dropout_bwd_f32): they form the probabilities again from `lse`, so they take the forward's context, mask,
+    scale and causal flag; `delta` is scratch of the call"""
     b, heads, s, d = dims
     delta = HipTensor.empty((b, heads, s), requires_grad=False)
-    _l.check(_l.lib().lg_attention_stream_bwd_f32(*q3, *k3, *v3, out.ptr, heads * d, s * heads * d, *g3, lse.ptr, delta.ptr, *dq3, *dk3, *dv3,
-                                                  b, heads, s, d, scale, mask3[1], mask3[2], int(causal)))
+    args = (*q3, *k3, *v3, out.ptr, heads * d, s * heads * d, *g3, lse.ptr, delta.ptr, *dq3, *dk3, *dv3, b, heads, s, d, scale,
+            mask3[1], mask3[2], int(causal))
+    if base is not None:
+        _l.check(_l.lib().lg_attention_stream_dropout_bwd_f32(*args, dropout, base.ptr))
+    else:
+        _l.check(_l.lib().lg_attention_stream_bwd_f32(*args))
 
 
 def _untaped(t):
@@ -220,8 +230,12 @@ class stream_attention(Function):
     online softmax over key chunks (csrc/attention_stream.hip), one launch forward, two backward, nothing of size s x s in
     memory.  The result carries `.attention_lse` (b, heads, s): the log-sum-exp of every row of biased scores, outside the tape -
     what the backward forms the probabilities from again; `.attention_probs` is None.  mask: float32 (b, s) or (1, s), no
-    gradient, None for none (the bits of a mask of ones).  causal=True: query i sees keys j <= i, in both directions' launches. """
-    def forward(ctx, q, k, v, heads=1, scale=1.0, mask=None, causal=False):
+    gradient, None for none (the bits of a mask of ones).  causal=True: query i sees keys j <= i, in both directions' launches.
+    dropout=p > 0: `probs.dropout(p)` between the softmax and the context inside the same three launches - the mask the composite
+    draws (one call of the stream, lightgrad_amd/random.py), formed again from the counter wherever a launch needs it;
+    `.attention_lse` is that of the undropped scores.  dropout=0.0: the launches and the bits of the call without it. """
+    def forward(ctx, q, k, v, heads=1, scale=1.0, mask=None, causal=False, dropout=0.0):
+        dropout = _attention_dropout(dropout)
         _require_f32(q, k, v)
         assert q._shape == k._shape == v._shape and stream_attention_supported(q, heads), \
             "stream_attention: unsupported shapes %s / %s / %s with %d heads" % (q._shape, k._shape, v._shape, heads)
@@ -230,18 +244,19 @@ class stream_attention(Function):
         mask3 = _key_mask(mask, b, s, "stream_attention")
         (q, ldq, sbq), (k, ldk, sbk), (v, ldv, sbv) = _token_rows(q), _token_rows(k), _token_rows(v)
         out = HipTensor.empty((b, s, width))
-        lse = _launch_stream_fwd((q.ptr, ldq, sbq), (k.ptr, ldk, sbk), (v.ptr, ldv, sbv), out, dims, float(scale), mask3, bool(causal))
-        ctx.save_for_backward(q, k, v, _untaped(out), lse, dims, float(scale), mask3, bool(causal))
+        lse, base = _launch_stream_fwd((q.ptr, ldq, sbq), (k.ptr, ldk, sbk), (v.ptr, ldv, sbv), out, dims, float(scale), mask3, bool(causal), dropout)
+        ctx.save_for_backward(q, k, v, _untaped(out), lse, dims, float(scale), mask3, bool(causal), dropout, base)
         out.attention_lse, out.attention_probs = lse, None
         return out
 
     def backward(ctx, out_grad):
-        q, k, v, out, lse, dims, scale, mask3, causal = ctx.get_saved_tensors()
+        q, k, v, out, lse, dims, scale, mask3, causal, dropout, base = ctx.get_saved_tensors()
         b, s, width = q._shape
         (q, ldq, sbq), (k, ldk, sbk), (v, ldv, sbv), (g, ldg, sbg) = _token_rows(q), _token_rows(k), _token_rows(v), _token_rows(out_grad)
         dq, dk, dv = HipTensor.empty((b, s, width)), HipTensor.empty((b, s, width)), HipTensor.empty((b, s, width))
         _launch_stream_bwd((q.ptr, ldq, sbq), (k.ptr, ldk, sbk), (v.ptr, ldv, sbv), out, (g.ptr, ldg, sbg), lse,
-                           (dq.ptr, width, s * width), (dk.ptr, width, s * width), (dv.ptr, width, s * width), dims, scale, mask3, causal)
+                           (dq.ptr, width, s * width), (dk.ptr, width, s * width), (dv.ptr, width, s * width), dims, scale, mask3, causal,
+                           dropout, base)
         return dq, dk, dv
 
 
@@ -280,12 +295,15 @@ class self_attention(Function):
     the same - also with causal=True, which only picks the causal forward launch of the attention.
     probs=False: the same node over the streaming launches of `stream_attention` in place of the stored-P ones - any length they
     take, `.attention_probs` None, `.attention_lse` in its place; projections, input gradient and weight gradients as before.
-    Dropout of the probabilities is not part of the streaming kernels: dropout > 0 with probs=False is refused. """
-    def forward(ctx, x, wq, bq, wk, bk, wv, bv, heads=1, scale=1.0, mask=None, dropout=0.0, causal=False, probs=True):
+    dropout > 0 with probs=False takes stream_dropout=True - the node over the dropout launches of `stream_attention(dropout=p)`;
+    without the keyword that call is refused, as it was before those launches existed. """
+    def forward(ctx, x, wq, bq, wk, bk, wv, bv, heads=1, scale=1.0, mask=None, dropout=0.0, causal=False, probs=True, stream_dropout=False):
         dropout = _attention_dropout(dropout)           # > 0: `probs.dropout(p)` inside the attention launches, as for `attention`
         _require_f32(x, wq, bq, wk, bk, wv, bv)
         stream = not probs
-        assert not (stream and dropout > 0.0), "self_attention: dropout > 0 with probs=False (the streaming kernels draw no attention dropout)"
+        assert not (stream_dropout and probs), "self_attention: stream_dropout=True with probs=True (the keyword belongs to the streaming launches: probs=False)"
+        assert not (stream and dropout > 0.0 and not stream_dropout), \
+            "self_attention: dropout > 0 with probs=False (the streaming kernels draw no attention dropout)"
         long = len(x._shape) == 3 and x._shape[1] > 128
         tail = mask is not None or (len(x._shape) == 3 and x._shape[1] % 32 != 0)
         assert self_attention_supported(x, wq, heads, masked=tail, long=long, causal=causal, stream=stream) and wq._shape == wk._shape == wv._shape and bq._shape == bk._shape == bv._shape == (wq._shape[0],), \
@@ -303,10 +321,10 @@ class self_attention(Function):
         ld, sb = 3 * width, s * 3 * width
         mask3 = _key_mask(mask, b, s, "self_attention")
         if stream:
-            lse = _launch_stream_fwd((base, ld, sb), (base + 4 * width, ld, sb), (base + 8 * width, ld, sb), out, (b, heads, s, width // heads),
-                                     float(scale), mask3, bool(causal))
+            lse, drop_base = _launch_stream_fwd((base, ld, sb), (base + 4 * width, ld, sb), (base + 8 * width, ld, sb), out,
+                                                (b, heads, s, width // heads), float(scale), mask3, bool(causal), dropout)
             # where the stored-P forms keep the probabilities: what the streaming backward needs in their place
-            ctx.save_for_backward(x, qkv, (_untaped(out), lse, mask3, bool(causal)), heads, float(scale), form, dropout, None)
+            ctx.save_for_backward(x, qkv, (_untaped(out), lse, mask3, bool(causal)), heads, float(scale), form, dropout, drop_base)
             out.attention_lse, out.attention_probs = lse, None
             out.attention_qkv = qkv
             return out
@@ -332,7 +350,7 @@ class self_attention(Function):
             out, lse, mask3, causal = probs
             _launch_stream_bwd((base, ld, sb), (base + 4 * width, ld, sb), (base + 8 * width, ld, sb), out, (g.ptr, ldg, sbg), lse,
                                (dbase, ld, sb), (dbase + 4 * width, ld, sb), (dbase + 8 * width, ld, sb),
-                               (b, heads, s, width // heads), scale, mask3, causal)
+                               (b, heads, s, width // heads), scale, mask3, causal, dropout, drop_base)
         else:
             _launch_attention_bwd(form, (base, ld, sb), (base + 4 * width, ld, sb), (base + 8 * width, ld, sb), (g.ptr, ldg, sbg), probs,
                                   (dbase, ld, sb), (dbase + 4 * width, ld, sb), (dbase + 8 * width, ld, sb),

@@ -250,6 +250,7 @@ class AbstractTensor(metaclass=_TensorType):
             return op(self, *args, **kwargs)
         dispatch.__name__ = name
         dispatch.__doc__ = op.__doc__
+        dispatch.op = op                # the Function behind the method: a model asks its `forward` which keywords the backend takes
         setattr(cls, name, dispatch)
         return op
 

@@ -114,6 +114,21 @@ __device__ __forceinline__ float rng_keep(float x, uint32_t word, uint32_t thres
     return word >= threshold ? __fmul_rn(x, s) : 0.0f;
 }
 
+// The same decisions as bits, for kernels whose words are due long before the values they meet (the streaming attention draws a
+// tile's words behind its first MFMAs): a register holds the verdicts of 16 elements where the words would take 16.
+// bit k: the stream keeps element i + k (its word >= threshold), k = 0 .. 3
+template <bool ALIGNED>
+__device__ __forceinline__ uint32_t rng_keep_bits4(int64_t i, unsigned long long seed, unsigned long long base, uint32_t threshold) {
+    uint32_t w[4];
+    rng_words4<ALIGNED>(i, seed, base, w);
+    return uint32_t(w[0] >= threshold) | uint32_t(w[1] >= threshold) << 1 | uint32_t(w[2] >= threshold) << 2 | uint32_t(w[3] >= threshold) << 3;
+}
+
+// rng_keep for an element whose word has met the threshold already
+__device__ __forceinline__ float rng_keep_bit(float x, bool kept, float s) {
+    return kept ? __fmul_rn(x, s) : 0.0f;
+}
+
 // What the attention kernels get of a call.  Forward: `state` is Runtime::rng_state (read, ticket, advance) and `base` the word
 // workgroup 0 writes; backward: `state` gives the seed, `base` is what the forward wrote, nothing is drawn.
 struct AttnDrop {
