@@ -179,22 +179,33 @@ def _bf16_refusal(cache):
 
 
 class BertSelfAttention(nn.Module):
-    def __init__(self, hidden_size, num_attention_heads, attention_probs_dropout_prob=0.0, causal=False, attention_probs=True):
+    def __init__(self, hidden_size, num_attention_heads, attention_probs_dropout_prob=0.0, causal=False, attention_probs=True,
+                 num_key_value_heads=None):
         """`causal=True`: query i sees keys j <= i only - the decoder-style mask of a causal language model.  The values are those
         of the composite branch below: one more additive constant, `(1 - tril) * -10000`, behind the key-padding bias.
         `attention_probs=False`: the caller does not want the (b, heads, s, s) probabilities - `forward` returns (context, None), and
         a backend with the streaming node (`self_attention(probs=False)`) never writes them to memory: any length it takes, also
-        beyond 512 positions"""
+        beyond 512 positions.
+        `num_key_value_heads` (default: the number of heads - the model as it was, launch for launch): GROUPED-QUERY attention.
+        `key` and `value` project onto that many heads, query head h reads K/V head h // (heads // num_key_value_heads), and a
+        cache holds rows of num_key_value_heads * d values (`kv_width`).  Full forward: `_grouped_forward`; greedy decode steps:
+        the backend's grouped-query launch (`self_attention_decode(kv_heads=, split=True)`) or the same folding over the tensor
+        API (`_grouped_decode`); the append, serve, beam, speculative and per-row routes refuse such a model by name"""
         nn.Module.__init__(self)
         assert hidden_size % num_attention_heads == 0
+        self.kvh = num_attention_heads if num_key_value_heads is None else int(num_key_value_heads)
+        assert self.kvh >= 1 and num_attention_heads % self.kvh == 0, \
+            "num_key_value_heads = %s does not divide num_attention_heads = %d" % (num_key_value_heads, num_attention_heads)
+        self._packed = {}           # ids of the six projection parameters -> (they, pack_qkv's copy): dropped by every full forward
         self.causal = bool(causal)
         self.attention_probs = bool(attention_probs)
         self._tril = {}             # (backend class, s, dtype) -> the (1, 1, s, s) lower-triangular constant of ones
         self.dropout = nn.Dropout(attention_probs_dropout_prob)
         self.h, self.d = num_attention_heads, hidden_size // num_attention_heads
         self.query = nn.Linear(hidden_size, hidden_size)
-        self.key = nn.Linear(hidden_size, hidden_size)
-        self.value = nn.Linear(hidden_size, hidden_size)
+        self.kv_width = self.kvh * self.d
+        self.key = nn.Linear(hidden_size, self.kv_width)
+        self.value = nn.Linear(hidden_size, self.kv_width)
 
     def _lower_triangle(self, like, s):
         key = (like.__class__, s, np.dtype(like.dtype))
@@ -205,10 +216,82 @@ class BertSelfAttention(nn.Module):
             self._tril[key] = t
         return self._tril[key]
 
+    def _no_grouped(self, route, cache=None):
+        """the routes that do not serve grouped-query attention yet refuse such a model by the name of its config key"""
+        assert self.kvh == self.h or (cache is not None and not getattr(cache, "per_row", False)), \
+            "%s does not take a model with num_key_value_heads = %d below its %d heads yet: grouped-query attention serves training, the " \
+            "prefill and the greedy steps of `generate` against a cache with one position" % (route, self.kvh, self.h)
+
+    def _grouped_forward(self, hidden, attention_mask, cache, index):
+        """the full forward (training, prefill) with num_key_value_heads below the heads, on the tape and without a broadcast op:
+        the R = heads / kv_heads query heads of a group become R * s query ROWS of their K/V head - q as (b, kv_heads, R * s, d)
+        against k (b, kv_heads, d, s) - with the causal bias tiled over R (the padding bias broadcasts over the rows as it is).
+        The cache takes the unexpanded k and v"""
+        b, s, _ = hidden.shape
+        R = self.h // self.kvh
+        q, k, v = self.query(hidden), self.key(hidden), self.value(hidden)
+        if cache is not None:
+            cache.fill(index, k, v)
+        q = q.reshape(b, s, self.h, self.d).transpose(0, 2, 1, 3).reshape(b, self.kvh, R * s, self.d)       # row r * s + i: head g R + r, query i
+        k = k.reshape(b, s, self.kvh, self.d).transpose(0, 2, 3, 1)
+        v = v.reshape(b, s, self.kvh, self.d).transpose(0, 2, 1, 3)
+        scores = (q @ k) / math.sqrt(self.d)
+        if attention_mask is not None:
+            mask = attention_mask.reshape(attention_mask.shape[0], 1, 1, attention_mask.shape[1])
+            scores = scores + ((1.0 - mask) * -10000.0).detach()
+        if self.causal:
+            key = (scores.__class__, s, np.dtype(scores.dtype), R)
+            if key not in self._tril:
+                tri = scores.__class__.from_numpy(np.tile(np.tril(np.ones((1, 1, s, s), dtype=scores.dtype)), (1, 1, R, 1)), requires_grad=False)
+                if hasattr(tri, "freeze"):
+                    tri.freeze()
+                self._tril[key] = tri
+            scores = scores + ((1.0 - self._tril[key]) * -10000.0).detach()
+        probs = scores.softmax(axis=-1)
+        context = (self.dropout(probs) @ v).reshape(b, self.h, s, self.d).transpose(0, 2, 1, 3).reshape(b, s, self.h * self.d)
+        return context, (probs.reshape(b, self.h, s, s) if self.attention_probs else None)
+
+    def _grouped_decode(self, hidden, attention_mask, cache, index):
+        """a decode step with num_key_value_heads below the heads: the backend's grouped-query route (two launches per layer: one
+        product on the row-concatenated projection weights, packed once behind a prefill, and lg_attention_decode_gqa_f32, which
+        reads a K/V head once for the R query heads of its group), or the folding of `_grouped_forward` over the tensor API"""
+        self._no_grouped("a decode step against a cache with a position per sequence", cache)
+        b = hidden.shape[0]
+        R = self.h // self.kvh
+        k_cache, v_cache = cache.k[index], cache.v[index]
+        mask_ok = attention_mask is None or (attention_mask.dtype == np.float32 and not attention_mask.requires_grad and
+                                             tuple(attention_mask.shape) in ((b, cache.capacity), (1, cache.capacity)))
+        if hasattr(hidden, "self_attention_decode") and mask_ok and \
+                hidden.self_attention_decode_supported(self.query.weight, self.h, cache.capacity, split=True, kv_heads=self.kvh):
+            params = (self.query.weight, self.query.bias, self.key.weight, self.key.bias, self.value.weight, self.value.bias)
+            key = tuple(id(t) for t in params)
+            if key not in self._packed:
+                self._packed = {key: (params, hidden.pack_qkv(*params))}
+            extra = {"mask": attention_mask} if attention_mask is not None else {}
+            context = hidden.self_attention_decode(*params, k_cache, v_cache, cache.pos, heads=self.h, scale=math.sqrt(self.d) ** -1, split=True,
+                                                   kv_heads=self.kvh, packed=self._packed[key][1], **extra)
+            return context, None
+        t = cache.length
+        assert t < cache.capacity, "the cache holds %d positions: no room for position %d" % (cache.capacity, t)
+        q, k, v = self.query(hidden), self.key(hidden), self.value(hidden)
+        k_cache[:, t:t + 1] = k
+        v_cache[:, t:t + 1] = v
+        q = q.reshape(b, self.kvh, R, self.d)
+        k = k_cache[:, :t + 1].reshape(b, t + 1, self.kvh, self.d).transpose(0, 2, 3, 1)
+        v = v_cache[:, :t + 1].reshape(b, t + 1, self.kvh, self.d).transpose(0, 2, 1, 3)
+        scores = (q @ k) / math.sqrt(self.d)
+        if attention_mask is not None:
+            mask = attention_mask[:, :t + 1]
+            scores = scores + ((1.0 - mask.reshape(mask.shape[0], 1, 1, t + 1)) * -10000.0).detach()
+        probs = scores.softmax(axis=-1)
+        return (probs @ v).reshape(b, 1, self.h * self.d), probs.reshape(b, self.h, 1, t + 1)
+
     def _decode(self, hidden, attention_mask, cache, index):
         """one new token per sequence against the cached keys and values: position t = the cache's position attends to keys 0 .. t
         - the row the causal forward computes for query t.  attention_mask: None or (b, capacity) over the cache's rows.  A cache
         with a position per sequence (per_row): the fused route passes `cache.pos` (b,) as it is - sequence r at its own t_r"""
+        if self.kvh != self.h:
+            return self._grouped_decode(hidden, attention_mask, cache, index)
         b = hidden.shape[0]
         scale = math.sqrt(self.d) ** -1
         k_cache, v_cache = cache.k[index], cache.v[index]
@@ -417,6 +500,7 @@ class BertSelfAttention(nn.Module):
         it to the launch as it is, the composite reads it.  cu: None, or an int32 tensor (slots + 1,) - the step is token-packed:
         `hidden` is (1, T, hidden), the tokens of all `cache.batch` slots, slot s owning rows cu[s] .. cu[s + 1] - 1
         (`_packed_composite` is the definition; the fused route is one projection launch on the T rows and one attention launch)"""
+        self._no_grouped("_extend (append=True, prefill_chunk=, serve)")
         counted = {} if count is None else {"count": count}
         assert count is None or getattr(cache, "per_row", False), "count= takes a cache with a position per sequence: nn.KVCache(..., per_row=True)"
         if isinstance(cache, nn.PagedKVCache):
@@ -517,6 +601,11 @@ class BertSelfAttention(nn.Module):
         if cache is not None and cache.length > 0:
             assert self.causal and hidden.shape[1] == 1, "a decode step is one token per sequence of a causal model"
             return self._decode(hidden, attention_mask, cache, index)
+        if self.kvh != self.h:
+            self._packed = {}               # training in between changes the parameters in place: the next decode step packs them again
+            if cache is not None:
+                self._no_grouped("a prefill into a cache with a position per sequence", cache)
+            return self._grouped_forward(hidden, attention_mask, cache, index)
         b, s, _ = hidden.shape
         # a padded batch (a mask) or a length the plain kernels do not take (no multiple of 32) goes to the backend's masked forms,
         # if it has them and the mask is what they read: a (b, s) or (1, s) float32 constant
@@ -598,9 +687,10 @@ class BertSelfAttention(nn.Module):
 
 class BertAttention(nn.Module):
     def __init__(self, hidden_size, num_attention_heads, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0, causal=False,
-                 attention_probs=True):
+                 attention_probs=True, num_key_value_heads=None):
         nn.Module.__init__(self)
-        self.self = BertSelfAttention(hidden_size, num_attention_heads, attention_probs_dropout_prob, causal=causal, attention_probs=attention_probs)
+        self.self = BertSelfAttention(hidden_size, num_attention_heads, attention_probs_dropout_prob, causal=causal, attention_probs=attention_probs,
+                                      num_key_value_heads=num_key_value_heads)
         self.dropout = nn.Dropout(hidden_dropout_prob)
         self.output = nn.Module()
         self.output.dense = nn.Linear(hidden_size, hidden_size)
@@ -628,10 +718,10 @@ class BertAttention(nn.Module):
 
 class BertLayer(nn.Module):
     def __init__(self, hidden_size, intermediate_size, num_attention_heads, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0,
-                 causal=False, attention_probs=True):
+                 causal=False, attention_probs=True, num_key_value_heads=None):
         nn.Module.__init__(self)
         self.attention = BertAttention(hidden_size, num_attention_heads, hidden_dropout_prob, attention_probs_dropout_prob, causal=causal,
-                                       attention_probs=attention_probs)
+                                       attention_probs=attention_probs, num_key_value_heads=num_key_value_heads)
         self.dropout = nn.Dropout(hidden_dropout_prob)
         self.intermediate = nn.Module()
         self.intermediate.dense = nn.Linear(hidden_size, intermediate_size)
@@ -666,7 +756,7 @@ class BertLayer(nn.Module):
 class BertModel(nn.Module):
     def __init__(self, hidden_size, intermediate_size, num_hidden_layers, num_attention_heads, vocab_size,
                  max_position_embeddings, type_vocab_size, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0, causal=False,
-                 attention_probs=True, **unused):
+                 attention_probs=True, num_key_value_heads=None, **unused):
         """`causal=True`: every layer's attention is causal - with the next-token objective (`clm_forward_backward`) a decoder-style
         language model of the same parameters.  `attention_probs=False`: no layer hands back its attention probabilities
         (BertSelfAttention) - on a backend with the streaming node they are never stored, and sequences beyond 512 positions stay
@@ -675,7 +765,8 @@ class BertModel(nn.Module):
         self.embeddings = BertEmbedding(hidden_size, vocab_size, max_position_embeddings, type_vocab_size, hidden_dropout_prob)
         self.encoder = nn.Module()
         self.encoder.layer = nn.ModuleList(*[BertLayer(hidden_size, intermediate_size, num_attention_heads, hidden_dropout_prob,
-                                                       attention_probs_dropout_prob, causal=causal, attention_probs=attention_probs)
+                                                       attention_probs_dropout_prob, causal=causal, attention_probs=attention_probs,
+                                                       num_key_value_heads=num_key_value_heads)
                                              for _ in range(num_hidden_layers)])
 
     def forward(self, input_ids, attention_mask=None, token_type_ids=None, cache=None, append=False, count=None, token_positions=None, cu=None):
@@ -1341,6 +1432,7 @@ def generate(model, ids, max_new_tokens, attention_mask=None, cache=None, graph=
     assert not isinstance(cache, nn.PagedKVCache), "generate: an nn.PagedKVCache serves the count= append path only (serve): pass an nn.KVCache" + \
         _bf16_refusal(cache)
     if num_beams is not None:
+        model.bert.encoder.layer[0].attention.self._no_grouped("generate(num_beams=)")
         assert int(num_beams) == num_beams and 1 <= num_beams <= 8, "num_beams is an int within 1 .. 8 (got %s)" % (num_beams,)
         assert temperature is None, "beam search is deterministic: temperature= (sampling beams) is not supported with num_beams="
         assert speculate is None, "speculate= drafts for one sequence per row: it is not supported with num_beams="
@@ -1353,6 +1445,7 @@ def generate(model, ids, max_new_tokens, attention_mask=None, cache=None, graph=
         return generate_beams(model, ids, max_new_tokens, lengths, eos_token_id, pad_token_id, cache, graph, prefill_chunk, int(num_beams),
                               float(length_penalty), int(poll), beams)
     if lengths is not None or eos_token_id is not None or speculate is not None:
+        model.bert.encoder.layer[0].attention.self._no_grouped("generate(speculate=)" if speculate is not None else "generate(lengths= / eos_token_id=)")
         assert max_new_tokens >= 1 and ids.shape[1] >= 1 and (prefill_chunk is None or prefill_chunk >= 1)
         assert model.bert.encoder.layer[0].attention.self.causal, "generate needs a model built with causal=True"
         assert not append or cache is not None, "append=True continues a cache: pass the one that holds the tokens so far"
@@ -1371,7 +1464,9 @@ def generate(model, ids, max_new_tokens, attention_mask=None, cache=None, graph=
     assert prefill_chunk is None or prefill_chunk >= 1, "prefill_chunk is a number of tokens >= 1"
     assert not append or cache is not None, "append=True continues a cache: pass the one that holds the tokens so far"
     if cache is None:
-        cache = nn.KVCache(len(model.bert.encoder.layer), b, s0 + max_new_tokens, layer0.h * layer0.d, like=model.bert.embeddings.word_embeddings.weight)
+        cache = nn.KVCache(len(model.bert.encoder.layer), b, s0 + max_new_tokens, layer0.kv_width, like=model.bert.embeddings.word_embeddings.weight)
+    if append or prefill_chunk is not None:
+        layer0._no_grouped("generate(append=True / prefill_chunk=)")
     start = cache.length if append else 0               # tokens in front of `ids`
     if append:
         assert start + s0 + max_new_tokens <= cache.capacity <= positions, \
@@ -1566,6 +1661,7 @@ def serve(model, prompts, max_new_tokens, slots=8, chunk=32, eos_token_id=None, 
     assert budgets.shape == (n,) and (budgets >= 1).all(), "serve: max_new_tokens is an int >= 1 or one per request"
     assert int(poll) == poll and poll >= 1 and slots >= 1 and chunk >= 1
     positions = model.bert.embeddings.position_embeddings.weight.shape[0]
+    model.bert.encoder.layer[0].attention.self._no_grouped("serve")
     paged, prefix_blocks = num_blocks is not None or isinstance(cache, nn.PagedKVCache), 0
     if paged:
         assert token_budget is None, "serve: token_budget= (token-packed steps) together with a paged cache (num_blocks= / nn.PagedKVCache) is not supported" + (
@@ -1772,6 +1868,9 @@ if __name__ == "__main__":
         long_config = {"max_position_embeddings": int(sys.argv[sys.argv.index("--positions") + 1])} if "--positions" in sys.argv else {}
         if "--no-attention-probs" in sys.argv:
             long_config["attention_probs"] = False
+        if "--kv-heads" in sys.argv:
+            # grouped-query attention: N K/V heads under TINY's heads - the decode steps take csrc/decode_gqa.hip
+            long_config["num_key_value_heads"] = int(sys.argv[sys.argv.index("--kv-heads") + 1])
         lm = BertForMaskedLM(**dict(TINY, causal=True, **long_config)).eval()
         prompt = light.from_numpy(np.random.randint(0, TINY["vocab_size"], (batch, prompt_length)).astype(np.int32), requires_grad=False)
         if not cpu:

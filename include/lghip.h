@@ -725,6 +725,28 @@ int lg_attention_decode_split_rows_f32(const float* q, int64_t sbq, const float*
                                        float* o, int64_t sbo, float* lse, int64_t batch, int64_t heads, int64_t capacity, int64_t D,
                                        float scale, const float* mask, int64_t sbm);
 
+/* ---- grouped-query attention of ONE new token: R = heads / kv_heads query heads share a cached K/V head (csrc/decode_gqa.hip) ---
+ * The operands and rules of lg_attention_decode_split_f32 plus `kv_heads`: q and o are (batch, heads * D), k_new / v_new (batch,
+ * kv_heads * D), the caches (batch, capacity, kv_heads * D) with ldc >= kv_heads * D, lse NULL or (batch, heads), the mask
+ * shared by all heads.  Query head h reads K/V head h / R.  The grid is (ceil(capacity / 256), kv_heads, batch): a workgroup
+ * loads its slice of a K/V head once and serves the R heads of the group from those registers, so the launch reads 1 / R of the
+ * bytes the split launch reads on caches whose heads were repeated R times - and returns the same bits, o and lse, per (batch,
+ * head); at kv_heads == heads it is that launch.  One ticket per (batch, K/V head) pair, a workspace slot per (batch, head, slice).
+ * Supported: D = 32 or 64, 1 <= capacity <= 16384, heads % kv_heads == 0, R = 1, 2, 4 or 8
+ * (lg_attention_decode_gqa_supported, pure host code).  Checked first, LG_EINVAL: heads / kv_heads; then the split entry's order
+ * with kv_heads * D as the caches' width and batch * kv_heads against the ticket pool. */
+int lg_attention_decode_gqa_supported(int64_t capacity, int64_t D, int64_t heads, int64_t kv_heads);
+int lg_attention_decode_gqa_f32(const float* q, int64_t sbq, const float* k_new, int64_t sbk, const float* v_new, int64_t sbv,
+                                float* k_cache, float* v_cache, int64_t ldc, int64_t sbc, const int32_t* pos, float* o, int64_t sbo,
+                                float* lse,                          /* NULL, or log-sum-exp (batch, heads), dense */
+                                int64_t batch, int64_t heads, int64_t kv_heads, int64_t capacity, int64_t D, float scale,
+                                const float* mask, int64_t sbm);
+int lg_attention_decode_gqa_rows_f32(const float* q, int64_t sbq, const float* k_new, int64_t sbk, const float* v_new, int64_t sbv,
+                                     float* k_cache, float* v_cache, int64_t ldc, int64_t sbc,
+                                     const int32_t* pos,             /* `batch` words in device memory: the position of each new token */
+                                     float* o, int64_t sbo, float* lse, int64_t batch, int64_t heads, int64_t kv_heads, int64_t capacity,
+                                     int64_t D, float scale, const float* mask, int64_t sbm);
+
 /* ---- attention of m NEW tokens against a filled key / value cache (csrc/extend.hip) --------------------------
  * Appending to a cache that already holds t = *pos tokens (a second prompt, a prompt prefilled in pieces, a continuation to
  * score, drafted tokens to verify): t is read BY THE KERNEL from one word in device memory, m is a host argument, and

@@ -171,6 +171,11 @@ PROTOTYPES = {
                                       + [c_void_p] + [c_int64] * 4 + [c_float] + [c_void_p, c_int64]),
     "lg_attention_decode_split_rows_f32": (c_int, [c_void_p, c_int64] * 3 + [c_void_p, c_void_p, c_int64, c_int64] + [c_void_p] + [c_void_p, c_int64]
                                            + [c_void_p] + [c_int64] * 4 + [c_float] + [c_void_p, c_int64]),
+    "lg_attention_decode_gqa_supported": (c_int, [c_int64] * 4),
+    "lg_attention_decode_gqa_f32": (c_int, [c_void_p, c_int64] * 3 + [c_void_p, c_void_p, c_int64, c_int64] + [c_void_p] + [c_void_p, c_int64]
+                                    + [c_void_p] + [c_int64] * 5 + [c_float] + [c_void_p, c_int64]),
+    "lg_attention_decode_gqa_rows_f32": (c_int, [c_void_p, c_int64] * 3 + [c_void_p, c_void_p, c_int64, c_int64] + [c_void_p] + [c_void_p, c_int64]
+                                         + [c_void_p] + [c_int64] * 5 + [c_float] + [c_void_p, c_int64]),
     "lg_attention_extend_supported": (c_int, [c_int64, c_int64, c_int64]),
     "lg_attention_extend_f32": (c_int, [c_void_p, c_int64, c_int64] * 3 + [c_void_p, c_void_p, c_int64, c_int64] + [c_void_p]
                                 + [c_void_p, c_int64, c_int64] + [c_void_p] + [c_int64] * 5 + [c_float] + [c_void_p, c_int64]),

@@ -474,10 +474,18 @@ def _cache_launch(name, mask, rows, capacity, k_cache, v_cache, extra_shape):
     return mask3, extra
 
 
-def _launch_decode(name, q2, k2, v2, k_cache, v_cache, pos, out, heads, scale, mask, probs, split=False, lse=False):
+def _launch_decode(name, q2, k2, v2, k_cache, v_cache, pos, out, heads, scale, mask, probs, split=False, lse=False, kv_heads=None):
     """q2, k2, v2: (address, batch pitch); out: (b, ..., width) dense.  Returns the probabilities (b, heads, 1, capacity) or None;
-    split=True (csrc/decode_split.hip): the log-sum-exp (b, heads) or None in their place"""
+    split=True (csrc/decode_split.hip): the log-sum-exp (b, heads) or None in their place.  kv_heads (below heads, with split):
+    the grouped-query launch (csrc/decode_gqa.hip) - the caches are kv_heads * d wide, out heads * d"""
     b, capacity, width = k_cache._shape
+    if kv_heads is not None:
+        mask3, extra = _cache_launch(name, mask, b, capacity, k_cache, v_cache, (b, heads) if lse else None)
+        pos, per_row = _positions(pos, b)
+        entry = getattr(_l.lib(), "lg_attention_decode_gqa%s_f32" % ("_rows" if per_row else ""))
+        _l.check(entry(*q2, *k2, *v2, k_cache.ptr, v_cache.ptr, k_cache._strides[1], k_cache._strides[0], pos.ptr, out.ptr, out._shape[-1],
+                       extra.ptr if extra is not None else None, b, heads, kv_heads, capacity, width // kv_heads, float(scale), mask3[1], mask3[2]))
+        return extra
     if split:
         shape = (b, heads) if lse else None
     else:
@@ -500,16 +508,33 @@ def _split_options(name, probs, split, lse):
     assert split or not lse, "%s: lse=True needs split=True (the 512-row launch returns probabilities, probs=True)" % name
 
 
-def decode_attention_supported(q, heads, capacity, split=False):
+def _grouped(name, heads, kv_heads, split, probs=False):
+    """the K/V heads of a grouped-query call, or None where the call is what it was without `kv_heads` (None, or equal to heads)"""
+    if kv_heads is None or kv_heads == heads:
+        return None
+    assert split, "%s: kv_heads = %d below heads = %d takes the grouped-query launch, which needs split=True" % (name, kv_heads, heads)
+    assert not probs, "%s: probs=True with kv_heads= (the grouped-query launch returns a log-sum-exp, lse=True, never probabilities)" % name
+    return int(kv_heads)
+
+
+def _gqa_fits(capacity, d, heads, kv_heads):
+    return bool(_l.lib().lg_attention_decode_gqa_supported(capacity, d, heads, kv_heads))
+
+
+def decode_attention_supported(q, heads, capacity, split=False, kv_heads=None):
     """does `q.decode_attention(k_new, v_new, k_cache, v_cache, pos, heads, scale)` exist for this shape?  (b, 1, heads * d) or
     (b, heads * d) float32 with d = 32 or 64, b >= 1 and a cache of 1 .. 512 rows.  split=True: the question of
-    `decode_attention(..., split=True)` - a cache of 1 .. 16384 rows"""
+    `decode_attention(..., split=True)` - a cache of 1 .. 16384 rows.  kv_heads below heads: the question of the grouped-query
+    launch - split=True, heads a multiple of kv_heads by 2, 4 or 8"""
     sh = q._shape
+    if kv_heads is not None and kv_heads != heads:
+        return (split and len(sh) in (2, 3) and (len(sh) == 2 or sh[1] == 1) and q._dtype == _F32 and sh[0] > 0 and sh[-1] % heads == 0
+                and _gqa_fits(capacity, sh[-1] // heads, heads, kv_heads))
     return (len(sh) in (2, 3) and (len(sh) == 2 or sh[1] == 1) and q._dtype == _F32 and sh[0] > 0 and sh[-1] % heads == 0
             and _decode_fits(capacity, sh[-1] // heads, split))
 
 
-def decode_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False, split=False, lse=False):
+def decode_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False, split=False, lse=False, kv_heads=None):
     """ attention of ONE new token per sequence against a key / value cache, one launch (lg_attention_decode_f32): with t = the
     int32 word `pos` holds ON THE DEVICE (`pos` of shape (b,): a position per sequence, t = pos[r] for sequence r, everything
     below per sequence - lg_attention_decode_rows_f32; a sequence whose position is outside the cache writes nothing, the others
@@ -521,11 +546,31 @@ def decode_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0,
     synchronisation.  An inference op: the result is outside the tape.
     split=True: the split-key launch (lg_attention_decode_split_f32 / _rows_f32, csrc/decode_split.hip) - caches of 1 .. 16384
     rows, the keys of a sequence spread over workgroups of 256 keys and merged inside the launch.  It returns no probabilities
-    (probs=True is refused); lse=True: `.attention_lse` (b, heads), the log of the sum of the exponentials of the scores 0 .. t. """
+    (probs=True is refused); lse=True: `.attention_lse` (b, heads), the log of the sum of the exponentials of the scores 0 .. t.
+    kv_heads (None or equal to heads: every call is what it is without it): GROUPED-QUERY attention, query head h reads K/V head
+    h // (heads // kv_heads) - k_new / v_new are (b, 1, kv_heads * d) or (b, kv_heads * d), the caches (b, capacity, kv_heads * d),
+    and the call takes lg_attention_decode_gqa_f32 / _rows_f32 (csrc/decode_gqa.hip): a workgroup loads its 256 rows of a K/V head
+    once for the 2, 4 or 8 query heads of its group.  It needs split=True and returns the bits of the split launch on caches
+    whose heads were repeated. """
     name = "decode_attention"
     _split_options(name, probs, split, lse)
     _inference_only(name, q, k_new, v_new)
     _require_f32(q, k_new, v_new)
+    kv_heads = _grouped(name, heads, kv_heads, split, probs)
+    if kv_heads is not None:
+        capacity = k_cache._shape[1] if len(k_cache._shape) == 3 else 0
+        assert k_new._shape == v_new._shape and len(k_new._shape) == len(q._shape) and k_new._shape[:-1] == q._shape[:-1] and \
+            decode_attention_supported(q, heads, capacity, split=True, kv_heads=kv_heads) and k_new._shape[-1] == q._shape[-1] // heads * kv_heads, \
+            "%s: unsupported shapes %s / %s / %s with %d heads over %d K/V heads and caches %s" % (name, q._shape, k_new._shape, v_new._shape, heads,
+                                                                                                  kv_heads, k_cache._shape)
+        _check_cache(name, k_cache, v_cache, pos, q._shape[0], k_new._shape[-1])
+        (q, sbq), (k_new, sbk), (v_new, sbv) = _token_row(q, name), _token_row(k_new, name), _token_row(v_new, name)
+        out = HipTensor.empty(q._shape, requires_grad=False)
+        p = _launch_decode(name, (q.ptr, sbq), (k_new.ptr, sbk), (v_new.ptr, sbv), k_cache, v_cache, pos, out, heads, scale, mask, False, True, lse,
+                           kv_heads=kv_heads)
+        if lse:
+            out.attention_lse = p
+        return out
     assert q._shape == k_new._shape == v_new._shape and decode_attention_supported(q, heads, k_cache._shape[1] if len(k_cache._shape) == 3 else 0, split=split), \
         "%s: unsupported shapes %s / %s / %s with %d heads and caches %s" % (name, q._shape, k_new._shape, v_new._shape, heads, k_cache._shape)
     _check_cache(name, k_cache, v_cache, pos, q._shape[0], q._shape[-1])
@@ -539,15 +584,66 @@ def decode_attention(q, k_new, v_new, k_cache, v_cache, pos, heads=1, scale=1.0,
     return out
 
 
+def pack_qkv(wq, bq, wk, bk, wv, bv):
+    """(weights, biases) of the three projections row-concatenated: ((heads + 2 kv_heads) * d, hidden) and its bias row - what
+    `self_attention_decode(kv_heads=, packed=)` multiplies by in one plain product.  A copy: whoever keeps it drops it when the
+    parameters change"""
+    _require_f32(wq, bq, wk, bk, wv, bv)
+    rows = [w._shape[0] for w in (wq, wk, wv)]
+    w = HipTensor.empty((sum(rows), wq._shape[1]), requires_grad=False)
+    bias = HipTensor.empty((sum(rows),), requires_grad=False)
+    at = 0
+    for n, wi, bi in zip(rows, (wq, wk, wv), (bq, bk, bv)):
+        w[at:at + n] = wi.detach()
+        bias[at:at + n] = bi.detach()
+        at += n
+    return w, bias
+
+
+def _grouped_self_attention_decode(name, x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, heads, kv_heads, scale, mask, lse, packed):
+    """lg_gemm_multi3_f32 writes three products of ONE width; q is heads * d wide, k and v kv_heads * d.  So the projection is one
+    plain product with the row-concatenated weights (`pack_qkv`; packed=: the caller's cached copy) into the (b, 1, (heads +
+    2 kv_heads) * d) buffer that the grouped-query launch reads in place: two launches with packed=, as without kv_heads"""
+    capacity = k_cache._shape[1] if len(k_cache._shape) == 3 else 0
+    width = wq._shape[0]
+    kvw = width // heads * kv_heads if heads and width % heads == 0 else -1
+    assert self_attention_decode_supported(x, wq, heads, capacity, split=True, kv_heads=kv_heads) and wk._shape == wv._shape == (kvw, wq._shape[1]) \
+        and bq._shape == (width,) and bk._shape == bv._shape == (kvw,), \
+        "%s: unsupported shapes %s with weights %s / %s / %s, %d heads over %d K/V heads and caches %s" % (
+            name, x._shape, wq._shape, wk._shape, wv._shape, heads, kv_heads, k_cache._shape)
+    b, _, hidden = x._shape
+    total = width + 2 * kvw
+    _check_cache(name, k_cache, v_cache, pos, b, kvw)
+    w, bias = pack_qkv(wq, bq, wk, bk, wv, bv) if packed is None else packed
+    assert w._shape == (total, hidden) and bias._shape == (total,) and w._dtype == _F32 and bias._dtype == _F32, \
+        "%s: packed= is pack_qkv's (weights (%d, %d), biases (%d,)), got %s / %s" % (name, total, hidden, total, w._shape, bias._shape)
+    x, w, bias = x.contiguous(), w.contiguous(), bias.contiguous()
+    qkv = HipTensor.empty((b, 1, total), requires_grad=False)
+    _l.check(_l.lib().lg_gemm_bias_f32(0, 1, b, total, hidden, x.ptr, hidden, 0, w.ptr, hidden, 0, qkv.ptr, total, 0, 1, bias.ptr))
+    out = HipTensor.empty((b, 1, width), requires_grad=False)
+    base = qkv.ptr
+    p = _launch_decode(name, (base, total), (base + 4 * width, total), (base + 4 * (width + kvw), total), k_cache, v_cache, pos, out, heads, scale,
+                       mask, False, True, lse, kv_heads=kv_heads)
+    if lse:
+        out.attention_lse = p
+    return out
+
+
 def self_attention_decode(x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, heads=1, scale=1.0, mask=None, probs=False, split=False,
-                          lse=False):
+                          lse=False, kv_heads=None, packed=None):
     """ the one-node form of a decode step's attention: the three projections of the new token in ONE launch (lg_gemm_multi3_f32,
     as in `self_attention`) into a (b, 1, 3 * width) buffer that the decode launch reads in place - two launches per layer.
-    x: (b, 1, hidden); everything else, `split` and `lse` included, as for `decode_attention`. """
+    x: (b, 1, hidden); everything else, `split` and `lse` included, as for `decode_attention`.
+    kv_heads below heads (with split=True): wk / wv are (kv_heads * d, hidden), bk / bv match them, and the route is
+    `_grouped_self_attention_decode` - one plain product on `pack_qkv`'s weights (packed=: a copy the caller keeps; without it
+    they are packed on every call) and the grouped-query launch. """
     name = "self_attention_decode"
     _split_options(name, probs, split, lse)
     _inference_only(name, x, wq, bq, wk, bk, wv, bv)
     _require_f32(x, wq, bq, wk, bk, wv, bv)
+    kv_heads = _grouped(name, heads, kv_heads, split, probs)
+    if kv_heads is not None:
+        return _grouped_self_attention_decode(name, x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, heads, kv_heads, scale, mask, lse, packed)
     assert self_attention_decode_supported(x, wq, heads, k_cache._shape[1] if len(k_cache._shape) == 3 else 0, split=split) and \
         wq._shape == wk._shape == wv._shape and bq._shape == bk._shape == bv._shape == (wq._shape[0],), \
         "%s: unsupported shapes %s with weights %s / %s / %s, %d heads and caches %s" % (name, x._shape, wq._shape, wk._shape, wv._shape, heads, k_cache._shape)
@@ -571,10 +667,14 @@ def self_attention_decode(x, wq, bq, wk, bk, wv, bv, k_cache, v_cache, pos, head
     return out
 
 
-def self_attention_decode_supported(x, wq, heads, capacity, split=False):
+def self_attention_decode_supported(x, wq, heads, capacity, split=False, kv_heads=None):
     """does `x.self_attention_decode(...)` exist for these shapes?  (b, 1, hidden) input, (width, hidden) weights with width =
     heads * d, d = 32 or 64, width a multiple of 64, a cache of 1 .. 512 rows (split=True: of 1 .. 16384 rows, the question of
-    `self_attention_decode(..., split=True)`)"""
+    `self_attention_decode(..., split=True)`).  kv_heads below heads: the question of the grouped-query route - split=True"""
+    if kv_heads is not None and kv_heads != heads:
+        return (split and len(x._shape) == 3 and x._shape[1] == 1 and x._dtype == _F32 and len(wq._shape) == 2 and wq._shape[1] == x._shape[2]
+                and heads >= 1 and wq._shape[0] % heads == 0 and x._shape[2] % 4 == 0 and x._shape[0] > 0
+                and _gqa_fits(capacity, wq._shape[0] // heads, heads, kv_heads))
     return (len(x._shape) == 3 and x._shape[1] == 1 and x._dtype == _F32 and len(wq._shape) == 2 and wq._shape[1] == x._shape[2]
             and wq._shape[0] % heads == 0 and wq._shape[0] % 64 == 0 and x._shape[2] % 4 == 0 and x._shape[0] > 0
             and _decode_fits(capacity, wq._shape[0] // heads, split))
@@ -582,6 +682,7 @@ def self_attention_decode_supported(x, wq, heads, capacity, split=False):
 
 HipTensor.decode_attention, HipTensor.decode_attention_supported = decode_attention, decode_attention_supported
 HipTensor.self_attention_decode, HipTensor.self_attention_decode_supported = self_attention_decode, self_attention_decode_supported
+HipTensor.pack_qkv = staticmethod(pack_qkv)
 
 
 """ Appending several tokens to a filled key / value cache in one attention launch (csrc/extend.hip; split=True: caches of up to
